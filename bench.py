@@ -16,10 +16,18 @@ models/Tor.obj, 1920x1080, 256 spp, -MRR 8, adaptive sampling off (-ERR -1, so a
 `--spp 64` is BASELINE configs[1], `--spp 1024` configs[2]).  For N > 1 the image grows with N
 (path-tracing_amd/bands.py: frame_for) so that every GPU keeps a 1080p-sized share: weak scaling, `value`.  Rank k of N renders
 every N-th tile row of 8 image rows (an interleaved split, pt_render_params::row_stride: contiguous bands cost unequal amounts,
-bands.py).  Next to it every run also times BASELINE configs[3] as written -- 3840x2160 x 256 spp split over the N ranks, one
+bands.py).  With --full a run also times BASELINE configs[3] as written -- 3840x2160 x 256 spp split over the N ranks, one
 gather -- and reports it as `configs3_strong` (strong scaling: the frame is fixed, 2160/N rows per GPU).
 
-Rank 0 prints ONE JSON line.  Besides the contract's fields it carries
+A plain run (no --full) does only what the headline needs: set up, warm up, time the --steps frames, and print the line with
+`value`, `ms_per_step` and the frame's `config`, plus `roofline` without hardware counters (the HIP-event kernel time of the timed
+launches).  --dump-outputs DIR then writes what the last timed frame computed -- the accumulators a caller of pt_render_device
+receives -- as DIR/radiance_sum.npy, DIR/radiance_sum2.npy (float32, H x W x 3) and DIR/sample_count.npy (float32, H x W); a
+frame above 64 MB is cut to a fixed, seeded sample of pixels (DIR/pixel_index.npy holds their row-major indices).  The inputs
+are fixed (models/Tor.obj, seed 42, counter RNG), so two builds can be compared output for output.
+
+--full adds everything else below (and --pmc / --cpu-seconds / --no-configs3 / --no-extra-legs / --save-pmc select within it).
+Rank 0 prints ONE JSON line.  Besides the contract's fields a --full run carries
   roofline      the integrator kernel against the roofline that bounds it, vector-ALU issue (the path is
                 neither HBM- nor MFMA-bound): achieved = VALU lane-operations the kernel EXECUTES per second
                 (SQ_INSTS_VALU x 64, counted by rocprofv3 --pmc child runs of the C++ front end on the same frame) over
@@ -41,6 +49,7 @@ Rank 0 prints ONE JSON line.  Besides the contract's fields it carries
                 instantiation with path regeneration; rate, live rays per wave-segment, segments per sample, bit identity with
                 the oracle on a band
   multi_gpu_diagnosis   (N > 1) every rank's own kernel time and one gather timed alone after all kernels are done
+  pcie_inclusive / end_to_end   (N = 1) the same frame through pt_render_host, and pt_render as a child process start to exit
 """
 import argparse
 import datetime
@@ -382,18 +391,45 @@ def cxx_frame_leg(n_bands, W, H, spp, steps, warmup, rehearse, error=-1.0, model
     return j
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20240917
+
+
+def dump_outputs(out_dir, s, s2, c, W, H):
+    """Writes the frame's accumulators (full-frame, row-major: sum / sum2 [W*H, 3], count [W*H]) as float32 .npy files.  Above
+    DUMP_MAX_BYTES only a fixed, seeded sample of pixels is written, in ascending index order, with the indices beside it."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    npx = W * H
+    arrays = {"radiance_sum": np.asarray(s, np.float32).reshape(H, W, 3), "radiance_sum2": np.asarray(s2, np.float32).reshape(H, W, 3),
+              "sample_count": np.asarray(c).astype(np.float32).reshape(H, W)}     # counts <= spp: exact in float32
+    if npx * 7 * 4 > DUMP_MAX_BYTES:
+        k = DUMP_MAX_BYTES // (7 * 4 + 8)      # + the float64 index of every sampled pixel
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(npx, size=k, replace=False))
+        arrays = {"radiance_sum": arrays["radiance_sum"].reshape(npx, 3)[idx], "radiance_sum2": arrays["radiance_sum2"].reshape(npx, 3)[idx],
+                  "sample_count": arrays["sample_count"].reshape(npx)[idx], "pixel_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--spp", type=int, default=SPP, help="samples per pixel of the frame (BASELINE configs: 64 / 256 / 1024)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget; 0 skips it")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement and check (counters, CPU baseline and accuracy, the other configurations, "
+                         "the C++ front end, PCIe-inclusive and end-to-end rates, the multi-GPU diagnosis); a plain run times the frame only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed frame's accumulators as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget (--full); 0 skips it")
     ap.add_argument("--pmc", choices=["live", "file", "off"], default="live",
-                    help="hardware counters of the timed kernels: collected now with rocprofv3 in child processes (N = 1), read "
+                    help="hardware counters of the timed kernels (--full): collected now with rocprofv3 in child processes (N = 1), read "
                          "from a committed summary of the same kernel source, or omitted")
-    ap.add_argument("--no-configs3", action="store_true", help="skip the 3840x2160 x 256 spp strong-scaling leg")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip configs1_64spp / adaptive_default / configs4_replica / cxx_frame")
+    ap.add_argument("--no-configs3", action="store_true", help="skip the 3840x2160 x 256 spp strong-scaling leg of --full")
+    ap.add_argument("--no-extra-legs", action="store_true", help="skip configs1_64spp / adaptive_default / configs4_replica / cxx_frame of --full")
     ap.add_argument("--save-pmc", default="", help="write the live counters as a summary `--pmc file` can read later (profiles/rNN_pmc_hbm.json)")
     ap.add_argument("--write-bmp", default="", help="resolve rank 0's gathered frame and write it here")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
@@ -408,7 +444,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
-    extra = world == 1 and not args.no_extra_legs
+    extra = args.full and world == 1 and not args.no_extra_legs
 
     # the replicated scenes of BASELINE configs[4] (generated: 64 and 195 torus instances in the room)
     replica_dir, replicas = None, []
@@ -425,7 +461,7 @@ def main():
 
     pmc, pmc_source, pmc_big, pmc_big_source = None, "not collected", None, "not collected"
     pmc_c2, pmc_c2_source, pmc_sky, pmc_sky_source = None, "not collected", None, "not collected"
-    if world == 1 and args.pmc == "live":      # child processes; this process has not touched the GPU yet
+    if args.full and world == 1 and args.pmc == "live":      # child processes; this process has not touched the GPU yet
         deadline = time.perf_counter() + 150
         pmc, pmc_source = pmc_live(PMC_PASSES_TOR, MODELS, "Tor.obj", args.spp, False, deadline)
         if extra:
@@ -529,6 +565,7 @@ def main():
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=rdev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
+        if world > 1 and args.full:
             # diagnosis (untimed): every rank's mean kernel time, and ONE gather alone -- all kernels are done, nothing overlaps it
             mine = torch.tensor([sum(kernel_ms) / max(len(kernel_ms), 1)], dtype=torch.float64, device=rdev)
             every = [torch.zeros_like(mine) for _ in range(world)]
@@ -555,7 +592,7 @@ def main():
     W, H = bands.frame_for(world)
     elapsed, kernel_ms, frame_stats, frame, rows = run_frames(scene, W, H, args.spp, args.steps, args.warmup)
     c3 = None
-    if not args.no_configs3:
+    if args.full and not args.no_configs3:
         c3_steps = max(1, min(args.steps, 5))
         c3_elapsed, c3_kms, c3_stats, _, c3_rows = run_frames(scene, C3_W, C3_H, C3_SPP, c3_steps, 1)
         c3 = {"workload": f"BASELINE configs[3]: Tor.obj {C3_W}x{C3_H} x {C3_SPP} spp, -MRR {MRR}, -ERR -1, {world} band(s) of "
@@ -661,7 +698,7 @@ def main():
 
     # the C++ host alone on the same frame(s): N = 1 must agree with `value`; for N > 1 it is the direct-RCCL frame path
     cxx = None
-    if not args.no_extra_legs:
+    if args.full and not args.no_extra_legs:
         if world > 1:
             store = dist.distributed_c10d._get_default_store()
             dist.barrier()
@@ -684,7 +721,9 @@ def main():
         kms = sum(kernel_ms) / max(len(kernel_ms), 1)
         # W*H*28 B of accumulators in and out per render call + the scene once
         algo_bytes = npx * 28 * 2 + n_tri * 56
-        if pmc is None and world == 1 and args.pmc != "off":
+        if not args.full:
+            pmc_source = "not collected (bench.py --full collects them)"
+        elif pmc is None and world == 1 and args.pmc != "off":
             why = pmc_source
             pmc, pmc_source = pmc_from_file(args.spp, W, H, kms)
             if pmc is None:
@@ -756,7 +795,7 @@ def main():
             if "configs3_strong" in cxx and c3 is not None and "value" in cxx["configs3_strong"]:
                 cxx["configs3_strong"]["over_torch_leg"] = cxx["configs3_strong"]["value"] / c3["value"]
             out["cxx_frame"] = cxx
-        if world == 1:
+        if world == 1 and args.full:
             # the host-buffer boundary (pt_render_host): same frame, accumulators staged over PCIe both ways; not `value`
             acc = (np.zeros((npx, 3), np.float32), np.zeros((npx, 3), np.float32), np.zeros(npx, np.int32))
             scene.render_host(W, H, args.spp, MRR, accum=acc, want_stats=False)      # warm-up
@@ -765,7 +804,7 @@ def main():
             th = time.perf_counter() - th
             out["pcie_inclusive"] = {"value": samples_per_step / th / 1e6, "unit": "Msamples/s", "ms_per_step": th * 1e3,
                                      "what": "pt_render_host: 116 MB of accumulators host->device and back around the same frame"}
-        if world == 1 and os.path.exists(EXE):
+        if world == 1 and args.full and os.path.exists(EXE):
             # end to end: the stand-alone front end from process start to the BMP on disk -- exec + dynamic
             # linking, OBJ/MTL parse, HIP start-up, table upload, hierarchy build, render, read-back, resolve (powf), BMP write,
             # exit.  A child process; -T0_NS lets it report the time before main().
@@ -793,15 +832,18 @@ def main():
                                  "phases": phases, "exit_and_wait_s": unexplained,
                                  "what": "pt_render (C++ front end) as a child process: process start -> BMP on disk -> exit, the faster of two "
                                          "runs; seconds = pre_main_s + main_s + exit_and_wait_s"}
-        if world == 1 and args.cpu_seconds > 0:
+        if world == 1 and args.full and args.cpu_seconds > 0:
             out["cpu_baseline"], out["accuracy"] = cpu_baseline(MODELS, args.cpu_seconds, pt, scene)
             out["accuracy"]["vs_reference_stream"] = reference_stream_accuracy(MODELS, pt, scene)
-        if args.write_bmp:
+        if args.write_bmp or args.dump_outputs:
             parts = [t.cpu().numpy() for t in frame]
             s, s2, c = bands.assemble(parts, W, H, world)
+        if args.write_bmp:
             bgr, disp = pt.resolve(W, H, s, s2, c)
             pt.write_bmp(args.write_bmp, bgr)
             out["config"]["dispersion_max_min_avg"] = [float(d) for d in disp]
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, s, s2, c, W, H)
         print(json.dumps(out), flush=True)
     if replica_dir:
         shutil.rmtree(replica_dir, ignore_errors=True)

@@ -1,4 +1,4 @@
-"""bench.py on the GPU box: one short run, JSON contract checked field by field."""
+"""bench.py on the GPU box: short runs, JSON contract checked field by field (--full: every leg; plain: the headline alone)."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_emits_one_valid_json_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--spp", "8",
-                        "--cpu-seconds", "2"], capture_output=True, text=True, cwd=ROOT, timeout=600)
+                        "--cpu-seconds", "2", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -96,6 +96,41 @@ def test_bench_emits_one_valid_json_line():
     assert abs(ee["seconds"] - ee["phases"]["pre_main_s"] - ee["phases"]["main_s"] - ee["exit_and_wait_s"]) < 1e-6
 
 
+def test_plain_run_times_the_frame_alone_and_dumps_it(tmp_path):
+    """Without --full only the headline is measured; --dump-outputs writes the last timed frame, the same bits as the
+    library renders for any band of it."""
+    import importlib
+    import numpy as np
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", "8",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert k in j, k
+    assert j["unit"] == "Msamples/s" and j["higher_is_better"] is True and j["dtype"] == "f32" and j["steps"] == 3
+    c = j["config"]
+    assert abs(j["value"] - c["width"] * c["height"] * c["spp"] / j["ms_per_step"] / 1e3) < 1e-6 * j["value"]
+    assert j["roofline"]["kernel_ms"] > 0 and j["roofline"]["achieved"] is None
+    for k in ("cpu_baseline", "accuracy", "configs3_strong", "configs1_64spp", "skybox_open", "cxx_frame", "pcie_inclusive", "end_to_end"):
+        assert k not in j, k
+    W, H = c["width"], c["height"]
+    s, s2, cnt = (np.load(out / f"{n}.npy") for n in ("radiance_sum", "radiance_sum2", "sample_count"))
+    assert sorted(os.listdir(out)) == ["radiance_sum.npy", "radiance_sum2.npy", "sample_count.npy"]
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 * 10 ** 6
+    assert s.dtype == s2.dtype == cnt.dtype == np.float32 and s.shape == s2.shape == (H, W, 3) and cnt.shape == (H, W)
+    pt = importlib.import_module("path-tracing_amd")
+    scene = pt.Scene.load_obj(os.path.join(ROOT, "models") + "/", "Tor.obj", device=0)
+    r0 = H // 2 - 8
+    gs, gs2, gc, _ = scene.render_host(W, H, 8, 8, rows=(r0, r0 + 16), want_stats=False)
+    scene.close()
+    assert np.array_equal(gs.reshape(16, W, 3).view(np.uint32), s[r0:r0 + 16].view(np.uint32))
+    assert np.array_equal(gs2.reshape(16, W, 3).view(np.uint32), s2[r0:r0 + 16].view(np.uint32))
+    assert np.array_equal(gc.reshape(16, W).astype(np.float32), cnt[r0:r0 + 16])
+
+
 def test_two_rank_rehearsal_frame_equals_single_process(tmp_path):
     """bench.py's N > 1 code path (row bands, packed accumulators, the asynchronous gather pipelined over two band
     buffers, assembly, resolve) with two ranks sharing this box's one GPU and gloo as the transport: the gathered
@@ -121,7 +156,7 @@ def test_self_launch_two_ranks_and_too_many_gpus(tmp_path):
     box's one GPU) and refuses, with a clear message and nothing run, when N exceeds the visible devices."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--spp", "4",
-                        "--rehearse-on-one-gpu", "--no-configs3"], capture_output=True, text=True, cwd=ROOT, timeout=600, env=env)
+                        "--rehearse-on-one-gpu", "--no-configs3", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["rccl_ranks_seen"] == 2 and j["config"]["parallelism"] == "tilerows_interleaved2"
@@ -148,7 +183,7 @@ def test_two_rank_rccl_frame_equals_single_process(tmp_path):
     bmp = str(tmp_path / "two_ranks.bmp")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--spp", "8",
-                        "--write-bmp", bmp], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
+                        "--full", "--write-bmp", bmp], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["rccl_ranks_seen"] == 2 and "REHEARSAL" not in j["data"]

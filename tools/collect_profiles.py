@@ -4,7 +4,7 @@ numbers the documents quote.
 
     python tools/collect_profiles.py [--tag r03]
 
-    profiles/<tag>_bench_1gpu.json        the default bench.py line
+    profiles/<tag>_bench_1gpu.json        the bench.py --full line
     profiles/<tag>_kernel_stats.csv       rocprofv3 --kernel-trace --stats of the same command
     profiles/<tag>_pmc_hbm.json           the live counters bench.py collected (kernel_source_sha, kernel_ms): --pmc file reads it
     profiles/<tag>_pmc_detail.json        SQ / TCP counter passes of the timed Tor.obj kernel and of the x64 replica, with derived ratios

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Refreshes the round's evidence in ONE gpurun call:  gpurun --timeout 1200 -- 'bash tools/profile_round.sh r02'
 # Everything lands under gpurun_out/<tag>/ ; tools/collect_profiles.py <tag> then copies the summaries into profiles/.
-#   bench_1gpu.json      default bench.py run (live PMC, CPU baseline, accuracy) + pmc_hbm.json (the counters as a summary)
+#   bench_1gpu.json      bench.py --full run (live PMC, CPU baseline, accuracy) + pmc_hbm.json (the counters as a summary)
 #                        + pmc_hbm_c2_pmc_hbm.json (FETCH_SIZE / WRITE_SIZE of the 1024-spp launch, BASELINE configs[2])
 #   kt/                  rocprofv3 --kernel-trace --stats of the same command (no PMC in that run, CPU leg skipped)
 #   configs.jsonl        every BASELINE configuration on one GPU (tools/run_configs.py)
@@ -16,9 +16,9 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$TAG
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-python3 "$R/bench.py" --steps 10 --warmup 2 --save-pmc "$O/pmc_hbm.json" > "$O/bench_1gpu.json" 2> "$O/bench_1gpu.err"
+python3 "$R/bench.py" --full --steps 10 --warmup 2 --save-pmc "$O/pmc_hbm.json" > "$O/bench_1gpu.json" 2> "$O/bench_1gpu.err"
 echo "bench done"
-rocprofv3 --kernel-trace --stats -d "$O/kt" -o kt --output-format csv -- python3 "$R/bench.py" --cpu-seconds 0 --pmc off --no-configs3 --no-extra-legs > "$O/kt.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$O/kt" -o kt --output-format csv -- python3 "$R/bench.py" --full --cpu-seconds 0 --pmc off --no-configs3 --no-extra-legs > "$O/kt.log" 2>&1
 echo "kernel trace done"
 python3 "$R/tools/run_configs.py" > "$O/configs.jsonl" 2> "$O/configs.err"
 echo "configs done"
