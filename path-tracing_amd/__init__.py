@@ -18,6 +18,7 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("PT_HIP_LIB") or os.path.join(_HERE, "lib", "libpt_hip.so")
 
 PT_OK = 0
+PT_ERR_INVALID_ARGUMENT, PT_ERR_UNSUPPORTED = 1, 7
 STATUS_NAMES = {0: "PT_OK", 1: "PT_ERR_INVALID_ARGUMENT", 2: "PT_ERR_IO", 3: "PT_ERR_PARSE", 4: "PT_ERR_NO_DEVICE",
                 5: "PT_ERR_HIP", 6: "PT_ERR_OUT_OF_MEMORY", 7: "PT_ERR_UNSUPPORTED"}
 PT_ABI_VERSION = 5
@@ -36,7 +37,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_scene_clone_to_device", "pt_scene_timings", "pt_table_limits_check", "pt_rccl_available",
                "pt_frame_create", "pt_frame_info", "pt_frame_render", "pt_frame_gather", "pt_frame_wait", "pt_frame_read",
                "pt_frame_clear", "pt_frame_destroy", "pt_frame_band_kernel_ms", "pt_scene_skybox_size", "pt_table_limits_check_tree",
-               "pt_band_rows", "pt_session_create_strided", "pt_frame_row_stride"]
+               "pt_band_rows", "pt_session_create_strided", "pt_frame_row_stride",
+               "pt_camera_look_at", "pt_scene_set_camera", "pt_scene_get_camera", "pt_frame_set_camera"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -63,6 +65,40 @@ class RenderStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Camera(C.Structure):
+    """pt_camera: primary rays start at `origin`; pixel (x, y) looks along normalize((u right + v up) + forward) with
+    u = (x + jx) / W - 0.5, v = -(y + jy) / H + 0.5 (main.cpp:126-128).  REFERENCE_CAMERA is the reference's fixed view."""
+    _fields_ = [("origin", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3)]
+
+    @classmethod
+    def of(cls, origin, right, up, forward):
+        return cls((C.c_float * 3)(*origin), (C.c_float * 3)(*right), (C.c_float * 3)(*up), (C.c_float * 3)(*forward))
+
+    def as_array(self):
+        """4 x 3 float32: origin, right, up, forward."""
+        return np.array([list(self.origin), list(self.right), list(self.up), list(self.forward)], np.float32)
+
+    def __eq__(self, other):
+        return isinstance(other, Camera) and np.array_equal(self.as_array().view(np.uint32), other.as_array().view(np.uint32))
+
+    def __repr__(self):
+        return "Camera(origin=%s, right=%s, up=%s, forward=%s)" % tuple(tuple(r) for r in self.as_array().tolist())
+
+
+REFERENCE_CAMERA = ((0.0, 0.0, -20.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))   # main.cpp:126-129
+REFERENCE_FOV_Y = 53.13010235415598   # 2 atan(0.5) in degrees: the reference's vertical (and horizontal) field of view
+
+
+def look_at(eye, target, up=(0.0, 1.0, 0.0), fov_y=REFERENCE_FOV_Y, aspect=0.0, library=None):
+    """pt_camera_look_at: a Camera at `eye` looking at `target`; fov_y in degrees; aspect = W / H for square pixels, 0 for the
+    reference's mapping (both image axes span fov_y)."""
+    L = library or lib()
+    f3 = C.c_float * 3
+    cam = Camera()
+    _check(L.pt_camera_look_at(f3(*eye), f3(*target), f3(*up), fov_y, aspect, C.byref(cam)), L)
+    return cam
 
 
 def build(force=False):
@@ -157,6 +193,10 @@ def load_library(path):
     L.pt_frame_row_stride.argtypes = [vp, ip]
     L.pt_scene_skybox_size.argtypes = [vp, ip, ip]
     L.pt_table_limits_check_tree.argtypes = [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]
+    L.pt_camera_look_at.argtypes = [fp, fp, fp, C.c_float, C.c_float, C.POINTER(Camera)]
+    L.pt_scene_set_camera.argtypes = [vp, C.POINTER(Camera)]
+    L.pt_scene_get_camera.argtypes = [vp, C.POINTER(Camera), ip]
+    L.pt_frame_set_camera.argtypes = [vp, C.POINTER(Camera)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     return L
@@ -260,6 +300,18 @@ class Scene:
         w, h = C.c_int32(), C.c_int32()
         _check(self._L.pt_scene_skybox_size(self._h, C.byref(w), C.byref(h)), self._L)
         return w.value, h.value
+
+    def set_camera(self, camera):
+        """pt_scene_set_camera: a Camera (or an (origin, right, up, forward) tuple) for this handle; None = the reference's."""
+        if camera is not None and not isinstance(camera, Camera):
+            camera = Camera.of(*camera)
+        _check(self._L.pt_scene_set_camera(self._h, C.byref(camera) if camera is not None else None), self._L)
+
+    def camera(self):
+        """The handle's Camera, or None if it has none (it then renders the reference's view, REFERENCE_CAMERA)."""
+        cam, is_set = Camera(), C.c_int32()
+        _check(self._L.pt_scene_get_camera(self._h, C.byref(cam), C.byref(is_set)), self._L)
+        return cam if is_set.value else None
 
     def cull_tables(self, eps=1e-4):
         """The culling hierarchy for `eps` (diagnostics): dict of clusters, spheres, bary records, constants."""
@@ -410,6 +462,12 @@ class Frame:
         st = RenderStats()
         _check(self._L.pt_frame_render(self._h, C.byref(p), C.byref(st) if want_stats else None), self._L)
         return st.as_dict() if want_stats else None
+
+    def set_camera(self, camera):
+        """pt_frame_set_camera: the camera of every device's copy of the frame's scene (None = the reference's)."""
+        if camera is not None and not isinstance(camera, Camera):
+            camera = Camera.of(*camera)
+        _check(self._L.pt_frame_set_camera(self._h, C.byref(camera) if camera is not None else None), self._L)
 
     def band_kernel_ms(self):
         """Kernel time of every band of the last render(want_stats=True), -1 where there is none."""

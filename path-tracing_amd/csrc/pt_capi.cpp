@@ -77,18 +77,21 @@ int check_table_limits(unsigned long long n_slots, unsigned long long n_bvh_node
 
 // The culling hierarchy of a scene for one eps: built once per (scene, eps) on the host, whatever number of devices,
 // sessions or diagnostic calls ask for it.  (The test-hook build rebuilds every time: its mutations change the result.)
-int get_cull(pt_scene_host &h, float eps, std::shared_ptr<const pt::CullTables> &out) {
+// Keyed on (eps, envelope radius): a camera whose origin lies inside the camera-free envelope shares its tables.
+// r_camera: largest |component| of the camera origin (20 = the reference's fixed camera).
+int get_cull(pt_scene_host &h, float eps, double r_camera, std::shared_ptr<const pt::CullTables> &out) {
     std::lock_guard<std::mutex> lock(h.cull_mutex);
 #ifndef PT_TEST_HOOKS
+    const double r_max = pt::cull_r_max(h.vertex_extent, r_camera);
     for (const auto &t : h.cull_cache)
-        if (std::memcmp(&t->eps, &eps, sizeof eps) == 0) {
+        if (std::memcmp(&t->eps, &eps, sizeof eps) == 0 && t->r_max == r_max) {
             out = t;
             return PT_OK;
         }
 #endif
     const auto t0 = std::chrono::steady_clock::now();
     auto t = std::make_shared<pt::CullTables>();
-    pt::build_cull_tables(h.host, eps, *t);
+    pt::build_cull_tables(h.host, eps, *t, r_camera);
     t->eps = eps;
     h.cull_build_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     long long levels = 0;
@@ -156,11 +159,19 @@ int upload_vec(const std::vector<T> &v, T **dst) {
 // The cull hierarchy's radii and margins depend on eps (-EPS): upload on first use, replace if eps changes.
 // Callers hold scene->launch_mutex from here until their kernel has been enqueued: a concurrent render with another eps
 // must not free the tables between this call and that launch.
+// The camera's envelope radius for the cull tables (get_cull): 20 for the reference's camera at (0, 0, -20).
+double camera_radius(const pt_scene *s) {
+    if (!s->has_camera) return 20.0;
+    const float *o = s->camera.origin;
+    return std::max({20.0, static_cast<double>(std::fabs(o[0])), static_cast<double>(std::fabs(o[1])), static_cast<double>(std::fabs(o[2]))});
+}
+
 int ensure_cull(pt_scene *s, float eps) {
     DeviceCull &c = s->cull;
-    if (c.valid && std::memcmp(&c.eps, &eps, sizeof eps) == 0) return PT_OK;
+    const double r_camera = camera_radius(s);
+    if (c.valid && std::memcmp(&c.eps, &eps, sizeof eps) == 0 && c.r_max == pt::cull_r_max(s->shared->vertex_extent, r_camera)) return PT_OK;
     std::shared_ptr<const pt::CullTables> t;
-    int rc = get_cull(*s->shared, eps, t);
+    int rc = get_cull(*s->shared, eps, r_camera, t);
     if (rc != PT_OK) return rc;
     if (c.valid) PT_HIP_TRY(hipDeviceSynchronize());   // a previous launch may still read the old tables
     c.valid = false;
@@ -180,6 +191,7 @@ int ensure_cull(pt_scene *s, float eps) {
     }
     if (!t->bvh.empty() && (rc = upload_vec(t->bvh, &c.bvh)) != PT_OK) return rc;
     c.eps = eps;
+    c.r_max = t->r_max;
     c.valid = true;
     return PT_OK;
 }
@@ -196,6 +208,7 @@ int finish_scene(ScenePtr s, int device, pt_scene **out) {
     for (int m : h.host.tri_mat)
         if (m < 0 || m >= h.host.n_mat()) return fail(PT_ERR_INVALID_ARGUMENT, "triangle refers to material " + std::to_string(m));
     pt::build_device_tables(h.host, h.tables);
+    h.vertex_extent = pt::vertex_extent(h.host);
     if (device >= 0) {
         const int rc = upload(s.get(), device);
         if (rc != PT_OK) return rc;
@@ -240,6 +253,10 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
     a.emis_clusters = t.emis_clusters;
     a.emis_large_w0 = t.emis_large_w0;
     a.emis_bvh = t.emis_bvh ? 1u : 0u;
+    if (scene->has_camera) {   // the camera twins of the kernels (pt_kernels.hip: integrate_kernel<..., ADAPT | 1>)
+        a.camera = 1;
+        std::memcpy(a.cam, &scene->camera, sizeof a.cam);
+    }
 }
 
 void zero_stats(const pt_scene *scene, pt_render_stats *stats) {
@@ -572,6 +589,8 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     ScenePtr s(new pt_scene);
     s->shared = src->shared;   // parsed model, tables, hierarchies built so far
     s->sky = src->sky;         // the skybox of the handle the copy is made from
+    s->has_camera = src->has_camera;   // and its camera
+    s->camera = src->camera;
     if (device >= 0) {
         const int rc = upload(s.get(), device);
         if (rc != PT_OK) return rc;
@@ -645,6 +664,84 @@ static int scene_set_skybox_bmp_impl(pt_scene *scene, const char *path) {
         sk->h = h;
         scene->sky = std::move(sk);
     }
+    return PT_OK;
+}
+
+static bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+static int camera_look_at_impl(const float eye[3], const float target[3], const float up[3], float fov_y_degrees, float aspect,
+                               pt_camera *out) {
+    if (!eye || !target || !up || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!finite3(eye) || !finite3(target) || !finite3(up) || !std::isfinite(fov_y_degrees) || !std::isfinite(aspect))
+        return fail(PT_ERR_INVALID_ARGUMENT, "look_at: non-finite input");
+    if (!(fov_y_degrees > 0.0f && fov_y_degrees < 180.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "look_at: fov_y must lie in (0, 180) degrees");
+    double f[3], u[3], r[3];
+    for (int i = 0; i < 3; ++i) {
+        f[i] = static_cast<double>(target[i]) - static_cast<double>(eye[i]);
+        u[i] = up[i];
+    }
+    const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+    const double ul = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    if (!(fl > 0.0) || !(ul > 0.0)) return fail(PT_ERR_INVALID_ARGUMENT, "look_at: eye == target or a zero up vector");
+    for (double &x : f) x /= fl;
+    r[0] = u[1] * f[2] - u[2] * f[1];   // cross(up, forward)
+    r[1] = u[2] * f[0] - u[0] * f[2];
+    r[2] = u[0] * f[1] - u[1] * f[0];
+    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    if (!(rl > 1e-6 * ul)) return fail(PT_ERR_INVALID_ARGUMENT, "look_at: up is parallel to the view direction");
+    for (double &x : r) x /= rl;
+    const double sy = 2.0 * std::tan(static_cast<double>(fov_y_degrees) * (M_PI / 360.0));
+    const double sx = sy * (aspect > 0.0f ? static_cast<double>(aspect) : 1.0);
+    const double v[3] = {f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]};   // cross(forward, right)
+    for (int i = 0; i < 3; ++i) {
+        out->origin[i] = eye[i];
+        out->right[i] = static_cast<float>(r[i] * sx);
+        out->up[i] = static_cast<float>(v[i] * sy);
+        out->forward[i] = static_cast<float>(f[i]);
+    }
+    return PT_OK;
+}
+
+// NULL: back to the reference's camera.  Checks everything before it changes anything.
+static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
+    if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (!cam) {
+        scene->has_camera = false;
+        scene->camera = pt_camera{};
+        return PT_OK;
+    }
+    if (!finite3(cam->origin) || !finite3(cam->right) || !finite3(cam->up) || !finite3(cam->forward))
+        return fail(PT_ERR_INVALID_ARGUMENT, "camera: non-finite component");
+    double r[3], u[3], f[3];
+    for (int i = 0; i < 3; ++i) {
+        r[i] = cam->right[i];
+        u[i] = cam->up[i];
+        f[i] = cam->forward[i];
+    }
+    auto len = [](const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+    if (!(len(f) > 0.0)) return fail(PT_ERR_INVALID_ARGUMENT, "camera: zero forward vector");
+    const double det = r[0] * (u[1] * f[2] - u[2] * f[1]) - r[1] * (u[0] * f[2] - u[2] * f[0]) + r[2] * (u[0] * f[1] - u[1] * f[0]);
+    if (!(std::fabs(det) > 1e-6 * len(r) * len(u) * len(f)))
+        return fail(PT_ERR_INVALID_ARGUMENT, "camera: right, up and forward are not linearly independent");
+    for (int i = 0; i < 3; ++i)
+        if (!(std::fabs(cam->origin[i]) <= PT_CAMERA_MAX_ORIGIN))
+            return fail(PT_ERR_UNSUPPORTED, "camera: origin component beyond PT_CAMERA_MAX_ORIGIN (" + std::to_string(PT_CAMERA_MAX_ORIGIN) +
+                                                "): the culling margins are not derived that far out");
+    scene->camera = *cam;
+    scene->has_camera = true;
+    return PT_OK;
+}
+
+static int scene_get_camera_impl(const pt_scene *scene, pt_camera *cam, int32_t *is_set) {
+    if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (cam) {
+        if (scene->has_camera) {
+            *cam = scene->camera;
+        } else {   // the reference's fixed camera, main.cpp:126-129
+            *cam = pt_camera{{0.0f, 0.0f, -20.0f}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}};
+        }
+    }
+    if (is_set) *is_set = scene->has_camera ? 1 : 0;
     return PT_OK;
 }
 
@@ -813,7 +910,7 @@ static int scene_cull_tables_impl(pt_scene *scene, float eps, int32_t *counts, f
                          float *constants) {
     if (!scene || !counts) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     std::shared_ptr<const pt::CullTables> tp;
-    const int rc = get_cull(*scene->shared, eps, tp);
+    const int rc = get_cull(*scene->shared, eps, camera_radius(scene), tp);
     if (rc != PT_OK) return rc;
     const pt::CullTables &t = *tp;
     counts[0] = static_cast<int32_t>(t.clusters.size());
@@ -836,7 +933,7 @@ static int scene_cull_tables_impl(pt_scene *scene, float eps, int32_t *counts, f
 static int scene_cull_layout_impl(pt_scene *scene, float eps, int32_t *counts, int32_t *slot_triangle, void *bvh_nodes) {
     if (!scene || !counts) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     std::shared_ptr<const pt::CullTables> tp;
-    const int rc = get_cull(*scene->shared, eps, tp);
+    const int rc = get_cull(*scene->shared, eps, camera_radius(scene), tp);
     if (rc != PT_OK) return rc;
     const pt::CullTables &t = *tp;
     counts[0] = static_cast<int32_t>(t.slot_tri.size());
@@ -1054,6 +1151,22 @@ int pt_scene_clone_to_device(const pt_scene *scene, int device, pt_scene **out) 
 
 int pt_scene_set_skybox_bmp(pt_scene *scene, const char *path) {
     return guarded([&] { return scene_set_skybox_bmp_impl(scene, path); });
+}
+
+int pt_camera_look_at(const float eye[3], const float target[3], const float up[3], float fov_y_degrees, float aspect, pt_camera *out) {
+    return guarded([&] { return camera_look_at_impl(eye, target, up, fov_y_degrees, aspect, out); });
+}
+
+int pt_scene_set_camera(pt_scene *scene, const pt_camera *camera) {
+    return guarded([&] {
+        if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+        std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);   // (a launch being enqueued reads the camera under it)
+        return scene_set_camera_impl(scene, camera);
+    });
+}
+
+int pt_scene_get_camera(const pt_scene *scene, pt_camera *camera, int32_t *is_set) {
+    return guarded([&] { return scene_get_camera_impl(scene, camera, is_set); });
 }
 
 int pt_render_device(pt_scene *scene, const pt_render_params *p, float *d_sum, float *d_sum2, int32_t *d_count, void *hip_stream, pt_render_stats *stats) {

@@ -24,6 +24,7 @@ struct pt_scene_host {
     std::vector<std::shared_ptr<const pt::CullTables>> cull_cache;   // most recent last; a handful of eps values at most
     double load_seconds = 0;                                         // parsing + per-triangle tables
     double cull_build_seconds = 0;                                   // host time spent in build_cull_tables (pt_render -TIMING)
+    double vertex_extent = 0;                                        // largest |vertex coordinate| (the cull envelope's key)
 };
 
 // Skybox texels (B,G,R; top-down rows; no padding).  A skybox belongs to a pt_scene handle, not to the shared model: a per-device
@@ -33,9 +34,11 @@ struct pt_sky_texels {
     int w = 0, h = 0;
 };
 
-// Device copy of one CullTables (they depend on eps; a scene keeps the one of the last eps it rendered with).
+// Device copy of one CullTables (they depend on eps and on the envelope the camera needs; a scene keeps the one of its last
+// render).
 struct DeviceCull {
     float eps = 0;
+    double r_max = 0;   // CullTables::r_max
     bool valid = false;
     std::shared_ptr<const pt::CullTables> host;
     pt::ClusterDesc *clusters = nullptr;
@@ -71,6 +74,8 @@ struct pt_scene {
     std::shared_ptr<const pt_sky_texels> sky;   // this handle's skybox (nullptr = none); copies made from it inherit it
     uint8_t *d_sky = nullptr;      // the same texels on this copy's device
     int sky_w = 0, sky_h = 0;
+    bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
+    pt_camera camera{};
     // ensure_cull + the enqueue of a launch happen under launch_mutex (a concurrent render with another eps must not free
     // the tables in between); nothing waits for the device while holding it.
     std::mutex launch_mutex;

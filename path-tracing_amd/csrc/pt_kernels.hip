@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstddef>
 #include <type_traits>
 
 #include "pt_fastfp.hpp"
@@ -1472,6 +1473,16 @@ constexpr int kMaxBatchPass = 32766;   // adaptive instantiations: a pixel's nex
 #ifndef PT_BIG_RAYS_PER_LANE
 #define PT_BIG_RAYS_PER_LANE 1   // the same for the statistics-free, skybox-free big-scene kernel
 #endif
+// The camera of a camera-twin launch (RenderArgs::cam: origin, right, up, forward), read where a primary ray is made.  The
+// address is made opaque there, so that the twelve scalar loads are not hoisted to the head of the kernel, where their
+// registers would be held -- spilled -- for the whole launch (the kernel's only argument sits at the start of its kernarg segment).
+using CameraView = const __attribute__((address_space(4))) float *;
+__device__ __forceinline__ CameraView camera_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, cam);
+    asm volatile("" : "+s"(p));
+    return reinterpret_cast<CameraView>(p);
+}
+
 // rays per lane of an instantiation: the launch geometry (tile width) follows from it on the host as well
 template <bool SKY, bool BIG, bool STATS>
 constexpr int rays_per_lane() { return (!SKY && !STATS) ? (BIG ? PT_BIG_RAYS_PER_LANE : PT_RAYS_PER_LANE) : 1; }
@@ -1484,13 +1495,17 @@ constexpr int integrator_waves() {
     return SKY ? ((BIG && STATS && ENV) ? PT_BIG_WAVES /* (that one spills at 5) */ : PT_SKY_WAVES)
                : BIG ? PT_BIG_WAVES : (STATS || (!NARROW && rays_per_lane<SKY, BIG, STATS>() > 1)) ? PT_WAVES_PER_SIMD - 1 : PT_WAVES_PER_SIMD;
 }
-// ADAPT = the two-pixel kernel for launches with adaptive sampling on (error >= 0), with tiles of 64 ADAPT pixels (2: 16 x 8,
-// 4: 32 x 8): see "Batches" in the pass loop.
+// ADAPT = POOL | CAM.  POOL (bits 1-2) = the two-pixel kernel for launches with adaptive sampling on (error >= 0), with tiles of
+// 64 POOL pixels (2: 16 x 8, 4: 32 x 8): see "Batches" in the pass loop.  CAM (bit 0) = the camera twin: primary rays from the
+// scene handle's pt_camera (RenderArgs::cam) instead of the reference's fixed eye.  (One template argument for both, so that the
+// camera-free kernels keep their names: tests/test_kernel_resources.py pins them by mangled name.)
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
+    constexpr int POOL = ADAPT & ~1;
+    constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!NARROW || (!SKY && !STATS), "only the statistics-free, skybox-free kernels have a narrow variant");
     constexpr int R = NARROW ? 1 : rays_per_lane<SKY, BIG, STATS>();   // pixels per lane: the wave's tile is kTileW * R x kTileH
-    static_assert(ADAPT == 0 || ((ADAPT == 2 || ADAPT == 4) && (R == 2 || BIG) && !STATS && !SKY), "batches of the tile's pixels (a pixel's number takes 8 bits): the two-pixel kernel and the box-tree kernel");
+    static_assert(POOL == 0 || ((POOL == 2 || POOL == 4) && (R == 2 || BIG) && !STATS && !SKY), "batches of the tile's pixels (a pixel's number takes 8 bits): the two-pixel kernel and the box-tree kernel");
     // REGEN = path regeneration: a lane whose path has ended starts its pixel's NEXT pass at once instead of idling until the
     // longest path of the wave is done.  The skybox instantiations run this way: a scene with a skybox is an open scene, most
     // paths end on their first or second segment (scene.cpp:125-155: a miss ends the path) -- Tor.obj without its back wall has
@@ -1500,14 +1515,14 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
     // segment) whatever the other lanes are doing.  The closed-room kernels keep the pass loop: there regeneration gains
     // nothing and would cost the last-segment filter, which needs the wave's rays to reach their last segment together.
     constexpr bool REGEN = SKY;
-    static_assert(!REGEN || !ADAPT, "the compacting instantiation keeps the pass loop");
+    static_assert(!REGEN || !POOL, "the compacting instantiation keeps the pass loop");
     // kDynSlots: batches of at most 64 pixels run with the second ray slots switched off (scalar branches around every per-ray piece of
     // the search and of shading).  The 16 x 8 kernel has them -- a third of its batches are such -- the 32 x 8 kernel does not: one batch
     // in eleven is, and the branches cost every batch 3-4 % (1080p 56.0 -> 54.1 ms, 3840 x 2160 215.5 -> 207.2, r04_ab_logs.txt adapt5).
-    constexpr bool kDynSlots = ADAPT != 0 && R == 2 && (ADAPT != 4 || PT_ADAPT4_DYN);
-    constexpr int kOwn = ADAPT ? ADAPT : R;   // pixels of the tile per lane: pixel j of the tile = column (j % 8) + 8 (j / 64), row (j % 64) / 8
+    constexpr bool kDynSlots = POOL != 0 && R == 2 && (POOL != 4 || PT_ADAPT4_DYN);
+    constexpr int kOwn = POOL ? POOL : R;   // pixels of the tile per lane: pixel j of the tile = column (j % 8) + 8 (j / 64), row (j % 64) / 8
     constexpr int kTW = kTileW * kOwn;
-    __shared__ WaveLds<std::conditional_t<BIG, std::conditional_t<ADAPT != 0, BigQueuesAdapt<ADAPT>, BigQueues>, std::conditional_t<(R > 1), SmallQueues2, SmallQueues>>, R, ADAPT> lds;   // one wave per workgroup: all wave-private
+    __shared__ WaveLds<std::conditional_t<BIG, std::conditional_t<POOL != 0, BigQueuesAdapt<POOL>, BigQueues>, std::conditional_t<(R > 1), SmallQueues2, SmallQueues>>, R, POOL> lds;   // one wave per workgroup: all wave-private
 
     const int lane = threadIdx.x;
     if constexpr (decltype(lds)::kMatCache > 0) {
@@ -1552,7 +1567,7 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
     // interleaved split of a frame over several devices, pt_frame.cpp).  acc_y0 = the tile's first row in the band's planes; its first
     // image row follows from it (and is what the camera ray and the RNG's pixel index take).
     int tile_x0 = static_cast<int>(tile % a.blocks_x) * kTW, acc_y0 = static_cast<int>(tile / a.blocks_x) * kTileH;   // wave-uniform
-    if constexpr (ADAPT != 0) {   // (the division runs on the vector unit: say that its results are scalars, or the 16 x 8 kernel spills one of them)
+    if constexpr (POOL != 0) {   // (the division runs on the vector unit: say that its results are scalars, or the 16 x 8 kernel spills one of them)
         tile_x0 = __builtin_amdgcn_readfirstlane(tile_x0);
         acc_y0 = __builtin_amdgcn_readfirstlane(acc_y0);
     }
@@ -1608,7 +1623,7 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
 #pragma unroll
     for (int k = 0; k < R; ++k) {
         lowvar[k] = false;
-        if constexpr (ADAPT) {
+        if constexpr (POOL) {
             // (the answers of this instantiation live in LDS, by pixel: below)
         } else if constexpr (!kAccInLds) {
             if (in_image[k] && a.error >= 0.0f) {   // (adaptive sampling off: nobody asks, and a work item need not read its tile at all)
@@ -1628,7 +1643,7 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
     auto job_of = [&](int k) { return (opaque(jobs) >> (8 * k)) & 0xFFu; };
     auto tile_x_of = [&](uint32_t j) { return tile_x0 + static_cast<int>((j & 63u) % kTileW) + kTileW * static_cast<int>(j >> 6); };
     auto tile_y_of = [&](uint32_t j) { return tile_y0 + static_cast<int>((j & 63u) / kTileW); };
-    if constexpr (ADAPT) {
+    if constexpr (POOL) {
 #pragma unroll
         for (int kb = 0; kb < kOwn; ++kb) {   // the lane's own pixels: next pass | answer
             const uint32_t j = static_cast<uint32_t>(lane) + 64u * kb;
@@ -1650,7 +1665,7 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
             // (opaque: or the addresses are formed at the head of the pass and held -- spilled -- until here)
             uint32_t le = opaque(static_cast<uint32_t>(lane));
             int kb = k;
-            if constexpr (ADAPT) {
+            if constexpr (POOL) {
                 const uint32_t j = job_of(k);
                 le = j & 63u;
                 kb = static_cast<int>(j >> 6);
@@ -1672,7 +1687,7 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
             lds.acc.v[6][id] = __int_as_float(nn);
         }
         const bool now_low = low_variance(n0, n1, n2, p0, p1, p2, nn);
-        if constexpr (ADAPT) {
+        if constexpr (POOL) {
             // (the answers live in LDS, by pixel, whoever traces it -- bit 0 of the pixel's word, its next pass above --; the owners
             // read them at the head of every batch)
             const uint32_t pj = job_of(k);
@@ -1720,11 +1735,11 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
         cur_pass[k] = next_pass[k] = pass_first;
         q[k].ox = q[k].oy = q[k].oz = 0.0f; q[k].dx = q[k].dy = 0.0f; q[k].dz = 1.0f;
     }
-    for (int pass = pass_first; ADAPT ? true : REGEN ? pass == pass_first : pass < pass_last; ++pass) {   // (REGEN: one trip, the loop inside runs all passes; ADAPT: one trip per batch)
+    for (int pass = pass_first; POOL ? true : REGEN ? pass == pass_first : pass < pass_last; ++pass) {   // (REGEN: one trip, the loop inside runs all passes; POOL: one trip per batch)
         // Adaptive skip, main.cpp:118-125.
         bool skip[R], traced[R];
         bool two = true;   // wave-uniform: some lane's second ray slot is in use this pass
-        if constexpr (!ADAPT) {
+        if constexpr (!POOL) {
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 skip[k] = !in_image[k] || (pass > 10 && (pass % 4) && lowvar[k]);
@@ -1752,13 +1767,13 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
         // and pass, the search returns the minimum over the same candidates), so the frame does not change.
         // the RNG's pixel index of ray slot k
         auto rng_pixel = [&](int k) {
-            if constexpr (ADAPT) {
+            if constexpr (POOL) {
                 const uint32_t j = job_of(k);
                 return static_cast<uint32_t>(static_cast<size_t>(tile_y_of(j)) * a.width + tile_x_of(j));
             }
             return opaque(gpix[k]);
         };
-        if constexpr (ADAPT) {
+        if constexpr (POOL) {
             wave_sync();   // (the answers written while shading the last batch, by whichever lane traced the pixel)
             uint32_t word[kOwn], np[kOwn];
             bool pend[kOwn], sel[kOwn];
@@ -1844,7 +1859,7 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
                     xi = tile_x0 + static_cast<int>(opaque(static_cast<uint32_t>(lane)) % kTileW) + kTileW * k;
                     yi = tile_y0 + static_cast<int>(opaque(static_cast<uint32_t>(lane)) / kTileW);
                 }
-                if constexpr (ADAPT) {
+                if constexpr (POOL) {
                     xi = tile_x_of(job_of(k));
                     yi = tile_y_of(job_of(k));
                 }
@@ -1852,15 +1867,31 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
                 asm volatile("" : "+v"(xi), "+v"(yi), "+s"(wi), "+s"(hi));
                 const float ddx = static_cast<float>((xi + jx) / wi - 0.5f);
                 const float ddy = static_cast<float>(-(yi + jy) / hi + 0.5f);
-                const float ddz = 1.0f;
-                const float inv = rcp_rn_normal(sqrt_rn_normal((ddx * ddx + ddy * ddy) + (1.0f * 1.0f + 0.0f * 0.0f)));   // 1 <= argument < 2
-                out_dx = ddx * inv; out_dy = ddy * inv; out_dz = ddz * inv;
+                if constexpr (CAM) {
+                    // u right + v up + forward, componentwise, unfused (-ffp-contract=off); with the reference camera every step
+                    // is exact (x 1, + 0) and |d|^2 is the sum below, so the twin's frame is the camera-free kernel's bit for bit
+                    const CameraView c = camera_view();
+                    float dx = (ddx * c[3] + ddy * c[6]) + c[9];
+                    float dy = (ddx * c[4] + ddy * c[7]) + c[10];
+                    float dz = (ddx * c[5] + ddy * c[8]) + c[11];
+                    normalize3(dx, dy, dz);
+                    out_dx = dx; out_dy = dy; out_dz = dz;
+                } else {
+                    const float ddz = 1.0f;
+                    const float inv = rcp_rn_normal(sqrt_rn_normal((ddx * ddx + ddy * ddy) + (1.0f * 1.0f + 0.0f * 0.0f)));   // 1 <= argument < 2
+                    out_dx = ddx * inv; out_dy = ddy * inv; out_dz = ddz * inv;
+                }
             }
         };
-        // starts slot k's path along a primary direction (eye fixed at (0, 0, -20), main.cpp:129; Ray::color_ = 1, ray.h:17)
+        // starts slot k's path along a primary direction (eye fixed at (0, 0, -20), main.cpp:129 -- or the camera's; Ray::color_ = 1, ray.h:17)
         auto start_path = [&](int k, float ddx, float ddy, float ddz) {
             q[k].dx = ddx; q[k].dy = ddy; q[k].dz = ddz;
-            q[k].ox = 0.0f; q[k].oy = 0.0f; q[k].oz = -20.0f;
+            if constexpr (CAM) {
+                const CameraView c = camera_view();
+                q[k].ox = c[0]; q[k].oy = c[1]; q[k].oz = c[2];
+            } else {
+                q[k].ox = 0.0f; q[k].oy = 0.0f; q[k].oz = -20.0f;
+            }
             tr[k] = tg[k] = tb[k] = 1.0f;
             depth[k] = 0;
         };
@@ -1871,7 +1902,7 @@ __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NAR
         };
         // the pass of ray slot k's path: the wave's (a scalar) -- or, with regeneration or batches, the slot's own
         auto pass_of = [&](int k) {
-            if constexpr (ADAPT) {   // (a traced pixel's word holds the pass AFTER this one: read where needed, a register would spill)
+            if constexpr (POOL) {   // (a traced pixel's word holds the pass AFTER this one: read where needed, a register would spill)
                 return static_cast<int>(lds.low.v[job_of(k)] >> 1) - 1;
             } else if constexpr (REGEN) {
                 return cur_pass[k];
@@ -2379,8 +2410,8 @@ hipError_t launch_integrator(const RenderArgs &args0, hipStream_t stream) {
     RenderArgs args = args0;
     args.blockprof = d_cnt;
     char name[128];
-    std::snprintf(name, sizeof name, "_ZN2pt16integrate_kernelILb%dELb%dELb%dELb%dELb0ELi0EEEvNS_10RenderArgsE", args.sky ? 1 : 0,
-                  (args.big != 0) ? 1 : 0, args.stats ? 1 : 0, args.may_leave_envelope ? 1 : 0);
+    std::snprintf(name, sizeof name, "_ZN2pt16integrate_kernelILb%dELb%dELb%dELb%dELb0ELi%dEEEvNS_10RenderArgsE", args.sky ? 1 : 0,
+                  (args.big != 0) ? 1 : 0, args.stats ? 1 : 0, args.may_leave_envelope ? 1 : 0, args.camera ? 1 : 0);
     hipFunction_t f;
     e = hipModuleGetFunction(&f, mod, name);
     if (e != hipSuccess) return e;
@@ -2426,58 +2457,65 @@ bool launch_with_stats(const RenderArgs &args) {
     return args.stats != nullptr;
 #endif
 }
-// Calls f(kernel) with the instantiation a launch with these arguments runs.
+// Calls f(kernel, id) with the instantiation a launch with these arguments runs (id: its index, 0 .. kInstantiations - 1).
+// A launch with a camera (RenderArgs::camera) runs the camera twin of the instantiation it would run without one: ADAPT | 1.
+constexpr int kInstantiations = 48;
 template <class F>
 void with_instantiation(const RenderArgs &args, F &&f) {
     const bool big = (args.big != 0);
     const bool stats = launch_with_stats(args);
-    auto pick = [&](auto sky, auto bg, auto st) {
+    auto pick = [&](auto sky, auto bg, auto st, auto cm) {
         constexpr bool S = decltype(sky)::value, B = decltype(bg)::value, T = decltype(st)::value;
+        constexpr int C = decltype(cm)::value;   // 0, or 1: the camera twin (its id is 24 higher)
         if constexpr (!S && !T && rays_per_lane<S, B, T>() > 1) {
             if (args.narrow) {
-                if (args.may_leave_envelope) f(integrate_kernel<false, B, false, true, true>, 17 + 2 * B);
-                else f(integrate_kernel<false, B, false, false, true>, 16 + 2 * B);
+                if (args.may_leave_envelope) f(integrate_kernel<false, B, false, true, true, C>, 17 + 2 * B + 24 * C);
+                else f(integrate_kernel<false, B, false, false, true, C>, 16 + 2 * B + 24 * C);
                 return;
             }
             if constexpr (!B) {
                 // adaptive sampling on: the instantiations that run batches (not built with the rare envelope test: one more
                 // spilled register there)
                 if (args.adapt_pool == 4) {
-                    f(integrate_kernel<false, false, false, false, false, 4>, 21);
+                    f(integrate_kernel<false, false, false, false, false, 4 | C>, 21 + 24 * C);
                     return;
                 }
                 if (args.adapt_pool == 2) {
-                    f(integrate_kernel<false, false, false, false, false, 2>, 20);
+                    f(integrate_kernel<false, false, false, false, false, 2 | C>, 20 + 24 * C);
                     return;
                 }
             }
         }
         if constexpr (!S && !T && B) {   // the box-tree kernel with adaptive sampling on: batches over 16 x 8 / 32 x 8 tiles, one ray slot per lane
             if (args.adapt_pool == 4) {
-                f(integrate_kernel<false, true, false, false, false, 4>, 23);
+                f(integrate_kernel<false, true, false, false, false, 4 | C>, 23 + 24 * C);
                 return;
             }
             if (args.adapt_pool == 2) {
-                f(integrate_kernel<false, true, false, false, false, 2>, 22);
+                f(integrate_kernel<false, true, false, false, false, 2 | C>, 22 + 24 * C);
                 return;
             }
         }
-        if (args.may_leave_envelope) f(integrate_kernel<S, B, T, true>, ((S * 2 + B) * 2 + T) * 2 + 1);
-        else f(integrate_kernel<S, B, T, false>, ((S * 2 + B) * 2 + T) * 2);
+        if (args.may_leave_envelope) f(integrate_kernel<S, B, T, true, false, C>, ((S * 2 + B) * 2 + T) * 2 + 1 + 24 * C);
+        else f(integrate_kernel<S, B, T, false, false, C>, ((S * 2 + B) * 2 + T) * 2 + 24 * C);
     };
     using Yes = std::true_type;
     using No = std::false_type;
-    if (stats) {
-        if (args.sky && big) pick(Yes(), Yes(), Yes());
-        else if (args.sky) pick(Yes(), No(), Yes());
-        else if (big) pick(No(), Yes(), Yes());
-        else pick(No(), No(), Yes());
-    } else {
-        if (args.sky && big) pick(Yes(), Yes(), No());
-        else if (args.sky) pick(Yes(), No(), No());
-        else if (big) pick(No(), Yes(), No());
-        else pick(No(), No(), No());
-    }
+    auto by_scene = [&](auto cm) {
+        if (stats) {
+            if (args.sky && big) pick(Yes(), Yes(), Yes(), cm);
+            else if (args.sky) pick(Yes(), No(), Yes(), cm);
+            else if (big) pick(No(), Yes(), Yes(), cm);
+            else pick(No(), No(), Yes(), cm);
+        } else {
+            if (args.sky && big) pick(Yes(), Yes(), No(), cm);
+            else if (args.sky) pick(Yes(), No(), No(), cm);
+            else if (big) pick(No(), Yes(), No(), cm);
+            else pick(No(), No(), No(), cm);
+        }
+    };
+    if (args.camera) by_scene(std::integral_constant<int, 1>());
+    else by_scene(std::integral_constant<int, 0>());
 }
 }  // namespace
 
@@ -2538,7 +2576,7 @@ void integrator_plan_tiles(RenderArgs &args, int cu_count, int force) {
 // calculation (registers, LDS, launch bounds): the scheduler's count of wave slots.  Asked once per instantiation and device.
 hipError_t integrator_waves_per_cu(const RenderArgs &args, int *waves) {
     constexpr int kDevices = 16;
-    static std::atomic<int> cache[kDevices][24];   // 0 = not asked yet
+    static std::atomic<int> cache[kDevices][kInstantiations];   // 0 = not asked yet
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;

@@ -59,6 +59,10 @@ struct RenderArgs {
     uint32_t regen_min_dead;            // skybox instantiations (path regeneration): new paths start once this many ray slots of the wave wait for one
     uint32_t last_segment_filter;       // 0 = off
     uint32_t emis_clusters, emis_large_w0, emis_bvh;
+    // The scene handle's camera (pt_hip.h: pt_camera), appended so that the fields above keep their offsets.  camera != 0: the
+    // launch runs the camera twins (integrate_kernel<..., ADAPT | 1>), which read cam = origin[3], right[3], up[3], forward[3].
+    int32_t camera;
+    float cam[12];
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif

@@ -889,7 +889,14 @@ void build_bvh_sah(const HostScene &s, const std::vector<TriGeo> &geo, const std
 
 }  // namespace
 
-void build_cull_tables(const HostScene &s, float eps_f, CullTables &out) {
+double vertex_extent(const HostScene &s) {
+    double r = 0.0;
+    for (int i = 0; i < s.n_tri(); ++i)
+        for (int k = 4; k < 13; ++k) r = std::max(r, static_cast<double>(std::fabs(s.tri[14 * static_cast<size_t>(i) + k])));
+    return r;
+}
+
+void build_cull_tables(const HostScene &s, float eps_f, CullTables &out, double r_camera) {
     const int T = s.n_tri();
     const double eps = eps_f;
     out = CullTables();
@@ -903,9 +910,9 @@ void build_cull_tables(const HostScene &s, float eps_f, CullTables &out) {
     out.big = big;
 
     // ---- scene-wide bounds
-    double r_max = 20.0;   // the camera origin (0,0,-20), main.cpp:129
-    for (int i = 0; i < T; ++i)
-        for (int k = 4; k < 13; ++k) r_max = std::max(r_max, static_cast<double>(std::fabs(s.tri[14 * static_cast<size_t>(i) + k])));
+    // the camera origin ((0,0,-20), main.cpp:129, unless the scene handle has a camera of its own) and every vertex
+    const double r_max = cull_r_max(vertex_extent(s), r_camera);
+    out.r_max = r_max;
     const double r_org = r_max + 1.0;                       // ray origins sit on surfaces, offset by eps*N
     out.r_org = static_cast<float>(r_org);
     const double d_max = 2.0 * std::sqrt(3.0) * r_org;      // bound on |c - o| for c, o inside the scene box

@@ -1,5 +1,6 @@
 // Host-side scene: OBJ/MTL ingestion with the reference's token semantics and the tables the kernels read.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -141,6 +142,7 @@ struct CullTables {
     CullConstants cc;
     float eps = 0;
     float r_org = 0;                 // the margins hold for ray origins with every |component| <= r_org
+    double r_max = 0;                // r_org - 1 in double: max(20, camera origin, vertex coordinates) -- with eps, the cache key
     bool may_leave_envelope = false; // some triangle can be "hit" at a point outside that envelope (near-degenerate triangles)
     // Where the emitters are (triangles whose material has an emissive lobe): a path's LAST segment can only contribute by
     // hitting one, so the integrator first searches among them alone (pt_kernels.hip: `emis_only`).
@@ -176,6 +178,12 @@ struct DeviceTables {
 };
 
 void build_device_tables(const HostScene &s, DeviceTables &out);
-void build_cull_tables(const HostScene &s, float eps, CullTables &out);
+// r_camera: largest |component| of the camera origin the primary rays start from (the reference's: 20, main.cpp:129).  The
+// envelope is r_org = cull_r_max(s, r_camera) + 1.
+void build_cull_tables(const HostScene &s, float eps, CullTables &out, double r_camera = 20.0);
+// largest |vertex coordinate| of the scene
+double vertex_extent(const HostScene &s);
+// max(20, r_camera, vertex_extent): the radius the envelope of build_cull_tables is built from
+inline double cull_r_max(double vertex_extent, double r_camera) { return std::max(std::max(20.0, r_camera), vertex_extent); }
 
 }  // namespace pt

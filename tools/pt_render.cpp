@@ -24,6 +24,11 @@
 // after w untimed ones and prints one JSON line on stdout instead of writing an image, -SELFCOLL 1 (test aid, one GPU)
 // routes the band through an RCCL send / receive to self, -FASTEXIT 1 leaves with _Exit once the files are written (skips the
 // runtime's teardown).
+// A camera (pt_camera_look_at, not in the reference): -EYE x,y,z (default 0,0,-20), -LOOKAT x,y,z (default 0,0,0), -UP x,y,z
+// (default 0,1,0), -FOV <vertical degrees> (default 53.13010235415598 = 2 atan(0.5)), -ASPECT <width / height> (default 0: both image
+// axes span -FOV, the reference's mapping).  Without any of them no camera is set and the reference's view is rendered as before;
+// with the defaults spelled out the camera is the reference's and the image is the same.  PT_RENDER_PRINT_CAMERA=1 prints the
+// camera the flags resolve to ("camera none" without one) and exits.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -51,6 +56,9 @@ struct Options {   // defaults: config.h:16-29
     int gpus = 0, rehearse = 0, selfcoll = 0, bench_steps = 0, bench_warmup = 1, fast_exit = 0;
     std::string devices;
     long long t0_ns = 0;   // -T0_NS: CLOCK_REALTIME of the parent just before it started this process (bench.py), for the start-up phase
+    bool camera = false;   // any of -EYE / -LOOKAT / -UP / -FOV / -ASPECT given
+    std::string eye = "0,0,-20", lookat = "0,0,0", up = "0,1,0";
+    float fov = 53.13010235415598f, aspect = 0.0f;
 };
 
 long long now_ms() {
@@ -89,7 +97,25 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-BENCH_WARMUP") o.bench_warmup = std::atoi(v);
         if (f == "-T0_NS") o.t0_ns = std::atoll(v);
         if (f == "-FASTEXIT") o.fast_exit = std::atoi(v);
+        if (f == "-EYE") { o.eye = v; o.camera = true; }
+        if (f == "-LOOKAT") { o.lookat = v; o.camera = true; }
+        if (f == "-UP") { o.up = v; o.camera = true; }
+        if (f == "-FOV") { o.fov = static_cast<float>(std::atof(v)); o.camera = true; }
+        if (f == "-ASPECT") { o.aspect = static_cast<float>(std::atof(v)); o.camera = true; }
     }
+}
+
+// "x,y,z": three finite numbers, nothing else
+bool parse_vec3(const std::string &text, float out[3]) {
+    const char *p = text.c_str();
+    for (int k = 0; k < 3; ++k) {
+        char *end = nullptr;
+        out[k] = std::strtof(p, &end);
+        if (end == p || !std::isfinite(out[k])) return false;
+        if (*end != (k < 2 ? ',' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
 }
 
 int die(const char *what) {
@@ -112,6 +138,27 @@ int main(int argc, char **argv) {
                     o.model_name.c_str(), o.skybox.c_str(), o.time_limit, sd);
         return 0;
     }
+    pt_camera camera;
+    if (o.camera) {
+        float eye[3], at[3], up[3];
+        if (!parse_vec3(o.eye, eye) || !parse_vec3(o.lookat, at) || !parse_vec3(o.up, up)) {
+            std::cerr << "pt_render: -EYE / -LOOKAT / -UP take three comma-separated numbers, x,y,z" << std::endl;
+            return 2;
+        }
+        if (pt_camera_look_at(eye, at, up, o.fov, o.aspect, &camera) != PT_OK) return die("pt_render");
+    }
+    if (std::getenv("PT_RENDER_PRINT_CAMERA")) {
+        if (!o.camera) {
+            std::printf("camera none\n");
+        } else {
+            const float *rows[4] = {camera.origin, camera.right, camera.up, camera.forward};
+            const char *names[4] = {"origin", "right", "up", "forward"};
+            for (int r = 0; r < 4; ++r)
+                std::printf("%s %.9g %.9g %.9g\n", names[r], static_cast<double>(rows[r][0]), static_cast<double>(rows[r][1]),
+                            static_cast<double>(rows[r][2]));
+        }
+        return 0;
+    }
     if (o.width <= 0 || o.height <= 0) {
         std::cerr << "pt_render: --W and --H must be positive" << std::endl;
         return 2;
@@ -131,6 +178,7 @@ int main(int argc, char **argv) {
     pt_scene *scene = nullptr;
     if (pt_scene_load_obj(o.model_path.c_str(), o.model_name.c_str(), -1, &scene) != PT_OK) return die("pt_render");
     if (!o.skybox.empty() && pt_scene_set_skybox_bmp(scene, o.skybox.c_str()) != PT_OK) return die("pt_render");   // scene.cpp:20-22
+    if (o.camera && pt_scene_set_camera(scene, &camera) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
     const clk::time_point t_parse = clk::now();
     const int n_dev = pt_device_count();   // first HIP call: runtime start-up
     if (n_dev < 1) {
