@@ -29,7 +29,7 @@
  * pt_render_device / pt_render_host share the scene's scheduler state and are ordered on the device; every pt_session has
  * its own, so sessions of ONE scene (row bands of an image) run side by side, and launches of different scenes are
  * independent anyway.  Calls on one pt_session / pt_frame are serialised by the caller.  pt_scene_set_skybox_bmp,
- * pt_scene_set_camera and pt_scene_destroy must not race with a render of the same scene.
+ * pt_scene_set_camera, pt_scene_set_lens and pt_scene_destroy must not race with a render of the same scene.
  * Several GPUs: pt_frame_* (below) renders one image on the devices of one node from one host program -- row bands, one RCCL
  * group of sends / receives to the root -- the counterpart of the reference's `omp parallel for` over rows, main.cpp:115,132,141.
  */
@@ -179,6 +179,36 @@ int pt_scene_set_camera(pt_scene *scene, const pt_camera *camera);
 /* The handle's camera; *is_set = 0 (and the reference camera in *camera) if it has none.  Either pointer may be NULL. */
 int pt_scene_get_camera(const pt_scene *scene, pt_camera *camera, int32_t *is_set);
 
+/* ---- lens (depth of field) ------------------------------------------------------------------------ */
+
+/* A thin lens in front of the camera: primary rays start on a disc of `radius` around the camera origin, in the plane spanned by
+ * right and up, and every ray of a pixel passes through the same point of the focal plane -- the plane perpendicular to forward
+ * at `focus_distance` from the origin, which is therefore sharp.  With
+ *   r^ = right / |right|,  u^ = up / |up|,  f^ = forward / |forward|       (computed in double, rounded to float once)
+ * the primary ray of pixel (x, y), pass p, with the Philox words w0..w3 of counter (pixel, p, 0xFFFFFFFF, 0) (w0, w1: the jitter) is
+ *   D      = (u * right + v * up) + forward                    (exactly as pt_camera computes it, before normalising)
+ *   rho    = radius * sqrt(unit_float(w2));   phi = 2 * 3.141593f * unit_float(w3);   (sn, cs) = portable sin / cos of phi
+ *   L_i    = (rho * cs) * r^_i + (rho * sn) * u^_i            (i = x, y, z)
+ *   s      = focus_distance / ((D_x f^_x + D_y f^_y) + D_z f^_z)
+ *   origin = camera origin + L;   direction = normalize(D * s - L)
+ * in float, each operation correctly rounded and nothing fused (unit_float(w) = ((w >> 9) << 1 | 1) * 2^-24; normalize as
+ * pt_camera's).  No other random number changes: with the same seed, a frame with a lens and one without draw the same words.
+ * A lens belongs to the scene HANDLE, like the camera: copies made from it afterwards (pt_scene_clone_to_device, pt_frame_create)
+ * inherit it, and a launch uses the lens its handle has when it is enqueued.  A lens on a handle without a camera applies to the
+ * reference camera.  Setting it must not race with a render of the same handle. */
+typedef struct pt_lens {
+    float radius;           /* aperture radius, in scene units; 0 = a pinhole (no lens) */
+    float focus_distance;   /* distance of the focal plane from the camera origin, along forward */
+} pt_lens;
+
+/* Sets the handle's lens; NULL or radius == 0 returns to the pinhole.  PT_ERR_INVALID_ARGUMENT: a non-finite value, radius < 0,
+ * focus_distance <= 0, or a camera for which D . f^ could reach 0 in the image (|forward| <= |right . f^| + |up . f^|).
+ * PT_ERR_UNSUPPORTED: a lens origin could lie beyond PT_CAMERA_MAX_ORIGIN.  pt_scene_set_camera applies the same checks to
+ * the lens the handle already has.  A failed call leaves the handle as it was. */
+int pt_scene_set_lens(pt_scene *scene, const pt_lens *lens);
+/* The handle's lens; *is_set = 0 (and zeros in *lens) if it has none.  Either pointer may be NULL. */
+int pt_scene_get_lens(const pt_scene *scene, pt_lens *lens, int32_t *is_set);
+
 int pt_scene_counts(const pt_scene *scene, int32_t *n_triangles, int32_t *n_materials);
 int pt_scene_get_triangles(const pt_scene *scene, float *triangles, int32_t *triangle_material);
 int pt_scene_get_materials(const pt_scene *scene, float *materials);
@@ -264,6 +294,8 @@ int pt_frame_clear(pt_frame *frame);
 /* pt_scene_set_camera on every device's copy of the frame's scene (NULL: the reference's camera).  The frame takes the camera
  * of the scene it was created from; this changes it for the slices enqueued afterwards.  Not while a slice is in flight. */
 int pt_frame_set_camera(pt_frame *frame, const pt_camera *camera);
+/* pt_scene_set_lens on every device's copy of the frame's scene (NULL: no lens), likewise. */
+int pt_frame_set_lens(pt_frame *frame, const pt_lens *lens);
 void pt_frame_destroy(pt_frame *frame);
 /* Can RCCL be loaded and does it export what the gather calls?  version = ncclGetVersion's.  Needs no GPU. */
 int pt_rccl_available(int32_t *version);
@@ -274,7 +306,8 @@ int pt_rccl_available(int32_t *version);
  * The culling hierarchy's float-error margins are derived for the rays the integrator itself produces: unit
  * directions (normalised as Ray's constructor does, ray.h:23) and origins with max |component| <= max(20, largest
  * |component of the handle's camera origin|, largest |vertex coordinate|) + 1 (the camera -- the reference's at (0,0,-20)
- * unless pt_scene_set_camera set one --, or a point on a surface).  A ray outside that envelope
+ * unless pt_scene_set_camera set one --, or a point on a surface; with a lens, max_i(|origin_i| + radius sqrt(r^_i^2 + u^_i^2))
+ * plus a rounding allowance instead of the origin).  A ray outside that envelope
  * (| |d|^2 - 1 | > 1e-5, a farther origin) is answered by the reference's own loop over ALL triangles on the
  * device instead, so every finite ray gets the reference's answer; only the speed differs.  A ray with a non-finite
  * component misses (all its distances are NaN, see the deviation below).
@@ -313,8 +346,8 @@ int pt_write_bmp(const char *path, int32_t width, int32_t height, const uint8_t 
 
 /* ---- diagnostics ---------------------------------------------------------------------------------- */
 
-/* The culling hierarchy built for `eps` and the handle's current camera (host side; works on device < 0 scenes).  A camera
- * whose origin lies within the default envelope (every |component| <= max(20, largest |vertex coordinate|)) shares the
+/* The culling hierarchy built for `eps` and the handle's current camera and lens (host side; works on device < 0 scenes).  A
+ * camera (with its lens) whose origins lie within the default envelope (every |component| <= max(20, largest |vertex coordinate|)) shares the
  * camera-free hierarchy; a farther one gets margins for its larger envelope.  counts[4] = clusters, sphere
  * records, barycentric records, triangles handled by the barycentric class.  Pass NULL tables to query counts only.
  * clusters: 16 words each (centre[3], r2, then as uint32 bit patterns first_tri, n_tri, kind, data_off, n_levels,

@@ -38,7 +38,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_frame_create", "pt_frame_info", "pt_frame_render", "pt_frame_gather", "pt_frame_wait", "pt_frame_read",
                "pt_frame_clear", "pt_frame_destroy", "pt_frame_band_kernel_ms", "pt_scene_skybox_size", "pt_table_limits_check_tree",
                "pt_band_rows", "pt_session_create_strided", "pt_frame_row_stride",
-               "pt_camera_look_at", "pt_scene_set_camera", "pt_scene_get_camera", "pt_frame_set_camera"]
+               "pt_camera_look_at", "pt_scene_set_camera", "pt_scene_get_camera", "pt_frame_set_camera",
+               "pt_scene_set_lens", "pt_scene_get_lens", "pt_frame_set_lens"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -89,6 +90,30 @@ class Camera(C.Structure):
 
 REFERENCE_CAMERA = ((0.0, 0.0, -20.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))   # main.cpp:126-129
 REFERENCE_FOV_Y = 53.13010235415598   # 2 atan(0.5) in degrees: the reference's vertical (and horizontal) field of view
+
+
+class Lens(C.Structure):
+    """pt_lens: a thin lens of aperture `radius` focused at `focus_distance` along the camera's forward axis (pt_hip.h states
+    the primary ray it gives exactly).  radius 0 is a pinhole."""
+    _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float)]
+
+    def __eq__(self, other):
+        return isinstance(other, Lens) and np.array_equal(np.array([self.radius, self.focus_distance], np.float32).view(np.uint32),
+                                                          np.array([other.radius, other.focus_distance], np.float32).view(np.uint32))
+
+    def __repr__(self):
+        return "Lens(radius=%r, focus_distance=%r)" % (self.radius, self.focus_distance)
+
+
+def _lens_arg(radius, focus_distance):
+    """(radius, focus_distance), a Lens, or None -> a pointer argument for pt_scene_set_lens / pt_frame_set_lens."""
+    if radius is None:
+        return None
+    if isinstance(radius, Lens):
+        return C.byref(radius)
+    if focus_distance is None:
+        raise TypeError("set_lens(radius, focus_distance): the focus distance is missing")
+    return C.byref(Lens(radius, focus_distance))
 
 
 def look_at(eye, target, up=(0.0, 1.0, 0.0), fov_y=REFERENCE_FOV_Y, aspect=0.0, library=None):
@@ -197,6 +222,9 @@ def load_library(path):
     L.pt_scene_set_camera.argtypes = [vp, C.POINTER(Camera)]
     L.pt_scene_get_camera.argtypes = [vp, C.POINTER(Camera), ip]
     L.pt_frame_set_camera.argtypes = [vp, C.POINTER(Camera)]
+    L.pt_scene_set_lens.argtypes = [vp, C.POINTER(Lens)]
+    L.pt_scene_get_lens.argtypes = [vp, C.POINTER(Lens), ip]
+    L.pt_frame_set_lens.argtypes = [vp, C.POINTER(Lens)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     return L
@@ -312,6 +340,17 @@ class Scene:
         cam, is_set = Camera(), C.c_int32()
         _check(self._L.pt_scene_get_camera(self._h, C.byref(cam), C.byref(is_set)), self._L)
         return cam if is_set.value else None
+
+    def set_lens(self, radius, focus_distance=None):
+        """pt_scene_set_lens: a thin lens of aperture `radius` focused at `focus_distance` (or a Lens); None or radius 0 = a
+        pinhole.  On a handle without a camera the lens applies to the reference camera."""
+        _check(self._L.pt_scene_set_lens(self._h, _lens_arg(radius, focus_distance)), self._L)
+
+    def lens(self):
+        """The handle's Lens, or None if it has none."""
+        lens, is_set = Lens(), C.c_int32()
+        _check(self._L.pt_scene_get_lens(self._h, C.byref(lens), C.byref(is_set)), self._L)
+        return lens if is_set.value else None
 
     def cull_tables(self, eps=1e-4):
         """The culling hierarchy for `eps` (diagnostics): dict of clusters, spheres, bary records, constants."""
@@ -468,6 +507,10 @@ class Frame:
         if camera is not None and not isinstance(camera, Camera):
             camera = Camera.of(*camera)
         _check(self._L.pt_frame_set_camera(self._h, C.byref(camera) if camera is not None else None), self._L)
+
+    def set_lens(self, radius, focus_distance=None):
+        """pt_frame_set_lens: the lens of every device's copy of the frame's scene (None = a pinhole)."""
+        _check(self._L.pt_frame_set_lens(self._h, _lens_arg(radius, focus_distance)), self._L)
 
     def band_kernel_ms(self):
         """Kernel time of every band of the last render(want_stats=True), -1 where there is none."""

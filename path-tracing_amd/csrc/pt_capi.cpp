@@ -159,8 +159,42 @@ int upload_vec(const std::vector<T> &v, T **dst) {
 // The cull hierarchy's radii and margins depend on eps (-EPS): upload on first use, replace if eps changes.
 // Callers hold scene->launch_mutex from here until their kernel has been enqueued: a concurrent render with another eps
 // must not free the tables between this call and that launch.
-// The camera's envelope radius for the cull tables (get_cull): 20 for the reference's camera at (0, 0, -20).
+const pt_camera kReferenceCamera = {{0.0f, 0.0f, -20.0f}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}};   // main.cpp:126-129
+
+// The camera primary rays are made from: the handle's, or the reference's fixed one.
+const pt_camera &view_camera(const pt_scene *s) { return s->has_camera ? s->camera : kReferenceCamera; }
+
+// r^, u^, f^ of a lens on camera c (pt_hip.h: pt_lens): right, up, forward normalised in double, rounded to float once.
+void lens_axes(const pt_camera &c, float out[9]) {
+    const float *v[3] = {c.right, c.up, c.forward};
+    for (int a = 0; a < 3; ++a) {
+        const double x = v[a][0], y = v[a][1], z = v[a][2];
+        const double n = std::sqrt(x * x + y * y + z * z);
+        for (int i = 0; i < 3; ++i) out[3 * a + i] = static_cast<float>(v[a][i] / n);
+    }
+}
+
+// Largest |component| an origin of lens l on camera c can have: max_i(|o_i| + radius sqrt(r^_i^2 + u^_i^2)), which bounds
+// |o_i + L_i| because |L_i| <= rho sqrt(cs^2 + sn^2) sqrt(r^_i^2 + u^_i^2) -- times 1 + 2^-18 for the rounding of rho, of the
+// sine and cosine, of the products and of the sums (a dozen half-ulps).  A component in which the disc does not extend
+// (r^_i = u^_i = 0: L_i is exactly 0) keeps |o_i| exactly, so a lens in front of the reference eye keeps its envelope.
+double lens_extent(const pt_camera &c, const pt_lens &l) {
+    float ax[9];
+    lens_axes(c, ax);
+    double e = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        const double lat = std::sqrt(static_cast<double>(ax[i]) * ax[i] + static_cast<double>(ax[3 + i]) * ax[3 + i]);
+        double ei = std::fabs(static_cast<double>(c.origin[i]));
+        if (lat > 0.0) ei = (ei + static_cast<double>(l.radius) * lat) * (1.0 + 0x1p-18);
+        e = std::max(e, ei);
+    }
+    return e;
+}
+
+// The envelope radius for the cull tables (get_cull): the largest |component| of every origin a primary ray can have -- 20 for
+// the reference's camera at (0, 0, -20).
 double camera_radius(const pt_scene *s) {
+    if (s->has_lens) return std::max(20.0, lens_extent(view_camera(s), s->lens));
     if (!s->has_camera) return 20.0;
     const float *o = s->camera.origin;
     return std::max({20.0, static_cast<double>(std::fabs(o[0])), static_cast<double>(std::fabs(o[1])), static_cast<double>(std::fabs(o[2]))});
@@ -253,9 +287,15 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
     a.emis_clusters = t.emis_clusters;
     a.emis_large_w0 = t.emis_large_w0;
     a.emis_bvh = t.emis_bvh ? 1u : 0u;
-    if (scene->has_camera) {   // the camera twins of the kernels (pt_kernels.hip: integrate_kernel<..., ADAPT | 1>)
+    if (scene->has_camera || scene->has_lens) {   // the camera twins of the kernels (pt_kernels.hip: integrate_kernel<..., ADAPT | 1>)
         a.camera = 1;
-        std::memcpy(a.cam, &scene->camera, sizeof a.cam);
+        std::memcpy(a.cam, &view_camera(scene), sizeof a.cam);
+    }
+    if (scene->has_lens) {   // their lens kernels (integrate_kernel_lens)
+        a.lens = 1;
+        a.lns[0] = scene->lens.radius;
+        a.lns[1] = scene->lens.focus_distance;
+        lens_axes(view_camera(scene), a.lns + 2);
     }
 }
 
@@ -591,6 +631,8 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->sky = src->sky;         // the skybox of the handle the copy is made from
     s->has_camera = src->has_camera;   // and its camera
     s->camera = src->camera;
+    s->has_lens = src->has_lens;       // and lens
+    s->lens = src->lens;
     if (device >= 0) {
         const int rc = upload(s.get(), device);
         if (rc != PT_OK) return rc;
@@ -702,10 +744,62 @@ static int camera_look_at_impl(const float eye[3], const float target[3], const 
     return PT_OK;
 }
 
+// Can lens l (radius > 0, focus distance > 0) be used with camera c?  D . f^ = u (right . f^) + v (up . f^) + |forward| with
+// |u|, |v| < 1 stays positive if |forward| > |right . f^| + |up . f^|; and every lens origin must lie within PT_CAMERA_MAX_ORIGIN.
+static int check_lens_on(const pt_camera &c, const pt_lens &l) {
+    double f[3], fl = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        f[i] = c.forward[i];
+        fl += f[i] * f[i];
+    }
+    fl = std::sqrt(fl);
+    double rf = 0.0, uf = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        rf += static_cast<double>(c.right[i]) * (f[i] / fl);
+        uf += static_cast<double>(c.up[i]) * (f[i] / fl);
+    }
+    if (!(fl > std::fabs(rf) + std::fabs(uf)))
+        return fail(PT_ERR_INVALID_ARGUMENT, "lens: the camera's view direction can reach the lens plane (|forward| <= |right . f| + |up . f|)");
+    if (!(lens_extent(c, l) <= PT_CAMERA_MAX_ORIGIN))
+        return fail(PT_ERR_UNSUPPORTED, "lens: an origin on the lens could lie beyond PT_CAMERA_MAX_ORIGIN (" + std::to_string(PT_CAMERA_MAX_ORIGIN) + ")");
+    return PT_OK;
+}
+
+// NULL or radius 0: back to the pinhole.  Checks everything before it changes anything.
+static int scene_set_lens_impl(pt_scene *scene, const pt_lens *lens) {
+    if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (lens) {
+        if (!std::isfinite(lens->radius) || !std::isfinite(lens->focus_distance)) return fail(PT_ERR_INVALID_ARGUMENT, "lens: non-finite value");
+        if (lens->radius < 0.0f) return fail(PT_ERR_INVALID_ARGUMENT, "lens: negative radius");
+    }
+    if (!lens || lens->radius == 0.0f) {
+        scene->has_lens = false;
+        scene->lens = pt_lens{};
+        return PT_OK;
+    }
+    if (!(lens->focus_distance > 0.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "lens: the focus distance must be positive");
+    const int rc = check_lens_on(view_camera(scene), *lens);
+    if (rc != PT_OK) return rc;
+    scene->lens = *lens;
+    scene->has_lens = true;
+    return PT_OK;
+}
+
+static int scene_get_lens_impl(const pt_scene *scene, pt_lens *lens, int32_t *is_set) {
+    if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (lens) *lens = scene->has_lens ? scene->lens : pt_lens{};
+    if (is_set) *is_set = scene->has_lens ? 1 : 0;
+    return PT_OK;
+}
+
 // NULL: back to the reference's camera.  Checks everything before it changes anything.
 static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
     if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
     if (!cam) {
+        if (scene->has_lens) {   // (the lens stays: it must fit the reference camera as well)
+            const int rc = check_lens_on(kReferenceCamera, scene->lens);
+            if (rc != PT_OK) return rc;
+        }
         scene->has_camera = false;
         scene->camera = pt_camera{};
         return PT_OK;
@@ -727,6 +821,10 @@ static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
         if (!(std::fabs(cam->origin[i]) <= PT_CAMERA_MAX_ORIGIN))
             return fail(PT_ERR_UNSUPPORTED, "camera: origin component beyond PT_CAMERA_MAX_ORIGIN (" + std::to_string(PT_CAMERA_MAX_ORIGIN) +
                                                 "): the culling margins are not derived that far out");
+    if (scene->has_lens) {
+        const int rc = check_lens_on(*cam, scene->lens);
+        if (rc != PT_OK) return rc;
+    }
     scene->camera = *cam;
     scene->has_camera = true;
     return PT_OK;
@@ -738,7 +836,7 @@ static int scene_get_camera_impl(const pt_scene *scene, pt_camera *cam, int32_t 
         if (scene->has_camera) {
             *cam = scene->camera;
         } else {   // the reference's fixed camera, main.cpp:126-129
-            *cam = pt_camera{{0.0f, 0.0f, -20.0f}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}};
+            *cam = kReferenceCamera;
         }
     }
     if (is_set) *is_set = scene->has_camera ? 1 : 0;
@@ -1167,6 +1265,18 @@ int pt_scene_set_camera(pt_scene *scene, const pt_camera *camera) {
 
 int pt_scene_get_camera(const pt_scene *scene, pt_camera *camera, int32_t *is_set) {
     return guarded([&] { return scene_get_camera_impl(scene, camera, is_set); });
+}
+
+int pt_scene_set_lens(pt_scene *scene, const pt_lens *lens) {
+    return guarded([&] {
+        if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+        std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);   // (a launch being enqueued reads the lens under it)
+        return scene_set_lens_impl(scene, lens);
+    });
+}
+
+int pt_scene_get_lens(const pt_scene *scene, pt_lens *lens, int32_t *is_set) {
+    return guarded([&] { return scene_get_lens_impl(scene, lens, is_set); });
 }
 
 int pt_render_device(pt_scene *scene, const pt_render_params *p, float *d_sum, float *d_sum2, int32_t *d_count, void *hip_stream, pt_render_stats *stats) {

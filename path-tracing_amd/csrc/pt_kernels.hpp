@@ -63,6 +63,10 @@ struct RenderArgs {
     // launch runs the camera twins (integrate_kernel<..., ADAPT | 1>), which read cam = origin[3], right[3], up[3], forward[3].
     int32_t camera;
     float cam[12];
+    // The handle's lens (pt_hip.h: pt_lens), appended likewise.  lens != 0 (only with camera != 0): the launch runs the lens kernels
+    // (integrate_kernel_lens), which read lns = radius, focus distance, r^[3], u^[3], f^[3] (right, up, forward as unit vectors).
+    int32_t lens;
+    float lns[11];
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif

@@ -29,6 +29,9 @@
 // axes span -FOV, the reference's mapping).  Without any of them no camera is set and the reference's view is rendered as before;
 // with the defaults spelled out the camera is the reference's and the image is the same.  PT_RENDER_PRINT_CAMERA=1 prints the
 // camera the flags resolve to ("camera none" without one) and exits.
+// A thin lens (pt_scene_set_lens, not in the reference): -APERTURE <radius> (default 0: no lens, a pinhole), -FOCUS <distance of
+// the focal plane> (default |LOOKAT - EYE|, 20 for the reference's camera).  PT_RENDER_PRINT_CAMERA=1 then also prints
+// "lens <radius> <focus distance>".
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -59,6 +62,8 @@ struct Options {   // defaults: config.h:16-29
     bool camera = false;   // any of -EYE / -LOOKAT / -UP / -FOV / -ASPECT given
     std::string eye = "0,0,-20", lookat = "0,0,0", up = "0,1,0";
     float fov = 53.13010235415598f, aspect = 0.0f;
+    std::string aperture, focus;   // -APERTURE / -FOCUS as given
+    bool aperture_given = false, focus_given = false;
 };
 
 long long now_ms() {
@@ -102,6 +107,8 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-UP") { o.up = v; o.camera = true; }
         if (f == "-FOV") { o.fov = static_cast<float>(std::atof(v)); o.camera = true; }
         if (f == "-ASPECT") { o.aspect = static_cast<float>(std::atof(v)); o.camera = true; }
+        if (f == "-APERTURE") { o.aperture = v; o.aperture_given = true; }
+        if (f == "-FOCUS") { o.focus = v; o.focus_given = true; }
     }
 }
 
@@ -116,6 +123,13 @@ bool parse_vec3(const std::string &text, float out[3]) {
         p = end + 1;
     }
     return true;
+}
+
+// one finite number, nothing else
+bool parse_float(const std::string &text, float &out) {
+    char *end = nullptr;
+    out = std::strtof(text.c_str(), &end);
+    return end != text.c_str() && *end == '\0' && std::isfinite(out);
 }
 
 int die(const char *what) {
@@ -147,6 +161,27 @@ int main(int argc, char **argv) {
         }
         if (pt_camera_look_at(eye, at, up, o.fov, o.aspect, &camera) != PT_OK) return die("pt_render");
     }
+    pt_lens lens{0.0f, 0.0f};
+    if (o.aperture_given && !(parse_float(o.aperture, lens.radius) && lens.radius >= 0.0f)) {
+        std::cerr << "pt_render: -APERTURE takes a radius >= 0" << std::endl;
+        return 2;
+    }
+    if (o.focus_given) {
+        if (!(parse_float(o.focus, lens.focus_distance) && lens.focus_distance > 0.0f)) {
+            std::cerr << "pt_render: -FOCUS takes a distance > 0" << std::endl;
+            return 2;
+        }
+    } else {   // the distance from the eye to the point looked at: 20 for the reference's camera
+        float eye[3] = {0.0f, 0.0f, -20.0f}, at[3] = {0.0f, 0.0f, 0.0f};
+        if (o.camera) {
+            parse_vec3(o.eye, eye);
+            parse_vec3(o.lookat, at);
+        }
+        double d2 = 0.0;
+        for (int i = 0; i < 3; ++i) d2 += (static_cast<double>(at[i]) - eye[i]) * (static_cast<double>(at[i]) - eye[i]);
+        lens.focus_distance = static_cast<float>(std::sqrt(d2));
+    }
+    const bool has_lens = lens.radius > 0.0f;
     if (std::getenv("PT_RENDER_PRINT_CAMERA")) {
         if (!o.camera) {
             std::printf("camera none\n");
@@ -157,6 +192,7 @@ int main(int argc, char **argv) {
                 std::printf("%s %.9g %.9g %.9g\n", names[r], static_cast<double>(rows[r][0]), static_cast<double>(rows[r][1]),
                             static_cast<double>(rows[r][2]));
         }
+        if (has_lens) std::printf("lens %.9g %.9g\n", static_cast<double>(lens.radius), static_cast<double>(lens.focus_distance));
         return 0;
     }
     if (o.width <= 0 || o.height <= 0) {
@@ -179,6 +215,7 @@ int main(int argc, char **argv) {
     if (pt_scene_load_obj(o.model_path.c_str(), o.model_name.c_str(), -1, &scene) != PT_OK) return die("pt_render");
     if (!o.skybox.empty() && pt_scene_set_skybox_bmp(scene, o.skybox.c_str()) != PT_OK) return die("pt_render");   // scene.cpp:20-22
     if (o.camera && pt_scene_set_camera(scene, &camera) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
+    if (has_lens && pt_scene_set_lens(scene, &lens) != PT_OK) return die("pt_render");         // and its lens
     const clk::time_point t_parse = clk::now();
     const int n_dev = pt_device_count();   // first HIP call: runtime start-up
     if (n_dev < 1) {
