@@ -322,6 +322,85 @@ int pt_rccl_available(int32_t *version);
 int pt_trace_rays_host(pt_scene *scene, int32_t n_rays, const float *origins, const float *directions, float eps,
                        int32_t *hit_index, float *hit_t);
 
+/* ---- first-hit feature buffers ---------------------------------------------------------------------- */
+
+/* What the camera sees first in every pixel: triangle, distance, position, normal, albedo -- the buffers picking, compositing and
+ * a denoiser need.  HOST buffers for rows [row_begin, row_end) of the image (pixel p as above; hit_index / hit_t 1 value per
+ * pixel, the others 3 floats); any output pointer may be NULL.  Of `params` width, height, row_begin, row_end, eps and
+ * row_stride are used (row_stride 0 / 1 only; n > 1 is PT_ERR_UNSUPPORTED), the pass, seed and other fields are ignored.
+ * Pixel (x, y) of a W x H image gets the ray pt_camera states with jitter 0:
+ *   u = x / W - 0.5,  v = -y / H + 0.5                          (in double, then rounded to float)
+ *   d = normalize((u * right + v * up) + forward)               (componentwise in float, nothing fused; d * (1 / sqrt((x x + y y) + z z)))
+ * from `origin`, with the handle's camera or, without one, the reference's.  The handle's LENS IS IGNORED: features are those
+ * of the pinhole view and stay sharp.  Then
+ *   hit_index, hit_t = what pt_trace_rays_host answers for that ray (-1 / +inf on a miss; its known deviation applies)
+ *   position         = origin + d * hit_t                       (componentwise in float: one product, one sum)
+ *   normal           = the hit triangle's stored plane normal (Triangle::GetNormal, triangles.h: plane_[0..2]; NOT flipped
+ *                      towards the viewer)
+ *   albedo           = Kd of the hit triangle's material (emitters included: the reference multiplies by Kd there too)
+ * and a miss writes zeros to position, normal and albedo. */
+int pt_render_features_host(pt_scene *scene, const pt_render_params *params, int32_t *hit_index, float *hit_t, float *position,
+                            float *normal, float *albedo);
+
+/* ---- feature-guided denoiser ------------------------------------------------------------------------ */
+
+/* An edge-avoiding a-trous wavelet filter (the spatial half of SVGF, no temporal reuse) on the LINEAR per-pixel mean, guided by
+ * the feature buffers above and by the sample variance the accumulators carry.  The chain of a denoised image is
+ *   pt_denoise_host -> pt_tonemap -> pt_post_filter_host (optional) -> pt_quantize,  the last three with count_out.
+ * All buffers are HOST buffers of the whole width x height image; the kernels run on HIP device `device`.  kernel_ms (may be
+ * NULL) = HIP-event time of the kernel chain.  count_out (may be NULL): count, except that a pixel without samples which the
+ * filter filled from its neighbours gets 1 -- the count to tone-map and quantize the result with.
+ *
+ * Parameters; a zeroed struct holds the defaults, except that `levels` says how much is filtered:
+ *   levels              a-trous passes, 0 .. 8; 0 = no filtering: mean_rgb = sum / n (sum where n = 0), count_out = count, no
+ *                       device and no feature buffer is needed (they may be NULL)
+ *   sigma_luminance     s_l; 0 = 4;    sigma_plane  s_p, in scene units; 0 = 0.1    (negative or non-finite: invalid)
+ *   normal_power_log2   k; 0 = 7; at most 16    (negative: invalid)
+ *   demodulate_albedo   0 or positive = filter radiance divided by the albedo; negative = filter radiance itself
+ *
+ * The arithmetic, exactly: every operation below is ONE correctly rounded float operation in the order written (+ - * / sqrt,
+ * comparisons; nothing fused, no exp / pow / reciprocal approximations), sums run over taps in row-major order (dy outer, dx
+ * inner), a tap outside the image is skipped.  lum(c) = (0.2126 c_r + 0.7152 c_g) + 0.0722 c_b.  pos(t) = t > 0 ? t : 0.
+ * A pixel has SAMPLES if n = count > 0, is a HIT if hit_index >= 0 (else a miss: it saw the sky), and two pixels are of one
+ * CLASS if both are hits or both are misses.
+ * 1. Per pixel and channel: m = sum / n;  a = max(albedo, 0.01) if demodulating and a hit (albedo > 0.01 ? albedo : 0.01), else 1;
+ *    c = m / a;  v = (pos(sum2 / n - m * m) / n) / (a * a);  var = lum(v).  A pixel without samples has no data: c = 0, var < 0.
+ * 2. Feature weight of a tap q for the centre p, f(p, q) = (w_n) * w_p if p is a hit, 1 if it is a miss:
+ *      w_n = pos((N_p.x N_q.x + N_p.y N_q.y) + N_p.z N_q.z), squared k times;    e = P_q - P_p;
+ *      w_p = 1 / (1 + u * u),  u = |(N_p.x e.x + N_p.y e.y) + N_p.z e.z| / s_p    (distance from the centre's tangent plane)
+ * 3. Variance estimate, for every pixel p with samples, over the 7 x 7 window around it (the centre included), using the taps
+ *    q of p's class that have samples:  inner 3 x 3 taps, b = (1/4, 1/2, 1/4)_dy * (1/4, 1/2, 1/4)_dx:  G += b * var_q, Gw += b;
+ *    all taps, w = 1 * f(p, q), l = lum(c_q):  Mw += w, M1 += w * l, M2 += w * (l * l).   g = G / Gw,  mu = M1 / Mw,
+ *    sp = pos(M2 / Mw - mu * mu);   var_p = g if n >= 4, else (g > sp ? g : sp)   (few samples say little about their own
+ *    variance -- one sample nothing --, so such a pixel takes at least the spatial variance of its surroundings).
+ * 4. Level i = 0 .. levels - 1, spacing 2^i, from the colours and variances of the previous level, for EVERY pixel p:
+ *      l_p = lum(c_p);  den = s_l * sqrt(var_p) + 1e-6;  h = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *      with data (var_p >= 0): W = 9/64, V = (9/64 * 9/64) * var_p;  without: W = 0, V = 0, var_p read as 0;   S = (0, 0, 0)
+ *      for the 24 taps q = p + 2^i (dx, dy) other than the centre that have data and are of p's class:
+ *        w = (h_dy * h_dx);  if p is a hit: w = (w * w_n) * w_p;  if p has data: t = (l_p - lum(c_q)) / den, w = w * (1 / (1 + t * t))
+ *        W += w;  S += w * (c_q - c_p);  V += (w * w) * var_q
+ *      if W > 1e-4:  c_p' = c_p + S / W,  var_p' = V / (W * W)  (a pixel without data has data from here on: it is FILLED);
+ *      else p is left as it is.
+ * 5. mean_rgb = pos(m + a * (c - c_0)) for a pixel with samples (c_0 = its c of step 1: what the filter did not change comes
+ *    back exactly), pos(a * c) for a filled pixel, sum for a pixel that has neither samples nor data. */
+typedef struct pt_denoise_params {
+    int32_t levels;
+    float sigma_luminance, sigma_plane;
+    int32_t normal_power_log2;
+    int32_t demodulate_albedo;
+} pt_denoise_params;
+#define PT_DENOISE_MAX_LEVELS 8
+/* PT_ERR_INVALID_ARGUMENT: a NULL buffer (sum, sum2, count, params, mean_rgb; the feature buffers if levels > 0), an empty image,
+ * a parameter outside what is stated above.  PT_ERR_NO_DEVICE: levels > 0 and `device` is not a usable HIP device (there is no
+ * CPU fallback). */
+int pt_denoise_host(int device, int32_t width, int32_t height, const float *sum, const float *sum2, const int32_t *count,
+                    const float *position, const float *normal, const float *albedo, const int32_t *hit_index,
+                    const pt_denoise_params *params, float *mean_rgb, int32_t *count_out, float *kernel_ms);
+
+/* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
+ * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
+int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);
+
 /* ---- resolve + image output (host side, as in the reference) --------------------------------------- */
 
 /* main.cpp:162-201: per-pixel mean, gamma tonemap *255, float->uint8 truncation (bitmap_image.hpp:194-206),

@@ -39,7 +39,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_frame_clear", "pt_frame_destroy", "pt_frame_band_kernel_ms", "pt_scene_skybox_size", "pt_table_limits_check_tree",
                "pt_band_rows", "pt_session_create_strided", "pt_frame_row_stride",
                "pt_camera_look_at", "pt_scene_set_camera", "pt_scene_get_camera", "pt_frame_set_camera",
-               "pt_scene_set_lens", "pt_scene_get_lens", "pt_frame_set_lens"]
+               "pt_scene_set_lens", "pt_scene_get_lens", "pt_frame_set_lens",
+               "pt_render_features_host", "pt_denoise_host", "pt_tonemap"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -103,6 +104,15 @@ class Lens(C.Structure):
 
     def __repr__(self):
         return "Lens(radius=%r, focus_distance=%r)" % (self.radius, self.focus_distance)
+
+
+class DenoiseParams(C.Structure):
+    """pt_denoise_params: a zeroed struct holds the defaults, except that `levels` says how much is filtered (0 = nothing)."""
+    _fields_ = [("levels", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float), ("normal_power_log2", C.c_int32),
+                ("demodulate_albedo", C.c_int32)]
+
+
+DENOISE_MAX_LEVELS = 8
 
 
 def _lens_arg(radius, focus_distance):
@@ -225,6 +235,9 @@ def load_library(path):
     L.pt_scene_set_lens.argtypes = [vp, C.POINTER(Lens)]
     L.pt_scene_get_lens.argtypes = [vp, C.POINTER(Lens), ip]
     L.pt_frame_set_lens.argtypes = [vp, C.POINTER(Lens)]
+    L.pt_render_features_host.argtypes = [vp, C.POINTER(RenderParams), ip, fp, fp, fp, fp]
+    L.pt_denoise_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, fp, ip, fp, fp, fp, ip, C.POINTER(DenoiseParams), fp, ip, fp]
+    L.pt_tonemap.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, fp]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     return L
@@ -386,6 +399,18 @@ class Scene:
         t = np.zeros(len(o), np.float32)
         _check(self._L.pt_trace_rays_host(self._h, len(o), _fp(o), _fp(d), eps, _ip(idx), _fp(t)), self._L)
         return idx, t
+
+    def render_features(self, width, height, rows=None, eps=1e-4, row_stride=0):
+        """pt_render_features_host: what the camera sees first in every pixel of rows [r0, r1) -- dict of hit_index [n] (-1 = a miss),
+        hit_t [n] (+inf), position / normal / albedo [n, 3] (zeros).  The lens is ignored."""
+        r0, r1 = rows if rows is not None else (0, height)
+        p = RenderParams(width, height, r0, r1, 0, 0, 0, eps, -1.0, 0, 0, row_stride)
+        n = max(0, r1 - r0) * max(0, width)
+        out = {"hit_index": np.full(n, -2, np.int32), "hit_t": np.zeros(n, np.float32), "position": np.zeros((n, 3), np.float32),
+               "normal": np.zeros((n, 3), np.float32), "albedo": np.zeros((n, 3), np.float32)}
+        _check(self._L.pt_render_features_host(self._h, C.byref(p), _ip(out["hit_index"]), _fp(out["hit_t"]), _fp(out["position"]),
+                                               _fp(out["normal"]), _fp(out["albedo"])), self._L)
+        return out
 
     def render_device(self, params, d_sum, d_sum2, d_count, stream=None, want_stats=False):
         """d_* are raw device pointers (ints), e.g. torch tensors' data_ptr(); stream is a hipStream_t value."""
@@ -576,6 +601,41 @@ def resolve_float(width, height, s, s2, c, gamma=None):
     _check(lib().pt_resolve_float(width, height, _fp(np.ascontiguousarray(s, np.float32)), _fp(np.ascontiguousarray(s2, np.float32)),
                                   _ip(np.ascontiguousarray(c, np.int32)), C.c_float(gamma), _fp(rgb), _fp(disp)))
     return rgb, disp
+
+
+def denoise(width, height, s, s2, c, features=None, *, levels=5, sigma_luminance=0.0, sigma_plane=0.0, normal_power_log2=0,
+            demodulate_albedo=0, device=0, want_ms=False):
+    """pt_denoise_host: the feature-guided a-trous filter on the linear mean of a whole frame's accumulators.  `features` is what
+    Scene.render_features returns (not needed for levels = 0).  Returns (mean_rgb float32 [H * W, 3], count_out int32 [H * W]) -- the
+    count to tone-map and quantize with --, and the kernel chain's milliseconds as a third value if want_ms."""
+    n = width * height
+    s, s2 = np.ascontiguousarray(s, np.float32), np.ascontiguousarray(s2, np.float32)
+    c = np.ascontiguousarray(c, np.int32)
+    if s.size != 3 * n or s2.size != 3 * n or c.size != n:
+        raise ValueError("denoise: the accumulators do not hold width x height pixels")
+    f = {}
+    for k, dt, m in (("position", np.float32, 3), ("normal", np.float32, 3), ("albedo", np.float32, 3), ("hit_index", np.int32, 1)):
+        f[k] = None if features is None else np.ascontiguousarray(features[k], dt)
+        if f[k] is not None and f[k].size != m * n:
+            raise ValueError(f"denoise: features[{k!r}] does not hold width x height pixels")
+    ptr = lambda a, fn: fn(a) if a is not None else None
+    prm = DenoiseParams(levels, sigma_luminance, sigma_plane, normal_power_log2, demodulate_albedo)
+    mean, cout, ms = np.zeros((n, 3), np.float32), np.zeros(n, np.int32), C.c_float()
+    _check(lib().pt_denoise_host(device, width, height, _fp(s), _fp(s2), _ip(c), ptr(f["position"], _fp), ptr(f["normal"], _fp),
+                                 ptr(f["albedo"], _fp), ptr(f["hit_index"], _ip), C.byref(prm), _fp(mean), _ip(cout), C.byref(ms)))
+    return (mean, cout, ms.value) if want_ms else (mean, cout)
+
+
+def tonemap(width, height, mean_rgb, c, gamma=None):
+    """pt_tonemap (main.cpp:179-182): rgb float32 [H, W, 3] = pow(mean, gamma) * 255 where c != 0, the mean's own value elsewhere."""
+    if gamma is None:
+        gamma = np.float32(1) / np.float32(2.2)
+    m, c = np.ascontiguousarray(mean_rgb, np.float32), np.ascontiguousarray(c, np.int32)
+    if m.size != 3 * width * height or c.size != width * height:
+        raise ValueError("tonemap: the buffers do not hold width x height pixels")
+    rgb = np.zeros((height, width, 3), np.float32)
+    _check(lib().pt_tonemap(width, height, _fp(m), _ip(c), C.c_float(gamma), _fp(rgb)))
+    return rgb
 
 
 def post_filter(rgb, gauss=0, median=0, device=0):

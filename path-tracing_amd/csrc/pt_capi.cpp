@@ -535,6 +535,15 @@ int session_enqueue(pt_session *s, const pt_render_params *p, bool want_stats) {
     return enqueue_render(s->scene, s->ctx, p, s->d_sum, s->d_sum2, s->d_count, s->stream, want_stats);
 }
 
+const pt_camera &view_camera(const pt_scene *s) { return ::view_camera(s); }
+
+int scene_trace_args(pt_scene *scene, float eps, pt::RenderArgs &a) {
+    const int rc = ensure_cull(scene, eps);
+    if (rc != PT_OK) return rc;
+    fill_scene_args(scene, eps, a);
+    return PT_OK;
+}
+
 int session_collect(pt_session *s, pt_render_stats *stats) {
     if (!s || !stats) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     return collect_stats(s->scene, s->ctx, s->stream, stats);
@@ -1188,6 +1197,15 @@ static int post_filter_host_impl(int device, int32_t width, int32_t height, floa
     if (d_b) (void)hipFree(d_b);
     if (d_w) (void)hipFree(d_w);
     return result;
+}
+
+int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb) {
+    if (width <= 0 || height <= 0 || !mean_rgb || !count || !rgb) return fail(PT_ERR_INVALID_ARGUMENT, "null buffer or empty image");
+    const size_t n = static_cast<size_t>(width) * height;
+    for (size_t p = 0; p < n; ++p)
+        for (int k = 0; k < 3; ++k)   // main.cpp:179-182
+            rgb[3 * p + k] = count[p] ? std::pow(mean_rgb[3 * p + k], gamma) * 255.0f : mean_rgb[3 * p + k];
+    return PT_OK;
 }
 
 int pt_quantize(int32_t width, int32_t height, const float *rgb, const int32_t *count, uint8_t *bgr) {

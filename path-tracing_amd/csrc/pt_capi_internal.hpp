@@ -136,5 +136,10 @@ int32_t band_rows(const pt_render_params *p);
 int session_enqueue(pt_session *s, const pt_render_params *p, bool want_stats);
 int session_collect(pt_session *s, pt_render_stats *stats);
 void ctx_destroy(LaunchCtx &c);
+// The camera primary rays are made from: the handle's, or the reference's fixed one.
+const pt_camera &view_camera(const pt_scene *s);
+// The scene part of the kernel arguments for `eps` (uploads the culling hierarchy on first use).  The scene's device is
+// current and the caller holds scene->launch_mutex until its kernels are enqueued.
+int scene_trace_args(pt_scene *scene, float eps, pt::RenderArgs &a);
 
 }  // namespace ptc

@@ -32,6 +32,11 @@
 // A thin lens (pt_scene_set_lens, not in the reference): -APERTURE <radius> (default 0: no lens, a pinhole), -FOCUS <distance of
 // the focal plane> (default |LOOKAT - EYE|, 20 for the reference's camera).  PT_RENDER_PRINT_CAMERA=1 then also prints
 // "lens <radius> <focus distance>".
+// The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
+// image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
+// plane-distance widths (default 0: the library's).  The order is resolve (so the dispersion numbers and the file name are those
+// of the undenoised frame) -> feature buffers -> denoise -> tone map -> -GAUSS / -MEDIAN -> quantize -> BMP, on the first device
+// of the frame.  Previews (-UPDATE) stay undenoised.  Without the flag nothing changes.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -64,6 +69,8 @@ struct Options {   // defaults: config.h:16-29
     float fov = 53.13010235415598f, aspect = 0.0f;
     std::string aperture, focus;   // -APERTURE / -FOCUS as given
     bool aperture_given = false, focus_given = false;
+    int denoise = 0;               // -DENOISE: a-trous levels, 0 = off
+    float dn_sigma_l = 0.0f, dn_sigma_p = 0.0f;
 };
 
 long long now_ms() {
@@ -109,6 +116,9 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-ASPECT") { o.aspect = static_cast<float>(std::atof(v)); o.camera = true; }
         if (f == "-APERTURE") { o.aperture = v; o.aperture_given = true; }
         if (f == "-FOCUS") { o.focus = v; o.focus_given = true; }
+        if (f == "-DENOISE") o.denoise = std::atoi(v);
+        if (f == "-DN_SIGMA_L") o.dn_sigma_l = static_cast<float>(std::atof(v));
+        if (f == "-DN_SIGMA_P") o.dn_sigma_p = static_cast<float>(std::atof(v));
     }
 }
 
@@ -398,7 +408,33 @@ int main(int argc, char **argv) {
     if (read_back() != PT_OK) return die("pt_render");
     const clk::time_point t_render = clk::now();
 
-    if (o.gauss || o.median) {   // main.cpp:187-201: filters act on the tonemapped float image, then set_pixel
+    double features_s = 0, denoise_s = 0;
+    float denoise_kernel_ms = 0;
+    if (o.denoise > 0) {
+        // the statistics of the frame as rendered; then the first hits of the pinhole view on the frame's first device, the
+        // denoiser on the linear mean, the tone map, the reference's filters and set_pixel
+        std::vector<float> rgb(3 * px), mean(3 * px), pos(3 * px), nrm(3 * px), alb(3 * px);
+        std::vector<int32_t> hit(px), count_out(px);
+        pt_resolve_float(o.width, o.height, sum, sum2, count, o.gamma_correction, rgb.data(), disp);
+        const clk::time_point f0 = clk::now();
+        pt_scene *view = nullptr;
+        if (pt_scene_clone_to_device(scene, devices[0], &view) != PT_OK) return die("pt_render");
+        const int frc = pt_render_features_host(view, &rp, hit.data(), nullptr, pos.data(), nrm.data(), alb.data());
+        pt_scene_destroy(view);
+        if (frc != PT_OK) return die("pt_render");
+        const clk::time_point f1 = clk::now();
+        pt_denoise_params dp;
+        std::memset(&dp, 0, sizeof dp);
+        dp.levels = o.denoise; dp.sigma_luminance = o.dn_sigma_l; dp.sigma_plane = o.dn_sigma_p;
+        if (pt_denoise_host(devices[0], o.width, o.height, sum, sum2, count, pos.data(), nrm.data(), alb.data(), hit.data(), &dp,
+                            mean.data(), count_out.data(), &denoise_kernel_ms) != PT_OK)
+            return die("pt_render");
+        features_s = secs(f0, f1);
+        denoise_s = secs(f1, clk::now());
+        pt_tonemap(o.width, o.height, mean.data(), count_out.data(), o.gamma_correction, rgb.data());
+        if ((o.gauss || o.median) && pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+        pt_quantize(o.width, o.height, rgb.data(), count_out.data(), bgr.data());
+    } else if (o.gauss || o.median) {   // main.cpp:187-201: filters act on the tonemapped float image, then set_pixel
         std::vector<float> rgb(3 * px);
         pt_resolve_float(o.width, o.height, sum, sum2, count, o.gamma_correction, rgb.data(), disp);
         if (pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
@@ -429,10 +465,12 @@ int main(int argc, char **argv) {
         pt_scene_timings(scene, host_s);
         std::fprintf(stderr, "{\"pre_main_s\": %.4f, \"parse_s\": %.4f, \"hip_startup_s\": %.4f, \"frame_setup_s\": %.4f, \"host_alloc_s\": %.4f, "
                              "\"enqueue_s\": %.4f, \"hierarchy_build_s\": %.4f, \"kernels_wait_s\": %.4f, \"read_back_s\": %.4f, \"previews_s\": %.4f, "
-                             "\"resolve_s\": %.4f, \"bmp_write_s\": %.4f, \"main_s\": %.4f, \"bands\": %zu, \"transport\": \"%s\"}\n",
+                             "\"resolve_s\": %.4f, \"bmp_write_s\": %.4f, \"main_s\": %.4f, \"bands\": %zu, \"transport\": \"%s\", "
+                             "\"features_s\": %.4f, \"denoise_s\": %.4f, \"denoise_kernel_ms\": %.3f}\n",
                      pre_main_s, secs(t_begin, t_parse), secs(t_parse, t_hip), secs(t_hip, t_load), alloc_in_wait,
                      secs(t_load, t_enqueued) - preview_s, host_s[1], secs(t_enqueued, t_kernels) - alloc_in_wait, secs(t_kernels, t_render), preview_s,
-                     secs(t_render, t_resolve), secs(t_resolve, t_end), secs(t_begin, t_end), devices.size(), transport_name);
+                     secs(t_render, t_resolve), secs(t_resolve, t_end), secs(t_begin, t_end), devices.size(), transport_name, features_s, denoise_s,
+                     static_cast<double>(denoise_kernel_ms));
     }
     if (o.fast_exit) {
         // Every file is written and closed; tearing the HIP runtime down (code objects, device heap, RCCL) is all that a normal
