@@ -13,12 +13,8 @@
 
 #include "pt_filters.hpp"
 
-#ifdef PT_TEST_HOOKS
-static int g_items_per_slot = 0;
-static int g_force_tile_width = 0;   // 1 = always 8 x 8 tiles, 2 = always 16 x 8 where the instantiation has them, 3 = the same and 32 x 8 for adaptive launches, 0 = by tile count
-static int g_regen_min_dead = 0;     // test build: overrides RenderArgs::regen_min_dead (0 = the library's)
-static int g_chunk_min = 0;          // test build: passes the scheduler's last geometric chunk holds at least (0 = the library's)
-#endif
+// Overrides of the launch plan: set by pt_test_set_mutation in the test builds, never in the product (which has no such entry point).
+static pt::plan::Overrides g_plan_overrides;
 
 namespace ptc {
 
@@ -324,10 +320,8 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, f
     a.width = p->width; a.height = p->height; a.row_begin = p->row_begin; a.row_end = p->row_end;
     a.row_stride = std::max(1, p->row_stride);
     a.band_rows = ptc::band_rows(p);
-    a.regen_min_dead = pt::regen_min_dead_for(p->max_ray_reflections);
-#ifdef PT_TEST_HOOKS
-    if (g_regen_min_dead > 0) a.regen_min_dead = static_cast<uint32_t>(g_regen_min_dead);
-#endif
+    const pt::plan::Overrides &ov = g_plan_overrides;
+    a.regen_min_dead = ov.regen_min_dead > 0 ? static_cast<uint32_t>(ov.regen_min_dead) : pt::regen_min_dead_for(p->max_ray_reflections);
     a.pass_begin = p->pass_begin; a.pass_count = p->pass_count; a.mrr = p->max_ray_reflections;
     a.error = p->error; a.seed = p->seed;
     if (p->row_end == p->row_begin) return PT_OK;
@@ -337,59 +331,18 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, f
         if ((rc = ctx_stats_ready(ctx)) != PT_OK) return rc;
         a.stats = ctx.d_stats;
     }
-    // one wave = one tile of 8 rows; how many pixels wide depends on the instantiation this launch runs
-#ifdef PT_TEST_HOOKS
-    pt::integrator_plan_tiles(a, scene->cu_count, g_force_tile_width);
-#else
-    pt::integrator_plan_tiles(a, scene->cu_count);
-#endif
-    const uint32_t n_tiles = a.n_tiles;
-    // Scheduler: cut the pass range into chunks so that the tail of the launch is balanced with small work items.  A tile's
-    // chunks run in order and each re-reads and re-writes the tile's accumulators, so there should be few of them: chunk c
-    // takes 3/4 of the passes that are left, down to single passes (256 passes: 192 + 48 + 12 + 3 + 1; until round 4 the last
-    // chunk held 8 to 31 passes -- 192 + 48 + 16 -- and launches below 32 passes were one chunk: 16 passes at 1080p 5.26 -> 4.71 ms,
-    // 64 passes 18.81 -> 18.20, 256 passes 72.70 -> 72.08, profiles/r04_ab_logs.txt chunks2).
-    // Wave slots of the chip FOR THE INSTANTIATION THIS LAUNCH RUNS: its occupancy is the compiler's and the LDS budget's
-    // business, asked from the runtime once per instantiation instead of assumed.
+    // one wave = one tile of 8 rows; how many pixels wide depends on the kernel this launch runs
+    const pt::plan::Tiles tiles = pt::plan::plan_tiles({a.width, a.band_rows, a.sky != nullptr, a.big != 0, want_stats, a.may_leave_envelope != 0, a.error,
+                                                        a.pass_begin, a.pass_count, a.lens ? 2 : a.camera ? 1 : 0, scene->cu_count},
+                                                       pt::integrator_build(), ov);
+    a.narrow = tiles.narrow;
+    a.adapt_pool = tiles.adapt_pool;
+    a.blocks_x = tiles.blocks_x;
+    const uint32_t n_tiles = tiles.n_tiles;
     int waves_per_cu = 24;
-    PT_HIP_TRY(pt::integrator_waves_per_cu(a, &waves_per_cu));
+    PT_HIP_TRY(pt::integrator_waves_per_cu(tiles.variant, &waves_per_cu));
     const uint32_t slots = static_cast<uint32_t>(scene->cu_count) * static_cast<uint32_t>(std::max(1, waves_per_cu));
-    uint32_t n_chunks = 1;
-    int32_t chunk_passes = 0;
-    // (launches that fill a statistics block keep the old floor of 8: every work item ends with a dozen atomic adds to the same
-    // few words, and 65 000 more items cost the 16-pass 1080p frame 6.7 -> 11.2 ms)
-    // (and the regenerating kernels under a sky, where a chunk's end is a tail of idle lanes; the 8 x 8 kernel with its accumulators
-    // in LDS stops at 2: chunks2)
-    int chunk_min = (want_stats || a.sky != nullptr) ? 8 : a.narrow ? 2 : 1;
-#ifdef PT_TEST_HOOKS
-    if (g_chunk_min > 0) chunk_min = g_chunk_min;
-#endif
-    if (n_tiles >= slots / 2u)
-        while (n_chunks < 6u && (p->pass_count >> (2u * n_chunks)) >= chunk_min) ++n_chunks;
-    // Between about one and two tiles per wave slot the first of those chunks is too coarse -- all tiles' 3/4 of the passes: the
-    // chip runs one full round of them and a second one half empty.  There the pass range is cut into EQUAL chunks, 8 to 32
-    // work items per wave slot: Tor.obj 1366 x 768 x 256 spp 47.5 -> 40.2 ms, 960 x 540 25.7 -> 21.9 ms, and the 32 x 8 tiles of
-    // adaptive 1080p launches (1.58 per slot) 65.2 -> 55.8 ms; from 2.3 tiles per slot up the 3/4 scheme wins again; the open
-    // scene under a sky at 960 x 540 22.2 -> 20.1 ms (profiles/r04_ab_logs.txt, chunks1).
-    int items_per_slot = 0;
-    {
-        const unsigned long long t100 = 100ull * n_tiles;
-        if (a.sky != nullptr) {   // (regenerating kernels: a chunk's end is a tail of idle lanes, so fewer, longer chunks and a narrower range)
-            if (t100 >= 75ull * slots && t100 < 190ull * slots) items_per_slot = 8;
-        } else if (t100 >= 75ull * slots && t100 < 230ull * slots) {
-            items_per_slot = t100 < 120ull * slots ? 8 : t100 < 190ull * slots ? 16 : 32;
-        }
-    }
-#ifdef PT_TEST_HOOKS
-    if (g_items_per_slot != 0) items_per_slot = std::max(0, g_items_per_slot);   // scheduler tuning, test build only (< 0: never equal chunks)
-#endif
-    if (items_per_slot > 0) {   // equal chunks, about items_per_slot work items per wave slot
-        n_chunks = (static_cast<uint32_t>(items_per_slot) * slots + n_tiles - 1u) / n_tiles;
-        n_chunks = std::max(1u, std::min(n_chunks, static_cast<uint32_t>(std::max(1, p->pass_count / 4))));
-        chunk_passes = std::max(1, (p->pass_count + static_cast<int32_t>(n_chunks) - 1) / static_cast<int32_t>(n_chunks));
-        n_chunks = static_cast<uint32_t>(std::max(1, (p->pass_count + chunk_passes - 1) / chunk_passes));
-        if (n_chunks == 1u) chunk_passes = 0;
-    }
+    const auto [n_chunks, chunk_passes] = pt::plan::plan_chunks(n_tiles, slots, p->pass_count, a.sky != nullptr, a.narrow != 0, want_stats, ov);
     if (static_cast<unsigned long long>(n_tiles) * n_chunks > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "too many work items");
     if (ctx.has_prev && ctx.prev_stream != stream) PT_HIP_TRY(hipStreamWaitEvent(stream, ctx.ev_done, 0));
     if (ctx.sched_words < 1 + static_cast<size_t>(n_tiles)) {
@@ -409,7 +362,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, f
         PT_HIP_TRY(hipMemsetAsync(ctx.d_stats, 0, 24 * sizeof(unsigned long long), stream));
         PT_HIP_TRY(hipEventRecord(ctx.ev0, stream));
     }
-    PT_HIP_TRY(pt::launch_integrator(a, stream));
+    PT_HIP_TRY(pt::launch_integrator(a, tiles.variant, stream));
     if (want_stats) PT_HIP_TRY(hipEventRecord(ctx.ev1, stream));
     PT_HIP_TRY(hipEventRecord(ctx.ev_done, stream));
     ctx.has_prev = true;
@@ -1401,9 +1354,9 @@ int pt_test_set_mutation(const char *family, double value) {
     if (!family) return PT_ERR_INVALID_ARGUMENT;
     const std::string f = family;
     pt::CullMutation &m = pt::g_cull_mutation;
-    if (f == "reset") { m = pt::CullMutation(); g_items_per_slot = 0; g_force_tile_width = 0; g_regen_min_dead = 0; g_chunk_min = 0; }
-    else if (f == "regen_min_dead") g_regen_min_dead = static_cast<int>(value);
-    else if (f == "chunk_min") g_chunk_min = static_cast<int>(value);
+    if (f == "reset") { m = pt::CullMutation(); g_plan_overrides = pt::plan::Overrides(); }
+    else if (f == "regen_min_dead") g_plan_overrides.regen_min_dead = static_cast<int>(value);
+    else if (f == "chunk_min") g_plan_overrides.chunk_min = static_cast<int>(value);
     else if (f == "sphere_r2") m.sphere_r2 = value;
     else if (f == "m0") m.m0 = value;
     else if (f == "k12") m.k12 = value;
@@ -1420,8 +1373,8 @@ int pt_test_set_mutation(const char *family, double value) {
     else if (f == "bvh_depth_cap") m.bvh_depth_cap = static_cast<int>(value);
     else if (f == "big_threshold") m.big_threshold = static_cast<int>(value);
     else if (f == "max_clusters") m.max_clusters = static_cast<int>(value);
-    else if (f == "items_per_slot") g_items_per_slot = static_cast<int>(value);
-    else if (f == "tile_width") g_force_tile_width = static_cast<int>(value);
+    else if (f == "items_per_slot") g_plan_overrides.items_per_slot = static_cast<int>(value);
+    else if (f == "tile_width") g_plan_overrides.tile_width = static_cast<int>(value);
     else return fail(PT_ERR_INVALID_ARGUMENT, "unknown mutation family " + f);
     return PT_OK;
 }

@@ -27,9 +27,11 @@
 // cannot reject a hit"; the verification build, -DPT_VERIFY_BRUTE, re-checks every segment against the all-triangles loop).
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <atomic>
 #include <cstddef>
 #include <type_traits>
+#include <utility>
 
 #include "pt_fastfp.hpp"
 #include "pt_kernels.hpp"
@@ -1490,9 +1492,23 @@ __device__ __forceinline__ LensView lens_view() {
     return reinterpret_cast<LensView>(p);
 }
 
+// What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
+// in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
+// gets; args.stats only receives the verdict.
+constexpr plan::Build kBuild = {kTileW, kTileH, PT_RAYS_PER_LANE, PT_BIG_RAYS_PER_LANE, PT_WAVES_PER_SIMD, kMaxBatchPass,
+#if defined(PT_BLOCK_PROFILE)
+                                plan::Stats::kAsAsked, true};
+#elif defined(PT_PHASE_TIMERS) || defined(PT_VERIFY_BRUTE)
+                                plan::Stats::kAlways, false};
+#elif defined(PT_VERIFY_SHIPPED) || defined(PT_ADAPT_COUNT)
+                                plan::Stats::kNever, false};
+#else
+                                plan::Stats::kAsAsked, false};
+#endif
+
 // rays per lane of an instantiation: the launch geometry (tile width) follows from it on the host as well
 template <bool SKY, bool BIG, bool STATS>
-constexpr int rays_per_lane() { return (!SKY && !STATS) ? (BIG ? PT_BIG_RAYS_PER_LANE : PT_RAYS_PER_LANE) : 1; }
+constexpr int rays_per_lane() { return plan::rays_per_lane(kBuild, SKY, BIG, STATS); }
 
 // NARROW = the statistics-free small-scene kernel with ONE pixel per lane (8 x 8 tiles): for launches with too few pixels to
 // fill the chip with 16 x 8 tiles (small previews, thin row bands) -- half as many waves would leave wave slots empty.
@@ -1505,7 +1521,8 @@ constexpr int integrator_waves() {
 // ADAPT = POOL | CAM.  POOL (bits 1-2) = the two-pixel kernel for launches with adaptive sampling on (error >= 0), with tiles of
 // 64 POOL pixels (2: 16 x 8, 4: 32 x 8): see "Batches" in the pass loop.  CAM (bit 0) = the camera twin: primary rays from the
 // scene handle's pt_camera (RenderArgs::cam) instead of the reference's fixed eye.  (One template argument for both, so that the
-// camera-free kernels keep their names: tests/test_kernel_resources.py pins them by mangled name.)
+// camera-free kernels keep their names: tests/test_kernel_resources.py pins them by mangled name.)  On the host a kernel is a
+// plan::Variant (pt_launch_plan.hpp): POOL = Variant::pool, CAM = Variant::view != 0; kernel_of below is the one place that maps them.
 // The body (pt_integrator_body.inc) is shared with integrate_kernel_lens TEXTUALLY, not through a device function: with the body
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
@@ -1616,13 +1633,13 @@ namespace pt {
 // Diagnostic build (libpt_blockprof.so): the integrator is launched from an INSTRUMENTED copy of this file's code object
 // (tools/asm_profile.py inserts an execution counter in front of every straight-line run of instructions of the compiler's
 // own assembly) and the counters are written to $PT_BLOCKPROF_OUT.<kernel> after every launch.  Never part of the product.
-hipError_t launch_integrator(const RenderArgs &args0, hipStream_t stream) {
+hipError_t launch_integrator(const RenderArgs &args0, const plan::Variant &v, hipStream_t stream) {
     constexpr size_t kCounters = 4096;
     static hipModule_t mod = nullptr;
     static uint32_t *d_cnt = nullptr;
     const int rows = args0.row_end - args0.row_begin;
     if (rows <= 0 || args0.width <= 0) return hipSuccess;
-    if (args0.lens) return hipErrorNotSupported;   // (the instrumented code object holds no lens kernel: refuse rather than run another)
+    if (!plan::variant_exists(v, kBuild)) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin or lens kernel: refuse rather than run another)
     if (!mod) {
         const char *path = std::getenv("PT_BLOCKPROF_HSACO");
         if (!path) return hipErrorInvalidValue;
@@ -1636,8 +1653,8 @@ hipError_t launch_integrator(const RenderArgs &args0, hipStream_t stream) {
     RenderArgs args = args0;
     args.blockprof = d_cnt;
     char name[128];
-    std::snprintf(name, sizeof name, "_ZN2pt16integrate_kernelILb%dELb%dELb%dELb%dELb0ELi%dEEEvNS_10RenderArgsE", args.sky ? 1 : 0,
-                  (args.big != 0) ? 1 : 0, args.stats ? 1 : 0, args.may_leave_envelope ? 1 : 0, args.camera ? 1 : 0);
+    std::snprintf(name, sizeof name, "_ZN2pt16integrate_kernelILb%dELb%dELb%dELb%dELb%dELi%dEEEvNS_10RenderArgsE", v.sky, v.big, v.stats, v.env, v.narrow,
+                  v.pool | v.view);
     hipFunction_t f;
     e = hipModuleGetFunction(&f, mod, name);
     if (e != hipSuccess) return e;
@@ -1658,188 +1675,70 @@ hipError_t launch_integrator(const RenderArgs &args0, hipStream_t stream) {
     }
     return hipSuccess;
 }
-hipError_t integrator_waves_per_cu(const RenderArgs &, int *waves) {
+hipError_t integrator_waves_per_cu(const plan::Variant &, int *waves) {
     *waves = 24;
     return hipSuccess;
 }
-void integrator_plan_tiles(RenderArgs &args, int, int) {   // (the instrumented code object holds the wide variant only)
-    const int rays = (!args.sky && !args.stats) ? ((args.big != 0) ? PT_BIG_RAYS_PER_LANE : PT_RAYS_PER_LANE) : 1;
-    args.narrow = 0;
-    args.adapt_pool = 0;
-    args.blocks_x = (args.width + kTileW * rays - 1) / (kTileW * rays);
-    args.n_tiles = static_cast<uint32_t>(args.blocks_x) * static_cast<uint32_t>((args.band_rows + kTileH - 1) / kTileH);
-}
 #else
 namespace {
-// statistics instantiation or not, for a launch with these arguments
-bool launch_with_stats(const RenderArgs &args) {
-#if defined(PT_PHASE_TIMERS) || defined(PT_VERIFY_BRUTE)
-    (void)args;
-    return true;
-#elif defined(PT_VERIFY_SHIPPED) || defined(PT_ADAPT_COUNT)
-    (void)args;
-    return false;   // the instantiations a caller without pt_render_stats gets; args.stats only receives the verdict
-#else
-    return args.stats != nullptr;
-#endif
+using Kernel = void (*)(const RenderArgs);
+// The kernel of variant I of this build, nullptr if the build has none: the one place where a plan::Variant becomes template arguments.
+template <int I>
+Kernel kernel_of() {
+    constexpr plan::Variant v = plan::variant_of(I);
+    if constexpr (!plan::variant_exists(v, kBuild)) return nullptr;
+    else if constexpr (v.view == 2) return &integrate_kernel_lens<v.sky, v.big, v.stats, v.env, v.narrow, v.pool | 1>;
+    else return &integrate_kernel<v.sky, v.big, v.stats, v.env, v.narrow, v.pool | v.view>;
 }
-// The integrator of variant C with template arguments S, B, T, E, N, P (P = POOL): C = 0 the camera-free kernel, 1 its camera
-// twin (ADAPT = P | 1), 2 the lens kernel of that twin.
-template <int C, bool S, bool B, bool T, bool E, bool N = false, int P = 0>
-auto integrator() {
-    if constexpr (C == 2) return &integrate_kernel_lens<S, B, T, E, N, P | 1>;
-    else return &integrate_kernel<S, B, T, E, N, P | C>;
-}
-// Calls f(kernel, id) with the instantiation a launch with these arguments runs (id: its index, 0 .. kInstantiations - 1).
-// A launch with a camera (RenderArgs::camera) runs the camera twin of the instantiation it would run without one: ADAPT | 1 (id + 24);
-// one with a lens as well (RenderArgs::lens) the lens kernel of that twin (id + 48).
-constexpr int kInstantiations = 72;
-template <class F>
-void with_instantiation(const RenderArgs &args, F &&f) {
-    const bool big = (args.big != 0);
-    const bool stats = launch_with_stats(args);
-    auto pick = [&](auto sky, auto bg, auto st, auto cm) {
-        constexpr bool S = decltype(sky)::value, B = decltype(bg)::value, T = decltype(st)::value;
-        constexpr int C = decltype(cm)::value;   // 0, 1: the camera twin (its id is 24 higher), 2: its lens kernel (48 higher)
-        if constexpr (!S && !T && rays_per_lane<S, B, T>() > 1) {
-            if (args.narrow) {
-                if (args.may_leave_envelope) f(integrator<C, false, B, false, true, true>(), 17 + 2 * B + 24 * C);
-                else f(integrator<C, false, B, false, false, true>(), 16 + 2 * B + 24 * C);
-                return;
-            }
-            if constexpr (!B) {
-                // adaptive sampling on: the instantiations that run batches (not built with the rare envelope test: one more
-                // spilled register there)
-                if (args.adapt_pool == 4) {
-                    f(integrator<C, false, false, false, false, false, 4>(), 21 + 24 * C);
-                    return;
-                }
-                if (args.adapt_pool == 2) {
-                    f(integrator<C, false, false, false, false, false, 2>(), 20 + 24 * C);
-                    return;
-                }
-            }
-        }
-        if constexpr (!S && !T && B) {   // the box-tree kernel with adaptive sampling on: batches over 16 x 8 / 32 x 8 tiles, one ray slot per lane
-            if (args.adapt_pool == 4) {
-                f(integrator<C, false, true, false, false, false, 4>(), 23 + 24 * C);
-                return;
-            }
-            if (args.adapt_pool == 2) {
-                f(integrator<C, false, true, false, false, false, 2>(), 22 + 24 * C);
-                return;
-            }
-        }
-        if (args.may_leave_envelope) f(integrator<C, S, B, T, true>(), ((S * 2 + B) * 2 + T) * 2 + 1 + 24 * C);
-        else f(integrator<C, S, B, T, false>(), ((S * 2 + B) * 2 + T) * 2 + 24 * C);
-    };
-    using Yes = std::true_type;
-    using No = std::false_type;
-    auto by_scene = [&](auto cm) {
-        if (stats) {
-            if (args.sky && big) pick(Yes(), Yes(), Yes(), cm);
-            else if (args.sky) pick(Yes(), No(), Yes(), cm);
-            else if (big) pick(No(), Yes(), Yes(), cm);
-            else pick(No(), No(), Yes(), cm);
-        } else {
-            if (args.sky && big) pick(Yes(), Yes(), No(), cm);
-            else if (args.sky) pick(Yes(), No(), No(), cm);
-            else if (big) pick(No(), Yes(), No(), cm);
-            else pick(No(), No(), No(), cm);
-        }
-    };
-    if (args.lens) by_scene(std::integral_constant<int, 2>());
-    else if (args.camera) by_scene(std::integral_constant<int, 1>());
-    else by_scene(std::integral_constant<int, 0>());
-}
+template <int... I>
+std::array<Kernel, sizeof...(I)> kernel_table(std::integer_sequence<int, I...>) { return {kernel_of<I>()...}; }
+const auto kKernels = kernel_table(std::make_integer_sequence<int, plan::kVariants>());   // by plan::variant_id
 }  // namespace
 
-hipError_t launch_integrator(const RenderArgs &args, hipStream_t stream) {
+hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
     const int rows = args.row_end - args.row_begin;
     if (rows <= 0 || args.width <= 0) return hipSuccess;
-    const unsigned grid = args.n_tiles * args.n_chunks;
-    with_instantiation(args, [&](auto kernel, int) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, args); });
+    const Kernel kernel = kKernels[plan::variant_id(v)];
+    if (!kernel) return hipErrorInvalidDeviceFunction;
+    hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
     return hipGetLastError();
 }
 
-// Cuts the launch's row band into the tiles of the instantiation it will run: fills narrow, blocks_x, n_tiles.  The
-// statistics-free small-scene kernel owns 16 x 8 tiles (two pixels per lane) -- unless that would leave the chip's wave slots
-// underfilled, in which case its 8 x 8 variant runs (a tile's passes are a serial chain: fewer tiles than slots means idle SIMDs).
-void integrator_plan_tiles(RenderArgs &args, int cu_count, int force) {
-    const bool sky = args.sky != nullptr, big = (args.big != 0), stats = launch_with_stats(args);
-    const uint32_t rows = static_cast<uint32_t>((args.band_rows + kTileH - 1) / kTileH);      // tile rows of the band (its planes hold band_rows rows)
-    int rays = (!sky && !stats) ? (big ? PT_BIG_RAYS_PER_LANE : PT_RAYS_PER_LANE) : 1;
-    args.narrow = 0;
-    args.adapt_pool = 0;
-    int tile_px = rays;   // tile width in 8-pixel column blocks
-    if (rays > 1) {
-        const uint32_t wide_tiles = static_cast<uint32_t>((args.width + kTileW * rays - 1) / (kTileW * rays)) * rows;
-        // adaptive sampling on: the instantiations that run batches (not built with the rare envelope test: one more spilled
-        // register there)
-        const bool batches = !big && args.error >= 0.0f && !args.may_leave_envelope && args.pass_begin >= 0 && args.pass_begin + args.pass_count <= kMaxBatchPass;
-        // one and a half rounds of its waves (measured, profiles/r03_ab_logs.txt ab53: 7 200 tiles -19 %, 8 160 tiles +3 %, 16 200 +6.6 %);
-        // the batch kernel beats the 8 x 8 kernel's sitting out from 1.2 rounds on (1280 x 720: 29.0 against 31.7 ms, r04_ab_logs.txt adapt6)
-        const uint32_t slots = static_cast<uint32_t>(cu_count) * 4u * static_cast<uint32_t>(PT_WAVES_PER_SIMD - 1);
-        uint32_t min_tiles = slots * 3u / 2u, min_wide = batches ? slots * 6u / 5u : min_tiles;
-        if (force == 1) min_tiles = min_wide = 0xFFFFFFFFu;   // (test builds: always 8 x 8 / always 16 x 8 / always 32 x 8 with adaptive sampling on)
-        if (force == 2 || force == 3) min_tiles = min_wide = 0;
-        if (wide_tiles < min_wide) {
-            rays = tile_px = 1;
-            args.narrow = 1;
-        } else if (batches) {   // over 32 x 8 tiles if there are enough of those as well, else over 16 x 8 tiles
-            const uint32_t pool4_tiles = static_cast<uint32_t>((args.width + kTileW * 4 - 1) / (kTileW * 4)) * rows;
-            args.adapt_pool = (force != 2 && pool4_tiles >= min_tiles) ? 4 : 2;
-            tile_px = args.adapt_pool;
-        }
-    }
-    if (rays == 1 && big && !sky && !stats && args.error >= 0.0f && !args.may_leave_envelope && args.pass_begin >= 0 &&
-        args.pass_begin + args.pass_count <= kMaxBatchPass && force != 1) {
-        // the box-tree kernel (one ray slot per lane, six waves per SIMD) with adaptive sampling on: batches of 64 over 16 x 8 tiles,
-        // over 32 x 8 tiles where the frame has one and a half rounds of those
-        const uint32_t min_tiles = (force == 2 || force == 3) ? 0u : static_cast<uint32_t>(cu_count) * 4u * static_cast<uint32_t>(PT_WAVES_PER_SIMD) * 3u / 2u;
-        const uint32_t pool2_tiles = static_cast<uint32_t>((args.width + kTileW * 2 - 1) / (kTileW * 2)) * rows;
-        const uint32_t pool4_tiles = static_cast<uint32_t>((args.width + kTileW * 4 - 1) / (kTileW * 4)) * rows;
-        if (force != 2 && pool4_tiles >= min_tiles) args.adapt_pool = 4;
-        else if (pool2_tiles >= min_tiles) args.adapt_pool = 2;
-        if (args.adapt_pool) tile_px = args.adapt_pool;
-    }
-    args.blocks_x = (args.width + kTileW * tile_px - 1) / (kTileW * tile_px);
-    args.n_tiles = static_cast<uint32_t>(args.blocks_x) * rows;
-}
-
-// Waves (= workgroups: one wave each) of that instantiation one compute unit holds at a time, from the runtime's occupancy
-// calculation (registers, LDS, launch bounds): the scheduler's count of wave slots.  Asked once per instantiation and device.
-hipError_t integrator_waves_per_cu(const RenderArgs &args, int *waves) {
+// Waves (= workgroups: one wave each) of that kernel one compute unit holds at a time, from the runtime's occupancy
+// calculation (registers, LDS, launch bounds): the scheduler's count of wave slots.  Asked once per kernel and device.
+hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves) {
     constexpr int kDevices = 16;
-    static std::atomic<int> cache[kDevices][kInstantiations];   // 0 = not asked yet
+    static std::atomic<int> cache[kDevices][plan::kVariants];   // 0 = not asked yet
+    const Kernel kernel = kKernels[plan::variant_id(v)];
+    if (!kernel) return hipErrorInvalidDeviceFunction;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    hipError_t result = hipSuccess;
-    with_instantiation(args, [&](auto kernel, int id) {
-        int n = dev < kDevices ? cache[dev][id].load(std::memory_order_relaxed) : 0;
-        if (n == 0) {
-            result = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kBlock, 0);
-            if (result == hipSuccess && n > 0) {
-                // The runtime's calculator divides the CU's LDS by the kernel's bytes; the hardware hands LDS out in granules of 1 280
-                // bytes (tools/lds_granule_probe.hip, profiles/r04_lds_granule.txt: 7 888 B -> 18 workgroups run, the runtime says 20).
-                hipFuncAttributes fa;
-                hipDeviceProp_t prop;
-                if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kernel)) == hipSuccess && fa.sharedSizeBytes > 0 &&
-                    hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.maxSharedMemoryPerMultiProcessor > 0) {
-                    constexpr size_t kLdsGranule = 1280;
-                    const size_t per_wave = (fa.sharedSizeBytes + kLdsGranule - 1) / kLdsGranule * kLdsGranule;
-                    const size_t by_lds = std::max<size_t>(prop.maxSharedMemoryPerMultiProcessor, prop.sharedMemPerBlock) / per_wave;
-                    if (by_lds >= 1 && by_lds < static_cast<size_t>(n)) n = static_cast<int>(by_lds);
-                }
+    std::atomic<int> *cached = dev < kDevices ? &cache[dev][plan::variant_id(v)] : nullptr;
+    int n = cached ? cached->load(std::memory_order_relaxed) : 0;
+    if (n == 0) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kBlock, 0);
+        if (e == hipSuccess && n > 0) {
+            // The runtime's calculator divides the CU's LDS by the kernel's bytes; the hardware hands LDS out in granules of 1 280
+            // bytes (tools/lds_granule_probe.hip, profiles/r04_lds_granule.txt: 7 888 B -> 18 workgroups run, the runtime says 20).
+            hipFuncAttributes fa;
+            hipDeviceProp_t prop;
+            if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kernel)) == hipSuccess && fa.sharedSizeBytes > 0 &&
+                hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.maxSharedMemoryPerMultiProcessor > 0) {
+                constexpr size_t kLdsGranule = 1280;
+                const size_t per_wave = (fa.sharedSizeBytes + kLdsGranule - 1) / kLdsGranule * kLdsGranule;
+                const size_t by_lds = std::max<size_t>(prop.maxSharedMemoryPerMultiProcessor, prop.sharedMemPerBlock) / per_wave;
+                if (by_lds >= 1 && by_lds < static_cast<size_t>(n)) n = static_cast<int>(by_lds);
             }
-            if (result != hipSuccess || n <= 0) n = 0;
-            else if (dev < kDevices) cache[dev][id].store(n, std::memory_order_relaxed);
         }
-        if (n > 0) *waves = n;
-    });
-    return result;
+        if (e != hipSuccess || n <= 0) n = 0;
+        else if (cached) cached->store(n, std::memory_order_relaxed);
+    }
+    if (n > 0) *waves = n;
+    return e;
 }
 #endif
+
+const plan::Build &integrator_build() { return kBuild; }
 
 }  // namespace pt

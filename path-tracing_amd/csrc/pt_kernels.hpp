@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "pt_launch_plan.hpp"
 #include "pt_scene.hpp"
 
 namespace pt {
@@ -72,13 +73,12 @@ struct RenderArgs {
 #endif
 };
 
-hipError_t launch_integrator(const RenderArgs &args, hipStream_t stream);
-// waves of the instantiation such a launch runs that one compute unit holds at a time (runtime occupancy query, cached)
-hipError_t integrator_waves_per_cu(const RenderArgs &args, int *waves);
-// cuts the launch's row band (width, row_begin, row_end, band_rows, scene, stats already set) into the tiles of the instantiation it will
-// run: fills narrow, adapt_pool, blocks_x and n_tiles
-// (force: 0 = by tile count, 1 = always 8 x 8 tiles, 2 = always 16 x 8, 3 = always 16 x 8 and 32 x 8 with adaptive sampling on: test builds)
-void integrator_plan_tiles(RenderArgs &args, int cu_count, int force = 0);
+// The constants the kernels of this library were compiled with: what plan::plan_tiles needs to know of the build.
+const plan::Build &integrator_build();
+// launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds)
+hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+// waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached)
+hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);
 // diagnostic: both forms of the box tree's child test on (node, ray, t_best) items; out[2 i] = float form, out[2 i + 1] = half-precision form
 hipError_t launch_box_masks(const BvhNode *d_nodes, const float *d_rays, const float *d_t_best, float err, int n, uint32_t *d_out, hipStream_t stream);
 hipError_t launch_trace_rays(const RenderArgs &args, const float *d_origins, const float *d_directions, int n_rays,

@@ -8,10 +8,10 @@
 #include <cstring>
 #include <vector>
 namespace pt {   // what pt_capi.cpp / pt_frame.cpp link against in the real library (pt_kernels.hip, pt_filters.hip)
-hipError_t launch_integrator(const RenderArgs &, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_trace_rays(const RenderArgs &, const float *, const float *, int, int32_t *, float *, hipStream_t) { return hipErrorNoDevice; }
-hipError_t integrator_waves_per_cu(const RenderArgs &, int *) { return hipErrorNoDevice; }
-void integrator_plan_tiles(RenderArgs &, int, int) {}
+hipError_t integrator_waves_per_cu(const plan::Variant &, int *) { return hipErrorNoDevice; }
+const plan::Build &integrator_build() { static const plan::Build b = {8, 8, 2, 1, 6, 32766, plan::Stats::kAsAsked, false}; return b; }   // (the kernels' translation unit says how it was built)
 hipError_t launch_gauss(const float *, float *, const float *, int, int, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_median(const float *, float *, int, int, int, hipStream_t) { return hipErrorNoDevice; }
 }

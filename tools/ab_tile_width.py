@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """8 x 8 against 16 x 8 tiles of the statistics-free small-scene kernel over frame sizes (test-hook knob `tile_width` of
-libpt_testhooks.so, same kernels as the product): where integrator_plan_tiles should switch.  profiles/r03_ab_logs.txt ab53.
+libpt_testhooks.so, same kernels as the product): where plan_tiles (pt_launch_plan.hpp) should switch.  profiles/r03_ab_logs.txt ab53.
 
     python tools/ab_tile_width.py
 """
