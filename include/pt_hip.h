@@ -397,6 +397,83 @@ int pt_denoise_host(int device, int32_t width, int32_t height, const float *sum,
                     const float *position, const float *normal, const float *albedo, const int32_t *hit_index,
                     const pt_denoise_params *params, float *mean_rgb, int32_t *count_out, float *kernel_ms);
 
+/* ---- temporal accumulation (moving camera) ----------------------------------------------------------- */
+
+/* The temporal half the denoiser lacks: the frames of ONE view sequence are accumulated by reprojection.  The stage is
+ * accumulator to accumulator: a push takes the accumulators of the current frame (sum, sum2, count, as every render entry point
+ * fills them; HOST buffers of the whole width x height image, no row bands) and returns accumulators of the same shape to which
+ * the reprojected history of the earlier frames has been ADDED -- history is kept as sums and an effective sample count, so a
+ * merge is what rendering more passes would have been, weighted by samples and not by a fixed blend factor.  Everything
+ * downstream (pt_denoise_host, pt_resolve, pt_tonemap, the post filters) consumes the result unchanged, and the variance the
+ * denoiser derives from sum2 / n - m * m shrinks by itself as the history grows.  Frame i of a sequence renders passes
+ * [i * RPP, (i + 1) * RPP) with one seed, so that the frames' samples are independent.
+ *
+ * A pt_temporal belongs to the scene handle it was created for (which must outlive it) and keeps its history on that handle's
+ * device.  A push reads the handle's CAMERA AT THE TIME OF THE CALL (the lens is ignored, as for the features), renders the
+ * feature buffers of that view on the device exactly as pt_render_features_host states them (eps from the create call), merges,
+ * stores the new history and -- if `denoise` is given -- runs the filter of pt_denoise_host on the merged planes and those
+ * features, all in one chain on the device: only the accumulators go up and only the requested outputs come down.  kernel_ms =
+ * HIP-event time of that chain.  Not to be called while the handle's camera is being set; calls on one pt_temporal are
+ * serialised by the library.
+ *
+ * Parameters; a zeroed struct holds the defaults:
+ *   max_frames       cap of the history's age in frames; 0 = 32; +inf = never capped       (negative or NaN: invalid)
+ *   sigma_plane      a history tap farther than this from the pixel's tangent plane is rejected, in scene units; 0 = 0.1
+ *   min_normal_dot   ... or whose normal agrees less than this; 0 = 0.9; at most 1   (both: negative or non-finite: invalid)
+ *
+ * The arithmetic, exactly, as for the denoiser: every operation below is ONE correctly rounded float operation in the order
+ * written (+ - * /, floor, comparisons, int <-> float conversions; nothing fused, no approximations).  x . y = (x_x y_x + x_y y_y)
+ * + x_z y_z.  State per pixel after a push: Hs[3], Hs2[3] (sums), Hn (their effective sample count, a float: exact only below
+ * 2^24), HL (the history's age in frames, a float), and the frame's features P' (position), N' (normal) and class (hit / miss, as
+ * the denoiser defines it).  Per object: that frame's camera and the rows i0, i1, i2 of the inverse of the matrix whose columns are
+ * its right, up, forward -- computed in double from the float components and rounded to float once:  cross(a, b) = (a_y b_z - a_z
+ * b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x);  det = (right_x c_x + right_y c_y) + right_z c_z with c = cross(up, forward);
+ * i0 = cross(up, forward) / det,  i1 = cross(forward, right) / det,  i2 = cross(right, up) / det.
+ * A push with the current camera, features P, N, class and accumulators s, s2, c computes per pixel p = (x, y) a history part
+ * h = (h_s[3], h_s2[3], h_n, h_L), or finds that it has NO HISTORY:
+ * 1. First frame (after create or reset): no history.
+ * 2. Static camera (the current camera equals the history's bit for bit): h = (Hs, Hs2, Hn, HL) of p itself if Hn > 0, else no
+ *    history -- no test, no weight: a sequence that does not move is exactly progressive rendering across calls.  Go to 5.
+ * 3. Where was this pixel?  e = P - origin' (the history's camera) for a hit; for a miss e = (u * right + v * up) + forward of the
+ *    CURRENT camera with u = x / W - 0.5, v = -y / H + 0.5 as pt_render_features_host states them (a direction: the sky is
+ *    reprojected by rotation only).  a = i0 . e, b = i1 . e, g = i2 . e.  Unless g > 0: no history.
+ *    fx = (a / g + 0.5) * W,  fy = (0.5 - b / g) * H  (W, H as floats; pixel centres sit at integer coordinates, as the feature
+ *    rays).  Unless -1 <= fx < W and -1 <= fy < H (false for a NaN; checked before any conversion to an integer): no history.
+ *    x0 = floor(fx), tx = fx - x0, likewise y0, ty.  The four taps q = (x0 + i, y0 + j), i, j in {0, 1}, visited j outer, i inner,
+ *    weigh w = (i ? tx : 1 - tx) * (j ? ty : 1 - ty).
+ * 4. Which taps count?  A tap q is used if it lies inside the image, Hn_q > 0, it is of p's class, and for hits
+ *    N . N'_q >= min_normal_dot and |N . (P'_q - P)| <= sigma_plane (a disoccluded or different surface fails the plane test).
+ *    Over the used taps, from 0: Wt += w, A_s += w * Hs_q, A_s2 += w * Hs2_q, A_n += w * Hn_q, A_L += w * HL_q.  Unless
+ *    Wt > 1e-3: no history.  Else h = A / Wt, component by component -- interpolating sums and counts with the same weights
+ *    makes the history's mean the count-weighted mean of the taps.
+ * 5. Cap: if h_L > max_frames: k = max_frames / h_L, and h_s, h_s2, h_n, h_L are each multiplied by k.
+ * 6. Merge and store.  With history: Hs = s + h_s, Hs2 = s2 + h_s2, Hn = float(c) + h_n, HL = 1 + h_L.  Without: Hs = s,
+ *    Hs2 = s2, Hn = float(c), HL = 1.  P', N', the class and the camera become the current ones.
+ * 7. Outputs, with an integer count.  With history: n_i = h_n > 0 ? max(1, int(h_n + 0.5)) : 0 (the conversion truncates),
+ *    r = float(n_i) / h_n (1 if n_i = 0);  sum_out = s + h_s * r, sum2_out = s2 + h_s2 * r, count_out = c + n_i.  Without:
+ *    sum_out = s, sum2_out = s2, count_out = c.  history_frames = HL.  The history's mean and second moment survive the rounding
+ *    of its count; with a static camera and no cap r = 1 and count_out is the exact total.
+ * With `denoise`: mean_rgb, mean_count are, bit for bit, what pt_denoise_host returns as mean_rgb, count_out for (sum_out,
+ * sum2_out, count_out) and the pt_render_features_host buffers of the same view (levels = 0: the unfiltered mean).  Without it
+ * they are left untouched. */
+typedef struct pt_temporal pt_temporal;          /* the history of ONE view sequence, resident on the scene's device */
+typedef struct pt_temporal_params {
+    float max_frames;
+    float sigma_plane;
+    float min_normal_dot;
+} pt_temporal_params;
+/* PT_ERR_INVALID_ARGUMENT: a NULL scene or `out`, an empty or too large image, eps not a number.  PT_ERR_NO_DEVICE: a host-only
+ * scene (there is no CPU fallback).  The history starts empty: the first push is a first frame. */
+int pt_temporal_create(pt_scene *scene, int32_t width, int32_t height, float eps, pt_temporal **out);
+/* Every output may be NULL.  PT_ERR_INVALID_ARGUMENT: a NULL handle, input buffer or `params`, a parameter outside what is stated
+ * above (those of `denoise` as pt_denoise_host checks them).  A failed call leaves the history as it was. */
+int pt_temporal_push_host(pt_temporal *t, const float *sum, const float *sum2, const int32_t *count,
+                          const pt_temporal_params *params, const pt_denoise_params *denoise /* NULL: none */,
+                          float *sum_out, float *sum2_out, int32_t *count_out, float *history_frames,
+                          float *mean_rgb, int32_t *mean_count, float *kernel_ms);
+int pt_temporal_reset(pt_temporal *t);           /* forget the history; the next push is a first frame */
+void pt_temporal_destroy(pt_temporal *t);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

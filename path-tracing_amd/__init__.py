@@ -40,7 +40,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_band_rows", "pt_session_create_strided", "pt_frame_row_stride",
                "pt_camera_look_at", "pt_scene_set_camera", "pt_scene_get_camera", "pt_frame_set_camera",
                "pt_scene_set_lens", "pt_scene_get_lens", "pt_frame_set_lens",
-               "pt_render_features_host", "pt_denoise_host", "pt_tonemap"]
+               "pt_render_features_host", "pt_denoise_host", "pt_tonemap",
+               "pt_temporal_create", "pt_temporal_push_host", "pt_temporal_reset", "pt_temporal_destroy"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -113,6 +114,11 @@ class DenoiseParams(C.Structure):
 
 
 DENOISE_MAX_LEVELS = 8
+
+
+class TemporalParams(C.Structure):
+    """pt_temporal_params: a zeroed struct holds the defaults (max_frames 32, sigma_plane 0.1, min_normal_dot 0.9)."""
+    _fields_ = [("max_frames", C.c_float), ("sigma_plane", C.c_float), ("min_normal_dot", C.c_float)]
 
 
 def _lens_arg(radius, focus_distance):
@@ -238,6 +244,11 @@ def load_library(path):
     L.pt_render_features_host.argtypes = [vp, C.POINTER(RenderParams), ip, fp, fp, fp, fp]
     L.pt_denoise_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, fp, ip, fp, fp, fp, ip, C.POINTER(DenoiseParams), fp, ip, fp]
     L.pt_tonemap.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, fp]
+    L.pt_temporal_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_float, C.POINTER(vp)]
+    L.pt_temporal_push_host.argtypes = [vp, fp, fp, ip, C.POINTER(TemporalParams), C.POINTER(DenoiseParams), fp, fp, ip, fp, fp, ip, fp]
+    L.pt_temporal_reset.argtypes = [vp]
+    L.pt_temporal_destroy.argtypes = [vp]
+    L.pt_temporal_destroy.restype = None
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     return L
@@ -476,6 +487,59 @@ class Session:
     def close(self):
         if self._h:
             self._L.pt_session_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Temporal:
+    """pt_temporal: the history of one view sequence on the scene's device.  push() merges the reprojected history into a frame's
+    accumulators (the scene's camera at the time of the call says where the frame was seen from) and optionally denoises the
+    merged frame in the same chain on the device."""
+
+    def __init__(self, scene, width, height, eps=1e-4):
+        self._scene, self._L = scene, scene._L      # the scene must outlive the history
+        self.width, self.height = width, height
+        self._h = C.c_void_p()
+        _check(self._L.pt_temporal_create(scene._h, width, height, eps, C.byref(self._h)), self._L)
+
+    def push(self, s, s2, c, *, max_frames=0.0, sigma_plane=0.0, min_normal_dot=0.0, denoise=None, want_ms=False):
+        """pt_temporal_push_host.  `denoise`: None, a DenoiseParams, or a dict of pt.denoise's keyword parameters (levels, ...).
+        Returns a dict: sum, sum2 [n, 3], count [n], history_frames [n]; with `denoise` also mean_rgb [n, 3], mean_count [n]; with
+        want_ms also kernel_ms."""
+        n = self.width * self.height
+        s, s2 = np.ascontiguousarray(s, np.float32), np.ascontiguousarray(s2, np.float32)
+        c = np.ascontiguousarray(c, np.int32)
+        if s.size != 3 * n or s2.size != 3 * n or c.size != n:
+            raise ValueError("Temporal.push: the accumulators do not hold width x height pixels")
+        if isinstance(denoise, dict):
+            denoise = DenoiseParams(denoise.get("levels", 5), denoise.get("sigma_luminance", 0.0), denoise.get("sigma_plane", 0.0),
+                                    denoise.get("normal_power_log2", 0), denoise.get("demodulate_albedo", 0))
+        prm = TemporalParams(max_frames, sigma_plane, min_normal_dot)
+        out = {"sum": np.zeros((n, 3), np.float32), "sum2": np.zeros((n, 3), np.float32), "count": np.zeros(n, np.int32),
+               "history_frames": np.zeros(n, np.float32)}
+        if denoise is not None:
+            out["mean_rgb"], out["mean_count"] = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        ms = C.c_float()
+        _check(self._L.pt_temporal_push_host(self._h, _fp(s), _fp(s2), _ip(c), C.byref(prm), C.byref(denoise) if denoise is not None else None,
+                                             _fp(out["sum"]), _fp(out["sum2"]), _ip(out["count"]), _fp(out["history_frames"]),
+                                             _fp(out["mean_rgb"]) if denoise is not None else None,
+                                             _ip(out["mean_count"]) if denoise is not None else None, C.byref(ms)), self._L)
+        if want_ms:
+            out["kernel_ms"] = ms.value
+        return out
+
+    def reset(self):
+        """Forget the history: the next push is a first frame."""
+        _check(self._L.pt_temporal_reset(self._h), self._L)
+
+    def close(self):
+        if self._h:
+            self._L.pt_temporal_destroy(self._h)
             self._h = None
 
     def __del__(self):

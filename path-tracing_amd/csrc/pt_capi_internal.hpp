@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "pt_denoise.hpp"
 #include "pt_kernels.hpp"
 #include "pt_scene.hpp"
 
@@ -141,5 +142,9 @@ const pt_camera &view_camera(const pt_scene *s);
 // The scene part of the kernel arguments for `eps` (uploads the culling hierarchy on first use).  The scene's device is
 // current and the caller holds scene->launch_mutex until its kernels are enqueued.
 int scene_trace_args(pt_scene *scene, float eps, pt::RenderArgs &a);
+// pt_denoise_params as pt_denoise_host checks them, into the parameter fields of the launch arguments (zero = the default).
+int denoise_params_to_args(const pt_denoise_params *prm, pt::DenoiseArgs &a);
+// levels = 0 of pt_denoise_host: mean_rgb = sum / n (sum where n = 0), count_out = count (may be NULL), on the host.
+void unfiltered_mean(size_t n, const float *sum, const int32_t *count, float *mean_rgb, int32_t *count_out);
 
 }  // namespace ptc

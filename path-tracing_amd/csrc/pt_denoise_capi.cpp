@@ -55,24 +55,44 @@ static int render_features_host_impl(pt_scene *scene, const pt_render_params *p,
 
 static_assert(PT_DENOISE_MAX_LEVELS == pt::kDenoiseMaxLevels, "the ABI header states the denoiser's level limit");
 
-static int denoise_host_impl(int device, int32_t width, int32_t height, const float *sum, const float *sum2, const int32_t *count,
-                             const float *position, const float *normal, const float *albedo, const int32_t *hit_index,
-                             const pt_denoise_params *prm, float *mean_rgb, int32_t *count_out, float *kernel_ms) {
-    if (width <= 0 || height <= 0 || !sum || !sum2 || !count || !prm || !mean_rgb) return fail(PT_ERR_INVALID_ARGUMENT, "null buffer or empty image");
-    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "image too large");
+namespace ptc {
+
+int denoise_params_to_args(const pt_denoise_params *prm, pt::DenoiseArgs &a) {
     if (prm->levels < 0 || prm->levels > PT_DENOISE_MAX_LEVELS) return fail(PT_ERR_INVALID_ARGUMENT, "denoise: levels must lie in 0 .. 8");
     if (!std::isfinite(prm->sigma_luminance) || !std::isfinite(prm->sigma_plane) || prm->sigma_luminance < 0.0f || prm->sigma_plane < 0.0f)
         return fail(PT_ERR_INVALID_ARGUMENT, "denoise: sigmas must be finite and not negative (0 = the default)");
     if (prm->normal_power_log2 < 0 || prm->normal_power_log2 > pt::kDenoiseMaxNormalPowerLog2)
         return fail(PT_ERR_INVALID_ARGUMENT, "denoise: normal_power_log2 must lie in 0 .. 16 (0 = the default)");
+    a.levels = prm->levels;
+    a.sigma_luminance = prm->sigma_luminance > 0.0f ? prm->sigma_luminance : pt::kDenoiseSigmaLuminance;
+    a.sigma_plane = prm->sigma_plane > 0.0f ? prm->sigma_plane : pt::kDenoiseSigmaPlane;
+    a.normal_power_log2 = prm->normal_power_log2 > 0 ? prm->normal_power_log2 : pt::kDenoiseNormalPowerLog2;
+    a.demodulate = prm->demodulate_albedo >= 0 ? 1 : 0;
+    return PT_OK;
+}
+
+void unfiltered_mean(size_t n, const float *sum, const int32_t *count, float *mean_rgb, int32_t *count_out) {
+    for (size_t p = 0; p < n; ++p) {
+        const float cn = static_cast<float>(count[p]);
+        for (int k = 0; k < 3; ++k) mean_rgb[3 * p + k] = count[p] ? sum[3 * p + k] / cn : sum[3 * p + k];
+        if (count_out) count_out[p] = count[p];
+    }
+}
+
+}  // namespace ptc
+
+static int denoise_host_impl(int device, int32_t width, int32_t height, const float *sum, const float *sum2, const int32_t *count,
+                             const float *position, const float *normal, const float *albedo, const int32_t *hit_index,
+                             const pt_denoise_params *prm, float *mean_rgb, int32_t *count_out, float *kernel_ms) {
+    if (width <= 0 || height <= 0 || !sum || !sum2 || !count || !prm || !mean_rgb) return fail(PT_ERR_INVALID_ARGUMENT, "null buffer or empty image");
+    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "image too large");
+    pt::DenoiseArgs a;
+    const int prc = ptc::denoise_params_to_args(prm, a);
+    if (prc != PT_OK) return prc;
     const size_t n = static_cast<size_t>(width) * height;
     if (kernel_ms) *kernel_ms = 0.0f;
     if (prm->levels == 0) {   // the unfiltered mean, on the host
-        for (size_t p = 0; p < n; ++p) {
-            const float cn = static_cast<float>(count[p]);
-            for (int k = 0; k < 3; ++k) mean_rgb[3 * p + k] = count[p] ? sum[3 * p + k] / cn : sum[3 * p + k];
-            if (count_out) count_out[p] = count[p];
-        }
+        ptc::unfiltered_mean(n, sum, count, mean_rgb, count_out);
         return PT_OK;
     }
     if (!position || !normal || !albedo || !hit_index) return fail(PT_ERR_INVALID_ARGUMENT, "denoise: null feature buffer");
@@ -94,12 +114,7 @@ static int denoise_host_impl(int device, int32_t width, int32_t height, const fl
     float *d_alb = reinterpret_cast<float *>(take(b12)), *d_mean = reinterpret_cast<float *>(take(b12));
     int32_t *d_cnt = reinterpret_cast<int32_t *>(take(b4)), *d_hit = reinterpret_cast<int32_t *>(take(b4));
     int32_t *d_cnt_out = reinterpret_cast<int32_t *>(take(b4));
-    pt::DenoiseArgs a;
-    a.width = width; a.height = height; a.levels = prm->levels;
-    a.sigma_luminance = prm->sigma_luminance > 0.0f ? prm->sigma_luminance : pt::kDenoiseSigmaLuminance;
-    a.sigma_plane = prm->sigma_plane > 0.0f ? prm->sigma_plane : pt::kDenoiseSigmaPlane;
-    a.normal_power_log2 = prm->normal_power_log2 > 0 ? prm->normal_power_log2 : pt::kDenoiseNormalPowerLog2;
-    a.demodulate = prm->demodulate_albedo >= 0 ? 1 : 0;
+    a.width = width; a.height = height;
     a.sum = d_sum; a.sum2 = d_sum2; a.count = d_cnt; a.position = d_pos; a.normal = d_nrm; a.albedo = d_alb; a.hit_index = d_hit;
     a.rec_a0 = take(b16); a.rec_a1 = take(b16); a.rec_b = take(b16); a.rec_c = take(b16);
     a.mean_rgb = d_mean; a.count_out = d_cnt_out;

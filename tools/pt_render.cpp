@@ -37,6 +37,14 @@
 // plane-distance widths (default 0: the library's).  The order is resolve (so the dispersion numbers and the file name are those
 // of the undenoised frame) -> feature buffers -> denoise -> tone map -> -GAUSS / -MEDIAN -> quantize -> BMP, on the first device
 // of the frame.  Previews (-UPDATE) stay undenoised.  Without the flag nothing changes.
+// A sequence (pt_temporal_*, not in the reference): -FRAMES n (default 1) renders n frames, frame i with passes [i RPP, (i + 1) RPP)
+// of the same seed, and writes each as frame_%04d.bmp in the working directory; the last frame also takes the usual outputs (the
+// named file and ../result.bmp, or -OUT).  -EYE_END x,y,z and -LOOKAT_END x,y,z (default: -EYE and -LOOKAT) move the camera: frame
+// i looks from start + (end - start) i / (n - 1), computed in double, through pt_camera_look_at.  -TEMPORAL m (default 0: off)
+// merges every frame with the reprojected history of the earlier ones before it is resolved, m being the cap of the history's age
+// in frames (32 is the usual choice); with -DENOISE the filter then runs on the merged frame, in the same chain on the device.
+// A sequence writes no previews and prints no -TIMING line, and -TL with -FRAMES > 1 is refused.  Without -FRAMES and -TEMPORAL
+// nothing changes.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -71,6 +79,9 @@ struct Options {   // defaults: config.h:16-29
     bool aperture_given = false, focus_given = false;
     int denoise = 0;               // -DENOISE: a-trous levels, 0 = off
     float dn_sigma_l = 0.0f, dn_sigma_p = 0.0f;
+    int frames = 1;                // -FRAMES
+    float temporal = 0.0f;         // -TEMPORAL: max_frames of the history, 0 = no temporal stage
+    std::string eye_end, lookat_end;   // -EYE_END / -LOOKAT_END as given ("" = the start value)
 };
 
 long long now_ms() {
@@ -119,6 +130,10 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-DENOISE") o.denoise = std::atoi(v);
         if (f == "-DN_SIGMA_L") o.dn_sigma_l = static_cast<float>(std::atof(v));
         if (f == "-DN_SIGMA_P") o.dn_sigma_p = static_cast<float>(std::atof(v));
+        if (f == "-FRAMES") o.frames = std::atoi(v);
+        if (f == "-TEMPORAL") o.temporal = static_cast<float>(std::atof(v));
+        if (f == "-EYE_END") o.eye_end = v;
+        if (f == "-LOOKAT_END") o.lookat_end = v;
     }
 }
 
@@ -207,6 +222,15 @@ int main(int argc, char **argv) {
     }
     if (o.width <= 0 || o.height <= 0) {
         std::cerr << "pt_render: --W and --H must be positive" << std::endl;
+        return 2;
+    }
+    const bool sequence = o.frames > 1 || o.temporal > 0.0f;
+    if (o.frames > 1 && o.time_limit != 0) {
+        std::cerr << "pt_render: -TL is not defined for a sequence (-FRAMES > 1)" << std::endl;
+        return 2;
+    }
+    if (o.frames < 1 || !(o.temporal >= 0.0f)) {
+        std::cerr << "pt_render: -FRAMES takes a count >= 1 and -TEMPORAL a history length >= 0" << std::endl;
         return 2;
     }
     const unsigned seed = o.seed < 0 ? static_cast<unsigned>(std::time(nullptr)) : static_cast<unsigned>(o.seed);   // config.h:101-104
@@ -352,6 +376,103 @@ int main(int argc, char **argv) {
         read_s += secs(a, clk::now());
         return rc;
     };
+
+    if (sequence) {
+        // n frames: frame i renders its own pass range from its own camera, is merged with the history (-TEMPORAL), denoised
+        // (-DENOISE), tone-mapped, filtered, quantized and written; the last one also takes the usual outputs
+        float eye0[3], at0[3], up[3], eye1[3], at1[3];
+        if (!parse_vec3(o.eye, eye0) || !parse_vec3(o.lookat, at0) || !parse_vec3(o.up, up) ||
+            !parse_vec3(o.eye_end.empty() ? o.eye : o.eye_end, eye1) || !parse_vec3(o.lookat_end.empty() ? o.lookat : o.lookat_end, at1)) {
+            std::cerr << "pt_render: -EYE / -EYE_END / -LOOKAT / -LOOKAT_END / -UP take three comma-separated numbers, x,y,z" << std::endl;
+            return 2;
+        }
+        const bool own_camera = o.camera || !o.eye_end.empty() || !o.lookat_end.empty();
+        pt_scene *view = nullptr;   // the scene on the first device: the history's and the feature buffers' handle
+        pt_temporal *history = nullptr;
+        if ((o.temporal > 0.0f || o.denoise > 0) && pt_scene_clone_to_device(scene, devices[0], &view) != PT_OK) return die("pt_render");
+        if (o.temporal > 0.0f && pt_temporal_create(view, o.width, o.height, o.eps, &history) != PT_OK) return die("pt_render");
+        if (!ensure_buffers()) return die("pt_render");
+        std::vector<float> msum, msum2, mean, rgb, pos, nrm, alb;
+        std::vector<int32_t> mcount, mean_count, hit;
+        if (history) { msum.resize(3 * px); msum2.resize(3 * px); mcount.resize(px); }
+        if (o.denoise > 0) { mean.resize(3 * px); mean_count.resize(px); }
+        if (o.denoise > 0 && !history) { pos.resize(3 * px); nrm.resize(3 * px); alb.resize(3 * px); hit.resize(px); }
+        if (o.denoise > 0 || o.gauss || o.median) rgb.resize(3 * px);
+        pt_temporal_params tp;
+        std::memset(&tp, 0, sizeof tp);
+        tp.max_frames = o.temporal;
+        pt_denoise_params dp;
+        std::memset(&dp, 0, sizeof dp);
+        dp.levels = o.denoise; dp.sigma_luminance = o.dn_sigma_l; dp.sigma_plane = o.dn_sigma_p;
+        for (int i = 0; i < o.frames; ++i) {
+            if (own_camera) {
+                float eye[3], at[3];
+                for (int k = 0; k < 3; ++k) {
+                    eye[k] = static_cast<float>(eye0[k] + (static_cast<double>(eye1[k]) - eye0[k]) * i / std::max(1, o.frames - 1));
+                    at[k] = static_cast<float>(at0[k] + (static_cast<double>(at1[k]) - at0[k]) * i / std::max(1, o.frames - 1));
+                }
+                if (pt_camera_look_at(eye, at, up, o.fov, o.aspect, &camera) != PT_OK || pt_frame_set_camera(frame, &camera) != PT_OK ||
+                    (view && pt_scene_set_camera(view, &camera) != PT_OK))
+                    return die("pt_render");
+            }
+            rp.pass_begin = i * o.rays_per_pixel;
+            rp.pass_count = o.rays_per_pixel;
+            if (pt_frame_clear(frame) != PT_OK || pt_frame_render(frame, &rp, nullptr) != PT_OK || read_back() != PT_OK) return die("pt_render");
+            pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);   // the statistics of the frame as rendered
+            const float *fs = sum, *fs2 = sum2;
+            const int32_t *fc = count;
+            if (history) {
+                if (pt_temporal_push_host(history, sum, sum2, count, &tp, o.denoise > 0 ? &dp : nullptr, msum.data(), msum2.data(), mcount.data(),
+                                          nullptr, o.denoise > 0 ? mean.data() : nullptr, o.denoise > 0 ? mean_count.data() : nullptr, nullptr) != PT_OK)
+                    return die("pt_render");
+                fs = msum.data(); fs2 = msum2.data(); fc = mcount.data();
+            } else if (o.denoise > 0) {
+                if (pt_render_features_host(view, &rp, hit.data(), nullptr, pos.data(), nrm.data(), alb.data()) != PT_OK ||
+                    pt_denoise_host(devices[0], o.width, o.height, fs, fs2, fc, pos.data(), nrm.data(), alb.data(), hit.data(), &dp, mean.data(),
+                                    mean_count.data(), nullptr) != PT_OK)
+                    return die("pt_render");
+            }
+            if (o.denoise > 0) {
+                pt_tonemap(o.width, o.height, mean.data(), mean_count.data(), o.gamma_correction, rgb.data());
+                if ((o.gauss || o.median) && pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+                pt_quantize(o.width, o.height, rgb.data(), mean_count.data(), bgr.data());
+            } else if (o.gauss || o.median) {
+                float unused[3];
+                pt_resolve_float(o.width, o.height, fs, fs2, fc, o.gamma_correction, rgb.data(), unused);
+                if (pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+                pt_quantize(o.width, o.height, rgb.data(), fc, bgr.data());
+            } else if (history) {
+                pt_resolve(o.width, o.height, fs, fs2, fc, o.gamma_correction, bgr.data(), nullptr);
+            }
+            if (o.frames > 1) {
+                char frame_name[32];
+                std::snprintf(frame_name, sizeof frame_name, "frame_%04d.bmp", i);
+                if (pt_write_bmp(frame_name, o.width, o.height, bgr.data()) != PT_OK) return die("pt_render");
+            }
+            if (!o.quiet) std::cerr << "frame " << i + 1 << " of " << o.frames << std::endl;
+        }
+        const long long end_time = now_ms();
+        const std::time_t t = std::time(nullptr);
+        const std::tm *now = std::localtime(&t);
+        const std::string name =   // main.cpp:206-213, for the last frame
+            std::to_string(now->tm_year + 1900) + '-' + std::to_string(now->tm_mon + 1) + '-' + std::to_string(now->tm_mday) + '-' +
+            std::to_string(now->tm_hour) + '-' + std::to_string(now->tm_min) + '-' + std::to_string(now->tm_sec) + "  " +
+            std::to_string(end_time - start_time) + "   " + std::to_string(o.rays_per_pixel) + " of " + std::to_string(o.rays_per_pixel) +
+            "  max_disp " + std::to_string(disp[0]) + "  min_disp " + std::to_string(disp[1]) + "  aver_disp " + std::to_string(disp[2]);
+        int rc = 0;
+        if (!o.out.empty()) {
+            if (pt_write_bmp(o.out.c_str(), o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
+        } else {
+            if (pt_write_bmp((name + ".bmp").c_str(), o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
+            if (pt_write_bmp("../result.bmp", o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
+        }
+        std::cout << name << std::endl;
+        pt_temporal_destroy(history);
+        if (view) pt_scene_destroy(view);
+        pt_frame_destroy(frame);
+        pt_scene_destroy(scene);
+        return rc;
+    }
 
     // Pass slices end exactly where the reference writes a preview (after every pass p with p % update == 0,
     // main.cpp:144-158) so that previews happen between GPU calls; with a time limit they are also kept short.
