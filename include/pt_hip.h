@@ -490,7 +490,9 @@ int pt_resolve(int32_t width, int32_t height, const float *sum, const float *sum
  *   pt_resolve_float     main.cpp:162-185: statistics + the tonemapped FLOAT image (rgb: height*width*3, r,g,b order;
  *                        pixels without samples keep their raw sums, as color_map does)
  *   pt_post_filter_host  GaussBlur (main.cpp:11-33) if gauss != 0, then MedianFilter (main.cpp:49-80) if median != 0,
- *                        on HIP device `device`, in place on the host image; median <= 11
+ *                        on HIP device `device`, in place on the host image; median <= 11.  The image is expected to hold
+ *                        neither NaN nor -0.0: the reference reads its "median" from a sorted window, where the place of a
+ *                        NaN is undefined and which of two equal zeros lands at the chosen rank is unspecified
  *   pt_quantize          main.cpp:193-201: float -> uint8 truncation, only for pixels with samples */
 int pt_resolve_float(int32_t width, int32_t height, const float *sum, const float *sum2, const int32_t *count,
                      float gamma, float *rgb, float *dispersion);
