@@ -159,9 +159,11 @@ typedef struct pt_camera {
     float forward[3];
 } pt_camera;
 
-/* Largest |component| of a camera origin pt_scene_set_camera accepts.  The culling margins are derived for origins within
- * max(20, largest |origin component|, largest |vertex coordinate|) + 1 of the world origin; they grow with that radius, and
- * beyond this bound they would stop being meaningful in float arithmetic. */
+/* Largest |component| of a camera origin pt_scene_set_camera accepts for every scene.  The culling margins are derived for
+ * origins within max(20, largest |origin component|, largest |vertex coordinate|) + 1 of the world origin; they grow with that
+ * radius, and beyond this bound they would stop being meaningful in float arithmetic.  A scene whose own vertices reach farther
+ * out (largest |vertex coordinate| > PT_CAMERA_MAX_ORIGIN) accepts origins up to that coordinate as well: they lie inside the
+ * envelope the scene has anyway. */
 #define PT_CAMERA_MAX_ORIGIN 4096.0f
 
 /* A camera at `eye` looking at `target`, computed in double and rounded to float once:
@@ -174,7 +176,7 @@ typedef struct pt_camera {
 int pt_camera_look_at(const float eye[3], const float target[3], const float up[3], float fov_y_degrees, float aspect, pt_camera *out);
 /* Sets the handle's camera; NULL returns to the reference's fixed camera.  PT_ERR_INVALID_ARGUMENT: a non-finite component, a
  * zero forward, or right / up / forward not linearly independent (|det| <= 1e-6 |right| |up| |forward|).  PT_ERR_UNSUPPORTED:
- * an origin component beyond PT_CAMERA_MAX_ORIGIN.  A failed call leaves the handle as it was. */
+ * an origin component beyond PT_CAMERA_MAX_ORIGIN and beyond the scene's largest |vertex coordinate|.  A failed call leaves the handle as it was. */
 int pt_scene_set_camera(pt_scene *scene, const pt_camera *camera);
 /* The handle's camera; *is_set = 0 (and the reference camera in *camera) if it has none.  Either pointer may be NULL. */
 int pt_scene_get_camera(const pt_scene *scene, pt_camera *camera, int32_t *is_set);

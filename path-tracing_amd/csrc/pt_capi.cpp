@@ -779,10 +779,13 @@ static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
     const double det = r[0] * (u[1] * f[2] - u[2] * f[1]) - r[1] * (u[0] * f[2] - u[2] * f[0]) + r[2] * (u[0] * f[1] - u[1] * f[0]);
     if (!(std::fabs(det) > 1e-6 * len(r) * len(u) * len(f)))
         return fail(PT_ERR_INVALID_ARGUMENT, "camera: right, up and forward are not linearly independent");
+    // (an origin within the scene's own extent does not enlarge the envelope the margins are derived for: a scene of any
+    // size can be viewed from inside its bounding cube, the scaled reference view included)
+    const double max_origin = std::max(static_cast<double>(PT_CAMERA_MAX_ORIGIN), scene->shared->vertex_extent);
     for (int i = 0; i < 3; ++i)
-        if (!(std::fabs(cam->origin[i]) <= PT_CAMERA_MAX_ORIGIN))
+        if (!(std::fabs(cam->origin[i]) <= max_origin))
             return fail(PT_ERR_UNSUPPORTED, "camera: origin component beyond PT_CAMERA_MAX_ORIGIN (" + std::to_string(PT_CAMERA_MAX_ORIGIN) +
-                                                "): the culling margins are not derived that far out");
+                                                ") and beyond the scene's largest |vertex coordinate|: the culling margins are not derived that far out");
     if (scene->has_lens) {
         const int rc = check_lens_on(*cam, scene->lens);
         if (rc != PT_OK) return rc;

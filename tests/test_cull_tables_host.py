@@ -10,29 +10,12 @@ import sys
 import numpy as np
 import pytest
 
+import cull_checks as K
 import oracle_lib as O
+from cull_checks import layout as _layout
 
 pt = importlib.import_module("path-tracing_amd")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _ray_sphere_keep(c, r2, o, d):
-    """float64 model of sphere_keep() in pt_kernels.hip (the float32 rounding slack is part of r2)."""
-    m = c - o
-    b = np.maximum((m * d).sum(-1), 0.0)
-    return ~((m * m).sum(-1) - b * b > r2)
-
-
-def _layout(t):
-    """slot -> (cluster, [sphere index of its ancestor at every level, top first ... level 0 last])."""
-    out = {}
-    for ci in range(len(t["kind"])):
-        if t["kind"][ci] != 0:
-            continue
-        for k in range(t["n_tri"][ci]):
-            chain = [t["data_off"][ci] + t["level_off"][ci][lv] + (k >> (3 * lv)) for lv in range(t["n_levels"][ci] - 1, -1, -1)]
-            out[t["first_tri"][ci] + k] = (ci, chain)
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -69,38 +52,10 @@ def test_structure_tor(tor):
 
 def test_accepted_triangles_are_never_culled(tor, oracle_scene):
     """Every (ray, triangle) pair the reference's Triangle::Intersect accepts passes all three sphere levels."""
-    import ctypes as C
-    t = tor.cull_tables()
-    lay = _layout(t)
-    tri, _ = tor.triangles()
-    st = tor.cull_layout()["slot_triangle"]
-    slot_of = np.argsort(st)
-    rng = np.random.default_rng(17)
-    v = tri[:, 4:13].reshape(-1, 3, 3).astype(np.float64)
-    # rays aimed at random points of small triangles (inside, on edges, just outside), from random origins
-    small = np.array(sorted(st[k] for k in lay))
     n = 40000
-    a = small[rng.integers(0, len(small), n)]
-    w = rng.dirichlet([0.6, 0.6, 0.6], n) * rng.choice([1.0, 1.0, 1.001, 1.01], n)[:, None]
-    target = (v[a] * w[:, :, None]).sum(1)
-    org = rng.uniform([-9.5, -9.5, -20.5], [9.5, 9.5, 9.5], (n, 3))
-    d = (target - org).astype(np.float32)
-    inv = np.float32(1) / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], dtype=np.float32)
-    d = d * inv[:, None]
-    o32 = org.astype(np.float32)
-    accepted = 0
-    best = C.c_float()
-    L = O.lib()
-    for i in range(n):
-        stage = L.orc_probe_intersect(oracle_scene.h, int(a[i]), o32[i].ctypes.data_as(C.POINTER(C.c_float)),
-                                      d[i].ctypes.data_as(C.POINTER(C.c_float)), 1e-4, np.float32(np.inf), C.byref(best))
-        if stage != 4:
-            continue
-        accepted += 1
-        ci, chain = lay[int(slot_of[a[i]])]
-        o64, d64 = o32[i].astype(np.float64), d[i].astype(np.float64)
-        for sph in [t["cluster_sphere"][ci]] + [t["spheres"][k] for k in chain]:
-            assert _ray_sphere_keep(sph[:3].astype(np.float64), float(sph[3]), o64, d64)
+    # rays aimed at random points of small triangles (inside, on edges, just outside), from random origins
+    accepted, dropped = K.sphere_levels(tor, oracle_scene, np.random.default_rng(17), n, [-9.5, -9.5, -20.5], [9.5, 9.5, 9.5])
+    assert not dropped, dropped[:3]
     assert accepted > 0.5 * n
 
 
@@ -157,47 +112,12 @@ def test_tables_depend_on_eps(tor):
 def test_quads_of_the_room_are_fused_and_never_cull_an_accepted_hit(tor, oracle_scene):
     """Large class: consecutive coplanar triangle pairs share one quad record (plane, alpha row, beta row).  Every
     (ray, wall triangle) pair the reference accepts must satisfy the quad test with the margins the kernel uses."""
-    import ctypes as C
     t = tor.cull_tables()
     large = np.flatnonzero(t["kind"] == 1)
     assert [int(t["level_off"][c][1]) for c in large] == [0b1010101010101]     # quad mask of word 0: walls and light, every pair fused
-    k1, k2, a_max, m0 = (t["constants"][k] for k in ("k1", "k2", "a_max", "m0"))
-    tri, _ = tor.triangles()
-    slot_tri = tor.cull_layout()["slot_triangle"]
-    v = tri[:, 4:13].reshape(-1, 3, 3).astype(np.float64)
-    rng = np.random.default_rng(23)
-    L = O.lib()
-    best = C.c_float()
-    checked = 0
-    for c in large:
-        first, n, off, mask = t["first_tri"][c], t["n_tri"][c], t["data_off"][c], int(t["level_off"][c][1])
-        for k in range(0, n, 2):
-            assert (mask >> k) & 1
-            rec = t["bary"][off + k].astype(np.float64)
-            for half in (0, 1):
-                ti = int(slot_tri[first + k + half])      # slot -> original triangle
-                w = rng.dirichlet([0.5, 0.5, 0.5], 3000) * rng.choice([1.0, 1.0, 1.0005], 3000)[:, None]   # incl. edges / just outside
-                target = (v[ti] * w[:, :, None]).sum(1)
-                org = rng.uniform([-9.5, -9.5, -20.5], [9.5, 9.5, 9.5], (3000, 3))
-                d = (target - org).astype(np.float32)
-                inv = np.float32(1) / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], dtype=np.float32)
-                d = d * inv[:, None]
-                o32 = org.astype(np.float32)
-                for i in range(len(o32)):
-                    st = L.orc_probe_intersect(oracle_scene.h, int(ti), o32[i].ctypes.data_as(C.POINTER(C.c_float)),
-                                               d[i].ctypes.data_as(C.POINTER(C.c_float)), 1e-4, np.float32(np.inf), C.byref(best))
-                    if st != 4:
-                        continue
-                    checked += 1
-                    o64, d64 = o32[i].astype(np.float64), d[i].astype(np.float64)
-                    num, den = rec[0:3] @ o64 + rec[3], rec[0:3] @ d64
-                    tt = -num / den
-                    P = o64 + tt * d64
-                    al, be = rec[4:7] @ P + rec[7], rec[8:11] @ P + rec[11]
-                    e = min(be, al - be, 1 - al) if half == 0 else min(al, be - al, 1 - be)
-                    et = (k1 * abs(tt) + k2) / abs(den)
-                    assert e >= -(a_max * et + m0) and tt >= -et, (ti, e, tt)
-    assert checked > 10000
+    quads, checked, failed = K.quad_records(tor, oracle_scene, np.random.default_rng(23), 3000, [-9.5, -9.5, -20.5], [9.5, 9.5, 9.5])
+    assert not failed, failed[:3]
+    assert quads == 7 and checked > 10000
 
 
 def _shuffled_copy(models_dir, tmp, seed):
@@ -238,7 +158,6 @@ def test_box_tree_never_drops_the_chain_above_a_hit(tmp_path, bvh_mode, request)
     """Big scenes: the chain of box-tree nodes above the triangle the reference hits survives the kernel's slab test
     (numpy restatement in float32, tests/bvh_emulation.py) for the tightest t_best the walk can hold: the hit's own t.
     Both tree builders (pt_scene.cpp: build_bvh, build_bvh_sah), chosen through the test-hook build."""
-    import bvh_emulation as B
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_replicated_scene as M
     d = str(tmp_path) + "/"
@@ -251,48 +170,10 @@ def test_box_tree_never_drops_the_chain_above_a_hit(tmp_path, bvh_mode, request)
     g = pt.Scene.load_obj(d, "x9.obj", device=-1, library=hooks)
     o = O.Scene.load(d, "x9.obj")
     lay = g.cull_layout()
-    t, fl = B.decode(lay["bvh"]), lay["bvh_inner_nodes"]
-    st = lay["slot_triangle"]
-    assert len(lay["bvh"]) > fl > 0 and sorted(st[st >= 0]) == list(range(n_tri))
-    assert (len(lay["bvh"]), fl) == ((491, 65) if bvh_mode == 0 else (516, 110))     # (the two builders' trees for this scene)
-    n_tree_slots = (len(lay["bvh"]) - fl) * 8
-    assert (st[n_tree_slots:] >= 0).all()                          # padding only inside the tree's leaves
-    par, pos = B.parents(t, fl)
-    assert (par[1:] >= 0).all() and par[0] == -1                   # one root, every other node has a parent
-    slot_of = np.full(n_tri, -1)
-    slot_of[st[st >= 0]] = np.flatnonzero(st >= 0)
-    tri, _ = o.triangles()
-    rng = np.random.default_rng(8)
-    n = 60000
-    v = tri[:, 4:13].reshape(-1, 3, 3).astype(np.float64)
-    a = rng.integers(0, n_tri, n)
-    w = rng.dirichlet([1, 1, 1], n)
-    src = ((v[a] * w[:, :, None]).sum(1) + tri[a, 0:3] * 1e-4).astype(np.float32)
-    dd = rng.normal(size=(n, 3)).astype(np.float32)
-    dd[::7, 0] = 0                                                  # some axis-parallel components (the 1e-30 substitution)
-    inv = np.float32(1) / np.sqrt((dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2], dtype=np.float32)
-    dd = (dd * inv[:, None]).astype(np.float32)
-    hi, ht, nan = o.closest_hits(src, dd)
-    ok = (hi >= 0) & ~nan
-    ok &= slot_of[np.maximum(hi, 0)] < n_tree_slots                 # hits on triangles of the tree (not the walls)
-    ro, rd, tb, sl = src[ok], dd[ok], ht[ok], slot_of[hi[ok]]
-    assert len(sl) > 10000
-    leaf_of_group = np.full(n_tree_slots // 8, -1)                  # leaf node that holds slots 8 g ... 8 g + 7
-    leaf_of_group[t["base"][t["leaf"]]] = np.flatnonzero(t["leaf"])
-    assert (leaf_of_group >= 0).all() and t["leaf"].sum() == len(lay["bvh"]) - fl
-    node, child = leaf_of_group[sl // 8], sl % 8
-    levels = 0
-    while len(node):
-        kept = B.children_kept(t, node, ro, rd, tb, 5e-7)
-        assert kept[np.arange(len(node)), child].all(), f"a node of level {levels} above a hit was dropped"
-        # the packed half-precision form of the test (pt_kernels.hip: box_children_kept_h, built with -DPT_BOX_F16=1) on the same items
-        kept_h = B.children_kept_f16(t, node, ro, rd, tb)
-        assert kept_h[np.arange(len(node)), child].all(), f"half precision: a node of level {levels} above a hit was dropped"
-        child, node = pos[node], par[node]
-        live = node >= 0
-        node, child, ro, rd, tb = node[live], child[live], ro[live], rd[live], tb[live]
-        levels += 1
-    assert levels >= 3
+    assert (len(lay["bvh"]), lay["bvh_inner_nodes"]) == ((491, 65) if bvh_mode == 0 else (516, 110))     # (the two builders' trees for this scene)
+    hits, levels, dropped = K.box_chain(g, o, np.random.default_rng(8), 60000)
+    assert not dropped, f"a node above a hit was dropped (level, form, rays): {dropped}"
+    assert hits > 10000 and levels >= 3
 
 
 def test_big_scene_keeps_its_few_emitters_in_the_large_class(tmp_path, models_dir):

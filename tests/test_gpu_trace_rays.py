@@ -7,56 +7,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from scene_transforms import adversarial_rays as _adversarial_rays, normalise as _normalise
 
 pt = importlib.import_module("path-tracing_amd")
 pytestmark = pytest.mark.gpu
-
-
-def _normalise(d):
-    """Ray's constructor (ray.h:23): v * (1 / sqrt((x*x + y*y) + z*z)) in float32."""
-    d = np.ascontiguousarray(d, np.float32)
-    inv = np.float32(1.0) / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], dtype=np.float32)
-    return (d * inv[:, None]).astype(np.float32)
-
-
-def _adversarial_rays(tri, rng, n):
-    T = len(tri)
-    v = tri[:, 4:13].reshape(T, 3, 3).astype(np.float64)
-    nrm = tri[:, 0:3].astype(np.float64)
-    O_, D_ = [], []
-    # (1) random interior origins, random directions
-    o = rng.uniform([-9.9, -9.9, -20.9], [9.9, 9.9, 9.9], (n, 3))
-    d = rng.normal(size=(n, 3))
-    O_.append(o); D_.append(d)
-    # (2) from a surface point (+eps*N like the lobes do) towards a point on another triangle's EDGE or VERTEX
-    a, b = rng.integers(0, T, n), rng.integers(0, T, n)
-    w = rng.dirichlet([1, 1, 1], n)
-    src = (v[a] * w[:, :, None]).sum(1) + nrm[a] * 1e-4
-    e = rng.random((n, 1))
-    kind = rng.integers(0, 3, n)
-    tgt = np.where((kind == 0)[:, None], v[b, 0], np.where((kind == 1)[:, None], v[b, 0] * e + v[b, 1] * (1 - e),
-                                                           v[b, 1] * e + v[b, 2] * (1 - e)))
-    O_.append(src); D_.append(tgt - src)
-    # (3) grazing: direction in the plane of a triangle, tilted by a tiny angle, from just above that plane
-    a = rng.integers(0, T, n)
-    tang = v[a, 1] - v[a, 0]
-    tang /= np.linalg.norm(tang, axis=1, keepdims=True) + 1e-30
-    tilt = rng.choice([0.0, 1e-7, -1e-7, 1e-5, -1e-5, 1e-3, -1e-3], n)[:, None]
-    src = (v[a] * w[:, :, None]).sum(1) + nrm[a] * rng.choice([0.0, 1e-4, -1e-4, 1e-2], n)[:, None] - tang * rng.uniform(0, 5, (n, 1))
-    O_.append(src); D_.append(tang + tilt * nrm[a])
-    # (4) axis-aligned directions and origins on lattice points (exact zeros in products)
-    o = rng.integers(-9, 10, (n, 3)).astype(np.float64)
-    d = np.zeros((n, 3)); d[np.arange(n), rng.integers(0, 3, n)] = rng.choice([-1.0, 1.0], n)
-    O_.append(o); D_.append(d)
-    # (5) towards the centroid of a random triangle, from far and from very near
-    a = rng.integers(0, T, n)
-    cen = v[a].mean(1)
-    src = np.where(rng.random((n, 1)) < 0.5, rng.uniform(-9, 9, (n, 3)), cen + rng.normal(size=(n, 3)) * 1e-3)
-    O_.append(src); D_.append(cen - src + 1e-12)
-    o = np.concatenate(O_).astype(np.float32)
-    d = _normalise(np.concatenate(D_).astype(np.float32))
-    ok = np.isfinite(d).all(1)
-    return o[ok], d[ok]
 
 
 def _check(g, o_scene, o, d, eps=1e-4):
