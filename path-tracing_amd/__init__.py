@@ -251,6 +251,9 @@ def load_library(path):
     L.pt_temporal_destroy.restype = None
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
+    if hasattr(L, "pt_test_live_device_objects"):
+        L.pt_test_live_device_objects.argtypes = []
+        L.pt_test_live_device_objects.restype = C.c_long
     return L
 
 

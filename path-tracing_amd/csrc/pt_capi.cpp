@@ -31,17 +31,14 @@ int hip_fail(hipError_t e, const char *what) {
     return fail(code, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-void ctx_destroy(LaunchCtx &c) {
-    if (c.d_sched) (void)hipFree(c.d_sched);
-    if (c.d_stats) (void)hipFree(c.d_stats);
-    if (c.ev0) (void)hipEventDestroy(c.ev0);
-    if (c.ev1) (void)hipEventDestroy(c.ev1);
-    if (c.ev_done) (void)hipEventDestroy(c.ev_done);
-    c.d_sched = nullptr;
-    c.d_stats = nullptr;
-    c.ev0 = c.ev1 = c.ev_done = nullptr;
-    c.sched_words = 0;
-    c.has_prev = false;
+std::atomic<long> g_live_device_objects{0};
+
+int use_device(int device, const char *stage) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n)
+        return fail(PT_ERR_NO_DEVICE, std::string(stage) + ": device " + std::to_string(device) + " is not a visible HIP device (there is no CPU fallback)");
+    PT_HIP_TRY(hipSetDevice(device));
+    return PT_OK;
 }
 
 }  // namespace ptc
@@ -105,51 +102,27 @@ int get_cull(pt_scene_host &h, float eps, double r_camera, std::shared_ptr<const
 }
 
 int upload(pt_scene *s, int device) {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(PT_ERR_NO_DEVICE, "no HIP device is visible: the integrator has no CPU fallback");
-    if (device >= n) return fail(PT_ERR_NO_DEVICE, "device ordinal " + std::to_string(device) + " out of range");
+    int rc = ptc::use_device(device, "scene");
+    if (rc != PT_OK) return rc;
     s->device = device;
-    PT_HIP_TRY(hipSetDevice(device));
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) s->cu_count = cus;
     const auto &t = s->shared->tables;
-    PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_exact), t.exact.size() * sizeof(pt::ExactRec) + 64));
-    PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_mats), t.mats.size() * sizeof(pt::MatRec) + 64));
-    if (!t.exact.empty()) PT_HIP_TRY(hipMemcpy(s->d_exact, t.exact.data(), t.exact.size() * sizeof(pt::ExactRec), hipMemcpyHostToDevice));
-    if (!t.mats.empty()) PT_HIP_TRY(hipMemcpy(s->d_mats, t.mats.data(), t.mats.size() * sizeof(pt::MatRec), hipMemcpyHostToDevice));
+    if ((rc = s->d_exact.upload(t.exact, "exact records", 64)) != PT_OK || (rc = s->d_mats.upload(t.mats, "materials", 64)) != PT_OK) return rc;
     if (s->sky && !s->sky->texels.empty()) {   // (a copy's skybox is the one of the handle it was made from)
-        const auto &sky = s->sky->texels;
-        PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_sky), sky.size() + 64));
-        PT_HIP_TRY(hipMemcpy(s->d_sky, sky.data(), sky.size(), hipMemcpyHostToDevice));
+        if ((rc = s->d_sky.upload(s->sky->texels, "skybox", 64)) != PT_OK) return rc;
         s->sky_w = s->sky->w;
         s->sky_h = s->sky->h;
     }
     return PT_OK;
 }
 
-// events / statistics block of a launch context, on first use (the scene's device is current)
-int ctx_ready(LaunchCtx &c) {
-    if (!c.ev_done) PT_HIP_TRY(hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming));
-    return PT_OK;
-}
+// statistics block and timing events of a launch context, on first use (the scene's device is current)
 int ctx_stats_ready(LaunchCtx &c) {
-    if (!c.d_stats) PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c.d_stats), 24 * sizeof(unsigned long long)));
-    if (!c.ev0) PT_HIP_TRY(hipEventCreate(&c.ev0));
-    if (!c.ev1) PT_HIP_TRY(hipEventCreate(&c.ev1));
-    return PT_OK;
-}
-
-template <class T>
-int upload_vec(const std::vector<T> &v, T **dst) {
-    if (*dst) {
-        (void)hipFree(*dst);
-        *dst = nullptr;
-    }
-    PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(T) + 256));
-    if (!v.empty()) PT_HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return PT_OK;
+    int rc = c.d_stats ? static_cast<int>(PT_OK) : c.d_stats.alloc(24 * sizeof(unsigned long long), "statistics block");
+    if (rc == PT_OK && !c.ev0) rc = c.ev0.create("statistics");
+    if (rc == PT_OK && !c.ev1) rc = c.ev1.create("statistics");
+    return rc;
 }
 
 // The cull hierarchy's radii and margins depend on eps (-EPS): upload on first use, replace if eps changes.
@@ -157,8 +130,7 @@ int upload_vec(const std::vector<T> &v, T **dst) {
 // must not free the tables between this call and that launch.
 const pt_camera kReferenceCamera = {{0.0f, 0.0f, -20.0f}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}};   // main.cpp:126-129
 
-// The camera primary rays are made from: the handle's, or the reference's fixed one.
-const pt_camera &view_camera(const pt_scene *s) { return s->has_camera ? s->camera : kReferenceCamera; }
+using ptc::view_camera;
 
 // r^, u^, f^ of a lens on camera c (pt_hip.h: pt_lens): right, up, forward normalised in double, rounded to float once.
 void lens_axes(const pt_camera &c, float out[9]) {
@@ -206,20 +178,13 @@ int ensure_cull(pt_scene *s, float eps) {
     if (c.valid) PT_HIP_TRY(hipDeviceSynchronize());   // a previous launch may still read the old tables
     c.valid = false;
     c.host = t;
-    if ((rc = upload_vec(t->clusters, &c.clusters)) != PT_OK) return rc;
-    if ((rc = upload_vec(t->spheres, &c.spheres)) != PT_OK) return rc;
-    if ((rc = upload_vec(t->bary, &c.bary)) != PT_OK) return rc;
-    if (c.bary_all) {
-        (void)hipFree(c.bary_all);
-        c.bary_all = nullptr;
-    }
-    if (!t->bary_all.empty() && (rc = upload_vec(t->bary_all, &c.bary_all)) != PT_OK) return rc;
-    if ((rc = upload_vec(t->exact_slot, &c.exact_slot)) != PT_OK) return rc;
-    if (c.bvh) {
-        (void)hipFree(c.bvh);
-        c.bvh = nullptr;
-    }
-    if (!t->bvh.empty() && (rc = upload_vec(t->bvh, &c.bvh)) != PT_OK) return rc;
+    const char *what = "cull tables";
+    if ((rc = c.clusters.upload(t->clusters, what)) != PT_OK || (rc = c.spheres.upload(t->spheres, what)) != PT_OK || (rc = c.bary.upload(t->bary, what)) != PT_OK) return rc;
+    c.bary_all.reset();   // (and bvh: no table where the host vector is empty)
+    if (!t->bary_all.empty() && (rc = c.bary_all.upload(t->bary_all, what)) != PT_OK) return rc;
+    if ((rc = c.exact_slot.upload(t->exact_slot, what)) != PT_OK) return rc;
+    c.bvh.reset();
+    if (!t->bvh.empty() && (rc = c.bvh.upload(t->bvh, what)) != PT_OK) return rc;
     c.eps = eps;
     c.r_max = t->r_max;
     c.valid = true;
@@ -252,19 +217,19 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
     std::memset(&a, 0, sizeof a);
     const pt::CullTables &t = *scene->cull.host;
     const pt::CullConstants &cc = t.cc, &ca = t.cc_all;
-    a.clusters = scene->cull.clusters;
-    a.spheres = scene->cull.spheres;
-    a.bary = scene->cull.bary;
-    a.bary_all = scene->cull.bary_all;
+    a.clusters = scene->cull.clusters.get<pt::ClusterDesc>();
+    a.spheres = scene->cull.spheres.get<pt::SphereRec>();
+    a.bary = scene->cull.bary.get<pt::CullRec>();
+    a.bary_all = scene->cull.bary_all.get<pt::CullRec>();
     a.a_max_all = ca.a_max; a.m0_all = ca.m0; a.t_guard_all = ca.t_guard;
-    a.exact = scene->d_exact;
-    a.exact_slot = scene->cull.exact_slot;
-    a.bvh = scene->cull.bvh;
+    a.exact = scene->d_exact.get<pt::ExactRec>();
+    a.exact_slot = scene->cull.exact_slot.get<pt::ExactRec>();
+    a.bvh = scene->cull.bvh.get<pt::BvhNode>();
     a.n_bvh = static_cast<uint32_t>(t.bvh.size());
     a.bvh_err = t.bvh_err;
-    a.mats = scene->d_mats;
+    a.mats = scene->d_mats.get<pt::MatRec>();
     a.n_mats = static_cast<int32_t>(scene->shared->tables.mats.size());
-    a.sky = scene->d_sky;
+    a.sky = scene->d_sky.get<uint8_t>();
     a.sky_w = scene->d_sky ? scene->sky_w : 0;
     a.sky_h = scene->d_sky ? scene->sky_h : 0;
     a.n_clusters = static_cast<int32_t>(t.clusters.size());
@@ -302,8 +267,8 @@ void zero_stats(const pt_scene *scene, pt_render_stats *stats) {
 
 // Enqueue one integrator launch on `stream` for the context `ctx` (its scheduler words, its statistics block).  Never waits
 // for the device except to grow the scheduler words.  The caller holds ctx.mutex.
-int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, float *d_sum, float *d_sum2, int32_t *d_count,
-                   hipStream_t stream, bool want_stats) {
+int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, const ptc::AccumPlanes &planes, hipStream_t stream,
+                   bool want_stats) {
     ctx.stats_pending = false;
     ctx.last_chunks = 0;
     PT_HIP_TRY(hipSetDevice(scene->device));
@@ -313,10 +278,10 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, f
     pt::RenderArgs a;
     fill_scene_args(scene, p->eps, a);
     a.vec_ok = (p->width % 4 == 0) &&
-               ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_sum2) | reinterpret_cast<uintptr_t>(d_count)) % 16 == 0);
-    a.sum = d_sum;
-    a.sum2 = d_sum2;
-    a.count = d_count;
+               ((reinterpret_cast<uintptr_t>(planes.sum) | reinterpret_cast<uintptr_t>(planes.sum2) | reinterpret_cast<uintptr_t>(planes.count)) % 16 == 0);
+    a.sum = planes.sum;
+    a.sum2 = planes.sum2;
+    a.count = planes.count;
     a.width = p->width; a.height = p->height; a.row_begin = p->row_begin; a.row_end = p->row_end;
     a.row_stride = std::max(1, p->row_stride);
     a.band_rows = ptc::band_rows(p);
@@ -325,11 +290,11 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, f
     a.pass_begin = p->pass_begin; a.pass_count = p->pass_count; a.mrr = p->max_ray_reflections;
     a.error = p->error; a.seed = p->seed;
     if (p->row_end == p->row_begin) return PT_OK;
-    int rc = ctx_ready(ctx);
-    if (rc != PT_OK) return rc;
+    int rc;
+    if (!ctx.ev_done && (rc = ctx.ev_done.create("launch context", hipEventDisableTiming)) != PT_OK) return rc;
     if (want_stats) {
         if ((rc = ctx_stats_ready(ctx)) != PT_OK) return rc;
-        a.stats = ctx.d_stats;
+        a.stats = ctx.d_stats.get<unsigned long long>();
     }
     // one wave = one tile of 8 rows; how many pixels wide depends on the kernel this launch runs
     const pt::plan::Tiles tiles = pt::plan::plan_tiles({a.width, a.band_rows, a.sky != nullptr, a.big != 0, want_stats, a.may_leave_envelope != 0, a.error,
@@ -344,27 +309,24 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, f
     const uint32_t slots = static_cast<uint32_t>(scene->cu_count) * static_cast<uint32_t>(std::max(1, waves_per_cu));
     const auto [n_chunks, chunk_passes] = pt::plan::plan_chunks(n_tiles, slots, p->pass_count, a.sky != nullptr, a.narrow != 0, want_stats, ov);
     if (static_cast<unsigned long long>(n_tiles) * n_chunks > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "too many work items");
-    if (ctx.has_prev && ctx.prev_stream != stream) PT_HIP_TRY(hipStreamWaitEvent(stream, ctx.ev_done, 0));
-    if (ctx.sched_words < 1 + static_cast<size_t>(n_tiles)) {
+    if (ctx.has_prev && ctx.prev_stream != stream) PT_HIP_TRY(hipStreamWaitEvent(stream, ctx.ev_done.get(), 0));
+    const size_t sched_bytes = (1 + static_cast<size_t>(n_tiles)) * sizeof(uint32_t);
+    if (ctx.d_sched.bytes() < sched_bytes) {
         if (ctx.has_prev) PT_HIP_TRY(hipStreamSynchronize(stream));   // an earlier launch of this context may still use the old words
-        if (ctx.d_sched) (void)hipFree(ctx.d_sched);
-        ctx.d_sched = nullptr;
-        ctx.sched_words = 0;
-        PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx.d_sched), (1 + static_cast<size_t>(n_tiles)) * sizeof(uint32_t)));
-        ctx.sched_words = 1 + static_cast<size_t>(n_tiles);
+        if ((rc = ctx.d_sched.alloc(sched_bytes, "scheduler words")) != PT_OK) return rc;
     }
-    PT_HIP_TRY(hipMemsetAsync(ctx.d_sched, 0, (1 + static_cast<size_t>(n_tiles)) * sizeof(uint32_t), stream));
-    a.sched = ctx.d_sched;
+    PT_HIP_TRY(hipMemsetAsync(ctx.d_sched.get<void>(), 0, sched_bytes, stream));
+    a.sched = ctx.d_sched.get<uint32_t>();
     a.n_tiles = n_tiles;
     a.n_chunks = n_chunks;
     a.chunk_passes = chunk_passes;
     if (want_stats) {
-        PT_HIP_TRY(hipMemsetAsync(ctx.d_stats, 0, 24 * sizeof(unsigned long long), stream));
-        PT_HIP_TRY(hipEventRecord(ctx.ev0, stream));
+        PT_HIP_TRY(hipMemsetAsync(ctx.d_stats.get<void>(), 0, 24 * sizeof(unsigned long long), stream));
+        PT_HIP_TRY(hipEventRecord(ctx.ev0.get(), stream));
     }
     PT_HIP_TRY(pt::launch_integrator(a, tiles.variant, stream));
-    if (want_stats) PT_HIP_TRY(hipEventRecord(ctx.ev1, stream));
-    PT_HIP_TRY(hipEventRecord(ctx.ev_done, stream));
+    if (want_stats) PT_HIP_TRY(hipEventRecord(ctx.ev1.get(), stream));
+    PT_HIP_TRY(hipEventRecord(ctx.ev_done.get(), stream));
     ctx.has_prev = true;
     ctx.prev_stream = stream;
     ctx.last_chunks = n_chunks;
@@ -379,10 +341,10 @@ int collect_stats(pt_scene *scene, LaunchCtx &ctx, hipStream_t stream, pt_render
     ctx.stats_pending = false;
     PT_HIP_TRY(hipSetDevice(scene->device));
     unsigned long long h[24];
-    PT_HIP_TRY(hipMemcpyAsync(h, ctx.d_stats, sizeof h, hipMemcpyDeviceToHost, stream));
+    PT_HIP_TRY(hipMemcpyAsync(h, ctx.d_stats.get<void>(), sizeof h, hipMemcpyDeviceToHost, stream));
     PT_HIP_TRY(hipStreamSynchronize(stream));
     float ms = -1.0f;
-    PT_HIP_TRY(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1));
+    PT_HIP_TRY(hipEventElapsedTime(&ms, ctx.ev0.get(), ctx.ev1.get()));
     stats->samples_traced = h[0];
     stats->segments = h[1];
     stats->contributing = h[2];
@@ -443,36 +405,30 @@ int check_params(const pt_scene *scene, const pt_render_params *p) {
     return PT_OK;
 }
 
-int session_create_on(pt_scene *scene, int32_t width, int32_t height, int32_t row_begin, int32_t row_end, float *d_sum,
-                      float *d_sum2, int32_t *d_count, pt_session **out, int32_t row_stride) {
+int session_create_on(pt_scene *scene, int32_t width, int32_t height, int32_t row_begin, int32_t row_end, const AccumPlanes *borrowed,
+                      pt_session **out, int32_t row_stride) {
     if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     pt_render_params p;
     std::memset(&p, 0, sizeof p);
     p.width = width; p.height = height; p.row_begin = row_begin; p.row_end = row_end; p.row_stride = row_stride;
-    const int rc = check_params(scene, &p);
+    int rc = check_params(scene, &p);
     if (rc != PT_OK) return rc;
     PT_HIP_TRY(hipSetDevice(scene->device));
     std::unique_ptr<pt_session> s(new pt_session);
     s->scene = scene;
     s->width = width; s->height = height; s->row_begin = row_begin; s->row_end = row_end; s->row_stride = std::max(1, row_stride);
     s->n = static_cast<size_t>(band_rows(&p)) * width;
-    PT_HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    hipError_t e = hipSuccess;
-    if (d_sum) {   // borrowed planes: the caller zeroes and frees them
-        s->d_sum = d_sum; s->d_sum2 = d_sum2; s->d_count = d_count;
+    if ((rc = s->stream.create("pt_session_create")) != PT_OK) return rc;
+    if (borrowed) {   // the caller zeroes and frees them
+        s->planes = *borrowed;
+        s->planes.n = s->n;
     } else {
-        const size_t plane_floats = (3 * s->n + 63) / 64 * 64;
-        const size_t bytes = (2 * plane_floats + s->n) * sizeof(float) + 256;
-        e = hipMalloc(reinterpret_cast<void **>(&s->d_band), bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_band, 0, bytes, s->stream);
-        s->d_sum = s->d_band; s->d_sum2 = s->d_band + plane_floats;
-        s->d_count = reinterpret_cast<int32_t *>(s->d_band + 2 * plane_floats);
-    }
-    if (e != hipSuccess) {
-        if (s->d_band) (void)hipFree(s->d_band);
-        (void)hipStreamDestroy(s->stream);
-        return hip_fail(e, "pt_session_create");
+        PlaneLayout l;
+        s->planes = AccumPlanes::in(l, s->n);
+        if ((rc = s->d_band.alloc(l.end + 256, "pt_session_create")) != PT_OK) return rc;
+        PT_HIP_TRY(hipMemsetAsync(s->d_band.get<void>(), 0, s->d_band.bytes(), s->stream.get()));
+        s->planes.bind(s->d_band);
     }
     *out = s.release();
     return PT_OK;
@@ -485,10 +441,10 @@ int session_enqueue(pt_session *s, const pt_render_params *p, bool want_stats) {
         return fail(PT_ERR_INVALID_ARGUMENT, "params describe another band than the session's");
     const int rc = check_params(s->scene, p);
     if (rc != PT_OK) return rc;
-    return enqueue_render(s->scene, s->ctx, p, s->d_sum, s->d_sum2, s->d_count, s->stream, want_stats);
+    return enqueue_render(s->scene, s->ctx, p, s->planes, s->stream.get(), want_stats);
 }
 
-const pt_camera &view_camera(const pt_scene *s) { return ::view_camera(s); }
+const pt_camera &view_camera(const pt_scene *s) { return s->has_camera ? s->camera : kReferenceCamera; }
 
 int scene_trace_args(pt_scene *scene, float eps, pt::RenderArgs &a) {
     const int rc = ensure_cull(scene, eps);
@@ -499,7 +455,7 @@ int scene_trace_args(pt_scene *scene, float eps, pt::RenderArgs &a) {
 
 int session_collect(pt_session *s, pt_render_stats *stats) {
     if (!s || !stats) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    return collect_stats(s->scene, s->ctx, s->stream, stats);
+    return collect_stats(s->scene, s->ctx, s->stream.get(), stats);
 }
 
 }  // namespace ptc
@@ -647,14 +603,9 @@ static int scene_set_skybox_bmp_impl(pt_scene *scene, const char *path) {
     if (scene->device >= 0) {
         PT_HIP_TRY(hipSetDevice(scene->device));
         PT_HIP_TRY(hipDeviceSynchronize());
-        if (scene->d_sky) {
-            (void)hipFree(scene->d_sky);
-            scene->d_sky = nullptr;
-        }
-        if (!texels.empty()) {
-            PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&scene->d_sky), texels.size() + 64));
-            PT_HIP_TRY(hipMemcpy(scene->d_sky, texels.data(), texels.size(), hipMemcpyHostToDevice));
-        }
+        scene->d_sky.reset();
+        int rc;
+        if (!texels.empty() && (rc = scene->d_sky.upload(texels, "skybox", 64)) != PT_OK) return rc;
     }
     // (per-device copies made from THIS handle afterwards inherit the skybox; other handles of the same model keep theirs)
     scene->sky_w = w;
@@ -829,25 +780,7 @@ int pt_scene_get_materials(const pt_scene *scene, float *materials) {
     return PT_OK;
 }
 
-void pt_scene_destroy(pt_scene *s) {
-    if (!s) return;
-    if (s->device >= 0) {
-        (void)hipSetDevice(s->device);
-        if (s->cull.clusters) (void)hipFree(s->cull.clusters);
-        if (s->cull.spheres) (void)hipFree(s->cull.spheres);
-        if (s->cull.bary) (void)hipFree(s->cull.bary);
-        if (s->cull.bary_all) (void)hipFree(s->cull.bary_all);
-        if (s->cull.exact_slot) (void)hipFree(s->cull.exact_slot);
-        if (s->cull.bvh) (void)hipFree(s->cull.bvh);
-        if (s->d_exact) (void)hipFree(s->d_exact);
-        if (s->d_mats) (void)hipFree(s->d_mats);
-        if (s->d_sky) (void)hipFree(s->d_sky);
-        if (s->d_host_band) (void)hipFree(s->d_host_band);
-        if (s->host_stream) (void)hipStreamDestroy(s->host_stream);
-        ptc::ctx_destroy(s->ctx);
-    }
-    delete s;
-}
+void pt_scene_destroy(pt_scene *s) { delete s; }   // (~pt_scene makes the scene's device current for its owners)
 
 static int render_device_impl(pt_scene *scene, const pt_render_params *p, float *d_sum, float *d_sum2, int32_t *d_count,
                      void *hip_stream, pt_render_stats *stats) {
@@ -856,7 +789,7 @@ static int render_device_impl(pt_scene *scene, const pt_render_params *p, float 
     if (!d_sum || !d_sum2 || !d_count) return fail(PT_ERR_INVALID_ARGUMENT, "null accumulator pointer");
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     std::lock_guard<std::mutex> ctx_lock(scene->ctx.mutex);
-    const int r = enqueue_render(scene, scene->ctx, p, d_sum, d_sum2, d_count, stream, stats != nullptr);
+    const int r = enqueue_render(scene, scene->ctx, p, {d_sum, d_sum2, d_count, 0}, stream, stats != nullptr);
     if (r != PT_OK || !stats) return r;
     return collect_stats(scene, scene->ctx, stream, stats);
 }
@@ -874,26 +807,19 @@ static int trace_rays_host_impl(pt_scene *scene, int32_t n_rays, const float *or
     if (crc != PT_OK) return crc;
     pt::RenderArgs a;
     fill_scene_args(scene, eps, a);
-    float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr;
-    int32_t *d_i = nullptr;
+    ptc::DeviceBuffer d_o, d_d, d_t, d_i;
     const size_t n = static_cast<size_t>(n_rays);
-    int result = PT_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_o), n * 12);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_d), n * 12);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_t), n * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_i), n * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_o, origins, n * 12, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_d, directions, n * 12, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = pt::launch_trace_rays(a, d_o, d_d, n_rays, d_i, d_t, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(hit_index, d_i, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hit_t, d_t, n * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) result = hip_fail(e, "pt_trace_rays_host");
-    if (d_o) (void)hipFree(d_o);
-    if (d_d) (void)hipFree(d_d);
-    if (d_t) (void)hipFree(d_t);
-    if (d_i) (void)hipFree(d_i);
-    return result;
+    int rc;
+    if ((rc = d_o.alloc(n * 12, "pt_trace_rays_host")) != PT_OK || (rc = d_d.alloc(n * 12, "pt_trace_rays_host")) != PT_OK ||
+        (rc = d_t.alloc(n * 4, "pt_trace_rays_host")) != PT_OK || (rc = d_i.alloc(n * 4, "pt_trace_rays_host")) != PT_OK)
+        return rc;
+    PT_HIP_TRY(hipMemcpy(d_o.get<void>(), origins, n * 12, hipMemcpyHostToDevice));
+    PT_HIP_TRY(hipMemcpy(d_d.get<void>(), directions, n * 12, hipMemcpyHostToDevice));
+    PT_HIP_TRY(pt::launch_trace_rays(a, d_o.get<float>(), d_d.get<float>(), n_rays, d_i.get<int32_t>(), d_t.get<float>(), nullptr));
+    PT_HIP_TRY(hipDeviceSynchronize());
+    PT_HIP_TRY(hipMemcpy(hit_index, d_i.get<void>(), n * 4, hipMemcpyDeviceToHost));
+    PT_HIP_TRY(hipMemcpy(hit_t, d_t.get<void>(), n * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 static int render_host_impl(pt_scene *scene, const pt_render_params *p, float *sum, float *sum2, int32_t *count,
@@ -910,32 +836,21 @@ static int render_host_impl(pt_scene *scene, const pt_render_params *p, float *s
     }
     std::lock_guard<std::mutex> host_lock(scene->host_mutex);
     // device band (sum | sum2 | count planes, 256-byte aligned planes), grown on demand and kept
-    const size_t plane = (3 * n + 63) / 64 * 64;
-    if (scene->host_band_floats < 2 * plane + n) {
-        if (scene->d_host_band) (void)hipFree(scene->d_host_band);
-        scene->d_host_band = nullptr;
-        scene->host_band_floats = 0;
-        PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&scene->d_host_band), (2 * plane + n) * sizeof(float) + 256));
-        scene->host_band_floats = 2 * plane + n;
-    }
-    if (!scene->host_stream) PT_HIP_TRY(hipStreamCreateWithFlags(&scene->host_stream, hipStreamNonBlocking));
-    float *d_sum = scene->d_host_band, *d_sum2 = d_sum + plane;
-    int32_t *d_count = reinterpret_cast<int32_t *>(d_sum2 + plane);
+    ptc::PlaneLayout l;
+    ptc::AccumPlanes band = ptc::AccumPlanes::in(l, n);
+    int r;
+    if (scene->d_host_band.bytes() < l.end + 256 && (r = scene->d_host_band.alloc(l.end + 256, "pt_render_host")) != PT_OK) return r;
+    if (!scene->host_stream && (r = scene->host_stream.create("pt_render_host")) != PT_OK) return r;
+    band.bind(scene->d_host_band);
     // One launch for the whole band between plain synchronous copies.  (Measured and dropped: cutting the band into row
     // slabs so that copies overlap kernels.  A tile's passes run strictly in order, so every launch lasts at least one
     // tile's whole pass chain -- 13.6 ms at 256 spp whatever the slab's height -- and ten slabs took 189 ms where one
     // launch takes 96 ms + 3.4 ms of copies; profiles/r02_host_path_slabs.txt.  hipMemcpyAsync into pageable memory ran
     // at about 1 GB/s here, the synchronous call at PCIe speed.)
-    PT_HIP_TRY(hipMemcpy(d_sum, sum, n * 12, hipMemcpyHostToDevice));
-    PT_HIP_TRY(hipMemcpy(d_sum2, sum2, n * 12, hipMemcpyHostToDevice));
-    PT_HIP_TRY(hipMemcpy(d_count, count, n * 4, hipMemcpyHostToDevice));
-    const int r = render_device_impl(scene, p, d_sum, d_sum2, d_count, scene->host_stream, stats);
-    if (r != PT_OK) return r;
-    PT_HIP_TRY(hipStreamSynchronize(scene->host_stream));
-    PT_HIP_TRY(hipMemcpy(sum, d_sum, n * 12, hipMemcpyDeviceToHost));
-    PT_HIP_TRY(hipMemcpy(sum2, d_sum2, n * 12, hipMemcpyDeviceToHost));
-    PT_HIP_TRY(hipMemcpy(count, d_count, n * 4, hipMemcpyDeviceToHost));
-    return PT_OK;
+    if ((r = band.upload(sum, sum2, count)) != PT_OK) return r;
+    if ((r = render_device_impl(scene, p, band.sum, band.sum2, band.count, scene->host_stream.get(), stats)) != PT_OK) return r;
+    PT_HIP_TRY(hipStreamSynchronize(scene->host_stream.get()));
+    return band.download(sum, sum2, count);
 }
 
 static int session_render_impl(pt_session *s, const pt_render_params *p, pt_render_stats *stats) {
@@ -952,19 +867,16 @@ static int session_read_impl(pt_session *s, float *sum, float *sum2, int32_t *co
     PT_HIP_TRY(hipSetDevice(s->scene->device));
     // wait for the session's kernels, then plain synchronous copies: the runtime's fast path for pageable destinations
     // (hipMemcpyAsync into pageable memory ran at about 1 GB/s here)
-    PT_HIP_TRY(hipStreamSynchronize(s->stream));
-    PT_HIP_TRY(hipMemcpy(sum, s->d_sum, 3 * s->n * sizeof(float), hipMemcpyDeviceToHost));
-    PT_HIP_TRY(hipMemcpy(sum2, s->d_sum2, 3 * s->n * sizeof(float), hipMemcpyDeviceToHost));
-    PT_HIP_TRY(hipMemcpy(count, s->d_count, s->n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return PT_OK;
+    PT_HIP_TRY(hipStreamSynchronize(s->stream.get()));
+    return s->planes.download(sum, sum2, count);
 }
 
 static int session_clear_impl(pt_session *s) {
     if (!s) return fail(PT_ERR_INVALID_ARGUMENT, "null session");
     PT_HIP_TRY(hipSetDevice(s->scene->device));
-    PT_HIP_TRY(hipMemsetAsync(s->d_sum, 0, 3 * s->n * sizeof(float), s->stream));
-    PT_HIP_TRY(hipMemsetAsync(s->d_sum2, 0, 3 * s->n * sizeof(float), s->stream));
-    PT_HIP_TRY(hipMemsetAsync(s->d_count, 0, s->n * sizeof(int32_t), s->stream));
+    PT_HIP_TRY(hipMemsetAsync(s->planes.sum, 0, 3 * s->n * sizeof(float), s->stream.get()));
+    PT_HIP_TRY(hipMemsetAsync(s->planes.sum2, 0, 3 * s->n * sizeof(float), s->stream.get()));
+    PT_HIP_TRY(hipMemsetAsync(s->planes.count, 0, s->n * sizeof(int32_t), s->stream.get()));
     return PT_OK;
 }
 
@@ -1117,17 +1029,14 @@ static int post_filter_host_impl(int device, int32_t width, int32_t height, floa
     if (gauss < 0 || median < 0) return fail(PT_ERR_INVALID_ARGUMENT, "negative filter size");
     if (median * median / 2 > pt::kMedianMaxRank) return fail(PT_ERR_INVALID_ARGUMENT, "-MEDIAN window larger than 11 is not supported");
     if (!gauss && !median) return PT_OK;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device < 0 || device >= n_dev)
-        return fail(PT_ERR_NO_DEVICE, "no usable HIP device for the post filters (there is no CPU fallback)");
-    PT_HIP_TRY(hipSetDevice(device));
+    int rc = ptc::use_device(device, "post filters");
+    if (rc != PT_OK) return rc;
     const size_t bytes = static_cast<size_t>(width) * height * 3 * sizeof(float);
-    float *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
-    int result = PT_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_a), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_b), bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_a, rgb, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && gauss) {   // main.cpp:187-189
+    ptc::DeviceBuffer buf_a, buf_b, d_w;
+    if ((rc = buf_a.alloc(bytes, "pt_post_filter_host")) != PT_OK || (rc = buf_b.alloc(bytes, "pt_post_filter_host")) != PT_OK) return rc;
+    float *d_a = buf_a.get<float>(), *d_b = buf_b.get<float>();   // input and output of the next filter
+    PT_HIP_TRY(hipMemcpy(d_a, rgb, bytes, hipMemcpyHostToDevice));
+    if (gauss) {   // main.cpp:187-189
         const float r = static_cast<float>(gauss), pi = 3.141593f;
         const int rs = static_cast<int>(std::ceil(r * 2.57));
         const int side = 2 * rs + 1;
@@ -1137,22 +1046,18 @@ static int post_filter_host_impl(int device, int32_t width, int32_t height, floa
                 const int dsq = dx * dx + dy * dy;
                 w[static_cast<size_t>(dy + rs) * side + (dx + rs)] = std::exp(-dsq / (2 * r * r)) / (pi * 2 * r * r);   // main.cpp:25
             }
-        e = hipMalloc(reinterpret_cast<void **>(&d_w), w.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(d_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = pt::launch_gauss(d_a, d_b, d_w, width, height, rs, nullptr);
+        if ((rc = d_w.alloc(w.size() * sizeof(float), "pt_post_filter_host")) != PT_OK) return rc;
+        PT_HIP_TRY(hipMemcpy(d_w.get<void>(), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        PT_HIP_TRY(pt::launch_gauss(d_a, d_b, d_w.get<float>(), width, height, rs, nullptr));
         std::swap(d_a, d_b);
     }
-    if (e == hipSuccess && median) {   // main.cpp:190-192
-        e = pt::launch_median(d_a, d_b, width, height, median, nullptr);
+    if (median) {   // main.cpp:190-192
+        PT_HIP_TRY(pt::launch_median(d_a, d_b, width, height, median, nullptr));
         std::swap(d_a, d_b);
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(rgb, d_a, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) result = hip_fail(e, "pt_post_filter_host");
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (d_w) (void)hipFree(d_w);
-    return result;
+    PT_HIP_TRY(hipDeviceSynchronize());
+    PT_HIP_TRY(hipMemcpy(rgb, d_a, bytes, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb) {
@@ -1269,11 +1174,11 @@ int32_t pt_band_rows(const pt_render_params *params) { return params ? ptc::band
 
 int pt_session_create_strided(pt_scene *scene, int32_t width, int32_t height, int32_t row_begin, int32_t row_end, int32_t row_stride,
                               pt_session **out) {
-    return guarded([&] { return ptc::session_create_on(scene, width, height, row_begin, row_end, nullptr, nullptr, nullptr, out, row_stride); });
+    return guarded([&] { return ptc::session_create_on(scene, width, height, row_begin, row_end, nullptr, out, row_stride); });
 }
 
 int pt_session_create(pt_scene *scene, int32_t width, int32_t height, int32_t row_begin, int32_t row_end, pt_session **out) {
-    return guarded([&] { return ptc::session_create_on(scene, width, height, row_begin, row_end, nullptr, nullptr, nullptr, out, 1); });
+    return guarded([&] { return ptc::session_create_on(scene, width, height, row_begin, row_end, nullptr, out, 1); });
 }
 
 int pt_session_render(pt_session *session, const pt_render_params *params, pt_render_stats *stats) {
@@ -1284,7 +1189,7 @@ int pt_session_wait(pt_session *session) {
     return guarded([&] {
         if (!session) return fail(PT_ERR_INVALID_ARGUMENT, "null session");
         PT_HIP_TRY(hipSetDevice(session->scene->device));
-        PT_HIP_TRY(hipStreamSynchronize(session->stream));
+        PT_HIP_TRY(hipStreamSynchronize(session->stream.get()));
         return static_cast<int>(PT_OK);
     });
 }
@@ -1297,17 +1202,7 @@ int pt_session_clear(pt_session *session) {
     return guarded([&] { return session_clear_impl(session); });
 }
 
-void pt_session_destroy(pt_session *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->scene->device);
-    if (s->stream) {
-        (void)hipStreamSynchronize(s->stream);
-        (void)hipStreamDestroy(s->stream);
-    }
-    if (s->d_band) (void)hipFree(s->d_band);
-    ptc::ctx_destroy(s->ctx);
-    delete s;
-}
+void pt_session_destroy(pt_session *s) { delete s; }   // (~pt_session: the scene's device current, the stream drained)
 
 int pt_scene_cull_tables(pt_scene *scene, float eps, int32_t *counts, float *clusters, float *spheres, float *bary, float *constants) {
     return guarded([&] { return scene_cull_tables_impl(scene, eps, counts, clusters, spheres, bary, constants); });
@@ -1335,23 +1230,22 @@ int pt_test_box_masks(const void *nodes, const float *rays, const float *t_best,
     if (!nodes || !rays || !t_best || !out || n < 0) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return PT_OK;
     PT_HIP_TRY(hipSetDevice(0));
-    void *d_nodes = nullptr, *d_rays = nullptr, *d_t = nullptr, *d_out = nullptr;
+    ptc::DeviceBuffer d_nodes, d_rays, d_t, d_out;
     const size_t nn = static_cast<size_t>(n);
-    hipError_t e = hipMalloc(&d_nodes, nn * 64);
-    if (e == hipSuccess) e = hipMalloc(&d_rays, nn * 24);
-    if (e == hipSuccess) e = hipMalloc(&d_t, nn * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_out, nn * 8);
-    if (e == hipSuccess) e = hipMemcpy(d_nodes, nodes, nn * 64, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, nn * 24, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_t, t_best, nn * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = pt::launch_box_masks(static_cast<const pt::BvhNode *>(d_nodes), static_cast<const float *>(d_rays), static_cast<const float *>(d_t), err, n,
-                                                  static_cast<uint32_t *>(d_out), nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, nn * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_nodes); (void)hipFree(d_rays); (void)hipFree(d_t); (void)hipFree(d_out);
-    if (e != hipSuccess) return hip_fail(e, "pt_test_box_masks");
+    int rc;
+    if ((rc = d_nodes.alloc(nn * 64, "pt_test_box_masks")) != PT_OK || (rc = d_rays.alloc(nn * 24, "pt_test_box_masks")) != PT_OK ||
+        (rc = d_t.alloc(nn * 4, "pt_test_box_masks")) != PT_OK || (rc = d_out.alloc(nn * 8, "pt_test_box_masks")) != PT_OK)
+        return rc;
+    PT_HIP_TRY(hipMemcpy(d_nodes.get<void>(), nodes, nn * 64, hipMemcpyHostToDevice));
+    PT_HIP_TRY(hipMemcpy(d_rays.get<void>(), rays, nn * 24, hipMemcpyHostToDevice));
+    PT_HIP_TRY(hipMemcpy(d_t.get<void>(), t_best, nn * 4, hipMemcpyHostToDevice));
+    PT_HIP_TRY(pt::launch_box_masks(d_nodes.get<pt::BvhNode>(), d_rays.get<float>(), d_t.get<float>(), err, n, d_out.get<uint32_t>(), nullptr));
+    PT_HIP_TRY(hipDeviceSynchronize());
+    PT_HIP_TRY(hipMemcpy(out, d_out.get<void>(), nn * 8, hipMemcpyDeviceToHost));
     return PT_OK;
 }
+
+long pt_test_live_device_objects(void) { return ptc::g_live_device_objects.load(std::memory_order_relaxed); }
 
 int pt_test_set_mutation(const char *family, double value) {
     if (!family) return PT_ERR_INVALID_ARGUMENT;

@@ -1,5 +1,6 @@
-// Types shared by the translation units behind the C ABI (pt_capi.cpp: scenes, sessions, resolve, BMP; pt_frame.cpp: the
-// multi-device frame).  Nothing here is part of the ABI.
+// Types shared by the translation units behind the C ABI (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters;
+// pt_frame.cpp: the multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp: the
+// temporal stage; pt_device_mem.hpp: the owners of everything they hold on a device).  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/pt_hip.h"
 
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "pt_denoise.hpp"
+#include "pt_device_mem.hpp"
 #include "pt_kernels.hpp"
 #include "pt_scene.hpp"
 
@@ -42,22 +44,15 @@ struct DeviceCull {
     double r_max = 0;   // CullTables::r_max
     bool valid = false;
     std::shared_ptr<const pt::CullTables> host;
-    pt::ClusterDesc *clusters = nullptr;
-    pt::SphereRec *spheres = nullptr;
-    pt::CullRec *bary = nullptr;
-    pt::CullRec *bary_all = nullptr;
-    pt::ExactRec *exact_slot = nullptr;
-    pt::BvhNode *bvh = nullptr;
+    ptc::DeviceBuffer clusters, spheres, bary, bary_all, exact_slot, bvh;   // (bary_all, bvh: empty where the host table is)
 };
 
 // What one stream of launches needs besides the scene: the scheduler words of the integrator (ticket + per-tile chunk
 // counters), the statistics block and the timing events.  Every pt_session owns one, so that sessions of ONE scene (row bands
 // of a frame on one device) run concurrently; a scene has one of its own for pt_render_device / pt_render_host.
 struct LaunchCtx {
-    uint32_t *d_sched = nullptr;
-    size_t sched_words = 0;
-    unsigned long long *d_stats = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_done = nullptr;
+    ptc::DeviceBuffer d_sched, d_stats;   // d_sched grows on demand
+    ptc::DeviceEvent ev0, ev1, ev_done;
     bool has_prev = false;          // launches of one context are ordered on the device: they share its scheduler words
     hipStream_t prev_stream = nullptr;
     uint32_t last_chunks = 0;       // of the last launch enqueued (reported with its statistics)
@@ -69,11 +64,10 @@ struct pt_scene {
     std::shared_ptr<pt_scene_host> shared;
     int device = -1;
     DeviceCull cull;
-    pt::ExactRec *d_exact = nullptr;
-    pt::MatRec *d_mats = nullptr;
+    ptc::DeviceBuffer d_exact, d_mats;
     int cu_count = 256;            // compute units of the scene's device
     std::shared_ptr<const pt_sky_texels> sky;   // this handle's skybox (nullptr = none); copies made from it inherit it
-    uint8_t *d_sky = nullptr;      // the same texels on this copy's device
+    ptc::DeviceBuffer d_sky;       // the same texels on this copy's device
     int sky_w = 0, sky_h = 0;
     bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
     pt_camera camera{};
@@ -85,9 +79,12 @@ struct pt_scene {
     LaunchCtx ctx;                 // pt_render_device / pt_render_host / pt_trace_rays_host
     // pt_render_host: device band kept between calls + the stream its kernel runs on (guarded by host_mutex)
     std::mutex host_mutex;
-    float *d_host_band = nullptr;
-    size_t host_band_floats = 0;
-    hipStream_t host_stream = nullptr;
+    ptc::DeviceBuffer d_host_band;
+    ptc::DeviceStream host_stream;
+    // Everything above is freed with the scene's device current; a scene without one holds nothing and makes no HIP call.
+    ~pt_scene() {
+        if (device >= 0) (void)hipSetDevice(device);
+    }
 };
 
 // A row band's accumulators kept on the device between pass slices (pt_session_*).
@@ -95,11 +92,14 @@ struct pt_session {
     pt_scene *scene = nullptr;
     int32_t width = 0, height = 0, row_begin = 0, row_end = 0, row_stride = 1;
     size_t n = 0;                 // pixels of the band
-    float *d_band = nullptr;      // owned: sum[3n] | sum2[3n] | count[n], each plane 256-byte aligned; nullptr if the planes are borrowed
-    float *d_sum = nullptr, *d_sum2 = nullptr;
-    int32_t *d_count = nullptr;
-    hipStream_t stream = nullptr;
     LaunchCtx ctx;
+    ptc::DeviceBuffer d_band;     // owned: sum[3n] | sum2[3n] | count[n], each plane 256-byte aligned; empty if the planes are borrowed
+    ptc::AccumPlanes planes;      // in d_band, or in the frame's planes
+    ptc::DeviceStream stream;
+    ~pt_session() {               // the stream drains, then it, the band and the context go, on the scene's device
+        (void)hipSetDevice(scene->device);
+        if (stream) (void)hipStreamSynchronize(stream.get());
+    }
 };
 
 namespace ptc {
@@ -128,20 +128,26 @@ int guarded(F &&f) noexcept {
 
 int check_params(const pt_scene *scene, const pt_render_params *p);
 // A session whose planes live in memory the caller owns (the root band of a frame renders straight into the frame's planes).
-int session_create_on(pt_scene *scene, int32_t width, int32_t height, int32_t row_begin, int32_t row_end, float *d_sum,
-                      float *d_sum2, int32_t *d_count, pt_session **out, int32_t row_stride = 1);
+int session_create_on(pt_scene *scene, int32_t width, int32_t height, int32_t row_begin, int32_t row_end, const AccumPlanes *borrowed,
+                      pt_session **out, int32_t row_stride = 1);
 // rows the accumulator planes of a call hold (pt_band_rows)
 int32_t band_rows(const pt_render_params *p);
 // pt_session_render in two halves: enqueue the slice (never waits for the device), then -- if statistics were asked for --
 // wait for it and read them.  A frame enqueues on every device before it waits on any.
 int session_enqueue(pt_session *s, const pt_render_params *p, bool want_stats);
 int session_collect(pt_session *s, pt_render_stats *stats);
-void ctx_destroy(LaunchCtx &c);
 // The camera primary rays are made from: the handle's, or the reference's fixed one.
 const pt_camera &view_camera(const pt_scene *s);
 // The scene part of the kernel arguments for `eps` (uploads the culling hierarchy on first use).  The scene's device is
 // current and the caller holds scene->launch_mutex until its kernels are enqueued.
 int scene_trace_args(pt_scene *scene, float eps, pt::RenderArgs &a);
+// The view's first hits for `rows` rows from `row_begin`: centre rays through `camera`, the closest-hit search with `a`
+// (scene_trace_args), the hit's features.  Enqueued on `stream`; the caller still holds scene->launch_mutex.
+int enqueue_first_hits(pt_scene *scene, const pt::RenderArgs &a, const pt_camera &camera, int32_t width, int32_t height, int32_t row_begin,
+                       int32_t rows, float *origins, float *directions, int32_t *hit, float *hit_t, float *position, float *normal,
+                       float *albedo, hipStream_t stream);
+// Makes `device` current if it is an ordinal of a visible device; PT_ERR_NO_DEVICE otherwise (`stage` names the caller in the message).
+int use_device(int device, const char *stage);
 // pt_denoise_params as pt_denoise_host checks them, into the parameter fields of the launch arguments (zero = the default).
 int denoise_params_to_args(const pt_denoise_params *prm, pt::DenoiseArgs &a);
 // levels = 0 of pt_denoise_host: mean_rgb = sum / n (sum where n = 0), count_out = count (may be NULL), on the host.

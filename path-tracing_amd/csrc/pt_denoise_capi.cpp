@@ -11,6 +11,19 @@ using ptc::fail;
 using ptc::guarded;
 using ptc::hip_fail;
 
+int ptc::enqueue_first_hits(pt_scene *scene, const pt::RenderArgs &a, const pt_camera &camera, int32_t width, int32_t height, int32_t row_begin,
+                            int32_t rows, float *origins, float *directions, int32_t *hit, float *hit_t, float *position, float *normal,
+                            float *albedo, hipStream_t stream) {
+    pt::FeatureCamera cam;
+    std::memcpy(cam.v, &camera, sizeof cam.v);
+    const int n = rows * width;
+    PT_HIP_TRY(pt::launch_feature_rays(cam, width, height, row_begin, rows, origins, directions, stream));
+    PT_HIP_TRY(pt::launch_trace_rays(a, origins, directions, n, hit, hit_t, stream));
+    PT_HIP_TRY(pt::launch_feature_gather(scene->d_exact.get<pt::ExactRec>(), scene->d_mats.get<pt::MatRec>(), origins, directions, hit, hit_t, n, position,
+                                         normal, albedo, stream));
+    return PT_OK;
+}
+
 // pt_render_features_host: centre rays on the device, the unchanged closest-hit search, then the hit's features.
 static int render_features_host_impl(pt_scene *scene, const pt_render_params *p, int32_t *hit_index, float *hit_t, float *position,
                                      float *normal, float *albedo) {
@@ -28,28 +41,22 @@ static int render_features_host_impl(pt_scene *scene, const pt_render_params *p,
     PT_HIP_TRY(hipSetDevice(scene->device));
     std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
     pt::RenderArgs a;
-    const int crc = ptc::scene_trace_args(scene, p->eps, a);
-    if (crc != PT_OK) return crc;
-    pt::FeatureCamera cam;
-    std::memcpy(cam.v, &ptc::view_camera(scene), sizeof cam.v);
+    int rc = ptc::scene_trace_args(scene, p->eps, a);
+    if (rc != PT_OK) return rc;
     // one allocation: origins | directions | position | normal | albedo (3 floats per pixel each) | hit_t | hit_index
-    float *d_all = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_all), n * 17 * sizeof(float));
-    if (e != hipSuccess) return hip_fail(e, "pt_render_features_host");
-    float *d_o = d_all, *d_d = d_o + 3 * n, *d_p = d_d + 3 * n, *d_n = d_p + 3 * n, *d_a = d_n + 3 * n, *d_t = d_a + 3 * n;
+    ptc::DeviceBuffer d_all;
+    if ((rc = d_all.alloc(n * 17 * sizeof(float), "pt_render_features_host")) != PT_OK) return rc;
+    float *d_o = d_all.get<float>(), *d_d = d_o + 3 * n, *d_p = d_d + 3 * n, *d_n = d_p + 3 * n, *d_a = d_n + 3 * n, *d_t = d_a + 3 * n;
     int32_t *d_i = reinterpret_cast<int32_t *>(d_t + n);
-    const int ni = static_cast<int>(n);
-    e = pt::launch_feature_rays(cam, p->width, p->height, p->row_begin, rows, d_o, d_d, nullptr);
-    if (e == hipSuccess) e = pt::launch_trace_rays(a, d_o, d_d, ni, d_i, d_t, nullptr);
-    if (e == hipSuccess) e = pt::launch_feature_gather(scene->d_exact, scene->d_mats, d_o, d_d, d_i, d_t, ni, d_p, d_n, d_a, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && hit_index) e = hipMemcpy(hit_index, d_i, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && hit_t) e = hipMemcpy(hit_t, d_t, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && position) e = hipMemcpy(position, d_p, n * 12, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && normal) e = hipMemcpy(normal, d_n, n * 12, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && albedo) e = hipMemcpy(albedo, d_a, n * 12, hipMemcpyDeviceToHost);
-    (void)hipFree(d_all);
-    return e == hipSuccess ? static_cast<int>(PT_OK) : hip_fail(e, "pt_render_features_host");
+    rc = ptc::enqueue_first_hits(scene, a, ptc::view_camera(scene), p->width, p->height, p->row_begin, rows, d_o, d_d, d_i, d_t, d_p, d_n, d_a, nullptr);
+    if (rc != PT_OK) return rc;
+    PT_HIP_TRY(hipDeviceSynchronize());
+    if (hit_index) PT_HIP_TRY(hipMemcpy(hit_index, d_i, n * 4, hipMemcpyDeviceToHost));
+    if (hit_t) PT_HIP_TRY(hipMemcpy(hit_t, d_t, n * 4, hipMemcpyDeviceToHost));
+    if (position) PT_HIP_TRY(hipMemcpy(position, d_p, n * 12, hipMemcpyDeviceToHost));
+    if (normal) PT_HIP_TRY(hipMemcpy(normal, d_n, n * 12, hipMemcpyDeviceToHost));
+    if (albedo) PT_HIP_TRY(hipMemcpy(albedo, d_a, n * 12, hipMemcpyDeviceToHost));
+    return PT_OK;
 }
 
 
@@ -96,50 +103,37 @@ static int denoise_host_impl(int device, int32_t width, int32_t height, const fl
         return PT_OK;
     }
     if (!position || !normal || !albedo || !hit_index) return fail(PT_ERR_INVALID_ARGUMENT, "denoise: null feature buffer");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device < 0 || device >= n_dev)
-        return fail(PT_ERR_NO_DEVICE, "no usable HIP device for the denoiser (there is no CPU fallback)");
-    PT_HIP_TRY(hipSetDevice(device));
+    int rc = ptc::use_device(device, "denoiser");
+    if (rc != PT_OK) return rc;
     // one allocation, every plane 256-byte aligned: sum, sum2, position, normal, albedo, mean (12 n), count, hit, count_out (4 n),
     // records A0, A1, B, C (16 n)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b12 = up(12 * n), b4 = up(4 * n), b16 = up(16 * n);
-    char *d = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d), 6 * b12 + 3 * b4 + 4 * b16);
-    if (e != hipSuccess) return hip_fail(e, "pt_denoise_host");
-    char *at = d;
-    auto take = [&](size_t b) { char *r = at; at += b; return r; };
-    float *d_sum = reinterpret_cast<float *>(take(b12)), *d_sum2 = reinterpret_cast<float *>(take(b12));
-    float *d_pos = reinterpret_cast<float *>(take(b12)), *d_nrm = reinterpret_cast<float *>(take(b12));
-    float *d_alb = reinterpret_cast<float *>(take(b12)), *d_mean = reinterpret_cast<float *>(take(b12));
-    int32_t *d_cnt = reinterpret_cast<int32_t *>(take(b4)), *d_hit = reinterpret_cast<int32_t *>(take(b4));
-    int32_t *d_cnt_out = reinterpret_cast<int32_t *>(take(b4));
+    ptc::PlaneLayout l;
+    const size_t o_sum = l.add(12 * n), o_sum2 = l.add(12 * n), o_pos = l.add(12 * n), o_nrm = l.add(12 * n), o_alb = l.add(12 * n), o_mean = l.add(12 * n);
+    const size_t o_cnt = l.add(4 * n), o_hit = l.add(4 * n), o_cnt_out = l.add(4 * n);
+    const size_t o_a0 = l.add(16 * n), o_a1 = l.add(16 * n), o_b = l.add(16 * n), o_c = l.add(16 * n);
+    ptc::DeviceBuffer d;
+    if ((rc = d.alloc(l, "pt_denoise_host")) != PT_OK) return rc;
+    const ptc::AccumPlanes acc = {d.at<float>(o_sum), d.at<float>(o_sum2), d.at<int32_t>(o_cnt), n};
     a.width = width; a.height = height;
-    a.sum = d_sum; a.sum2 = d_sum2; a.count = d_cnt; a.position = d_pos; a.normal = d_nrm; a.albedo = d_alb; a.hit_index = d_hit;
-    a.rec_a0 = take(b16); a.rec_a1 = take(b16); a.rec_b = take(b16); a.rec_c = take(b16);
-    a.mean_rgb = d_mean; a.count_out = d_cnt_out;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    e = hipMemcpy(d_sum, sum, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_sum2, sum2, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_cnt, count, 4 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pos, position, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_nrm, normal, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_alb, albedo, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_hit, hit_index, 4 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipEventCreate(&ev0);
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
-    if (e == hipSuccess) e = hipEventRecord(ev0, nullptr);
-    if (e == hipSuccess) e = pt::launch_denoise(a, nullptr);
-    if (e == hipSuccess) e = hipEventRecord(ev1, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(ev1);
+    a.sum = acc.sum; a.sum2 = acc.sum2; a.count = acc.count;
+    a.position = d.at<float>(o_pos); a.normal = d.at<float>(o_nrm); a.albedo = d.at<float>(o_alb); a.hit_index = d.at<int32_t>(o_hit);
+    a.rec_a0 = d.at<void>(o_a0); a.rec_a1 = d.at<void>(o_a1); a.rec_b = d.at<void>(o_b); a.rec_c = d.at<void>(o_c);
+    a.mean_rgb = d.at<float>(o_mean); a.count_out = d.at<int32_t>(o_cnt_out);
+    if ((rc = acc.upload(sum, sum2, count)) != PT_OK) return rc;
+    PT_HIP_TRY(hipMemcpy(d.at<void>(o_pos), position, 12 * n, hipMemcpyHostToDevice));
+    PT_HIP_TRY(hipMemcpy(d.at<void>(o_nrm), normal, 12 * n, hipMemcpyHostToDevice));
+    PT_HIP_TRY(hipMemcpy(d.at<void>(o_alb), albedo, 12 * n, hipMemcpyHostToDevice));
+    PT_HIP_TRY(hipMemcpy(d.at<void>(o_hit), hit_index, 4 * n, hipMemcpyHostToDevice));
+    ptc::DeviceEvent ev0, ev1;
+    if ((rc = ev0.create("pt_denoise_host")) != PT_OK || (rc = ev1.create("pt_denoise_host")) != PT_OK) return rc;
+    PT_HIP_TRY(hipEventRecord(ev0.get(), nullptr));
+    PT_HIP_TRY(pt::launch_denoise(a, nullptr));
+    PT_HIP_TRY(hipEventRecord(ev1.get(), nullptr));
+    PT_HIP_TRY(hipEventSynchronize(ev1.get()));
     float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
-    if (e == hipSuccess) e = hipMemcpy(mean_rgb, d_mean, 12 * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && count_out) e = hipMemcpy(count_out, d_cnt_out, 4 * n, hipMemcpyDeviceToHost);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(e, "pt_denoise_host");
+    PT_HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+    PT_HIP_TRY(hipMemcpy(mean_rgb, a.mean_rgb, 12 * n, hipMemcpyDeviceToHost));
+    if (count_out) PT_HIP_TRY(hipMemcpy(count_out, a.count_out, 4 * n, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;
 }

@@ -105,7 +105,7 @@ struct FrameXfer {
     size_t full_tile_rows = 0;        // tile rows copied whole
     size_t tail_bytes = 0;            // rows of the band's last tile row that lie inside the image (0: it is whole too)
     bool staged = false;              // the band is on another device: its plane arrives in the root's staging buffer first
-    size_t stage_offset = 0;          // ... at this offset (floats)
+    size_t stage_offset = 0;          // ... at this offset (bytes)
 };
 
 struct pt_frame {
@@ -115,23 +115,19 @@ struct pt_frame {
     std::vector<int> band_device;          // per band
     std::vector<int32_t> band_rows;        // 2 per band: [begin, end) (interleaved split: [8 b, height), every row_stride-th tile row)
     int32_t row_stride = 1;                // 1: contiguous bands; n > 1: interleaved tile rows
-    float *d_staging = nullptr;            // root device, interleaved split: the bands' planes as they arrive, before the scatter
+    ptc::DeviceBuffer d_staging;           // root device, interleaved split: the bands' planes as they arrive, before the scatter
     std::vector<int> devices;              // distinct devices, devices[0] = root
     std::vector<pt_scene *> scenes;        // one per distinct device (owned)
     std::vector<int> band_scene;           // band -> index into scenes / devices
     std::vector<pt_session *> sessions;    // per band (owned)
-    std::vector<char> band_on_root_planes; // the band renders straight into the root's frame planes
-    float *d_frame = nullptr;              // root device: sum[3 W H] | sum2[3 W H] | count[W H], planes 256-byte aligned
-    size_t plane_floats = 0;
+    ptc::DeviceBuffer d_frame;             // root device: sum[3 W H] | sum2[3 W H] | count[W H], planes 256-byte aligned
+    ptc::AccumPlanes root;                 // ... the planes in it
     std::vector<FrameXfer> xfers;
     std::vector<ncclComm_t> comms;         // RCCL transport: one communicator per distinct device, rank = index
-    hipStream_t gather_stream = nullptr;   // root device, RCCL transport only: the receives of the gather
+    ptc::DeviceStream gather_stream;       // root device: the receives of the gather (RCCL), the scatter of staged bands
     bool dirty = false;                    // a band was rendered or cleared since the last gather
     std::vector<float> band_kernel_ms;     // per band: kernel time of the last pt_frame_render that asked for statistics (-1 = none yet)
     size_t n_px() const { return static_cast<size_t>(width) * height; }
-    float *root_sum() const { return d_frame; }
-    float *root_sum2() const { return d_frame + plane_floats; }
-    int32_t *root_count() const { return reinterpret_cast<int32_t *>(d_frame + 2 * plane_floats); }
 };
 
 namespace {
@@ -197,34 +193,32 @@ int frame_create_impl(const pt_scene *scene, const int32_t *devices, int32_t n_b
     // the root's full-frame planes
     const int root = f->devices[0];
     PT_HIP_TRY(hipSetDevice(root));
-    const size_t n = f->n_px();
-    f->plane_floats = (3 * n + 63) / 64 * 64;
-    const size_t bytes = (2 * f->plane_floats + n) * sizeof(float) + 256;
-    PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&f->d_frame), bytes));
-    PT_HIP_TRY(hipMemset(f->d_frame, 0, bytes));
+    ptc::PlaneLayout frame_layout;
+    f->root = ptc::AccumPlanes::in(frame_layout, f->n_px());
+    int rc = f->d_frame.alloc(frame_layout.end + 256, "pt_frame_create");
+    if (rc != PT_OK) return rc;
+    PT_HIP_TRY(hipMemset(f->d_frame.get<void>(), 0, f->d_frame.bytes()));
+    f->root.bind(f->d_frame);
     // sessions.  Band 0 (the root's) renders into the frame planes themselves; with the RCCL transport every other band is on
     // another device and has its own buffer; a rehearsal gives EVERY other band its own buffer, also on the root device, so
     // that the N-band gather really moves N - 1 bands.
     // (interleaved split: every band, the root's too, renders into packed planes of its own; bands on other devices are staged on
     // the root before their tile rows are put in place)
     const bool interleaved = f->row_stride > 1;
-    size_t staging_floats = 0;
+    ptc::PlaneLayout staging;
     for (int b = 0; b < n_bands; ++b) {
         const int32_t r0 = f->band_rows[2 * b], r1 = f->band_rows[2 * b + 1];
         const size_t first = static_cast<size_t>(r0) * width;
         const bool on_planes = !interleaved && b == 0 && !self_coll;
         pt_session *ses = nullptr;
-        const int rc = on_planes ? ptc::session_create_on(f->scenes[f->band_scene[b]], width, height, r0, r1, f->root_sum() + 3 * first,
-                                                          f->root_sum2() + 3 * first, f->root_count() + first, &ses)
-                                 : ptc::session_create_on(f->scenes[f->band_scene[b]], width, height, r0, r1, nullptr, nullptr, nullptr, &ses,
-                                                          f->row_stride);
+        const ptc::AccumPlanes rows = {f->root.sum + 3 * first, f->root.sum2 + 3 * first, f->root.count + first};   // the band's rows in the root's planes
+        rc = ptc::session_create_on(f->scenes[f->band_scene[b]], width, height, r0, r1, on_planes ? &rows : nullptr, &ses, f->row_stride);
         if (rc != PT_OK) return rc;
         f->sessions.push_back(ses);
-        f->band_on_root_planes.push_back(on_planes ? 1 : 0);
         if (!on_planes && ses->n > 0) {
-            f->xfers.push_back({b, ses->d_sum, f->root_sum() + 3 * first, 3 * ses->n});
-            f->xfers.push_back({b, ses->d_sum2, f->root_sum2() + 3 * first, 3 * ses->n});
-            f->xfers.push_back({b, ses->d_count, f->root_count() + first, ses->n});
+            f->xfers.push_back({b, ses->planes.sum, rows.sum, 3 * ses->n});
+            f->xfers.push_back({b, ses->planes.sum2, rows.sum2, 3 * ses->n});
+            f->xfers.push_back({b, ses->planes.count, rows.count, ses->n});
             if (interleaved) {
                 // band b holds tile rows b, b + n, ...: all whole except possibly the image's last one
                 const size_t count = (static_cast<size_t>(tile_rows) - b + f->row_stride - 1) / f->row_stride;
@@ -241,26 +235,23 @@ int frame_create_impl(const pt_scene *scene, const int32_t *devices, int32_t n_b
                     x.tail_bytes = partial ? last_rows * static_cast<size_t>(width) * elem : 0;
                     x.dst = nullptr;                         // staged bands: set once the staging buffer exists
                     x.staged = staged;
-                    if (staged) {
-                        x.stage_offset = staging_floats;
-                        staging_floats += (x.words + 63) / 64 * 64;
-                    }
+                    if (staged) x.stage_offset = staging.add(x.words * 4);
                 }
             }
         }
     }
     if (interleaved) {
         PT_HIP_TRY(hipSetDevice(root));
-        if (staging_floats > 0) {
-            PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&f->d_staging), staging_floats * sizeof(float)));
+        if (staging.end > 0) {
+            if ((rc = f->d_staging.alloc(staging, "pt_frame_create")) != PT_OK) return rc;
             for (FrameXfer &x : f->xfers)
-                if (x.staged) x.dst = f->d_staging + x.stage_offset;
+                if (x.staged) x.dst = f->d_staging.at<float>(x.stage_offset);
         }
-        if (!f->gather_stream) PT_HIP_TRY(hipStreamCreateWithFlags(&f->gather_stream, hipStreamNonBlocking));   // staged bands are put in place on it
+        if ((rc = f->gather_stream.create("pt_frame_create")) != PT_OK) return rc;   // staged bands are put in place on it
     }
     if (f->transport == PT_FRAME_TRANSPORT_RCCL) {
         PT_HIP_TRY(hipSetDevice(root));
-        if (!f->gather_stream) PT_HIP_TRY(hipStreamCreateWithFlags(&f->gather_stream, hipStreamNonBlocking));   // the receives of the gather
+        if (!f->gather_stream && (rc = f->gather_stream.create("pt_frame_create")) != PT_OK) return rc;   // the receives of the gather
         Rccl &r = rccl();
         if (!r.error.empty()) return fail(PT_ERR_UNSUPPORTED, r.error);
         f->comms.assign(f->devices.size(), nullptr);
@@ -335,19 +326,19 @@ int frame_gather_impl(pt_frame *f) {
             PT_HIP_TRY(hipSetDevice(s->scene->device));
             if (x.scatter_dst) {
                 if (s->scene->device == root) {
-                    const int rc = scatter(x, x.src, s->stream);
+                    const int rc = scatter(x, x.src, s->stream.get());
                     if (rc != PT_OK) return rc;
                 } else {   // staged on the root, then put in place there once the copy has arrived
-                    PT_HIP_TRY(hipMemcpyPeerAsync(x.dst, root, x.src, s->scene->device, x.words * 4, s->stream));
-                    PT_HIP_TRY(hipStreamSynchronize(s->stream));      // (a rehearsal across devices: not a path anything times)
+                    PT_HIP_TRY(hipMemcpyPeerAsync(x.dst, root, x.src, s->scene->device, x.words * 4, s->stream.get()));
+                    PT_HIP_TRY(hipStreamSynchronize(s->stream.get()));      // (a rehearsal across devices: not a path anything times)
                     PT_HIP_TRY(hipSetDevice(root));
-                    const int rc = scatter(x, x.dst, f->gather_stream);
+                    const int rc = scatter(x, x.dst, f->gather_stream.get());
                     if (rc != PT_OK) return rc;
                 }
             } else if (s->scene->device == root) {
-                PT_HIP_TRY(hipMemcpyAsync(x.dst, x.src, x.words * 4, hipMemcpyDeviceToDevice, s->stream));
+                PT_HIP_TRY(hipMemcpyAsync(x.dst, x.src, x.words * 4, hipMemcpyDeviceToDevice, s->stream.get()));
             } else {
-                PT_HIP_TRY(hipMemcpyPeerAsync(x.dst, root, x.src, s->scene->device, x.words * 4, s->stream));
+                PT_HIP_TRY(hipMemcpyPeerAsync(x.dst, root, x.src, s->scene->device, x.words * 4, s->stream.get()));
             }
         }
         f->dirty = false;
@@ -362,8 +353,8 @@ int frame_gather_impl(pt_frame *f) {
         pt_session *s = f->sessions[x.band];
         const int rank = f->band_scene[x.band];
         if (x.scatter_dst && !x.dst) continue;       // interleaved split, a band on the root device: no transfer, only the scatter below
-        ncclResult_t e = r.Send(x.src, x.words, ncclFloat32, 0, f->comms[rank], s->stream);
-        if (e == ncclSuccess) e = r.Recv(x.dst, x.words, ncclFloat32, rank, f->comms[0], f->gather_stream);
+        ncclResult_t e = r.Send(x.src, x.words, ncclFloat32, 0, f->comms[rank], s->stream.get());
+        if (e == ncclSuccess) e = r.Recv(x.dst, x.words, ncclFloat32, rank, f->comms[0], f->gather_stream.get());
         if (e != ncclSuccess && first_error == ncclSuccess) first_error = e;
     }
     const ncclResult_t ge = r.GroupEnd();
@@ -374,7 +365,7 @@ int frame_gather_impl(pt_frame *f) {
     for (const FrameXfer &x : f->xfers) {
         if (!x.scatter_dst) continue;
         PT_HIP_TRY(hipSetDevice(root));
-        const int rc = x.dst ? scatter(x, x.dst, f->gather_stream) : scatter(x, x.src, f->sessions[x.band]->stream);
+        const int rc = x.dst ? scatter(x, x.dst, f->gather_stream.get()) : scatter(x, x.src, f->sessions[x.band]->stream.get());
         if (rc != PT_OK) return rc;
     }
     f->dirty = false;
@@ -385,11 +376,11 @@ int frame_wait_impl(pt_frame *f) {
     if (!f) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
     for (pt_session *s : f->sessions) {
         PT_HIP_TRY(hipSetDevice(s->scene->device));
-        PT_HIP_TRY(hipStreamSynchronize(s->stream));
+        PT_HIP_TRY(hipStreamSynchronize(s->stream.get()));
     }
     if (f->gather_stream) {
         PT_HIP_TRY(hipSetDevice(f->devices[0]));
-        PT_HIP_TRY(hipStreamSynchronize(f->gather_stream));
+        PT_HIP_TRY(hipStreamSynchronize(f->gather_stream.get()));
     }
     return PT_OK;
 }
@@ -399,11 +390,7 @@ int frame_read_impl(pt_frame *f, float *sum, float *sum2, int32_t *count) {
     int rc;
     if (f->dirty && (rc = frame_gather_impl(f)) != PT_OK) return rc;
     if ((rc = frame_wait_impl(f)) != PT_OK) return rc;
-    const size_t n = f->n_px();
-    PT_HIP_TRY(hipMemcpy(sum, f->root_sum(), 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    PT_HIP_TRY(hipMemcpy(sum2, f->root_sum2(), 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    PT_HIP_TRY(hipMemcpy(count, f->root_count(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return PT_OK;
+    return f->root.download(sum, sum2, count);
 }
 
 int frame_clear_impl(pt_frame *f) {
@@ -511,7 +498,7 @@ void pt_frame_destroy(pt_frame *f) {
     // drained before the communicators go
     if (f->gather_stream && !f->devices.empty()) {
         (void)hipSetDevice(f->devices[0]);
-        (void)hipStreamSynchronize(f->gather_stream);
+        (void)hipStreamSynchronize(f->gather_stream.get());
     }
     for (pt_session *s : f->sessions) pt_session_destroy(s);   // waits for the band's stream
     if (!f->comms.empty()) {
@@ -521,12 +508,10 @@ void pt_frame_destroy(pt_frame *f) {
     }
     if (!f->devices.empty()) {
         (void)hipSetDevice(f->devices[0]);
-        if (f->gather_stream) {
-            (void)hipStreamSynchronize(f->gather_stream);
-            (void)hipStreamDestroy(f->gather_stream);
-        }
-        if (f->d_frame) (void)hipFree(f->d_frame);
-        if (f->d_staging) (void)hipFree(f->d_staging);
+        if (f->gather_stream) (void)hipStreamSynchronize(f->gather_stream.get());
+        f->gather_stream.reset();   // the root's objects go here, with the root current: the scenes below make their own devices current
+        f->d_frame.reset();
+        f->d_staging.reset();
     }
     for (pt_scene *s : f->scenes) pt_scene_destroy(s);
     delete f;

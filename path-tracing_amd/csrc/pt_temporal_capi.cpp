@@ -17,25 +17,25 @@ struct pt_temporal {
     float eps = 0;
     size_t n = 0;
     std::mutex mutex;             // one push / reset at a time
-    char *d_all = nullptr;        // everything below but the denoiser's planes
-    float *d_sum = nullptr, *d_sum2 = nullptr, *d_origins = nullptr, *d_directions = nullptr, *d_position = nullptr, *d_normal = nullptr,
-          *d_albedo = nullptr, *d_hit_t = nullptr, *d_sum_out = nullptr, *d_sum2_out = nullptr, *d_frames = nullptr;
-    int32_t *d_count = nullptr, *d_hit = nullptr, *d_count_out = nullptr;
+    ptc::DeviceBuffer d_all;      // everything below but the denoiser's planes
+    ptc::AccumPlanes in, out;     // the frame pushed, the merged accumulators
+    float *d_origins = nullptr, *d_directions = nullptr, *d_position = nullptr, *d_normal = nullptr, *d_albedo = nullptr, *d_hit_t = nullptr,
+          *d_frames = nullptr;
+    int32_t *d_hit = nullptr;
     pt::TemporalRecords rec[2];   // ping-pong; rec[cur] holds the history
     int cur = 0;
     bool has_history = false;
     pt_camera camera{};           // of the history
     float inverse[9] = {};        // rows of the inverse of [right up forward] of that camera
-    char *d_denoise = nullptr;    // allocated by the first push that filters: records A0, A1, B, C, mean, count
+    ptc::DeviceBuffer d_denoise;  // allocated by the first push that filters: records A0, A1, B, C, mean, count
     void *dn_a0 = nullptr, *dn_a1 = nullptr, *dn_b = nullptr, *dn_c = nullptr;
     float *d_mean = nullptr;
     int32_t *d_mean_count = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ptc::DeviceEvent ev0, ev1;
+    ~pt_temporal() { (void)hipSetDevice(scene->device); }   // (a handle exists only over a scene with a device)
 };
 
 namespace {
-
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 
 // Rows of the inverse of the matrix whose columns are right, up, forward: cross products over the determinant, in double,
 // rounded to float once (pt_hip.h states the order).
@@ -58,15 +58,6 @@ void camera_inverse(const pt_camera &c, float out[9]) {
     }
 }
 
-void temporal_free(pt_temporal *t) {
-    if (t->scene && t->scene->device >= 0) (void)hipSetDevice(t->scene->device);
-    if (t->ev0) (void)hipEventDestroy(t->ev0);
-    if (t->ev1) (void)hipEventDestroy(t->ev1);
-    if (t->d_denoise) (void)hipFree(t->d_denoise);
-    if (t->d_all) (void)hipFree(t->d_all);
-    delete t;
-}
-
 int temporal_create_impl(pt_scene *scene, int32_t width, int32_t height, float eps, pt_temporal **out) {
     if (!scene || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null scene or output pointer");
     *out = nullptr;
@@ -75,26 +66,29 @@ int temporal_create_impl(pt_scene *scene, int32_t width, int32_t height, float e
     if (std::isnan(eps)) return fail(PT_ERR_INVALID_ARGUMENT, "eps is not a number");
     if (scene->device < 0) return fail(PT_ERR_NO_DEVICE, "scene was created without a device (device < 0); there is no CPU fallback");
     PT_HIP_TRY(hipSetDevice(scene->device));
-    pt_temporal *t = new pt_temporal;
+    std::unique_ptr<pt_temporal> t(new pt_temporal);
     t->scene = scene; t->width = width; t->height = height; t->eps = eps;
     const size_t n = t->n = static_cast<size_t>(width) * height;
-    const size_t b12 = up256(12 * n), b4 = up256(4 * n), b16 = up256(16 * n);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->d_all), 9 * b12 + 5 * b4 + 8 * b16);
-    if (e == hipSuccess) e = hipEventCreate(&t->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&t->ev1);
-    if (e != hipSuccess) {
-        temporal_free(t);
-        return hip_fail(e, "pt_temporal_create");
-    }
-    char *at = t->d_all;
-    auto take = [&](size_t b) { char *r = at; at += b; return r; };
-    auto f = [&](size_t b) { return reinterpret_cast<float *>(take(b)); };
-    auto i = [&](size_t b) { return reinterpret_cast<int32_t *>(take(b)); };
-    t->d_sum = f(b12); t->d_sum2 = f(b12); t->d_origins = f(b12); t->d_directions = f(b12); t->d_position = f(b12);
-    t->d_normal = f(b12); t->d_albedo = f(b12); t->d_sum_out = f(b12); t->d_sum2_out = f(b12);
-    t->d_count = i(b4); t->d_hit = i(b4); t->d_count_out = i(b4); t->d_hit_t = f(b4); t->d_frames = f(b4);
-    for (auto &r : t->rec) { r.sum_n = take(b16); r.sum2_age = take(b16); r.normal = take(b16); r.position = take(b16); }
-    *out = t;
+    // one allocation: nine planes of 12 n bytes, five of 4 n, the two sets of four records of 16 n
+    ptc::PlaneLayout l;
+    t->in = ptc::AccumPlanes::in(l, n);
+    t->out = ptc::AccumPlanes::in(l, n);
+    const size_t o_org = l.add(12 * n), o_dir = l.add(12 * n), o_pos = l.add(12 * n), o_nrm = l.add(12 * n), o_alb = l.add(12 * n);
+    const size_t o_hit = l.add(4 * n), o_hit_t = l.add(4 * n), o_frames = l.add(4 * n);
+    size_t o_rec[8];
+    for (size_t &o : o_rec) o = l.add(16 * n);
+    int rc;
+    if ((rc = t->d_all.alloc(l, "pt_temporal_create")) != PT_OK || (rc = t->ev0.create("pt_temporal_create")) != PT_OK ||
+        (rc = t->ev1.create("pt_temporal_create")) != PT_OK)
+        return rc;
+    const ptc::DeviceBuffer &d = t->d_all;
+    t->in.bind(d); t->out.bind(d);
+    t->d_origins = d.at<float>(o_org); t->d_directions = d.at<float>(o_dir); t->d_position = d.at<float>(o_pos);
+    t->d_normal = d.at<float>(o_nrm); t->d_albedo = d.at<float>(o_alb);
+    t->d_hit = d.at<int32_t>(o_hit); t->d_hit_t = d.at<float>(o_hit_t); t->d_frames = d.at<float>(o_frames);
+    for (int k = 0; k < 2; ++k)
+        t->rec[k] = {d.at<void>(o_rec[4 * k]), d.at<void>(o_rec[4 * k + 1]), d.at<void>(o_rec[4 * k + 2]), d.at<void>(o_rec[4 * k + 3])};
+    *out = t.release();
     return PT_OK;
 }
 
@@ -119,12 +113,14 @@ int temporal_push_impl(pt_temporal *t, const float *sum, const float *sum2, cons
     PT_HIP_TRY(hipSetDevice(scene->device));
     std::lock_guard<std::mutex> push_lock(t->mutex);
     if (da.levels > 0 && !t->d_denoise) {
-        const size_t b12 = up256(12 * n), b4 = up256(4 * n), b16 = up256(16 * n);
-        PT_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&t->d_denoise), 4 * b16 + b12 + b4));
-        char *at = t->d_denoise;
-        t->dn_a0 = at; t->dn_a1 = at + b16; t->dn_b = at + 2 * b16; t->dn_c = at + 3 * b16;
-        t->d_mean = reinterpret_cast<float *>(at + 4 * b16);
-        t->d_mean_count = reinterpret_cast<int32_t *>(at + 4 * b16 + b12);
+        ptc::PlaneLayout l;
+        const size_t o_a0 = l.add(16 * n), o_a1 = l.add(16 * n), o_b = l.add(16 * n), o_c = l.add(16 * n), o_mean = l.add(12 * n), o_cnt = l.add(4 * n);
+        const int rc = t->d_denoise.alloc(l, "pt_temporal_push_host");
+        if (rc != PT_OK) return rc;
+        const ptc::DeviceBuffer &d = t->d_denoise;
+        t->dn_a0 = d.at<void>(o_a0); t->dn_a1 = d.at<void>(o_a1); t->dn_b = d.at<void>(o_b); t->dn_c = d.at<void>(o_c);
+        t->d_mean = d.at<float>(o_mean);
+        t->d_mean_count = d.at<int32_t>(o_cnt);
     }
     const pt_camera cam = ptc::view_camera(scene);
     pt::TemporalArgs a;
@@ -137,56 +133,45 @@ int temporal_push_impl(pt_temporal *t, const float *sum, const float *sum2, cons
     std::memcpy(a.cam, &cam, sizeof a.cam);
     std::memcpy(a.prev_origin, t->camera.origin, sizeof a.prev_origin);
     std::memcpy(a.prev_inverse, t->inverse, sizeof a.prev_inverse);
-    a.sum = t->d_sum; a.sum2 = t->d_sum2; a.count = t->d_count;
+    a.sum = t->in.sum; a.sum2 = t->in.sum2; a.count = t->in.count;
     a.position = t->d_position; a.normal = t->d_normal; a.hit_index = t->d_hit;
     a.prev = t->rec[t->cur]; a.next = t->rec[t->cur ^ 1];
-    a.sum_out = t->d_sum_out; a.sum2_out = t->d_sum2_out; a.count_out = t->d_count_out; a.history_frames = t->d_frames;
+    a.sum_out = t->out.sum; a.sum2_out = t->out.sum2; a.count_out = t->out.count; a.history_frames = t->d_frames;
     da.width = t->width; da.height = t->height;
-    da.sum = t->d_sum_out; da.sum2 = t->d_sum2_out; da.count = t->d_count_out;
+    da.sum = t->out.sum; da.sum2 = t->out.sum2; da.count = t->out.count;
     da.position = t->d_position; da.normal = t->d_normal; da.albedo = t->d_albedo; da.hit_index = t->d_hit;
     da.rec_a0 = t->dn_a0; da.rec_a1 = t->dn_a1; da.rec_b = t->dn_b; da.rec_c = t->dn_c;
     da.mean_rgb = t->d_mean; da.count_out = t->d_mean_count;
 
-    hipError_t e = hipMemcpy(t->d_sum, sum, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t->d_sum2, sum2, 12 * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(t->d_count, count, 4 * n, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail(e, "pt_temporal_push_host");
+    int rc = t->in.upload(sum, sum2, count);
+    if (rc != PT_OK) return rc;
     {   // the chain: the view's first hits, the merge, the filter -- one stream, no host synchronisation in between
         std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
         pt::RenderArgs ra;
-        const int crc = ptc::scene_trace_args(scene, t->eps, ra);
-        if (crc != PT_OK) return crc;
-        pt::FeatureCamera fc;
-        std::memcpy(fc.v, &cam, sizeof fc.v);
-        const int ni = static_cast<int>(n);
-        e = hipEventRecord(t->ev0, nullptr);
-        if (e == hipSuccess) e = pt::launch_feature_rays(fc, t->width, t->height, 0, t->height, t->d_origins, t->d_directions, nullptr);
-        if (e == hipSuccess) e = pt::launch_trace_rays(ra, t->d_origins, t->d_directions, ni, t->d_hit, t->d_hit_t, nullptr);
-        if (e == hipSuccess)
-            e = pt::launch_feature_gather(scene->d_exact, scene->d_mats, t->d_origins, t->d_directions, t->d_hit, t->d_hit_t, ni, t->d_position,
-                                          t->d_normal, t->d_albedo, nullptr);
-        if (e == hipSuccess) e = pt::launch_temporal_merge(a, nullptr);
-        if (e == hipSuccess && da.levels > 0) e = pt::launch_denoise(da, nullptr);
-        if (e == hipSuccess) e = hipEventRecord(t->ev1, nullptr);
+        if ((rc = ptc::scene_trace_args(scene, t->eps, ra)) != PT_OK) return rc;
+        PT_HIP_TRY(hipEventRecord(t->ev0.get(), nullptr));
+        rc = ptc::enqueue_first_hits(scene, ra, cam, t->width, t->height, 0, t->height, t->d_origins, t->d_directions, t->d_hit, t->d_hit_t,
+                                     t->d_position, t->d_normal, t->d_albedo, nullptr);
+        if (rc != PT_OK) return rc;
+        PT_HIP_TRY(pt::launch_temporal_merge(a, nullptr));
+        if (da.levels > 0) PT_HIP_TRY(pt::launch_denoise(da, nullptr));
+        PT_HIP_TRY(hipEventRecord(t->ev1.get(), nullptr));
     }
-    if (e == hipSuccess) e = hipEventSynchronize(t->ev1);
+    // (an error return from here on leaves the history the previous one: rec[cur] was only read)
+    PT_HIP_TRY(hipEventSynchronize(t->ev1.get()));
     float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, t->ev0, t->ev1);
-    if (e == hipSuccess && sum_out) e = hipMemcpy(sum_out, t->d_sum_out, 12 * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && sum2_out) e = hipMemcpy(sum2_out, t->d_sum2_out, 12 * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && count_out) e = hipMemcpy(count_out, t->d_count_out, 4 * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && history_frames) e = hipMemcpy(history_frames, t->d_frames, 4 * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && dn && da.levels > 0) {
-        if (mean_rgb) e = hipMemcpy(mean_rgb, t->d_mean, 12 * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && mean_count) e = hipMemcpy(mean_count, t->d_mean_count, 4 * n, hipMemcpyDeviceToHost);
-    } else if (e == hipSuccess && dn && mean_rgb) {   // levels = 0: the unfiltered mean of the merged accumulators, on the host
+    PT_HIP_TRY(hipEventElapsedTime(&ms, t->ev0.get(), t->ev1.get()));
+    if ((rc = t->out.download(sum_out, sum2_out, count_out)) != PT_OK) return rc;
+    if (history_frames) PT_HIP_TRY(hipMemcpy(history_frames, t->d_frames, 4 * n, hipMemcpyDeviceToHost));
+    if (dn && da.levels > 0) {
+        if (mean_rgb) PT_HIP_TRY(hipMemcpy(mean_rgb, t->d_mean, 12 * n, hipMemcpyDeviceToHost));
+        if (mean_count) PT_HIP_TRY(hipMemcpy(mean_count, t->d_mean_count, 4 * n, hipMemcpyDeviceToHost));
+    } else if (dn && mean_rgb) {   // levels = 0: the unfiltered mean of the merged accumulators, on the host
         std::vector<float> s(3 * n);
         std::vector<int32_t> c(n);
-        e = hipMemcpy(s.data(), t->d_sum_out, 12 * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(c.data(), t->d_count_out, 4 * n, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) ptc::unfiltered_mean(n, s.data(), c.data(), mean_rgb, mean_count);
+        if ((rc = t->out.download(s.data(), nullptr, c.data())) != PT_OK) return rc;
+        ptc::unfiltered_mean(n, s.data(), c.data(), mean_rgb, mean_count);
     }
-    if (e != hipSuccess) return hip_fail(e, "pt_temporal_push_host");   // the history is still the previous one: rec[cur] was only read
     t->cur ^= 1;
     t->has_history = true;
     t->camera = cam;
@@ -222,7 +207,7 @@ int pt_temporal_reset(pt_temporal *t) {
 }
 
 void pt_temporal_destroy(pt_temporal *t) {
-    if (t) temporal_free(t);
+    delete t;   // (~pt_temporal makes the scene's device current for its owners)
 }
 
 }  // extern "C"

@@ -50,10 +50,10 @@ MUTATIONS = [
     ("median_clamps_exchanged", FILTERS, [("const int i = max(min(wx + x, width - 1), 0);", "const int i = min(max(min(wx + x, height - 1), 0), width - 1);"),
                                           ("const int j = max(min(wy + y, height - 1), 0);", "const int j = min(max(min(wy + y, width - 1), 0), height - 1);")], 2,
      "test_filters_shape_grid[0-4]", "width and height exchanged in the clamps of both median kernels (clamped again to stay inside)"),
-    ("filter_order", CAPI, [("    if (e == hipSuccess && gauss) {   // main.cpp:187-189",
-                             "    if (e == hipSuccess && median) { e = pt::launch_median(d_a, d_b, width, height, median, nullptr); std::swap(d_a, d_b); }\n"
-                             "    if (e == hipSuccess && gauss) {   // main.cpp:187-189"),
-                            ("    if (e == hipSuccess && median) {   // main.cpp:190-192", "    if (false) {   // main.cpp:190-192")], 1,
+    ("filter_order", CAPI, [("    if (gauss) {   // main.cpp:187-189",
+                             "    if (median) { PT_HIP_TRY(pt::launch_median(d_a, d_b, width, height, median, nullptr)); std::swap(d_a, d_b); }\n"
+                             "    if (gauss) {   // main.cpp:187-189"),
+                            ("    if (median) {   // main.cpp:190-192", "    if (false) {   // main.cpp:190-192")], 1,
      "test_filters_composition[33-31]", "median before Gaussian"),
     ("albedo_floor_ge", DENOISE, [("al > kDenoiseAlbedoFloor ? al : kDenoiseAlbedoFloor", "al >= kDenoiseAlbedoFloor ? al : kDenoiseAlbedoFloor")], 1,
      None, "EQUIVALENT, expected to pass everything: at al == 0.01 both branches give 0.01, and no other input tells > from >=.  Kept as the control "
