@@ -1223,9 +1223,9 @@ int pt_post_filter_host(int device, int32_t width, int32_t height, float *rgb, i
 // per wave slot; < 0: the 3/4 - of - the - rest chunks always; 0: the library's rule), "chunk_min" (the smallest last chunk of that
 // scheme), "tile_width" (1: 8 x 8 tiles always; 2: 16 x 8 where the instantiation has them, batches over 16 x 8 tiles for adaptive
 // launches; 3: the same with 32 x 8 batch tiles; 0: by tile count), "regen_min_dead" (path regeneration threshold).
-// Test builds only: both forms of the box tree's child test (pt_kernels.hip: box_children_kept / box_children_kept_h) on n
-// caller-supplied items -- nodes: n x 64 bytes (BvhNode), rays: n x 6 floats (origin, unit direction), t_best: n floats --
-// out: 2 n masks (float form, half-precision form).  Host pointers; device 0.
+// Test builds only: the box tree's child test (pt_kernels.hip: box_children_kept) on n caller-supplied items -- nodes:
+// n x 64 bytes (BvhNode), rays: n x 6 floats (origin, unit direction), t_best: n floats -- out: n masks, one per item.
+// Host pointers; device 0.
 int pt_test_box_masks(const void *nodes, const float *rays, const float *t_best, float err, int32_t n, uint32_t *out) {
     if (!nodes || !rays || !t_best || !out || n < 0) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return PT_OK;
@@ -1234,14 +1234,14 @@ int pt_test_box_masks(const void *nodes, const float *rays, const float *t_best,
     const size_t nn = static_cast<size_t>(n);
     int rc;
     if ((rc = d_nodes.alloc(nn * 64, "pt_test_box_masks")) != PT_OK || (rc = d_rays.alloc(nn * 24, "pt_test_box_masks")) != PT_OK ||
-        (rc = d_t.alloc(nn * 4, "pt_test_box_masks")) != PT_OK || (rc = d_out.alloc(nn * 8, "pt_test_box_masks")) != PT_OK)
+        (rc = d_t.alloc(nn * 4, "pt_test_box_masks")) != PT_OK || (rc = d_out.alloc(nn * 4, "pt_test_box_masks")) != PT_OK)
         return rc;
     PT_HIP_TRY(hipMemcpy(d_nodes.get<void>(), nodes, nn * 64, hipMemcpyHostToDevice));
     PT_HIP_TRY(hipMemcpy(d_rays.get<void>(), rays, nn * 24, hipMemcpyHostToDevice));
     PT_HIP_TRY(hipMemcpy(d_t.get<void>(), t_best, nn * 4, hipMemcpyHostToDevice));
     PT_HIP_TRY(pt::launch_box_masks(d_nodes.get<pt::BvhNode>(), d_rays.get<float>(), d_t.get<float>(), err, n, d_out.get<uint32_t>(), nullptr));
     PT_HIP_TRY(hipDeviceSynchronize());
-    PT_HIP_TRY(hipMemcpy(out, d_out.get<void>(), nn * 8, hipMemcpyDeviceToHost));
+    PT_HIP_TRY(hipMemcpy(out, d_out.get<void>(), nn * 4, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

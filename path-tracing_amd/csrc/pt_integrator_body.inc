@@ -17,9 +17,10 @@
     constexpr bool REGEN = SKY;
     static_assert(!REGEN || !POOL, "the compacting instantiation keeps the pass loop");
     // kDynSlots: batches of at most 64 pixels run with the second ray slots switched off (scalar branches around every per-ray piece of
-    // the search and of shading).  The 16 x 8 kernel has them -- a third of its batches are such -- the 32 x 8 kernel does not: one batch
-    // in eleven is, and the branches cost every batch 3-4 % (1080p 56.0 -> 54.1 ms, 3840 x 2160 215.5 -> 207.2, r04_ab_logs.txt adapt5).
-    constexpr bool kDynSlots = POOL != 0 && R == 2 && (POOL != 4 || PT_ADAPT4_DYN);
+    // the search and of shading).  Only the 16 x 8 kernel (POOL == 2) has them -- a third of its batches are such.  In the 32 x 8 kernel
+    // one batch in eleven is, and the branches cost every batch 3-4 % (1080p 56.0 -> 54.1 ms, 3840 x 2160 215.5 -> 207.2,
+    // r04_ab_logs.txt adapt5), so it always runs both slots.
+    constexpr bool kDynSlots = POOL == 2 && R == 2;
     constexpr int kOwn = POOL ? POOL : R;   // pixels of the tile per lane: pixel j of the tile = column (j % 8) + 8 (j / 64), row (j % 64) / 8
     constexpr int kTW = kTileW * kOwn;
     __shared__ WaveLds<std::conditional_t<BIG, std::conditional_t<POOL != 0, BigQueuesAdapt<POOL>, BigQueues>, std::conditional_t<(R > 1), SmallQueues2, SmallQueues>>, R, POOL> lds;   // one wave per workgroup: all wave-private
@@ -293,7 +294,7 @@
                 behind = min(behind, pend[kb] ? np[kb] : ~0u);
             }
             if (n_pend == 0) break;
-            // (the box-tree kernel has one ray slot per lane; without kDynSlots a batch costs the same however few it holds)
+            // (the box-tree kernel has one ray slot per lane; in the 32 x 8 kernel, which has no kDynSlots, a batch costs the same however few it holds)
             const uint32_t quota = (R == 2 && (!kDynSlots || n_pend >= static_cast<uint32_t>(PT_ADAPT_TWO_AT))) ? 128u : 64u;
             if (n_pend > quota) {
                 const uint32_t m = wave_min(behind);

@@ -79,9 +79,6 @@ struct SmallQueues2 { static constexpr int kNodeStack = PT_SMALL2_NODES, kPairQu
 #ifndef PT_BOX_SCHED
 #define PT_BOX_SCHED 1        // box tree's child test: a scheduling barrier after every PT_BOX_SCHED children (9 = none)
 #endif
-#ifndef PT_BOX_SPREAD
-#define PT_BOX_SPREAD 0       // 1: under-filled box-tree rounds spread a node's children over 2 / 4 / 8 lanes (measured: +-0 on the x64
-#endif                        // replica, -1 % on x195 -- the tail rounds wait for their node loads, not for issue slots; ab62)
 #ifndef PT_BIG_WAVES
 #define PT_BIG_WAVES (PT_WAVES_PER_SIMD - 2)   // waves per SIMD the big-scene instantiations are compiled for (they fit 6: 77 VGPRs)
 #endif
@@ -561,184 +558,6 @@ __device__ __forceinline__ uint32_t box_children_kept(const uint4 q0, const uint
     return m;
 }
 
-#ifndef PT_BOX_MIX
-#define PT_BOX_MIX 0   // 1: the float test with the byte -> float conversion folded into the multiply-add (box_children_kept_mix)
-#endif
-// ---------------------------------------------------------------------------------------------------------------
-// The float test again, bit for bit -- with the conversions gone (round 4; profiles/r04_ab_logs.txt slabmix).  A plane byte q,
-// zero-extended to 16 bits, is the half-precision subnormal q 2^-24; v_fma_mix_f32 takes one operand as a half, widens it exactly
-// and does the fused multiply-add in float32.  With A 2^24 for coefficient (folded into the step's exponent) the product is the
-// same real number A q, the sum and its single rounding the same: fma(A 2^24, q 2^-24, B) == fma(A, float(q), B) for every input.
-// So the masks, the rounds, the frames and every argument of DESIGN.md section 5 are those of box_children_kept; what changes is
-// the instruction count: per child six v_fma_mix_f32 instead of six v_cvt_f32_ubyteN + six v_fma_f32, and per node 24
-// instructions that unpack the bytes of the twelve row words into halves (one unpacked register serves two children).
-// ---------------------------------------------------------------------------------------------------------------
-// (Written as inline assembly on purpose.  Left to the compiler -- __builtin_fmaf(a, float(half), b) selects the same
-// v_fma_mix_f32, 203 instructions per node visit instead of 218 with the waits it puts around inline assembly -- the kernel is
-// 2.5 % SLOWER than the float test on the x64 replica instead of 0.8 % faster: its scheduler hoists all twelve unpackings and
-// lengthens the dependent stretch of a visit; r04_ab_logs.txt slabmix.)
-template <int HI>
-__device__ __forceinline__ float fma_mix_h(float a, uint32_t q2, float b) {   // a * half(q2.lo or q2.hi) + b, one rounding, float32
-    float d;
-    if constexpr (HI == 0) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(d) : "v"(a), "v"(q2), "v"(b));
-    else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(d) : "v"(a), "v"(q2), "v"(b));
-    return d;
-}
-__device__ __forceinline__ uint32_t box_children_kept_mix(const uint4 q0, const uint4 q1, const uint4 q2, const uint4 q3, const Ray &r,
-                                                          float ix, float iy, float iz, float t_best, float err) {
-    // the coefficients times 2^24: the factor goes into the step's exponent (pt_scene.cpp keeps it at or below 2^100), everything
-    // derived from them scales back by an exact power of two, so e2 and the planes are those of box_children_kept bit for bit
-    const float step24 = __uint_as_float(((q0.w & 0xFFu) + 24u) << 23);
-    const float cx = step24 * ix, cy = step24 * iy, cz = step24 * iz;
-    const float bx = (__uint_as_float(q0.x) - r.ox) * ix, by = (__uint_as_float(q0.y) - r.oy) * iy, bz = (__uint_as_float(q0.z) - r.oz) * iz;
-    const float bmax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by)), __builtin_fabsf(bz));
-    const float cmax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(cx), __builtin_fabsf(cy)), __builtin_fabsf(cz));
-    const float e2 = 2.0f * err * __builtin_fmaf(255.0f * 5.9604644775390625e-08f, cmax, bmax);   // 255 |A|max + |B|max
-    const float nbx = bx - e2, nby = by - e2, nbz = bz - e2, t_min = -e2;
-    const bool sx = ix < 0.0f, sy = iy < 0.0f, sz = iz < 0.0f;
-    const uint32_t nx[2] = {sx ? q2.z : q1.x, sx ? q2.w : q1.y}, fx[2] = {sx ? q1.x : q2.z, sx ? q1.y : q2.w};
-    const uint32_t ny[2] = {sy ? q3.x : q1.z, sy ? q3.y : q1.w}, fy[2] = {sy ? q1.z : q3.x, sy ? q1.w : q3.y};
-    const uint32_t nz[2] = {sz ? q3.z : q2.x, sz ? q3.w : q2.y}, fz[2] = {sz ? q2.x : q3.z, sz ? q2.y : q3.w};
-    uint32_t m = 0;
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-#pragma unroll
-        for (int par = 0; par < 2; ++par) {
-            // bytes (0, 2) or (1, 3) of a row word as two 16-bit numbers: children 4 w + par and 4 w + par + 2
-            auto un = [&](uint32_t v) {
-                if (par == 0) return v & 0x00FF00FFu;
-                uint32_t d;
-                asm("v_pk_lshrrev_b16 %0, 8, %1 op_sel_hi:[0,1]" : "=v"(d) : "v"(v));   // (op_sel_hi: the inline 8 shifts the high half too)
-                return d;
-            };
-            const uint32_t unx = un(nx[w]), uny = un(ny[w]), unz = un(nz[w]), ufx = un(fx[w]), ufy = un(fy[w]), ufz = un(fz[w]);
-            auto child = [&](auto hi_c) {
-                constexpr int HI = decltype(hi_c)::value;
-                const float tnx = fma_mix_h<HI>(cx, unx, nbx), tfx = fma_mix_h<HI>(cx, ufx, bx);
-                const float tny = fma_mix_h<HI>(cy, uny, nby), tfy = fma_mix_h<HI>(cy, ufy, by);
-                const float tnz = fma_mix_h<HI>(cz, unz, nbz), tfz = fma_mix_h<HI>(cz, ufz, bz);
-                // (max / min by name: on the outputs of inline assembly the compiler would first quiet possible signalling NaNs,
-                // one v_max_f32 x, x per value)
-                float t_in, t_out;
-                asm("v_max3_f32 %0, %1, %2, %3" : "=v"(t_in) : "v"(tnx), "v"(tny), "v"(tnz));
-                asm("v_max_f32 %0, %1, %2" : "=v"(t_in) : "v"(t_in), "v"(t_min));
-                asm("v_min3_f32 %0, %1, %2, %3" : "=v"(t_out) : "v"(tfx), "v"(tfy), "v"(tfz));
-                asm("v_min_f32 %0, %1, %2" : "=v"(t_out) : "v"(t_out), "v"(t_best));
-                m |= !(t_in > t_out) ? (1u << (4 * w + par + 2 * HI)) : 0u;   // a NaN keeps
-            };
-            child(std::integral_constant<int, 0>());
-            child(std::integral_constant<int, 1>());
-            // one pair of children at a time: the unpacked rows of all four would cost a wave per SIMD
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    return m;
-}
-
-#ifndef PT_BOX_F16
-#define PT_BOX_F16 0   // 1: the box tree's child boxes are tested two at a time in packed half precision (box_children_kept_h)
-#endif
-// ---------------------------------------------------------------------------------------------------------------
-// The same test in PACKED HALF PRECISION, two children per instruction (round 4; profiles/r04_ab_logs.txt slab16).
-//   * The ray is recentred on the point where it enters the node's frame (t_enter = the latest of the three near planes of the
-//     frame [0, 255]^3) and scaled by a power of two S: T = (t - t_enter) S, with S chosen from the exponent of the smallest
-//     |A| so that the frame's extent along the ray, at most 255 min|A|, is below 2^-10.  What the test compares then lies in
-//     [0, 2^-10), where half precision resolves 2^-21 or better: an eighth to a quarter of the smallest quantisation step.
-//   * A child plane byte q is used AS IT IS: zero-extended to 16 bits it is the half-precision subnormal q 2^-24, and
-//     v_pk_fma_f16 multiplies it exactly (half-precision denormals are on: the kernel descriptor's default); the factor 2^24 goes
-//     into the coefficient.  A ray travelling down an axis sees the frame mirrored (q -> 255 - q = ~q), so every coefficient is
-//     non-negative and every offset non-positive, and the DIRECTED roundings are free: v_cvt_pkrtz rounds the entry planes'
-//     coefficient down and the exit planes' offset up, one added to the bit pattern gives the other two.
-//   * Both roundings of a comparison (the two fused multiply-adds, half an ulp of a value below 2^-10 each: 2^-21 (1 + 2^-6)) and
-//     the float32 stage's own error (3 err (|B| + 255 |A|)_max S) go into the entry planes' offset once per node, like the
-//     allowance of the float version.
-//   * Overflow is conservative by construction: a coefficient beyond the half-precision range saturates at 65504 (entry: a lower
-//     bound) and its successor is +inf (exit: an upper bound); inf * 0 and inf - inf give NaNs, which max / min skip and whose
-//     difference has a clear sign bit: kept.
-// CONSERVATIVE like the float test (tests/bvh_emulation.py: children_kept_f16 restates it operation for operation;
-// tests/test_cull_tables_host.py holds it to the chain test), a little looser: 2 % more node visits and 8 % more (ray, triangle)
-// pairs on the x64 replica (tools/slab_f16_study.py).
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t pk_fma_h(uint32_t a, uint32_t q, uint32_t b) {
-    uint32_t d;
-    asm("v_pk_fma_f16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(q), "v"(b));
-    return d;
-}
-__device__ __forceinline__ uint32_t pk_max_h(uint32_t a, uint32_t b) {
-    uint32_t d;
-    asm("v_pk_max_f16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ uint32_t pk_min_h(uint32_t a, uint32_t b) {
-    uint32_t d;
-    asm("v_pk_min_f16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ uint32_t pk_sub_h(uint32_t a, uint32_t b) {   // a - b in both halves
-    uint32_t d;
-    asm("v_pk_add_f16 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ uint32_t pk_rtz2(float x) {   // (x, x) as two halves, rounded toward zero
-    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(x, x));
-}
-__device__ __forceinline__ uint32_t box_children_kept_h(const uint4 q0, const uint4 q1, const uint4 q2, const uint4 q3, const Ray &r,
-                                                        float ix, float iy, float iz, float t_best, float err) {
-    const float step = __uint_as_float((q0.w & 0xFFu) << 23);
-    const float ax = step * ix, ay = step * iy, az = step * iz;
-    const float bx = (__uint_as_float(q0.x) - r.ox) * ix, by = (__uint_as_float(q0.y) - r.oy) * iy, bz = (__uint_as_float(q0.z) - r.oz) * iz;
-    // the frame's near plane along every axis, the point of entry, the scale
-    const float lx = __builtin_fminf(bx, __builtin_fmaf(255.0f, ax, bx)), ly = __builtin_fminf(by, __builtin_fmaf(255.0f, ay, by)),
-                lz = __builtin_fminf(bz, __builtin_fmaf(255.0f, az, bz));
-    const float t_enter = __builtin_fmaxf(__builtin_fmaxf(lx, ly), lz);
-    const float amin = __builtin_fminf(__builtin_fminf(__builtin_fabsf(ax), __builtin_fabsf(ay)), __builtin_fabsf(az));
-    const float s24 = __uint_as_float(0x81800000u - (__float_as_uint(amin) & 0x7F800000u));   // 2^(5 - exponent of amin): amin s24 in [2^5, 2^6)
-    const float s = s24 * 5.9604644775390625e-08f;                                            // 2^-24
-    // the allowance, in T units: the float32 stage's own rounding (reciprocal to an ulp, products, differences: within err of
-    // |B| + 255 |A| per plane as in the float test, taken with half as much again for the recentring's extra difference) + the two
-    // half-precision roundings of a comparison, 2^-21 (1 + 2^-6); both scale with err (test hooks: CullMutation::box_err)
-    const float bmax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by)), __builtin_fabsf(bz));
-    const float amax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay)), __builtin_fabsf(az));
-    const float m = __builtin_fmaf(3.0f * err * __builtin_fmaf(255.0f, amax, bmax), s, err * (4.842877388e-07f / 5.0e-07f));
-    const uint32_t one = 0x00010001u;                      // one ulp away from zero, both halves
-    const uint32_t anx = pk_rtz2(__builtin_fabsf(ax) * s24), any_ = pk_rtz2(__builtin_fabsf(ay) * s24), anz = pk_rtz2(__builtin_fabsf(az) * s24);
-    const uint32_t afx = anx + one, afy = any_ + one, afz = anz + one;
-    const float dx = lx - t_enter, dy = ly - t_enter, dz = lz - t_enter;   // <= 0
-    const uint32_t bfx = pk_rtz2(dx * s), bfy = pk_rtz2(dy * s), bfz = pk_rtz2(dz * s);
-    const uint32_t bnx = pk_rtz2(__builtin_fmaf(dx, s, -m)) + one, bny = pk_rtz2(__builtin_fmaf(dy, s, -m)) + one, bnz = pk_rtz2(__builtin_fmaf(dz, s, -m)) + one;
-    const float tm = __builtin_fmaf(-t_enter, s, -m), tb = (t_best - t_enter) * s;
-    const uint32_t tmin = pk_rtz2(__builtin_fmaf(__builtin_fabsf(tm), -1.953125e-03f, tm));    // rounded down whatever its sign (2^-9 of slack)
-    const uint32_t tbest = pk_rtz2(__builtin_fmaf(__builtin_fabsf(tb), 1.953125e-03f, tb));    // rounded up
-    // rows: near = lower planes for a ray going up the axis, else the mirrored upper planes (~hi); far likewise.  One v_bitop3 each.
-    const uint32_t mx = static_cast<uint32_t>(__float_as_int(ix) >> 31), my = static_cast<uint32_t>(__float_as_int(iy) >> 31), mz = static_cast<uint32_t>(__float_as_int(iz) >> 31);
-    auto sel = [](uint32_t lo, uint32_t hi, uint32_t mk) { return static_cast<uint32_t>(__builtin_amdgcn_bitop3_b32(lo, hi, mk, 0x72)); };   // mk ? ~hi : lo
-    const uint32_t nx[2] = {sel(q1.x, q2.z, mx), sel(q1.y, q2.w, mx)}, fx[2] = {sel(q2.z, q1.x, mx), sel(q2.w, q1.y, mx)};
-    const uint32_t ny[2] = {sel(q1.z, q3.x, my), sel(q1.w, q3.y, my)}, fy[2] = {sel(q3.x, q1.z, my), sel(q3.y, q1.w, my)};
-    const uint32_t nz[2] = {sel(q2.x, q3.z, mz), sel(q2.y, q3.w, mz)}, fz[2] = {sel(q3.z, q2.x, mz), sel(q3.w, q2.y, mz)};
-    uint32_t dd[2][2];   // [word][parity]: t_out - t_in of children (4 word + parity, 4 word + parity + 2) in the (low, high) half
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-#pragma unroll
-        for (int par = 0; par < 2; ++par) {
-            // bytes (0, 2) or (1, 3) of a row word as two 16-bit numbers: one v_and_b32 / one v_pk_lshrrev_b16
-            auto un = [&](uint32_t v) {
-                if (par == 0) return v & 0x00FF00FFu;
-                uint32_t d;
-                asm("v_pk_lshrrev_b16 %0, 8, %1 op_sel_hi:[0,1]" : "=v"(d) : "v"(v));   // (op_sel_hi: the inline 8 shifts the high half too)
-                return d;
-            };
-            const uint32_t tnx = pk_fma_h(anx, un(nx[w]), bnx), tny = pk_fma_h(any_, un(ny[w]), bny), tnz = pk_fma_h(anz, un(nz[w]), bnz);
-            const uint32_t tfx = pk_fma_h(afx, un(fx[w]), bfx), tfy = pk_fma_h(afy, un(fy[w]), bfy), tfz = pk_fma_h(afz, un(fz[w]), bfz);
-            const uint32_t t_in = pk_max_h(pk_max_h(tnx, tny), pk_max_h(tnz, tmin));
-            const uint32_t t_out = pk_min_h(pk_min_h(tfx, tfy), pk_min_h(tfz, tbest));
-            dd[w][par] = pk_sub_h(t_out, t_in);
-        }
-    }
-    // sign bits -> mask of the children to DROP: child 4 w + par + 2 h sits in bit 15 + 16 h of dd[w][par]
-    const uint32_t acc = ((dd[0][0] >> 15) & 0x00010001u) | ((dd[0][1] >> 14) & 0x00020002u) | ((dd[1][0] >> 11) & 0x00100010u) | ((dd[1][1] >> 10) & 0x00200020u);
-    return ~(acc | (acc >> 14)) & 0xFFu;
-}
-
 // Scene::TraceRay's triangle loop exactly as the reference runs it (scene.cpp:116-120): every triangle, in index order,
 // through Triangle::Intersect for this lane's ray; returns the closest-hit key (~0 = miss).  Wave-uniform control flow.
 // Only the verification build calls it.
@@ -847,9 +666,6 @@ __device__ __forceinline__ void closest_hit(const RenderArgs &a, Lds &lds, const
                     rec.au[0] = c1.x; rec.au[1] = c1.y; rec.au[2] = c1.z; rec.cu = c1.w;
                     rec.av[0] = c2.x; rec.av[1] = c2.y; rec.av[2] = c2.z; rec.cv = c2.w;
                     keep = !cull_reject(rec, r, a.k1, a.k2, a.a_max_all, a.m0_all, a.t_guard_all) || (e >> 31) != 0u;   // bit 31: never filtered
-#ifdef PT_DBG_NO_PREFILTER
-                    keep = true;
-#endif
                 }
                 const unsigned long long ball = __ballot(keep);
                 if (keep) lds.filtered[n_filtered + lanes_below(ball)] = e;
@@ -1317,9 +1133,12 @@ __device__ __forceinline__ void closest_hit(const RenderArgs &a, Lds &lds, const
             while (n_nodes > 0) {
                 ++st.w_node_rounds;
                 const uint32_t cnt = min(64u, n_nodes);
-                // (PT_BOX_SPREAD, off: a round with few items -- the tail of every walk: 1.3 of the x64 replica's 9.1 rounds per
-                // wave-segment hold at most 32 -- spreads each item's 8 children over 2, 4 or 8 lanes, like the sphere-tree walk)
-                uint32_t shift = PT_BOX_SPREAD ? (cnt <= 8u ? 3u : cnt <= 16u ? 2u : cnt <= 32u ? 1u : 0u) : 0u;
+                // One lane per item: shift is always 0.  (Spreading the items of an under-filled round -- the tail of every walk: 1.3 of
+                // the x64 replica's 9.1 rounds per wave-segment hold at most 32 -- over 2, 4 or 8 lanes each, like the sphere-tree walk,
+                // was measured at +-0 on the x64 replica and -1 % on x195: those rounds wait for their node loads, not for issue slots;
+                // r03_ab_logs.txt ab62.  The switch is gone; the walk keeps the shape the compiler was given then, because any other
+                // spelling of it moved the code of the box-tree kernels, profiles/r07_kernel_cleanup.txt.)
+                uint32_t shift = 0u;
                 uint32_t m8, src, base, kids, keep, packed, incl, tot;
                 bool leaf;
                 for (;;) {
@@ -1334,23 +1153,11 @@ __device__ __forceinline__ void closest_hit(const RenderArgs &a, Lds &lds, const
                     r.ox = lds.ray[0][src]; r.oy = lds.ray[1][src]; r.oz = lds.ray[2][src];
                     r.dx = lds.ray[3][src]; r.dy = lds.ray[4][src]; r.dz = lds.ray[5][src];
                     const uint32_t bh = reinterpret_cast<const uint32_t *>(&lds.best[src])[1];   // high word: ordered bits of t
-#ifdef PT_DBG_NO_PRUNE
-                    const float t_best = bh == 0x12345u ? 0.0f : __builtin_inff();
-#else
                     const float t_best = bh == 0xFFFFFFFFu ? __builtin_inff() : from_ordered_bits(bh);
-#endif
                     const uint4 *np = reinterpret_cast<const uint4 *>(a.bvh + node);
                     const uint4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
                     const float ix = lds.rinv.v[0][src], iy = lds.rinv.v[1][src], iz = lds.rinv.v[2][src];
-#if PT_BOX_F16
-                    static_assert(!PT_BOX_SPREAD, "the half-precision test handles a node's eight children in one lane");
-                    if (shift == 0u) m8 = box_children_kept_h(q0, q1, q2, q3, r, ix, iy, iz, t_best, a.bvh_err);
-#elif PT_BOX_MIX
-                    static_assert(!PT_BOX_SPREAD, "the mixed-precision form handles a node's eight children in one lane");
-                    if (shift == 0u) m8 = box_children_kept_mix(q0, q1, q2, q3, r, ix, iy, iz, t_best, a.bvh_err);
-#else
                     if (shift == 0u) m8 = box_children_kept<8>(q0, q1, q2, q3, r, ix, iy, iz, t_best, a.bvh_err);
-#endif
                     else if (shift == 1u) m8 = box_children_kept<4>(q0, q1, q2, q3, r, ix, iy, iz, t_best, a.bvh_err, sub);
                     else if (shift == 2u) m8 = box_children_kept<2>(q0, q1, q2, q3, r, ix, iy, iz, t_best, a.bvh_err, sub);
                     else m8 = box_children_kept<1>(q0, q1, q2, q3, r, ix, iy, iz, t_best, a.bvh_err, sub);
@@ -1466,9 +1273,6 @@ __device__ __forceinline__ void closest_hit(const RenderArgs &a, Lds &lds, const
 #define PT_RAYS_PER_LANE 2   // pixels (rays) per lane of the small-scene, statistics-free, skybox-free kernel; 1 = one 8 x 8 tile per wave
 #endif
 constexpr int kMaxBatchPass = 32766;   // adaptive instantiations: a pixel's next pass (at most one past the launch's last) << 1 | a flag in 16 bits
-#ifndef PT_ADAPT4_DYN
-#define PT_ADAPT4_DYN 0   // 32 x 8 adaptive kernel: 1 = batches of at most 64 switch the second ray slots off (scalar branches around every per-ray piece)
-#endif
 #ifndef PT_ADAPT_TWO_AT
 #define PT_ADAPT_TWO_AT 100   // adaptive kernels: pixels with a pass to run from which a batch takes up to 128, two per lane (80 ... 112 within 1 %, adapt3)
 #endif
@@ -1580,8 +1384,8 @@ __global__ __launch_bounds__(kBlock, BIG ? PT_BIG_WAVES : PT_WAVES_PER_SIMD) voi
     }
 }
 
-// Diagnostic (test builds call it through pt_test_box_masks): both forms of the box tree's child test on caller-supplied
-// (node, ray, t_best) items, one item per lane -- out[2 i] = box_children_kept<8>, out[2 i + 1] = box_children_kept_h.
+// Diagnostic (test builds call it through pt_test_box_masks): the box tree's child test on caller-supplied
+// (node, ray, t_best) items, one item per lane -- out[i] = box_children_kept of item i, children that do not exist masked off.
 __global__ __launch_bounds__(kBlock) void box_masks_kernel(const BvhNode *__restrict__ nodes, const float *__restrict__ rays,
                                                            const float *__restrict__ t_best, float err, int n, uint32_t *__restrict__ out) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -1593,10 +1397,7 @@ __global__ __launch_bounds__(kBlock) void box_masks_kernel(const BvhNode *__rest
     r.dx = rays[6 * i + 3]; r.dy = rays[6 * i + 4]; r.dz = rays[6 * i + 5];
     const float ix = __builtin_amdgcn_rcpf(r.dx), iy = __builtin_amdgcn_rcpf(r.dy), iz = __builtin_amdgcn_rcpf(r.dz);
     const uint32_t exists = (2u << ((q0.w >> 8) & 7u)) - 1u;
-    out[2 * i] = box_children_kept<8>(q0, q1, q2, q3, r, ix, iy, iz, t_best[i], err) & exists;
-    // (bits 8-15 of the second word: the mixed-precision form, which must equal the float form bit for bit)
-    out[2 * i + 1] = (box_children_kept_h(q0, q1, q2, q3, r, ix, iy, iz, t_best[i], err) & exists) |
-                     ((box_children_kept_mix(q0, q1, q2, q3, r, ix, iy, iz, t_best[i], err) & exists) << 8);
+    out[i] = box_children_kept<8>(q0, q1, q2, q3, r, ix, iy, iz, t_best[i], err) & exists;
 }
 hipError_t launch_box_masks(const BvhNode *d_nodes, const float *d_rays, const float *d_t_best, float err, int n, uint32_t *d_out, hipStream_t stream) {
     if (n <= 0) return hipSuccess;

@@ -79,7 +79,7 @@ const plan::Build &integrator_build();
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached)
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);
-// diagnostic: both forms of the box tree's child test on (node, ray, t_best) items; out[2 i] = float form, out[2 i + 1] = half-precision form
+// diagnostic: the box tree's child test on n (node, ray, t_best) items; out[i] = the mask of item i's kept children
 hipError_t launch_box_masks(const BvhNode *d_nodes, const float *d_rays, const float *d_t_best, float err, int n, uint32_t *d_out, hipStream_t stream);
 hipError_t launch_trace_rays(const RenderArgs &args, const float *d_origins, const float *d_directions, int n_rays,
                              int32_t *d_hit_index, float *d_hit_t, hipStream_t stream);

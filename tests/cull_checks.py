@@ -121,7 +121,7 @@ def quad_records(scene, oracle_scene, rng, n_per_triangle, lo, hi, eps=1e-4):
 
 def box_chain(g, o, rng, n, unit=1.0, eps=1e-4):
     """Big scenes: the chain of box-tree nodes above the triangle the reference hits must survive the kernel's slab test (numpy
-    restatement in float32, tests/bvh_emulation.py; the float and the packed half-precision form) for the tightest t_best the
+    restatement in float32, tests/bvh_emulation.py) for the tightest t_best the
     walk can hold: the hit's own t.  n rays from points `1e-4 unit` off random surfaces into random directions.  `g`: the
     library's scene (its box tree), `o`: the oracle's.  Returns (hits on triangles of the tree, levels walked, dropped: [(level,
     form, count)])."""
@@ -160,10 +160,6 @@ def box_chain(g, o, rng, n, unit=1.0, eps=1e-4):
         kept = B.children_kept(t, node, ro, rd, tb, 5e-7)
         if not kept[np.arange(len(node)), child].all():
             dropped.append((levels, "float", int((~kept[np.arange(len(node)), child]).sum())))
-        # the packed half-precision form of the test (pt_kernels.hip: box_children_kept_h, built with -DPT_BOX_F16=1) on the same items
-        kept_h = B.children_kept_f16(t, node, ro, rd, tb)
-        if not kept_h[np.arange(len(node)), child].all():
-            dropped.append((levels, "half", int((~kept_h[np.arange(len(node)), child]).sum())))
         child, node = pos[node], par[node]
         live = node >= 0
         node, child, ro, rd, tb = node[live], child[live], ro[live], rd[live], tb[live]

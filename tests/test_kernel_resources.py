@@ -17,7 +17,7 @@ USAGE = os.path.join(ROOT, "path-tracing_amd", "lib", "asm", "resource_usage.txt
 
 @pytest.fixture(scope="module")
 def usage():
-    srcs = [os.path.join(CSRC, f) for f in ("pt_kernels.hip", "pt_kernels.hpp", "pt_fastfp.hpp", "pt_scene.hpp", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("pt_kernels.hip", "pt_integrator_body.inc", "pt_kernels.hpp", "pt_launch_plan.hpp", "pt_fastfp.hpp", "pt_scene.hpp", "Makefile")]
     if not os.path.exists(USAGE) or os.path.getmtime(USAGE) < max(os.path.getmtime(f) for f in srcs):
         subprocess.check_call(["make", "-C", CSRC, "-s", "asm"])
     out, name = {}, None
