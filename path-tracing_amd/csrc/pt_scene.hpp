@@ -1,4 +1,5 @@
-// Host-side scene: OBJ/MTL ingestion with the reference's token semantics and the tables the kernels read.
+// Host-side scene: OBJ/MTL ingestion with the reference's token semantics (pt_scene.cpp) and the tables the kernels read
+// (device tables: pt_scene.cpp; culling hierarchy: pt_cull_tables.cpp).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -15,6 +16,8 @@ struct HostScene {
     int n_tri() const { return static_cast<int>(tri_mat.size()); }
     int n_mat() const { return static_cast<int>(mat.size() / 10); }
 };
+// A material with Ke != 0 is the emissive lobe alone (Factory, material.h:58-106).  `mat`: the material's ten floats.
+inline bool material_emits(const float *mat) { return mat[3] != 0.0f || mat[4] != 0.0f || mat[5] != 0.0f; }
 
 // Scene::LoadModel (scene.cpp:26-109).  Returns false and sets `err` on I/O or index errors
 // (the reference exits or has undefined behaviour there).
@@ -61,11 +64,11 @@ static const int kMaxLevels = 8; // small class: tree levels per cluster (8^8 tr
 #define PT_TILE_W 8
 #endif
 static const int kTileW = PT_TILE_W, kTileH = 64 / PT_TILE_W;
-// The box tree's depth is variable (build_bvh_sah).  The kernel's walk commits the top item of a full node stack whatever
+// The box tree's depth is variable (pt_cull_tables.cpp: sah_topology).  The kernel's walk commits the top item of a full node stack whatever
 // its children need (pt_kernels.hip, "Rare: not everything fits"): in that mode the stack holds a depth-first path, at most 7
 // waiting siblings per inner level above kNodeStack, and the stack has 64 entries of slack: 7 x (depth - 1) <= 64 allows 10
 // levels; 9 are allowed (same value as PT_MAX_BVH_DEPTH of the ABI header).  A deeper SAH tree is replaced by the uniform-depth
-// tree (build_bvh: at most 8 levels below 2^24 triangles).
+// tree (uniform_topology: at most 8 levels below 2^24 triangles).
 static const int kMaxBvhDepth = 9;
 // Above kBigSceneTriangles triangles a scene gets ONE box tree over all its small triangles and the big-scene kernels (deep
 // queues, pair pre-filter); up to it, sphere trees per connected group and the small-scene kernels.  The switch is made by the
@@ -125,7 +128,8 @@ struct CullConstants {
     float t_guard;    // beyond this |t| the cull test abstains
 };
 
-// Everything the cull stage reads; depends on eps, so a scene caches one set per eps value.
+// Everything the cull stage reads; depends on eps, so a scene caches one set per eps value.  (A new field also goes into the
+// digest of tests/native/cull_tables_digest_main.cpp, which pins every byte of these tables.)
 struct CullTables {
     std::vector<uint32_t> slot_tri;  // slot -> original triangle index (kNoTriangle for padding slots)
     std::vector<ExactRec> exact_slot;// exact records in slot order
@@ -177,7 +181,8 @@ struct DeviceTables {
     std::vector<MatRec> mats;      // n_mat
 };
 
-void build_device_tables(const HostScene &s, DeviceTables &out);
+void build_device_tables(const HostScene &s, DeviceTables &out);   // pt_scene.cpp
+// The culling hierarchy (pt_cull_tables.cpp).
 // r_camera: largest |component| of the camera origin the primary rays start from (the reference's: 20, main.cpp:129).  The
 // envelope is r_org = cull_r_max(s, r_camera) + 1.
 void build_cull_tables(const HostScene &s, float eps, CullTables &out, double r_camera = 20.0);

@@ -1,7 +1,7 @@
 """The soundness checks of the culling hierarchy as functions of the scene -- test infrastructure, no test.
 
 "A triangle the reference ACCEPTS for a ray is never culled for that ray", restated for the three structures the host builds
-(pt_scene.cpp: build_cull_tables): the sphere levels of a small cluster, the quad records of the large class and the chain of
+(pt_cull_tables.cpp: build_cull_tables): the sphere levels of a small cluster, the quad records of the large class and the chain of
 box-tree nodes above a hit.  tests/test_cull_tables_host.py runs them on the scenes as they are, tests/test_scene_scales_host.py on
 scaled and shifted copies; each takes the box its ray origins are drawn from and the length unit of its offsets."""
 import ctypes as C

@@ -1,6 +1,6 @@
 """Scenes at other scales and places, and the adversarial rays that go with them -- test infrastructure, no test.
 
-The culling margins (pt_scene.cpp: build_cull_tables, cull_constants) are derived from the scene's extent, and several of
+The culling margins (pt_cull_tables.cpp: build_cull_tables, margins) are derived from the scene's extent, and several of
 their constants are in absolute units.  transformed() writes an OBJ whose vertices are scaled by a power of two and / or
 shifted, camera_for() moves the reference's camera along, adversarial_rays() takes the box the origins are drawn from and the
 length unit of its offsets, so that a test can ask at every entry of TRANSFORMS what the suite asks at scale 1."""

@@ -1,4 +1,4 @@
-"""The float-error constants behind the culling margins (pt_scene.cpp: tri_geometry, build_cull_tables, build_bvh), each
+"""The float-error constants behind the culling margins (pt_cull_tables.cpp: tri_geometry, margins, build_box_tree), each
 written as the inequality it stands for and checked on random triangles / rays: float32 arithmetic in the operation order
 of the code it bounds, against float64 on the SAME float32 inputs.  CPU only.
 

@@ -1,4 +1,4 @@
-"""CPU checks of the culling hierarchy the host builds (pt_scene.cpp: build_cull_tables): structure, containment, and
+"""CPU checks of the culling hierarchy the host builds (pt_cull_tables.cpp: build_cull_tables): structure, containment, and
 the property everything rests on -- a triangle the reference ACCEPTS for a ray is never culled for that ray.
 
 The hierarchy lists the triangles in its own SLOT order (spatial grouping, independent of the file order); cluster
@@ -157,7 +157,7 @@ def test_hierarchy_does_not_depend_on_the_file_order(tmp_path, models_dir, tor):
 def test_box_tree_never_drops_the_chain_above_a_hit(tmp_path, bvh_mode, request):
     """Big scenes: the chain of box-tree nodes above the triangle the reference hits survives the kernel's slab test
     (numpy restatement in float32, tests/bvh_emulation.py) for the tightest t_best the walk can hold: the hit's own t.
-    Both tree builders (pt_scene.cpp: build_bvh, build_bvh_sah), chosen through the test-hook build."""
+    Both tree builders (pt_cull_tables.cpp: uniform_topology, sah_topology), chosen through the test-hook build."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_replicated_scene as M
     d = str(tmp_path) + "/"
@@ -177,7 +177,7 @@ def test_box_tree_never_drops_the_chain_above_a_hit(tmp_path, bvh_mode, request)
 
 
 def test_big_scene_keeps_its_few_emitters_in_the_large_class(tmp_path, models_dir):
-    """pt_scene.cpp: a big scene's emitters (<= 8 triangles: the light of a room) join the large class whatever their size,
+    """pt_cull_tables.cpp: a big scene's emitters (<= 8 triangles: the light of a room) join the large class whatever their size,
     so that the kernel's last-segment test has their records; many emissive triangles stay under the box tree."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_replicated_scene as M

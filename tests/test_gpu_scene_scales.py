@@ -1,7 +1,7 @@
 """The device's closest hits and frames at other scene scales and positions (tests/scene_transforms.py: TRANSFORMS).
 
 Every other scene of the suite lies within about 25 units of the origin, so the scale dependence of the culling margins -- the
-absolute constants of pt_scene.cpp (r_org's + 1, the envelope's 0.01, m0's 1e-6, t_guard, the absorption bound, disc_err), the
+absolute constants of pt_cull_tables.cpp (r_org's + 1, the envelope's 0.01, m0's 1e-6, t_guard, the absorption bound, disc_err), the
 8-bit quantisation of the box tree's nodes and the kernel's envelope test -- went unchecked on the device.  The reference itself
 behaves differently there (at 2^10 with the default eps its area test drowns in float error and it accepts barely half of the
 aimed rays), and the library promises its bits for any OBJ.  Three scenes -- Tor.obj (sphere trees, large class), its x9

@@ -17,7 +17,7 @@ def test_scene_code_is_clean_under_asan_and_ubsan(tmp_path, models_dir):
     csrc = os.path.join(ROOT, "path-tracing_amd", "csrc")
     build = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                             "-fno-omit-frame-pointer", "-I", csrc, os.path.join(ROOT, "tests", "native", "scene_sanitizer_main.cpp"),
-                            os.path.join(csrc, "pt_scene.cpp"), "-o", exe], capture_output=True, text=True)
+                            os.path.join(csrc, "pt_scene.cpp"), os.path.join(csrc, "pt_cull_tables.cpp"), "-o", exe], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-3000:]
     run = subprocess.run([exe, models_dir, str(tmp_path) + "/"], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, (run.stdout[-1500:], run.stderr[-3000:])
@@ -33,13 +33,13 @@ def test_scene_code_is_clean_under_asan_and_ubsan(tmp_path, models_dir):
 @pytest.mark.skipif(shutil.which("g++") is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime_api.h"), reason="g++ or the HIP headers are not available")
 def test_c_api_host_side_is_clean_under_tsan(tmp_path, models_dir):
     """pt_resolve runs bands of rows on several host threads and per-device copies of a scene share one hierarchy cache:
-    the C API's host code (pt_capi.cpp, pt_frame.cpp, pt_scene.cpp; kernel launchers stubbed) under ThreadSanitizer, on the CPU."""
+    the C API's host code (pt_capi.cpp, pt_frame.cpp, pt_scene.cpp, pt_cull_tables.cpp; kernel launchers stubbed) under ThreadSanitizer, on the CPU."""
     exe = str(tmp_path / "capi_tsan")
     csrc = os.path.join(ROOT, "path-tracing_amd", "csrc")
     build = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=thread", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__",
                             "-I", csrc, "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
                             os.path.join(ROOT, "tests", "native", "resolve_tsan_main.cpp"), os.path.join(csrc, "pt_capi.cpp"),
-                            os.path.join(csrc, "pt_frame.cpp"), os.path.join(csrc, "pt_scene.cpp"), "-o", exe,
+                            os.path.join(csrc, "pt_frame.cpp"), os.path.join(csrc, "pt_scene.cpp"), os.path.join(csrc, "pt_cull_tables.cpp"), "-o", exe,
                             "-L/opt/rocm/lib", "-lamdhip64", "-ldl", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-3000:]
     run = subprocess.run([exe, models_dir], capture_output=True, text=True, timeout=600)
@@ -60,7 +60,7 @@ def test_c_api_error_paths_are_clean_under_asan(tmp_path, models_dir):
     build = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
                             "-D__HIP_PLATFORM_AMD__", "-I", csrc, "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
                             os.path.join(ROOT, "tests", "native", "capi_asan_main.cpp"), os.path.join(csrc, "pt_capi.cpp"),
-                            os.path.join(csrc, "pt_frame.cpp"), os.path.join(csrc, "pt_scene.cpp"), "-o", exe,
+                            os.path.join(csrc, "pt_frame.cpp"), os.path.join(csrc, "pt_scene.cpp"), os.path.join(csrc, "pt_cull_tables.cpp"), "-o", exe,
                             "-L/opt/rocm/lib", "-lamdhip64", "-ldl", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr[-3000:]
     sky = str(tmp_path / "sky.bmp")

@@ -174,7 +174,7 @@ def _tables(scene, eps=1e-4):
 
 
 def _r_org(scene, eps=1e-4):
-    """k2 = kU (24 sqrt(3) + 8) r_org (pt_scene.cpp, margins of the barycentric test)."""
+    """k2 = kU (24 sqrt(3) + 8) r_org (pt_cull_tables.cpp, margins of the barycentric test)."""
     return scene.cull_tables(eps)["constants"]["k2"] / (KU * (24 * np.sqrt(3) + 8))
 
 

@@ -1,6 +1,6 @@
 """CPU checks of the culling hierarchy at other scene scales and positions (tests/scene_transforms.py: TRANSFORMS).
 
-The margins of pt_scene.cpp (build_cull_tables, cull_constants) are derived from the scene's extent r_org, and several of their
+The margins of pt_cull_tables.cpp (build_cull_tables, margins) are derived from the scene's extent r_org, and several of their
 constants are absolute; every other scene of the suite lies within about 25 units of the origin.  Here Tor.obj and its x9
 replica are scaled by 2^-10 ... 2^10 and shifted by up to 4096, and the soundness checks of test_cull_tables_host.py
 (tests/cull_checks.py) are asked again, each with the reference's default eps and with eps scaled along with the scene: a
