@@ -476,6 +476,60 @@ int pt_temporal_push_host(pt_temporal *t, const float *sum, const float *sum2, c
 int pt_temporal_reset(pt_temporal *t);           /* forget the history; the next push is a first frame */
 void pt_temporal_destroy(pt_temporal *t);
 
+/* ---- device-resident display path: accumulators to image bytes ------------------------------------------- */
+
+/* What a preview or a fly-through needs on the host is 3 bytes per pixel.  A pt_display turns the accumulators of a session or a
+ * frame into those bytes WHERE THEY LIE: a present runs, as one chain on the device and behind every slice enqueued so far, the
+ * first-hit features (if a stage needs them), the temporal merge, the denoiser, then the tone map and quantization, and copies
+ * height * width * 3 bytes (top-down rows, B,G,R, as pt_resolve writes them) to the host.  The bytes are DEFINED by the host
+ * chain and equal it bit for bit, for every input:
+ *   temporal = 0, denoise.levels = 0   pt_resolve(sum, sum2, count, gamma) of pt_session_read / pt_frame_read
+ *   temporal = 0, denoise.levels > 0   pt_render_features_host -> pt_denoise_host -> pt_tonemap -> pt_quantize, with count_out
+ *   temporal != 0, denoise.levels = 0  pt_temporal_push_host -> pt_resolve of the merged accumulators
+ *   temporal != 0, denoise.levels > 0  pt_temporal_push_host with `denoise` -> pt_tonemap -> pt_quantize, with mean_count
+ * Every present with temporal != 0 pushes one frame into the display's own history, exactly as one pt_temporal_push_host call
+ * would; a failed present leaves the history as it was.  A present reads the handle's camera at the time of the call (the lens
+ * is ignored, as for the features); `eps` of the create call is the features'.
+ *
+ * How the device can equal std::pow: for gamma > 0, L(m) = (int)(pow(m, gamma) * 255.0f) is a non-decreasing step function of
+ * m >= 0, so L(m) is the number of thresholds T_k <= m, T_k being the smallest float with L >= k, and the byte is L(m) & 255
+ * (levels above 255 wrap: a mean of 2 gives 349 and the byte 93 at the default gamma).  The host tabulates T_1 .. T_K, K <= 4096,
+ * from its own pow by bisection (pt_display_table), checks the 64 floats on either side of every threshold and records a DOUBT
+ * BAND [lo_k, hi_k) where they disagree with "below: < k, at or above: >= k"; levels no finite float reaches shorten the table.
+ * The kernel only compares.  A pixel with a channel that is negative or NaN, at or above the last threshold, or inside a doubt
+ * band is DEFERRED: the kernel puts it on a list, the host finishes it with pt_tonemap's and pt_quantize's own arithmetic. */
+typedef struct pt_display pt_display;
+typedef struct pt_display_params {
+    float gamma;                 /* finite and > 0, else PT_ERR_INVALID_ARGUMENT */
+    int32_t temporal;            /* 0: no temporal stage; else merge with this display's history */
+    pt_temporal_params temporal_params;
+    pt_denoise_params denoise;   /* levels = 0: no filter */
+} pt_display_params;
+typedef struct pt_display_info {
+    float kernel_ms;             /* HIP events around the whole chain */
+    int32_t deferred_pixels;     /* pixels finished on the host */
+    int32_t table_levels;        /* thresholds in use (<= 4096) */
+    int32_t doubt_bands;
+} pt_display_info;
+
+/* A display of a session that covers the whole image (row_begin 0, row_end = height, row_stride 0 / 1; anything else:
+ * PT_ERR_UNSUPPORTED), or of any frame: a present of a frame gathers first if a band changed, as pt_frame_read does, and then works
+ * on the root device's full-frame planes with the root copy's camera.  The session / frame must outlive the display; calls on one
+ * display and its session / frame are serialised by the caller. */
+int pt_display_create(pt_session *session, float eps, pt_display **out);
+int pt_display_create_frame(pt_frame *frame, float eps, pt_display **out);
+int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info /* may be NULL */);
+int pt_display_reset(pt_display *d);     /* forget the history: the next present with a temporal stage is a first frame */
+void pt_display_destroy(pt_display *d);
+
+/* The kernel alone, on a host image: the bytes of pt_tonemap -> pt_quantize for (mean_rgb, count), made on HIP device `device`.
+ * PT_ERR_NO_DEVICE if that is not a usable device (there is no CPU fallback). */
+int pt_display_bytes_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count,
+                          float gamma, uint8_t *bgr, pt_display_info *info /* may be NULL */);
+/* The table itself (host only, no device).  *levels = K; thresholds, doubt_lo, doubt_hi (each may be NULL: pass all NULL to query
+ * K) get K floats: T_k at [k - 1], and the doubt band of level k, empty (lo == hi) where none is needed. */
+int pt_display_table(float gamma, int32_t *levels, float *thresholds, float *doubt_lo, float *doubt_hi);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

@@ -41,7 +41,9 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_camera_look_at", "pt_scene_set_camera", "pt_scene_get_camera", "pt_frame_set_camera",
                "pt_scene_set_lens", "pt_scene_get_lens", "pt_frame_set_lens",
                "pt_render_features_host", "pt_denoise_host", "pt_tonemap",
-               "pt_temporal_create", "pt_temporal_push_host", "pt_temporal_reset", "pt_temporal_destroy"]
+               "pt_temporal_create", "pt_temporal_push_host", "pt_temporal_reset", "pt_temporal_destroy",
+               "pt_display_create", "pt_display_create_frame", "pt_display_present", "pt_display_reset", "pt_display_destroy",
+               "pt_display_bytes_host", "pt_display_table"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -119,6 +121,22 @@ DENOISE_MAX_LEVELS = 8
 class TemporalParams(C.Structure):
     """pt_temporal_params: a zeroed struct holds the defaults (max_frames 32, sigma_plane 0.1, min_normal_dot 0.9)."""
     _fields_ = [("max_frames", C.c_float), ("sigma_plane", C.c_float), ("min_normal_dot", C.c_float)]
+
+
+class DisplayParams(C.Structure):
+    """pt_display_params: gamma, whether the display's temporal stage runs (and its parameters), the filter (levels 0 = none)."""
+    _fields_ = [("gamma", C.c_float), ("temporal", C.c_int32), ("temporal_params", TemporalParams), ("denoise", DenoiseParams)]
+
+
+class DisplayInfo(C.Structure):
+    """pt_display_info: the chain's milliseconds, the pixels the host finished, the table's levels and doubt bands."""
+    _fields_ = [("kernel_ms", C.c_float), ("deferred_pixels", C.c_int32), ("table_levels", C.c_int32), ("doubt_bands", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+DISPLAY_MAX_LEVELS = 4096
 
 
 def _lens_arg(radius, focus_distance):
@@ -249,6 +267,15 @@ def load_library(path):
     L.pt_temporal_reset.argtypes = [vp]
     L.pt_temporal_destroy.argtypes = [vp]
     L.pt_temporal_destroy.restype = None
+    bp = C.POINTER(C.c_uint8)
+    L.pt_display_create.argtypes = [vp, C.c_float, C.POINTER(vp)]
+    L.pt_display_create_frame.argtypes = [vp, C.c_float, C.POINTER(vp)]
+    L.pt_display_present.argtypes = [vp, C.POINTER(DisplayParams), bp, C.POINTER(DisplayInfo)]
+    L.pt_display_reset.argtypes = [vp]
+    L.pt_display_destroy.argtypes = [vp]
+    L.pt_display_destroy.restype = None
+    L.pt_display_bytes_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, bp, C.POINTER(DisplayInfo)]
+    L.pt_display_table.argtypes = [C.c_float, ip, fp, fp, fp]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -550,6 +577,90 @@ class Temporal:
             self.close()
         except Exception:
             pass
+
+
+def _denoise_params(denoise):
+    """None, a DenoiseParams, or a dict of pt.denoise's keyword parameters -> a DenoiseParams (None: levels = 0)."""
+    if denoise is None:
+        return DenoiseParams()
+    if isinstance(denoise, dict):
+        return DenoiseParams(denoise.get("levels", 5), denoise.get("sigma_luminance", 0.0), denoise.get("sigma_plane", 0.0),
+                             denoise.get("normal_power_log2", 0), denoise.get("demodulate_albedo", 0))
+    return denoise
+
+
+class Display:
+    """pt_display: the image bytes of a Session (covering the whole image) or a Frame, made on the device where the accumulators
+    lie.  present() runs features, the temporal merge with the display's own history, the denoiser, the tone map and the
+    quantization as one chain behind the slices enqueued so far; the bytes equal the host chain's."""
+
+    def __init__(self, session_or_frame, eps=1e-4):
+        self._src, self._L = session_or_frame, session_or_frame._L      # the session / frame must outlive the display
+        self.width, self.height = session_or_frame.width, session_or_frame.height
+        self._h = C.c_void_p()
+        create = self._L.pt_display_create_frame if isinstance(session_or_frame, Frame) else self._L.pt_display_create
+        _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
+
+    def present(self, gamma=None, temporal=None, denoise=None):
+        """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
+        parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
+        parameters.  Returns (bgr uint8 [H, W, 3], info dict)."""
+        if gamma is None:
+            gamma = np.float32(1) / np.float32(2.2)   # config.h:25
+        if isinstance(temporal, dict):
+            temporal = TemporalParams(temporal.get("max_frames", 0.0), temporal.get("sigma_plane", 0.0), temporal.get("min_normal_dot", 0.0))
+        on = temporal is not None and temporal is not False
+        prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
+                            _denoise_params(denoise))
+        bgr = np.zeros((self.height, self.width, 3), np.uint8)
+        info = DisplayInfo()
+        _check(self._L.pt_display_present(self._h, C.byref(prm), bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)), self._L)
+        return bgr, info.as_dict()
+
+    def reset(self):
+        """Forget the history: the next present with a temporal stage is a first frame."""
+        _check(self._L.pt_display_reset(self._h), self._L)
+
+    def close(self):
+        if self._h:
+            self._L.pt_display_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def display_bytes(mean_rgb, count, gamma=None, device=0, library=None):
+    """pt_display_bytes_host: the display kernel alone on a host image mean_rgb [H, W, 3] with count [H, W] -- the bytes of
+    quantize(tonemap(...)).  Returns (bgr uint8 [H, W, 3], info dict)."""
+    L = library or lib()
+    if gamma is None:
+        gamma = np.float32(1) / np.float32(2.2)
+    m = np.ascontiguousarray(mean_rgb, np.float32)
+    if m.ndim != 3 or m.shape[2] != 3:
+        raise ValueError("display_bytes: mean_rgb must be [H, W, 3]")
+    h, w, _ = m.shape
+    c = np.ascontiguousarray(count, np.int32)
+    if c.size != w * h:
+        raise ValueError("display_bytes: count does not hold width x height pixels")
+    bgr = np.zeros((h, w, 3), np.uint8)
+    info = DisplayInfo()
+    _check(L.pt_display_bytes_host(device, w, h, _fp(m), _ip(c), C.c_float(gamma), bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)), L)
+    return bgr, info.as_dict()
+
+
+def display_table(gamma, library=None):
+    """pt_display_table (host only): dict of thresholds [K] (T_k at [k - 1]: the smallest float the host's tone map puts at level k
+    or above), doubt_lo / doubt_hi [K] (the doubt band of level k, empty where lo == hi)."""
+    L = library or lib()
+    k = C.c_int32()
+    _check(L.pt_display_table(C.c_float(gamma), C.byref(k), None, None, None), L)
+    out = {"thresholds": np.zeros(k.value, np.float32), "doubt_lo": np.zeros(k.value, np.float32), "doubt_hi": np.zeros(k.value, np.float32)}
+    _check(L.pt_display_table(C.c_float(gamma), C.byref(k), _fp(out["thresholds"]), _fp(out["doubt_lo"]), _fp(out["doubt_hi"])), L)
+    return out
 
 
 def bvh_depth(nodes):

@@ -941,7 +941,7 @@ static void resolve_rows(int32_t width, int y0, int y1, const float *sum, const 
             for (int k = 0; k < 3; ++k) {
                 const float mean = sum[3 * p + k] / n;
                 dd[k] = sum2[3 * p + k] / n - mean * mean;
-                c[k] = std::pow(sum[3 * p + k] / n, gamma) * 255.0f;   // main.cpp:179-182
+                c[k] = ptc::tonemap_value(sum[3 * p + k] / n, gamma);   // main.cpp:179-182
             }
             const float d = dd[0] + dd[1] + dd[2];
             if (d > max_d) max_d = d;
@@ -1003,9 +1003,9 @@ int pt_resolve(int32_t width, int32_t height, const float *sum, const float *sum
                 return;
             }
             // set_pixel(x, y, float, float, float): float -> unsigned char (bitmap_image.hpp:194-206)
-            bgr[3 * p + 0] = static_cast<uint8_t>(static_cast<int>(c[2]));
-            bgr[3 * p + 1] = static_cast<uint8_t>(static_cast<int>(c[1]));
-            bgr[3 * p + 2] = static_cast<uint8_t>(static_cast<int>(c[0]));
+            bgr[3 * p + 0] = ptc::quantize_value(c[2]);
+            bgr[3 * p + 1] = ptc::quantize_value(c[1]);
+            bgr[3 * p + 2] = ptc::quantize_value(c[0]);
         });
         return static_cast<int>(PT_OK);
     });
@@ -1065,7 +1065,7 @@ int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32
     const size_t n = static_cast<size_t>(width) * height;
     for (size_t p = 0; p < n; ++p)
         for (int k = 0; k < 3; ++k)   // main.cpp:179-182
-            rgb[3 * p + k] = count[p] ? std::pow(mean_rgb[3 * p + k], gamma) * 255.0f : mean_rgb[3 * p + k];
+            rgb[3 * p + k] = count[p] ? ptc::tonemap_value(mean_rgb[3 * p + k], gamma) : mean_rgb[3 * p + k];
     return PT_OK;
 }
 
@@ -1075,9 +1075,9 @@ int pt_quantize(int32_t width, int32_t height, const float *rgb, const int32_t *
     std::memset(bgr, 0, n * 3);
     for (size_t p = 0; p < n; ++p) {   // main.cpp:193-201: only pixels with samples are written
         if (!count[p]) continue;
-        bgr[3 * p + 0] = static_cast<uint8_t>(static_cast<int>(rgb[3 * p + 2]));
-        bgr[3 * p + 1] = static_cast<uint8_t>(static_cast<int>(rgb[3 * p + 1]));
-        bgr[3 * p + 2] = static_cast<uint8_t>(static_cast<int>(rgb[3 * p + 0]));
+        bgr[3 * p + 0] = ptc::quantize_value(rgb[3 * p + 2]);
+        bgr[3 * p + 1] = ptc::quantize_value(rgb[3 * p + 1]);
+        bgr[3 * p + 2] = ptc::quantize_value(rgb[3 * p + 0]);
     }
     return PT_OK;
 }

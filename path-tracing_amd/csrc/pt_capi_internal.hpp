@@ -1,11 +1,13 @@
 // Types shared by the translation units behind the C ABI (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters;
 // pt_frame.cpp: the multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp: the
-// temporal stage; pt_device_mem.hpp: the owners of everything they hold on a device).  Nothing here is part of the ABI.
+// temporal stage; pt_display_capi.cpp: the device-resident display path; pt_device_mem.hpp: the owners of everything they hold
+// on a device).  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/pt_hip.h"
 
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -152,5 +154,28 @@ int use_device(int device, const char *stage);
 int denoise_params_to_args(const pt_denoise_params *prm, pt::DenoiseArgs &a);
 // levels = 0 of pt_denoise_host: mean_rgb = sum / n (sum where n = 0), count_out = count (may be NULL), on the host.
 void unfiltered_mean(size_t n, const float *sum, const int32_t *count, float *mean_rgb, int32_t *count_out);
+
+// main.cpp:179-182 for one channel, and set_pixel's float -> unsigned char (bitmap_image.hpp:194-206): the ONE spelling of the
+// two steps, shared by pt_resolve, pt_tonemap, pt_quantize and the display path, whose threshold table is made from them.
+inline float tonemap_value(float mean, float gamma) { return std::pow(mean, gamma) * 255.0f; }
+inline uint8_t quantize_value(float value) { return static_cast<uint8_t>(static_cast<int>(value)); }
+
+// pt_temporal_push_host in two halves, for a chain whose frame already lies on the device (pt_display_present).
+// temporal_enqueue checks the parameters and enqueues features -> merge -> filter on `stream`, reading the frame's accumulators
+// from `frame` in place; *out names the planes the chain writes (they belong to `t`).  The history is only read: it advances
+// when the caller, once the chain has finished, calls temporal_commit -- or stays as it was if it never does.
+struct TemporalPlanes {
+    AccumPlanes merged;                  // sum_out, sum2_out, count_out
+    const float *history_frames = nullptr;
+    const float *mean = nullptr;         // with a filter (levels > 0) only
+    const int32_t *mean_count = nullptr;
+};
+int temporal_enqueue(pt_temporal *t, const AccumPlanes &frame, const pt_temporal_params *prm, const pt_denoise_params *dn,
+                     hipStream_t stream, TemporalPlanes *out);
+void temporal_commit(pt_temporal *t);
+
+// What a display needs of a frame: gathers if a band changed and waits, as pt_frame_read does; then the root device's copy of
+// the scene, its full-frame planes and the root band's stream.
+int frame_root_planes(pt_frame *f, pt_scene **scene, AccumPlanes *planes, hipStream_t *stream, int32_t *width, int32_t *height);
 
 }  // namespace ptc

@@ -1,0 +1,34 @@
+// Launch interface of the display kernel (pt_display.hip; include/pt_hip.h: pt_display_*): linear means to image bytes.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+namespace pt {
+
+// Thresholds the kernel searches: the host's table (pt_display_table), padded with +inf to this length.
+constexpr int kDisplayTableSize = 4096;
+
+// One entry of the list of pixels the kernel leaves to the host: 16 bytes.
+struct DisplayDeferred {
+    int32_t pixel;
+    float mean[3];   // r, g, b: what the host tone-maps and quantizes
+};
+
+struct DisplayArgs {
+    int n;                       // pixels of the flat plane
+    int divide;                  // 0: rgb holds the means; 1: rgb holds sums, the mean is rgb / float(count)
+    const float *rgb;            // 3 floats per pixel, 16-byte aligned
+    const int32_t *count;        // 16-byte aligned; a pixel with count == 0 gets three zero bytes
+    const float *table;          // kDisplayTableSize thresholds, non-decreasing, +inf behind the last one in use; 16-byte aligned
+    float last;                  // the last threshold in use: a mean at or above it is deferred
+    int n_bands;                 // doubt bands [band_lo[i], band_hi[i]): a mean inside one is deferred
+    const float *band_lo, *band_hi;
+    uint32_t *bgr;               // 3 bytes per pixel (B, G, R), written as dwords: room for (n + 3) / 4 * 12 bytes
+    DisplayDeferred *deferred;   // room for n entries, 16-byte aligned
+    uint32_t *n_deferred;        // zero before the launch
+};
+// One kernel: per channel the number of thresholds <= the mean, & 255; deferred pixels go to the list with zero bytes.
+hipError_t launch_display(const DisplayArgs &args, hipStream_t stream);
+
+}  // namespace pt

@@ -409,6 +409,19 @@ int frame_clear_impl(pt_frame *f) {
 
 }  // namespace
 
+int ptc::frame_root_planes(pt_frame *f, pt_scene **scene, AccumPlanes *planes, hipStream_t *stream, int32_t *width, int32_t *height) {
+    if (!f) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
+    int rc;
+    if (f->dirty && (rc = frame_gather_impl(f)) != PT_OK) return rc;
+    if ((rc = frame_wait_impl(f)) != PT_OK) return rc;
+    *scene = f->scenes[0];
+    *planes = f->root;
+    *stream = f->sessions[0]->stream.get();   // band 0 lies on the root device
+    *width = f->width;
+    *height = f->height;
+    return PT_OK;
+}
+
 extern "C" {
 
 int pt_rccl_available(int32_t *version) {

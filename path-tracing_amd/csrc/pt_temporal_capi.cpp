@@ -26,6 +26,7 @@ struct pt_temporal {
     int cur = 0;
     bool has_history = false;
     pt_camera camera{};           // of the history
+    pt_camera pending_camera{};   // of the chain enqueued last: the history's once that chain is committed
     float inverse[9] = {};        // rows of the inverse of [right up forward] of that camera
     ptc::DeviceBuffer d_denoise;  // allocated by the first push that filters: records A0, A1, B, C, mean, count
     void *dn_a0 = nullptr, *dn_a1 = nullptr, *dn_b = nullptr, *dn_c = nullptr;
@@ -92,30 +93,32 @@ int temporal_create_impl(pt_scene *scene, int32_t width, int32_t height, float e
     return PT_OK;
 }
 
-int temporal_push_impl(pt_temporal *t, const float *sum, const float *sum2, const int32_t *count, const pt_temporal_params *prm,
-                       const pt_denoise_params *dn, float *sum_out, float *sum2_out, int32_t *count_out, float *history_frames,
-                       float *mean_rgb, int32_t *mean_count, float *kernel_ms) {
-    if (!t || !sum || !sum2 || !count || !prm) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, accumulator buffer or params");
+int check_temporal_params(const pt_temporal_params *prm) {
     if (std::isnan(prm->max_frames) || prm->max_frames < 0.0f) return fail(PT_ERR_INVALID_ARGUMENT, "temporal: max_frames must not be negative (0 = the default)");
     if (!std::isfinite(prm->sigma_plane) || prm->sigma_plane < 0.0f)
         return fail(PT_ERR_INVALID_ARGUMENT, "temporal: sigma_plane must be finite and not negative (0 = the default)");
     if (!std::isfinite(prm->min_normal_dot) || prm->min_normal_dot < 0.0f || prm->min_normal_dot > 1.0f)
         return fail(PT_ERR_INVALID_ARGUMENT, "temporal: min_normal_dot must lie in 0 .. 1 (0 = the default)");
+    return PT_OK;
+}
+
+// The chain of a push on `stream`, from accumulators that lie on the device (`frame`: the handle's own upload planes, or a
+// session's): the view's first hits, the merge, the filter -- no host synchronisation in between.  The caller holds t->mutex and
+// has made the scene's device current.  ev0 / ev1 (NULL: none) are recorded around the kernels.  The history is only read.
+int enqueue_chain(pt_temporal *t, const ptc::AccumPlanes &frame, const pt_temporal_params *prm, const pt_denoise_params *dn,
+                  hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int *levels) {
+    int rc = check_temporal_params(prm);
+    if (rc != PT_OK) return rc;
     pt::DenoiseArgs da;
     da.levels = 0;
-    if (dn) {
-        const int rc = ptc::denoise_params_to_args(dn, da);
-        if (rc != PT_OK) return rc;
-    }
+    if (dn && (rc = ptc::denoise_params_to_args(dn, da)) != PT_OK) return rc;
+    *levels = da.levels;
     pt_scene *scene = t->scene;
     const size_t n = t->n;
-    if (kernel_ms) *kernel_ms = 0.0f;
-    PT_HIP_TRY(hipSetDevice(scene->device));
-    std::lock_guard<std::mutex> push_lock(t->mutex);
     if (da.levels > 0 && !t->d_denoise) {
         ptc::PlaneLayout l;
         const size_t o_a0 = l.add(16 * n), o_a1 = l.add(16 * n), o_b = l.add(16 * n), o_c = l.add(16 * n), o_mean = l.add(12 * n), o_cnt = l.add(4 * n);
-        const int rc = t->d_denoise.alloc(l, "pt_temporal_push_host");
+        rc = t->d_denoise.alloc(l, "pt_temporal_push_host");
         if (rc != PT_OK) return rc;
         const ptc::DeviceBuffer &d = t->d_denoise;
         t->dn_a0 = d.at<void>(o_a0); t->dn_a1 = d.at<void>(o_a1); t->dn_b = d.at<void>(o_b); t->dn_c = d.at<void>(o_c);
@@ -133,7 +136,7 @@ int temporal_push_impl(pt_temporal *t, const float *sum, const float *sum2, cons
     std::memcpy(a.cam, &cam, sizeof a.cam);
     std::memcpy(a.prev_origin, t->camera.origin, sizeof a.prev_origin);
     std::memcpy(a.prev_inverse, t->inverse, sizeof a.prev_inverse);
-    a.sum = t->in.sum; a.sum2 = t->in.sum2; a.count = t->in.count;
+    a.sum = frame.sum; a.sum2 = frame.sum2; a.count = frame.count;
     a.position = t->d_position; a.normal = t->d_normal; a.hit_index = t->d_hit;
     a.prev = t->rec[t->cur]; a.next = t->rec[t->cur ^ 1];
     a.sum_out = t->out.sum; a.sum2_out = t->out.sum2; a.count_out = t->out.count; a.history_frames = t->d_frames;
@@ -143,27 +146,50 @@ int temporal_push_impl(pt_temporal *t, const float *sum, const float *sum2, cons
     da.rec_a0 = t->dn_a0; da.rec_a1 = t->dn_a1; da.rec_b = t->dn_b; da.rec_c = t->dn_c;
     da.mean_rgb = t->d_mean; da.count_out = t->d_mean_count;
 
-    int rc = t->in.upload(sum, sum2, count);
+    std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
+    pt::RenderArgs ra;
+    if ((rc = ptc::scene_trace_args(scene, t->eps, ra)) != PT_OK) return rc;
+    if (ev0) PT_HIP_TRY(hipEventRecord(ev0, stream));
+    rc = ptc::enqueue_first_hits(scene, ra, cam, t->width, t->height, 0, t->height, t->d_origins, t->d_directions, t->d_hit, t->d_hit_t,
+                                 t->d_position, t->d_normal, t->d_albedo, stream);
     if (rc != PT_OK) return rc;
-    {   // the chain: the view's first hits, the merge, the filter -- one stream, no host synchronisation in between
-        std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
-        pt::RenderArgs ra;
-        if ((rc = ptc::scene_trace_args(scene, t->eps, ra)) != PT_OK) return rc;
-        PT_HIP_TRY(hipEventRecord(t->ev0.get(), nullptr));
-        rc = ptc::enqueue_first_hits(scene, ra, cam, t->width, t->height, 0, t->height, t->d_origins, t->d_directions, t->d_hit, t->d_hit_t,
-                                     t->d_position, t->d_normal, t->d_albedo, nullptr);
-        if (rc != PT_OK) return rc;
-        PT_HIP_TRY(pt::launch_temporal_merge(a, nullptr));
-        if (da.levels > 0) PT_HIP_TRY(pt::launch_denoise(da, nullptr));
-        PT_HIP_TRY(hipEventRecord(t->ev1.get(), nullptr));
-    }
+    PT_HIP_TRY(pt::launch_temporal_merge(a, stream));
+    if (da.levels > 0) PT_HIP_TRY(pt::launch_denoise(da, stream));
+    if (ev1) PT_HIP_TRY(hipEventRecord(ev1, stream));
+    t->pending_camera = cam;
+    return PT_OK;
+}
+
+// The chain has finished: the records it wrote are the history now.
+void commit_chain(pt_temporal *t) {
+    t->cur ^= 1;
+    t->has_history = true;
+    t->camera = t->pending_camera;
+    camera_inverse(t->camera, t->inverse);
+}
+
+int temporal_push_impl(pt_temporal *t, const float *sum, const float *sum2, const int32_t *count, const pt_temporal_params *prm,
+                       const pt_denoise_params *dn, float *sum_out, float *sum2_out, int32_t *count_out, float *history_frames,
+                       float *mean_rgb, int32_t *mean_count, float *kernel_ms) {
+    if (!t || !sum || !sum2 || !count || !prm) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, accumulator buffer or params");
+    int rc = check_temporal_params(prm);
+    if (rc != PT_OK) return rc;
+    pt::DenoiseArgs checked;
+    if (dn && (rc = ptc::denoise_params_to_args(dn, checked)) != PT_OK) return rc;
+    const size_t n = t->n;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    PT_HIP_TRY(hipSetDevice(t->scene->device));
+    std::lock_guard<std::mutex> push_lock(t->mutex);
+    if ((rc = t->in.upload(sum, sum2, count)) != PT_OK) return rc;
+    int levels = 0;
+    if ((rc = enqueue_chain(t, t->in, prm, dn, nullptr, t->ev0.get(), t->ev1.get(), &levels)) != PT_OK) return rc;
     // (an error return from here on leaves the history the previous one: rec[cur] was only read)
     PT_HIP_TRY(hipEventSynchronize(t->ev1.get()));
     float ms = 0.0f;
     PT_HIP_TRY(hipEventElapsedTime(&ms, t->ev0.get(), t->ev1.get()));
     if ((rc = t->out.download(sum_out, sum2_out, count_out)) != PT_OK) return rc;
     if (history_frames) PT_HIP_TRY(hipMemcpy(history_frames, t->d_frames, 4 * n, hipMemcpyDeviceToHost));
-    if (dn && da.levels > 0) {
+    if (dn && levels > 0) {
         if (mean_rgb) PT_HIP_TRY(hipMemcpy(mean_rgb, t->d_mean, 12 * n, hipMemcpyDeviceToHost));
         if (mean_count) PT_HIP_TRY(hipMemcpy(mean_count, t->d_mean_count, 4 * n, hipMemcpyDeviceToHost));
     } else if (dn && mean_rgb) {   // levels = 0: the unfiltered mean of the merged accumulators, on the host
@@ -172,15 +198,33 @@ int temporal_push_impl(pt_temporal *t, const float *sum, const float *sum2, cons
         if ((rc = t->out.download(s.data(), nullptr, c.data())) != PT_OK) return rc;
         ptc::unfiltered_mean(n, s.data(), c.data(), mean_rgb, mean_count);
     }
-    t->cur ^= 1;
-    t->has_history = true;
-    t->camera = cam;
-    camera_inverse(cam, t->inverse);
+    commit_chain(t);
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;
 }
 
 }  // namespace
+
+int ptc::temporal_enqueue(pt_temporal *t, const AccumPlanes &frame, const pt_temporal_params *prm, const pt_denoise_params *dn,
+                          hipStream_t stream, TemporalPlanes *out) {
+    if (!t || !prm || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or output");
+    if (frame.n != t->n) return fail(PT_ERR_INVALID_ARGUMENT, "temporal: the frame's planes do not hold width x height pixels");
+    PT_HIP_TRY(hipSetDevice(t->scene->device));
+    std::lock_guard<std::mutex> push_lock(t->mutex);
+    int levels = 0;
+    const int rc = enqueue_chain(t, frame, prm, dn, stream, nullptr, nullptr, &levels);
+    if (rc != PT_OK) return rc;
+    out->merged = t->out;
+    out->history_frames = t->d_frames;
+    out->mean = levels > 0 ? t->d_mean : nullptr;
+    out->mean_count = levels > 0 ? t->d_mean_count : nullptr;
+    return PT_OK;
+}
+
+void ptc::temporal_commit(pt_temporal *t) {
+    std::lock_guard<std::mutex> push_lock(t->mutex);
+    commit_chain(t);
+}
 
 extern "C" {
 

@@ -45,6 +45,12 @@
 // in frames (32 is the usual choice); with -DENOISE the filter then runs on the merged frame, in the same chain on the device.
 // A sequence writes no previews and prints no -TIMING line, and -TL with -FRAMES > 1 is refused.  Without -FRAMES and -TEMPORAL
 // nothing changes.
+// The device-resident display path (pt_display_*, not in the reference): -DEVICE_RESOLVE 1 (default 0) makes the images' bytes on
+// the first device of the frame, where the accumulators lie -- temporal merge, denoiser, tone map and quantization in one chain,
+// 3 bytes per pixel to the host -- instead of reading 28 bytes per pixel back and tone-mapping on the host.  The files are
+// byte-identical with and without it.  In a sequence only the last frame is also read back, for the dispersion figures in the
+// output name.  -GAUSS / -MEDIAN act on the tone-mapped float image and stay on the host path: with either of them, or with a
+// -GAMMA that is not a finite positive number, the flag is ignored with a message on stderr.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -82,6 +88,7 @@ struct Options {   // defaults: config.h:16-29
     int frames = 1;                // -FRAMES
     float temporal = 0.0f;         // -TEMPORAL: max_frames of the history, 0 = no temporal stage
     std::string eye_end, lookat_end;   // -EYE_END / -LOOKAT_END as given ("" = the start value)
+    int device_resolve = 0;        // -DEVICE_RESOLVE: 1 = the images' bytes are made on the device (pt_display_*)
 };
 
 long long now_ms() {
@@ -134,6 +141,7 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-TEMPORAL") o.temporal = static_cast<float>(std::atof(v));
         if (f == "-EYE_END") o.eye_end = v;
         if (f == "-LOOKAT_END") o.lookat_end = v;
+        if (f == "-DEVICE_RESOLVE") o.device_resolve = std::atoi(v);
     }
 }
 
@@ -232,6 +240,15 @@ int main(int argc, char **argv) {
     if (o.frames < 1 || !(o.temporal >= 0.0f)) {
         std::cerr << "pt_render: -FRAMES takes a count >= 1 and -TEMPORAL a history length >= 0" << std::endl;
         return 2;
+    }
+    bool device_resolve = o.device_resolve != 0;
+    if (device_resolve && (o.gauss || o.median)) {
+        std::cerr << "pt_render: -DEVICE_RESOLVE is ignored with -GAUSS / -MEDIAN: they filter the tone-mapped float image, on the host path" << std::endl;
+        device_resolve = false;
+    }
+    if (device_resolve && !(std::isfinite(o.gamma_correction) && o.gamma_correction > 0.0f)) {
+        std::cerr << "pt_render: -DEVICE_RESOLVE is ignored: it needs a finite -GAMMA > 0" << std::endl;
+        device_resolve = false;
     }
     const unsigned seed = o.seed < 0 ? static_cast<unsigned>(std::time(nullptr)) : static_cast<unsigned>(o.seed);   // config.h:101-104
 
@@ -377,6 +394,16 @@ int main(int argc, char **argv) {
         return rc;
     };
 
+    // -DEVICE_RESOLVE: the display of the frame, and what a present is asked for
+    pt_display *display = nullptr;
+    pt_display_params show;
+    std::memset(&show, 0, sizeof show);
+    show.gamma = o.gamma_correction;
+    show.temporal = o.temporal > 0.0f ? 1 : 0;
+    show.temporal_params.max_frames = o.temporal;
+    show.denoise.levels = o.denoise; show.denoise.sigma_luminance = o.dn_sigma_l; show.denoise.sigma_plane = o.dn_sigma_p;
+    if (device_resolve && pt_display_create_frame(frame, o.eps, &display) != PT_OK) return die("pt_render");
+
     if (sequence) {
         // n frames: frame i renders its own pass range from its own camera, is merged with the history (-TEMPORAL), denoised
         // (-DENOISE), tone-mapped, filtered, quantized and written; the last one also takes the usual outputs
@@ -389,15 +416,15 @@ int main(int argc, char **argv) {
         const bool own_camera = o.camera || !o.eye_end.empty() || !o.lookat_end.empty();
         pt_scene *view = nullptr;   // the scene on the first device: the history's and the feature buffers' handle
         pt_temporal *history = nullptr;
-        if ((o.temporal > 0.0f || o.denoise > 0) && pt_scene_clone_to_device(scene, devices[0], &view) != PT_OK) return die("pt_render");
-        if (o.temporal > 0.0f && pt_temporal_create(view, o.width, o.height, o.eps, &history) != PT_OK) return die("pt_render");
+        if (!display && (o.temporal > 0.0f || o.denoise > 0) && pt_scene_clone_to_device(scene, devices[0], &view) != PT_OK) return die("pt_render");
+        if (!display && o.temporal > 0.0f && pt_temporal_create(view, o.width, o.height, o.eps, &history) != PT_OK) return die("pt_render");
         if (!ensure_buffers()) return die("pt_render");
         std::vector<float> msum, msum2, mean, rgb, pos, nrm, alb;
         std::vector<int32_t> mcount, mean_count, hit;
         if (history) { msum.resize(3 * px); msum2.resize(3 * px); mcount.resize(px); }
-        if (o.denoise > 0) { mean.resize(3 * px); mean_count.resize(px); }
-        if (o.denoise > 0 && !history) { pos.resize(3 * px); nrm.resize(3 * px); alb.resize(3 * px); hit.resize(px); }
-        if (o.denoise > 0 || o.gauss || o.median) rgb.resize(3 * px);
+        if (o.denoise > 0 && !display) { mean.resize(3 * px); mean_count.resize(px); }
+        if (o.denoise > 0 && !history && !display) { pos.resize(3 * px); nrm.resize(3 * px); alb.resize(3 * px); hit.resize(px); }
+        if ((o.denoise > 0 && !display) || o.gauss || o.median) rgb.resize(3 * px);
         pt_temporal_params tp;
         std::memset(&tp, 0, sizeof tp);
         tp.max_frames = o.temporal;
@@ -417,32 +444,42 @@ int main(int argc, char **argv) {
             }
             rp.pass_begin = i * o.rays_per_pixel;
             rp.pass_count = o.rays_per_pixel;
-            if (pt_frame_clear(frame) != PT_OK || pt_frame_render(frame, &rp, nullptr) != PT_OK || read_back() != PT_OK) return die("pt_render");
-            pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);   // the statistics of the frame as rendered
-            const float *fs = sum, *fs2 = sum2;
-            const int32_t *fc = count;
-            if (history) {
-                if (pt_temporal_push_host(history, sum, sum2, count, &tp, o.denoise > 0 ? &dp : nullptr, msum.data(), msum2.data(), mcount.data(),
-                                          nullptr, o.denoise > 0 ? mean.data() : nullptr, o.denoise > 0 ? mean_count.data() : nullptr, nullptr) != PT_OK)
-                    return die("pt_render");
-                fs = msum.data(); fs2 = msum2.data(); fc = mcount.data();
-            } else if (o.denoise > 0) {
-                if (pt_render_features_host(view, &rp, hit.data(), nullptr, pos.data(), nrm.data(), alb.data()) != PT_OK ||
-                    pt_denoise_host(devices[0], o.width, o.height, fs, fs2, fc, pos.data(), nrm.data(), alb.data(), hit.data(), &dp, mean.data(),
-                                    mean_count.data(), nullptr) != PT_OK)
-                    return die("pt_render");
-            }
-            if (o.denoise > 0) {
-                pt_tonemap(o.width, o.height, mean.data(), mean_count.data(), o.gamma_correction, rgb.data());
-                if ((o.gauss || o.median) && pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
-                pt_quantize(o.width, o.height, rgb.data(), mean_count.data(), bgr.data());
-            } else if (o.gauss || o.median) {
-                float unused[3];
-                pt_resolve_float(o.width, o.height, fs, fs2, fc, o.gamma_correction, rgb.data(), unused);
-                if (pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
-                pt_quantize(o.width, o.height, rgb.data(), fc, bgr.data());
-            } else if (history) {
-                pt_resolve(o.width, o.height, fs, fs2, fc, o.gamma_correction, bgr.data(), nullptr);
+            if (pt_frame_clear(frame) != PT_OK || pt_frame_render(frame, &rp, nullptr) != PT_OK) return die("pt_render");
+            if (display) {
+                // the bytes come from the device; only the last frame is also read back, for the statistics in the output's name
+                if (i == o.frames - 1) {
+                    if (read_back() != PT_OK) return die("pt_render");
+                    pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
+                }
+                if (pt_display_present(display, &show, bgr.data(), nullptr) != PT_OK) return die("pt_render");
+            } else {
+                if (read_back() != PT_OK) return die("pt_render");
+                pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);   // the statistics of the frame as rendered
+                const float *fs = sum, *fs2 = sum2;
+                const int32_t *fc = count;
+                if (history) {
+                    if (pt_temporal_push_host(history, sum, sum2, count, &tp, o.denoise > 0 ? &dp : nullptr, msum.data(), msum2.data(), mcount.data(),
+                                              nullptr, o.denoise > 0 ? mean.data() : nullptr, o.denoise > 0 ? mean_count.data() : nullptr, nullptr) != PT_OK)
+                        return die("pt_render");
+                    fs = msum.data(); fs2 = msum2.data(); fc = mcount.data();
+                } else if (o.denoise > 0) {
+                    if (pt_render_features_host(view, &rp, hit.data(), nullptr, pos.data(), nrm.data(), alb.data()) != PT_OK ||
+                        pt_denoise_host(devices[0], o.width, o.height, fs, fs2, fc, pos.data(), nrm.data(), alb.data(), hit.data(), &dp, mean.data(),
+                                        mean_count.data(), nullptr) != PT_OK)
+                        return die("pt_render");
+                }
+                if (o.denoise > 0) {
+                    pt_tonemap(o.width, o.height, mean.data(), mean_count.data(), o.gamma_correction, rgb.data());
+                    if ((o.gauss || o.median) && pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+                    pt_quantize(o.width, o.height, rgb.data(), mean_count.data(), bgr.data());
+                } else if (o.gauss || o.median) {
+                    float unused[3];
+                    pt_resolve_float(o.width, o.height, fs, fs2, fc, o.gamma_correction, rgb.data(), unused);
+                    if (pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+                    pt_quantize(o.width, o.height, rgb.data(), fc, bgr.data());
+                } else if (history) {
+                    pt_resolve(o.width, o.height, fs, fs2, fc, o.gamma_correction, bgr.data(), nullptr);
+                }
             }
             if (o.frames > 1) {
                 char frame_name[32];
@@ -469,6 +506,7 @@ int main(int argc, char **argv) {
         std::cout << name << std::endl;
         pt_temporal_destroy(history);
         if (view) pt_scene_destroy(view);
+        pt_display_destroy(display);
         pt_frame_destroy(frame);
         pt_scene_destroy(scene);
         return rc;
@@ -531,7 +569,17 @@ int main(int argc, char **argv) {
 
     double features_s = 0, denoise_s = 0;
     float denoise_kernel_ms = 0;
-    if (o.denoise > 0) {
+    if (display) {
+        // the statistics of the frame as rendered, on the host; the image's bytes from the device (features, denoiser, tone map)
+        pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
+        const clk::time_point f1 = clk::now();
+        pt_display_info shown;
+        if (pt_display_present(display, &show, bgr.data(), &shown) != PT_OK) return die("pt_render");
+        if (o.denoise > 0) {
+            denoise_s = secs(f1, clk::now());
+            denoise_kernel_ms = shown.kernel_ms;
+        }
+    } else if (o.denoise > 0) {
         // the statistics of the frame as rendered; then the first hits of the pinhole view on the frame's first device, the
         // denoiser on the linear mean, the tone map, the reference's filters and set_pixel
         std::vector<float> rgb(3 * px), mean(3 * px), pos(3 * px), nrm(3 * px), alb(3 * px);
@@ -600,6 +648,7 @@ int main(int argc, char **argv) {
         std::cerr.flush();
         std::_Exit(rc);
     }
+    pt_display_destroy(display);
     pt_frame_destroy(frame);
     pt_scene_destroy(scene);
     return rc;
