@@ -399,6 +399,59 @@ int pt_denoise_host(int device, int32_t width, int32_t height, const float *sum,
                     const float *position, const float *normal, const float *albedo, const int32_t *hit_index,
                     const pt_denoise_params *params, float *mean_rgb, int32_t *count_out, float *kernel_ms);
 
+/* ---- reduced-resolution rendering: feature-guided upsampling ----------------------------------------- */
+
+/* Radiance is what costs: hundreds of path segments per pixel against ONE primary ray for the first-hit features.  So a frame may
+ * be traced at (W / s) x (H / s) and shown at W x H: the low-resolution LINEAR mean (what pt_denoise_host returns, or sum / n) is
+ * reconstructed at full resolution by a joint bilateral upsample that follows the full-resolution features -- edges and material
+ * boundaries stay at output resolution.  The chain of such an image is
+ *   pt_denoise_host (or the plain mean) at w x h -> pt_render_features_host at W x H -> pt_upsample_host -> pt_tonemap ->
+ *   pt_post_filter_host (optional) -> pt_quantize,  the last three at W x H with count_out.
+ * width x height is the OUTPUT size W x H; both must be multiples of s = scale, and w = W / s, h = H / s.  mean_lo (3 floats per
+ * pixel) and count_lo are HOST buffers of the w x h image, the feature buffers, mean_rgb and count_out (may be NULL) HOST buffers of
+ * the W x H image; the kernels run on HIP device `device`.  kernel_ms (may be NULL) = HIP-event time of the kernel chain.
+ *
+ * Parameters; a zeroed struct holds the defaults, except that `scale` must be given:
+ *   scale               s: 2, 3 or 4
+ *   sigma_plane         s_p, in scene units; 0 = 0.1, as the denoiser's    (negative or non-finite: invalid)
+ *   normal_power_log2   k; 0 = 7; at most 16    (negative: invalid)
+ *   demodulate_albedo   0 or positive = interpolate radiance divided by the albedo; negative = radiance itself
+ *
+ * The arithmetic, exactly, as for the denoiser: every operation below is ONE correctly rounded float operation in the order
+ * written (+ - * /, floor, comparisons, int -> float conversions; nothing fused, no approximations).  lum, pos, HIT / MISS, CLASS and
+ * the feature weight f(p, .) = (w_n) * w_p are exactly what pt_denoise_host defines, with s_p = sigma_plane, k = normal_power_log2.
+ * Integer divisions truncate.
+ * 1. Guide of a low pixel.  The guide of the low pixel Q = (X, Y) is the full-resolution pixel g(Q) = (s X + s / 2, s Y + s / 2); it
+ *    always lies inside the image.  Q has DATA if count_lo[Q] > 0.  Per channel a_Q = max(albedo, 0.01) of g(Q) if demodulating and
+ *    g(Q) is a hit (albedo > 0.01 ? albedo : 0.01), else 1;  c_Q = m_Q / a_Q  (m = mean_lo).
+ * 2. Position in the low grid, for the output pixel p = (x, y); a_p is defined likewise from p's own albedo and class.  A low
+ *    pixel's footprint is the s x s output pixels it was jittered over, so  fx = float(2 x + 1 - s) / float(2 s),  fy likewise;
+ *    X0 = floor(fx), tx = fx - X0, likewise Y0, ty (X0, Y0 may be -1).  The four taps Q = (X0 + i, Y0 + j), i, j in {0, 1}, are
+ *    visited j outer, i inner; the tent weight of a tap is  t = (i ? tx : 1 - tx) * (j ? ty : 1 - ty).
+ * 3. Which taps are used?  A tap is USED if it lies inside the low image, has data and g(Q) is of p's class.  Its weight is
+ *    o = t for a miss p and o = (t * w_n) * w_p for a hit p: f(p, g(Q)) with p's N, P and g(Q)'s N, P.
+ * 4. Combination.  The base b is the c of the used tap with the largest o (the first such tap in visiting order: a later tap
+ *    replaces it only if its o is greater).  Over the used taps in visiting order, from 0:  Wt += o,  S += o * (c_Q - b).  If
+ *    Wt > 1e-4:  c = b + S / Wt,  mean_rgb = pos(a_p * c),  count_out = 1.
+ * 5. Fallback, if Wt <= 1e-4 (no tap usable, or only across an edge): R = (x / s, y / s), the low pixel that contains p.  If R has
+ *    data: mean_rgb = m_R as it is, count_out = 1; else mean_rgb = 0, count_out = 0.
+ * Taking the heaviest tap as the base makes two properties exact: without demodulation a constant low image comes back as that
+ * constant bit for bit (every difference c_Q - b is 0), and where every positively weighted tap of a pixel carries one value the
+ * pixel gets exactly that value (taps across a fold, whose guide normals are perpendicular to p's, weigh exactly 0). */
+typedef struct pt_upsample_params {
+    int32_t scale;
+    float sigma_plane;
+    int32_t normal_power_log2;
+    int32_t demodulate_albedo;
+} pt_upsample_params;
+#define PT_UPSAMPLE_MAX_SCALE 4
+/* PT_ERR_INVALID_ARGUMENT: a NULL buffer (mean_lo, count_lo, the feature buffers, params, mean_rgb), an empty image, width or
+ * height not a multiple of scale, a parameter outside what is stated above -- all checked BEFORE the device is looked at.
+ * PT_ERR_NO_DEVICE: otherwise, if `device` is not a usable HIP device (there is no CPU fallback). */
+int pt_upsample_host(int device, int32_t width, int32_t height, const float *mean_lo, const int32_t *count_lo,
+                     const float *position, const float *normal, const float *albedo, const int32_t *hit_index,
+                     const pt_upsample_params *params, float *mean_rgb, int32_t *count_out, float *kernel_ms);
+
 /* ---- temporal accumulation (moving camera) ----------------------------------------------------------- */
 
 /* The temporal half the denoiser lacks: the frames of ONE view sequence are accumulated by reprojection.  The stage is
@@ -519,6 +572,17 @@ typedef struct pt_display_info {
 int pt_display_create(pt_session *session, float eps, pt_display **out);
 int pt_display_create_frame(pt_frame *frame, float eps, pt_display **out);
 int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info /* may be NULL */);
+/* A present at s times the session's / frame's size (u->scale = s): the accumulators stay w x h = width x height of the display,
+ * the image is W x H = s w x s h, bgr holds H * W * 3 bytes.  One chain on the device: the low-resolution features (if a stage needs
+ * them), the temporal merge at w x h on the display's own history (the same history pt_display_present uses), the denoiser at
+ * w x h, the features at W x H from the same camera, the upsample, then the tone map and quantization at W x H with the same kernel
+ * and deferred list, and W * H * 3 bytes to the host.  The bytes are DEFINED by the host chain and equal it bit for bit:
+ *   the w x h mean and count of the row of the table above (levels = 0: sum / n and count, of the accumulators or of the merged
+ *   ones; levels > 0: mean_rgb, count_out of pt_denoise_host or mean_rgb, mean_count of pt_temporal_push_host)
+ *   -> pt_render_features_host at W x H -> pt_upsample_host with *u -> pt_tonemap -> pt_quantize, with the upsample's count_out.
+ * *u is checked as pt_upsample_host checks it, before anything is enqueued: a failed call leaves the history as it was. */
+int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, uint8_t *bgr,
+                              pt_display_info *info /* may be NULL */);
 int pt_display_reset(pt_display *d);     /* forget the history: the next present with a temporal stage is a first frame */
 void pt_display_destroy(pt_display *d);
 

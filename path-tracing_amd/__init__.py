@@ -43,7 +43,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_render_features_host", "pt_denoise_host", "pt_tonemap",
                "pt_temporal_create", "pt_temporal_push_host", "pt_temporal_reset", "pt_temporal_destroy",
                "pt_display_create", "pt_display_create_frame", "pt_display_present", "pt_display_reset", "pt_display_destroy",
-               "pt_display_bytes_host", "pt_display_table"]
+               "pt_display_bytes_host", "pt_display_table",
+               "pt_upsample_host", "pt_display_present_scaled"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -116,6 +117,15 @@ class DenoiseParams(C.Structure):
 
 
 DENOISE_MAX_LEVELS = 8
+
+
+class UpsampleParams(C.Structure):
+    """pt_upsample_params: scale 2, 3 or 4; the other fields zeroed hold the defaults (sigma_plane 0.1, normal_power_log2 7,
+    demodulation on)."""
+    _fields_ = [("scale", C.c_int32), ("sigma_plane", C.c_float), ("normal_power_log2", C.c_int32), ("demodulate_albedo", C.c_int32)]
+
+
+UPSAMPLE_MAX_SCALE = 4
 
 
 class TemporalParams(C.Structure):
@@ -271,6 +281,8 @@ def load_library(path):
     L.pt_display_create.argtypes = [vp, C.c_float, C.POINTER(vp)]
     L.pt_display_create_frame.argtypes = [vp, C.c_float, C.POINTER(vp)]
     L.pt_display_present.argtypes = [vp, C.POINTER(DisplayParams), bp, C.POINTER(DisplayInfo)]
+    L.pt_display_present_scaled.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), bp, C.POINTER(DisplayInfo)]
+    L.pt_upsample_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, fp, fp, fp, ip, C.POINTER(UpsampleParams), fp, ip, fp]
     L.pt_display_reset.argtypes = [vp]
     L.pt_display_destroy.argtypes = [vp]
     L.pt_display_destroy.restype = None
@@ -579,6 +591,14 @@ class Temporal:
             pass
 
 
+def _upsample_params(upsample):
+    """An UpsampleParams, or a dict of pt.upsample's keyword parameters (scale, ...) -> an UpsampleParams."""
+    if isinstance(upsample, dict):
+        return UpsampleParams(upsample.get("scale", 2), upsample.get("sigma_plane", 0.0), upsample.get("normal_power_log2", 0),
+                              upsample.get("demodulate_albedo", 0))
+    return upsample
+
+
 def _denoise_params(denoise):
     """None, a DenoiseParams, or a dict of pt.denoise's keyword parameters -> a DenoiseParams (None: levels = 0)."""
     if denoise is None:
@@ -601,10 +621,12 @@ class Display:
         create = self._L.pt_display_create_frame if isinstance(session_or_frame, Frame) else self._L.pt_display_create
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
-    def present(self, gamma=None, temporal=None, denoise=None):
+    def present(self, gamma=None, temporal=None, denoise=None, upsample=None):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
-        parameters.  Returns (bgr uint8 [H, W, 3], info dict)."""
+        parameters.  Returns (bgr uint8 [H, W, 3], info dict).
+        `upsample`: None, an UpsampleParams, or a dict of pt.upsample's parameters ({"scale": 2}) -- pt_display_present_scaled: the
+        image is then scale times the session's size, bgr uint8 [scale * H, scale * W, 3]."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -612,8 +634,15 @@ class Display:
         on = temporal is not None and temporal is not False
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
-        bgr = np.zeros((self.height, self.width, 3), np.uint8)
         info = DisplayInfo()
+        if upsample is not None:
+            up = _upsample_params(upsample)
+            k = up.scale if 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1       # (a scale the library refuses: it writes nothing)
+            bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8)
+            _check(self._L.pt_display_present_scaled(self._h, C.byref(prm), C.byref(up), bgr.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                     C.byref(info)), self._L)
+            return bgr, info.as_dict()
+        bgr = np.zeros((self.height, self.width, 3), np.uint8)
         _check(self._L.pt_display_present(self._h, C.byref(prm), bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)), self._L)
         return bgr, info.as_dict()
 
@@ -801,6 +830,30 @@ def denoise(width, height, s, s2, c, features=None, *, levels=5, sigma_luminance
     mean, cout, ms = np.zeros((n, 3), np.float32), np.zeros(n, np.int32), C.c_float()
     _check(lib().pt_denoise_host(device, width, height, _fp(s), _fp(s2), _ip(c), ptr(f["position"], _fp), ptr(f["normal"], _fp),
                                  ptr(f["albedo"], _fp), ptr(f["hit_index"], _ip), C.byref(prm), _fp(mean), _ip(cout), C.byref(ms)))
+    return (mean, cout, ms.value) if want_ms else (mean, cout)
+
+
+def upsample(device, width, height, mean_lo, count_lo, features, scale=2, *, sigma_plane=0.0, normal_power_log2=0, demodulate_albedo=0,
+             want_ms=False):
+    """pt_upsample_host: a frame traced at (width / scale) x (height / scale) reconstructed at width x height, guided by the
+    full-resolution `features` (what Scene.render_features returns for width x height).  mean_lo [h * w, 3], count_lo [h * w]: what
+    pt.denoise returns for the low frame.  Returns (mean_rgb float32 [H * W, 3], count_out int32 [H * W]) -- the count to tone-map and
+    quantize with --, and the kernel chain's milliseconds as a third value if want_ms."""
+    n = width * height
+    n_lo = n // (scale * scale) if scale > 0 else 0
+    m = np.ascontiguousarray(mean_lo, np.float32)
+    c = np.ascontiguousarray(count_lo, np.int32)
+    if scale > 0 and width % scale == 0 and height % scale == 0 and (m.size != 3 * n_lo or c.size != n_lo):
+        raise ValueError("upsample: mean_lo / count_lo do not hold (width / scale) x (height / scale) pixels")
+    f = {}
+    for k, dt, per in (("position", np.float32, 3), ("normal", np.float32, 3), ("albedo", np.float32, 3), ("hit_index", np.int32, 1)):
+        f[k] = np.ascontiguousarray(features[k], dt)
+        if f[k].size != per * n:
+            raise ValueError(f"upsample: features[{k!r}] does not hold width x height pixels")
+    prm = UpsampleParams(scale, sigma_plane, normal_power_log2, demodulate_albedo)
+    mean, cout, ms = np.zeros((max(n, 0), 3), np.float32), np.zeros(max(n, 0), np.int32), C.c_float()
+    _check(lib().pt_upsample_host(device, width, height, _fp(m), _ip(c), _fp(f["position"]), _fp(f["normal"]), _fp(f["albedo"]),
+                                  _ip(f["hit_index"]), C.byref(prm), _fp(mean), _ip(cout), C.byref(ms)))
     return (mean, cout, ms.value) if want_ms else (mean, cout)
 
 

@@ -1,6 +1,6 @@
 // Types shared by the translation units behind the C ABI (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters;
 // pt_frame.cpp: the multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp: the
-// temporal stage; pt_display_capi.cpp: the device-resident display path; pt_device_mem.hpp: the owners of everything they hold
+// temporal stage; pt_display_capi.cpp: the device-resident display path; pt_upsample_capi.cpp: the upsampler; pt_device_mem.hpp: the owners of everything they hold
 // on a device).  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/pt_hip.h"
@@ -18,6 +18,7 @@
 #include "pt_device_mem.hpp"
 #include "pt_kernels.hpp"
 #include "pt_scene.hpp"
+#include "pt_upsample.hpp"
 
 // The host side of a scene: parsed model, its device-independent tables and the culling hierarchies built so far (one per
 // eps).  Immutable once the scene is finished and shared by every per-device copy of it (pt_scene_clone_to_device, pt_frame):
@@ -154,6 +155,9 @@ int use_device(int device, const char *stage);
 int denoise_params_to_args(const pt_denoise_params *prm, pt::DenoiseArgs &a);
 // levels = 0 of pt_denoise_host: mean_rgb = sum / n (sum where n = 0), count_out = count (may be NULL), on the host.
 void unfiltered_mean(size_t n, const float *sum, const int32_t *count, float *mean_rgb, int32_t *count_out);
+// pt_upsample_params and the OUTPUT size as pt_upsample_host checks them (no device is touched), into the parameter fields of the
+// launch arguments (zero = the default).
+int upsample_params_to_args(const pt_upsample_params *prm, int32_t width, int32_t height, pt::UpsampleArgs &a);
 
 // main.cpp:179-182 for one channel, and set_pixel's float -> unsigned char (bitmap_image.hpp:194-206): the ONE spelling of the
 // two steps, shared by pt_resolve, pt_tonemap, pt_quantize and the display path, whose threshold table is made from them.

@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "pt_denoise.hpp"
+#include "pt_feature_weight.hpp"
 
 #pragma clang fp contract(off)
 
@@ -107,20 +108,6 @@ __global__ __launch_bounds__(256) void denoise_prepare_kernel(DenoiseArgs a, int
     static_cast<float4 *>(a.rec_b)[p] =
         make_float4(a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2], a.hit_index[p] >= 0 ? 1.0f : 0.0f);
     static_cast<float4 *>(a.rec_c)[p] = make_float4(a.position[3 * p], a.position[3 * p + 1], a.position[3 * p + 2], 0.0f);
-}
-
-// w * w_n * w_p of a tap q for a centre p on a triangle: w_n = max(0, n_p . n_q)^(2^k) by k squarings,
-// w_p = 1 / (1 + (|n_p . (P_q - P_p)| / sigma_plane)^2)
-__device__ __forceinline__ float feature_weight(float w, const float4 &bp, const float4 &cp, const float4 &bq, const float4 &cq,
-                                                float sigma_plane, int k) {
-    const float dn = (bp.x * bq.x + bp.y * bq.y) + bp.z * bq.z;
-    float wn = dn > 0.0f ? dn : 0.0f;
-    for (int i = 0; i < k; ++i) wn = wn * wn;
-    const float ex = cq.x - cp.x, ey = cq.y - cp.y, ez = cq.z - cp.z;
-    const float dist = __builtin_fabsf((bp.x * ex + bp.y * ey) + bp.z * ez);
-    const float up = dist / sigma_plane;
-    const float wp = 1.0f / (1.0f + up * up);
-    return (w * wn) * wp;
 }
 
 // The variance a pixel with samples enters the filter with: the 3 x 3 binomial mean of the sample variance, and for pixels with

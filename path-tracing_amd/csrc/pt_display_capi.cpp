@@ -1,5 +1,5 @@
 // Host side of the device-resident display path (include/pt_hip.h: pt_display_*): the threshold table made from the host's own
-// tone map, the chain features -> temporal merge -> a-trous -> bytes on the stream of the session it displays, and the few
+// tone map, the chain features -> temporal merge -> a-trous -> (upsample ->) bytes on the stream of the session it displays, and the few
 // pixels the kernel leaves to the host.
 #include "pt_capi_internal.hpp"
 
@@ -153,6 +153,15 @@ struct pt_display {
     float *d_origins = nullptr, *d_directions = nullptr, *d_position = nullptr, *d_normal = nullptr, *d_albedo = nullptr, *d_hit_t = nullptr, *d_mean = nullptr;
     int32_t *d_hit = nullptr, *d_mean_count = nullptr;
     void *dn_a0 = nullptr, *dn_a1 = nullptr, *dn_b = nullptr, *dn_c = nullptr;
+    // a scaled present: the output image's features, mean and count, the low mean and the upsampler's records, and the output's
+    // bytes and deferred list -- allocated by the first scaled present, again when the scale changes
+    int32_t up_scale = 0;
+    ptc::DeviceBuffer d_up;
+    DisplayDevice dev_up;
+    float *up_origins = nullptr, *up_directions = nullptr, *up_position = nullptr, *up_normal = nullptr, *up_albedo = nullptr, *up_hit_t = nullptr,
+          *up_mean = nullptr, *up_mean_lo = nullptr;
+    int32_t *up_hit = nullptr, *up_count = nullptr;
+    void *up_a = nullptr, *up_b = nullptr, *up_c = nullptr;
     ptc::DeviceEvent ev0, ev1;
     ~pt_display() {
         (void)hipSetDevice(scene->device);
@@ -177,10 +186,38 @@ int display_create_impl(pt_scene *scene, int32_t width, int32_t height, float ep
     return PT_OK;
 }
 
-int display_present_impl(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info) {
-    if (!d || !p || !bgr) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or image");
+// What a scaled present needs on the device for scale s (the caller holds d->mutex and has made the device current).
+int ensure_scaled(pt_display *d, int32_t s) {
+    if (d->up_scale == s) return PT_OK;
+    d->up_scale = 0;
+    const size_t n_lo = d->n, n = n_lo * static_cast<size_t>(s) * s;
+    ptc::PlaneLayout l;
+    const size_t o_org = l.add(12 * n), o_dir = l.add(12 * n), o_pos = l.add(12 * n), o_nrm = l.add(12 * n), o_alb = l.add(12 * n), o_mean = l.add(12 * n);
+    const size_t o_hit = l.add(4 * n), o_hit_t = l.add(4 * n), o_cnt = l.add(4 * n);
+    const size_t o_mlo = l.add(12 * n_lo), o_a = l.add(16 * n_lo), o_b = l.add(16 * n_lo), o_c = l.add(16 * n_lo);
+    int rc;
+    if ((rc = d->d_up.alloc(l, "pt_display_present_scaled")) != PT_OK || (rc = d->dev_up.alloc(n, "pt_display_present_scaled")) != PT_OK) return rc;
+    d->dev_up.host.reset();   // (a new allocation holds no table yet)
+    const ptc::DeviceBuffer &b = d->d_up;
+    d->up_origins = b.at<float>(o_org); d->up_directions = b.at<float>(o_dir); d->up_position = b.at<float>(o_pos);
+    d->up_normal = b.at<float>(o_nrm); d->up_albedo = b.at<float>(o_alb); d->up_mean = b.at<float>(o_mean);
+    d->up_hit = b.at<int32_t>(o_hit); d->up_hit_t = b.at<float>(o_hit_t); d->up_count = b.at<int32_t>(o_cnt);
+    d->up_mean_lo = b.at<float>(o_mlo);
+    d->up_a = b.at<void>(o_a); d->up_b = b.at<void>(o_b); d->up_c = b.at<void>(o_c);
+    d->up_scale = s;
+    return PT_OK;
+}
+
+// `u` = NULL: pt_display_present.  Else the scaled present: the same chain at the display's size, then the upsample to s times it.
+int display_present_impl(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, bool scaled, uint8_t *bgr, pt_display_info *info) {
+    if (!d || !p || !bgr || (scaled && !u)) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or image");
     int rc = check_gamma(p->gamma);
     if (rc != PT_OK) return rc;
+    pt::UpsampleArgs ua;
+    if (scaled) {
+        if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
+        if ((rc = ptc::upsample_params_to_args(u, d->width * u->scale, d->height * u->scale, ua)) != PT_OK) return rc;
+    }
     pt::DenoiseArgs da;
     if ((rc = ptc::denoise_params_to_args(&p->denoise, da)) != PT_OK) return rc;
     const bool temporal = p->temporal != 0, filter = da.levels > 0;
@@ -200,7 +237,9 @@ int display_present_impl(pt_display *d, const pt_display_params *p, uint8_t *bgr
     }
     pt_scene *scene = d->scene;
     PT_HIP_TRY(hipSetDevice(scene->device));
-    if ((rc = d->dev.use_table(table, "pt_display_present")) != PT_OK) return rc;
+    DisplayDevice &dev = scaled ? d->dev_up : d->dev;
+    if (scaled && (rc = ensure_scaled(d, ua.scale)) != PT_OK) return rc;
+    if ((rc = dev.use_table(table, "pt_display_present")) != PT_OK) return rc;
     if (temporal && !d->history && (rc = pt_temporal_create(scene, d->width, d->height, d->eps, &d->history)) != PT_OK) return rc;
     if (filter && !temporal && !d->d_filter) {
         ptc::PlaneLayout l;
@@ -243,7 +282,30 @@ int display_present_impl(pt_display *d, const pt_display_params *p, uint8_t *bgr
             rgb = d->d_mean; count = d->d_mean_count;
             divide = false;
         }
-        if ((rc = d->dev.enqueue(rgb, count, divide, stream)) != PT_OK) return rc;
+        if (scaled) {
+            // the low mean (levels = 0: sum / n of the accumulators as they are, or merged), the output image's features from the
+            // same camera, the upsample; the bytes are then made from its mean and count
+            if (divide) {
+                PT_HIP_TRY(pt::launch_upsample_mean(rgb, count, static_cast<int>(n), d->up_mean_lo, stream));
+                rgb = d->up_mean_lo;
+            }
+            {
+                std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
+                pt::RenderArgs ra;
+                if ((rc = ptc::scene_trace_args(scene, d->eps, ra)) != PT_OK) return rc;
+                rc = ptc::enqueue_first_hits(scene, ra, ptc::view_camera(scene), ua.width, ua.height, 0, ua.height, d->up_origins, d->up_directions,
+                                             d->up_hit, d->up_hit_t, d->up_position, d->up_normal, d->up_albedo, stream);
+                if (rc != PT_OK) return rc;
+            }
+            ua.mean_lo = rgb; ua.count_lo = count;
+            ua.position = d->up_position; ua.normal = d->up_normal; ua.albedo = d->up_albedo; ua.hit_index = d->up_hit;
+            ua.rec_a = d->up_a; ua.rec_b = d->up_b; ua.rec_c = d->up_c;
+            ua.mean_rgb = d->up_mean; ua.count_out = d->up_count;
+            PT_HIP_TRY(pt::launch_upsample(ua, stream));
+            rgb = d->up_mean; count = d->up_count;
+            divide = false;
+        }
+        if ((rc = dev.enqueue(rgb, count, divide, stream)) != PT_OK) return rc;
         PT_HIP_TRY(hipEventRecord(d->ev1.get(), stream));
     }
     // (an error return from here on leaves the history as it was: its records were only read)
@@ -251,9 +313,9 @@ int display_present_impl(pt_display *d, const pt_display_params *p, uint8_t *bgr
     float ms = 0.0f;
     PT_HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));
     int32_t n_deferred = 0;
-    if ((rc = d->dev.collect(p->gamma, bgr, &n_deferred)) != PT_OK) return rc;
+    if ((rc = dev.collect(p->gamma, bgr, &n_deferred)) != PT_OK) return rc;
     if (temporal) ptc::temporal_commit(d->history);
-    d->dev.fill(info, ms, n_deferred);
+    dev.fill(info, ms, n_deferred);
     return PT_OK;
 }
 
@@ -343,7 +405,11 @@ int pt_display_create_frame(pt_frame *frame, float eps, pt_display **out) {
 }
 
 int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return display_present_impl(d, p, bgr, info); });
+    return guarded([&] { return display_present_impl(d, p, nullptr, false, bgr, info); });
+}
+
+int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, uint8_t *bgr, pt_display_info *info) {
+    return guarded([&] { return display_present_impl(d, p, u, true, bgr, info); });
 }
 
 int pt_display_reset(pt_display *d) {

@@ -51,6 +51,14 @@
 // byte-identical with and without it.  In a sequence only the last frame is also read back, for the dispersion figures in the
 // output name.  -GAUSS / -MEDIAN act on the tone-mapped float image and stay on the host path: with either of them, or with a
 // -GAMMA that is not a finite positive number, the flag is ignored with a message on stderr.
+// Reduced-resolution rendering (pt_upsample_host, not in the reference): -RENDER_SCALE s (default 1: off; 2, 3 or 4) traces the
+// frame at (W / s) x (H / s) and writes it at --W x --H: the low frame's linear mean (denoised with -DENOISE, merged with -TEMPORAL,
+// all at the traced size) is reconstructed at the written size by the feature-guided upsampler from first-hit features rendered
+// at the written size, then tone-mapped, filtered (-GAUSS / -MEDIAN, at the written size) and quantized.  --W and --H must be
+// multiples of s: otherwise, or with s outside 1 .. 4, a message goes to stderr and the exit status is 1.  The dispersion numbers
+// in the file name are those of the low-resolution accumulators; previews (-UPDATE) show the traced frame at its own size.  With
+// -DEVICE_RESOLVE 1 the chain runs on the device (pt_display_present_scaled); the files are byte-identical either way.  With
+// -RENDER_SCALE 1 nothing changes.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -89,6 +97,7 @@ struct Options {   // defaults: config.h:16-29
     float temporal = 0.0f;         // -TEMPORAL: max_frames of the history, 0 = no temporal stage
     std::string eye_end, lookat_end;   // -EYE_END / -LOOKAT_END as given ("" = the start value)
     int device_resolve = 0;        // -DEVICE_RESOLVE: 1 = the images' bytes are made on the device (pt_display_*)
+    int render_scale = 1;          // -RENDER_SCALE: the frame is traced at (W / s) x (H / s) and upsampled to W x H
 };
 
 long long now_ms() {
@@ -142,6 +151,7 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-EYE_END") o.eye_end = v;
         if (f == "-LOOKAT_END") o.lookat_end = v;
         if (f == "-DEVICE_RESOLVE") o.device_resolve = std::atoi(v);
+        if (f == "-RENDER_SCALE") o.render_scale = std::atoi(v);
     }
 }
 
@@ -232,6 +242,15 @@ int main(int argc, char **argv) {
         std::cerr << "pt_render: --W and --H must be positive" << std::endl;
         return 2;
     }
+    if (o.render_scale < 1 || o.render_scale > PT_UPSAMPLE_MAX_SCALE || o.width % o.render_scale || o.height % o.render_scale) {
+        std::cerr << "pt_render: -RENDER_SCALE takes 1, 2, 3 or 4, and --W and --H must be multiples of it" << std::endl;
+        return 1;
+    }
+    const int scale = o.render_scale;
+    const int tw = o.width / scale, th = o.height / scale;   // the traced size; --W x --H is the written size
+    pt_upsample_params upsample;
+    std::memset(&upsample, 0, sizeof upsample);
+    upsample.scale = scale; upsample.sigma_plane = o.dn_sigma_p;
     const bool sequence = o.frames > 1 || o.temporal > 0.0f;
     if (o.frames > 1 && o.time_limit != 0) {
         std::cerr << "pt_render: -TL is not defined for a sequence (-FRAMES > 1)" << std::endl;
@@ -292,7 +311,7 @@ int main(int argc, char **argv) {
     if (o.rehearse) flags |= PT_FRAME_REHEARSE;
     if (o.selfcoll) flags |= PT_FRAME_SELF_COLLECTIVE;
     pt_frame *frame = nullptr;
-    if (pt_frame_create(scene, devices.data(), static_cast<int32_t>(devices.size()), o.width, o.height, flags, &frame) != PT_OK)
+    if (pt_frame_create(scene, devices.data(), static_cast<int32_t>(devices.size()), tw, th, flags, &frame) != PT_OK)
         return die("pt_render");
     int32_t transport = 0;
     pt_frame_info(frame, nullptr, nullptr, nullptr, &transport);
@@ -304,7 +323,7 @@ int main(int argc, char **argv) {
 
     pt_render_params rp;
     std::memset(&rp, 0, sizeof rp);
-    rp.width = o.width; rp.height = o.height; rp.row_begin = 0; rp.row_end = o.height;
+    rp.width = tw; rp.height = th; rp.row_begin = 0; rp.row_end = th;
     rp.max_ray_reflections = o.max_ray_reflections;
     rp.eps = o.eps; rp.error = o.error; rp.seed = seed;
 
@@ -323,7 +342,7 @@ int main(int argc, char **argv) {
             if (!one_frame()) return die("pt_render");
         if (pt_frame_wait(frame) != PT_OK) return die("pt_render");
         const double dt = secs(a, clk::now());
-        const double samples = static_cast<double>(o.width) * o.height * o.rays_per_pixel * o.bench_steps;
+        const double samples = static_cast<double>(tw) * th * o.rays_per_pixel * o.bench_steps;
         // With more than one band: one more frame, untimed, taken apart -- every band's own kernel time (HIP events on its
         // stream), then, with all kernels done, the gather alone on the host's clock -- so that the first run on several devices
         // says where the time went and not only how long it took.
@@ -350,14 +369,14 @@ int main(int argc, char **argv) {
         }
         std::printf("{\"cxx_frame\": true, \"value\": %.3f, \"unit\": \"Msamples/s\", \"ms_per_step\": %.4f, \"steps\": %d, \"warmup\": %d, "
                     "\"bands\": %zu, \"devices_visible\": %d, \"transport\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"mrr\": %d, \"error\": %g%s}\n",
-                    samples / dt / 1e6, dt / o.bench_steps * 1e3, o.bench_steps, o.bench_warmup, devices.size(), n_dev, transport_name, o.width, o.height,
+                    samples / dt / 1e6, dt / o.bench_steps * 1e3, o.bench_steps, o.bench_warmup, devices.size(), n_dev, transport_name, tw, th,
                     o.rays_per_pixel, o.max_ray_reflections, static_cast<double>(o.error), diagnosis.c_str());
         pt_frame_destroy(frame);
         pt_scene_destroy(scene);
         return 0;
     }
 
-    const size_t px = static_cast<size_t>(o.width) * o.height;
+    const size_t px = static_cast<size_t>(tw) * th;
     // Page-locked accumulators: the read-back then runs at PCIe speed without staging copies.  They are allocated on first
     // use -- normally while the GPUs are busy with the frame (pinning 116 MB takes 20 ms, which the host has nothing else to
     // do with between enqueueing the passes and waiting for them).
@@ -404,6 +423,28 @@ int main(int argc, char **argv) {
     show.denoise.levels = o.denoise; show.denoise.sigma_luminance = o.dn_sigma_l; show.denoise.sigma_plane = o.dn_sigma_p;
     if (device_resolve && pt_display_create_frame(frame, o.eps, &display) != PT_OK) return die("pt_render");
 
+    // -RENDER_SCALE s > 1: the written image, and the host chain that makes it from the traced frame's mean and count --
+    // features at the written size from `view` (the scene on the first device, with the frame's camera), the upsample, the
+    // tone map, the reference's filters and set_pixel
+    std::vector<uint8_t> out_bgr;
+    if (scale > 1) out_bgr.resize(3 * static_cast<size_t>(o.width) * o.height);
+    auto upsample_to_output = [&](pt_scene *view, const float *mean_lo, const int32_t *count_lo) {
+        const size_t opx = static_cast<size_t>(o.width) * o.height;
+        std::vector<float> pos(3 * opx), nrm(3 * opx), alb(3 * opx), mean(3 * opx), rgb(3 * opx);
+        std::vector<int32_t> hit(opx), count_out(opx);
+        pt_render_params fp = rp;
+        fp.width = o.width; fp.height = o.height; fp.row_begin = 0; fp.row_end = o.height;
+        if (pt_render_features_host(view, &fp, hit.data(), nullptr, pos.data(), nrm.data(), alb.data()) != PT_OK ||
+            pt_upsample_host(devices[0], o.width, o.height, mean_lo, count_lo, pos.data(), nrm.data(), alb.data(), hit.data(), &upsample, mean.data(),
+                             count_out.data(), nullptr) != PT_OK)
+            return false;
+        pt_tonemap(o.width, o.height, mean.data(), count_out.data(), o.gamma_correction, rgb.data());
+        if ((o.gauss || o.median) && pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return false;
+        return pt_quantize(o.width, o.height, rgb.data(), count_out.data(), out_bgr.data()) == PT_OK;
+    };
+    // what the files hold: the traced frame's bytes, or the upsampled image's
+    auto out_bytes = [&]() { return scale > 1 ? out_bgr.data() : bgr.data(); };
+
     if (sequence) {
         // n frames: frame i renders its own pass range from its own camera, is merged with the history (-TEMPORAL), denoised
         // (-DENOISE), tone-mapped, filtered, quantized and written; the last one also takes the usual outputs
@@ -416,13 +457,13 @@ int main(int argc, char **argv) {
         const bool own_camera = o.camera || !o.eye_end.empty() || !o.lookat_end.empty();
         pt_scene *view = nullptr;   // the scene on the first device: the history's and the feature buffers' handle
         pt_temporal *history = nullptr;
-        if (!display && (o.temporal > 0.0f || o.denoise > 0) && pt_scene_clone_to_device(scene, devices[0], &view) != PT_OK) return die("pt_render");
-        if (!display && o.temporal > 0.0f && pt_temporal_create(view, o.width, o.height, o.eps, &history) != PT_OK) return die("pt_render");
+        if (!display && (o.temporal > 0.0f || o.denoise > 0 || scale > 1) && pt_scene_clone_to_device(scene, devices[0], &view) != PT_OK) return die("pt_render");
+        if (!display && o.temporal > 0.0f && pt_temporal_create(view, tw, th, o.eps, &history) != PT_OK) return die("pt_render");
         if (!ensure_buffers()) return die("pt_render");
         std::vector<float> msum, msum2, mean, rgb, pos, nrm, alb;
         std::vector<int32_t> mcount, mean_count, hit;
         if (history) { msum.resize(3 * px); msum2.resize(3 * px); mcount.resize(px); }
-        if (o.denoise > 0 && !display) { mean.resize(3 * px); mean_count.resize(px); }
+        if ((o.denoise > 0 || scale > 1) && !display) { mean.resize(3 * px); mean_count.resize(px); }
         if (o.denoise > 0 && !history && !display) { pos.resize(3 * px); nrm.resize(3 * px); alb.resize(3 * px); hit.resize(px); }
         if ((o.denoise > 0 && !display) || o.gauss || o.median) rgb.resize(3 * px);
         pt_temporal_params tp;
@@ -449,12 +490,14 @@ int main(int argc, char **argv) {
                 // the bytes come from the device; only the last frame is also read back, for the statistics in the output's name
                 if (i == o.frames - 1) {
                     if (read_back() != PT_OK) return die("pt_render");
-                    pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
+                    pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
                 }
-                if (pt_display_present(display, &show, bgr.data(), nullptr) != PT_OK) return die("pt_render");
+                if (scale > 1 ? pt_display_present_scaled(display, &show, &upsample, out_bgr.data(), nullptr) != PT_OK
+                              : pt_display_present(display, &show, bgr.data(), nullptr) != PT_OK)
+                    return die("pt_render");
             } else {
                 if (read_back() != PT_OK) return die("pt_render");
-                pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);   // the statistics of the frame as rendered
+                pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);   // the statistics of the frame as rendered
                 const float *fs = sum, *fs2 = sum2;
                 const int32_t *fc = count;
                 if (history) {
@@ -464,27 +507,35 @@ int main(int argc, char **argv) {
                     fs = msum.data(); fs2 = msum2.data(); fc = mcount.data();
                 } else if (o.denoise > 0) {
                     if (pt_render_features_host(view, &rp, hit.data(), nullptr, pos.data(), nrm.data(), alb.data()) != PT_OK ||
-                        pt_denoise_host(devices[0], o.width, o.height, fs, fs2, fc, pos.data(), nrm.data(), alb.data(), hit.data(), &dp, mean.data(),
+                        pt_denoise_host(devices[0], tw, th, fs, fs2, fc, pos.data(), nrm.data(), alb.data(), hit.data(), &dp, mean.data(),
                                         mean_count.data(), nullptr) != PT_OK)
                         return die("pt_render");
                 }
-                if (o.denoise > 0) {
-                    pt_tonemap(o.width, o.height, mean.data(), mean_count.data(), o.gamma_correction, rgb.data());
-                    if ((o.gauss || o.median) && pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
-                    pt_quantize(o.width, o.height, rgb.data(), mean_count.data(), bgr.data());
+                if (scale > 1) {
+                    // the traced frame's mean (the filter's, or sum / n of the frame as rendered or merged), upsampled
+                    pt_denoise_params none;
+                    std::memset(&none, 0, sizeof none);
+                    if (o.denoise == 0 && pt_denoise_host(devices[0], tw, th, fs, fs2, fc, nullptr, nullptr, nullptr, nullptr, &none, mean.data(),
+                                                          mean_count.data(), nullptr) != PT_OK)
+                        return die("pt_render");
+                    if (!upsample_to_output(view, mean.data(), mean_count.data())) return die("pt_render");
+                } else if (o.denoise > 0) {
+                    pt_tonemap(tw, th, mean.data(), mean_count.data(), o.gamma_correction, rgb.data());
+                    if ((o.gauss || o.median) && pt_post_filter_host(devices[0], tw, th, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+                    pt_quantize(tw, th, rgb.data(), mean_count.data(), bgr.data());
                 } else if (o.gauss || o.median) {
                     float unused[3];
-                    pt_resolve_float(o.width, o.height, fs, fs2, fc, o.gamma_correction, rgb.data(), unused);
-                    if (pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
-                    pt_quantize(o.width, o.height, rgb.data(), fc, bgr.data());
+                    pt_resolve_float(tw, th, fs, fs2, fc, o.gamma_correction, rgb.data(), unused);
+                    if (pt_post_filter_host(devices[0], tw, th, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+                    pt_quantize(tw, th, rgb.data(), fc, bgr.data());
                 } else if (history) {
-                    pt_resolve(o.width, o.height, fs, fs2, fc, o.gamma_correction, bgr.data(), nullptr);
+                    pt_resolve(tw, th, fs, fs2, fc, o.gamma_correction, bgr.data(), nullptr);
                 }
             }
             if (o.frames > 1) {
                 char frame_name[32];
                 std::snprintf(frame_name, sizeof frame_name, "frame_%04d.bmp", i);
-                if (pt_write_bmp(frame_name, o.width, o.height, bgr.data()) != PT_OK) return die("pt_render");
+                if (pt_write_bmp(frame_name, o.width, o.height, out_bytes()) != PT_OK) return die("pt_render");
             }
             if (!o.quiet) std::cerr << "frame " << i + 1 << " of " << o.frames << std::endl;
         }
@@ -498,10 +549,10 @@ int main(int argc, char **argv) {
             "  max_disp " + std::to_string(disp[0]) + "  min_disp " + std::to_string(disp[1]) + "  aver_disp " + std::to_string(disp[2]);
         int rc = 0;
         if (!o.out.empty()) {
-            if (pt_write_bmp(o.out.c_str(), o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
+            if (pt_write_bmp(o.out.c_str(), o.width, o.height, out_bytes()) != PT_OK) rc = die("pt_render");
         } else {
-            if (pt_write_bmp((name + ".bmp").c_str(), o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
-            if (pt_write_bmp("../result.bmp", o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
+            if (pt_write_bmp((name + ".bmp").c_str(), o.width, o.height, out_bytes()) != PT_OK) rc = die("pt_render");
+            if (pt_write_bmp("../result.bmp", o.width, o.height, out_bytes()) != PT_OK) rc = die("pt_render");
         }
         std::cout << name << std::endl;
         pt_temporal_destroy(history);
@@ -547,8 +598,8 @@ int main(int argc, char **argv) {
             if (o.update != 0 && p % o.update == 0) {
                 const clk::time_point b = clk::now();
                 if (read_back() != PT_OK) return die("pt_render");
-                pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), nullptr);
-                if (o.out.empty() && pt_write_bmp("../result.bmp", o.width, o.height, bgr.data()) != PT_OK)
+                pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), nullptr);
+                if (o.out.empty() && pt_write_bmp("../result.bmp", tw, th, bgr.data()) != PT_OK)
                     std::cerr << pt_last_error() << std::endl;   // the reference's save_image only prints, too
                 std::cerr << "Image update" << std::endl;
                 preview_s += secs(b, clk::now());
@@ -571,20 +622,44 @@ int main(int argc, char **argv) {
     float denoise_kernel_ms = 0;
     if (display) {
         // the statistics of the frame as rendered, on the host; the image's bytes from the device (features, denoiser, tone map)
-        pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
+        pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
         const clk::time_point f1 = clk::now();
         pt_display_info shown;
-        if (pt_display_present(display, &show, bgr.data(), &shown) != PT_OK) return die("pt_render");
+        if (scale > 1 ? pt_display_present_scaled(display, &show, &upsample, out_bgr.data(), &shown) != PT_OK
+                      : pt_display_present(display, &show, bgr.data(), &shown) != PT_OK)
+            return die("pt_render");
         if (o.denoise > 0) {
             denoise_s = secs(f1, clk::now());
             denoise_kernel_ms = shown.kernel_ms;
         }
+    } else if (scale > 1) {
+        // the statistics of the traced frame; its mean (the filter's with -DENOISE, else sum / n); the upsample to the written size
+        std::vector<float> mean(3 * px), pos, nrm, alb;
+        std::vector<int32_t> hit, count_lo(px);
+        pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
+        pt_scene *view = nullptr;
+        if (pt_scene_clone_to_device(scene, devices[0], &view) != PT_OK) return die("pt_render");
+        pt_denoise_params dp;
+        std::memset(&dp, 0, sizeof dp);
+        dp.levels = o.denoise; dp.sigma_luminance = o.dn_sigma_l; dp.sigma_plane = o.dn_sigma_p;
+        if (o.denoise > 0) {
+            pos.resize(3 * px); nrm.resize(3 * px); alb.resize(3 * px); hit.resize(px);
+            if (pt_render_features_host(view, &rp, hit.data(), nullptr, pos.data(), nrm.data(), alb.data()) != PT_OK) return die("pt_render");
+        }
+        const clk::time_point f1 = clk::now();
+        if (pt_denoise_host(devices[0], tw, th, sum, sum2, count, pos.data(), nrm.data(), alb.data(), hit.data(), &dp, mean.data(), count_lo.data(),
+                            &denoise_kernel_ms) != PT_OK)
+            return die("pt_render");
+        const bool ok = upsample_to_output(view, mean.data(), count_lo.data());
+        pt_scene_destroy(view);
+        if (!ok) return die("pt_render");
+        denoise_s = secs(f1, clk::now());
     } else if (o.denoise > 0) {
         // the statistics of the frame as rendered; then the first hits of the pinhole view on the frame's first device, the
         // denoiser on the linear mean, the tone map, the reference's filters and set_pixel
         std::vector<float> rgb(3 * px), mean(3 * px), pos(3 * px), nrm(3 * px), alb(3 * px);
         std::vector<int32_t> hit(px), count_out(px);
-        pt_resolve_float(o.width, o.height, sum, sum2, count, o.gamma_correction, rgb.data(), disp);
+        pt_resolve_float(tw, th, sum, sum2, count, o.gamma_correction, rgb.data(), disp);
         const clk::time_point f0 = clk::now();
         pt_scene *view = nullptr;
         if (pt_scene_clone_to_device(scene, devices[0], &view) != PT_OK) return die("pt_render");
@@ -595,21 +670,21 @@ int main(int argc, char **argv) {
         pt_denoise_params dp;
         std::memset(&dp, 0, sizeof dp);
         dp.levels = o.denoise; dp.sigma_luminance = o.dn_sigma_l; dp.sigma_plane = o.dn_sigma_p;
-        if (pt_denoise_host(devices[0], o.width, o.height, sum, sum2, count, pos.data(), nrm.data(), alb.data(), hit.data(), &dp,
+        if (pt_denoise_host(devices[0], tw, th, sum, sum2, count, pos.data(), nrm.data(), alb.data(), hit.data(), &dp,
                             mean.data(), count_out.data(), &denoise_kernel_ms) != PT_OK)
             return die("pt_render");
         features_s = secs(f0, f1);
         denoise_s = secs(f1, clk::now());
-        pt_tonemap(o.width, o.height, mean.data(), count_out.data(), o.gamma_correction, rgb.data());
-        if ((o.gauss || o.median) && pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
-        pt_quantize(o.width, o.height, rgb.data(), count_out.data(), bgr.data());
+        pt_tonemap(tw, th, mean.data(), count_out.data(), o.gamma_correction, rgb.data());
+        if ((o.gauss || o.median) && pt_post_filter_host(devices[0], tw, th, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+        pt_quantize(tw, th, rgb.data(), count_out.data(), bgr.data());
     } else if (o.gauss || o.median) {   // main.cpp:187-201: filters act on the tonemapped float image, then set_pixel
         std::vector<float> rgb(3 * px);
-        pt_resolve_float(o.width, o.height, sum, sum2, count, o.gamma_correction, rgb.data(), disp);
-        if (pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
-        pt_quantize(o.width, o.height, rgb.data(), count, bgr.data());
+        pt_resolve_float(tw, th, sum, sum2, count, o.gamma_correction, rgb.data(), disp);
+        if (pt_post_filter_host(devices[0], tw, th, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+        pt_quantize(tw, th, rgb.data(), count, bgr.data());
     } else {
-        pt_resolve(o.width, o.height, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
+        pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
     }
     const clk::time_point t_resolve = clk::now();
     const long long end_time = now_ms();
@@ -622,10 +697,10 @@ int main(int argc, char **argv) {
         "  max_disp " + std::to_string(disp[0]) + "  min_disp " + std::to_string(disp[1]) + "  aver_disp " + std::to_string(disp[2]);
     int rc = 0;
     if (!o.out.empty()) {
-        if (pt_write_bmp(o.out.c_str(), o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
+        if (pt_write_bmp(o.out.c_str(), o.width, o.height, out_bytes()) != PT_OK) rc = die("pt_render");
     } else {
-        if (pt_write_bmp((name + ".bmp").c_str(), o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
-        if (pt_write_bmp("../result.bmp", o.width, o.height, bgr.data()) != PT_OK) rc = die("pt_render");
+        if (pt_write_bmp((name + ".bmp").c_str(), o.width, o.height, out_bytes()) != PT_OK) rc = die("pt_render");
+        if (pt_write_bmp("../result.bmp", o.width, o.height, out_bytes()) != PT_OK) rc = die("pt_render");
     }
     std::cout << name << std::endl;
     if (o.timing) {
