@@ -583,7 +583,8 @@ int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, 
  * *u is checked as pt_upsample_host checks it, before anything is enqueued: a failed call leaves the history as it was. */
 int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, uint8_t *bgr,
                               pt_display_info *info /* may be NULL */);
-int pt_display_reset(pt_display *d);     /* forget the history: the next present with a temporal stage is a first frame */
+int pt_display_reset(pt_display *d);     /* forget the history: the next present with a temporal stage is a first frame (and the
+                                          * next metered present of pt_display_present_graded a first one) */
 void pt_display_destroy(pt_display *d);
 
 /* The kernel alone, on a host image: the bytes of pt_tonemap -> pt_quantize for (mean_rgb, count), made on HIP device `device`.
@@ -593,6 +594,96 @@ int pt_display_bytes_host(int device, int32_t width, int32_t height, const float
 /* The table itself (host only, no device).  *levels = K; thresholds, doubt_lo, doubt_hi (each may be NULL: pass all NULL to query
  * K) get K floats: T_k at [k - 1], and the doubt band of level k, empty (lo == hi) where none is needed. */
 int pt_display_table(float gamma, int32_t *levels, float *thresholds, float *doubt_lo, float *doubt_hi);
+
+/* ---- display grading: exposure, saturating tone curves, metered auto-exposure ----------------------------- */
+
+/* The reference's last step, byte = (uint8_t)(int)(pow(m, gamma) * 255), wraps above 1 (a mean of 2 is byte 93), has no exposure
+ * and cannot adapt.  Grading is one step BEFORE it, on the linear mean: per channel of a pixel with samples
+ *   x = m * e,   g = curve(x),
+ * and g takes the mean's place in pt_tonemap -> pt_quantize (host) or in the display kernel's table search (device).  The table
+ * of pt_display_table is the ungraded one: it depends on gamma alone, never on the curve or the exposure.
+ *
+ * The arithmetic, exactly, as for the denoiser: every operation below is ONE correctly rounded float operation in the order
+ * written (* / + -, comparisons; nothing fused, no approximations), so host and device compute the same g bit for bit.
+ *   PT_CURVE_REFERENCE   g = x                      (with e = 1: today's bytes, wrap included)
+ *   PT_CURVE_CLAMP       g = x > 1 ? 1 : x
+ *   PT_CURVE_REINHARD    g = x / (1 + x)
+ *   PT_CURVE_ACES        a = x * ((2.51 * x) + 0.03),  b = (x * ((2.43 * x) + 0.59)) + 0.14,  g = a / b,  g = g > 1 ? 1 : g
+ * (the constants are the floats nearest to the decimals written).  NaN, negative and infinite values get no special case: whatever
+ * g comes out goes on; on the device a negative or NaN g defers its pixel to the host, as a negative or NaN mean does, and the
+ * host finishes it from the pixel's ungraded mean with these same steps.
+ *
+ * Metering.  The histogram has 129 uint32 counts.  Of every pixel with count != 0:  l = lum(m) = (0.2126 m_r + 0.7152 m_g) + 0.0722 m_b
+ * of the UNGRADED linear mean.  If !(l > 0) -- zero, negative, NaN --: hist[128] += 1 ("dark").  Else idx = bits(l) >> 21 (the
+ * exponent and two mantissa bits: quarter-octave bins), bin = idx - 444 clamped to 0 .. 127, hist[bin] += 1.  444 = bits(2^-16) >> 21:
+ * the bins cover 2^-16 .. 2^16, +inf lands in bin 127, denormals in bin 0; the lower edge of bin b is the float
+ * edge(b) = from_bits((b + 444) << 21).  Integer sums do not depend on the order, so the histogram is exact.
+ *
+ * Exposure from a histogram.  N = hist[0] + .. + hist[127].  If N = 0: e* = e_prev if there is a previous exposure, else 1.
+ * Otherwise b_p = the smallest b with 100 * (hist[0] + .. + hist[b]) >= percentile * N (64-bit integers),  e* = key / edge(b_p),
+ * e* = e* < e_min ? e_min : (e* > e_max ? e_max : e*).  Without a previous exposure, or if rate >= 1: e = e*.  Otherwise
+ * e = e_prev + (e* - e_prev) * rate.
+ *
+ * Parameters; a zeroed struct holds the defaults (no grading at all: REFERENCE, e = 1, no metering):
+ *   curve           PT_CURVE_*                                                       (anything else: invalid)
+ *   exposure        the manual e; 0 = 1                                              (negative or non-finite: invalid)
+ *   auto_exposure   0: e = exposure.  Else e comes from the meter and `exposure` is checked but not used
+ *   percentile      0 = 50; else 1 .. 100                                            (outside: invalid)
+ *   key             0 = 0.18       e_min  0 = 2^-8       e_max  0 = 2^8       rate  0 = 1     (negative or non-finite: invalid)
+ *   e_min > e_max (after the defaults): invalid. */
+#define PT_CURVE_REFERENCE 0
+#define PT_CURVE_CLAMP 1
+#define PT_CURVE_REINHARD 2
+#define PT_CURVE_ACES 3
+#define PT_METER_ENTRIES 129
+typedef struct pt_grade_params {
+    int32_t curve;
+    float exposure;
+    int32_t auto_exposure;
+    int32_t percentile;
+    float key, e_min, e_max, rate;
+} pt_grade_params;
+typedef struct pt_grade_info {
+    float exposure;              /* the e that was used */
+    float target;                /* e* (a manual exposure: the same as `exposure`) */
+    uint32_t metered, dark;      /* N and hist[128] of the metering (a manual exposure: 0, 0) */
+} pt_grade_info;
+
+/* Host only, no device: out_rgb = curve(mean_rgb * exposure) per channel for pixels with count != 0, the others keep their
+ * value (out_rgb may be mean_rgb).  The chain of a graded image is ... -> pt_grade_host -> pt_tonemap -> pt_quantize.
+ * PT_ERR_INVALID_ARGUMENT: a NULL buffer, an empty image, an unknown curve, an exposure that is not finite and > 0 (0 is NOT
+ * a default here: the caller passes the e it means). */
+int pt_grade_host(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure, int32_t curve,
+                  float *out_rgb);
+/* The meter kernel alone, on a host image: hist[0 .. 128] of (mean_rgb, count), made on HIP device `device`; kernel_ms (may be
+ * NULL) = HIP-event time of the kernel.  Buffers and sizes are checked BEFORE the device is looked at; PT_ERR_NO_DEVICE if that
+ * is not a usable device (there is no CPU fallback). */
+int pt_meter_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count,
+                  uint32_t *hist /* PT_METER_ENTRIES */, float *kernel_ms);
+/* Host only, pure: the rule above.  has_prev != 0: e_prev is the e of the previous metered present.  On PT_ERR_INVALID_ARGUMENT
+ * (a NULL pointer, a parameter outside what is stated above) *e and *e_target are not written. */
+int pt_exposure_from_histogram(const uint32_t *hist, const pt_grade_params *params, int32_t has_prev, float e_prev, float *e,
+                               float *e_target);
+
+/* pt_display_present (u = NULL) or pt_display_present_scaled (u given) with grading: the same chain, and between its last
+ * image stage and the display kernel -- if g->auto_exposure -- the meter and the exposure kernel, all on the session's stream
+ * with no host synchronisation inside.  The meter sees the linear mean the display kernel is about to read, at the OUTPUT size
+ * (after the upsample if u is given).  The bytes are DEFINED by the host chain and equal it bit for bit: the row of the tables
+ * above up to the linear mean and count (a row that ends in pt_resolve: mean = sum / n and count, as pt_denoise_host with
+ * levels = 0 gives them), then, if automatic, pt_meter_host -> pt_exposure_from_histogram with the display's previous
+ * exposure, then pt_grade_host -> pt_tonemap -> pt_quantize.  With curve = REFERENCE, exposure 0 or 1 and no auto-exposure
+ * the bytes are those of the ungraded present.
+ * The display keeps the e of its last metered present; like the history it advances only after the bytes have reached the host,
+ * so a failed present leaves it as it was, and pt_display_reset forgets it: the next metered present is a first one.  A manual
+ * present neither reads nor changes it.  *g is checked before anything is enqueued and before the device is looked at. */
+int pt_display_present_graded(pt_display *d, const pt_display_params *p, const pt_upsample_params *u /* NULL: not scaled */,
+                              const pt_grade_params *g, uint8_t *bgr, pt_display_info *info /* may be NULL */,
+                              pt_grade_info *grade_info /* may be NULL */);
+/* pt_display_bytes_host with grading: meter (if automatic; has_prev, e_prev as for pt_exposure_from_histogram), exposure and the
+ * graded display kernel as one chain on HIP device `device`, on a host image. */
+int pt_display_bytes_graded_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count,
+                                 float gamma, const pt_grade_params *g, int32_t has_prev, float e_prev, uint8_t *bgr,
+                                 pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
 
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */

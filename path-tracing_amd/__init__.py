@@ -44,7 +44,9 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_temporal_create", "pt_temporal_push_host", "pt_temporal_reset", "pt_temporal_destroy",
                "pt_display_create", "pt_display_create_frame", "pt_display_present", "pt_display_reset", "pt_display_destroy",
                "pt_display_bytes_host", "pt_display_table",
-               "pt_upsample_host", "pt_display_present_scaled"]
+               "pt_upsample_host", "pt_display_present_scaled",
+               "pt_grade_host", "pt_meter_host", "pt_exposure_from_histogram", "pt_display_present_graded",
+               "pt_display_bytes_graded_host"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -147,6 +149,34 @@ class DisplayInfo(C.Structure):
 
 
 DISPLAY_MAX_LEVELS = 4096
+CURVE_REFERENCE, CURVE_CLAMP, CURVE_REINHARD, CURVE_ACES = 0, 1, 2, 3
+CURVES = {"reference": CURVE_REFERENCE, "clamp": CURVE_CLAMP, "reinhard": CURVE_REINHARD, "aces": CURVE_ACES}
+METER_ENTRIES = 129
+
+
+class GradeParams(C.Structure):
+    """pt_grade_params: the tone curve, the manual exposure (0 = 1) or auto_exposure with its metering rule; a zeroed struct is no
+    grading at all, and zeroed metering fields hold the defaults (percentile 50, key 0.18, e_min 2^-8, e_max 2^8, rate 1)."""
+    _fields_ = [("curve", C.c_int32), ("exposure", C.c_float), ("auto_exposure", C.c_int32), ("percentile", C.c_int32),
+                ("key", C.c_float), ("e_min", C.c_float), ("e_max", C.c_float), ("rate", C.c_float)]
+
+
+class GradeInfo(C.Structure):
+    """pt_grade_info: the exposure used, the meter's target e*, the metered and the dark pixels."""
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("metered", C.c_uint32), ("dark", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _grade_params(grade):
+    """A GradeParams, or a dict of its fields (curve may be a name: "clamp") -> a GradeParams."""
+    if isinstance(grade, dict):
+        curve = grade.get("curve", CURVE_REFERENCE)
+        return GradeParams(CURVES[curve] if isinstance(curve, str) else curve, grade.get("exposure", 0.0), 1 if grade.get("auto_exposure") else 0,
+                           grade.get("percentile", 0), grade.get("key", 0.0), grade.get("e_min", 0.0), grade.get("e_max", 0.0),
+                           grade.get("rate", 0.0))
+    return grade
 
 
 def _lens_arg(radius, focus_distance):
@@ -288,6 +318,14 @@ def load_library(path):
     L.pt_display_destroy.restype = None
     L.pt_display_bytes_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, bp, C.POINTER(DisplayInfo)]
     L.pt_display_table.argtypes = [C.c_float, ip, fp, fp, fp]
+    up = C.POINTER(C.c_uint32)
+    L.pt_grade_host.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, C.c_int32, fp]
+    L.pt_meter_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, up, fp]
+    L.pt_exposure_from_histogram.argtypes = [up, C.POINTER(GradeParams), C.c_int32, C.c_float, fp, fp]
+    L.pt_display_present_graded.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), bp,
+                                            C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_display_bytes_graded_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(GradeParams), C.c_int32, C.c_float, bp,
+                                               C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -621,12 +659,14 @@ class Display:
         create = self._L.pt_display_create_frame if isinstance(session_or_frame, Frame) else self._L.pt_display_create
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
-    def present(self, gamma=None, temporal=None, denoise=None, upsample=None):
+    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
         parameters.  Returns (bgr uint8 [H, W, 3], info dict).
         `upsample`: None, an UpsampleParams, or a dict of pt.upsample's parameters ({"scale": 2}) -- pt_display_present_scaled: the
-        image is then scale times the session's size, bgr uint8 [scale * H, scale * W, 3]."""
+        image is then scale times the session's size, bgr uint8 [scale * H, scale * W, 3].
+        `grade`: None, a GradeParams, or a dict of its fields ({"curve": "aces", "auto_exposure": True}) -- pt_display_present_graded:
+        exposure and a tone curve before the tone map; info then also holds exposure, target, metered, dark."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -635,6 +675,14 @@ class Display:
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
         info = DisplayInfo()
+        if grade is not None:
+            gp, ginfo = _grade_params(grade), GradeInfo()
+            up = _upsample_params(upsample) if upsample is not None else None
+            k = up.scale if up is not None and 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1
+            bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8)
+            _check(self._L.pt_display_present_graded(self._h, C.byref(prm), C.byref(up) if up is not None else None, C.byref(gp),
+                                                     bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info), C.byref(ginfo)), self._L)
+            return bgr, dict(info.as_dict(), **ginfo.as_dict())
         if upsample is not None:
             up = _upsample_params(upsample)
             k = up.scale if 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1       # (a scale the library refuses: it writes nothing)
@@ -679,6 +727,67 @@ def display_bytes(mean_rgb, count, gamma=None, device=0, library=None):
     info = DisplayInfo()
     _check(L.pt_display_bytes_host(device, w, h, _fp(m), _ip(c), C.c_float(gamma), bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)), L)
     return bgr, info.as_dict()
+
+
+def _image_args(name, mean_rgb, count):
+    m = np.ascontiguousarray(mean_rgb, np.float32)
+    if m.ndim != 3 or m.shape[2] != 3:
+        raise ValueError(f"{name}: mean_rgb must be [H, W, 3]")
+    c = np.ascontiguousarray(count, np.int32)
+    if c.size != m.shape[0] * m.shape[1]:
+        raise ValueError(f"{name}: count does not hold width x height pixels")
+    return m, c
+
+
+def grade(mean_rgb, count, exposure=1.0, curve=CURVE_REFERENCE, library=None):
+    """pt_grade_host (host only): curve(mean * exposure) per channel of the pixels with samples of mean_rgb [H, W, 3]; the others
+    keep their value.  `curve`: a CURVE_* or its name."""
+    L = library or lib()
+    m, c = _image_args("grade", mean_rgb, count)
+    out = np.zeros_like(m)
+    _check(L.pt_grade_host(m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), CURVES[curve] if isinstance(curve, str) else curve,
+                           _fp(out)), L)
+    return out
+
+
+def meter(mean_rgb, count, device=0, want_ms=False, library=None):
+    """pt_meter_host: the meter kernel alone on a host image -- the 129 counts of the luminance histogram (uint32; [128] = dark),
+    and the kernel's milliseconds as a second value if want_ms."""
+    L = library or lib()
+    m, c = _image_args("meter", mean_rgb, count)
+    hist, ms = np.zeros(METER_ENTRIES, np.uint32), C.c_float()
+    _check(L.pt_meter_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(ms)), L)
+    return (hist, ms.value) if want_ms else hist
+
+
+def exposure_from_histogram(hist, grade=None, e_prev=None, library=None):
+    """pt_exposure_from_histogram (host only): (e, e*) of a histogram under the metering rule of `grade` (None: the defaults);
+    e_prev = the previous metered exposure, None on a first frame."""
+    L = library or lib()
+    h = np.ascontiguousarray(hist, np.uint32)
+    if h.size != METER_ENTRIES:
+        raise ValueError("exposure_from_histogram: the histogram has 129 counts")
+    gp = _grade_params(grade) if grade is not None else GradeParams()
+    e, t = C.c_float(), C.c_float()
+    _check(L.pt_exposure_from_histogram(h.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(gp), 0 if e_prev is None else 1,
+                                        C.c_float(0.0 if e_prev is None else e_prev), C.byref(e), C.byref(t)), L)
+    return np.float32(e.value), np.float32(t.value)
+
+
+def display_bytes_graded(mean_rgb, count, grade, gamma=None, e_prev=None, device=0, library=None):
+    """pt_display_bytes_graded_host: meter (if automatic), exposure and the graded display kernel on a host image.  Returns
+    (bgr uint8 [H, W, 3], info dict with the display's and the grade's fields)."""
+    L = library or lib()
+    if gamma is None:
+        gamma = np.float32(1) / np.float32(2.2)
+    m, c = _image_args("display_bytes_graded", mean_rgb, count)
+    gp = _grade_params(grade)
+    bgr = np.zeros(m.shape, np.uint8)
+    info, ginfo = DisplayInfo(), GradeInfo()
+    _check(L.pt_display_bytes_graded_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(gamma), C.byref(gp),
+                                          0 if e_prev is None else 1, C.c_float(0.0 if e_prev is None else e_prev),
+                                          bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info), C.byref(ginfo)), L)
+    return bgr, dict(info.as_dict(), **ginfo.as_dict())
 
 
 def display_table(gamma, library=None):

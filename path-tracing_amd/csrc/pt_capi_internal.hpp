@@ -1,6 +1,6 @@
 // Types shared by the translation units behind the C ABI (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters;
 // pt_frame.cpp: the multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp: the
-// temporal stage; pt_display_capi.cpp: the device-resident display path; pt_upsample_capi.cpp: the upsampler; pt_device_mem.hpp: the owners of everything they hold
+// temporal stage; pt_display_capi.cpp: the device-resident display path; pt_grade_capi.cpp: display grading; pt_upsample_capi.cpp: the upsampler; pt_device_mem.hpp: the owners of everything they hold
 // on a device).  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/pt_hip.h"
@@ -16,6 +16,7 @@
 
 #include "pt_denoise.hpp"
 #include "pt_device_mem.hpp"
+#include "pt_grade.hpp"
 #include "pt_kernels.hpp"
 #include "pt_scene.hpp"
 #include "pt_upsample.hpp"
@@ -163,6 +164,15 @@ int upsample_params_to_args(const pt_upsample_params *prm, int32_t width, int32_
 // two steps, shared by pt_resolve, pt_tonemap, pt_quantize and the display path, whose threshold table is made from them.
 inline float tonemap_value(float mean, float gamma) { return std::pow(mean, gamma) * 255.0f; }
 inline uint8_t quantize_value(float value) { return static_cast<uint8_t>(static_cast<int>(value)); }
+
+// pt_grade_params as every entry point checks them (no device is touched), with the defaults filled in.
+struct GradeSetup {
+    int curve = pt::kCurveReference;
+    bool automatic = false;
+    float exposure = 1.0f;   // the manual e
+    pt::ExposureRule rule{};
+};
+int grade_params_check(const pt_grade_params *g, GradeSetup &out);
 
 // pt_temporal_push_host in two halves, for a chain whose frame already lies on the device (pt_display_present).
 // temporal_enqueue checks the parameters and enqueues features -> merge -> filter on `stream`, reading the frame's accumulators

@@ -30,5 +30,9 @@ struct DisplayArgs {
 };
 // One kernel: per channel the number of thresholds <= the mean, & 255; deferred pixels go to the list with zero bytes.
 hipError_t launch_display(const DisplayArgs &args, hipStream_t stream);
+// The same with grading (pt_display_graded.hip): per channel g = curve(mean * *exposure) is what is looked up and what decides
+// whether a pixel is deferred; a deferred entry still carries the ungraded mean.  `curve` is a PT_CURVE_* (pt_grade.hpp), `exposure`
+// a device scalar written earlier on `stream`.
+hipError_t launch_display_graded(const DisplayArgs &args, int curve, const float *exposure, hipStream_t stream);
 
 }  // namespace pt

@@ -1,6 +1,7 @@
 // Host side of the device-resident display path (include/pt_hip.h: pt_display_*): the threshold table made from the host's own
 // tone map, the chain features -> temporal merge -> a-trous -> (upsample ->) bytes on the stream of the session it displays, and the few
-// pixels the kernel leaves to the host.
+// pixels the kernel leaves to the host.  With grading (pt_display_present_graded): the meter and the exposure kernel before the
+// display kernel, the exposure in a device scalar, and deferred pixels finished through pt_grade.hpp.
 #include "pt_capi_internal.hpp"
 
 #include <algorithm>
@@ -9,6 +10,7 @@
 
 #include "pt_display.hpp"
 #include "pt_display_table.hpp"
+#include "pt_meter.hpp"
 
 using ptc::fail;
 using ptc::guarded;
@@ -48,15 +50,33 @@ void finish_on_host(const std::vector<pt::DisplayDeferred> &list, float gamma, u
         bgr[3 * p + 2] = ptc::quantize_value(ptc::tonemap_value(d.mean[0], gamma));
     }
 }
+// The same for a graded image: the list carries the ungraded mean, the grade is the host chain's own (pt_grade.hpp).
+void finish_on_host_graded(const std::vector<pt::DisplayDeferred> &list, float gamma, int curve, float e, uint8_t *bgr) {
+    for (const pt::DisplayDeferred &d : list) {
+        const size_t p = static_cast<size_t>(d.pixel);
+        for (int k = 0; k < 3; ++k)
+            bgr[3 * p + k] = ptc::quantize_value(ptc::tonemap_value(pt::grade_value(curve, d.mean[2 - k], e), gamma));
+    }
+}
+
+// What a graded present is asked for: the checked parameters, and the display's previous metered exposure.
+struct GradeRequest {
+    ptc::GradeSetup setup;
+    bool has_prev = false;
+    float e_prev = 0.0f;
+};
 
 // ---- what one image needs on its device -------------------------------------------------------------------------------
 // The table of the gamma used last, the output bytes, the deferred list and its length.
 struct DisplayDevice {
+    static constexpr size_t kExposureAt = (4 * pt::kMeterEntries + 15) / 16 * 16, kGradeBytes = kExposureAt + sizeof(pt::ExposureOut);
     size_t n = 0;
     ptc::DeviceBuffer d_table, d_out;
     float *table = nullptr, *band_lo = nullptr, *band_hi = nullptr;
     uint32_t *bgr = nullptr, *n_deferred = nullptr;
     pt::DisplayDeferred *deferred = nullptr;
+    uint32_t *hist = nullptr;               // grading: the meter's histogram and, behind it, what the exposure kernel writes --
+    pt::ExposureOut *exposure = nullptr;    // cleared together on the stream of every graded present
     std::shared_ptr<const DisplayTable> host;   // what d_table holds
     size_t band_room = 0;
 
@@ -64,8 +84,11 @@ struct DisplayDevice {
         n = pixels;
         ptc::PlaneLayout l;
         const size_t o_bgr = l.add((n + 3) / 4 * 12), o_list = l.add(16 * n), o_len = l.add(4);
+        const size_t o_grade = l.add(kGradeBytes);
         const int rc = d_out.alloc(l, what);
         if (rc != PT_OK) return rc;
+        hist = d_out.at<uint32_t>(o_grade);
+        exposure = d_out.at<pt::ExposureOut>(o_grade + kExposureAt);
         bgr = d_out.at<uint32_t>(o_bgr);
         deferred = d_out.at<pt::DisplayDeferred>(o_list);
         n_deferred = d_out.at<uint32_t>(o_len);
@@ -94,8 +117,9 @@ struct DisplayDevice {
         host = t;
         return PT_OK;
     }
-    // Zero the list's length and launch the kernel on `stream`.
-    int enqueue(const float *rgb, const int32_t *count, bool divide, hipStream_t stream) {
+    // Zero the list's length and launch the kernel on `stream`; with `grade`, the exposure first -- metered from the image the
+    // kernel is about to read, or the manual one written into the device scalar -- and then the graded kernel.
+    int enqueue(const float *rgb, const int32_t *count, bool divide, hipStream_t stream, const GradeRequest *grade = nullptr) {
         pt::DisplayArgs a;
         a.n = static_cast<int>(n);
         a.divide = divide ? 1 : 0;
@@ -106,12 +130,34 @@ struct DisplayDevice {
         a.band_lo = band_lo; a.band_hi = band_hi;
         a.bgr = bgr; a.deferred = deferred; a.n_deferred = n_deferred;
         PT_HIP_TRY(hipMemsetAsync(n_deferred, 0, 4, stream));
-        PT_HIP_TRY(pt::launch_display(a, stream));
+        if (!grade) {
+            PT_HIP_TRY(pt::launch_display(a, stream));
+            return PT_OK;
+        }
+        PT_HIP_TRY(hipMemsetAsync(hist, 0, kGradeBytes, stream));
+        if (grade->setup.automatic) {
+            pt::MeterArgs m;
+            m.n = a.n; m.divide = a.divide; m.rgb = rgb; m.count = count; m.hist = hist;
+            PT_HIP_TRY(pt::launch_meter(m, stream));
+            PT_HIP_TRY(pt::launch_exposure(hist, grade->setup.rule, grade->has_prev, grade->e_prev, exposure, stream));
+        } else {
+            uint32_t bits;
+            std::memcpy(&bits, &grade->setup.exposure, sizeof bits);
+            PT_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&exposure->exposure), static_cast<int>(bits), 1, stream));
+        }
+        PT_HIP_TRY(pt::launch_display_graded(a, grade->setup.curve, &exposure->exposure, stream));
         return PT_OK;
     }
     // The kernel has finished: 3 bytes per pixel and the deferred list come to the host, which finishes the list's pixels.
-    int collect(float gamma, uint8_t *out, int32_t *n_deferred_out) {
+    int collect(float gamma, uint8_t *out, int32_t *n_deferred_out, const GradeRequest *grade = nullptr, pt_grade_info *used = nullptr) {
         PT_HIP_TRY(hipMemcpy(out, bgr, 3 * n, hipMemcpyDeviceToHost));
+        if (grade) {
+            pt::ExposureOut o;
+            PT_HIP_TRY(hipMemcpy(&o, exposure, sizeof o, hipMemcpyDeviceToHost));
+            used->exposure = o.exposure;
+            used->target = grade->setup.automatic ? o.target : o.exposure;
+            used->metered = o.metered; used->dark = o.dark;
+        }
         uint32_t len = 0;
         PT_HIP_TRY(hipMemcpy(&len, n_deferred, 4, hipMemcpyDeviceToHost));
         if (len > n) return fail(PT_ERR_HIP, "display: the deferred list is longer than the image");
@@ -120,7 +166,8 @@ struct DisplayDevice {
             PT_HIP_TRY(hipMemcpy(list.data(), deferred, sizeof(pt::DisplayDeferred) * len, hipMemcpyDeviceToHost));
             for (const pt::DisplayDeferred &d : list)
                 if (d.pixel < 0 || static_cast<size_t>(d.pixel) >= n) return fail(PT_ERR_HIP, "display: a deferred pixel lies outside the image");
-            finish_on_host(list, gamma, out);
+            if (grade) finish_on_host_graded(list, gamma, grade->setup.curve, used->exposure, out);
+            else finish_on_host(list, gamma, out);
         }
         *n_deferred_out = static_cast<int32_t>(len);
         return PT_OK;
@@ -163,6 +210,8 @@ struct pt_display {
     int32_t *up_hit = nullptr, *up_count = nullptr;
     void *up_a = nullptr, *up_b = nullptr, *up_c = nullptr;
     ptc::DeviceEvent ev0, ev1;
+    bool has_exposure = false;       // the e of the last metered present (pt_display_present_graded), until a reset
+    float exposure = 0.0f;
     ~pt_display() {
         (void)hipSetDevice(scene->device);
         pt_temporal_destroy(history);
@@ -209,10 +258,14 @@ int ensure_scaled(pt_display *d, int32_t s) {
 }
 
 // `u` = NULL: pt_display_present.  Else the scaled present: the same chain at the display's size, then the upsample to s times it.
-int display_present_impl(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, bool scaled, uint8_t *bgr, pt_display_info *info) {
-    if (!d || !p || !bgr || (scaled && !u)) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or image");
+// `g` = NULL: no grading.  Else pt_display_present_graded: the exposure and the graded kernel in place of the display kernel.
+int display_present_impl(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, bool scaled, uint8_t *bgr, pt_display_info *info,
+                         const pt_grade_params *g = nullptr, bool graded = false, pt_grade_info *grade_info = nullptr) {
+    if (!d || !p || !bgr || (scaled && !u) || (graded && !g)) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or image");
     int rc = check_gamma(p->gamma);
     if (rc != PT_OK) return rc;
+    GradeRequest grade;
+    if (graded && (rc = ptc::grade_params_check(g, grade.setup)) != PT_OK) return rc;
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -222,6 +275,7 @@ int display_present_impl(pt_display *d, const pt_display_params *p, const pt_ups
     if ((rc = ptc::denoise_params_to_args(&p->denoise, da)) != PT_OK) return rc;
     const bool temporal = p->temporal != 0, filter = da.levels > 0;
     std::lock_guard<std::mutex> present_lock(d->mutex);
+    grade.has_prev = d->has_exposure; grade.e_prev = d->exposure;
     const std::shared_ptr<const DisplayTable> table = display_table(p->gamma);
     const size_t n = d->n;
     // the accumulators, where they lie, and the stream their slices were enqueued on: the chain goes behind them
@@ -305,26 +359,37 @@ int display_present_impl(pt_display *d, const pt_display_params *p, const pt_ups
             rgb = d->up_mean; count = d->up_count;
             divide = false;
         }
-        if ((rc = dev.enqueue(rgb, count, divide, stream)) != PT_OK) return rc;
+        if ((rc = dev.enqueue(rgb, count, divide, stream, graded ? &grade : nullptr)) != PT_OK) return rc;
         PT_HIP_TRY(hipEventRecord(d->ev1.get(), stream));
     }
-    // (an error return from here on leaves the history as it was: its records were only read)
+    // (an error return from here on leaves the history and the metered exposure as they were: they were only read)
     PT_HIP_TRY(hipEventSynchronize(d->ev1.get()));
     float ms = 0.0f;
     PT_HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));
     int32_t n_deferred = 0;
-    if ((rc = dev.collect(p->gamma, bgr, &n_deferred)) != PT_OK) return rc;
+    pt_grade_info used{};
+    if ((rc = dev.collect(p->gamma, bgr, &n_deferred, graded ? &grade : nullptr, &used)) != PT_OK) return rc;
     if (temporal) ptc::temporal_commit(d->history);
+    if (graded && grade.setup.automatic) {
+        d->has_exposure = true;
+        d->exposure = used.exposure;
+    }
+    if (graded && grade_info) *grade_info = used;
     dev.fill(info, ms, n_deferred);
     return PT_OK;
 }
 
+// `g` = NULL: pt_display_bytes_host.  Else pt_display_bytes_graded_host.
 int display_bytes_host_impl(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
-                            uint8_t *bgr, pt_display_info *info) {
-    if (width <= 0 || height <= 0 || !mean_rgb || !count || !bgr) return fail(PT_ERR_INVALID_ARGUMENT, "null buffer or empty image");
+                            uint8_t *bgr, pt_display_info *info, const pt_grade_params *g = nullptr, bool graded = false, bool has_prev = false,
+                            float e_prev = 0.0f, pt_grade_info *grade_info = nullptr) {
+    if (width <= 0 || height <= 0 || !mean_rgb || !count || !bgr || (graded && !g)) return fail(PT_ERR_INVALID_ARGUMENT, "null buffer or empty image");
     if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "image too large");
     int rc = check_gamma(gamma);
     if (rc != PT_OK) return rc;
+    GradeRequest grade;
+    if (graded && (rc = ptc::grade_params_check(g, grade.setup)) != PT_OK) return rc;
+    grade.has_prev = has_prev; grade.e_prev = e_prev;
     if ((rc = ptc::use_device(device, "display")) != PT_OK) return rc;
     const size_t n = static_cast<size_t>(width) * height;
     const std::shared_ptr<const DisplayTable> table = display_table(gamma);
@@ -340,13 +405,15 @@ int display_bytes_host_impl(int device, int32_t width, int32_t height, const flo
     PT_HIP_TRY(hipMemcpy(d_in.at<void>(o_mean), mean_rgb, 12 * n, hipMemcpyHostToDevice));
     PT_HIP_TRY(hipMemcpy(d_in.at<void>(o_cnt), count, 4 * n, hipMemcpyHostToDevice));
     PT_HIP_TRY(hipEventRecord(ev0.get(), nullptr));
-    if ((rc = dev.enqueue(d_in.at<float>(o_mean), d_in.at<int32_t>(o_cnt), false, nullptr)) != PT_OK) return rc;
+    if ((rc = dev.enqueue(d_in.at<float>(o_mean), d_in.at<int32_t>(o_cnt), false, nullptr, graded ? &grade : nullptr)) != PT_OK) return rc;
     PT_HIP_TRY(hipEventRecord(ev1.get(), nullptr));
     PT_HIP_TRY(hipEventSynchronize(ev1.get()));
     float ms = 0.0f;
     PT_HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
     int32_t n_deferred = 0;
-    if ((rc = dev.collect(gamma, bgr, &n_deferred)) != PT_OK) return rc;
+    pt_grade_info used{};
+    if ((rc = dev.collect(gamma, bgr, &n_deferred, graded ? &grade : nullptr, &used)) != PT_OK) return rc;
+    if (graded && grade_info) *grade_info = used;
     dev.fill(info, ms, n_deferred);
     return PT_OK;
 }
@@ -412,11 +479,18 @@ int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const p
     return guarded([&] { return display_present_impl(d, p, u, true, bgr, info); });
 }
 
+int pt_display_present_graded(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g, uint8_t *bgr,
+                              pt_display_info *info, pt_grade_info *grade_info) {
+    return guarded([&] { return display_present_impl(d, p, u, u != nullptr, bgr, info, g, true, grade_info); });
+}
+
 int pt_display_reset(pt_display *d) {
     return guarded([&] {
         if (!d) return fail(PT_ERR_INVALID_ARGUMENT, "null handle");
         std::lock_guard<std::mutex> lock(d->mutex);
-        return d->history ? pt_temporal_reset(d->history) : static_cast<int>(PT_OK);
+        const int rc = d->history ? pt_temporal_reset(d->history) : static_cast<int>(PT_OK);
+        if (rc == PT_OK) d->has_exposure = false;   // the next metered present is a first one
+        return rc;
     });
 }
 
@@ -427,6 +501,14 @@ void pt_display_destroy(pt_display *d) {
 int pt_display_bytes_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
                           uint8_t *bgr, pt_display_info *info) {
     return guarded([&] { return display_bytes_host_impl(device, width, height, mean_rgb, count, gamma, bgr, info); });
+}
+
+int pt_display_bytes_graded_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
+                                 const pt_grade_params *g, int32_t has_prev, float e_prev, uint8_t *bgr, pt_display_info *info,
+                                 pt_grade_info *grade_info) {
+    return guarded([&] {
+        return display_bytes_host_impl(device, width, height, mean_rgb, count, gamma, bgr, info, g, true, has_prev != 0, e_prev, grade_info);
+    });
 }
 
 int pt_display_table(float gamma, int32_t *levels, float *thresholds, float *doubt_lo, float *doubt_hi) {

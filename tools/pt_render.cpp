@@ -59,6 +59,14 @@
 // in the file name are those of the low-resolution accumulators; previews (-UPDATE) show the traced frame at its own size.  With
 // -DEVICE_RESOLVE 1 the chain runs on the device (pt_display_present_scaled); the files are byte-identical either way.  With
 // -RENDER_SCALE 1 nothing changes.
+// Display grading (pt_grade_host, pt_display_present_graded, not in the reference): -TONE reference|clamp|reinhard|aces (default
+// reference: the reference's wrapping conversion) applies a tone curve and -EXPOSURE <stops> (default 0) an exposure e = 2^stops to
+// the linear mean before the tone map; -AUTO_EXPOSURE 1 meters e from the image instead (a luminance histogram on the device),
+// with -KEY <the luminance the percentile is brought to, default 0.18>, -PERCENTILE <1 .. 100, default 50> and -ADAPT <rate, default
+// 1: no smoothing> -- in a sequence frame i starts from frame i - 1's exposure.  The order is ... -> linear mean -> meter -> grade ->
+// tone map -> -GAUSS / -MEDIAN -> quantize; previews (-UPDATE) stay ungraded.  It works on the host path and with
+// -DEVICE_RESOLVE 1, with byte-identical files, and with -RENDER_SCALE, -DENOISE, -TEMPORAL and -FRAMES.  Without any of these
+// flags nothing changes.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -98,6 +106,10 @@ struct Options {   // defaults: config.h:16-29
     std::string eye_end, lookat_end;   // -EYE_END / -LOOKAT_END as given ("" = the start value)
     int device_resolve = 0;        // -DEVICE_RESOLVE: 1 = the images' bytes are made on the device (pt_display_*)
     int render_scale = 1;          // -RENDER_SCALE: the frame is traced at (W / s) x (H / s) and upsampled to W x H
+    std::string tone = "reference";   // -TONE
+    bool grading = false;          // any of -TONE / -EXPOSURE / -AUTO_EXPOSURE given
+    float exposure_stops = 0.0f, key = 0.0f, adapt = 0.0f;   // -EXPOSURE, -KEY, -ADAPT (0 = the library's default)
+    int auto_exposure = 0, percentile = 0;                   // -AUTO_EXPOSURE, -PERCENTILE
 };
 
 long long now_ms() {
@@ -152,6 +164,12 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-LOOKAT_END") o.lookat_end = v;
         if (f == "-DEVICE_RESOLVE") o.device_resolve = std::atoi(v);
         if (f == "-RENDER_SCALE") o.render_scale = std::atoi(v);
+        if (f == "-TONE") { o.tone = v; o.grading = true; }
+        if (f == "-EXPOSURE") { o.exposure_stops = static_cast<float>(std::atof(v)); o.grading = true; }
+        if (f == "-AUTO_EXPOSURE") { o.auto_exposure = std::atoi(v); o.grading = true; }
+        if (f == "-KEY") o.key = static_cast<float>(std::atof(v));
+        if (f == "-PERCENTILE") o.percentile = std::atoi(v);
+        if (f == "-ADAPT") o.adapt = static_cast<float>(std::atof(v));
     }
 }
 
@@ -268,6 +286,26 @@ int main(int argc, char **argv) {
     if (device_resolve && !(std::isfinite(o.gamma_correction) && o.gamma_correction > 0.0f)) {
         std::cerr << "pt_render: -DEVICE_RESOLVE is ignored: it needs a finite -GAMMA > 0" << std::endl;
         device_resolve = false;
+    }
+    // -TONE / -EXPOSURE / -AUTO_EXPOSURE: what every graded image is asked for; the library checks it (no device needed)
+    const bool grading = o.grading;
+    pt_grade_params grade;
+    std::memset(&grade, 0, sizeof grade);
+    if (grading) {
+        const char *names[4] = {"reference", "clamp", "reinhard", "aces"};
+        grade.curve = -1;
+        for (int k = 0; k < 4; ++k)
+            if (o.tone == names[k]) grade.curve = k;
+        grade.exposure = std::exp2f(o.exposure_stops);
+        grade.auto_exposure = o.auto_exposure != 0;
+        grade.percentile = o.percentile; grade.key = o.key; grade.rate = o.adapt;
+        const uint32_t empty[PT_METER_ENTRIES] = {0};
+        float e = 0, target = 0;
+        if (pt_exposure_from_histogram(empty, &grade, 0, 0.0f, &e, &target) != PT_OK) {
+            std::cerr << "pt_render: -TONE takes reference, clamp, reinhard or aces; -EXPOSURE stops; -KEY, -ADAPT >= 0; -PERCENTILE 1 .. 100 ("
+                      << pt_last_error() << ")" << std::endl;
+            return 2;
+        }
     }
     const unsigned seed = o.seed < 0 ? static_cast<unsigned>(std::time(nullptr)) : static_cast<unsigned>(o.seed);   // config.h:101-104
 
@@ -423,11 +461,47 @@ int main(int argc, char **argv) {
     show.denoise.levels = o.denoise; show.denoise.sigma_luminance = o.dn_sigma_l; show.denoise.sigma_plane = o.dn_sigma_p;
     if (device_resolve && pt_display_create_frame(frame, o.eps, &display) != PT_OK) return die("pt_render");
 
+    std::vector<uint8_t> out_bgr;   // -RENDER_SCALE s > 1: the written image
+    if (scale > 1) out_bgr.resize(3 * static_cast<size_t>(o.width) * o.height);
+
+    // grading on the host path: linear mean and count -> meter and exposure (if automatic; a sequence's frame starts from the
+    // previous frame's) -> grade -> tone map -> the reference's filters -> set_pixel
+    bool has_exposure = false;
+    float last_exposure = 0.0f;
+    auto graded_to_bytes = [&](int w, int h, const float *mean, const int32_t *cnt, uint8_t *out) {
+        float e = grade.exposure, target = 0.0f;
+        if (grade.auto_exposure) {
+            uint32_t hist[PT_METER_ENTRIES];
+            if (pt_meter_host(devices[0], w, h, mean, cnt, hist, nullptr) != PT_OK ||
+                pt_exposure_from_histogram(hist, &grade, has_exposure ? 1 : 0, last_exposure, &e, &target) != PT_OK)
+                return false;
+            has_exposure = true;
+            last_exposure = e;
+        }
+        std::vector<float> rgb(3 * static_cast<size_t>(w) * h);
+        if (pt_grade_host(w, h, mean, cnt, e, grade.curve, rgb.data()) != PT_OK) return false;
+        pt_tonemap(w, h, rgb.data(), cnt, o.gamma_correction, rgb.data());
+        if ((o.gauss || o.median) && pt_post_filter_host(devices[0], w, h, rgb.data(), o.gauss, o.median) != PT_OK) return false;
+        return pt_quantize(w, h, rgb.data(), cnt, out) == PT_OK;
+    };
+    // ... from accumulators: their mean is sum / n
+    auto graded_from_accumulators = [&](const float *fs, const float *fs2, const int32_t *fc, uint8_t *out) {
+        std::vector<float> mean(3 * px);
+        std::vector<int32_t> cnt(px);
+        pt_denoise_params none;
+        std::memset(&none, 0, sizeof none);
+        return pt_denoise_host(devices[0], tw, th, fs, fs2, fc, nullptr, nullptr, nullptr, nullptr, &none, mean.data(), cnt.data(), nullptr) == PT_OK &&
+               graded_to_bytes(tw, th, mean.data(), cnt.data(), out);
+    };
+    // the device path's present: plain, scaled, or either with grading
+    auto present = [&](pt_display_info *info) {
+        if (grading) return pt_display_present_graded(display, &show, scale > 1 ? &upsample : nullptr, &grade, scale > 1 ? out_bgr.data() : bgr.data(), info, nullptr);
+        return scale > 1 ? pt_display_present_scaled(display, &show, &upsample, out_bgr.data(), info) : pt_display_present(display, &show, bgr.data(), info);
+    };
+
     // -RENDER_SCALE s > 1: the written image, and the host chain that makes it from the traced frame's mean and count --
     // features at the written size from `view` (the scene on the first device, with the frame's camera), the upsample, the
     // tone map, the reference's filters and set_pixel
-    std::vector<uint8_t> out_bgr;
-    if (scale > 1) out_bgr.resize(3 * static_cast<size_t>(o.width) * o.height);
     auto upsample_to_output = [&](pt_scene *view, const float *mean_lo, const int32_t *count_lo) {
         const size_t opx = static_cast<size_t>(o.width) * o.height;
         std::vector<float> pos(3 * opx), nrm(3 * opx), alb(3 * opx), mean(3 * opx), rgb(3 * opx);
@@ -438,6 +512,7 @@ int main(int argc, char **argv) {
             pt_upsample_host(devices[0], o.width, o.height, mean_lo, count_lo, pos.data(), nrm.data(), alb.data(), hit.data(), &upsample, mean.data(),
                              count_out.data(), nullptr) != PT_OK)
             return false;
+        if (grading) return graded_to_bytes(o.width, o.height, mean.data(), count_out.data(), out_bgr.data());
         pt_tonemap(o.width, o.height, mean.data(), count_out.data(), o.gamma_correction, rgb.data());
         if ((o.gauss || o.median) && pt_post_filter_host(devices[0], o.width, o.height, rgb.data(), o.gauss, o.median) != PT_OK) return false;
         return pt_quantize(o.width, o.height, rgb.data(), count_out.data(), out_bgr.data()) == PT_OK;
@@ -492,9 +567,7 @@ int main(int argc, char **argv) {
                     if (read_back() != PT_OK) return die("pt_render");
                     pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
                 }
-                if (scale > 1 ? pt_display_present_scaled(display, &show, &upsample, out_bgr.data(), nullptr) != PT_OK
-                              : pt_display_present(display, &show, bgr.data(), nullptr) != PT_OK)
-                    return die("pt_render");
+                if (present(nullptr) != PT_OK) return die("pt_render");
             } else {
                 if (read_back() != PT_OK) return die("pt_render");
                 pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);   // the statistics of the frame as rendered
@@ -519,6 +592,10 @@ int main(int argc, char **argv) {
                                                           mean_count.data(), nullptr) != PT_OK)
                         return die("pt_render");
                     if (!upsample_to_output(view, mean.data(), mean_count.data())) return die("pt_render");
+                } else if (grading) {
+                    // the mean the filter made, or sum / n of the frame as rendered or merged; then meter, grade, tone map
+                    if (o.denoise > 0 ? !graded_to_bytes(tw, th, mean.data(), mean_count.data(), bgr.data()) : !graded_from_accumulators(fs, fs2, fc, bgr.data()))
+                        return die("pt_render");
                 } else if (o.denoise > 0) {
                     pt_tonemap(tw, th, mean.data(), mean_count.data(), o.gamma_correction, rgb.data());
                     if ((o.gauss || o.median) && pt_post_filter_host(devices[0], tw, th, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
@@ -625,9 +702,7 @@ int main(int argc, char **argv) {
         pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
         const clk::time_point f1 = clk::now();
         pt_display_info shown;
-        if (scale > 1 ? pt_display_present_scaled(display, &show, &upsample, out_bgr.data(), &shown) != PT_OK
-                      : pt_display_present(display, &show, bgr.data(), &shown) != PT_OK)
-            return die("pt_render");
+        if (present(&shown) != PT_OK) return die("pt_render");
         if (o.denoise > 0) {
             denoise_s = secs(f1, clk::now());
             denoise_kernel_ms = shown.kernel_ms;
@@ -675,9 +750,16 @@ int main(int argc, char **argv) {
             return die("pt_render");
         features_s = secs(f0, f1);
         denoise_s = secs(f1, clk::now());
-        pt_tonemap(tw, th, mean.data(), count_out.data(), o.gamma_correction, rgb.data());
-        if ((o.gauss || o.median) && pt_post_filter_host(devices[0], tw, th, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
-        pt_quantize(tw, th, rgb.data(), count_out.data(), bgr.data());
+        if (grading) {
+            if (!graded_to_bytes(tw, th, mean.data(), count_out.data(), bgr.data())) return die("pt_render");
+        } else {
+            pt_tonemap(tw, th, mean.data(), count_out.data(), o.gamma_correction, rgb.data());
+            if ((o.gauss || o.median) && pt_post_filter_host(devices[0], tw, th, rgb.data(), o.gauss, o.median) != PT_OK) return die("pt_render");
+            pt_quantize(tw, th, rgb.data(), count_out.data(), bgr.data());
+        }
+    } else if (grading) {   // the statistics of the frame as rendered; then sum / n, meter, grade, tone map, filters, set_pixel
+        pt_resolve(tw, th, sum, sum2, count, o.gamma_correction, bgr.data(), disp);
+        if (!graded_from_accumulators(sum, sum2, count, bgr.data())) return die("pt_render");
     } else if (o.gauss || o.median) {   // main.cpp:187-201: filters act on the tonemapped float image, then set_pixel
         std::vector<float> rgb(3 * px);
         pt_resolve_float(tw, th, sum, sum2, count, o.gamma_correction, rgb.data(), disp);
