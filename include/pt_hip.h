@@ -685,6 +685,72 @@ int pt_display_bytes_graded_host(int device, int32_t width, int32_t height, cons
                                  float gamma, const pt_grade_params *g, int32_t has_prev, float e_prev, uint8_t *bgr,
                                  pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
 
+/* ---- bloom: bright-pass glare pyramid before the tone curve ------------------------------------------------ */
+
+/* The saturating curves map everything far above 1 to flat white with a hard edge.  Bloom is one stage BEFORE the grade, mean ->
+ * mean, on the linear ungraded mean at the output size: the light above a threshold is spread over its neighbourhood and added
+ * back, so the picture says how much brighter than white the light is.  It runs after the last image stage and after the meter
+ * and the exposure, and before the grade.
+ *
+ * The arithmetic, exactly: every line below is ONE correctly rounded float operation in the order written; nothing is fused.
+ * c(i, n) = min(max(i, 0), n - 1).
+ *
+ * Inputs.  m = the pixel's linear mean (a chain row that ends in sums: m = sum / (float)n, as the display chain divides), its
+ * count, the exposure e (manual or from the meter), and the parameters threshold T, strength S, levels L.
+ *
+ * Bright pass, at W x H.  t = T / e.  A pixel with count == 0 contributes B = 0.  Otherwise
+ *   l = ((0.2126 m_r) + (0.7152 m_g)) + (0.0722 m_b)          (the meter's luminance)
+ *   if !(l > t) or !(l <= FLT_MAX):  B = 0 in all channels
+ *   else  s = (l - t) / l,  B_c = m_c * s.
+ *
+ * Down, k = 1 .. L.  D_0 = B;  w_0 = W, h_0 = H, w_k = (w_{k-1} + 1) >> 1, h_k likewise.
+ *   horizontal, at the decimated columns only, for X < w_k and y < h_{k-1}:  p_j = D_{k-1}(c(2X + j, w_{k-1}), y), j = -1 .. 2,
+ *     G(X, y) = ((p_0 + p_1) * 0.375) + ((p_{-1} + p_2) * 0.125)
+ *   vertical, the same formula on G with rows c(2Y + j, h_{k-1}), gives D_k(X, Y).
+ * The taps are (1 3 3 1)/8, centred between samples 2X and 2X + 1, so that the up pass below is aligned with it.
+ *
+ * Up, k = L-1 .. 0.  U_L = D_L;  V_k = up2(U_{k+1}) at w_k x h_k:
+ *   horizontal first, with X = x >> 1:
+ *     x even:  g = (U(c(X - 1, w_{k+1}), .) * 0.25) + (U(X, .) * 0.75)
+ *     x odd:   g = (U(X, .) * 0.75) + (U(c(X + 1, w_{k+1}), .) * 0.25)
+ *   then the same rule vertically, on g.
+ *   k >= 1:  U_k = D_k + V_k.      k = 0:  A = V_0  (the pixel's own unblurred bright part is already in m).
+ *
+ * Output.  wgt = S / (float)L, one division on the host, passed by value.  A pixel with count != 0 gets
+ *   out_c = m_c + (A_c * wgt);
+ * the others keep their value, as pt_grade_host leaves them.  NaN, negative and infinite channels get no special case beyond the
+ * two luminance tests: whatever comes out goes on (a NaN or infinite channel of a pixel whose luminance passes both tests spreads
+ * over the 2^L-neighbourhood its taps reach; a NaN's payload is not defined).
+ *
+ * Parameters; a zeroed struct means no bloom:
+ *   strength    0: the stage is not run (the bytes are those of pt_display_present_graded)    (negative or non-finite: invalid)
+ *   threshold   0 = 1                                                                        (negative or non-finite: invalid)
+ *   levels      0 = 5; else 1 .. PT_BLOOM_MAX_LEVELS                                         (outside: invalid)
+ * Any image size from 1 x 1 is valid. */
+#define PT_BLOOM_MAX_LEVELS 8
+typedef struct pt_bloom_params {
+    float threshold;
+    float strength;
+    int32_t levels;
+} pt_bloom_params;
+
+/* The bloom kernels alone, on a host image: out_rgb (may be mean_rgb) = the output above for (mean_rgb, count), made on HIP device
+ * `device`; kernel_ms (may be NULL) = HIP-event time of the 2 L kernels.  Buffers, sizes, `exposure` (finite and > 0; 0 is NOT a
+ * default here, as in pt_grade_host) and *b are checked BEFORE the device is looked at; PT_ERR_NO_DEVICE afterwards if that is
+ * not a usable device (there is no CPU fallback).  With strength == 0 it copies. */
+int pt_bloom_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure,
+                  const pt_bloom_params *b, float *out_rgb, float *kernel_ms);
+/* pt_display_present_graded with bloom: the same chain with the bloom kernels between the exposure kernel and the display kernel,
+ * on the session's stream with no host synchronisation inside; the bright pass reads e from the device scalar the display kernel
+ * reads.  The bytes are DEFINED by the host chain and equal it bit for bit: the row of the tables above up to the linear mean and
+ * count, then, if automatic, pt_meter_host -> pt_exposure_from_histogram on the mean BEFORE bloom, then
+ * pt_bloom_host(e) -> pt_grade_host(e, curve) -> pt_tonemap -> pt_quantize.  *b is checked with *g, before anything is enqueued; a
+ * failed present leaves the history and the previous exposure as they were.  A deferred pixel carries the bloomed ungraded mean
+ * the display kernel read, and the host grades that.  With strength == 0 the call is pt_display_present_graded. */
+int pt_display_present_bloom(pt_display *d, const pt_display_params *p, const pt_upsample_params *u /* NULL: not scaled */,
+                             const pt_grade_params *g, const pt_bloom_params *b, uint8_t *bgr, pt_display_info *info /* may be NULL */,
+                             pt_grade_info *grade_info /* may be NULL */);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

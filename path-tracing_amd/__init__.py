@@ -46,7 +46,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_display_bytes_host", "pt_display_table",
                "pt_upsample_host", "pt_display_present_scaled",
                "pt_grade_host", "pt_meter_host", "pt_exposure_from_histogram", "pt_display_present_graded",
-               "pt_display_bytes_graded_host"]
+               "pt_display_bytes_graded_host",
+               "pt_bloom_host", "pt_display_present_bloom"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -177,6 +178,21 @@ def _grade_params(grade):
                            grade.get("percentile", 0), grade.get("key", 0.0), grade.get("e_min", 0.0), grade.get("e_max", 0.0),
                            grade.get("rate", 0.0))
     return grade
+
+
+BLOOM_MAX_LEVELS = 8
+
+
+class BloomParams(C.Structure):
+    """pt_bloom_params: a zeroed struct is no bloom (strength 0); threshold 0 = 1, levels 0 = 5 (1 .. 8)."""
+    _fields_ = [("threshold", C.c_float), ("strength", C.c_float), ("levels", C.c_int32)]
+
+
+def _bloom_params(bloom):
+    """A BloomParams, or a dict of its fields ({"strength": 0.5}) -> a BloomParams."""
+    if isinstance(bloom, dict):
+        return BloomParams(bloom.get("threshold", 0.0), bloom.get("strength", 0.0), bloom.get("levels", 0))
+    return bloom
 
 
 def _lens_arg(radius, focus_distance):
@@ -326,6 +342,9 @@ def load_library(path):
                                             C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     L.pt_display_bytes_graded_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(GradeParams), C.c_int32, C.c_float, bp,
                                                C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_bloom_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(BloomParams), fp, fp]
+    L.pt_display_present_bloom.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
+                                           bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -659,14 +678,16 @@ class Display:
         create = self._L.pt_display_create_frame if isinstance(session_or_frame, Frame) else self._L.pt_display_create
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
-    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None):
+    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
         parameters.  Returns (bgr uint8 [H, W, 3], info dict).
         `upsample`: None, an UpsampleParams, or a dict of pt.upsample's parameters ({"scale": 2}) -- pt_display_present_scaled: the
         image is then scale times the session's size, bgr uint8 [scale * H, scale * W, 3].
         `grade`: None, a GradeParams, or a dict of its fields ({"curve": "aces", "auto_exposure": True}) -- pt_display_present_graded:
-        exposure and a tone curve before the tone map; info then also holds exposure, target, metered, dark."""
+        exposure and a tone curve before the tone map; info then also holds exposure, target, metered, dark.
+        `bloom`: None, a BloomParams, or a dict of its fields ({"strength": 0.5}) -- pt_display_present_bloom: the light above the
+        threshold spread over its neighbourhood before the grade (`grade` None: no grading at all, as a zeroed GradeParams)."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -675,13 +696,18 @@ class Display:
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
         info = DisplayInfo()
-        if grade is not None:
-            gp, ginfo = _grade_params(grade), GradeInfo()
+        if grade is not None or bloom is not None:
+            gp, ginfo = _grade_params(grade) if grade is not None else GradeParams(), GradeInfo()
             up = _upsample_params(upsample) if upsample is not None else None
             k = up.scale if up is not None and 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1
             bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8)
-            _check(self._L.pt_display_present_graded(self._h, C.byref(prm), C.byref(up) if up is not None else None, C.byref(gp),
-                                                     bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info), C.byref(ginfo)), self._L)
+            up_arg, out = C.byref(up) if up is not None else None, bgr.ctypes.data_as(C.POINTER(C.c_uint8))
+            if bloom is not None:
+                bp_ = _bloom_params(bloom)
+                _check(self._L.pt_display_present_bloom(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), out, C.byref(info),
+                                                        C.byref(ginfo)), self._L)
+            else:
+                _check(self._L.pt_display_present_graded(self._h, C.byref(prm), up_arg, C.byref(gp), out, C.byref(info), C.byref(ginfo)), self._L)
             return bgr, dict(info.as_dict(), **ginfo.as_dict())
         if upsample is not None:
             up = _upsample_params(upsample)
@@ -748,6 +774,18 @@ def grade(mean_rgb, count, exposure=1.0, curve=CURVE_REFERENCE, library=None):
     _check(L.pt_grade_host(m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), CURVES[curve] if isinstance(curve, str) else curve,
                            _fp(out)), L)
     return out
+
+
+def bloom(device, mean_rgb, count, exposure=1.0, threshold=1.0, strength=0.5, levels=5, want_ms=False, library=None):
+    """pt_bloom_host: the bloom kernels alone on a host image mean_rgb [H, W, 3] with count [H, W] -- mean + glare * strength / levels,
+    the glare being the light above threshold / exposure spread by a pyramid of `levels` levels; and the kernels' milliseconds as a
+    second value if want_ms."""
+    L = library or lib()
+    m, c = _image_args("bloom", mean_rgb, count)
+    out, ms = np.zeros_like(m), C.c_float()
+    prm = BloomParams(threshold, strength, levels)
+    _check(L.pt_bloom_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), C.byref(prm), _fp(out), C.byref(ms)), L)
+    return (out, ms.value) if want_ms else out
 
 
 def meter(mean_rgb, count, device=0, want_ms=False, library=None):

@@ -1,0 +1,81 @@
+// Host side of bloom (include/pt_hip.h: pt_bloom_host): the parameter check every bloomed entry point shares, and the kernels alone
+// on a host image.  The arithmetic is pt_bloom.hip's; there is no host copy of it (the suite restates the header in numpy).
+#include "pt_capi_internal.hpp"
+
+#include <cmath>
+#include <cstring>
+
+#include "pt_bloom.hpp"
+
+using ptc::fail;
+using ptc::guarded;
+using ptc::hip_fail;
+
+static_assert(PT_BLOOM_MAX_LEVELS == pt::kBloomMaxLevels, "the ABI header states the deepest pyramid");
+
+int ptc::bloom_params_check(const pt_bloom_params *b, BloomSetup &out) {
+    if (!b) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: null params");
+    auto bad = [](float v) { return !std::isfinite(v) || v < 0.0f; };
+    if (bad(b->strength) || bad(b->threshold)) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: strength and threshold must be finite and not negative");
+    if (b->levels < 0 || b->levels > pt::kBloomMaxLevels) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: levels must lie in 1 .. 8 (0 = 5)");
+    BloomSetup s;
+    s.on = b->strength > 0.0f;
+    s.threshold = b->threshold > 0.0f ? b->threshold : 1.0f;
+    s.levels = b->levels > 0 ? b->levels : 5;
+    s.weight = b->strength / static_cast<float>(s.levels);
+    out = s;
+    return PT_OK;
+}
+
+namespace {
+
+int bloom_host_impl(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure, const pt_bloom_params *b,
+                    float *out_rgb, float *kernel_ms) {
+    if (width <= 0 || height <= 0 || !mean_rgb || !count || !out_rgb) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: null buffer or empty image");
+    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: image too large");
+    if (!std::isfinite(exposure) || !(exposure > 0.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: exposure must be finite and > 0");
+    ptc::BloomSetup setup;
+    int rc = ptc::bloom_params_check(b, setup);
+    if (rc != PT_OK) return rc;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if ((rc = ptc::use_device(device, "bloom")) != PT_OK) return rc;
+    const size_t n = static_cast<size_t>(width) * height;
+    if (!setup.on) {
+        if (out_rgb != mean_rgb) std::memmove(out_rgb, mean_rgb, 12 * n);
+        return PT_OK;
+    }
+    ptc::PlaneLayout l;
+    const size_t o_mean = l.add(12 * n), o_cnt = l.add(4 * n), o_e = l.add(4), o_out = l.add(12 * n);
+    const size_t o_pyr = l.add(16 * pt::bloom_pyramid_records(width, height, setup.levels));
+    ptc::DeviceBuffer d;
+    ptc::DeviceEvent ev0, ev1;
+    if ((rc = d.alloc(l, "pt_bloom_host")) != PT_OK || (rc = ev0.create("pt_bloom_host")) != PT_OK || (rc = ev1.create("pt_bloom_host")) != PT_OK) return rc;
+    PT_HIP_TRY(hipMemcpy(d.at<void>(o_mean), mean_rgb, 12 * n, hipMemcpyHostToDevice));
+    PT_HIP_TRY(hipMemcpy(d.at<void>(o_cnt), count, 4 * n, hipMemcpyHostToDevice));
+    PT_HIP_TRY(hipMemcpy(d.at<void>(o_e), &exposure, 4, hipMemcpyHostToDevice));
+    pt::BloomArgs a;
+    a.width = width; a.height = height; a.levels = setup.levels; a.divide = 0;
+    a.rgb = d.at<float>(o_mean); a.count = d.at<int32_t>(o_cnt); a.exposure = d.at<float>(o_e);
+    a.threshold = setup.threshold; a.weight = setup.weight;
+    a.pyramid = d.at<void>(o_pyr); a.out_rgb = d.at<float>(o_out);
+    PT_HIP_TRY(hipEventRecord(ev0.get(), nullptr));
+    PT_HIP_TRY(pt::launch_bloom(a, nullptr));
+    PT_HIP_TRY(hipEventRecord(ev1.get(), nullptr));
+    PT_HIP_TRY(hipEventSynchronize(ev1.get()));
+    float ms = 0.0f;
+    PT_HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+    PT_HIP_TRY(hipMemcpy(out_rgb, a.out_rgb, 12 * n, hipMemcpyDeviceToHost));
+    if (kernel_ms) *kernel_ms = ms;
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pt_bloom_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure, const pt_bloom_params *b,
+                  float *out_rgb, float *kernel_ms) {
+    return guarded([&] { return bloom_host_impl(device, width, height, mean_rgb, count, exposure, b, out_rgb, kernel_ms); });
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // Types shared by the translation units behind the C ABI (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters;
 // pt_frame.cpp: the multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp: the
-// temporal stage; pt_display_capi.cpp: the device-resident display path; pt_grade_capi.cpp: display grading; pt_upsample_capi.cpp: the upsampler; pt_device_mem.hpp: the owners of everything they hold
+// temporal stage; pt_display_capi.cpp: the device-resident display path; pt_grade_capi.cpp: display grading; pt_bloom_capi.cpp: bloom; pt_upsample_capi.cpp: the upsampler; pt_device_mem.hpp: the owners of everything they hold
 // on a device).  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/pt_hip.h"
@@ -173,6 +173,15 @@ struct GradeSetup {
     pt::ExposureRule rule{};
 };
 int grade_params_check(const pt_grade_params *g, GradeSetup &out);
+
+// pt_bloom_params as every entry point checks them (no device is touched), with the defaults filled in (pt_bloom_capi.cpp).
+struct BloomSetup {
+    bool on = false;          // strength > 0: the stage runs
+    float threshold = 1.0f;   // T
+    int levels = 5;           // L
+    float weight = 0.0f;      // strength / (float)L
+};
+int bloom_params_check(const pt_bloom_params *b, BloomSetup &out);
 
 // pt_temporal_push_host in two halves, for a chain whose frame already lies on the device (pt_display_present).
 // temporal_enqueue checks the parameters and enqueues features -> merge -> filter on `stream`, reading the frame's accumulators

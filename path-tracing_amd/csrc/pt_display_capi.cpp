@@ -1,13 +1,15 @@
 // Host side of the device-resident display path (include/pt_hip.h: pt_display_*): the threshold table made from the host's own
 // tone map, the chain features -> temporal merge -> a-trous -> (upsample ->) bytes on the stream of the session it displays, and the few
 // pixels the kernel leaves to the host.  With grading (pt_display_present_graded): the meter and the exposure kernel before the
-// display kernel, the exposure in a device scalar, and deferred pixels finished through pt_grade.hpp.
+// display kernel, the exposure in a device scalar, and deferred pixels finished through pt_grade.hpp.  With bloom
+// (pt_display_present_bloom): the bloom kernels between the exposure and the display kernel, which then reads the bloomed means.
 #include "pt_capi_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
+#include "pt_bloom.hpp"
 #include "pt_display.hpp"
 #include "pt_display_table.hpp"
 #include "pt_meter.hpp"
@@ -64,6 +66,8 @@ struct GradeRequest {
     ptc::GradeSetup setup;
     bool has_prev = false;
     float e_prev = 0.0f;
+    ptc::BloomSetup bloom;   // on: the bloom kernels run between the exposure and the display kernel
+    int32_t width = 0, height = 0;   // of the image the display kernel reads (bloom needs its shape)
 };
 
 // ---- what one image needs on its device -------------------------------------------------------------------------------
@@ -79,9 +83,14 @@ struct DisplayDevice {
     pt::ExposureOut *exposure = nullptr;    // cleared together on the stream of every graded present
     std::shared_ptr<const DisplayTable> host;   // what d_table holds
     size_t band_room = 0;
+    // bloom: the deepest pyramid of the image and the plane of bloomed means, allocated by the first bloomed present
+    ptc::DeviceBuffer d_bloom;
+    void *pyramid = nullptr;
+    float *bloomed = nullptr;
 
     int alloc(size_t pixels, const char *what) {
         n = pixels;
+        d_bloom.reset();   // (of another size's image)
         ptc::PlaneLayout l;
         const size_t o_bgr = l.add((n + 3) / 4 * 12), o_list = l.add(16 * n), o_len = l.add(4);
         const size_t o_grade = l.add(kGradeBytes);
@@ -92,6 +101,15 @@ struct DisplayDevice {
         bgr = d_out.at<uint32_t>(o_bgr);
         deferred = d_out.at<pt::DisplayDeferred>(o_list);
         n_deferred = d_out.at<uint32_t>(o_len);
+        return PT_OK;
+    }
+    int ensure_bloom(int32_t width, int32_t height, const char *what) {
+        if (d_bloom) return PT_OK;
+        ptc::PlaneLayout l;
+        const size_t o_out = l.add(12 * n), o_pyr = l.add(16 * pt::bloom_pyramid_records(width, height, pt::kBloomMaxLevels));
+        const int rc = d_bloom.alloc(l, what);
+        if (rc != PT_OK) return rc;
+        bloomed = d_bloom.at<float>(o_out); pyramid = d_bloom.at<void>(o_pyr);
         return PT_OK;
     }
     // (no kernel of this object is in flight: every call that launches one waits for it)
@@ -144,6 +162,15 @@ struct DisplayDevice {
             uint32_t bits;
             std::memcpy(&bits, &grade->setup.exposure, sizeof bits);
             PT_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&exposure->exposure), static_cast<int>(bits), 1, stream));
+        }
+        if (grade->bloom.on) {   // the display kernel reads m + A * weight, a plane of means, with the chain's count
+            pt::BloomArgs b;
+            b.width = grade->width; b.height = grade->height; b.levels = grade->bloom.levels; b.divide = a.divide;
+            b.rgb = rgb; b.count = count; b.exposure = &exposure->exposure;
+            b.threshold = grade->bloom.threshold; b.weight = grade->bloom.weight;
+            b.pyramid = pyramid; b.out_rgb = bloomed;
+            PT_HIP_TRY(pt::launch_bloom(b, stream));
+            a.rgb = bloomed; a.divide = 0;
         }
         PT_HIP_TRY(pt::launch_display_graded(a, grade->setup.curve, &exposure->exposure, stream));
         return PT_OK;
@@ -259,13 +286,16 @@ int ensure_scaled(pt_display *d, int32_t s) {
 
 // `u` = NULL: pt_display_present.  Else the scaled present: the same chain at the display's size, then the upsample to s times it.
 // `g` = NULL: no grading.  Else pt_display_present_graded: the exposure and the graded kernel in place of the display kernel.
+// `b` (with `g` only): pt_display_present_bloom.
 int display_present_impl(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, bool scaled, uint8_t *bgr, pt_display_info *info,
-                         const pt_grade_params *g = nullptr, bool graded = false, pt_grade_info *grade_info = nullptr) {
-    if (!d || !p || !bgr || (scaled && !u) || (graded && !g)) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or image");
+                         const pt_grade_params *g = nullptr, bool graded = false, pt_grade_info *grade_info = nullptr,
+                         const pt_bloom_params *b = nullptr, bool bloomed = false) {
+    if (!d || !p || !bgr || (scaled && !u) || (graded && !g) || (bloomed && !b)) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or image");
     int rc = check_gamma(p->gamma);
     if (rc != PT_OK) return rc;
     GradeRequest grade;
     if (graded && (rc = ptc::grade_params_check(g, grade.setup)) != PT_OK) return rc;
+    if (bloomed && (rc = ptc::bloom_params_check(b, grade.bloom)) != PT_OK) return rc;
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -294,6 +324,8 @@ int display_present_impl(pt_display *d, const pt_display_params *p, const pt_ups
     DisplayDevice &dev = scaled ? d->dev_up : d->dev;
     if (scaled && (rc = ensure_scaled(d, ua.scale)) != PT_OK) return rc;
     if ((rc = dev.use_table(table, "pt_display_present")) != PT_OK) return rc;
+    grade.width = scaled ? ua.width : d->width; grade.height = scaled ? ua.height : d->height;
+    if (grade.bloom.on && (rc = dev.ensure_bloom(grade.width, grade.height, "pt_display_present_bloom")) != PT_OK) return rc;
     if (temporal && !d->history && (rc = pt_temporal_create(scene, d->width, d->height, d->eps, &d->history)) != PT_OK) return rc;
     if (filter && !temporal && !d->d_filter) {
         ptc::PlaneLayout l;
@@ -482,6 +514,11 @@ int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const p
 int pt_display_present_graded(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g, uint8_t *bgr,
                               pt_display_info *info, pt_grade_info *grade_info) {
     return guarded([&] { return display_present_impl(d, p, u, u != nullptr, bgr, info, g, true, grade_info); });
+}
+
+int pt_display_present_bloom(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
+                             const pt_bloom_params *b, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
+    return guarded([&] { return display_present_impl(d, p, u, u != nullptr, bgr, info, g, true, grade_info, b, true); });
 }
 
 int pt_display_reset(pt_display *d) {

@@ -67,6 +67,12 @@
 // tone map -> -GAUSS / -MEDIAN -> quantize; previews (-UPDATE) stay ungraded.  It works on the host path and with
 // -DEVICE_RESOLVE 1, with byte-identical files, and with -RENDER_SCALE, -DENOISE, -TEMPORAL and -FRAMES.  Without any of these
 // flags nothing changes.
+// Bloom (pt_bloom_host, pt_display_present_bloom, not in the reference): -BLOOM <strength, default 0: off> spreads the light above
+// -BLOOM_THRESHOLD <luminance after exposure, default 1> over its neighbourhood with a pyramid of -BLOOM_LEVELS <1 .. 8, default 5>
+// levels, on the linear mean at the written size: ... -> linear mean -> meter -> bloom -> grade -> tone map -> -GAUSS / -MEDIAN ->
+// quantize (without -TONE / -EXPOSURE / -AUTO_EXPOSURE the grade is the reference's: no curve, e = 1); previews stay unbloomed.
+// It works on the host path and with -DEVICE_RESOLVE 1, with byte-identical files, and with every flag grading works with.
+// Without -BLOOM, or with -BLOOM 0, nothing changes.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -110,6 +116,8 @@ struct Options {   // defaults: config.h:16-29
     bool grading = false;          // any of -TONE / -EXPOSURE / -AUTO_EXPOSURE given
     float exposure_stops = 0.0f, key = 0.0f, adapt = 0.0f;   // -EXPOSURE, -KEY, -ADAPT (0 = the library's default)
     int auto_exposure = 0, percentile = 0;                   // -AUTO_EXPOSURE, -PERCENTILE
+    float bloom = 0.0f, bloom_threshold = 0.0f;              // -BLOOM, -BLOOM_THRESHOLD (0 = the library's default)
+    int bloom_levels = 0;                                    // -BLOOM_LEVELS
 };
 
 long long now_ms() {
@@ -170,6 +178,9 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-KEY") o.key = static_cast<float>(std::atof(v));
         if (f == "-PERCENTILE") o.percentile = std::atoi(v);
         if (f == "-ADAPT") o.adapt = static_cast<float>(std::atof(v));
+        if (f == "-BLOOM") o.bloom = static_cast<float>(std::atof(v));
+        if (f == "-BLOOM_THRESHOLD") o.bloom_threshold = static_cast<float>(std::atof(v));
+        if (f == "-BLOOM_LEVELS") o.bloom_levels = std::atoi(v);
     }
 }
 
@@ -288,10 +299,21 @@ int main(int argc, char **argv) {
         device_resolve = false;
     }
     // -TONE / -EXPOSURE / -AUTO_EXPOSURE: what every graded image is asked for; the library checks it (no device needed)
-    const bool grading = o.grading;
+    // -BLOOM: a stage of the graded chain; alone it runs with the zeroed grade, whose bytes are the ungraded ones
+    pt_bloom_params bloom;
+    std::memset(&bloom, 0, sizeof bloom);
+    bloom.strength = o.bloom; bloom.threshold = o.bloom_threshold; bloom.levels = o.bloom_levels;
+    // (checked here, not by a call of the library's device entry point: nothing before the scene is parsed may start the HIP runtime)
+    if (!(std::isfinite(bloom.strength) && bloom.strength >= 0.0f) || !(std::isfinite(bloom.threshold) && bloom.threshold >= 0.0f) ||
+        bloom.levels < 0 || bloom.levels > PT_BLOOM_MAX_LEVELS) {
+        std::cerr << "pt_render: -BLOOM and -BLOOM_THRESHOLD take a number >= 0, -BLOOM_LEVELS 1 .. " << PT_BLOOM_MAX_LEVELS << std::endl;
+        return 2;
+    }
+    const bool blooming = bloom.strength > 0.0f;
+    const bool grading = o.grading || blooming;
     pt_grade_params grade;
     std::memset(&grade, 0, sizeof grade);
-    if (grading) {
+    if (o.grading) {
         const char *names[4] = {"reference", "clamp", "reinhard", "aces"};
         grade.curve = -1;
         for (int k = 0; k < 4; ++k)
@@ -465,11 +487,11 @@ int main(int argc, char **argv) {
     if (scale > 1) out_bgr.resize(3 * static_cast<size_t>(o.width) * o.height);
 
     // grading on the host path: linear mean and count -> meter and exposure (if automatic; a sequence's frame starts from the
-    // previous frame's) -> grade -> tone map -> the reference's filters -> set_pixel
+    // previous frame's) -> bloom (-BLOOM) -> grade -> tone map -> the reference's filters -> set_pixel
     bool has_exposure = false;
     float last_exposure = 0.0f;
     auto graded_to_bytes = [&](int w, int h, const float *mean, const int32_t *cnt, uint8_t *out) {
-        float e = grade.exposure, target = 0.0f;
+        float e = grade.exposure > 0.0f ? grade.exposure : 1.0f, target = 0.0f;   // (0 = 1, as the library reads it)
         if (grade.auto_exposure) {
             uint32_t hist[PT_METER_ENTRIES];
             if (pt_meter_host(devices[0], w, h, mean, cnt, hist, nullptr) != PT_OK ||
@@ -479,6 +501,10 @@ int main(int argc, char **argv) {
             last_exposure = e;
         }
         std::vector<float> rgb(3 * static_cast<size_t>(w) * h);
+        if (blooming) {
+            if (pt_bloom_host(devices[0], w, h, mean, cnt, e, &bloom, rgb.data(), nullptr) != PT_OK) return false;
+            mean = rgb.data();
+        }
         if (pt_grade_host(w, h, mean, cnt, e, grade.curve, rgb.data()) != PT_OK) return false;
         pt_tonemap(w, h, rgb.data(), cnt, o.gamma_correction, rgb.data());
         if ((o.gauss || o.median) && pt_post_filter_host(devices[0], w, h, rgb.data(), o.gauss, o.median) != PT_OK) return false;
@@ -495,6 +521,7 @@ int main(int argc, char **argv) {
     };
     // the device path's present: plain, scaled, or either with grading
     auto present = [&](pt_display_info *info) {
+        if (blooming) return pt_display_present_bloom(display, &show, scale > 1 ? &upsample : nullptr, &grade, &bloom, scale > 1 ? out_bgr.data() : bgr.data(), info, nullptr);
         if (grading) return pt_display_present_graded(display, &show, scale > 1 ? &upsample : nullptr, &grade, scale > 1 ? out_bgr.data() : bgr.data(), info, nullptr);
         return scale > 1 ? pt_display_present_scaled(display, &show, &upsample, out_bgr.data(), info) : pt_display_present(display, &show, bgr.data(), info);
     };
