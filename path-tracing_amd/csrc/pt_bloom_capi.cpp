@@ -32,11 +32,11 @@ namespace {
 int bloom_host_impl(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure, const pt_bloom_params *b,
                     float *out_rgb, float *kernel_ms) {
     if (width <= 0 || height <= 0 || !mean_rgb || !count || !out_rgb) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: null buffer or empty image");
-    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: image too large");
+    int rc = ptc::check_image_size(width, height, "bloom: ");
+    if (rc != PT_OK) return rc;
     if (!std::isfinite(exposure) || !(exposure > 0.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "bloom: exposure must be finite and > 0");
     ptc::BloomSetup setup;
-    int rc = ptc::bloom_params_check(b, setup);
-    if (rc != PT_OK) return rc;
+    if ((rc = ptc::bloom_params_check(b, setup)) != PT_OK) return rc;
     if (kernel_ms) *kernel_ms = 0.0f;
     if ((rc = ptc::use_device(device, "bloom")) != PT_OK) return rc;
     const size_t n = static_cast<size_t>(width) * height;
@@ -45,25 +45,25 @@ int bloom_host_impl(int device, int32_t width, int32_t height, const float *mean
         return PT_OK;
     }
     ptc::PlaneLayout l;
-    const size_t o_mean = l.add(12 * n), o_cnt = l.add(4 * n), o_e = l.add(4), o_out = l.add(12 * n);
+    ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
+    const size_t o_e = l.add(4), o_out = l.add(12 * n);
     const size_t o_pyr = l.add(16 * pt::bloom_pyramid_records(width, height, setup.levels));
     ptc::DeviceBuffer d;
-    ptc::DeviceEvent ev0, ev1;
-    if ((rc = d.alloc(l, "pt_bloom_host")) != PT_OK || (rc = ev0.create("pt_bloom_host")) != PT_OK || (rc = ev1.create("pt_bloom_host")) != PT_OK) return rc;
-    PT_HIP_TRY(hipMemcpy(d.at<void>(o_mean), mean_rgb, 12 * n, hipMemcpyHostToDevice));
-    PT_HIP_TRY(hipMemcpy(d.at<void>(o_cnt), count, 4 * n, hipMemcpyHostToDevice));
+    ptc::DeviceTimer timer;
+    if ((rc = d.alloc(l, "pt_bloom_host")) != PT_OK || (rc = timer.create("pt_bloom_host")) != PT_OK) return rc;
+    in.bind(d);
+    if ((rc = in.upload(mean_rgb, count)) != PT_OK) return rc;
     PT_HIP_TRY(hipMemcpy(d.at<void>(o_e), &exposure, 4, hipMemcpyHostToDevice));
     pt::BloomArgs a;
     a.width = width; a.height = height; a.levels = setup.levels; a.divide = 0;
-    a.rgb = d.at<float>(o_mean); a.count = d.at<int32_t>(o_cnt); a.exposure = d.at<float>(o_e);
+    a.rgb = in.rgb; a.count = in.count; a.exposure = d.at<float>(o_e);
     a.threshold = setup.threshold; a.weight = setup.weight;
     a.pyramid = d.at<void>(o_pyr); a.out_rgb = d.at<float>(o_out);
-    PT_HIP_TRY(hipEventRecord(ev0.get(), nullptr));
+    PT_HIP_TRY(timer.begin(nullptr));
     PT_HIP_TRY(pt::launch_bloom(a, nullptr));
-    PT_HIP_TRY(hipEventRecord(ev1.get(), nullptr));
-    PT_HIP_TRY(hipEventSynchronize(ev1.get()));
+    PT_HIP_TRY(timer.end(nullptr));
     float ms = 0.0f;
-    PT_HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+    PT_HIP_TRY(timer.wait_ms(&ms));
     PT_HIP_TRY(hipMemcpy(out_rgb, a.out_rgb, 12 * n, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;

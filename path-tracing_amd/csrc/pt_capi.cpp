@@ -389,7 +389,7 @@ int32_t band_rows(const pt_render_params *p) {
 
 int check_params(const pt_scene *scene, const pt_render_params *p) {
     if (!scene || !p) return fail(PT_ERR_INVALID_ARGUMENT, "null scene or params");
-    if (scene->device < 0) return fail(PT_ERR_NO_DEVICE, "scene was created without a device (device < 0)");
+    if (const int rc = check_has_device(scene)) return rc;
     if (p->width <= 0 || p->height <= 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
     if (p->row_begin < 0 || p->row_end > p->height || p->row_begin > p->row_end)
         return fail(PT_ERR_INVALID_ARGUMENT, "row band outside the image");
@@ -797,7 +797,7 @@ static int render_device_impl(pt_scene *scene, const pt_render_params *p, float 
 static int trace_rays_host_impl(pt_scene *scene, int32_t n_rays, const float *origins, const float *directions, float eps,
                        int32_t *hit_index, float *hit_t) {
     if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
-    if (scene->device < 0) return fail(PT_ERR_NO_DEVICE, "scene was created without a device (device < 0)");
+    if (const int rc = ptc::check_has_device(scene)) return rc;
     if (n_rays < 0 || (n_rays > 0 && (!origins || !directions || !hit_index || !hit_t)))
         return fail(PT_ERR_INVALID_ARGUMENT, "null ray buffer or negative count");
     if (n_rays == 0) return PT_OK;

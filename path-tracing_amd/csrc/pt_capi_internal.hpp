@@ -1,7 +1,9 @@
-// Types shared by the translation units behind the C ABI (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters;
-// pt_frame.cpp: the multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp: the
-// temporal stage; pt_display_capi.cpp: the device-resident display path; pt_grade_capi.cpp: display grading; pt_bloom_capi.cpp: bloom; pt_upsample_capi.cpp: the upsampler; pt_device_mem.hpp: the owners of everything they hold
-// on a device).  Nothing here is part of the ABI.
+// What the translation units behind the C ABI share (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters; pt_frame.cpp: the
+// multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
+// pt_grade_capi.cpp, pt_bloom_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident display path, which
+// chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
+// arguments, and the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments.
+// Nothing here is part of the ABI.
 #pragma once
 #include "../../include/pt_hip.h"
 
@@ -130,6 +132,16 @@ int guarded(F &&f) noexcept {
     }
 }
 
+// The two checks whose text every stage shares: `prefix` names the stage ("bloom: "), `tail` is what a handle's creation adds.
+inline int check_image_size(int32_t width, int32_t height, const char *prefix = "") {
+    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, std::string(prefix) + "image too large");
+    return PT_OK;
+}
+inline int check_has_device(const pt_scene *scene, const char *tail = "") {
+    if (scene->device < 0) return fail(PT_ERR_NO_DEVICE, std::string("scene was created without a device (device < 0)") + tail);
+    return PT_OK;
+}
+
 int check_params(const pt_scene *scene, const pt_render_params *p);
 // A session whose planes live in memory the caller owns (the root band of a frame renders straight into the frame's planes).
 int session_create_on(pt_scene *scene, int32_t width, int32_t height, int32_t row_begin, int32_t row_end, const AccumPlanes *borrowed,
@@ -148,12 +160,25 @@ int scene_trace_args(pt_scene *scene, float eps, pt::RenderArgs &a);
 // The view's first hits for `rows` rows from `row_begin`: centre rays through `camera`, the closest-hit search with `a`
 // (scene_trace_args), the hit's features.  Enqueued on `stream`; the caller still holds scene->launch_mutex.
 int enqueue_first_hits(pt_scene *scene, const pt::RenderArgs &a, const pt_camera &camera, int32_t width, int32_t height, int32_t row_begin,
-                       int32_t rows, float *origins, float *directions, int32_t *hit, float *hit_t, float *position, float *normal,
-                       float *albedo, hipStream_t stream);
+                       int32_t rows, const FeaturePlanes &out, hipStream_t stream);
 // Makes `device` current if it is an ordinal of a visible device; PT_ERR_NO_DEVICE otherwise (`stage` names the caller in the message).
 int use_device(int device, const char *stage);
 // pt_denoise_params as pt_denoise_host checks them, into the parameter fields of the launch arguments (zero = the default).
 int denoise_params_to_args(const pt_denoise_params *prm, pt::DenoiseArgs &a);
+// The planes a launch reads and writes, from their views: the one place each argument struct's pointers are spelled.
+inline void bind_planes(pt::DenoiseArgs &a, const AccumPlanes &in, const FeaturePlanes &f, const DenoisePlanes &w) {
+    a.sum = in.sum; a.sum2 = in.sum2; a.count = in.count;
+    a.position = f.position; a.normal = f.normal; a.albedo = f.albedo; a.hit_index = f.hit;
+    a.rec_a0 = w.rec_a0; a.rec_a1 = w.rec_a1; a.rec_b = w.rec_b; a.rec_c = w.rec_c;
+    a.mean_rgb = w.out.rgb; a.count_out = w.out.count;
+}
+inline void bind_planes(pt::UpsampleArgs &a, const float *mean_lo, const int32_t *count_lo, const FeaturePlanes &f, const UpsamplePlanes &w,
+                        const MeanPlanes &out) {
+    a.mean_lo = mean_lo; a.count_lo = count_lo;
+    a.position = f.position; a.normal = f.normal; a.albedo = f.albedo; a.hit_index = f.hit;
+    a.rec_a = w.rec_a; a.rec_b = w.rec_b; a.rec_c = w.rec_c;
+    a.mean_rgb = out.rgb; a.count_out = out.count;
+}
 // levels = 0 of pt_denoise_host: mean_rgb = sum / n (sum where n = 0), count_out = count (may be NULL), on the host.
 void unfiltered_mean(size_t n, const float *sum, const int32_t *count, float *mean_rgb, int32_t *count_out);
 // pt_upsample_params and the OUTPUT size as pt_upsample_host checks them (no device is touched), into the parameter fields of the

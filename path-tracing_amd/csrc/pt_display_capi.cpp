@@ -70,6 +70,11 @@ struct GradeRequest {
     int32_t width = 0, height = 0;   // of the image the display kernel reads (bloom needs its shape)
 };
 
+// The image a chain has reached: planes on the device, sums still (divide) or means.
+struct Image { const float *rgb; const int32_t *count; bool divide; };
+// What collect brings back besides the bytes (used: of a graded image).
+struct Presented { int32_t n_deferred = 0; pt_grade_info used{}; };
+
 // ---- what one image needs on its device -------------------------------------------------------------------------------
 // The table of the gamma used last, the output bytes, the deferred list and its length.
 struct DisplayDevice {
@@ -137,11 +142,11 @@ struct DisplayDevice {
     }
     // Zero the list's length and launch the kernel on `stream`; with `grade`, the exposure first -- metered from the image the
     // kernel is about to read, or the manual one written into the device scalar -- and then the graded kernel.
-    int enqueue(const float *rgb, const int32_t *count, bool divide, hipStream_t stream, const GradeRequest *grade = nullptr) {
+    int enqueue(const Image &image, hipStream_t stream, const GradeRequest *grade) {
         pt::DisplayArgs a;
         a.n = static_cast<int>(n);
-        a.divide = divide ? 1 : 0;
-        a.rgb = rgb; a.count = count;
+        a.divide = image.divide ? 1 : 0;
+        a.rgb = image.rgb; a.count = image.count;
         a.table = table;
         a.last = host->thresholds.empty() ? 0.0f : host->thresholds.back();   // (no level at all: everything is the host's)
         a.n_bands = static_cast<int>(host->band_lo.size());
@@ -155,7 +160,7 @@ struct DisplayDevice {
         PT_HIP_TRY(hipMemsetAsync(hist, 0, kGradeBytes, stream));
         if (grade->setup.automatic) {
             pt::MeterArgs m;
-            m.n = a.n; m.divide = a.divide; m.rgb = rgb; m.count = count; m.hist = hist;
+            m.n = a.n; m.divide = a.divide; m.rgb = a.rgb; m.count = a.count; m.hist = hist;
             PT_HIP_TRY(pt::launch_meter(m, stream));
             PT_HIP_TRY(pt::launch_exposure(hist, grade->setup.rule, grade->has_prev, grade->e_prev, exposure, stream));
         } else {
@@ -166,7 +171,7 @@ struct DisplayDevice {
         if (grade->bloom.on) {   // the display kernel reads m + A * weight, a plane of means, with the chain's count
             pt::BloomArgs b;
             b.width = grade->width; b.height = grade->height; b.levels = grade->bloom.levels; b.divide = a.divide;
-            b.rgb = rgb; b.count = count; b.exposure = &exposure->exposure;
+            b.rgb = a.rgb; b.count = a.count; b.exposure = &exposure->exposure;
             b.threshold = grade->bloom.threshold; b.weight = grade->bloom.weight;
             b.pyramid = pyramid; b.out_rgb = bloomed;
             PT_HIP_TRY(pt::launch_bloom(b, stream));
@@ -176,14 +181,14 @@ struct DisplayDevice {
         return PT_OK;
     }
     // The kernel has finished: 3 bytes per pixel and the deferred list come to the host, which finishes the list's pixels.
-    int collect(float gamma, uint8_t *out, int32_t *n_deferred_out, const GradeRequest *grade = nullptr, pt_grade_info *used = nullptr) {
+    int collect(float gamma, uint8_t *out, const GradeRequest *grade, Presented &got) {
         PT_HIP_TRY(hipMemcpy(out, bgr, 3 * n, hipMemcpyDeviceToHost));
         if (grade) {
             pt::ExposureOut o;
             PT_HIP_TRY(hipMemcpy(&o, exposure, sizeof o, hipMemcpyDeviceToHost));
-            used->exposure = o.exposure;
-            used->target = grade->setup.automatic ? o.target : o.exposure;
-            used->metered = o.metered; used->dark = o.dark;
+            got.used.exposure = o.exposure;
+            got.used.target = grade->setup.automatic ? o.target : o.exposure;
+            got.used.metered = o.metered; got.used.dark = o.dark;
         }
         uint32_t len = 0;
         PT_HIP_TRY(hipMemcpy(&len, n_deferred, 4, hipMemcpyDeviceToHost));
@@ -193,16 +198,16 @@ struct DisplayDevice {
             PT_HIP_TRY(hipMemcpy(list.data(), deferred, sizeof(pt::DisplayDeferred) * len, hipMemcpyDeviceToHost));
             for (const pt::DisplayDeferred &d : list)
                 if (d.pixel < 0 || static_cast<size_t>(d.pixel) >= n) return fail(PT_ERR_HIP, "display: a deferred pixel lies outside the image");
-            if (grade) finish_on_host_graded(list, gamma, grade->setup.curve, used->exposure, out);
+            if (grade) finish_on_host_graded(list, gamma, grade->setup.curve, got.used.exposure, out);
             else finish_on_host(list, gamma, out);
         }
-        *n_deferred_out = static_cast<int32_t>(len);
+        got.n_deferred = static_cast<int32_t>(len);
         return PT_OK;
     }
-    void fill(pt_display_info *info, float ms, int32_t n_def) const {
+    void fill(pt_display_info *info, float ms, const Presented &got) const {
         if (!info) return;
         info->kernel_ms = ms;
-        info->deferred_pixels = n_def;
+        info->deferred_pixels = got.n_deferred;
         info->table_levels = static_cast<int32_t>(host->thresholds.size());
         info->doubt_bands = static_cast<int32_t>(host->band_lo.size());
     }
@@ -224,19 +229,17 @@ struct pt_display {
     pt_temporal *history = nullptr;  // created by the first present with a temporal stage
     // a filter without a temporal stage: the view's features and the denoiser's planes, allocated by the first such present
     ptc::DeviceBuffer d_filter;
-    float *d_origins = nullptr, *d_directions = nullptr, *d_position = nullptr, *d_normal = nullptr, *d_albedo = nullptr, *d_hit_t = nullptr, *d_mean = nullptr;
-    int32_t *d_hit = nullptr, *d_mean_count = nullptr;
-    void *dn_a0 = nullptr, *dn_a1 = nullptr, *dn_b = nullptr, *dn_c = nullptr;
+    ptc::FeaturePlanes features;
+    ptc::DenoisePlanes denoise;
     // a scaled present: the output image's features, mean and count, the low mean and the upsampler's records, and the output's
     // bytes and deferred list -- allocated by the first scaled present, again when the scale changes
     int32_t up_scale = 0;
     ptc::DeviceBuffer d_up;
     DisplayDevice dev_up;
-    float *up_origins = nullptr, *up_directions = nullptr, *up_position = nullptr, *up_normal = nullptr, *up_albedo = nullptr, *up_hit_t = nullptr,
-          *up_mean = nullptr, *up_mean_lo = nullptr;
-    int32_t *up_hit = nullptr, *up_count = nullptr;
-    void *up_a = nullptr, *up_b = nullptr, *up_c = nullptr;
-    ptc::DeviceEvent ev0, ev1;
+    ptc::FeaturePlanes up_features;
+    ptc::MeanPlanes up_out;
+    ptc::UpsamplePlanes up_work;
+    ptc::DeviceTimer timer;
     bool has_exposure = false;       // the e of the last metered present (pt_display_present_graded), until a reset
     float exposure = 0.0f;
     ~pt_display() {
@@ -248,17 +251,27 @@ struct pt_display {
 namespace {
 
 int display_create_impl(pt_scene *scene, int32_t width, int32_t height, float eps, std::unique_ptr<pt_display> &d) {
-    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "image too large");
+    int rc = ptc::check_image_size(width, height);
+    if (rc != PT_OK) return rc;
     if (std::isnan(eps)) return fail(PT_ERR_INVALID_ARGUMENT, "eps is not a number");
-    if (scene->device < 0) return fail(PT_ERR_NO_DEVICE, "scene was created without a device (device < 0); there is no CPU fallback");
+    if ((rc = ptc::check_has_device(scene, "; there is no CPU fallback")) != PT_OK) return rc;
     PT_HIP_TRY(hipSetDevice(scene->device));
     d.reset(new pt_display);
     d->scene = scene; d->width = width; d->height = height; d->eps = eps;
     d->n = static_cast<size_t>(width) * height;
-    int rc;
-    if ((rc = d->dev.alloc(d->n, "pt_display_create")) != PT_OK || (rc = d->ev0.create("pt_display_create")) != PT_OK ||
-        (rc = d->ev1.create("pt_display_create")) != PT_OK)
-        return rc;
+    if ((rc = d->dev.alloc(d->n, "pt_display_create")) != PT_OK) return rc;
+    return d->timer.create("pt_display_create");
+}
+
+// What a filtered present without a temporal stage needs on the device (the caller holds d->mutex and has made the device current).
+int ensure_filter(pt_display *d) {
+    if (d->d_filter) return PT_OK;
+    ptc::PlaneLayout l;
+    d->features = ptc::FeaturePlanes::in(l, d->n);
+    d->denoise = ptc::DenoisePlanes::in(l, d->n);
+    const int rc = d->d_filter.alloc(l, "pt_display_present");
+    if (rc != PT_OK) return rc;
+    d->features.bind(d->d_filter); d->denoise.bind(d->d_filter);
     return PT_OK;
 }
 
@@ -268,34 +281,47 @@ int ensure_scaled(pt_display *d, int32_t s) {
     d->up_scale = 0;
     const size_t n_lo = d->n, n = n_lo * static_cast<size_t>(s) * s;
     ptc::PlaneLayout l;
-    const size_t o_org = l.add(12 * n), o_dir = l.add(12 * n), o_pos = l.add(12 * n), o_nrm = l.add(12 * n), o_alb = l.add(12 * n), o_mean = l.add(12 * n);
-    const size_t o_hit = l.add(4 * n), o_hit_t = l.add(4 * n), o_cnt = l.add(4 * n);
-    const size_t o_mlo = l.add(12 * n_lo), o_a = l.add(16 * n_lo), o_b = l.add(16 * n_lo), o_c = l.add(16 * n_lo);
+    d->up_features = ptc::FeaturePlanes::in(l, n);
+    d->up_out = ptc::MeanPlanes::in(l, n);
+    d->up_work = ptc::UpsamplePlanes::in(l, n_lo, true);
     int rc;
     if ((rc = d->d_up.alloc(l, "pt_display_present_scaled")) != PT_OK || (rc = d->dev_up.alloc(n, "pt_display_present_scaled")) != PT_OK) return rc;
     d->dev_up.host.reset();   // (a new allocation holds no table yet)
-    const ptc::DeviceBuffer &b = d->d_up;
-    d->up_origins = b.at<float>(o_org); d->up_directions = b.at<float>(o_dir); d->up_position = b.at<float>(o_pos);
-    d->up_normal = b.at<float>(o_nrm); d->up_albedo = b.at<float>(o_alb); d->up_mean = b.at<float>(o_mean);
-    d->up_hit = b.at<int32_t>(o_hit); d->up_hit_t = b.at<float>(o_hit_t); d->up_count = b.at<int32_t>(o_cnt);
-    d->up_mean_lo = b.at<float>(o_mlo);
-    d->up_a = b.at<void>(o_a); d->up_b = b.at<void>(o_b); d->up_c = b.at<void>(o_c);
+    d->up_features.bind(d->d_up); d->up_out.bind(d->d_up); d->up_work.bind(d->d_up);
     d->up_scale = s;
     return PT_OK;
 }
 
-// `u` = NULL: pt_display_present.  Else the scaled present: the same chain at the display's size, then the upsample to s times it.
-// `g` = NULL: no grading.  Else pt_display_present_graded: the exposure and the graded kernel in place of the display kernel.
-// `b` (with `g` only): pt_display_present_bloom.
-int display_present_impl(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, bool scaled, uint8_t *bgr, pt_display_info *info,
-                         const pt_grade_params *g = nullptr, bool graded = false, pt_grade_info *grade_info = nullptr,
-                         const pt_bloom_params *b = nullptr, bool bloomed = false) {
-    if (!d || !p || !bgr || (scaled && !u) || (graded && !g) || (bloomed && !b)) return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or image");
+// The first hits of the whole view through the scene's camera at width x height, on `stream`.  The caller holds
+// scene->launch_mutex, and keeps it for whatever else its launches need of the scene.
+int enqueue_view_first_hits(pt_scene *scene, float eps, int32_t width, int32_t height, const ptc::FeaturePlanes &out, hipStream_t stream) {
+    pt::RenderArgs ra;
+    const int rc = ptc::scene_trace_args(scene, eps, ra);
+    if (rc != PT_OK) return rc;
+    return ptc::enqueue_first_hits(scene, ra, ptc::view_camera(scene), width, height, 0, height, out, stream);
+}
+
+int null_argument() { return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params or image"); }
+
+// What one present is asked for.  A NULL stage is off: the entry point that requires one has refused its absence already.
+struct PresentRequest {
+    const pt_display_params *display;
+    const pt_upsample_params *upsample;   // the same chain at the display's size, then the upsample to scale times it
+    const pt_grade_params *grade;         // the exposure and the graded kernel in place of the display kernel
+    const pt_bloom_params *bloom;         // with grade only
+    pt_grade_info *grade_info;            // with grade only; may be NULL
+};
+
+int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, pt_display_info *info) {
+    const pt_display_params *p = rq.display;
+    const pt_upsample_params *u = rq.upsample;
+    if (!d || !p || !bgr) return null_argument();
+    const bool scaled = u != nullptr, graded = rq.grade != nullptr;
     int rc = check_gamma(p->gamma);
     if (rc != PT_OK) return rc;
     GradeRequest grade;
-    if (graded && (rc = ptc::grade_params_check(g, grade.setup)) != PT_OK) return rc;
-    if (bloomed && (rc = ptc::bloom_params_check(b, grade.bloom)) != PT_OK) return rc;
+    if (graded && (rc = ptc::grade_params_check(rq.grade, grade.setup)) != PT_OK) return rc;
+    if (rq.bloom && (rc = ptc::bloom_params_check(rq.bloom, grade.bloom)) != PT_OK) return rc;
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -307,7 +333,6 @@ int display_present_impl(pt_display *d, const pt_display_params *p, const pt_ups
     std::lock_guard<std::mutex> present_lock(d->mutex);
     grade.has_prev = d->has_exposure; grade.e_prev = d->exposure;
     const std::shared_ptr<const DisplayTable> table = display_table(p->gamma);
-    const size_t n = d->n;
     // the accumulators, where they lie, and the stream their slices were enqueued on: the chain goes behind them
     ptc::AccumPlanes planes;
     hipStream_t stream = nullptr;
@@ -327,126 +352,92 @@ int display_present_impl(pt_display *d, const pt_display_params *p, const pt_ups
     grade.width = scaled ? ua.width : d->width; grade.height = scaled ? ua.height : d->height;
     if (grade.bloom.on && (rc = dev.ensure_bloom(grade.width, grade.height, "pt_display_present_bloom")) != PT_OK) return rc;
     if (temporal && !d->history && (rc = pt_temporal_create(scene, d->width, d->height, d->eps, &d->history)) != PT_OK) return rc;
-    if (filter && !temporal && !d->d_filter) {
-        ptc::PlaneLayout l;
-        const size_t o_org = l.add(12 * n), o_dir = l.add(12 * n), o_pos = l.add(12 * n), o_nrm = l.add(12 * n), o_alb = l.add(12 * n), o_mean = l.add(12 * n);
-        const size_t o_hit = l.add(4 * n), o_hit_t = l.add(4 * n), o_cnt = l.add(4 * n);
-        const size_t o_a0 = l.add(16 * n), o_a1 = l.add(16 * n), o_b = l.add(16 * n), o_c = l.add(16 * n);
-        if ((rc = d->d_filter.alloc(l, "pt_display_present")) != PT_OK) return rc;
-        const ptc::DeviceBuffer &b = d->d_filter;
-        d->d_origins = b.at<float>(o_org); d->d_directions = b.at<float>(o_dir); d->d_position = b.at<float>(o_pos);
-        d->d_normal = b.at<float>(o_nrm); d->d_albedo = b.at<float>(o_alb); d->d_mean = b.at<float>(o_mean);
-        d->d_hit = b.at<int32_t>(o_hit); d->d_hit_t = b.at<float>(o_hit_t); d->d_mean_count = b.at<int32_t>(o_cnt);
-        d->dn_a0 = b.at<void>(o_a0); d->dn_a1 = b.at<void>(o_a1); d->dn_b = b.at<void>(o_b); d->dn_c = b.at<void>(o_c);
-    }
+    if (filter && !temporal && (rc = ensure_filter(d)) != PT_OK) return rc;
     {   // the chain, behind every slice enqueued so far: no host synchronisation until its last kernel is in the queue
         std::unique_lock<std::mutex> ctx_lock;
         if (d->session) ctx_lock = std::unique_lock<std::mutex>(d->session->ctx.mutex);
-        PT_HIP_TRY(hipEventRecord(d->ev0.get(), stream));
-        const float *rgb = planes.sum;
-        const int32_t *count = planes.count;
-        bool divide = true;
+        PT_HIP_TRY(d->timer.begin(stream));
+        Image image = {planes.sum, planes.count, true};
         if (temporal) {
             ptc::TemporalPlanes merged;
             if ((rc = ptc::temporal_enqueue(d->history, planes, &p->temporal_params, filter ? &p->denoise : nullptr, stream, &merged)) != PT_OK) return rc;
-            rgb = filter ? merged.mean : merged.merged.sum;
-            count = filter ? merged.mean_count : merged.merged.count;
-            divide = !filter;
+            image = filter ? Image{merged.mean, merged.mean_count, false} : Image{merged.merged.sum, merged.merged.count, true};
         } else if (filter) {
             std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
-            pt::RenderArgs ra;
-            if ((rc = ptc::scene_trace_args(scene, d->eps, ra)) != PT_OK) return rc;
-            rc = ptc::enqueue_first_hits(scene, ra, ptc::view_camera(scene), d->width, d->height, 0, d->height, d->d_origins, d->d_directions, d->d_hit,
-                                         d->d_hit_t, d->d_position, d->d_normal, d->d_albedo, stream);
-            if (rc != PT_OK) return rc;
+            if ((rc = enqueue_view_first_hits(scene, d->eps, d->width, d->height, d->features, stream)) != PT_OK) return rc;
             da.width = d->width; da.height = d->height;
-            da.sum = planes.sum; da.sum2 = planes.sum2; da.count = planes.count;
-            da.position = d->d_position; da.normal = d->d_normal; da.albedo = d->d_albedo; da.hit_index = d->d_hit;
-            da.rec_a0 = d->dn_a0; da.rec_a1 = d->dn_a1; da.rec_b = d->dn_b; da.rec_c = d->dn_c;
-            da.mean_rgb = d->d_mean; da.count_out = d->d_mean_count;
+            ptc::bind_planes(da, planes, d->features, d->denoise);
             PT_HIP_TRY(pt::launch_denoise(da, stream));
-            rgb = d->d_mean; count = d->d_mean_count;
-            divide = false;
+            image = {d->denoise.out.rgb, d->denoise.out.count, false};
         }
         if (scaled) {
             // the low mean (levels = 0: sum / n of the accumulators as they are, or merged), the output image's features from the
             // same camera, the upsample; the bytes are then made from its mean and count
-            if (divide) {
-                PT_HIP_TRY(pt::launch_upsample_mean(rgb, count, static_cast<int>(n), d->up_mean_lo, stream));
-                rgb = d->up_mean_lo;
+            if (image.divide) {
+                PT_HIP_TRY(pt::launch_upsample_mean(image.rgb, image.count, static_cast<int>(d->n), d->up_work.mean_lo, stream));
+                image.rgb = d->up_work.mean_lo;
             }
             {
                 std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
-                pt::RenderArgs ra;
-                if ((rc = ptc::scene_trace_args(scene, d->eps, ra)) != PT_OK) return rc;
-                rc = ptc::enqueue_first_hits(scene, ra, ptc::view_camera(scene), ua.width, ua.height, 0, ua.height, d->up_origins, d->up_directions,
-                                             d->up_hit, d->up_hit_t, d->up_position, d->up_normal, d->up_albedo, stream);
-                if (rc != PT_OK) return rc;
+                if ((rc = enqueue_view_first_hits(scene, d->eps, ua.width, ua.height, d->up_features, stream)) != PT_OK) return rc;
             }
-            ua.mean_lo = rgb; ua.count_lo = count;
-            ua.position = d->up_position; ua.normal = d->up_normal; ua.albedo = d->up_albedo; ua.hit_index = d->up_hit;
-            ua.rec_a = d->up_a; ua.rec_b = d->up_b; ua.rec_c = d->up_c;
-            ua.mean_rgb = d->up_mean; ua.count_out = d->up_count;
+            ptc::bind_planes(ua, image.rgb, image.count, d->up_features, d->up_work, d->up_out);
             PT_HIP_TRY(pt::launch_upsample(ua, stream));
-            rgb = d->up_mean; count = d->up_count;
-            divide = false;
+            image = {d->up_out.rgb, d->up_out.count, false};
         }
-        if ((rc = dev.enqueue(rgb, count, divide, stream, graded ? &grade : nullptr)) != PT_OK) return rc;
-        PT_HIP_TRY(hipEventRecord(d->ev1.get(), stream));
+        if ((rc = dev.enqueue(image, stream, graded ? &grade : nullptr)) != PT_OK) return rc;
+        PT_HIP_TRY(d->timer.end(stream));
     }
     // (an error return from here on leaves the history and the metered exposure as they were: they were only read)
-    PT_HIP_TRY(hipEventSynchronize(d->ev1.get()));
     float ms = 0.0f;
-    PT_HIP_TRY(hipEventElapsedTime(&ms, d->ev0.get(), d->ev1.get()));
-    int32_t n_deferred = 0;
-    pt_grade_info used{};
-    if ((rc = dev.collect(p->gamma, bgr, &n_deferred, graded ? &grade : nullptr, &used)) != PT_OK) return rc;
+    PT_HIP_TRY(d->timer.wait_ms(&ms));
+    Presented got;
+    if ((rc = dev.collect(p->gamma, bgr, graded ? &grade : nullptr, got)) != PT_OK) return rc;
     if (temporal) ptc::temporal_commit(d->history);
     if (graded && grade.setup.automatic) {
         d->has_exposure = true;
-        d->exposure = used.exposure;
+        d->exposure = got.used.exposure;
     }
-    if (graded && grade_info) *grade_info = used;
-    dev.fill(info, ms, n_deferred);
+    if (graded && rq.grade_info) *rq.grade_info = got.used;
+    dev.fill(info, ms, got);
     return PT_OK;
 }
 
-// `g` = NULL: pt_display_bytes_host.  Else pt_display_bytes_graded_host.
-int display_bytes_host_impl(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
-                            uint8_t *bgr, pt_display_info *info, const pt_grade_params *g = nullptr, bool graded = false, bool has_prev = false,
-                            float e_prev = 0.0f, pt_grade_info *grade_info = nullptr) {
-    if (width <= 0 || height <= 0 || !mean_rgb || !count || !bgr || (graded && !g)) return fail(PT_ERR_INVALID_ARGUMENT, "null buffer or empty image");
-    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "image too large");
-    int rc = check_gamma(gamma);
-    if (rc != PT_OK) return rc;
+// A mean image in host memory, and how it is to be graded (pt_display_bytes_graded_host).
+struct HostImage { int device; int32_t width, height; const float *mean_rgb; const int32_t *count; };
+struct HostGrade { const pt_grade_params *params; bool has_prev; float e_prev; pt_grade_info *info; };   // (info may be NULL)
+
+// `g` = NULL: pt_display_bytes_host.
+int display_bytes_host_impl(const HostImage &image, float gamma, const HostGrade *g, uint8_t *bgr, pt_display_info *info) {
+    if (image.width <= 0 || image.height <= 0 || !image.mean_rgb || !image.count || !bgr || (g && !g->params))
+        return fail(PT_ERR_INVALID_ARGUMENT, "null buffer or empty image");
+    int rc = ptc::check_image_size(image.width, image.height);
+    if (rc != PT_OK || (rc = check_gamma(gamma)) != PT_OK) return rc;
     GradeRequest grade;
-    if (graded && (rc = ptc::grade_params_check(g, grade.setup)) != PT_OK) return rc;
-    grade.has_prev = has_prev; grade.e_prev = e_prev;
-    if ((rc = ptc::use_device(device, "display")) != PT_OK) return rc;
-    const size_t n = static_cast<size_t>(width) * height;
+    if (g && (rc = ptc::grade_params_check(g->params, grade.setup)) != PT_OK) return rc;
+    if (g) grade.has_prev = g->has_prev, grade.e_prev = g->e_prev;
+    if ((rc = ptc::use_device(image.device, "display")) != PT_OK) return rc;
+    const size_t n = static_cast<size_t>(image.width) * image.height;
     const std::shared_ptr<const DisplayTable> table = display_table(gamma);
     DisplayDevice dev;
     ptc::PlaneLayout l;
-    const size_t o_mean = l.add(12 * n), o_cnt = l.add(4 * n);
+    ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
     ptc::DeviceBuffer d_in;
-    ptc::DeviceEvent ev0, ev1;
+    ptc::DeviceTimer timer;
     if ((rc = d_in.alloc(l, "pt_display_bytes_host")) != PT_OK || (rc = dev.alloc(n, "pt_display_bytes_host")) != PT_OK ||
-        (rc = dev.use_table(table, "pt_display_bytes_host")) != PT_OK || (rc = ev0.create("pt_display_bytes_host")) != PT_OK ||
-        (rc = ev1.create("pt_display_bytes_host")) != PT_OK)
+        (rc = dev.use_table(table, "pt_display_bytes_host")) != PT_OK || (rc = timer.create("pt_display_bytes_host")) != PT_OK)
         return rc;
-    PT_HIP_TRY(hipMemcpy(d_in.at<void>(o_mean), mean_rgb, 12 * n, hipMemcpyHostToDevice));
-    PT_HIP_TRY(hipMemcpy(d_in.at<void>(o_cnt), count, 4 * n, hipMemcpyHostToDevice));
-    PT_HIP_TRY(hipEventRecord(ev0.get(), nullptr));
-    if ((rc = dev.enqueue(d_in.at<float>(o_mean), d_in.at<int32_t>(o_cnt), false, nullptr, graded ? &grade : nullptr)) != PT_OK) return rc;
-    PT_HIP_TRY(hipEventRecord(ev1.get(), nullptr));
-    PT_HIP_TRY(hipEventSynchronize(ev1.get()));
+    in.bind(d_in);
+    if ((rc = in.upload(image.mean_rgb, image.count)) != PT_OK) return rc;
+    PT_HIP_TRY(timer.begin(nullptr));
+    if ((rc = dev.enqueue({in.rgb, in.count, false}, nullptr, g ? &grade : nullptr)) != PT_OK) return rc;
+    PT_HIP_TRY(timer.end(nullptr));
     float ms = 0.0f;
-    PT_HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
-    int32_t n_deferred = 0;
-    pt_grade_info used{};
-    if ((rc = dev.collect(gamma, bgr, &n_deferred, graded ? &grade : nullptr, &used)) != PT_OK) return rc;
-    if (graded && grade_info) *grade_info = used;
-    dev.fill(info, ms, n_deferred);
+    PT_HIP_TRY(timer.wait_ms(&ms));
+    Presented got;
+    if ((rc = dev.collect(gamma, bgr, g ? &grade : nullptr, got)) != PT_OK) return rc;
+    if (g && g->info) *g->info = got.used;
+    dev.fill(info, ms, got);
     return PT_OK;
 }
 
@@ -504,21 +495,21 @@ int pt_display_create_frame(pt_frame *frame, float eps, pt_display **out) {
 }
 
 int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return display_present_impl(d, p, nullptr, false, bgr, info); });
+    return guarded([&] { return display_present_impl(d, {p, nullptr, nullptr, nullptr, nullptr}, bgr, info); });
 }
 
 int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return display_present_impl(d, p, u, true, bgr, info); });
+    return guarded([&] { return u ? display_present_impl(d, {p, u, nullptr, nullptr, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_graded(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g, uint8_t *bgr,
                               pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return display_present_impl(d, p, u, u != nullptr, bgr, info, g, true, grade_info); });
+    return guarded([&] { return g ? display_present_impl(d, {p, u, g, nullptr, grade_info}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_bloom(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                              const pt_bloom_params *b, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return display_present_impl(d, p, u, u != nullptr, bgr, info, g, true, grade_info, b, true); });
+    return guarded([&] { return g && b ? display_present_impl(d, {p, u, g, b, grade_info}, bgr, info) : null_argument(); });
 }
 
 int pt_display_reset(pt_display *d) {
@@ -537,14 +528,15 @@ void pt_display_destroy(pt_display *d) {
 
 int pt_display_bytes_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
                           uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return display_bytes_host_impl(device, width, height, mean_rgb, count, gamma, bgr, info); });
+    return guarded([&] { return display_bytes_host_impl({device, width, height, mean_rgb, count}, gamma, nullptr, bgr, info); });
 }
 
 int pt_display_bytes_graded_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
                                  const pt_grade_params *g, int32_t has_prev, float e_prev, uint8_t *bgr, pt_display_info *info,
                                  pt_grade_info *grade_info) {
     return guarded([&] {
-        return display_bytes_host_impl(device, width, height, mean_rgb, count, gamma, bgr, info, g, true, has_prev != 0, e_prev, grade_info);
+        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info};
+        return display_bytes_host_impl({device, width, height, mean_rgb, count}, gamma, &grade, bgr, info);
     });
 }
 

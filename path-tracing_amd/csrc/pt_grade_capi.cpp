@@ -62,29 +62,28 @@ int exposure_impl(const uint32_t *hist, const pt_grade_params *params, int32_t h
 
 int meter_host_impl(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, uint32_t *hist, float *kernel_ms) {
     if (width <= 0 || height <= 0 || !mean_rgb || !count || !hist) return fail(PT_ERR_INVALID_ARGUMENT, "meter: null buffer or empty image");
-    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "meter: image too large");
-    if (kernel_ms) *kernel_ms = 0.0f;
-    int rc = ptc::use_device(device, "meter");
+    int rc = ptc::check_image_size(width, height, "meter: ");
     if (rc != PT_OK) return rc;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if ((rc = ptc::use_device(device, "meter")) != PT_OK) return rc;
     const size_t n = static_cast<size_t>(width) * height;
     ptc::PlaneLayout l;
-    const size_t o_mean = l.add(12 * n), o_cnt = l.add(4 * n), o_hist = l.add(4 * pt::kMeterEntries);
+    ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
+    const size_t o_hist = l.add(4 * pt::kMeterEntries);
     ptc::DeviceBuffer d;
-    ptc::DeviceEvent ev0, ev1;
-    if ((rc = d.alloc(l, "pt_meter_host")) != PT_OK || (rc = ev0.create("pt_meter_host")) != PT_OK || (rc = ev1.create("pt_meter_host")) != PT_OK)
-        return rc;
-    PT_HIP_TRY(hipMemcpy(d.at<void>(o_mean), mean_rgb, 12 * n, hipMemcpyHostToDevice));
-    PT_HIP_TRY(hipMemcpy(d.at<void>(o_cnt), count, 4 * n, hipMemcpyHostToDevice));
+    ptc::DeviceTimer timer;
+    if ((rc = d.alloc(l, "pt_meter_host")) != PT_OK || (rc = timer.create("pt_meter_host")) != PT_OK) return rc;
+    in.bind(d);
+    if ((rc = in.upload(mean_rgb, count)) != PT_OK) return rc;
     PT_HIP_TRY(hipMemset(d.at<void>(o_hist), 0, 4 * pt::kMeterEntries));
     pt::MeterArgs a;
     a.n = static_cast<int>(n); a.divide = 0;
-    a.rgb = d.at<float>(o_mean); a.count = d.at<int32_t>(o_cnt); a.hist = d.at<uint32_t>(o_hist);
-    PT_HIP_TRY(hipEventRecord(ev0.get(), nullptr));
+    a.rgb = in.rgb; a.count = in.count; a.hist = d.at<uint32_t>(o_hist);
+    PT_HIP_TRY(timer.begin(nullptr));
     PT_HIP_TRY(pt::launch_meter(a, nullptr));
-    PT_HIP_TRY(hipEventRecord(ev1.get(), nullptr));
-    PT_HIP_TRY(hipEventSynchronize(ev1.get()));
+    PT_HIP_TRY(timer.end(nullptr));
     float ms = 0.0f;
-    PT_HIP_TRY(hipEventElapsedTime(&ms, ev0.get(), ev1.get()));
+    PT_HIP_TRY(timer.wait_ms(&ms));
     PT_HIP_TRY(hipMemcpy(hist, a.hist, 4 * pt::kMeterEntries, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;

@@ -19,20 +19,17 @@ struct pt_temporal {
     std::mutex mutex;             // one push / reset at a time
     ptc::DeviceBuffer d_all;      // everything below but the denoiser's planes
     ptc::AccumPlanes in, out;     // the frame pushed, the merged accumulators
-    float *d_origins = nullptr, *d_directions = nullptr, *d_position = nullptr, *d_normal = nullptr, *d_albedo = nullptr, *d_hit_t = nullptr,
-          *d_frames = nullptr;
-    int32_t *d_hit = nullptr;
+    ptc::FeaturePlanes features;  // the first hits of the view the frame was rendered from
+    float *d_frames = nullptr;
     pt::TemporalRecords rec[2];   // ping-pong; rec[cur] holds the history
     int cur = 0;
     bool has_history = false;
     pt_camera camera{};           // of the history
     pt_camera pending_camera{};   // of the chain enqueued last: the history's once that chain is committed
     float inverse[9] = {};        // rows of the inverse of [right up forward] of that camera
-    ptc::DeviceBuffer d_denoise;  // allocated by the first push that filters: records A0, A1, B, C, mean, count
-    void *dn_a0 = nullptr, *dn_a1 = nullptr, *dn_b = nullptr, *dn_c = nullptr;
-    float *d_mean = nullptr;
-    int32_t *d_mean_count = nullptr;
-    ptc::DeviceEvent ev0, ev1;
+    ptc::DeviceBuffer d_denoise;  // allocated by the first push that filters
+    ptc::DenoisePlanes denoise;
+    ptc::DeviceTimer timer;
     ~pt_temporal() { (void)hipSetDevice(scene->device); }   // (a handle exists only over a scene with a device)
 };
 
@@ -63,30 +60,26 @@ int temporal_create_impl(pt_scene *scene, int32_t width, int32_t height, float e
     if (!scene || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null scene or output pointer");
     *out = nullptr;
     if (width <= 0 || height <= 0) return fail(PT_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, "image too large");
+    int rc = ptc::check_image_size(width, height);
+    if (rc != PT_OK) return rc;
     if (std::isnan(eps)) return fail(PT_ERR_INVALID_ARGUMENT, "eps is not a number");
-    if (scene->device < 0) return fail(PT_ERR_NO_DEVICE, "scene was created without a device (device < 0); there is no CPU fallback");
+    if ((rc = ptc::check_has_device(scene, "; there is no CPU fallback")) != PT_OK) return rc;
     PT_HIP_TRY(hipSetDevice(scene->device));
     std::unique_ptr<pt_temporal> t(new pt_temporal);
     t->scene = scene; t->width = width; t->height = height; t->eps = eps;
     const size_t n = t->n = static_cast<size_t>(width) * height;
-    // one allocation: nine planes of 12 n bytes, five of 4 n, the two sets of four records of 16 n
+    // one allocation: the two accumulator triples, the features, the frame counts, the two sets of four records of 16 n
     ptc::PlaneLayout l;
     t->in = ptc::AccumPlanes::in(l, n);
     t->out = ptc::AccumPlanes::in(l, n);
-    const size_t o_org = l.add(12 * n), o_dir = l.add(12 * n), o_pos = l.add(12 * n), o_nrm = l.add(12 * n), o_alb = l.add(12 * n);
-    const size_t o_hit = l.add(4 * n), o_hit_t = l.add(4 * n), o_frames = l.add(4 * n);
+    t->features = ptc::FeaturePlanes::in(l, n);
+    const size_t o_frames = l.add(4 * n);
     size_t o_rec[8];
     for (size_t &o : o_rec) o = l.add(16 * n);
-    int rc;
-    if ((rc = t->d_all.alloc(l, "pt_temporal_create")) != PT_OK || (rc = t->ev0.create("pt_temporal_create")) != PT_OK ||
-        (rc = t->ev1.create("pt_temporal_create")) != PT_OK)
-        return rc;
+    if ((rc = t->d_all.alloc(l, "pt_temporal_create")) != PT_OK || (rc = t->timer.create("pt_temporal_create")) != PT_OK) return rc;
     const ptc::DeviceBuffer &d = t->d_all;
-    t->in.bind(d); t->out.bind(d);
-    t->d_origins = d.at<float>(o_org); t->d_directions = d.at<float>(o_dir); t->d_position = d.at<float>(o_pos);
-    t->d_normal = d.at<float>(o_nrm); t->d_albedo = d.at<float>(o_alb);
-    t->d_hit = d.at<int32_t>(o_hit); t->d_hit_t = d.at<float>(o_hit_t); t->d_frames = d.at<float>(o_frames);
+    t->in.bind(d); t->out.bind(d); t->features.bind(d);
+    t->d_frames = d.at<float>(o_frames);
     for (int k = 0; k < 2; ++k)
         t->rec[k] = {d.at<void>(o_rec[4 * k]), d.at<void>(o_rec[4 * k + 1]), d.at<void>(o_rec[4 * k + 2]), d.at<void>(o_rec[4 * k + 3])};
     *out = t.release();
@@ -104,9 +97,9 @@ int check_temporal_params(const pt_temporal_params *prm) {
 
 // The chain of a push on `stream`, from accumulators that lie on the device (`frame`: the handle's own upload planes, or a
 // session's): the view's first hits, the merge, the filter -- no host synchronisation in between.  The caller holds t->mutex and
-// has made the scene's device current.  ev0 / ev1 (NULL: none) are recorded around the kernels.  The history is only read.
+// has made the scene's device current.  `timer` (NULL: none) times the kernels.  The history is only read.
 int enqueue_chain(pt_temporal *t, const ptc::AccumPlanes &frame, const pt_temporal_params *prm, const pt_denoise_params *dn,
-                  hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int *levels) {
+                  hipStream_t stream, const ptc::DeviceTimer *timer, int *levels) {
     int rc = check_temporal_params(prm);
     if (rc != PT_OK) return rc;
     pt::DenoiseArgs da;
@@ -114,16 +107,11 @@ int enqueue_chain(pt_temporal *t, const ptc::AccumPlanes &frame, const pt_tempor
     if (dn && (rc = ptc::denoise_params_to_args(dn, da)) != PT_OK) return rc;
     *levels = da.levels;
     pt_scene *scene = t->scene;
-    const size_t n = t->n;
     if (da.levels > 0 && !t->d_denoise) {
         ptc::PlaneLayout l;
-        const size_t o_a0 = l.add(16 * n), o_a1 = l.add(16 * n), o_b = l.add(16 * n), o_c = l.add(16 * n), o_mean = l.add(12 * n), o_cnt = l.add(4 * n);
-        rc = t->d_denoise.alloc(l, "pt_temporal_push_host");
-        if (rc != PT_OK) return rc;
-        const ptc::DeviceBuffer &d = t->d_denoise;
-        t->dn_a0 = d.at<void>(o_a0); t->dn_a1 = d.at<void>(o_a1); t->dn_b = d.at<void>(o_b); t->dn_c = d.at<void>(o_c);
-        t->d_mean = d.at<float>(o_mean);
-        t->d_mean_count = d.at<int32_t>(o_cnt);
+        t->denoise = ptc::DenoisePlanes::in(l, t->n);
+        if ((rc = t->d_denoise.alloc(l, "pt_temporal_push_host")) != PT_OK) return rc;
+        t->denoise.bind(t->d_denoise);
     }
     const pt_camera cam = ptc::view_camera(scene);
     pt::TemporalArgs a;
@@ -136,26 +124,21 @@ int enqueue_chain(pt_temporal *t, const ptc::AccumPlanes &frame, const pt_tempor
     std::memcpy(a.cam, &cam, sizeof a.cam);
     std::memcpy(a.prev_origin, t->camera.origin, sizeof a.prev_origin);
     std::memcpy(a.prev_inverse, t->inverse, sizeof a.prev_inverse);
-    a.sum = frame.sum; a.sum2 = frame.sum2; a.count = frame.count;
-    a.position = t->d_position; a.normal = t->d_normal; a.hit_index = t->d_hit;
     a.prev = t->rec[t->cur]; a.next = t->rec[t->cur ^ 1];
+    a.sum = frame.sum; a.sum2 = frame.sum2; a.count = frame.count;
+    a.position = t->features.position; a.normal = t->features.normal; a.hit_index = t->features.hit;
     a.sum_out = t->out.sum; a.sum2_out = t->out.sum2; a.count_out = t->out.count; a.history_frames = t->d_frames;
     da.width = t->width; da.height = t->height;
-    da.sum = t->out.sum; da.sum2 = t->out.sum2; da.count = t->out.count;
-    da.position = t->d_position; da.normal = t->d_normal; da.albedo = t->d_albedo; da.hit_index = t->d_hit;
-    da.rec_a0 = t->dn_a0; da.rec_a1 = t->dn_a1; da.rec_b = t->dn_b; da.rec_c = t->dn_c;
-    da.mean_rgb = t->d_mean; da.count_out = t->d_mean_count;
+    ptc::bind_planes(da, t->out, t->features, t->denoise);
 
     std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
     pt::RenderArgs ra;
     if ((rc = ptc::scene_trace_args(scene, t->eps, ra)) != PT_OK) return rc;
-    if (ev0) PT_HIP_TRY(hipEventRecord(ev0, stream));
-    rc = ptc::enqueue_first_hits(scene, ra, cam, t->width, t->height, 0, t->height, t->d_origins, t->d_directions, t->d_hit, t->d_hit_t,
-                                 t->d_position, t->d_normal, t->d_albedo, stream);
-    if (rc != PT_OK) return rc;
+    if (timer) PT_HIP_TRY(timer->begin(stream));
+    if ((rc = ptc::enqueue_first_hits(scene, ra, cam, t->width, t->height, 0, t->height, t->features, stream)) != PT_OK) return rc;
     PT_HIP_TRY(pt::launch_temporal_merge(a, stream));
     if (da.levels > 0) PT_HIP_TRY(pt::launch_denoise(da, stream));
-    if (ev1) PT_HIP_TRY(hipEventRecord(ev1, stream));
+    if (timer) PT_HIP_TRY(timer->end(stream));
     t->pending_camera = cam;
     return PT_OK;
 }
@@ -182,16 +165,14 @@ int temporal_push_impl(pt_temporal *t, const float *sum, const float *sum2, cons
     std::lock_guard<std::mutex> push_lock(t->mutex);
     if ((rc = t->in.upload(sum, sum2, count)) != PT_OK) return rc;
     int levels = 0;
-    if ((rc = enqueue_chain(t, t->in, prm, dn, nullptr, t->ev0.get(), t->ev1.get(), &levels)) != PT_OK) return rc;
+    if ((rc = enqueue_chain(t, t->in, prm, dn, nullptr, &t->timer, &levels)) != PT_OK) return rc;
     // (an error return from here on leaves the history the previous one: rec[cur] was only read)
-    PT_HIP_TRY(hipEventSynchronize(t->ev1.get()));
     float ms = 0.0f;
-    PT_HIP_TRY(hipEventElapsedTime(&ms, t->ev0.get(), t->ev1.get()));
+    PT_HIP_TRY(t->timer.wait_ms(&ms));
     if ((rc = t->out.download(sum_out, sum2_out, count_out)) != PT_OK) return rc;
     if (history_frames) PT_HIP_TRY(hipMemcpy(history_frames, t->d_frames, 4 * n, hipMemcpyDeviceToHost));
     if (dn && levels > 0) {
-        if (mean_rgb) PT_HIP_TRY(hipMemcpy(mean_rgb, t->d_mean, 12 * n, hipMemcpyDeviceToHost));
-        if (mean_count) PT_HIP_TRY(hipMemcpy(mean_count, t->d_mean_count, 4 * n, hipMemcpyDeviceToHost));
+        if ((rc = t->denoise.out.download(mean_rgb, mean_count)) != PT_OK) return rc;
     } else if (dn && mean_rgb) {   // levels = 0: the unfiltered mean of the merged accumulators, on the host
         std::vector<float> s(3 * n);
         std::vector<int32_t> c(n);
@@ -212,12 +193,12 @@ int ptc::temporal_enqueue(pt_temporal *t, const AccumPlanes &frame, const pt_tem
     PT_HIP_TRY(hipSetDevice(t->scene->device));
     std::lock_guard<std::mutex> push_lock(t->mutex);
     int levels = 0;
-    const int rc = enqueue_chain(t, frame, prm, dn, stream, nullptr, nullptr, &levels);
+    const int rc = enqueue_chain(t, frame, prm, dn, stream, nullptr, &levels);
     if (rc != PT_OK) return rc;
     out->merged = t->out;
     out->history_frames = t->d_frames;
-    out->mean = levels > 0 ? t->d_mean : nullptr;
-    out->mean_count = levels > 0 ? t->d_mean_count : nullptr;
+    out->mean = levels > 0 ? t->denoise.out.rgb : nullptr;
+    out->mean_count = levels > 0 ? t->denoise.out.count : nullptr;
     return PT_OK;
 }
 

@@ -1,9 +1,11 @@
 // pt_device_mem.hpp on the CPU, under AddressSanitizer + UBSan: the plane layout is a pure function of sizes and gives the
 // allocation sizes the host layer had when they were written out by hand; the owners free exactly once, an empty owner makes
-// no HIP call, a failed allocation leaves nothing behind.  Built and run by tests/test_device_mem_host.py; the six HIP calls
-// the header makes are stubbed here and count themselves.
+// no HIP call, a failed allocation leaves nothing behind; the views of the plane sets lay out what the entry points had, and the
+// timer owns its two events.  Built and run by tests/test_device_mem_host.py; the HIP calls the header makes are stubbed here
+// and count themselves.
 #include "pt_device_mem.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <set>
 #include <utility>
@@ -12,7 +14,8 @@
 static int g_mallocs = 0, g_frees = 0, g_event_destroys = 0, g_stream_destroys = 0, g_double_frees = 0;
 static bool g_fail_malloc = false;
 static std::set<void *> g_blocks;   // what the stubbed hipMalloc handed out and hipFree has not seen yet
-static char g_arena[64];            // tagged pointers: block k is &g_arena[k] (never dereferenced)
+static char g_arena[8192];          // tagged pointers: block k is &g_arena[k] (never dereferenced); room for the views of one pixel
+static int g_records = 0, g_syncs = 0, g_copies = 0;
 
 extern "C" {
 hipError_t hipMalloc(void **p, size_t) {
@@ -26,12 +29,15 @@ hipError_t hipFree(void *p) {
     if (!g_blocks.erase(p)) ++g_double_frees;
     return hipSuccess;
 }
-hipError_t hipMemcpy(void *, const void *, size_t, hipMemcpyKind) { return hipSuccess; }
+hipError_t hipMemcpy(void *, const void *, size_t, hipMemcpyKind) { return ++g_copies, hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
     *e = reinterpret_cast<hipEvent_t>(&g_arena[1]);
     return hipSuccess;
 }
 hipError_t hipEventDestroy(hipEvent_t) { return ++g_event_destroys, hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return ++g_records, hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t) { return ++g_syncs, hipSuccess; }
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { return *ms = 2.5f, hipSuccess; }
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) {
     *s = reinterpret_cast<hipStream_t>(&g_arena[2]);
     return hipSuccess;
@@ -57,10 +63,15 @@ int hip_fail(hipError_t e, const char *) {   // pt_capi.cpp's mapping
     } while (0)
 
 using ptc::AccumPlanes;
+using ptc::DenoisePlanes;
 using ptc::DeviceBuffer;
 using ptc::DeviceEvent;
 using ptc::DeviceStream;
+using ptc::DeviceTimer;
+using ptc::FeaturePlanes;
+using ptc::MeanPlanes;
 using ptc::PlaneLayout;
+using ptc::UpsamplePlanes;
 
 static long live() { return ptc::g_live_device_objects.load(); }
 static size_t up(size_t b) { return (b + 255) / 256 * 256; }
@@ -82,6 +93,146 @@ static bool add_accum(PlaneLayout &l, size_t n, size_t &prev_end) {
         prev_end = a.offset[k] + bytes[k];
     }
     return a.n == n && l.end == prev_end;
+}
+
+// The planes of a view as (offset, bytes), for the same checks: whatever order the view adds them in, each starts on a multiple
+// of 256 at or behind the end of the plane before it, and the last one added ends the layout.
+using Spans = std::vector<std::pair<size_t, size_t>>;
+static Spans spans(const MeanPlanes &m) { return {{m.offset[0], 12 * m.n}, {m.offset[1], 4 * m.n}}; }
+static Spans spans(const FeaturePlanes &f) {
+    Spans s = {{f.offset[0], 12 * f.n}, {f.offset[1], 12 * f.n}, {f.offset[2], 12 * f.n}, {f.offset[3], 4 * f.n}};
+    if (f.traced) s.insert(s.end(), {{f.offset[4], 12 * f.n}, {f.offset[5], 12 * f.n}, {f.offset[6], 4 * f.n}});
+    return s;
+}
+static Spans spans(const DenoisePlanes &w) {
+    Spans s = spans(w.out);
+    for (size_t o : w.offset) s.push_back({o, 16 * w.out.n});
+    return s;
+}
+static Spans spans(const UpsamplePlanes &w) {
+    Spans s = {{w.offset[0], 16 * w.n_lo}, {w.offset[1], 16 * w.n_lo}, {w.offset[2], 16 * w.n_lo}};
+    if (w.own_mean) s.push_back({w.offset[3], 12 * w.n_lo});
+    return s;
+}
+static size_t pixels(const MeanPlanes &m) { return m.n; }
+static size_t pixels(const FeaturePlanes &f) { return f.n; }
+static size_t pixels(const DenoisePlanes &w) { return w.out.n; }
+static size_t pixels(const UpsamplePlanes &w) { return w.n_lo; }
+static bool spans_ok(Spans s, const PlaneLayout &l, size_t &prev_end) {
+    std::sort(s.begin(), s.end());
+    for (const auto &p : s) {
+        if (p.first % 256 != 0 || p.first < prev_end) return false;
+        prev_end = p.first + p.second;
+    }
+    return l.end == prev_end;
+}
+template <class View, class... More>
+static bool add_view(PlaneLayout &l, size_t n, size_t &prev_end, size_t planes, More... more) {
+    const View v = View::in(l, n, more...);
+    return pixels(v) == n && spans(v).size() == planes && spans_ok(spans(v), l, prev_end);
+}
+
+// The views as the entry points compose them: the totals are the sums those places wrote out by hand.
+static int test_views() {
+    for (size_t n : {size_t(1), size_t(63), size_t(64), size_t(65), size_t(2073600)}) {
+        const size_t b12 = up(12 * n), b4 = up(4 * n), b16 = up(16 * n);
+        {   // pt_denoise_host: the accumulators, the uploaded features, the denoiser's planes
+            PlaneLayout l;
+            size_t e = 0;
+            EXPECT(add_accum(l, n, e));
+            const FeaturePlanes f = FeaturePlanes::uploaded_in(l, n);
+            EXPECT(f.n == n && !f.traced && spans(f).size() == 4 && spans_ok(spans(f), l, e));
+            EXPECT(add_view<DenoisePlanes>(l, n, e, 6));
+            EXPECT(l.total() == 6 * b12 + 3 * b4 + 4 * b16 && l.total() >= e);
+        }
+        {   // pt_temporal_create: the frame's and the merged accumulators, the view's features, the frame counts, eight records
+            PlaneLayout l;
+            size_t e = 0;
+            EXPECT(add_accum(l, n, e) && add_accum(l, n, e) && add_view<FeaturePlanes>(l, n, e, 7));
+            EXPECT(add_planes(l, 1, 4 * n, e) && add_planes(l, 8, 16 * n, e));
+            EXPECT(l.total() == 9 * b12 + 5 * b4 + 8 * b16 && l.total() >= e);
+        }
+        {   // the temporal stage's denoiser planes
+            PlaneLayout l;
+            size_t e = 0;
+            EXPECT(add_view<DenoisePlanes>(l, n, e, 6));
+            EXPECT(l.total() == 4 * b16 + b12 + b4 && l.total() >= e);
+        }
+        {   // the display's filter planes: the view's features, the denoiser's planes
+            PlaneLayout l;
+            size_t e = 0;
+            EXPECT(add_view<FeaturePlanes>(l, n, e, 7) && add_view<DenoisePlanes>(l, n, e, 6));
+            EXPECT(l.total() == 6 * b12 + 3 * b4 + 4 * b16 && l.total() >= e);
+        }
+        for (size_t s : {size_t(2), size_t(3), size_t(4)}) {
+            if (n % (s * s)) continue;
+            const size_t n_lo = n / (s * s);
+            {   // a scaled present: the output's features, mean and count; the low mean and the records
+                PlaneLayout l;
+                size_t e = 0;
+                EXPECT(add_view<FeaturePlanes>(l, n, e, 7) && add_view<MeanPlanes>(l, n, e, 2) && add_view<UpsamplePlanes>(l, n_lo, e, 4, true));
+                EXPECT(l.total() == 6 * b12 + 3 * b4 + up(12 * n_lo) + 3 * up(16 * n_lo) && l.total() >= e);
+            }
+            {   // pt_upsample_host: the low image, the uploaded features, the output's mean and count, the records
+                PlaneLayout l;
+                size_t e = 0;
+                EXPECT(add_view<MeanPlanes>(l, n_lo, e, 2));
+                const FeaturePlanes f = FeaturePlanes::uploaded_in(l, n);
+                EXPECT(f.n == n && spans(f).size() == 4 && spans_ok(spans(f), l, e));
+                EXPECT(add_view<MeanPlanes>(l, n, e, 2) && add_view<UpsamplePlanes>(l, n_lo, e, 3, false));
+                EXPECT(l.total() == up(12 * n_lo) + up(4 * n_lo) + 4 * b12 + 2 * b4 + 3 * up(16 * n_lo) && l.total() >= e);
+            }
+        }
+    }
+    {   // bind makes pointers of the offsets; what a view did not lay out stays NULL; a NULL side skips its plane's copy
+        PlaneLayout l;
+        FeaturePlanes f = FeaturePlanes::in(l, 1), g = FeaturePlanes::uploaded_in(l, 1);
+        DenoisePlanes w = DenoisePlanes::in(l, 1);
+        UpsamplePlanes u = UpsamplePlanes::in(l, 1, true), v = UpsamplePlanes::in(l, 1, false);
+        DeviceBuffer b;
+        EXPECT(l.total() <= sizeof g_arena - 64 && b.alloc(l, "views") == PT_OK);
+        f.bind(b); g.bind(b); w.bind(b); u.bind(b); v.bind(b);
+        char *const base = b.get<char>();
+        EXPECT((char *)f.position == base + f.offset[0] && (char *)f.normal == base + f.offset[1] && (char *)f.albedo == base + f.offset[2]);
+        EXPECT((char *)f.hit == base + f.offset[3] && (char *)f.origins == base + f.offset[4] && (char *)f.directions == base + f.offset[5]);
+        EXPECT((char *)f.hit_t == base + f.offset[6]);
+        EXPECT(!g.origins && !g.directions && !g.hit_t && (char *)g.position == base + g.offset[0] && (char *)g.hit == base + g.offset[3]);
+        EXPECT((char *)w.rec_a0 == base + w.offset[0] && (char *)w.rec_c == base + w.offset[3] && (char *)w.out.rgb == base + w.out.offset[0]);
+        EXPECT((char *)w.out.count == base + w.out.offset[1]);
+        EXPECT((char *)u.rec_a == base + u.offset[0] && (char *)u.rec_c == base + u.offset[2] && (char *)u.mean_lo == base + u.offset[3] && !v.mean_lo);
+        EXPECT((char *)v.rec_b == base + v.offset[1]);
+        float x[3] = {0, 0, 0};
+        int32_t i = 0;
+        g_copies = 0;
+        FeaturePlanes some, all;
+        some.hit = all.hit = &i;
+        some.position = all.position = all.normal = all.albedo = all.hit_t = x;
+        EXPECT(f.download(some) == PT_OK && g_copies == 2 && f.download(all) == PT_OK && g_copies == 7);
+        EXPECT(g.upload(x, x, x, &i) == PT_OK && g_copies == 11 && g.download(all) == PT_OK && g_copies == 15);   // (g has no hit_t plane)
+        EXPECT(w.out.download(x, nullptr) == PT_OK && g_copies == 16 && w.out.upload(x, &i) == PT_OK && g_copies == 18);
+    }
+    EXPECT(live() == 0);
+    return 0;
+}
+
+static int test_timer() {
+    const int destroyed = g_event_destroys;
+    {
+        DeviceTimer empty, moved_to(std::move(empty));   // (no event: no HIP call)
+        EXPECT(g_event_destroys == destroyed && live() == 0);
+        DeviceTimer t;
+        EXPECT(t.create("timer") == PT_OK && live() == 2);
+        EXPECT(t.create("again") == PT_OK && live() == 2 && g_event_destroys == destroyed + 2);   // the first pair went
+        float ms = 0.0f;
+        EXPECT(t.begin(nullptr) == hipSuccess && t.end(nullptr) == hipSuccess && g_records == 2 && g_syncs == 0);
+        EXPECT(t.wait_ms(&ms) == hipSuccess && g_syncs == 1 && ms == 2.5f);
+        DeviceTimer u(std::move(t));
+        EXPECT(live() == 2 && g_event_destroys == destroyed + 2);
+        moved_to = std::move(u);
+        EXPECT(live() == 2 && g_event_destroys == destroyed + 2);
+    }
+    EXPECT(g_event_destroys == destroyed + 4 && live() == 0);
+    return 0;
 }
 
 static int test_layout() {
@@ -172,7 +323,7 @@ static int test_owners() {
 }
 
 int main() {
-    if (test_layout() || test_owners()) return 1;
+    if (test_layout() || test_owners() || test_views() || test_timer()) return 1;
     std::printf("device mem ok\n");
     return 0;
 }

@@ -175,3 +175,33 @@ def test_refused_calls_leave_the_count_alone(hooks, models_dir):
         assert _denoise(hooks, W, H, z3, z3, zi, f, 9)[0] == pt.PT_ERR_INVALID_ARGUMENT
         assert hooks.pt_frame_create(g._h, pt._ip(devs), 1, 16, 16, 0, C.byref(h)) == 4 and not h.value     # PT_ERR_NO_DEVICE
     g.close()
+
+
+def test_display_reaches_every_lazy_plane_set_of_one_handle(hooks, models_dir):
+    """One display, every plane set it allocates on demand: the filter planes, the temporal stage with its denoiser planes, the
+    scaled planes at two scales (the second replaces the first), the bloom pyramids of both output sizes.  All of it goes with
+    the handle, and what an earlier present allocated does not reach a later result."""
+    W, H = 24, 16
+    g = _tor(hooks, models_dir)
+    ses = pt.Session(g, W, H)
+    ses.render(0, 2, 8)                                             # (the scene's own cull tables exist from here on)
+    look = {"grade": {"curve": "aces", "auto_exposure": True}, "bloom": {"strength": 0.5}}
+    with balanced(hooks):
+        d = pt.Display(ses)
+        created = hooks.pt_test_live_device_objects()
+        assert d.present()[0].shape == (H, W, 3)
+        d.present(denoise={"levels": 2})
+        d.present(temporal=True, denoise={"levels": 2})
+        scaled, _ = d.present(upsample={"scale": 2})
+        assert d.present(upsample={"scale": 3})[0].shape == (3 * H, 3 * W, 3)
+        d.present(**look)
+        assert d.present(upsample={"scale": 2}, **look)[0].shape == (2 * H, 2 * W, 3)
+        assert hooks.pt_test_live_device_objects() > created
+        fresh = pt.Display(ses)
+        want, _ = fresh.present(upsample={"scale": 2})
+        fresh.close()
+        d.reset()
+        d.close()
+    assert scaled.shape == (2 * H, 2 * W, 3) and scaled.any() and np.array_equal(scaled, want)
+    ses.close()
+    g.close()
