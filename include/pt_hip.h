@@ -751,6 +751,85 @@ int pt_display_present_bloom(pt_display *d, const pt_display_params *p, const pt
                              const pt_grade_params *g, const pt_bloom_params *b, uint8_t *bgr, pt_display_info *info /* may be NULL */,
                              pt_grade_info *grade_info /* may be NULL */);
 
+/* ---- local exposure: edge-aware dodge and burn before the tone curve ---------------------------------------- */
+
+/* One exposure and one curve serve a picture whose parts differ by orders of magnitude badly: the exposure opens for the dark part
+ * and the curve flattens the bright one, or the other way round.  Local exposure is one stage BEFORE the grade and AFTER bloom,
+ * mean -> mean, on the linear ungraded mean at the output size: every pixel is multiplied by a gain g that depends on a smooth,
+ * edge-stopped base of the luminance around it.  Where the base is brighter than the pivot the pixel is pulled down, where it is
+ * darker it is lifted; the detail m / base is untouched, because g depends on the base alone.  The meter sees the picture before
+ * bloom and before this stage.
+ *
+ * The arithmetic, exactly: every line below is ONE correctly rounded float operation in the order written (* / + -, comparisons);
+ * nothing is fused, and there is no log, exp or pow -- the operator is rational, for the reason the denoiser's weights are.
+ *
+ * Inputs.  m = the pixel's linear mean (a chain row that ends in sums: m = sum / (float)n, as the display chain divides; with bloom,
+ * bloom's output), its count, the exposure e (manual or from the meter), and the parameters strength c, pivot, levels L, sigma.
+ *
+ * Luminance plane, at W x H.  A pixel with count == 0 is INVALID.  Otherwise
+ *   l = ((0.2126 m_r) + (0.7152 m_g)) + (0.0722 m_b)          (the meter's luminance)
+ *   if !(l >= 0) or !(l <= 2^64):  INVALID  (negative, NaN, +inf or too large; 2^64 keeps every sum and product below finite)
+ *   else  b_0 = l.
+ * An invalid pixel is invalid at every level, is never a tap, gets g = 1 and keeps its value, NaN or infinity included.
+ *
+ * Base, k = 0 .. L-1: one level of the 5 x 5 B3 spline h = (1 4 6 4 1)/16 at tap spacing 2^k, edge-stopped.  For a valid pixel
+ * p = (x, y):  sw = 0, sd = 0, and for dy = -2 .. 2, for dx = -2 .. 2 (in that order), q = (x + dx 2^k, y + dy 2^k); a q outside
+ * the image or invalid is skipped; otherwise, with bp = b_k(p), bq = b_k(q):
+ *   d  = bq - bp
+ *   mn = bq < bp ? bq : bp
+ *   s  = (sigma * mn) + 1e-30
+ *   r  = d / s
+ *   wr = 1 / (1 + (r * r))
+ *   w  = (h_dy * h_dx) * wr          (h_dy * h_dx is exact: a multiple of 1/256)
+ *   sw = sw + w
+ *   sd = sd + (w * d)
+ * and then  b_{k+1}(p) = bp + (sd / sw).  The centre tap needs no special case: d = 0 gives r = 0 and wr = 1 exactly, so sw >= 36/256.
+ * This is the denoiser's form: a constant plane has every d = 0 and stays constant to the bit.  The range term is relative to
+ * the SMALLER of the two values: across an edge of ratio R the weight falls like sigma^2 / (R - 1)^2, so what leaks across, weight
+ * times difference, shrinks as the edge grows (a term relative to bp + bq would saturate at sigma^2 and leak more the stronger the
+ * edge).  Every b_k is a weighted mean of values in 0 .. 2^64 in which the pixel's own value has at least 36/256 of the weight, so
+ * it stays finite and never falls below zero (the kernels mark an invalid pixel by a negative value in the plane of b_k and rely
+ * on that), and no step gives inf - inf, inf / inf or 0 / 0: an r beyond FLT_MAX is +-inf, its wr is 0.
+ *
+ * Gain and output.  A valid pixel gets
+ *   a = b_L * e
+ *   g = (1 + c) / (1 + ((c * a) / pivot))
+ *   out_ch = m_ch * g          per channel;
+ * the others keep their value, as pt_grade_host leaves them.  g = 1 where the exposed base equals the pivot, at most 1 + c (a
+ * black base), and falls with the base: a bright region is pulled towards pivot (1 + c) / c.
+ *
+ * Parameters; a zeroed struct means the stage does not run:
+ *   strength    c; 0: the stage is not run (the bytes are those of pt_display_present_bloom)   (negative or non-finite: invalid)
+ *   pivot       0 = 0.18                                                                       (negative or non-finite: invalid)
+ *   levels      0 = 5; else 1 .. PT_LOCAL_MAX_LEVELS                                           (outside: invalid)
+ *   sigma       0 = 0.5                                                                        (negative or non-finite: invalid)
+ * Any image size from 1 x 1 is valid. */
+#define PT_LOCAL_MAX_LEVELS 8
+typedef struct pt_local_params {
+    float strength;
+    float pivot;
+    int32_t levels;
+    float sigma;
+} pt_local_params;
+
+/* The local exposure kernels alone, on a host image: out_rgb (may be mean_rgb) = the output above for (mean_rgb, count), made on
+ * HIP device `device`; kernel_ms (may be NULL) = HIP-event time of the L + 2 kernels.  Buffers, sizes, `exposure` (finite and > 0; 0
+ * is NOT a default here, as in pt_grade_host) and *l are checked BEFORE the device is looked at; PT_ERR_NO_DEVICE afterwards if that
+ * is not a usable device (there is no CPU fallback).  With strength == 0 it copies. */
+int pt_local_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure,
+                  const pt_local_params *l, float *out_rgb, float *kernel_ms);
+/* pt_display_present_bloom with local exposure: the same chain with the local exposure kernels between bloom's and the display
+ * kernel, on the session's stream with no host synchronisation inside; the gain reads e from the device scalar the display kernel
+ * reads.  The bytes are DEFINED by the host chain and equal it bit for bit: the row of the tables above up to the linear mean and
+ * count, then, if automatic, pt_meter_host -> pt_exposure_from_histogram on the mean BEFORE bloom, then
+ * pt_bloom_host(e) -> pt_local_host(e) -> pt_grade_host(e, curve) -> pt_tonemap -> pt_quantize, at the output size (after the
+ * upsample if u is given).  *b and *l are checked with *g, before anything is enqueued and before the device is looked at; a failed
+ * present leaves the history and the previous exposure as they were.  A deferred pixel carries the locally exposed ungraded mean
+ * the display kernel read, and the host grades that.  With a zeroed *l the call is pt_display_present_bloom. */
+int pt_display_present_local(pt_display *d, const pt_display_params *p, const pt_upsample_params *u /* NULL: not scaled */,
+                             const pt_grade_params *g, const pt_bloom_params *b, const pt_local_params *l, uint8_t *bgr,
+                             pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

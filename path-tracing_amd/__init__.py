@@ -47,7 +47,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_upsample_host", "pt_display_present_scaled",
                "pt_grade_host", "pt_meter_host", "pt_exposure_from_histogram", "pt_display_present_graded",
                "pt_display_bytes_graded_host",
-               "pt_bloom_host", "pt_display_present_bloom"]
+               "pt_bloom_host", "pt_display_present_bloom",
+               "pt_local_host", "pt_display_present_local"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -193,6 +194,21 @@ def _bloom_params(bloom):
     if isinstance(bloom, dict):
         return BloomParams(bloom.get("threshold", 0.0), bloom.get("strength", 0.0), bloom.get("levels", 0))
     return bloom
+
+
+LOCAL_MAX_LEVELS = 8
+
+
+class LocalParams(C.Structure):
+    """pt_local_params: a zeroed struct is no local exposure (strength 0); pivot 0 = 0.18, levels 0 = 5 (1 .. 8), sigma 0 = 0.5."""
+    _fields_ = [("strength", C.c_float), ("pivot", C.c_float), ("levels", C.c_int32), ("sigma", C.c_float)]
+
+
+def _local_params(local):
+    """A LocalParams, or a dict of its fields ({"strength": 1.0}) -> a LocalParams."""
+    if isinstance(local, dict):
+        return LocalParams(local.get("strength", 0.0), local.get("pivot", 0.0), local.get("levels", 0), local.get("sigma", 0.0))
+    return local
 
 
 def _lens_arg(radius, focus_distance):
@@ -345,6 +361,9 @@ def load_library(path):
     L.pt_bloom_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(BloomParams), fp, fp]
     L.pt_display_present_bloom.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
                                            bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_local_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(LocalParams), fp, fp]
+    L.pt_display_present_local.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
+                                           C.POINTER(LocalParams), bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -678,7 +697,7 @@ class Display:
         create = self._L.pt_display_create_frame if isinstance(session_or_frame, Frame) else self._L.pt_display_create
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
-    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None):
+    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
         parameters.  Returns (bgr uint8 [H, W, 3], info dict).
@@ -687,7 +706,9 @@ class Display:
         `grade`: None, a GradeParams, or a dict of its fields ({"curve": "aces", "auto_exposure": True}) -- pt_display_present_graded:
         exposure and a tone curve before the tone map; info then also holds exposure, target, metered, dark.
         `bloom`: None, a BloomParams, or a dict of its fields ({"strength": 0.5}) -- pt_display_present_bloom: the light above the
-        threshold spread over its neighbourhood before the grade (`grade` None: no grading at all, as a zeroed GradeParams)."""
+        threshold spread over its neighbourhood before the grade (`grade` None: no grading at all, as a zeroed GradeParams).
+        `local`: None, a LocalParams, or a dict of its fields ({"strength": 1.0}) -- pt_display_present_local: a gain per pixel from
+        an edge-aware base of the luminance, after bloom and before the grade (`grade`, `bloom` None: zeroed, as above)."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -696,13 +717,17 @@ class Display:
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
         info = DisplayInfo()
-        if grade is not None or bloom is not None:
+        if grade is not None or bloom is not None or local is not None:
             gp, ginfo = _grade_params(grade) if grade is not None else GradeParams(), GradeInfo()
             up = _upsample_params(upsample) if upsample is not None else None
             k = up.scale if up is not None and 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1
             bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8)
             up_arg, out = C.byref(up) if up is not None else None, bgr.ctypes.data_as(C.POINTER(C.c_uint8))
-            if bloom is not None:
+            if local is not None:
+                bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local)
+                _check(self._L.pt_display_present_local(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), C.byref(lp), out, C.byref(info),
+                                                        C.byref(ginfo)), self._L)
+            elif bloom is not None:
                 bp_ = _bloom_params(bloom)
                 _check(self._L.pt_display_present_bloom(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), out, C.byref(info),
                                                         C.byref(ginfo)), self._L)
@@ -785,6 +810,18 @@ def bloom(device, mean_rgb, count, exposure=1.0, threshold=1.0, strength=0.5, le
     out, ms = np.zeros_like(m), C.c_float()
     prm = BloomParams(threshold, strength, levels)
     _check(L.pt_bloom_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), C.byref(prm), _fp(out), C.byref(ms)), L)
+    return (out, ms.value) if want_ms else out
+
+
+def local_exposure(device, mean_rgb, count, exposure=1.0, strength=1.0, pivot=0.18, levels=5, sigma=0.5, want_ms=False, library=None):
+    """pt_local_host: the local exposure kernels alone on a host image mean_rgb [H, W, 3] with count [H, W] -- mean * g, the gain g
+    = (1 + strength) / (1 + strength * base * exposure / pivot) from an edge-aware base of the luminance (`levels` levels of a 5 x 5
+    spline, range weight `sigma`); and the kernels' milliseconds as a second value if want_ms."""
+    L = library or lib()
+    m, c = _image_args("local_exposure", mean_rgb, count)
+    out, ms = np.zeros_like(m), C.c_float()
+    prm = LocalParams(strength, pivot, levels, sigma)
+    _check(L.pt_local_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), C.byref(prm), _fp(out), C.byref(ms)), L)
     return (out, ms.value) if want_ms else out
 
 

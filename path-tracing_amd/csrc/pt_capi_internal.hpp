@@ -1,7 +1,7 @@
 // What the translation units behind the C ABI share (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters; pt_frame.cpp: the
 // multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
-// pt_grade_capi.cpp, pt_bloom_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident display path, which
-// chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
+// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
+// display path, which chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
 // arguments, and the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments.
 // Nothing here is part of the ABI.
 #pragma once
@@ -207,6 +207,16 @@ struct BloomSetup {
     float weight = 0.0f;      // strength / (float)L
 };
 int bloom_params_check(const pt_bloom_params *b, BloomSetup &out);
+
+// pt_local_params as every entry point checks them (no device is touched), with the defaults filled in (pt_local_capi.cpp).
+struct LocalSetup {
+    bool on = false;          // strength > 0: the stage runs
+    float strength = 0.0f;    // c
+    float pivot = 0.18f;
+    int levels = 5;           // L
+    float sigma = 0.5f;
+};
+int local_params_check(const pt_local_params *l, LocalSetup &out);
 
 // pt_temporal_push_host in two halves, for a chain whose frame already lies on the device (pt_display_present).
 // temporal_enqueue checks the parameters and enqueues features -> merge -> filter on `stream`, reading the frame's accumulators

@@ -3,6 +3,7 @@
 // pixels the kernel leaves to the host.  With grading (pt_display_present_graded): the meter and the exposure kernel before the
 // display kernel, the exposure in a device scalar, and deferred pixels finished through pt_grade.hpp.  With bloom
 // (pt_display_present_bloom): the bloom kernels between the exposure and the display kernel, which then reads the bloomed means.
+// With local exposure (pt_display_present_local): its kernels behind bloom's, on the plane of means bloom wrote or on the chain's image.
 #include "pt_capi_internal.hpp"
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include "pt_bloom.hpp"
 #include "pt_display.hpp"
 #include "pt_display_table.hpp"
+#include "pt_local.hpp"
 #include "pt_meter.hpp"
 
 using ptc::fail;
@@ -67,7 +69,8 @@ struct GradeRequest {
     bool has_prev = false;
     float e_prev = 0.0f;
     ptc::BloomSetup bloom;   // on: the bloom kernels run between the exposure and the display kernel
-    int32_t width = 0, height = 0;   // of the image the display kernel reads (bloom needs its shape)
+    ptc::LocalSetup local;   // on: the local exposure kernels run behind them
+    int32_t width = 0, height = 0;   // of the image the display kernel reads (bloom and local exposure need its shape)
 };
 
 // The image a chain has reached: planes on the device, sums still (divide) or means.
@@ -92,10 +95,15 @@ struct DisplayDevice {
     ptc::DeviceBuffer d_bloom;
     void *pyramid = nullptr;
     float *bloomed = nullptr;
+    // local exposure: the two planes of the base and the plane of locally exposed means, allocated by the first present with the stage
+    ptc::DeviceBuffer d_local;
+    float *local_base[2] = {nullptr, nullptr};
+    float *localised = nullptr;
 
     int alloc(size_t pixels, const char *what) {
         n = pixels;
         d_bloom.reset();   // (of another size's image)
+        d_local.reset();
         ptc::PlaneLayout l;
         const size_t o_bgr = l.add((n + 3) / 4 * 12), o_list = l.add(16 * n), o_len = l.add(4);
         const size_t o_grade = l.add(kGradeBytes);
@@ -115,6 +123,15 @@ struct DisplayDevice {
         const int rc = d_bloom.alloc(l, what);
         if (rc != PT_OK) return rc;
         bloomed = d_bloom.at<float>(o_out); pyramid = d_bloom.at<void>(o_pyr);
+        return PT_OK;
+    }
+    int ensure_local(const char *what) {
+        if (d_local) return PT_OK;
+        ptc::PlaneLayout l;
+        const size_t o_out = l.add(12 * n), o_b0 = l.add(4 * n), o_b1 = l.add(4 * n);
+        const int rc = d_local.alloc(l, what);
+        if (rc != PT_OK) return rc;
+        localised = d_local.at<float>(o_out); local_base[0] = d_local.at<float>(o_b0); local_base[1] = d_local.at<float>(o_b1);
         return PT_OK;
     }
     // (no kernel of this object is in flight: every call that launches one waits for it)
@@ -176,6 +193,15 @@ struct DisplayDevice {
             b.pyramid = pyramid; b.out_rgb = bloomed;
             PT_HIP_TRY(pt::launch_bloom(b, stream));
             a.rgb = bloomed; a.divide = 0;
+        }
+        if (grade->local.on) {   // ... and then m * g of that plane, or of the chain's image
+            pt::LocalArgs l;
+            l.width = grade->width; l.height = grade->height; l.levels = grade->local.levels; l.divide = a.divide;
+            l.rgb = a.rgb; l.count = a.count; l.exposure = &exposure->exposure;
+            l.strength = grade->local.strength; l.pivot = grade->local.pivot; l.sigma = grade->local.sigma;
+            l.base[0] = local_base[0]; l.base[1] = local_base[1]; l.out_rgb = localised;
+            PT_HIP_TRY(pt::launch_local(l, stream));
+            a.rgb = localised; a.divide = 0;
         }
         PT_HIP_TRY(pt::launch_display_graded(a, grade->setup.curve, &exposure->exposure, stream));
         return PT_OK;
@@ -309,6 +335,7 @@ struct PresentRequest {
     const pt_upsample_params *upsample;   // the same chain at the display's size, then the upsample to scale times it
     const pt_grade_params *grade;         // the exposure and the graded kernel in place of the display kernel
     const pt_bloom_params *bloom;         // with grade only
+    const pt_local_params *local;         // with grade only
     pt_grade_info *grade_info;            // with grade only; may be NULL
 };
 
@@ -322,6 +349,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     GradeRequest grade;
     if (graded && (rc = ptc::grade_params_check(rq.grade, grade.setup)) != PT_OK) return rc;
     if (rq.bloom && (rc = ptc::bloom_params_check(rq.bloom, grade.bloom)) != PT_OK) return rc;
+    if (rq.local && (rc = ptc::local_params_check(rq.local, grade.local)) != PT_OK) return rc;
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -351,6 +379,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if ((rc = dev.use_table(table, "pt_display_present")) != PT_OK) return rc;
     grade.width = scaled ? ua.width : d->width; grade.height = scaled ? ua.height : d->height;
     if (grade.bloom.on && (rc = dev.ensure_bloom(grade.width, grade.height, "pt_display_present_bloom")) != PT_OK) return rc;
+    if (grade.local.on && (rc = dev.ensure_local("pt_display_present_local")) != PT_OK) return rc;
     if (temporal && !d->history && (rc = pt_temporal_create(scene, d->width, d->height, d->eps, &d->history)) != PT_OK) return rc;
     if (filter && !temporal && (rc = ensure_filter(d)) != PT_OK) return rc;
     {   // the chain, behind every slice enqueued so far: no host synchronisation until its last kernel is in the queue
@@ -495,21 +524,26 @@ int pt_display_create_frame(pt_frame *frame, float eps, pt_display **out) {
 }
 
 int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return display_present_impl(d, {p, nullptr, nullptr, nullptr, nullptr}, bgr, info); });
+    return guarded([&] { return display_present_impl(d, {p, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info); });
 }
 
 int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return u ? display_present_impl(d, {p, u, nullptr, nullptr, nullptr}, bgr, info) : null_argument(); });
+    return guarded([&] { return u ? display_present_impl(d, {p, u, nullptr, nullptr, nullptr, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_graded(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g, uint8_t *bgr,
                               pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g ? display_present_impl(d, {p, u, g, nullptr, grade_info}, bgr, info) : null_argument(); });
+    return guarded([&] { return g ? display_present_impl(d, {p, u, g, nullptr, nullptr, grade_info}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_bloom(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                              const pt_bloom_params *b, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g && b ? display_present_impl(d, {p, u, g, b, grade_info}, bgr, info) : null_argument(); });
+    return guarded([&] { return g && b ? display_present_impl(d, {p, u, g, b, nullptr, grade_info}, bgr, info) : null_argument(); });
+}
+
+int pt_display_present_local(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
+                             const pt_bloom_params *b, const pt_local_params *l, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
+    return guarded([&] { return g && b && l ? display_present_impl(d, {p, u, g, b, l, grade_info}, bgr, info) : null_argument(); });
 }
 
 int pt_display_reset(pt_display *d) {

@@ -1,0 +1,83 @@
+// Host side of local exposure (include/pt_hip.h: pt_local_host): the parameter check every entry point with the stage shares, and
+// the kernels alone on a host image.  The arithmetic is pt_local.hip's; there is no host copy of it (the suite restates the header
+// in numpy).
+#include "pt_capi_internal.hpp"
+
+#include <cmath>
+#include <cstring>
+
+#include "pt_local.hpp"
+
+using ptc::fail;
+using ptc::guarded;
+using ptc::hip_fail;
+
+static_assert(PT_LOCAL_MAX_LEVELS == pt::kLocalMaxLevels, "the ABI header states the deepest base");
+
+int ptc::local_params_check(const pt_local_params *l, LocalSetup &out) {
+    if (!l) return fail(PT_ERR_INVALID_ARGUMENT, "local: null params");
+    auto bad = [](float v) { return !std::isfinite(v) || v < 0.0f; };
+    if (bad(l->strength) || bad(l->pivot) || bad(l->sigma))
+        return fail(PT_ERR_INVALID_ARGUMENT, "local: strength must be finite and not negative, pivot and sigma finite and > 0 (0 = the default)");
+    if (l->levels < 0 || l->levels > pt::kLocalMaxLevels) return fail(PT_ERR_INVALID_ARGUMENT, "local: levels must lie in 1 .. 8 (0 = 5)");
+    LocalSetup s;
+    s.on = l->strength > 0.0f;
+    s.strength = l->strength;
+    s.pivot = l->pivot > 0.0f ? l->pivot : 0.18f;
+    s.levels = l->levels > 0 ? l->levels : 5;
+    s.sigma = l->sigma > 0.0f ? l->sigma : 0.5f;
+    out = s;
+    return PT_OK;
+}
+
+namespace {
+
+int local_host_impl(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure, const pt_local_params *p,
+                    float *out_rgb, float *kernel_ms) {
+    if (width <= 0 || height <= 0 || !mean_rgb || !count || !out_rgb) return fail(PT_ERR_INVALID_ARGUMENT, "local: null buffer or empty image");
+    int rc = ptc::check_image_size(width, height, "local: ");
+    if (rc != PT_OK) return rc;
+    if (!std::isfinite(exposure) || !(exposure > 0.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "local: exposure must be finite and > 0");
+    ptc::LocalSetup setup;
+    if ((rc = ptc::local_params_check(p, setup)) != PT_OK) return rc;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if ((rc = ptc::use_device(device, "local")) != PT_OK) return rc;
+    const size_t n = static_cast<size_t>(width) * height;
+    if (!setup.on) {
+        if (out_rgb != mean_rgb) std::memmove(out_rgb, mean_rgb, 12 * n);
+        return PT_OK;
+    }
+    ptc::PlaneLayout l;
+    ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
+    const size_t o_e = l.add(4), o_out = l.add(12 * n), o_b0 = l.add(4 * n), o_b1 = l.add(4 * n);
+    ptc::DeviceBuffer d;
+    ptc::DeviceTimer timer;
+    if ((rc = d.alloc(l, "pt_local_host")) != PT_OK || (rc = timer.create("pt_local_host")) != PT_OK) return rc;
+    in.bind(d);
+    if ((rc = in.upload(mean_rgb, count)) != PT_OK) return rc;
+    PT_HIP_TRY(hipMemcpy(d.at<void>(o_e), &exposure, 4, hipMemcpyHostToDevice));
+    pt::LocalArgs a;
+    a.width = width; a.height = height; a.levels = setup.levels; a.divide = 0;
+    a.rgb = in.rgb; a.count = in.count; a.exposure = d.at<float>(o_e);
+    a.strength = setup.strength; a.pivot = setup.pivot; a.sigma = setup.sigma;
+    a.base[0] = d.at<float>(o_b0); a.base[1] = d.at<float>(o_b1); a.out_rgb = d.at<float>(o_out);
+    PT_HIP_TRY(timer.begin(nullptr));
+    PT_HIP_TRY(pt::launch_local(a, nullptr));
+    PT_HIP_TRY(timer.end(nullptr));
+    float ms = 0.0f;
+    PT_HIP_TRY(timer.wait_ms(&ms));
+    PT_HIP_TRY(hipMemcpy(out_rgb, a.out_rgb, 12 * n, hipMemcpyDeviceToHost));
+    if (kernel_ms) *kernel_ms = ms;
+    return PT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pt_local_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure, const pt_local_params *p,
+                  float *out_rgb, float *kernel_ms) {
+    return guarded([&] { return local_host_impl(device, width, height, mean_rgb, count, exposure, p, out_rgb, kernel_ms); });
+}
+
+}  // extern "C"

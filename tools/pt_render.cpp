@@ -71,8 +71,14 @@
 // the grade is the reference's: no curve, e = 1); previews stay unbloomed.
 // It works on the host path and with -DEVICE_RESOLVE 1, with byte-identical files, and with every flag grading works with.
 // Without -BLOOM, or with -BLOOM 0, nothing changes.
+// Local exposure (pt_local_host, pt_display_present_local, not in the reference): -LOCAL <strength, default 0: off> multiplies every
+// pixel by a gain from an edge-aware base of the luminance around it -- above -LOCAL_PIVOT <luminance after exposure, default 0.18>
+// it is pulled down, below it lifted by at most 1 + strength -- made with -LOCAL_LEVELS <1 .. 8, default 5> levels of a 5 x 5
+// spline whose range weight is -LOCAL_SIGMA <default 0.5>, on the linear mean at the written size, after bloom and before the
+// grade (alone it runs with the zeroed grade, as -BLOOM does); previews stay as they are.  It works on the host path and with
+// -DEVICE_RESOLVE 1, with byte-identical files, and with every flag grading works with.  Without -LOCAL, or with -LOCAL 0, nothing changes.
 // The image chain is stated once, in HostChain::bytes, in the order the paragraphs above give: temporal merge -> first-hit
-// features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> meter, bloom, grade -> tone map
+// features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> meter, bloom, local exposure, grade -> tone map
 // -> -GAUSS / -MEDIAN -> quantize.  A single frame and every frame of a sequence go through it; with -DEVICE_RESOLVE 1 the
 // bytes come from present() instead.
 #include <algorithm>
@@ -121,6 +127,7 @@ struct Options {
     pt_denoise_params denoise{};   // -DENOISE (levels, 0 = off), -DN_SIGMA_L, -DN_SIGMA_P
     pt_temporal_params temporal{}; // -TEMPORAL: max_frames of the history, 0 = no temporal stage
     pt_bloom_params bloom{};       // -BLOOM, -BLOOM_THRESHOLD, -BLOOM_LEVELS
+    pt_local_params local{};       // -LOCAL, -LOCAL_PIVOT, -LOCAL_LEVELS, -LOCAL_SIGMA
     pt_upsample_params upsample{};
     pt_grade_params grade{};       // zeroed without -TONE / -EXPOSURE / -AUTO_EXPOSURE: the reference's bytes
     pt_display_params show{};      // what a present of the device path is asked for
@@ -130,7 +137,7 @@ struct Options {
     bool sequence = false;         // -FRAMES > 1 or -TEMPORAL
     bool merging = false;          // -TEMPORAL > 0
     bool display = false;          // -DEVICE_RESOLVE 1 and nothing that keeps the image on the host path
-    bool blooming = false, grading = false;   // -BLOOM > 0; that, or any of the tone flags
+    bool blooming = false, localising = false, grading = false;   // -BLOOM > 0; -LOCAL > 0; either, or any of the tone flags
     pt_camera view;                // with `camera`
     pt_lens lens{0.0f, 0.0f};
     bool has_lens = false;
@@ -202,6 +209,10 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-BLOOM") o.bloom.strength = static_cast<float>(std::atof(v));
         if (f == "-BLOOM_THRESHOLD") o.bloom.threshold = static_cast<float>(std::atof(v));
         if (f == "-BLOOM_LEVELS") o.bloom.levels = std::atoi(v);
+        if (f == "-LOCAL") o.local.strength = static_cast<float>(std::atof(v));
+        if (f == "-LOCAL_PIVOT") o.local.pivot = static_cast<float>(std::atof(v));
+        if (f == "-LOCAL_LEVELS") o.local.levels = std::atoi(v);
+        if (f == "-LOCAL_SIGMA") o.local.sigma = static_cast<float>(std::atof(v));
     }
 }
 
@@ -307,7 +318,12 @@ int configure(int argc, char **argv, Options &o) {
         o.bloom.levels < 0 || o.bloom.levels > PT_BLOOM_MAX_LEVELS)
         return refuse(2, "-BLOOM and -BLOOM_THRESHOLD take a number >= 0, -BLOOM_LEVELS 1 .. " + std::to_string(PT_BLOOM_MAX_LEVELS));
     o.blooming = o.bloom.strength > 0.0f;
-    o.grading = o.tone_flags || o.blooming;
+    // -LOCAL: the same, behind bloom
+    if (!(std::isfinite(o.local.strength) && o.local.strength >= 0.0f) || !(std::isfinite(o.local.pivot) && o.local.pivot >= 0.0f) ||
+        !(std::isfinite(o.local.sigma) && o.local.sigma >= 0.0f) || o.local.levels < 0 || o.local.levels > PT_LOCAL_MAX_LEVELS)
+        return refuse(2, "-LOCAL, -LOCAL_PIVOT and -LOCAL_SIGMA take a number >= 0, -LOCAL_LEVELS 1 .. " + std::to_string(PT_LOCAL_MAX_LEVELS));
+    o.localising = o.local.strength > 0.0f;
+    o.grading = o.tone_flags || o.blooming || o.localising;
     // -TONE / -EXPOSURE / -AUTO_EXPOSURE: what every graded image is asked for
     if (o.tone_flags) {
         const char *names[4] = {"reference", "clamp", "reinhard", "aces"};
@@ -418,10 +434,11 @@ struct HostFrame {
     uint8_t *image() { return out_bgr.empty() ? bgr.data() : out_bgr.data(); }
 };
 
-// The device path's present: plain, scaled, or either with grading or bloom
+// The device path's present: plain, scaled, or either with grading, bloom or local exposure
 int present(const Run &r, HostFrame &host, pt_display_info *info) {
     const Options &o = r.o;
     const pt_upsample_params *up = o.scale > 1 ? &o.upsample : nullptr;
+    if (o.localising) return pt_display_present_local(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, host.image(), info, nullptr);
     if (o.blooming) return pt_display_present_bloom(r.display, &o.show, up, &o.grade, &o.bloom, host.image(), info, nullptr);
     if (o.grading) return pt_display_present_graded(r.display, &o.show, up, &o.grade, host.image(), info, nullptr);
     return up ? pt_display_present_scaled(r.display, &o.show, up, host.image(), info) : pt_display_present(r.display, &o.show, host.image(), info);
@@ -532,7 +549,7 @@ bool HostChain::bytes(HostFrame &host, float dispersion[3], ChainTimes &times) {
         m = up_mean.data(); n = up_count.data();
     }
     rgb.resize(3 * static_cast<size_t>(w) * h);
-    if (o.grading) {   // meter (a sequence's frame starts from the previous frame's exposure), bloom, grade
+    if (o.grading) {   // meter (a sequence's frame starts from the previous frame's exposure), bloom, local exposure, grade
         float e = o.grade.exposure > 0.0f ? o.grade.exposure : 1.0f, target = 0.0f;   // (0 = 1, as the library reads it)
         if (o.grade.auto_exposure) {
             uint32_t hist[PT_METER_ENTRIES];
@@ -544,6 +561,10 @@ bool HostChain::bytes(HostFrame &host, float dispersion[3], ChainTimes &times) {
         }
         if (o.blooming) {
             if (pt_bloom_host(dev, w, h, m, n, e, &o.bloom, rgb.data(), nullptr) != PT_OK) return false;
+            m = rgb.data();
+        }
+        if (o.localising) {
+            if (pt_local_host(dev, w, h, m, n, e, &o.local, rgb.data(), nullptr) != PT_OK) return false;
             m = rgb.data();
         }
         if (pt_grade_host(w, h, m, n, e, o.grade.curve, rgb.data()) != PT_OK) return false;
