@@ -29,7 +29,7 @@
  * pt_render_device / pt_render_host share the scene's scheduler state and are ordered on the device; every pt_session has
  * its own, so sessions of ONE scene (row bands of an image) run side by side, and launches of different scenes are
  * independent anyway.  Calls on one pt_session / pt_frame are serialised by the caller.  pt_scene_set_skybox_bmp,
- * pt_scene_set_camera, pt_scene_set_lens and pt_scene_destroy must not race with a render of the same scene.
+ * pt_scene_set_camera, pt_scene_set_lens, pt_scene_set_camera_motion and pt_scene_destroy must not race with a render of the same scene.
  * Several GPUs: pt_frame_* (below) renders one image on the devices of one node from one host program -- row bands, one RCCL
  * group of sends / receives to the root -- the counterpart of the reference's `omp parallel for` over rows, main.cpp:115,132,141.
  */
@@ -211,6 +211,45 @@ int pt_scene_set_lens(pt_scene *scene, const pt_lens *lens);
 /* The handle's lens; *is_set = 0 (and zeros in *lens) if it has none.  Either pointer may be NULL. */
 int pt_scene_get_lens(const pt_scene *scene, pt_lens *lens, int32_t *is_set);
 
+/* ---- camera motion (motion blur) ------------------------------------------------------------------ */
+
+/* A camera that moves while the shutter is open: a second pt_camera, the END pose; the START pose is the handle's camera or,
+ * without one, the reference's.  Every path draws its own time in the shutter interval and sees the camera interpolated there.
+ * With a = start and b = end, each as 12 floats (origin, right, up, forward), the primary ray of pixel (x, y), pass p is
+ *   t       = unit_float(w0'),  w0' = word 0 of the Philox counter (pixel, p, 0xFFFFFFFE, 0)   (same key; t in [2^-24, 1))
+ *   delta_j = b_j - a_j                                          (one float subtraction per component, on the host)
+ *   c_j(t)  = a_j + t * delta_j                                  (one product and one sum in float, nothing fused; j = 0 .. 11)
+ * and then everything pt_camera states with c(t) in place of the camera: D = (u * right + v * up) + forward, the origin c_origin(t),
+ * normalize as there.  The words w0..w3 of counter (pixel, p, 0xFFFFFFFF, 0) keep their meaning (jitter, lens) and no segment
+ * word changes: with the same seed, a frame with motion and one without draw the same numbers for everything else.
+ * With a lens, r^, u^, f^ are computed for a and for b exactly as pt_lens states (in double, rounded to float once), their
+ * per-component float differences are taken on the host, and the axes are interpolated the same way,
+ *   r^_j(t) = r^a_j + t * (r^b_j - r^a_j),   likewise u^ and f^;
+ * the pt_lens formulas then run with c(t) and these axes.  The interpolated axes are NOT renormalised: for a rotation of theta
+ * within one shutter their length is at least cos(theta / 2) (the chord's midpoint), so the disc shrinks by at most that factor.
+ * An end pose equal to the start pose bit for bit is no motion: the handle then launches exactly the kernels it launches without.
+ * The motion belongs to the scene HANDLE, like the camera and the lens: copies made from it afterwards (pt_scene_clone_to_device,
+ * pt_frame_create) inherit it, and a launch uses the motion its handle has when it is enqueued.  Setting it must not race with a
+ * render of the same handle.  First-hit features, the temporal reprojection and every pt_display stage read the START pose and
+ * ignore the motion, as they ignore the lens. */
+
+/* Sets the handle's camera motion; NULL (or an end pose equal to the handle's camera bit for bit) removes it.  Checked on the host,
+ * in double, so that no t in [0, 1] gives a zero or non-finite D or a zero D . f^:
+ *   PT_ERR_INVALID_ARGUMENT  `end` fails a check of pt_scene_set_camera (or, with a lens, of pt_scene_set_lens); or one of the
+ *                            eight determinants det(right_X, up_Y, forward_Z), X, Y, Z in {start, end}, has |det| <= 1e-6 |right_X|
+ *                            |up_Y| |forward_Z| or a sign other than the rest (det of the interpolated axes is a combination of the
+ *                            eight with non-negative weights that sum to 1); or, with a lens, one of the four pairs (X, Y) has
+ *                            forward_X . f^_Y <= |right_X . f^_Y| + |up_X . f^_Y| (D(t) . f^(t) is such a combination of them)
+ *   PT_ERR_UNSUPPORTED       an origin component of `end` beyond PT_CAMERA_MAX_ORIGIN and the scene's largest |vertex coordinate|,
+ *                            or an origin between the poses that could lie beyond the bound: per component the larger of the two
+ *                            poses' values (with a lens, of |origin_i| + radius sqrt(r^_i^2 + u^_i^2), each pose with its own axes),
+ *                            times 1 + 2^-18 for the rounding of a component that moves or lies in the disc
+ * pt_scene_set_camera and pt_scene_set_lens apply the same checks to the motion the handle already has.  A failed call leaves the
+ * handle as it was. */
+int pt_scene_set_camera_motion(pt_scene *scene, const pt_camera *end);
+/* The handle's end pose; *is_set = 0 (and the start pose in *end) if it has no motion.  Either pointer may be NULL. */
+int pt_scene_get_camera_motion(const pt_scene *scene, pt_camera *end, int32_t *is_set);
+
 int pt_scene_counts(const pt_scene *scene, int32_t *n_triangles, int32_t *n_materials);
 int pt_scene_get_triangles(const pt_scene *scene, float *triangles, int32_t *triangle_material);
 int pt_scene_get_materials(const pt_scene *scene, float *materials);
@@ -298,6 +337,8 @@ int pt_frame_clear(pt_frame *frame);
 int pt_frame_set_camera(pt_frame *frame, const pt_camera *camera);
 /* pt_scene_set_lens on every device's copy of the frame's scene (NULL: no lens), likewise. */
 int pt_frame_set_lens(pt_frame *frame, const pt_lens *lens);
+/* pt_scene_set_camera_motion on every device's copy of the frame's scene (NULL: no motion), likewise. */
+int pt_frame_set_camera_motion(pt_frame *frame, const pt_camera *end);
 void pt_frame_destroy(pt_frame *frame);
 /* Can RCCL be loaded and does it export what the gather calls?  version = ncclGetVersion's.  Needs no GPU. */
 int pt_rccl_available(int32_t *version);
@@ -309,7 +350,7 @@ int pt_rccl_available(int32_t *version);
  * directions (normalised as Ray's constructor does, ray.h:23) and origins with max |component| <= max(20, largest
  * |component of the handle's camera origin|, largest |vertex coordinate|) + 1 (the camera -- the reference's at (0,0,-20)
  * unless pt_scene_set_camera set one --, or a point on a surface; with a lens, max_i(|origin_i| + radius sqrt(r^_i^2 + u^_i^2))
- * plus a rounding allowance instead of the origin).  A ray outside that envelope
+ * plus a rounding allowance instead of the origin; with a camera motion, the larger of the two poses' values).  A ray outside that envelope
  * (| |d|^2 - 1 | > 1e-5, a farther origin) is answered by the reference's own loop over ALL triangles on the
  * device instead, so every finite ray gets the reference's answer; only the speed differs.  A ray with a non-finite
  * component misses (all its distances are NaN, see the deviation below).
@@ -334,7 +375,7 @@ int pt_trace_rays_host(pt_scene *scene, int32_t n_rays, const float *origins, co
  *   u = x / W - 0.5,  v = -y / H + 0.5                          (in double, then rounded to float)
  *   d = normalize((u * right + v * up) + forward)               (componentwise in float, nothing fused; d * (1 / sqrt((x x + y y) + z z)))
  * from `origin`, with the handle's camera or, without one, the reference's.  The handle's LENS IS IGNORED: features are those
- * of the pinhole view and stay sharp.  Then
+ * of the pinhole view and stay sharp.  So is its CAMERA MOTION: features are those of the start pose.  Then
  *   hit_index, hit_t = what pt_trace_rays_host answers for that ray (-1 / +inf on a miss; its known deviation applies)
  *   position         = origin + d * hit_t                       (componentwise in float: one product, one sum)
  *   normal           = the hit triangle's stored plane normal (Triangle::GetNormal, triangles.h: plane_[0..2]; NOT flipped
@@ -464,7 +505,7 @@ int pt_upsample_host(int device, int32_t width, int32_t height, const float *mea
  * [i * RPP, (i + 1) * RPP) with one seed, so that the frames' samples are independent.
  *
  * A pt_temporal belongs to the scene handle it was created for (which must outlive it) and keeps its history on that handle's
- * device.  A push reads the handle's CAMERA AT THE TIME OF THE CALL (the lens is ignored, as for the features), renders the
+ * device.  A push reads the handle's CAMERA AT THE TIME OF THE CALL (the lens and the camera motion are ignored, as for the features), renders the
  * feature buffers of that view on the device exactly as pt_render_features_host states them (eps from the create call), merges,
  * stores the new history and -- if `denoise` is given -- runs the filter of pt_denoise_host on the merged planes and those
  * features, all in one chain on the device: only the accumulators go up and only the requested outputs come down.  kernel_ms =
@@ -542,7 +583,7 @@ void pt_temporal_destroy(pt_temporal *t);
  *   temporal != 0, denoise.levels > 0  pt_temporal_push_host with `denoise` -> pt_tonemap -> pt_quantize, with mean_count
  * Every present with temporal != 0 pushes one frame into the display's own history, exactly as one pt_temporal_push_host call
  * would; a failed present leaves the history as it was.  A present reads the handle's camera at the time of the call (the lens
- * is ignored, as for the features); `eps` of the create call is the features'.
+ * and the camera motion are ignored, as for the features); `eps` of the create call is the features'.
  *
  * How the device can equal std::pow: for gamma > 0, L(m) = (int)(pow(m, gamma) * 255.0f) is a non-decreasing step function of
  * m >= 0, so L(m) is the number of thresholds T_k <= m, T_k being the smallest float with L >= k, and the byte is L(m) & 255

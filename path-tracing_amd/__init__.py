@@ -40,6 +40,7 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_band_rows", "pt_session_create_strided", "pt_frame_row_stride",
                "pt_camera_look_at", "pt_scene_set_camera", "pt_scene_get_camera", "pt_frame_set_camera",
                "pt_scene_set_lens", "pt_scene_get_lens", "pt_frame_set_lens",
+               "pt_scene_set_camera_motion", "pt_scene_get_camera_motion", "pt_frame_set_camera_motion",
                "pt_render_features_host", "pt_denoise_host", "pt_tonemap",
                "pt_temporal_create", "pt_temporal_push_host", "pt_temporal_reset", "pt_temporal_destroy",
                "pt_display_create", "pt_display_create_frame", "pt_display_present", "pt_display_reset", "pt_display_destroy",
@@ -331,6 +332,9 @@ def load_library(path):
     L.pt_scene_set_lens.argtypes = [vp, C.POINTER(Lens)]
     L.pt_scene_get_lens.argtypes = [vp, C.POINTER(Lens), ip]
     L.pt_frame_set_lens.argtypes = [vp, C.POINTER(Lens)]
+    L.pt_scene_set_camera_motion.argtypes = [vp, C.POINTER(Camera)]
+    L.pt_scene_get_camera_motion.argtypes = [vp, C.POINTER(Camera), ip]
+    L.pt_frame_set_camera_motion.argtypes = [vp, C.POINTER(Camera)]
     L.pt_render_features_host.argtypes = [vp, C.POINTER(RenderParams), ip, fp, fp, fp, fp]
     L.pt_denoise_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, fp, ip, fp, fp, fp, ip, C.POINTER(DenoiseParams), fp, ip, fp]
     L.pt_tonemap.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, fp]
@@ -493,6 +497,21 @@ class Scene:
         lens, is_set = Lens(), C.c_int32()
         _check(self._L.pt_scene_get_lens(self._h, C.byref(lens), C.byref(is_set)), self._L)
         return lens if is_set.value else None
+
+    def set_camera_motion(self, end_camera):
+        """pt_scene_set_camera_motion: the camera moves from the handle's camera to `end_camera` (a Camera or its four vectors)
+        while the shutter is open, every path at a time of its own; None, or an end pose equal to the camera, = no motion.
+        The handle's camera, lens and motion are checked against one another whenever one is set: before moving the camera of a
+        handle that has a motion, clear the motion (None), then set_camera, then the new end pose."""
+        if end_camera is not None and not isinstance(end_camera, Camera):
+            end_camera = Camera.of(*end_camera)
+        _check(self._L.pt_scene_set_camera_motion(self._h, C.byref(end_camera) if end_camera is not None else None), self._L)
+
+    def get_camera_motion(self):
+        """The handle's end pose (a Camera), or None if it has no motion."""
+        end, is_set = Camera(), C.c_int32()
+        _check(self._L.pt_scene_get_camera_motion(self._h, C.byref(end), C.byref(is_set)), self._L)
+        return end if is_set.value else None
 
     def cull_tables(self, eps=1e-4):
         """The culling hierarchy for `eps` (diagnostics): dict of clusters, spheres, bary records, constants."""
@@ -927,6 +946,12 @@ class Frame:
     def set_lens(self, radius, focus_distance=None):
         """pt_frame_set_lens: the lens of every device's copy of the frame's scene (None = a pinhole)."""
         _check(self._L.pt_frame_set_lens(self._h, _lens_arg(radius, focus_distance)), self._L)
+
+    def set_camera_motion(self, end_camera):
+        """pt_frame_set_camera_motion: the end pose of every device's copy of the frame's scene (None = no motion)."""
+        if end_camera is not None and not isinstance(end_camera, Camera):
+            end_camera = Camera.of(*end_camera)
+        _check(self._L.pt_frame_set_camera_motion(self._h, C.byref(end_camera) if end_camera is not None else None), self._L)
 
     def band_kernel_ms(self):
         """Kernel time of every band of the last render(want_stats=True), -1 where there is none."""

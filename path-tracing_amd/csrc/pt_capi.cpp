@@ -159,9 +159,36 @@ double lens_extent(const pt_camera &c, const pt_lens &l) {
     return e;
 }
 
+// Does the handle's camera move during a launch?  An end pose equal to the start pose bit for bit is no motion (pt_hip.h).
+bool motion_active(const pt_scene *s) { return s->has_motion && std::memcmp(&view_camera(s), &s->motion_end, sizeof(pt_camera)) != 0; }
+
+// The same bound for a camera that moves from a to b (pt_hip.h: camera motion), with lens l or none: per component the larger of
+// the two poses' values, each pose with its own axes.  Both |o_i(t)| and sqrt(r^_i(t)^2 + u^_i(t)^2) are convex in t (the absolute
+// value and the Euclidean norm of functions linear in t), so their largest value over [0, 1] is taken at an end.  A component that
+// moves gets lens_extent's rounding allowance (o_i + t * delta_i adds three roundings to its dozen); one that neither moves nor
+// lies in the disc keeps |o_i| exactly.
+double motion_extent(const pt_camera &a, const pt_camera &b, const pt_lens *l) {
+    float axa[9] = {0}, axb[9] = {0};
+    if (l) {
+        lens_axes(a, axa);
+        lens_axes(b, axb);
+    }
+    double e = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        const double lata = std::sqrt(static_cast<double>(axa[i]) * axa[i] + static_cast<double>(axa[3 + i]) * axa[3 + i]);
+        const double latb = std::sqrt(static_cast<double>(axb[i]) * axb[i] + static_cast<double>(axb[3 + i]) * axb[3 + i]);
+        const double radius = l ? static_cast<double>(l->radius) : 0.0;
+        double ei = std::max(std::fabs(static_cast<double>(a.origin[i])) + radius * lata, std::fabs(static_cast<double>(b.origin[i])) + radius * latb);
+        if (lata > 0.0 || latb > 0.0 || std::memcmp(&a.origin[i], &b.origin[i], sizeof(float)) != 0) ei *= 1.0 + 0x1p-18;
+        e = std::max(e, ei);
+    }
+    return e;
+}
+
 // The envelope radius for the cull tables (get_cull): the largest |component| of every origin a primary ray can have -- 20 for
 // the reference's camera at (0, 0, -20).
 double camera_radius(const pt_scene *s) {
+    if (motion_active(s)) return std::max(20.0, motion_extent(view_camera(s), s->motion_end, s->has_lens ? &s->lens : nullptr));
     if (s->has_lens) return std::max(20.0, lens_extent(view_camera(s), s->lens));
     if (!s->has_camera) return 20.0;
     const float *o = s->camera.origin;
@@ -248,7 +275,8 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
     a.emis_clusters = t.emis_clusters;
     a.emis_large_w0 = t.emis_large_w0;
     a.emis_bvh = t.emis_bvh ? 1u : 0u;
-    if (scene->has_camera || scene->has_lens) {   // the camera twins of the kernels (pt_kernels.hip: integrate_kernel<..., ADAPT | 1>)
+    const bool moving = motion_active(scene);
+    if (scene->has_camera || scene->has_lens || moving) {   // the camera twins of the kernels (pt_kernels.hip: integrate_kernel<..., ADAPT | 1>)
         a.camera = 1;
         std::memcpy(a.cam, &view_camera(scene), sizeof a.cam);
     }
@@ -257,6 +285,18 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
         a.lns[0] = scene->lens.radius;
         a.lns[1] = scene->lens.focus_distance;
         lens_axes(view_camera(scene), a.lns + 2);
+    }
+    if (moving) {   // the motion twins of either (integrate_kernel_motion, integrate_kernel_motion_lens): end - start, one float subtraction each
+        a.motion = 1;
+        float end_pose[12];
+        static_assert(sizeof end_pose == sizeof(pt_camera), "pt_camera: twelve floats");
+        std::memcpy(end_pose, &scene->motion_end, sizeof end_pose);
+        for (int j = 0; j < 12; ++j) a.cam_d[j] = end_pose[j] - a.cam[j];
+        if (scene->has_lens) {
+            float end_axes[9];
+            lens_axes(scene->motion_end, end_axes);
+            for (int j = 0; j < 9; ++j) a.lns_d[j] = end_axes[j] - a.lns[2 + j];
+        }
     }
 }
 
@@ -298,7 +338,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     }
     // one wave = one tile of 8 rows; how many pixels wide depends on the kernel this launch runs
     const pt::plan::Tiles tiles = pt::plan::plan_tiles({a.width, a.band_rows, a.sky != nullptr, a.big != 0, want_stats, a.may_leave_envelope != 0, a.error,
-                                                        a.pass_begin, a.pass_count, a.lens ? 2 : a.camera ? 1 : 0, scene->cu_count},
+                                                        a.pass_begin, a.pass_count, pt::plan::view_of(a.camera != 0, a.lens != 0, a.motion != 0), scene->cu_count},
                                                        pt::integrator_build(), ov);
     a.narrow = tiles.narrow;
     a.adapt_pool = tiles.adapt_pool;
@@ -551,6 +591,8 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->camera = src->camera;
     s->has_lens = src->has_lens;       // and lens
     s->lens = src->lens;
+    s->has_motion = src->has_motion;   // and camera motion
+    s->motion_end = src->motion_end;
     if (device >= 0) {
         const int rc = upload(s.get(), device);
         if (rc != PT_OK) return rc;
@@ -678,6 +720,8 @@ static int check_lens_on(const pt_camera &c, const pt_lens &l) {
     return PT_OK;
 }
 
+static int recheck_motion(const pt_scene *scene, const pt_camera &cam, const pt_lens *l);   // (below, with the motion's checks)
+
 // NULL or radius 0: back to the pinhole.  Checks everything before it changes anything.
 static int scene_set_lens_impl(pt_scene *scene, const pt_lens *lens) {
     if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
@@ -686,13 +730,17 @@ static int scene_set_lens_impl(pt_scene *scene, const pt_lens *lens) {
         if (lens->radius < 0.0f) return fail(PT_ERR_INVALID_ARGUMENT, "lens: negative radius");
     }
     if (!lens || lens->radius == 0.0f) {
+        const int mrc = recheck_motion(scene, view_camera(scene), nullptr);   // (without a lens the origin bound is the camera's)
+        if (mrc != PT_OK) return mrc;
         scene->has_lens = false;
         scene->lens = pt_lens{};
         return PT_OK;
     }
     if (!(lens->focus_distance > 0.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "lens: the focus distance must be positive");
-    const int rc = check_lens_on(view_camera(scene), *lens);
+    int rc = check_lens_on(view_camera(scene), *lens);
     if (rc != PT_OK) return rc;
+    if (scene->has_motion && (rc = check_lens_on(scene->motion_end, *lens)) != PT_OK) return rc;
+    if ((rc = recheck_motion(scene, view_camera(scene), lens)) != PT_OK) return rc;
     scene->lens = *lens;
     scene->has_lens = true;
     return PT_OK;
@@ -705,6 +753,57 @@ static int scene_get_lens_impl(const pt_scene *scene, pt_lens *lens, int32_t *is
     return PT_OK;
 }
 
+// Can the camera move from a to b within one launch (pt_hip.h: camera motion), with lens l or none?  Every axis is linear in t, so
+// det(right(t), up(t), forward(t)) is a combination, with non-negative weights that sum to 1, of the eight mixed determinants
+// det(right_X, up_Y, forward_Z), X, Y, Z in {a, b}: with all eight of one sign and away from 0 no t in [0, 1] makes the axes
+// dependent, and D = u right + v up + forward (coefficient 1 on forward) cannot vanish.  Likewise D(t) . f^(t) is such a combination
+// of D_X . f^_Y, each positive in the image if forward_X . f^_Y > |right_X . f^_Y| + |up_X . f^_Y|.
+static int check_motion(const pt_scene *scene, const pt_camera &a, const pt_lens *l, const pt_camera &b) {
+    const pt_camera *pose[2] = {&a, &b};
+    auto len = [](const float *v) { return std::sqrt(static_cast<double>(v[0]) * v[0] + static_cast<double>(v[1]) * v[1] + static_cast<double>(v[2]) * v[2]); };
+    int sign = 0;
+    for (int k = 0; k < 8; ++k) {
+        const float *rf = pose[k & 1]->right, *uf = pose[(k >> 1) & 1]->up, *ff = pose[k >> 2]->forward;
+        const double r[3] = {rf[0], rf[1], rf[2]}, u[3] = {uf[0], uf[1], uf[2]}, f[3] = {ff[0], ff[1], ff[2]};
+        const double det = r[0] * (u[1] * f[2] - u[2] * f[1]) - r[1] * (u[0] * f[2] - u[2] * f[0]) + r[2] * (u[0] * f[1] - u[1] * f[0]);
+        if (!(std::fabs(det) > 1e-6 * len(rf) * len(uf) * len(ff)))
+            return fail(PT_ERR_INVALID_ARGUMENT, "camera motion: right, up and forward can become linearly dependent between the two poses");
+        const int sg = det > 0.0 ? 1 : -1;
+        if (sign != 0 && sg != sign)
+            return fail(PT_ERR_INVALID_ARGUMENT, "camera motion: the orientation of right, up and forward changes between the two poses");
+        sign = sg;
+    }
+    if (l) {
+        float ax[2][9];
+        lens_axes(a, ax[0]);
+        lens_axes(b, ax[1]);
+        for (int x = 0; x < 2; ++x)
+            for (int y = 0; y < 2; ++y) {
+                const float *fh = ax[y] + 6;
+                double rf = 0.0, uf = 0.0, ff = 0.0;
+                for (int i = 0; i < 3; ++i) {
+                    rf += static_cast<double>(pose[x]->right[i]) * fh[i];
+                    uf += static_cast<double>(pose[x]->up[i]) * fh[i];
+                    ff += static_cast<double>(pose[x]->forward[i]) * fh[i];
+                }
+                if (!(ff > std::fabs(rf) + std::fabs(uf)))
+                    return fail(PT_ERR_INVALID_ARGUMENT, "camera motion: a view direction can reach the lens plane between the two poses (forward . f <= |right . f| + |up . f|)");
+            }
+    }
+    const double bound = l ? static_cast<double>(PT_CAMERA_MAX_ORIGIN) : std::max(static_cast<double>(PT_CAMERA_MAX_ORIGIN), scene->shared->vertex_extent);
+    if (!(motion_extent(a, b, l) <= bound))
+        return fail(PT_ERR_UNSUPPORTED, "camera motion: an origin between the two poses could lie beyond PT_CAMERA_MAX_ORIGIN (" + std::to_string(PT_CAMERA_MAX_ORIGIN) + ")");
+    return PT_OK;
+}
+
+static int check_camera(const pt_scene *scene, const pt_camera *cam);
+
+// The motion the handle has against a camera and lens it is about to get (an end pose equal to the new camera is no motion).
+static int recheck_motion(const pt_scene *scene, const pt_camera &cam, const pt_lens *l) {
+    if (!scene->has_motion || std::memcmp(&cam, &scene->motion_end, sizeof cam) == 0) return PT_OK;
+    return check_motion(scene, cam, l, scene->motion_end);
+}
+
 // NULL: back to the reference's camera.  Checks everything before it changes anything.
 static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
     if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
@@ -713,10 +812,23 @@ static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
             const int rc = check_lens_on(kReferenceCamera, scene->lens);
             if (rc != PT_OK) return rc;
         }
+        const int mrc = recheck_motion(scene, kReferenceCamera, scene->has_lens ? &scene->lens : nullptr);
+        if (mrc != PT_OK) return mrc;
         scene->has_camera = false;
         scene->camera = pt_camera{};
         return PT_OK;
     }
+    int rc = check_camera(scene, cam);
+    if (rc != PT_OK) return rc;
+    if (scene->has_lens && (rc = check_lens_on(*cam, scene->lens)) != PT_OK) return rc;
+    if ((rc = recheck_motion(scene, *cam, scene->has_lens ? &scene->lens : nullptr)) != PT_OK) return rc;
+    scene->camera = *cam;
+    scene->has_camera = true;
+    return PT_OK;
+}
+
+// What pt_scene_set_camera asks of a camera by itself (the end pose of a motion passes the same).
+static int check_camera(const pt_scene *scene, const pt_camera *cam) {
     if (!finite3(cam->origin) || !finite3(cam->right) || !finite3(cam->up) || !finite3(cam->forward))
         return fail(PT_ERR_INVALID_ARGUMENT, "camera: non-finite component");
     double r[3], u[3], f[3];
@@ -737,12 +849,34 @@ static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
         if (!(std::fabs(cam->origin[i]) <= max_origin))
             return fail(PT_ERR_UNSUPPORTED, "camera: origin component beyond PT_CAMERA_MAX_ORIGIN (" + std::to_string(PT_CAMERA_MAX_ORIGIN) +
                                                 ") and beyond the scene's largest |vertex coordinate|: the culling margins are not derived that far out");
-    if (scene->has_lens) {
-        const int rc = check_lens_on(*cam, scene->lens);
+    return PT_OK;
+}
+
+// NULL, or an end pose equal to the handle's camera bit for bit: no motion.  Checks everything before it changes anything.
+static int scene_set_camera_motion_impl(pt_scene *scene, const pt_camera *end) {
+    if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (end) {
+        int rc = check_camera(scene, end);
         if (rc != PT_OK) return rc;
+        if (scene->has_lens && (rc = check_lens_on(*end, scene->lens)) != PT_OK) return rc;
     }
-    scene->camera = *cam;
-    scene->has_camera = true;
+    if (!end || std::memcmp(end, &view_camera(scene), sizeof *end) == 0) {
+        scene->has_motion = false;
+        scene->motion_end = pt_camera{};
+        return PT_OK;
+    }
+    const int rc = check_motion(scene, view_camera(scene), scene->has_lens ? &scene->lens : nullptr, *end);
+    if (rc != PT_OK) return rc;
+    scene->motion_end = *end;
+    scene->has_motion = true;
+    return PT_OK;
+}
+
+static int scene_get_camera_motion_impl(const pt_scene *scene, pt_camera *end, int32_t *is_set) {
+    if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    const bool on = motion_active(scene);
+    if (end) *end = on ? scene->motion_end : view_camera(scene);
+    if (is_set) *is_set = on ? 1 : 0;
     return PT_OK;
 }
 
@@ -1156,6 +1290,18 @@ int pt_scene_set_lens(pt_scene *scene, const pt_lens *lens) {
 
 int pt_scene_get_lens(const pt_scene *scene, pt_lens *lens, int32_t *is_set) {
     return guarded([&] { return scene_get_lens_impl(scene, lens, is_set); });
+}
+
+int pt_scene_set_camera_motion(pt_scene *scene, const pt_camera *end) {
+    return guarded([&] {
+        if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+        std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);   // (a launch being enqueued reads the motion under it)
+        return scene_set_camera_motion_impl(scene, end);
+    });
+}
+
+int pt_scene_get_camera_motion(const pt_scene *scene, pt_camera *end, int32_t *is_set) {
+    return guarded([&] { return scene_get_camera_motion_impl(scene, end, is_set); });
 }
 
 int pt_render_device(pt_scene *scene, const pt_render_params *p, float *d_sum, float *d_sum2, int32_t *d_count, void *hip_stream, pt_render_stats *stats) {

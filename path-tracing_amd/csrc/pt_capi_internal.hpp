@@ -79,6 +79,8 @@ struct pt_scene {
     pt_camera camera{};
     bool has_lens = false;         // this handle's lens (pt_scene_set_lens; radius > 0); copies made from it inherit it
     pt_lens lens{};
+    bool has_motion = false;       // this handle's camera motion (pt_scene_set_camera_motion): the END pose; copies inherit it
+    pt_camera motion_end{};
     // ensure_cull + the enqueue of a launch happen under launch_mutex (a concurrent render with another eps must not free
     // the tables in between); nothing waits for the device while holding it.
     std::mutex launch_mutex;

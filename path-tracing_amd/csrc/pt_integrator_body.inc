@@ -1,8 +1,9 @@
-// The body of pt::integrate_kernel and pt::integrate_kernel_lens (pt_kernels.hip), included inside both.  It sees the kernel's
-// template arguments, its argument `a` and `constexpr bool LENS`, which the including kernel defines.
+// The body of pt::integrate_kernel, pt::integrate_kernel_lens and their motion twins (pt_kernels.hip), included inside each.  It sees
+// the kernel's template arguments, its argument `a` and `constexpr bool LENS` and `MOTION`, which the including kernel defines.
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
+    static_assert(!MOTION || CAM, "a motion kernel is the motion variant of a camera twin or of its lens kernel");
     static_assert(!NARROW || (!SKY && !STATS), "only the statistics-free, skybox-free kernels have a narrow variant");
     constexpr int R = NARROW ? 1 : rays_per_lane<SKY, BIG, STATS>();   // pixels per lane: the wave's tile is kTileW * R x kTileH
     static_assert(POOL == 0 || ((POOL == 2 || POOL == 4) && (R == 2 || BIG) && !STATS && !SKY), "batches of the tile's pixels (a pixel's number takes 8 bits): the two-pixel kernel and the box-tree kernel");
@@ -344,8 +345,18 @@
         const bool k1_on = kDynSlots ? two : true;   // (PT_SLOT_ON)
 
         // Primary ray, main.cpp:126-129 + Ray ctor ray.h:21-25 (double arithmetic, then narrowed).
-        auto primary_dir = [&](int k, int pass_k, float &out_dx, float &out_dy, float &out_dz) {
+        // MOTION: every component of the camera (and of the lens axes) is c[j] + t * delta[j] (pt_hip.h: camera motion), formed
+        // where it is consumed from the two kernel-argument segments, so that the interpolated camera never sits in registers.
+        // Returns t, the path's time within the shutter interval (start_path takes the origin with it), 0 without MOTION.
+        auto primary_dir = [&](int k, int pass_k, float &out_dx, float &out_dy, float &out_dz) -> float {
+            float t = 0.0f;
             {
+                // the time comes first: only t is held across the double-precision jitter below
+                if constexpr (MOTION) {
+                    uint32_t m0, m1, m2, m3;
+                    philox4x32_10(rng_pixel(k), static_cast<uint32_t>(pass_k), 0xFFFFFFFEu, 0u, a.seed, kPhiloxKey1, m0, m1, m2, m3);
+                    t = unit_float(m0);
+                }
                 uint32_t w0, w1, w2, w3;
                 philox4x32_10(rng_pixel(k), static_cast<uint32_t>(pass_k), 0xFFFFFFFFu, 0u, a.seed, kPhiloxKey1, w0, w1, w2, w3);
                 // LENS: the point of the thin lens (pt_hip.h: pt_lens) from the two words the jitter leaves unused, in polar form
@@ -383,23 +394,36 @@
                     // u right + v up + forward, componentwise, unfused (-ffp-contract=off); with the reference camera every step
                     // is exact (x 1, + 0) and |d|^2 is the sum below, so the twin's frame is the camera-free kernel's bit for bit
                     const CameraView c = camera_view();
-                    float dx = (ddx * c[3] + ddy * c[6]) + c[9];
-                    float dy = (ddx * c[4] + ddy * c[7]) + c[10];
-                    float dz = (ddx * c[5] + ddy * c[8]) + c[11];
+                    MotionView cd = nullptr;
+                    if constexpr (MOTION) cd = camera_delta_view();
+                    const auto cam = [&](int j) -> float {
+                        if constexpr (MOTION) return c[j] + t * cd[j];
+                        else return c[j];
+                    };
+                    float dx = (ddx * cam(3) + ddy * cam(6)) + cam(9);
+                    float dy = (ddx * cam(4) + ddy * cam(7)) + cam(10);
+                    float dz = (ddx * cam(5) + ddy * cam(8)) + cam(11);
                     if constexpr (LENS) {
                         // the lens point L = pa r^ + pb u^ (r^ = lns[2..4], u^ = lns[5..7]); the ray from origin + L through the
                         // point where D meets the focal plane (distance lns[1] along f^ = lns[8..10]).  The origin goes straight
                         // into the ray slot, one component at a time.
+                        // (MOTION: r^, u^, f^ interpolated like the camera, not renormalised)
                         const LensView l = lens_view();
-                        const float s = l[1] / ((dx * l[8] + dy * l[9]) + dz * l[10]);
-                        const float lx = pa * l[2] + pb * l[5];
-                        q[k].ox = c[0] + lx;
+                        MotionView ld = nullptr;
+                        if constexpr (MOTION) ld = lens_delta_view();
+                        const auto axis = [&](int j) -> float {   // j = 2 .. 10
+                            if constexpr (MOTION) return l[j] + t * ld[j - 2];
+                            else return l[j];
+                        };
+                        const float s = l[1] / ((dx * axis(8) + dy * axis(9)) + dz * axis(10));
+                        const float lx = pa * axis(2) + pb * axis(5);
+                        q[k].ox = cam(0) + lx;
                         dx = dx * s - lx;
-                        const float ly = pa * l[3] + pb * l[6];
-                        q[k].oy = c[1] + ly;
+                        const float ly = pa * axis(3) + pb * axis(6);
+                        q[k].oy = cam(1) + ly;
                         dy = dy * s - ly;
-                        const float lz = pa * l[4] + pb * l[7];
-                        q[k].oz = c[2] + lz;
+                        const float lz = pa * axis(4) + pb * axis(7);
+                        q[k].oz = cam(2) + lz;
                         dz = dz * s - lz;
                     }
                     normalize3(dx, dy, dz);
@@ -410,12 +434,17 @@
                     out_dx = ddx * inv; out_dy = ddy * inv; out_dz = ddz * inv;
                 }
             }
+            return t;
         };
         // starts slot k's path along a primary direction (eye fixed at (0, 0, -20), main.cpp:129 -- or the camera's; Ray::color_ = 1, ray.h:17)
-        auto start_path = [&](int k, float ddx, float ddy, float ddz) {
+        auto start_path = [&](int k, float ddx, float ddy, float ddz, float t) {
             q[k].dx = ddx; q[k].dy = ddy; q[k].dz = ddz;
             if constexpr (LENS) {
                 // (the origin, camera origin + lens point: primary_dir wrote it)
+            } else if constexpr (MOTION) {
+                const CameraView c = camera_view();
+                const MotionView cd = camera_delta_view();
+                q[k].ox = c[0] + t * cd[0]; q[k].oy = c[1] + t * cd[1]; q[k].oz = c[2] + t * cd[2];
             } else if constexpr (CAM) {
                 const CameraView c = camera_view();
                 q[k].ox = c[0]; q[k].oy = c[1]; q[k].oz = c[2];
@@ -427,8 +456,8 @@
         };
         auto primary_ray = [&](int k, int pass_k) {
             float ddx, ddy, ddz;
-            primary_dir(k, pass_k, ddx, ddy, ddz);
-            start_path(k, ddx, ddy, ddz);
+            const float t = primary_dir(k, pass_k, ddx, ddy, ddz);
+            start_path(k, ddx, ddy, ddz, t);
         };
         // the pass of ray slot k's path: the wave's (a scalar) -- or, with regeneration or batches, the slot's own
         auto pass_of = [&](int k) {

@@ -1295,6 +1295,18 @@ __device__ __forceinline__ LensView lens_view() {
     asm volatile("" : "+s"(p));
     return reinterpret_cast<LensView>(p);
 }
+// The camera motion of a motion-twin launch (RenderArgs::cam_d: end pose - cam; RenderArgs::lns_d: the same for r^, u^, f^), likewise.
+using MotionView = const __attribute__((address_space(4))) float *;
+__device__ __forceinline__ MotionView camera_delta_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, cam_d);
+    asm volatile("" : "+s"(p));
+    return reinterpret_cast<MotionView>(p);
+}
+__device__ __forceinline__ MotionView lens_delta_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, lns_d);
+    asm volatile("" : "+s"(p));
+    return reinterpret_cast<MotionView>(p);
+}
 
 // What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
 // in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
@@ -1331,7 +1343,7 @@ constexpr int integrator_waves() {
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
-    constexpr bool LENS = false;
+    constexpr bool LENS = false, MOTION = false;
 #include "pt_integrator_body.inc"
 }
 // The lens kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary ray
@@ -1347,7 +1359,28 @@ constexpr int lens_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (lens_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_lens(const RenderArgs a) {
-    constexpr bool LENS = true;
+    constexpr bool LENS = true, MOTION = false;
+#include "pt_integrator_body.inc"
+}
+// The motion twins (pt_hip.h: camera motion): the camera twin and its lens kernel with the camera -- and the lens axes -- interpolated
+// between the handle's camera and its end pose at a time t drawn per path, RenderArgs::cam + t * RenderArgs::cam_d.  Kernels of
+// their own for the reason the lens kernel is one.  Waves per SIMD: motion_waves (tests/test_motion_resources.py pins them).
+// The parent's (the camera twin's, the lens kernel's) -- except for the lens twin of the two-pixel small-scene kernel with the
+// envelope test, which at its parent's 5 waves and 96 VGPRs spilled one VGPR (68 spilled SGPRs no longer fit the lanes set aside
+// for them): it is compiled for 4.
+template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, bool LENS_>
+constexpr int motion_waves() {
+    constexpr int w = LENS_ ? lens_waves<SKY, BIG, STATS, ENV, NARROW>() : integrator_waves<SKY, BIG, STATS, ENV, NARROW>();
+    return (LENS_ && !SKY && !BIG && !STATS && ENV && !NARROW) ? w - 1 : w;
+}
+template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
+__global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, false>())) void integrate_kernel_motion(const RenderArgs a) {
+    constexpr bool LENS = false, MOTION = true;
+#include "pt_integrator_body.inc"
+}
+template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
+__global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, true>())) void integrate_kernel_motion_lens(const RenderArgs a) {
+    constexpr bool LENS = true, MOTION = true;
 #include "pt_integrator_body.inc"
 }
 
@@ -1488,12 +1521,15 @@ template <int I>
 Kernel kernel_of() {
     constexpr plan::Variant v = plan::variant_of(I);
     if constexpr (!plan::variant_exists(v, kBuild)) return nullptr;
-    else if constexpr (v.view == 2) return &integrate_kernel_lens<v.sky, v.big, v.stats, v.env, v.narrow, v.pool | 1>;
+    else if constexpr (plan::view_has_motion(v.view) && plan::view_has_lens(v.view)) return &integrate_kernel_motion_lens<v.sky, v.big, v.stats, v.env, v.narrow, v.pool | 1>;
+    else if constexpr (plan::view_has_motion(v.view)) return &integrate_kernel_motion<v.sky, v.big, v.stats, v.env, v.narrow, v.pool | 1>;
+    else if constexpr (plan::view_has_lens(v.view)) return &integrate_kernel_lens<v.sky, v.big, v.stats, v.env, v.narrow, v.pool | 1>;
     else return &integrate_kernel<v.sky, v.big, v.stats, v.env, v.narrow, v.pool | v.view>;
 }
 template <int... I>
 std::array<Kernel, sizeof...(I)> kernel_table(std::integer_sequence<int, I...>) { return {kernel_of<I>()...}; }
-const auto kKernels = kernel_table(std::make_integer_sequence<int, plan::kVariants>());   // by plan::variant_id
+const auto kKernels = kernel_table(std::make_integer_sequence<int, plan::kAllVariants>());   // by plan::variant_id
+static_assert(plan::variant_id({true, true, true, true, false, 0, plan::kViews - 1}) < plan::kAllVariants, "every view's ids fit the table");
 }  // namespace
 
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
@@ -1509,7 +1545,7 @@ hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hip
 // calculation (registers, LDS, launch bounds): the scheduler's count of wave slots.  Asked once per kernel and device.
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves) {
     constexpr int kDevices = 16;
-    static std::atomic<int> cache[kDevices][plan::kVariants];   // 0 = not asked yet
+    static std::atomic<int> cache[kDevices][plan::kAllVariants];   // 0 = not asked yet
     const Kernel kernel = kKernels[plan::variant_id(v)];
     if (!kernel) return hipErrorInvalidDeviceFunction;
     int dev = 0;

@@ -68,6 +68,13 @@ struct RenderArgs {
     // (integrate_kernel_lens), which read lns = radius, focus distance, r^[3], u^[3], f^[3] (right, up, forward as unit vectors).
     int32_t lens;
     float lns[11];
+    // The handle's camera motion (pt_hip.h: pt_scene_set_camera_motion), appended likewise.  motion != 0 (only with camera != 0): the
+    // launch runs the motion twins (integrate_kernel_motion, integrate_kernel_motion_lens), which interpolate every component they
+    // read: cam[j] + t * cam_d[j] with cam_d = end pose - cam, and lns[2 + j] + t * lns_d[j] with lns_d = the end pose's r^, u^, f^
+    // minus lns[2 ..] (float differences taken on the host; lns_d is zero without a lens).
+    int32_t motion;
+    float cam_d[12];
+    float lns_d[9];
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif

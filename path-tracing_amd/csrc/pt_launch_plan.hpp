@@ -19,7 +19,8 @@ struct Build {
     bool wide_only;             // the code object holds the camera-free wide kernels only: no 8 x 8, batch, camera-twin or lens kernels (the PT_BLOCK_PROFILE build's instrumented copy)
 };
 
-// One integrator kernel.  view: 0 = camera-free, 1 = its camera twin, 2 = the lens kernel of that twin.
+// One integrator kernel.  view: 0 = camera-free, 1 = its camera twin, 2 = the lens kernel of that twin, 3 / 4 = the motion twins
+// of 1 / 2 (pt_hip.h: camera motion -- the camera interpolated between two poses at a time drawn per path).
 // pool: 0, or 2 / 4 = the adaptive-sampling kernel that runs batches over 16 x 8 / 32 x 8 tiles.
 struct Variant {
     bool sky, big, stats, env, narrow;
@@ -33,8 +34,16 @@ constexpr bool operator==(const Variant &a, const Variant &b) {
 constexpr int rays_per_lane(const Build &b, bool sky, bool big, bool stats) { return (!sky && !stats) ? (big ? b.rays_big : b.rays_small) : 1; }
 
 // Ids: per view 0-15 the wide kernels ((sky, big, stats, env) as bits 3..0), 16-19 the 8 x 8 ones ((big, env) as bits 1..0),
-// 20-23 the batch kernels ((big, pool == 4) as bits 1..0); the camera twins 24 higher, the lens kernels 48 higher.
-constexpr int kVariantsPerView = 24, kVariants = 3 * kVariantsPerView;
+// 20-23 the batch kernels ((big, pool == 4) as bits 1..0); the camera twins 24 higher, the lens kernels 48 higher, the motion
+// twins of the two 72 and 96 higher.  A table indexed by id (the kernels, the occupancy cache) has kAllVariants entries.
+constexpr int kVariantsPerView = 24, kViews = 5, kAllVariants = kViews * kVariantsPerView;
+// The ids of the still views 0-2 come first: kStillVariants of them.  NOT a table size.  (kVariants is its name from before the
+// motion views, kept because tests/native/launch_plan_main.cpp enumerates the still ids under it; new code says kStillVariants.)
+constexpr int kStillVariants = 3 * kVariantsPerView, kVariants = kStillVariants;
+// The view of a launch from what its handle has (a lens or a motion implies the camera twin), and back.
+constexpr int view_of(bool camera, bool lens, bool motion) { return motion ? (lens ? 4 : 3) : lens ? 2 : camera ? 1 : 0; }
+constexpr bool view_has_lens(int view) { return view == 2 || view == 4; }
+constexpr bool view_has_motion(int view) { return view == 3 || view == 4; }
 constexpr int variant_id(const Variant &v) {
     return kVariantsPerView * v.view + (v.narrow ? 16 + 2 * v.big + v.env : v.pool ? 20 + 2 * v.big + (v.pool == 4) : ((v.sky * 2 + v.big) * 2 + v.stats) * 2 + v.env);
 }

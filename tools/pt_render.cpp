@@ -44,6 +44,12 @@
 // in frames (32 is the usual choice); with -DENOISE the filter then runs on the merged frame, in the same chain on the device.
 // A sequence writes no previews and prints no -TIMING line, and -TL with -FRAMES > 1 is refused.  Without -FRAMES and -TEMPORAL
 // nothing changes.
+// Motion blur (pt_scene_set_camera_motion, not in the reference): -SHUTTER f (0 <= f <= 1, default 0: off) keeps the shutter open
+// for the fraction f of a frame interval.  Frame i starts at its pose above and ends at the pose of the same formula with i + f in
+// place of i (beyond -EYE_END for the last frame; with -FRAMES 1 at EYE + f (EYE_END - EYE)); every path draws its own time in
+// between (PT_RENDER_PRINT_CAMERA=1 then also prints both poses of every frame, "shutter <frame> start|end" and twelve numbers).
+// Features, the temporal history and the display stages use the start pose.  Without -SHUTTER, with -SHUTTER 0 or
+// without -EYE_END / -LOOKAT_END every file is byte-identical.
 // The device-resident display path (pt_display_*, not in the reference): -DEVICE_RESOLVE 1 (default 0) makes the images' bytes on
 // the first device of the frame, where the accumulators lie -- temporal merge, denoiser, tone map and quantization in one chain,
 // 3 bytes per pixel to the host -- instead of reading 28 bytes per pixel back and tone-mapping on the host.  The files are
@@ -115,6 +121,8 @@ struct Options {
     std::string eye = "0,0,-20", lookat = "0,0,0", up = "0,1,0", eye_end, lookat_end;   // as given ("" = the start value)
     float fov = 53.13010235415598f, aspect = 0.0f;
     std::string aperture, focus;   // -APERTURE / -FOCUS as given
+    std::string shutter_text;      // -SHUTTER as given
+    float shutter = 0.0f;          // the fraction of a frame interval the shutter is open; 0 = off
     bool aperture_given = false, focus_given = false;
     int frames = 1;                // -FRAMES
     int device_resolve = 0;        // -DEVICE_RESOLVE as given
@@ -143,6 +151,7 @@ struct Options {
     bool has_lens = false;
     float eye0[3], at0[3], up0[3], eye1[3], at1[3];   // the vectors, parsed; a sequence moves from 0 to 1
     bool moving = false;           // a sequence sets a camera of its own every frame
+    bool blurring = false;         // -SHUTTER > 0 and a camera that moves: every frame gets an end pose (pt_frame_set_camera_motion)
     std::vector<int32_t> devices;  // row bands -> devices; choose_devices() fills it once the device count is known
 };
 
@@ -191,6 +200,7 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-ASPECT") { o.aspect = static_cast<float>(std::atof(v)); o.camera = true; }
         if (f == "-APERTURE") { o.aperture = v; o.aperture_given = true; }
         if (f == "-FOCUS") { o.focus = v; o.focus_given = true; }
+        if (f == "-SHUTTER") o.shutter_text = v;
         if (f == "-DENOISE") o.denoise.levels = std::atoi(v);
         if (f == "-DN_SIGMA_L") o.denoise.sigma_luminance = static_cast<float>(std::atof(v));
         if (f == "-DN_SIGMA_P") o.denoise.sigma_plane = static_cast<float>(std::atof(v));
@@ -246,6 +256,40 @@ int refuse(int status, const std::string &why) {
     return status;
 }
 
+// The camera at time `i` of the sequence, in frames: start + (end - start) i / (n - 1), in double, through pt_camera_look_at.  Frame i
+// starts at i and, with -SHUTTER f, ends at i + f (the last frame's end pose lies beyond -EYE_END; with -FRAMES 1 it is EYE + f (EYE_END - EYE)).
+bool pose_at(const Options &o, double i, pt_camera &out) {
+    float eye[3], at[3];
+    for (int k = 0; k < 3; ++k) {
+        eye[k] = static_cast<float>(o.eye0[k] + (static_cast<double>(o.eye1[k]) - o.eye0[k]) * i / std::max(1, o.frames - 1));
+        at[k] = static_cast<float>(o.at0[k] + (static_cast<double>(o.at1[k]) - o.at0[k]) * i / std::max(1, o.frames - 1));
+    }
+    return pt_camera_look_at(eye, at, o.up0, o.fov, o.aspect, &out) == PT_OK;
+}
+
+// PT_RENDER_PRINT_CAMERA with an open shutter: every frame's two poses as the run would set them (no device needed).
+bool shutter_poses(Options &o) {
+    if (!o.blurring) return true;
+    if (!parse_vec3(o.eye, o.eye0) || !parse_vec3(o.lookat, o.at0) || !parse_vec3(o.up, o.up0) ||
+        !parse_vec3(o.eye_end.empty() ? o.eye : o.eye_end, o.eye1) || !parse_vec3(o.lookat_end.empty() ? o.lookat : o.lookat_end, o.at1)) {
+        std::cerr << "pt_render: -EYE / -EYE_END / -LOOKAT / -LOOKAT_END / -UP take three comma-separated numbers, x,y,z" << std::endl;
+        return false;
+    }
+    for (int i = 0; i < o.frames; ++i)
+        for (int e = 0; e < 2; ++e) {
+            pt_camera c;
+            if (!pose_at(o, i + (e ? static_cast<double>(o.shutter) : 0.0), c)) {
+                std::cerr << "pt_render: " << pt_last_error() << std::endl;
+                return false;
+            }
+            std::printf("shutter %d %s", i, e ? "end" : "start");
+            const float *rows[4] = {c.origin, c.right, c.up, c.forward};
+            for (int k = 0; k < 12; ++k) std::printf(" %.9g", static_cast<double>(rows[k / 3][k % 3]));
+            std::printf("\n");
+        }
+    return true;
+}
+
 // Fills `o` from the command line and makes every refusal that needs neither the model nor a device.  Returns -1 to go on,
 // else the exit status.  Nothing in here may start the HIP runtime: the model is parsed before the first HIP call, and
 // PT_RENDER_PRINT_CONFIG / PT_RENDER_PRINT_CAMERA return before any device call (the CPU tests run them without a device).
@@ -275,6 +319,10 @@ int configure(int argc, char **argv, Options &o) {
         o.lens.focus_distance = static_cast<float>(std::sqrt(d2));
     }
     o.has_lens = o.lens.radius > 0.0f;
+    if (!o.shutter_text.empty() && !(parse_float(o.shutter_text, o.shutter) && o.shutter >= 0.0f && o.shutter <= 1.0f))
+        return refuse(2, "-SHUTTER takes the open fraction of a frame interval, 0 .. 1");
+    const bool travels = !o.eye_end.empty() || !o.lookat_end.empty();
+    o.blurring = o.shutter > 0.0f && travels;
     if (std::getenv("PT_RENDER_PRINT_CAMERA")) {
         if (!o.camera) {
             std::printf("camera none\n");
@@ -286,6 +334,8 @@ int configure(int argc, char **argv, Options &o) {
                             static_cast<double>(rows[r][2]));
         }
         if (o.has_lens) std::printf("lens %.9g %.9g\n", static_cast<double>(o.lens.radius), static_cast<double>(o.lens.focus_distance));
+        // with -SHUTTER > 0 and a camera that travels: the start and the end pose of every frame, "shutter <frame> start|end <12 numbers>"
+        if (!shutter_poses(o)) return 2;
         return 0;
     }
     if (o.width <= 0 || o.height <= 0) return refuse(2, "--W and --H must be positive");
@@ -340,10 +390,10 @@ int configure(int argc, char **argv, Options &o) {
             return refuse(2, std::string("-TONE takes reference, clamp, reinhard or aces; -EXPOSURE stops; -KEY, -ADAPT >= 0; -PERCENTILE 1 .. 100 (") +
                                  pt_last_error() + ")");
     }
-    if (o.sequence) {
-        if (!parse_vec3(o.eye_end.empty() ? o.eye : o.eye_end, o.eye1) || !parse_vec3(o.lookat_end.empty() ? o.lookat : o.lookat_end, o.at1))
+    if (o.sequence || o.blurring) {
+        if (!vectors || !parse_vec3(o.eye_end.empty() ? o.eye : o.eye_end, o.eye1) || !parse_vec3(o.lookat_end.empty() ? o.lookat : o.lookat_end, o.at1))
             return refuse(2, "-EYE / -EYE_END / -LOOKAT / -LOOKAT_END / -UP take three comma-separated numbers, x,y,z");
-        o.moving = o.camera || !o.eye_end.empty() || !o.lookat_end.empty();
+        o.moving = o.sequence && (o.camera || travels);
     }
     return -1;
 }
@@ -681,14 +731,11 @@ int run_sequence(Run &r) {
     ChainTimes unused;
     for (int i = 0; i < o.frames; ++i) {
         if (o.moving) {
-            float eye[3], at[3];
-            for (int k = 0; k < 3; ++k) {
-                eye[k] = static_cast<float>(o.eye0[k] + (static_cast<double>(o.eye1[k]) - o.eye0[k]) * i / std::max(1, o.frames - 1));
-                at[k] = static_cast<float>(o.at0[k] + (static_cast<double>(o.at1[k]) - o.at0[k]) * i / std::max(1, o.frames - 1));
-            }
-            pt_camera camera;
-            if (pt_camera_look_at(eye, at, o.up0, o.fov, o.aspect, &camera) != PT_OK || pt_frame_set_camera(r.frame, &camera) != PT_OK ||
-                !chain.set_camera(camera))
+            pt_camera camera, end;
+            // (the previous frame's motion goes first: a camera is checked against the motion its handle has)
+            if (o.blurring && pt_frame_set_camera_motion(r.frame, nullptr) != PT_OK) return die("pt_render");
+            if (!pose_at(o, i, camera) || pt_frame_set_camera(r.frame, &camera) != PT_OK || !chain.set_camera(camera)) return die("pt_render");
+            if (o.blurring && (!pose_at(o, i + static_cast<double>(o.shutter), end) || pt_frame_set_camera_motion(r.frame, &end) != PT_OK))
                 return die("pt_render");
         }
         rp.pass_begin = i * o.rays_per_pixel;
@@ -820,6 +867,10 @@ int main(int argc, char **argv) {
     if (!o.skybox.empty() && pt_scene_set_skybox_bmp(r.scene, o.skybox.c_str()) != PT_OK) return die("pt_render");   // scene.cpp:20-22
     if (o.camera && pt_scene_set_camera(r.scene, &o.view) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
     if (o.has_lens && pt_scene_set_lens(r.scene, &o.lens) != PT_OK) return die("pt_render");   // and its lens
+    if (o.blurring && !o.sequence) {   // one frame with an open shutter: from -EYE / -LOOKAT towards -EYE_END / -LOOKAT_END
+        pt_camera end;
+        if (!pose_at(o, static_cast<double>(o.shutter), end) || pt_scene_set_camera_motion(r.scene, &end) != PT_OK) return die("pt_render");
+    }
     r.t_parse = clk::now();
     r.n_dev = pt_device_count();   // first HIP call: runtime start-up
     if (r.n_dev < 1) return refuse(1, "no HIP device (the integrator has no CPU fallback)");
