@@ -871,6 +871,101 @@ int pt_display_present_local(pt_display *d, const pt_display_params *p, const pt
                              const pt_grade_params *g, const pt_bloom_params *b, const pt_local_params *l, uint8_t *bgr,
                              pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
 
+/* ---- colour grading: white balance, saturation, matrix and a .cube 3D LUT ---------------------------------------- */
+
+/* Everything above acts on luminance or per channel; nothing can move a colour.  Colour grading is the grade with two steps more,
+ * in two places.  A 3 x 3 MATRIX acts on the linear mean BEFORE the exposure and the curve: white balance gains, saturation and a
+ * user matrix, folded into one matrix, belong to scene-referred light, where they are linear.  A 3D LUT with tetrahedral
+ * interpolation acts on the curve's OUTPUT g, before the gamma table is searched: a look exported by a grading tool as a .cube file
+ * is display-referred, made for values in 0 .. 1.  The stage takes pt_grade_host's place in the chain; per pixel with count != 0 it is
+ *   m' = M m,   x = m' * e,   g = curve(x),   out = LUT(g),
+ * and out takes g's place in pt_tonemap -> pt_quantize (host) or in the display kernel's table search (device).  The meter, bloom
+ * and local exposure read the mean BEFORE the matrix: the metered exposure, the bright pass and the base do not depend on it.
+ *
+ * The arithmetic, exactly: every line below is ONE correctly rounded float operation in the order written (* + -, comparisons,
+ * one float -> int conversion); nothing is fused, and there is no pow, log or exp.
+ *
+ * Matrix.  Composed on the host in double, M = U S W, each entry rounded to float once:
+ *   W = diag(wb)                                         wb = 0 0 0 means 1 1 1
+ *   S = s I + (1 - s) 1 (0.2126, 0.7152, 0.0722)         (every row of the second term is the meter's weights, as doubles)
+ *       s = saturation if saturation_set != 0 or saturation != 0, else 1: a caller who wants grey passes saturation = 0 with
+ *       saturation_set = 1
+ *   U = matrix, row-major;                               all nine zero means the identity
+ *   in this order, in double:  X_ij = ((i == j ? s : 0) + ((1 - s) * lum_j)) * w_j,   M_ij = ((U_i0 * X_0j) + (U_i1 * X_1j)) + (U_i2 * X_2j),
+ *   then (float)M_ij.  With nothing set every M_ij is 1 or +0 exactly.
+ * Applied to the mean pt_grade_host would read (after bloom and local exposure):
+ *   m'_r = ((M00 * m_r) + (M01 * m_g)) + (M02 * m_b)
+ *   m'_g = ((M10 * m_r) + (M11 * m_g)) + (M12 * m_b)
+ *   m'_b = ((M20 * m_r) + (M21 * m_g)) + (M22 * m_b)
+ * If M is the identity BIT FOR BIT (1 on the diagonal, +0 elsewhere) the three lines are skipped: 1 * x + 0 * y is not x for NaN or
+ * infinite inputs, and the bytes are then pt_grade_host's.
+ *
+ * LUT of size N, 2 <= N <= PT_LUT_MAX_SIZE; vertices c(i_r, i_g, i_b), three floats each, at index ((i_b N) + i_g) N + i_r: the
+ * red index runs fastest, the order of a .cube file.  Per channel ch of g:
+ *   x = !(g_ch >= 0) ? 0 : (g_ch > 1 ? 1 : g_ch)         (NaN and negatives -> 0)
+ *   s = x * (float)(N - 1)
+ *   i = (int)s;   if (i > N - 2) i = N - 2
+ *   f = s - (float)i                                      (x = 1 gives i = N - 2, f = 1 exactly)
+ * The tetrahedron, by comparisons in this order (ties have one answer); its path names the axes in the order f1 >= f2 >= f3:
+ *   f_r >= f_g:   f_g >= f_b -> r,g,b     else f_r >= f_b -> r,b,g     else -> b,r,g
+ *   otherwise:    f_r >= f_b -> g,r,b     else f_g >= f_b -> g,b,r     else -> b,g,r
+ * Vertices:  A = c(i),  B = A's index + 1 on the first axis,  C = B's index + 1 on the second axis,  D = c(i_r + 1, i_g + 1, i_b + 1).
+ * Per output channel:
+ *   out = ((A + (f1 * (B - A))) + (f2 * (C - B))) + (f3 * (D - C))
+ * At a vertex (all f = 0) out = A to the bit (entries whose differences are finite; a -0 comes out as +0); a constant LUT returns its constant to the bit; along any path
+ * out is piecewise linear and continuous.  A negative or NaN out defers the pixel on the device, as a negative or NaN g does; the
+ * host finishes a deferred pixel from the mean the kernel read -- the one before the matrix -- with these same steps.
+ *
+ * Parameters; a zeroed struct means the stage does not run (the bytes are those without it):
+ *   wb           three gains, each finite and >= 0; all zero = 1 1 1                              (else: invalid)
+ *   saturation   finite and >= 0; see s above                                                    (else: invalid)
+ *   matrix       nine finite numbers; all zero = identity                                        (else: invalid)
+ *   lut          NULL: no LUT; else a pt_lut that outlives the call */
+#define PT_LUT_MAX_SIZE 65
+typedef struct pt_lut pt_lut;                    /* an immutable 3D LUT in host memory */
+typedef struct pt_colour_params {
+    float wb[3];
+    float saturation;
+    int32_t saturation_set;
+    float matrix[9];
+    const pt_lut *lut;
+} pt_colour_params;
+
+/* Host only, no device.  pt_lut_create copies n^3 vertices of three floats (red index fastest); pt_lut_load_cube reads a .cube file:
+ * blank lines, lines that start with '#', TITLE "...", LUT_3D_SIZE N, DOMAIN_MIN 0 0 0, DOMAIN_MAX 1 1 1 and exactly N^3 data lines
+ * of three numbers read with strtof, with LF or CR LF line ends.  PT_ERR_UNSUPPORTED: LUT_1D_SIZE, any other domain, N outside
+ * 2 .. PT_LUT_MAX_SIZE.  PT_ERR_INVALID_ARGUMENT: a NULL pointer, too few or too many data lines, a token that does not parse, a value
+ * that is not finite, a missing or repeated size line.  PT_ERR_IO: the file cannot be opened.  A failed call writes nothing to *out,
+ * and pt_last_error names the line.  Every LUT made carries a generation number of its own: a display uploads a LUT again only
+ * when the one it is given is not the one it holds. */
+int pt_lut_create(int32_t n, const float *rgb, pt_lut **out);
+int pt_lut_load_cube(const char *path, pt_lut **out);
+int pt_lut_size(const pt_lut *lut, int32_t *n);
+void pt_lut_destroy(pt_lut *lut);
+
+/* Host only, pure: M of *c as stated above, row-major.  On PT_ERR_INVALID_ARGUMENT out is not written. */
+int pt_colour_matrix(const pt_colour_params *c, float out[9]);
+/* Host only, no device: out_rgb = LUT(curve((M mean_rgb) * exposure)) for pixels with count != 0, the others keep their value
+ * (out_rgb may be mean_rgb).  The chain of an image with the stage is ... -> pt_colour_host -> pt_tonemap -> pt_quantize.  Checked as
+ * pt_grade_host checks, and *c as above; with a zeroed *c it is pt_grade_host. */
+int pt_colour_host(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure, int32_t curve,
+                   const pt_colour_params *c, float *out_rgb);
+/* pt_display_bytes_graded_host with the colour stage: meter (if automatic, on the mean before the matrix), exposure and the colour
+ * display kernel as one chain on HIP device `device`, on a host image.  Everything is checked before the device is looked at. */
+int pt_display_bytes_colour_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count,
+                                 float gamma, const pt_grade_params *g, const pt_colour_params *c, int32_t has_prev, float e_prev,
+                                 uint8_t *bgr, pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
+/* pt_display_present_local with the colour stage: the same chain with the colour display kernel in the graded one's place; the
+ * kernel reads the mean once and writes 3 bytes.  The bytes are DEFINED by the host chain and equal it bit for bit: the row of the
+ * tables above up to the linear mean and count, then, if automatic, pt_meter_host -> pt_exposure_from_histogram on the mean BEFORE
+ * bloom, then pt_bloom_host(e) -> pt_local_host(e) -> pt_colour_host(e, curve) -> pt_tonemap -> pt_quantize, at the output size.  *c is
+ * checked with *g, before anything is enqueued and before the device is looked at; a failed present leaves the history and the
+ * previous exposure as they were.  The display keeps a device copy of the LUT and uploads again only when the generation of the
+ * pt_lut it is given differs.  With a zeroed *c the call is pt_display_present_local. */
+int pt_display_present_colour(pt_display *d, const pt_display_params *p, const pt_upsample_params *u /* NULL: not scaled */,
+                              const pt_grade_params *g, const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c,
+                              uint8_t *bgr, pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

@@ -49,7 +49,9 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_grade_host", "pt_meter_host", "pt_exposure_from_histogram", "pt_display_present_graded",
                "pt_display_bytes_graded_host",
                "pt_bloom_host", "pt_display_present_bloom",
-               "pt_local_host", "pt_display_present_local"]
+               "pt_local_host", "pt_display_present_local",
+               "pt_lut_create", "pt_lut_load_cube", "pt_lut_size", "pt_lut_destroy", "pt_colour_matrix", "pt_colour_host",
+               "pt_display_bytes_colour_host", "pt_display_present_colour"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -212,6 +214,80 @@ def _local_params(local):
     return local
 
 
+LUT_MAX_SIZE = 65
+
+
+class ColourParams(C.Structure):
+    """pt_colour_params: a zeroed struct is no colour stage; wb 0 0 0 = 1 1 1, saturation 0 = 1 unless saturation_set, matrix all
+    zero = identity, lut NULL = none."""
+    _fields_ = [("wb", C.c_float * 3), ("saturation", C.c_float), ("saturation_set", C.c_int32), ("matrix", C.c_float * 9), ("lut", C.c_void_p)]
+
+
+class Lut:
+    """pt_lut: an immutable 3D LUT in host memory (tetrahedral interpolation on the tone curve's output)."""
+
+    def __init__(self, handle, library=None):
+        self._h, self._L = handle, library or lib()
+
+    @classmethod
+    def load_cube(cls, path, library=None):
+        """pt_lut_load_cube: a .cube file with LUT_3D_SIZE 2 .. 65 and the domain 0 .. 1."""
+        L = library or lib()
+        h = C.c_void_p()
+        _check(L.pt_lut_load_cube(os.fsencode(path), C.byref(h)), L)
+        return cls(h, L)
+
+    @classmethod
+    def create(cls, array, library=None):
+        """pt_lut_create: array [N, N, N, 3] indexed [blue, green, red] (the red index runs fastest, the order of a .cube file)."""
+        L = library or lib()
+        a = np.ascontiguousarray(array, np.float32)
+        if a.ndim != 4 or a.shape[3] != 3 or not (a.shape[0] == a.shape[1] == a.shape[2]):
+            raise ValueError("Lut.create: the array must be [N, N, N, 3]")
+        h = C.c_void_p()
+        _check(L.pt_lut_create(a.shape[0], _fp(a), C.byref(h)), L)
+        return cls(h, L)
+
+    @property
+    def size(self):
+        n = C.c_int32()
+        _check(self._L.pt_lut_size(self._h, C.byref(n)), self._L)
+        return n.value
+
+    def close(self):
+        if self._h:
+            self._L.pt_lut_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _colour_params(colour):
+    """A ColourParams, or a dict of its fields ({"wb": (1.1, 1, 0.9), "saturation": 0.8, "matrix": 3 x 3, "lut": Lut}) -> a ColourParams.
+    A saturation given in a dict is meant as given: 0 is grey."""
+    if isinstance(colour, dict):
+        unknown = set(colour) - {"wb", "saturation", "matrix", "lut"}
+        if unknown:
+            raise ValueError(f"colour: unknown fields {sorted(unknown)}")
+        prm = ColourParams()
+        if colour.get("wb") is not None:
+            prm.wb = (C.c_float * 3)(*[float(v) for v in colour["wb"]])
+        if colour.get("saturation") is not None:
+            prm.saturation, prm.saturation_set = float(colour["saturation"]), 1
+        if colour.get("matrix") is not None:
+            prm.matrix = (C.c_float * 9)(*[float(v) for v in np.asarray(colour["matrix"], np.float64).reshape(9)])
+        lut = colour.get("lut")
+        if lut is not None:
+            prm.lut = lut._h if isinstance(lut, Lut) else lut
+            prm._keep = lut   # the LUT outlives the parameters
+        return prm
+    return colour
+
+
 def _lens_arg(radius, focus_distance):
     """(radius, focus_distance), a Lens, or None -> a pointer argument for pt_scene_set_lens / pt_frame_set_lens."""
     if radius is None:
@@ -368,6 +444,18 @@ def load_library(path):
     L.pt_local_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(LocalParams), fp, fp]
     L.pt_display_present_local.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
                                            C.POINTER(LocalParams), bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    cp = C.POINTER(ColourParams)
+    L.pt_lut_create.argtypes = [C.c_int32, fp, C.POINTER(vp)]
+    L.pt_lut_load_cube.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.pt_lut_size.argtypes = [vp, ip]
+    L.pt_lut_destroy.argtypes = [vp]
+    L.pt_lut_destroy.restype = None
+    L.pt_colour_matrix.argtypes = [cp, fp]
+    L.pt_colour_host.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, C.c_int32, cp, fp]
+    L.pt_display_bytes_colour_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(GradeParams), cp, C.c_int32, C.c_float, bp,
+                                               C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_display_present_colour.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
+                                            C.POINTER(LocalParams), cp, bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -716,7 +804,7 @@ class Display:
         create = self._L.pt_display_create_frame if isinstance(session_or_frame, Frame) else self._L.pt_display_create
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
-    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None):
+    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None, colour=None):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
         parameters.  Returns (bgr uint8 [H, W, 3], info dict).
@@ -727,7 +815,9 @@ class Display:
         `bloom`: None, a BloomParams, or a dict of its fields ({"strength": 0.5}) -- pt_display_present_bloom: the light above the
         threshold spread over its neighbourhood before the grade (`grade` None: no grading at all, as a zeroed GradeParams).
         `local`: None, a LocalParams, or a dict of its fields ({"strength": 1.0}) -- pt_display_present_local: a gain per pixel from
-        an edge-aware base of the luminance, after bloom and before the grade (`grade`, `bloom` None: zeroed, as above)."""
+        an edge-aware base of the luminance, after bloom and before the grade (`grade`, `bloom` None: zeroed, as above).
+        `colour`: None, a ColourParams, or a dict {"wb": .., "saturation": .., "matrix": .., "lut": Lut} -- pt_display_present_colour: a
+        matrix on the mean before the exposure and a 3D LUT behind the curve (`grade`, `bloom`, `local` None: zeroed)."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -736,13 +826,18 @@ class Display:
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
         info = DisplayInfo()
-        if grade is not None or bloom is not None or local is not None:
+        if grade is not None or bloom is not None or local is not None or colour is not None:
             gp, ginfo = _grade_params(grade) if grade is not None else GradeParams(), GradeInfo()
             up = _upsample_params(upsample) if upsample is not None else None
             k = up.scale if up is not None and 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1
             bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8)
             up_arg, out = C.byref(up) if up is not None else None, bgr.ctypes.data_as(C.POINTER(C.c_uint8))
-            if local is not None:
+            if colour is not None:
+                bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local) if local is not None else LocalParams()
+                cp_ = _colour_params(colour)
+                _check(self._L.pt_display_present_colour(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), C.byref(lp), C.byref(cp_), out,
+                                                         C.byref(info), C.byref(ginfo)), self._L)
+            elif local is not None:
                 bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local)
                 _check(self._L.pt_display_present_local(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), C.byref(lp), out, C.byref(info),
                                                         C.byref(ginfo)), self._L)
@@ -879,6 +974,45 @@ def display_bytes_graded(mean_rgb, count, grade, gamma=None, e_prev=None, device
     bgr = np.zeros(m.shape, np.uint8)
     info, ginfo = DisplayInfo(), GradeInfo()
     _check(L.pt_display_bytes_graded_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(gamma), C.byref(gp),
+                                          0 if e_prev is None else 1, C.c_float(0.0 if e_prev is None else e_prev),
+                                          bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info), C.byref(ginfo)), L)
+    return bgr, dict(info.as_dict(), **ginfo.as_dict())
+
+
+def colour_matrix(wb=None, saturation=None, matrix=None, library=None):
+    """pt_colour_matrix (host only): M = U S W as float32 [3, 3] -- W = diag(wb), S the saturation about the meter's luminance,
+    U the user matrix; None: the identity of that factor."""
+    L = library or lib()
+    prm = _colour_params({"wb": wb, "saturation": saturation, "matrix": matrix})
+    out = np.zeros((3, 3), np.float32)
+    _check(L.pt_colour_matrix(C.byref(prm), _fp(out)), L)
+    return out
+
+
+def colour(mean_rgb, count, exposure=1.0, curve=CURVE_REFERENCE, colour=None, library=None):
+    """pt_colour_host (host only): LUT(curve((M mean) * exposure)) of the pixels with samples of mean_rgb [H, W, 3]; the others keep
+    their value.  `colour`: None (pt_grade_host), a ColourParams, or a dict of its fields."""
+    L = library or lib()
+    m, c = _image_args("colour", mean_rgb, count)
+    prm = _colour_params(colour) if colour is not None else ColourParams()
+    out = np.zeros_like(m)
+    _check(L.pt_colour_host(m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), CURVES[curve] if isinstance(curve, str) else curve,
+                            C.byref(prm), _fp(out)), L)
+    return out
+
+
+def display_bytes_colour(mean_rgb, count, grade, colour, gamma=None, e_prev=None, device=0, library=None):
+    """pt_display_bytes_colour_host: meter (if automatic), exposure and the colour display kernel on a host image.  Returns
+    (bgr uint8 [H, W, 3], info dict with the display's and the grade's fields)."""
+    L = library or lib()
+    if gamma is None:
+        gamma = np.float32(1) / np.float32(2.2)
+    m, c = _image_args("display_bytes_colour", mean_rgb, count)
+    gp = _grade_params(grade) if grade is not None else GradeParams()
+    prm = _colour_params(colour) if colour is not None else ColourParams()
+    bgr = np.zeros(m.shape, np.uint8)
+    info, ginfo = DisplayInfo(), GradeInfo()
+    _check(L.pt_display_bytes_colour_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(gamma), C.byref(gp), C.byref(prm),
                                           0 if e_prev is None else 1, C.c_float(0.0 if e_prev is None else e_prev),
                                           bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info), C.byref(ginfo)), L)
     return bgr, dict(info.as_dict(), **ginfo.as_dict())

@@ -1,6 +1,6 @@
 // What the translation units behind the C ABI share (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters; pt_frame.cpp: the
 // multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
-// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
+// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
 // display path, which chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
 // arguments, and the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments.
 // Nothing here is part of the ABI.
@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "pt_colour.hpp"
 #include "pt_denoise.hpp"
 #include "pt_device_mem.hpp"
 #include "pt_grade.hpp"
@@ -108,6 +109,14 @@ struct pt_session {
         (void)hipSetDevice(scene->device);
         if (stream) (void)hipStreamSynchronize(stream.get());
     }
+};
+
+// A 3D LUT (pt_lut_create, pt_lut_load_cube): immutable once made.  No two LUTs of a process share a generation, so a display
+// knows from the number alone whether its device copy is this one.
+struct pt_lut {
+    int32_t n = 0;
+    uint64_t generation = 0;
+    std::vector<pt::LutVertex> vertices;   // n^3, red index fastest
 };
 
 namespace ptc {
@@ -219,6 +228,15 @@ struct LocalSetup {
     float sigma = 0.5f;
 };
 int local_params_check(const pt_local_params *l, LocalSetup &out);
+
+// pt_colour_params as every entry point checks them (no device is touched): M composed, and the LUT's vertices in host memory
+// (pt_colour_capi.cpp).  `step.lut` points into *lut, which the caller of the entry point keeps alive.
+struct ColourSetup {
+    bool on = false;          // M is not the identity, or there is a LUT: the stage runs
+    pt::ColourStep step{};
+    const pt_lut *lut = nullptr;
+};
+int colour_params_check(const pt_colour_params *c, ColourSetup &out);
 
 // pt_temporal_push_host in two halves, for a chain whose frame already lies on the device (pt_display_present).
 // temporal_enqueue checks the parameters and enqueues features -> merge -> filter on `stream`, reading the frame's accumulators

@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "pt_colour.hpp"
+
 namespace pt {
 
 // Thresholds the kernel searches: the host's table (pt_display_table), padded with +inf to this length.
@@ -34,5 +36,8 @@ hipError_t launch_display(const DisplayArgs &args, hipStream_t stream);
 // whether a pixel is deferred; a deferred entry still carries the ungraded mean.  `curve` is a PT_CURVE_* (pt_grade.hpp), `exposure`
 // a device scalar written earlier on `stream`.
 hipError_t launch_display_graded(const DisplayArgs &args, int curve, const float *exposure, hipStream_t stream);
+// The same with colour grading (pt_display_colour.hip): per pixel matrix -> exposure -> curve -> LUT (pt_colour.hpp) makes the g;
+// a deferred entry carries the mean before the matrix.  `colour.lut` is device memory, valid until the kernel has finished.
+hipError_t launch_display_colour(const DisplayArgs &args, int curve, const float *exposure, const ColourStep &colour, hipStream_t stream);
 
 }  // namespace pt

@@ -4,6 +4,8 @@
 // pt_grade.hpp) and exposure (a device scalar).  Then every channel becomes g = curve(m * *exposure) between the optional divide
 // and the out-of-table test: what is looked up, compared and deferred on is g, while a deferred entry still carries the ungraded
 // mean -- the host finishes such a pixel with the same pt_grade.hpp, so a NaN's payload never has to agree between host and device.
+// With PT_DISPLAY_COLOUR defined as well (pt_display_colour.hip) also LUT (a bool) and colour (a ColourStep of pt_colour.hpp): g is
+// then what matrix -> exposure -> curve -> LUT makes of the pixel, and a deferred entry carries the mean before the matrix.
     __shared__ __attribute__((aligned(16))) float T[kDisplayTableSize];
     for (int i = threadIdx.x; i < kDisplayTableSize / 4; i += kDisplayBlock)
         reinterpret_cast<float4 *>(T)[i] = reinterpret_cast<const float4 *>(a.table)[i];
@@ -43,11 +45,23 @@
         }
 #ifdef PT_DISPLAY_GRADED
         float mean[12];   // what a deferred entry carries: the ungraded mean
+#ifdef PT_DISPLAY_COLOUR
+#pragma unroll
+        for (int i = 0; i < 12; ++i) mean[i] = m[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {   // matrix -> exposure -> curve -> LUT (pt_colour.hpp); the LUT's loads are in bounds for any value
+            if (colour.apply_matrix) colour_matrix_apply(colour.m, m[3 * j], m[3 * j + 1], m[3 * j + 2]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) m[3 * j + k] = grade_value<CURVE>(m[3 * j + k], e);
+            if (LUT) colour_lut_apply(colour.lut, colour.lut_n, m[3 * j], m[3 * j + 1], m[3 * j + 2]);
+        }
+#else
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
             mean[i] = m[i];
             m[i] = grade_value<CURVE>(m[i], e);
         }
+#endif
 #endif
         bool out_of_table[12];
 #pragma unroll

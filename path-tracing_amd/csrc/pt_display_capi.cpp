@@ -4,6 +4,8 @@
 // display kernel, the exposure in a device scalar, and deferred pixels finished through pt_grade.hpp.  With bloom
 // (pt_display_present_bloom): the bloom kernels between the exposure and the display kernel, which then reads the bloomed means.
 // With local exposure (pt_display_present_local): its kernels behind bloom's, on the plane of means bloom wrote or on the chain's image.
+// With colour grading (pt_display_present_colour): the colour display kernel in the graded one's place, its LUT in device memory of the
+// display's, uploaded when the generation of the pt_lut given differs from the one held.
 #include "pt_capi_internal.hpp"
 
 #include <algorithm>
@@ -63,6 +65,16 @@ void finish_on_host_graded(const std::vector<pt::DisplayDeferred> &list, float g
     }
 }
 
+// The same with the colour stage: matrix -> exposure -> curve -> LUT on the mean the list carries (pt_colour.hpp, on the host's LUT).
+void finish_on_host_colour(const std::vector<pt::DisplayDeferred> &list, float gamma, int curve, float e, const pt::ColourStep &step, uint8_t *bgr) {
+    for (const pt::DisplayDeferred &d : list) {
+        const size_t p = static_cast<size_t>(d.pixel);
+        float v[3] = {d.mean[0], d.mean[1], d.mean[2]};
+        pt::colour_pixel(step, curve, e, v[0], v[1], v[2]);
+        for (int k = 0; k < 3; ++k) bgr[3 * p + k] = ptc::quantize_value(ptc::tonemap_value(v[2 - k], gamma));
+    }
+}
+
 // What a graded present is asked for: the checked parameters, and the display's previous metered exposure.
 struct GradeRequest {
     ptc::GradeSetup setup;
@@ -70,6 +82,7 @@ struct GradeRequest {
     float e_prev = 0.0f;
     ptc::BloomSetup bloom;   // on: the bloom kernels run between the exposure and the display kernel
     ptc::LocalSetup local;   // on: the local exposure kernels run behind them
+    ptc::ColourSetup colour; // on: the colour display kernel takes the graded one's place
     int32_t width = 0, height = 0;   // of the image the display kernel reads (bloom and local exposure need its shape)
 };
 
@@ -99,6 +112,10 @@ struct DisplayDevice {
     ptc::DeviceBuffer d_local;
     float *local_base[2] = {nullptr, nullptr};
     float *localised = nullptr;
+    // colour grading: the LUT of the last present with one, and the generation of the pt_lut it was copied from (0: none)
+    ptc::DeviceBuffer d_lut;
+    uint64_t lut_generation = 0;
+    size_t lut_room = 0;
 
     int alloc(size_t pixels, const char *what) {
         n = pixels;
@@ -135,6 +152,21 @@ struct DisplayDevice {
         return PT_OK;
     }
     // (no kernel of this object is in flight: every call that launches one waits for it)
+    int use_lut(const pt_lut *lut, const char *what) {
+        if (lut_generation == lut->generation) return PT_OK;
+        lut_generation = 0;
+        const size_t bytes = sizeof(pt::LutVertex) * lut->vertices.size();
+        if (!d_lut || bytes > lut_room) {
+            ptc::PlaneLayout l;
+            l.add(bytes);
+            const int rc = d_lut.alloc(l, what);
+            if (rc != PT_OK) return rc;
+            lut_room = bytes;
+        }
+        PT_HIP_TRY(hipMemcpy(d_lut.at<void>(0), lut->vertices.data(), bytes, hipMemcpyHostToDevice));
+        lut_generation = lut->generation;
+        return PT_OK;
+    }
     int use_table(const std::shared_ptr<const DisplayTable> &t, const char *what) {
         if (host == t) return PT_OK;
         host.reset();
@@ -203,6 +235,12 @@ struct DisplayDevice {
             PT_HIP_TRY(pt::launch_local(l, stream));
             a.rgb = localised; a.divide = 0;
         }
+        if (grade->colour.on) {   // (use_lut has brought the LUT of this request to the device)
+            pt::ColourStep step = grade->colour.step;
+            step.lut = step.lut_n ? d_lut.at<pt::LutVertex>(0) : nullptr;
+            PT_HIP_TRY(pt::launch_display_colour(a, grade->setup.curve, &exposure->exposure, step, stream));
+            return PT_OK;
+        }
         PT_HIP_TRY(pt::launch_display_graded(a, grade->setup.curve, &exposure->exposure, stream));
         return PT_OK;
     }
@@ -224,7 +262,8 @@ struct DisplayDevice {
             PT_HIP_TRY(hipMemcpy(list.data(), deferred, sizeof(pt::DisplayDeferred) * len, hipMemcpyDeviceToHost));
             for (const pt::DisplayDeferred &d : list)
                 if (d.pixel < 0 || static_cast<size_t>(d.pixel) >= n) return fail(PT_ERR_HIP, "display: a deferred pixel lies outside the image");
-            if (grade) finish_on_host_graded(list, gamma, grade->setup.curve, got.used.exposure, out);
+            if (grade && grade->colour.on) finish_on_host_colour(list, gamma, grade->setup.curve, got.used.exposure, grade->colour.step, out);
+            else if (grade) finish_on_host_graded(list, gamma, grade->setup.curve, got.used.exposure, out);
             else finish_on_host(list, gamma, out);
         }
         got.n_deferred = static_cast<int32_t>(len);
@@ -337,6 +376,7 @@ struct PresentRequest {
     const pt_bloom_params *bloom;         // with grade only
     const pt_local_params *local;         // with grade only
     pt_grade_info *grade_info;            // with grade only; may be NULL
+    const pt_colour_params *colour;       // with grade only
 };
 
 int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, pt_display_info *info) {
@@ -350,6 +390,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (graded && (rc = ptc::grade_params_check(rq.grade, grade.setup)) != PT_OK) return rc;
     if (rq.bloom && (rc = ptc::bloom_params_check(rq.bloom, grade.bloom)) != PT_OK) return rc;
     if (rq.local && (rc = ptc::local_params_check(rq.local, grade.local)) != PT_OK) return rc;
+    if (rq.colour && (rc = ptc::colour_params_check(rq.colour, grade.colour)) != PT_OK) return rc;
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -380,6 +421,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     grade.width = scaled ? ua.width : d->width; grade.height = scaled ? ua.height : d->height;
     if (grade.bloom.on && (rc = dev.ensure_bloom(grade.width, grade.height, "pt_display_present_bloom")) != PT_OK) return rc;
     if (grade.local.on && (rc = dev.ensure_local("pt_display_present_local")) != PT_OK) return rc;
+    if (grade.colour.lut && (rc = dev.use_lut(grade.colour.lut, "pt_display_present_colour")) != PT_OK) return rc;
     if (temporal && !d->history && (rc = pt_temporal_create(scene, d->width, d->height, d->eps, &d->history)) != PT_OK) return rc;
     if (filter && !temporal && (rc = ensure_filter(d)) != PT_OK) return rc;
     {   // the chain, behind every slice enqueued so far: no host synchronisation until its last kernel is in the queue
@@ -434,7 +476,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
 
 // A mean image in host memory, and how it is to be graded (pt_display_bytes_graded_host).
 struct HostImage { int device; int32_t width, height; const float *mean_rgb; const int32_t *count; };
-struct HostGrade { const pt_grade_params *params; bool has_prev; float e_prev; pt_grade_info *info; };   // (info may be NULL)
+struct HostGrade { const pt_grade_params *params; bool has_prev; float e_prev; pt_grade_info *info; const pt_colour_params *colour; };   // (info, colour may be NULL)
 
 // `g` = NULL: pt_display_bytes_host.
 int display_bytes_host_impl(const HostImage &image, float gamma, const HostGrade *g, uint8_t *bgr, pt_display_info *info) {
@@ -445,6 +487,7 @@ int display_bytes_host_impl(const HostImage &image, float gamma, const HostGrade
     GradeRequest grade;
     if (g && (rc = ptc::grade_params_check(g->params, grade.setup)) != PT_OK) return rc;
     if (g) grade.has_prev = g->has_prev, grade.e_prev = g->e_prev;
+    if (g && g->colour && (rc = ptc::colour_params_check(g->colour, grade.colour)) != PT_OK) return rc;
     if ((rc = ptc::use_device(image.device, "display")) != PT_OK) return rc;
     const size_t n = static_cast<size_t>(image.width) * image.height;
     const std::shared_ptr<const DisplayTable> table = display_table(gamma);
@@ -456,6 +499,7 @@ int display_bytes_host_impl(const HostImage &image, float gamma, const HostGrade
     if ((rc = d_in.alloc(l, "pt_display_bytes_host")) != PT_OK || (rc = dev.alloc(n, "pt_display_bytes_host")) != PT_OK ||
         (rc = dev.use_table(table, "pt_display_bytes_host")) != PT_OK || (rc = timer.create("pt_display_bytes_host")) != PT_OK)
         return rc;
+    if (grade.colour.lut && (rc = dev.use_lut(grade.colour.lut, "pt_display_bytes_colour_host")) != PT_OK) return rc;
     in.bind(d_in);
     if ((rc = in.upload(image.mean_rgb, image.count)) != PT_OK) return rc;
     PT_HIP_TRY(timer.begin(nullptr));
@@ -524,26 +568,32 @@ int pt_display_create_frame(pt_frame *frame, float eps, pt_display **out) {
 }
 
 int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return display_present_impl(d, {p, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info); });
+    return guarded([&] { return display_present_impl(d, {p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info); });
 }
 
 int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return u ? display_present_impl(d, {p, u, nullptr, nullptr, nullptr, nullptr}, bgr, info) : null_argument(); });
+    return guarded([&] { return u ? display_present_impl(d, {p, u, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_graded(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g, uint8_t *bgr,
                               pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g ? display_present_impl(d, {p, u, g, nullptr, nullptr, grade_info}, bgr, info) : null_argument(); });
+    return guarded([&] { return g ? display_present_impl(d, {p, u, g, nullptr, nullptr, grade_info, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_bloom(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                              const pt_bloom_params *b, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g && b ? display_present_impl(d, {p, u, g, b, nullptr, grade_info}, bgr, info) : null_argument(); });
+    return guarded([&] { return g && b ? display_present_impl(d, {p, u, g, b, nullptr, grade_info, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_local(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                              const pt_bloom_params *b, const pt_local_params *l, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g && b && l ? display_present_impl(d, {p, u, g, b, l, grade_info}, bgr, info) : null_argument(); });
+    return guarded([&] { return g && b && l ? display_present_impl(d, {p, u, g, b, l, grade_info, nullptr}, bgr, info) : null_argument(); });
+}
+
+int pt_display_present_colour(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
+                              const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c, uint8_t *bgr, pt_display_info *info,
+                              pt_grade_info *grade_info) {
+    return guarded([&] { return g && b && l && c ? display_present_impl(d, {p, u, g, b, l, grade_info, c}, bgr, info) : null_argument(); });
 }
 
 int pt_display_reset(pt_display *d) {
@@ -569,7 +619,17 @@ int pt_display_bytes_graded_host(int device, int32_t width, int32_t height, cons
                                  const pt_grade_params *g, int32_t has_prev, float e_prev, uint8_t *bgr, pt_display_info *info,
                                  pt_grade_info *grade_info) {
     return guarded([&] {
-        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info};
+        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info, nullptr};
+        return display_bytes_host_impl({device, width, height, mean_rgb, count}, gamma, &grade, bgr, info);
+    });
+}
+
+int pt_display_bytes_colour_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
+                                 const pt_grade_params *g, const pt_colour_params *c, int32_t has_prev, float e_prev, uint8_t *bgr,
+                                 pt_display_info *info, pt_grade_info *grade_info) {
+    return guarded([&] {
+        if (!c) return null_argument();
+        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info, c};
         return display_bytes_host_impl({device, width, height, mean_rgb, count}, gamma, &grade, bgr, info);
     });
 }

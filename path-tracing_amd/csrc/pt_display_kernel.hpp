@@ -1,5 +1,5 @@
 // What the display kernels share besides their statements (pt_display_body.inc): the launch shape and the table search.
-// Device code; included by pt_display.hip and pt_display_graded.hip only.
+// Device code; included by pt_display.hip, pt_display_graded.hip and pt_display_colour.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -83,8 +83,15 @@
 // spline whose range weight is -LOCAL_SIGMA <default 0.5>, on the linear mean at the written size, after bloom and before the
 // grade (alone it runs with the zeroed grade, as -BLOOM does); previews stay as they are.  It works on the host path and with
 // -DEVICE_RESOLVE 1, with byte-identical files, and with every flag grading works with.  Without -LOCAL, or with -LOCAL 0, nothing changes.
+// Colour grading (pt_colour_host, pt_display_present_colour, not in the reference): -WB <r,g,b gains, default 1,1,1>, -SATURATION <s,
+// default 1; 0 is grey> and -COLOR_MATRIX <m00,..,m22, row-major, default the identity> are folded into one 3 x 3 matrix on the
+// linear mean, after local exposure and before the exposure and the curve; -LUT <file.cube> applies a 3D LUT (LUT_3D_SIZE 2 .. 65,
+// domain 0 .. 1, tetrahedral interpolation) to the curve's output, before the gamma conversion.  The meter, bloom and local exposure
+// see the mean before the matrix; previews stay as they are.  It works on the host path and with -DEVICE_RESOLVE 1, with
+// byte-identical files, and with every flag grading works with (alone it runs with the zeroed grade).  Without these flags nothing
+// changes.
 // The image chain is stated once, in HostChain::bytes, in the order the paragraphs above give: temporal merge -> first-hit
-// features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> meter, bloom, local exposure, grade -> tone map
+// features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> meter, bloom, local exposure, colour / grade -> tone map
 // -> -GAUSS / -MEDIAN -> quantize.  A single frame and every frame of a sequence go through it; with -DEVICE_RESOLVE 1 the
 // bytes come from present() instead.
 #include <algorithm>
@@ -136,6 +143,9 @@ struct Options {
     pt_temporal_params temporal{}; // -TEMPORAL: max_frames of the history, 0 = no temporal stage
     pt_bloom_params bloom{};       // -BLOOM, -BLOOM_THRESHOLD, -BLOOM_LEVELS
     pt_local_params local{};       // -LOCAL, -LOCAL_PIVOT, -LOCAL_LEVELS, -LOCAL_SIGMA
+    std::string wb, saturation, colour_matrix, lut_path;   // -WB, -SATURATION, -COLOR_MATRIX, -LUT as given
+    pt_colour_params colour{};     // what they make; colour.lut is owned here
+    pt_lut *lut = nullptr;
     pt_upsample_params upsample{};
     pt_grade_params grade{};       // zeroed without -TONE / -EXPOSURE / -AUTO_EXPOSURE: the reference's bytes
     pt_display_params show{};      // what a present of the device path is asked for
@@ -145,7 +155,8 @@ struct Options {
     bool sequence = false;         // -FRAMES > 1 or -TEMPORAL
     bool merging = false;          // -TEMPORAL > 0
     bool display = false;          // -DEVICE_RESOLVE 1 and nothing that keeps the image on the host path
-    bool blooming = false, localising = false, grading = false;   // -BLOOM > 0; -LOCAL > 0; either, or any of the tone flags
+    bool blooming = false, localising = false, grading = false;   // -BLOOM > 0; -LOCAL > 0; either, colour, or any of the tone flags
+    bool colouring = false;        // a matrix that is not the identity, or a LUT
     pt_camera view;                // with `camera`
     pt_lens lens{0.0f, 0.0f};
     bool has_lens = false;
@@ -153,6 +164,9 @@ struct Options {
     bool moving = false;           // a sequence sets a camera of its own every frame
     bool blurring = false;         // -SHUTTER > 0 and a camera that moves: every frame gets an end pose (pt_frame_set_camera_motion)
     std::vector<int32_t> devices;  // row bands -> devices; choose_devices() fills it once the device count is known
+    Options() = default;
+    Options(const Options &) = delete;
+    ~Options() { pt_lut_destroy(lut); }
 };
 
 long long now_ms() {
@@ -223,6 +237,10 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-LOCAL_PIVOT") o.local.pivot = static_cast<float>(std::atof(v));
         if (f == "-LOCAL_LEVELS") o.local.levels = std::atoi(v);
         if (f == "-LOCAL_SIGMA") o.local.sigma = static_cast<float>(std::atof(v));
+        if (f == "-WB") o.wb = v;
+        if (f == "-SATURATION") o.saturation = v;
+        if (f == "-COLOR_MATRIX") o.colour_matrix = v;
+        if (f == "-LUT") o.lut_path = v;
     }
 }
 
@@ -234,6 +252,19 @@ bool parse_vec3(const std::string &text, float out[3]) {
         out[k] = std::strtof(p, &end);
         if (end == p || !std::isfinite(out[k])) return false;
         if (*end != (k < 2 ? ',' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
+}
+
+// "m00,..,m22": nine finite numbers, nothing else
+bool parse_vec9(const std::string &text, float out[9]) {
+    const char *p = text.c_str();
+    for (int k = 0; k < 9; ++k) {
+        char *end = nullptr;
+        out[k] = std::strtof(p, &end);
+        if (end == p || !std::isfinite(out[k])) return false;
+        if (*end != (k < 8 ? ',' : '\0')) return false;
         p = end + 1;
     }
     return true;
@@ -373,7 +404,27 @@ int configure(int argc, char **argv, Options &o) {
         !(std::isfinite(o.local.sigma) && o.local.sigma >= 0.0f) || o.local.levels < 0 || o.local.levels > PT_LOCAL_MAX_LEVELS)
         return refuse(2, "-LOCAL, -LOCAL_PIVOT and -LOCAL_SIGMA take a number >= 0, -LOCAL_LEVELS 1 .. " + std::to_string(PT_LOCAL_MAX_LEVELS));
     o.localising = o.local.strength > 0.0f;
-    o.grading = o.tone_flags || o.blooming || o.localising;
+    // -WB / -SATURATION / -COLOR_MATRIX / -LUT: the colour stage, in the grade's place; alone it runs with the zeroed grade too.  The
+    // .cube file is read here, by the library's host-only reader.
+    if (!o.wb.empty() && !(parse_vec3(o.wb, o.colour.wb) && o.colour.wb[0] >= 0.0f && o.colour.wb[1] >= 0.0f && o.colour.wb[2] >= 0.0f))
+        return refuse(2, "-WB takes three comma-separated gains >= 0, r,g,b");
+    if (!o.saturation.empty()) {
+        if (!(parse_float(o.saturation, o.colour.saturation) && o.colour.saturation >= 0.0f)) return refuse(2, "-SATURATION takes a number >= 0 (0: grey, 1: unchanged)");
+        o.colour.saturation_set = 1;
+    }
+    if (!o.colour_matrix.empty() && !parse_vec9(o.colour_matrix, o.colour.matrix))
+        return refuse(2, "-COLOR_MATRIX takes nine comma-separated numbers, m00,m01,m02,m10,..,m22");
+    if (!o.lut_path.empty()) {
+        if (pt_lut_load_cube(o.lut_path.c_str(), &o.lut) != PT_OK) return die("pt_render: -LUT");
+        o.colour.lut = o.lut;
+    }
+    {
+        float m[9];
+        if (pt_colour_matrix(&o.colour, m) != PT_OK) return refuse(2, std::string("-WB / -SATURATION / -COLOR_MATRIX (") + pt_last_error() + ")");
+        const float identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        o.colouring = o.lut != nullptr || std::memcmp(m, identity, sizeof m) != 0;
+    }
+    o.grading = o.tone_flags || o.blooming || o.localising || o.colouring;
     // -TONE / -EXPOSURE / -AUTO_EXPOSURE: what every graded image is asked for
     if (o.tone_flags) {
         const char *names[4] = {"reference", "clamp", "reinhard", "aces"};
@@ -484,10 +535,11 @@ struct HostFrame {
     uint8_t *image() { return out_bgr.empty() ? bgr.data() : out_bgr.data(); }
 };
 
-// The device path's present: plain, scaled, or either with grading, bloom or local exposure
+// The device path's present: plain, scaled, or either with grading, bloom, local exposure or colour
 int present(const Run &r, HostFrame &host, pt_display_info *info) {
     const Options &o = r.o;
     const pt_upsample_params *up = o.scale > 1 ? &o.upsample : nullptr;
+    if (o.colouring) return pt_display_present_colour(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, host.image(), info, nullptr);
     if (o.localising) return pt_display_present_local(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, host.image(), info, nullptr);
     if (o.blooming) return pt_display_present_bloom(r.display, &o.show, up, &o.grade, &o.bloom, host.image(), info, nullptr);
     if (o.grading) return pt_display_present_graded(r.display, &o.show, up, &o.grade, host.image(), info, nullptr);
@@ -617,7 +669,9 @@ bool HostChain::bytes(HostFrame &host, float dispersion[3], ChainTimes &times) {
             if (pt_local_host(dev, w, h, m, n, e, &o.local, rgb.data(), nullptr) != PT_OK) return false;
             m = rgb.data();
         }
-        if (pt_grade_host(w, h, m, n, e, o.grade.curve, rgb.data()) != PT_OK) return false;
+        if (o.colouring ? pt_colour_host(w, h, m, n, e, o.grade.curve, &o.colour, rgb.data()) != PT_OK
+                        : pt_grade_host(w, h, m, n, e, o.grade.curve, rgb.data()) != PT_OK)
+            return false;
         m = rgb.data();
     }
     pt_tonemap(w, h, m, n, o.gamma_correction, rgb.data());
