@@ -966,6 +966,92 @@ int pt_display_present_colour(pt_display *d, const pt_display_params *p, const p
                               const pt_grade_params *g, const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c,
                               uint8_t *bgr, pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
 
+/* ---- lens optics: radial distortion, lateral chromatic aberration, vignetting ------------------------------------ */
+
+/* pt_camera and pt_lens form the ray; nothing above bends a straight line, splits an edge into colour fringes or darkens the
+ * corners, as the glass of a real lens does.  Optics is one stage, (mean, count) -> (mean', count'), on the linear mean at the
+ * OUTPUT size: after the denoiser, the temporal merge and the upsample, and BEFORE the meter, bloom, local exposure and the grade or
+ * colour stage, which all read mean' and count' in place of mean and count -- the sensor meters what the lens delivers.  The
+ * first-hit features, the temporal reprojection and the upsampler do not see the stage.  It is a gather: each output channel is
+ * resampled from four taps at a position of its own.
+ *
+ * The arithmetic, exactly: every line below is ONE correctly rounded float operation in the order written (* / + -, comparisons,
+ * int <-> float conversions); nothing is fused, and there is no pow, log, exp or trigonometry -- the stage is rational.
+ *
+ * Geometry, for output pixel (x, y) of W x H:
+ *   cx = 0.5 * (float)(W - 1),   cy = 0.5 * (float)(H - 1)            (the centre)
+ *   px = (float)x - cx,          py = (float)y - cy
+ *   hh = 0.5 * (float)H,         u = px / hh,   v = py / hh            (normalised by half the height)
+ *   r2 = (u * u) + (v * v)
+ *   f  = 1 + (r2 * (k1 + (k2 * r2)))                                   (k1 < 0: barrel; k1 > 0: pincushion)
+ * The magnification of channel ch, composed on the host and rounded once:  mag = (1 - ca, 1, 1 + ca)  for r, g, b.  The source
+ * position of channel ch:
+ *   s  = f * mag_ch
+ *   sx = cx + (px * s),   sy = cy + (py * s)
+ *   sx = !(sx >= 0) ? 0 : (sx > (float)(W - 1) ? (float)(W - 1) : sx),   sy likewise against H - 1      (NaN -> 0; the edge repeats)
+ *
+ * Bilinear resample of channel ch at (sx, sy):
+ *   x0 = (int)sx,   fx = sx - (float)x0,   x1 = x0 + 1, and x1 = W - 1 if it exceeds that;   y0, fy, y1 likewise
+ *   the taps in the order (x0,y0), (x1,y0), (x0,y1), (x1,y1), each with  w = wx * wy,  where wx = 1 - fx for x0 and fx for x1,
+ *   wy = 1 - fy for y0 and fy for y1
+ *   a tap with w == 0 or with count == 0 is skipped: its value is never read, so a NaN in an unsampled pixel cannot leak
+ *   otherwise, with m = the tap's mean of channel ch (a chain row that ends in sums: m = sum / (float)count, as the display divides):
+ *     the FIRST tap kept:   ref = m,   sw = w,   sd = 0
+ *     every later one:      sw = sw + w
+ *                           sd = sd + (w * (m - ref))
+ *   no tap kept: the channel is EMPTY;  else  val_ch = ref + (sd / sw).
+ * This is the weighted mean sum(w m) / sum(w) of the taps kept, taken about the first of them -- the form of the denoiser's and of
+ * local exposure's sums (b + sd / sw), for their reason: rounded products w * m of EQUAL values do not add up to that value times the
+ * rounded sum of w (of random c, fx, fy in 0 .. 1 a third come back an ulp off from sum(w c) / sum(w)), while differences of equal
+ * values are 0.
+ *
+ * Vignette, from the OUTPUT pixel's r2:
+ *   q    = 1 + (vig * r2)
+ *   gain = 1 / (q * q)            (cos^4 of the field angle whose tangent is sqrt(vig) r: the natural fall-off, without a root)
+ *   out_ch = val_ch * gain
+ *
+ * Count.  If any channel is empty, out = 0 0 0 and count' = 0; otherwise count' = 1 (the denoiser's count_out convention).
+ *
+ * Properties (the tests rely on them):
+ *   - k1 = k2 = ca = 0:  f = 1 and mag = 1, so s = 1;  px = x - cx is exact (multiples of 0.5 below 2^22) and cx + px gives back
+ *     x exactly, for W and H below 2^22: sx == x and sy == y.  Then fx = fy = 0, the one tap with a weight is the pixel itself,
+ *     ref = m, sd = 0, and m + (0 / 1) = m: the resample returns m to the bit (a -0 comes out as +0), and a pixel with count == 0
+ *     comes out empty, whatever its rgb holds.
+ *   - vig = 0:  q = 1 and gain = 1 exactly.
+ *   - an image that is constant over its valid pixels stays constant to the bit under the resample, whatever taps are skipped:
+ *     every m - ref is 0, so sd = 0 and val = ref + 0.
+ *
+ * Parameters; a zeroed struct means the stage does not run, and the bytes and counts are those of the chain without it:
+ *   k1, k2      finite, |k| <= 4                                                               (else: invalid)
+ *   ca          finite, |ca| <= 0.25                                                           (else: invalid)
+ *   vignette    finite, 0 .. 64                                                                (else: invalid)
+ * Any image size from 1 x 1 is valid. */
+typedef struct pt_optics_params {
+    float k1, k2;
+    float ca;
+    float vignette;
+} pt_optics_params;
+
+/* The optics kernel alone, on a host image: (out_rgb, out_count) = the output above for (mean_rgb, count), made on HIP device
+ * `device`; kernel_ms (may be NULL) = HIP-event time of the kernel.  The stage is a gather: out_rgb must not be mean_rgb and
+ * out_count must not be count.  Buffers, sizes and *o are checked BEFORE the device is looked at; PT_ERR_NO_DEVICE afterwards if
+ * that is not a usable device (there is no CPU fallback).  With a zeroed *o it copies mean_rgb and count. */
+int pt_optics_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, const pt_optics_params *o,
+                   float *out_rgb, int32_t *out_count, float *kernel_ms);
+/* pt_display_present_colour with the optics stage: the same chain with the optics kernel enqueued on the session's stream AHEAD of
+ * the meter, with no host synchronisation inside; the meter, bloom, local exposure and the display kernel read the planes it
+ * wrote.  The bytes are DEFINED by the host chain and equal it bit for bit: the row of the tables above up to the linear mean and
+ * count at the output size (after the upsample if u is given), then pt_optics_host, then, if automatic, pt_meter_host ->
+ * pt_exposure_from_histogram on mean' and count', then pt_bloom_host(e) -> pt_local_host(e) -> pt_colour_host(e, curve) ->
+ * pt_tonemap -> pt_quantize with count'.  *o is checked with *g, before anything is enqueued and before the device is looked at; a
+ * failed present leaves the history and the previous exposure as they were.  A deferred pixel carries the mean AFTER optics (and
+ * bloom and local exposure), which the host finishes.  The display owns two more planes, rgb and count at the output size,
+ * allocated by the first present with the stage.  With a zeroed *o the call is pt_display_present_colour. */
+int pt_display_present_optics(pt_display *d, const pt_display_params *p, const pt_upsample_params *u /* NULL: not scaled */,
+                              const pt_grade_params *g, const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c,
+                              const pt_optics_params *o, uint8_t *bgr, pt_display_info *info /* may be NULL */,
+                              pt_grade_info *grade_info /* may be NULL */);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

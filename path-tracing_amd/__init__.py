@@ -51,7 +51,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_bloom_host", "pt_display_present_bloom",
                "pt_local_host", "pt_display_present_local",
                "pt_lut_create", "pt_lut_load_cube", "pt_lut_size", "pt_lut_destroy", "pt_colour_matrix", "pt_colour_host",
-               "pt_display_bytes_colour_host", "pt_display_present_colour"]
+               "pt_display_bytes_colour_host", "pt_display_present_colour",
+               "pt_optics_host", "pt_display_present_optics"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -288,6 +289,21 @@ def _colour_params(colour):
     return colour
 
 
+class OpticsParams(C.Structure):
+    """pt_optics_params: a zeroed struct is no optics stage; k1, k2 in -4 .. 4, ca in -0.25 .. 0.25, vignette in 0 .. 64."""
+    _fields_ = [("k1", C.c_float), ("k2", C.c_float), ("ca", C.c_float), ("vignette", C.c_float)]
+
+
+def _optics_params(optics):
+    """An OpticsParams, or a dict of its fields ({"k1": -0.1, "ca": 0.01, "vignette": 1.0}) -> an OpticsParams."""
+    if isinstance(optics, dict):
+        unknown = set(optics) - {"k1", "k2", "ca", "vignette"}
+        if unknown:
+            raise ValueError(f"optics: unknown fields {sorted(unknown)}")
+        return OpticsParams(optics.get("k1", 0.0), optics.get("k2", 0.0), optics.get("ca", 0.0), optics.get("vignette", 0.0))
+    return optics
+
+
 def _lens_arg(radius, focus_distance):
     """(radius, focus_distance), a Lens, or None -> a pointer argument for pt_scene_set_lens / pt_frame_set_lens."""
     if radius is None:
@@ -456,6 +472,9 @@ def load_library(path):
                                                C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     L.pt_display_present_colour.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
                                             C.POINTER(LocalParams), cp, bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_optics_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.POINTER(OpticsParams), fp, ip, fp]
+    L.pt_display_present_optics.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
+                                            C.POINTER(LocalParams), cp, C.POINTER(OpticsParams), bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -804,7 +823,7 @@ class Display:
         create = self._L.pt_display_create_frame if isinstance(session_or_frame, Frame) else self._L.pt_display_create
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
-    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None, colour=None):
+    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None, colour=None, optics=None):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
         parameters.  Returns (bgr uint8 [H, W, 3], info dict).
@@ -817,7 +836,10 @@ class Display:
         `local`: None, a LocalParams, or a dict of its fields ({"strength": 1.0}) -- pt_display_present_local: a gain per pixel from
         an edge-aware base of the luminance, after bloom and before the grade (`grade`, `bloom` None: zeroed, as above).
         `colour`: None, a ColourParams, or a dict {"wb": .., "saturation": .., "matrix": .., "lut": Lut} -- pt_display_present_colour: a
-        matrix on the mean before the exposure and a 3D LUT behind the curve (`grade`, `bloom`, `local` None: zeroed)."""
+        matrix on the mean before the exposure and a 3D LUT behind the curve (`grade`, `bloom`, `local` None: zeroed).
+        `optics`: None, an OpticsParams, or a dict of its fields ({"k1": -0.1, "ca": 0.01, "vignette": 1.0}) --
+        pt_display_present_optics: distortion, chromatic aberration and vignetting of the linear mean ahead of the meter (the other
+        stages None: zeroed)."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -826,13 +848,18 @@ class Display:
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
         info = DisplayInfo()
-        if grade is not None or bloom is not None or local is not None or colour is not None:
+        if grade is not None or bloom is not None or local is not None or colour is not None or optics is not None:
             gp, ginfo = _grade_params(grade) if grade is not None else GradeParams(), GradeInfo()
             up = _upsample_params(upsample) if upsample is not None else None
             k = up.scale if up is not None and 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1
             bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8)
             up_arg, out = C.byref(up) if up is not None else None, bgr.ctypes.data_as(C.POINTER(C.c_uint8))
-            if colour is not None:
+            if optics is not None:
+                bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local) if local is not None else LocalParams()
+                cp_, op = _colour_params(colour) if colour is not None else ColourParams(), _optics_params(optics)
+                _check(self._L.pt_display_present_optics(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), C.byref(lp), C.byref(cp_),
+                                                         C.byref(op), out, C.byref(info), C.byref(ginfo)), self._L)
+            elif colour is not None:
                 bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local) if local is not None else LocalParams()
                 cp_ = _colour_params(colour)
                 _check(self._L.pt_display_present_colour(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), C.byref(lp), C.byref(cp_), out,
@@ -937,6 +964,19 @@ def local_exposure(device, mean_rgb, count, exposure=1.0, strength=1.0, pivot=0.
     prm = LocalParams(strength, pivot, levels, sigma)
     _check(L.pt_local_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), C.byref(prm), _fp(out), C.byref(ms)), L)
     return (out, ms.value) if want_ms else out
+
+
+def optics(device, mean_rgb, count, k1=0.0, k2=0.0, ca=0.0, vignette=0.0, want_ms=False, library=None):
+    """pt_optics_host: the lens optics kernel alone on a host image mean_rgb [H, W, 3] with count [H, W] -- radial distortion
+    f = 1 + r2 (k1 + k2 r2), the channels magnified by 1 - ca, 1, 1 + ca, resampled bilinearly, times the vignette 1 / (1 + vignette r2)^2.
+    Returns (out [H, W, 3], count_out [H, W]: 1, or 0 where a channel found no sampled tap), and the kernel's milliseconds as a third
+    value if want_ms."""
+    L = library or lib()
+    m, c = _image_args("optics", mean_rgb, count)
+    out, out_count, ms = np.zeros_like(m), np.zeros(m.shape[:2], np.int32), C.c_float()
+    prm = OpticsParams(k1, k2, ca, vignette)
+    _check(L.pt_optics_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.byref(prm), _fp(out), _ip(out_count), C.byref(ms)), L)
+    return (out, out_count, ms.value) if want_ms else (out, out_count)
 
 
 def meter(mean_rgb, count, device=0, want_ms=False, library=None):

@@ -1,6 +1,6 @@
 // What the translation units behind the C ABI share (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters; pt_frame.cpp: the
 // multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
-// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
+// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
 // display path, which chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
 // arguments, and the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments.
 // Nothing here is part of the ABI.
@@ -237,6 +237,16 @@ struct ColourSetup {
     const pt_lut *lut = nullptr;
 };
 int colour_params_check(const pt_colour_params *c, ColourSetup &out);
+
+// pt_optics_params as every entry point checks them (no device is touched), with the channels' magnifications composed
+// (pt_optics_capi.cpp).
+struct OpticsSetup {
+    bool on = false;          // any field is not zero: the stage runs
+    float k1 = 0.0f, k2 = 0.0f;
+    float mag[3] = {1.0f, 1.0f, 1.0f};   // 1 - ca, 1, 1 + ca
+    float vignette = 0.0f;
+};
+int optics_params_check(const pt_optics_params *o, OpticsSetup &out);
 
 // pt_temporal_push_host in two halves, for a chain whose frame already lies on the device (pt_display_present).
 // temporal_enqueue checks the parameters and enqueues features -> merge -> filter on `stream`, reading the frame's accumulators

@@ -6,6 +6,8 @@
 // With local exposure (pt_display_present_local): its kernels behind bloom's, on the plane of means bloom wrote or on the chain's image.
 // With colour grading (pt_display_present_colour): the colour display kernel in the graded one's place, its LUT in device memory of the
 // display's, uploaded when the generation of the pt_lut given differs from the one held.
+// With lens optics (pt_display_present_optics): its kernel ahead of all of these, from the chain's image into a mean image of the
+// display's, which the meter and every later stage read in the chain's place.
 #include "pt_capi_internal.hpp"
 
 #include <algorithm>
@@ -17,6 +19,7 @@
 #include "pt_display_table.hpp"
 #include "pt_local.hpp"
 #include "pt_meter.hpp"
+#include "pt_optics.hpp"
 
 using ptc::fail;
 using ptc::guarded;
@@ -83,6 +86,7 @@ struct GradeRequest {
     ptc::BloomSetup bloom;   // on: the bloom kernels run between the exposure and the display kernel
     ptc::LocalSetup local;   // on: the local exposure kernels run behind them
     ptc::ColourSetup colour; // on: the colour display kernel takes the graded one's place
+    ptc::OpticsSetup optics; // on: the optics kernel runs ahead of the meter, and everything behind it reads what it wrote
     int32_t width = 0, height = 0;   // of the image the display kernel reads (bloom and local exposure need its shape)
 };
 
@@ -116,11 +120,15 @@ struct DisplayDevice {
     ptc::DeviceBuffer d_lut;
     uint64_t lut_generation = 0;
     size_t lut_room = 0;
+    // lens optics: the mean image the stage writes, allocated by the first present with it
+    ptc::DeviceBuffer d_optics;
+    ptc::MeanPlanes optics_out;
 
     int alloc(size_t pixels, const char *what) {
         n = pixels;
         d_bloom.reset();   // (of another size's image)
         d_local.reset();
+        d_optics.reset();
         ptc::PlaneLayout l;
         const size_t o_bgr = l.add((n + 3) / 4 * 12), o_list = l.add(16 * n), o_len = l.add(4);
         const size_t o_grade = l.add(kGradeBytes);
@@ -149,6 +157,15 @@ struct DisplayDevice {
         const int rc = d_local.alloc(l, what);
         if (rc != PT_OK) return rc;
         localised = d_local.at<float>(o_out); local_base[0] = d_local.at<float>(o_b0); local_base[1] = d_local.at<float>(o_b1);
+        return PT_OK;
+    }
+    int ensure_optics(const char *what) {
+        if (d_optics) return PT_OK;
+        ptc::PlaneLayout l;
+        optics_out = ptc::MeanPlanes::in(l, n);
+        const int rc = d_optics.alloc(l, what);
+        if (rc != PT_OK) return rc;
+        optics_out.bind(d_optics);
         return PT_OK;
     }
     // (no kernel of this object is in flight: every call that launches one waits for it)
@@ -205,6 +222,16 @@ struct DisplayDevice {
         if (!grade) {
             PT_HIP_TRY(pt::launch_display(a, stream));
             return PT_OK;
+        }
+        if (grade->optics.on) {   // the lens first: the meter and everything behind it read mean' and count'
+            pt::OpticsArgs o;
+            o.width = grade->width; o.height = grade->height; o.divide = a.divide;
+            o.rgb = a.rgb; o.count = a.count;
+            o.k1 = grade->optics.k1; o.k2 = grade->optics.k2; o.vignette = grade->optics.vignette;
+            for (int k = 0; k < 3; ++k) o.mag[k] = grade->optics.mag[k];
+            o.out_rgb = optics_out.rgb; o.out_count = optics_out.count;
+            PT_HIP_TRY(pt::launch_optics(o, stream));
+            a.rgb = optics_out.rgb; a.count = optics_out.count; a.divide = 0;
         }
         PT_HIP_TRY(hipMemsetAsync(hist, 0, kGradeBytes, stream));
         if (grade->setup.automatic) {
@@ -377,6 +404,7 @@ struct PresentRequest {
     const pt_local_params *local;         // with grade only
     pt_grade_info *grade_info;            // with grade only; may be NULL
     const pt_colour_params *colour;       // with grade only
+    const pt_optics_params *optics;       // with grade only
 };
 
 int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, pt_display_info *info) {
@@ -391,6 +419,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (rq.bloom && (rc = ptc::bloom_params_check(rq.bloom, grade.bloom)) != PT_OK) return rc;
     if (rq.local && (rc = ptc::local_params_check(rq.local, grade.local)) != PT_OK) return rc;
     if (rq.colour && (rc = ptc::colour_params_check(rq.colour, grade.colour)) != PT_OK) return rc;
+    if (rq.optics && (rc = ptc::optics_params_check(rq.optics, grade.optics)) != PT_OK) return rc;
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -422,6 +451,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (grade.bloom.on && (rc = dev.ensure_bloom(grade.width, grade.height, "pt_display_present_bloom")) != PT_OK) return rc;
     if (grade.local.on && (rc = dev.ensure_local("pt_display_present_local")) != PT_OK) return rc;
     if (grade.colour.lut && (rc = dev.use_lut(grade.colour.lut, "pt_display_present_colour")) != PT_OK) return rc;
+    if (grade.optics.on && (rc = dev.ensure_optics("pt_display_present_optics")) != PT_OK) return rc;
     if (temporal && !d->history && (rc = pt_temporal_create(scene, d->width, d->height, d->eps, &d->history)) != PT_OK) return rc;
     if (filter && !temporal && (rc = ensure_filter(d)) != PT_OK) return rc;
     {   // the chain, behind every slice enqueued so far: no host synchronisation until its last kernel is in the queue
@@ -568,32 +598,38 @@ int pt_display_create_frame(pt_frame *frame, float eps, pt_display **out) {
 }
 
 int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return display_present_impl(d, {p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info); });
+    return guarded([&] { return display_present_impl(d, {p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info); });
 }
 
 int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return u ? display_present_impl(d, {p, u, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info) : null_argument(); });
+    return guarded([&] { return u ? display_present_impl(d, {p, u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_graded(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g, uint8_t *bgr,
                               pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g ? display_present_impl(d, {p, u, g, nullptr, nullptr, grade_info, nullptr}, bgr, info) : null_argument(); });
+    return guarded([&] { return g ? display_present_impl(d, {p, u, g, nullptr, nullptr, grade_info, nullptr, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_bloom(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                              const pt_bloom_params *b, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g && b ? display_present_impl(d, {p, u, g, b, nullptr, grade_info, nullptr}, bgr, info) : null_argument(); });
+    return guarded([&] { return g && b ? display_present_impl(d, {p, u, g, b, nullptr, grade_info, nullptr, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_local(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                              const pt_bloom_params *b, const pt_local_params *l, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g && b && l ? display_present_impl(d, {p, u, g, b, l, grade_info, nullptr}, bgr, info) : null_argument(); });
+    return guarded([&] { return g && b && l ? display_present_impl(d, {p, u, g, b, l, grade_info, nullptr, nullptr}, bgr, info) : null_argument(); });
 }
 
 int pt_display_present_colour(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                               const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c, uint8_t *bgr, pt_display_info *info,
                               pt_grade_info *grade_info) {
-    return guarded([&] { return g && b && l && c ? display_present_impl(d, {p, u, g, b, l, grade_info, c}, bgr, info) : null_argument(); });
+    return guarded([&] { return g && b && l && c ? display_present_impl(d, {p, u, g, b, l, grade_info, c, nullptr}, bgr, info) : null_argument(); });
+}
+
+int pt_display_present_optics(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
+                              const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c, const pt_optics_params *o,
+                              uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
+    return guarded([&] { return g && b && l && c && o ? display_present_impl(d, {p, u, g, b, l, grade_info, c, o}, bgr, info) : null_argument(); });
 }
 
 int pt_display_reset(pt_display *d) {

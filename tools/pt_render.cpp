@@ -90,8 +90,16 @@
 // see the mean before the matrix; previews stay as they are.  It works on the host path and with -DEVICE_RESOLVE 1, with
 // byte-identical files, and with every flag grading works with (alone it runs with the zeroed grade).  Without these flags nothing
 // changes.
+// Lens optics (pt_optics_host, pt_display_present_optics, not in the reference): -DISTORTION <k1,k2, default 0,0> bends straight lines
+// (f = 1 + r2 (k1 + k2 r2) with r measured in half image heights; k1 < 0 barrel, k1 > 0 pincushion), -CA <a, default 0> magnifies the
+// red and blue channels by 1 - a and 1 + a (lateral chromatic aberration), -VIGNETTE <v, default 0> darkens the corners by
+// 1 / (1 + v r2)^2, on the linear mean at the written size, after the upsample and BEFORE the meter, bloom, local exposure and the
+// grade, which see the image the lens delivers and its count; previews stay as they are.  The library judges the values (|k| <= 4,
+// |a| <= 0.25, 0 <= v <= 64) and its message goes to stderr with exit status 2.  It works on the host path and with -DEVICE_RESOLVE 1,
+// with byte-identical files, and with every flag grading works with (alone it runs with the zeroed grade).  Without these flags
+// nothing changes.
 // The image chain is stated once, in HostChain::bytes, in the order the paragraphs above give: temporal merge -> first-hit
-// features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> meter, bloom, local exposure, colour / grade -> tone map
+// features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> optics -> meter, bloom, local exposure, colour / grade -> tone map
 // -> -GAUSS / -MEDIAN -> quantize.  A single frame and every frame of a sequence go through it; with -DEVICE_RESOLVE 1 the
 // bytes come from present() instead.
 #include <algorithm>
@@ -146,6 +154,8 @@ struct Options {
     std::string wb, saturation, colour_matrix, lut_path;   // -WB, -SATURATION, -COLOR_MATRIX, -LUT as given
     pt_colour_params colour{};     // what they make; colour.lut is owned here
     pt_lut *lut = nullptr;
+    std::string distortion, ca, vignette;   // -DISTORTION, -CA, -VIGNETTE as given
+    pt_optics_params optics{};     // what they make
     pt_upsample_params upsample{};
     pt_grade_params grade{};       // zeroed without -TONE / -EXPOSURE / -AUTO_EXPOSURE: the reference's bytes
     pt_display_params show{};      // what a present of the device path is asked for
@@ -157,6 +167,7 @@ struct Options {
     bool display = false;          // -DEVICE_RESOLVE 1 and nothing that keeps the image on the host path
     bool blooming = false, localising = false, grading = false;   // -BLOOM > 0; -LOCAL > 0; either, colour, or any of the tone flags
     bool colouring = false;        // a matrix that is not the identity, or a LUT
+    bool optical = false;          // any of -DISTORTION / -CA / -VIGNETTE is not zero (it makes `grading` true as well)
     pt_camera view;                // with `camera`
     pt_lens lens{0.0f, 0.0f};
     bool has_lens = false;
@@ -241,6 +252,9 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-SATURATION") o.saturation = v;
         if (f == "-COLOR_MATRIX") o.colour_matrix = v;
         if (f == "-LUT") o.lut_path = v;
+        if (f == "-DISTORTION") o.distortion = v;
+        if (f == "-CA") o.ca = v;
+        if (f == "-VIGNETTE") o.vignette = v;
     }
 }
 
@@ -275,6 +289,15 @@ bool parse_float(const std::string &text, float &out) {
     char *end = nullptr;
     out = std::strtof(text.c_str(), &end);
     return end != text.c_str() && *end == '\0' && std::isfinite(out);
+}
+
+// one number, nothing else -- finite or not: whoever asks judges the value
+bool parse_number(const char *text, char stop, float &out, const char **rest) {
+    char *end = nullptr;
+    out = std::strtof(text, &end);
+    if (end == text || *end != stop) return false;
+    *rest = end + 1;
+    return true;
 }
 
 int die(const char *what) {
@@ -424,7 +447,23 @@ int configure(int argc, char **argv, Options &o) {
         const float identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
         o.colouring = o.lut != nullptr || std::memcmp(m, identity, sizeof m) != 0;
     }
-    o.grading = o.tone_flags || o.blooming || o.localising || o.colouring;
+    // -DISTORTION / -CA / -VIGNETTE: the optics stage, ahead of the meter; alone it runs with the zeroed grade too.  The values are
+    // the library's to judge: pt_optics_host checks them before it looks at a device, so a call that names none answers for them.
+    if (!o.distortion.empty() || !o.ca.empty() || !o.vignette.empty()) {
+        const char *rest = nullptr;
+        if (!o.distortion.empty() && !(parse_number(o.distortion.c_str(), ',', o.optics.k1, &rest) && parse_number(rest, '\0', o.optics.k2, &rest)))
+            return refuse(2, "-DISTORTION takes two comma-separated numbers, k1,k2");
+        if (!o.ca.empty() && !parse_number(o.ca.c_str(), '\0', o.optics.ca, &rest)) return refuse(2, "-CA takes a number");
+        if (!o.vignette.empty() && !parse_number(o.vignette.c_str(), '\0', o.optics.vignette, &rest)) return refuse(2, "-VIGNETTE takes a number");
+        const float one_mean[3] = {0, 0, 0};
+        const int32_t one_count = 0;
+        float out_mean[3];
+        int32_t out_count;
+        if (pt_optics_host(-1, 1, 1, one_mean, &one_count, &o.optics, out_mean, &out_count, nullptr) == PT_ERR_INVALID_ARGUMENT)
+            return refuse(2, std::string("-DISTORTION / -CA / -VIGNETTE (") + pt_last_error() + ")");
+        o.optical = o.optics.k1 != 0.0f || o.optics.k2 != 0.0f || o.optics.ca != 0.0f || o.optics.vignette != 0.0f;
+    }
+    o.grading = o.tone_flags || o.blooming || o.localising || o.colouring || o.optical;
     // -TONE / -EXPOSURE / -AUTO_EXPOSURE: what every graded image is asked for
     if (o.tone_flags) {
         const char *names[4] = {"reference", "clamp", "reinhard", "aces"};
@@ -535,10 +574,12 @@ struct HostFrame {
     uint8_t *image() { return out_bgr.empty() ? bgr.data() : out_bgr.data(); }
 };
 
-// The device path's present: plain, scaled, or either with grading, bloom, local exposure or colour
+// The device path's present: plain, scaled, or either with grading, bloom, local exposure, colour or optics
 int present(const Run &r, HostFrame &host, pt_display_info *info) {
     const Options &o = r.o;
     const pt_upsample_params *up = o.scale > 1 ? &o.upsample : nullptr;
+    if (o.optical)
+        return pt_display_present_optics(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, &o.optics, host.image(), info, nullptr);
     if (o.colouring) return pt_display_present_colour(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, host.image(), info, nullptr);
     if (o.localising) return pt_display_present_local(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, host.image(), info, nullptr);
     if (o.blooming) return pt_display_present_bloom(r.display, &o.show, up, &o.grade, &o.bloom, host.image(), info, nullptr);
@@ -585,7 +626,8 @@ private:
     pt_temporal *history = nullptr;
     const pt_denoise_params mean_only{};   // levels 0: mean = sum / n, on the host
     std::vector<float> msum, msum2, mean, up_mean, rgb, pos, nrm, alb;
-    std::vector<int32_t> mcount, mean_count, up_count, hit;
+    std::vector<float> lens_mean;
+    std::vector<int32_t> mcount, mean_count, up_count, lens_count, hit;
     bool has_exposure = false;
     float last_exposure = 0.0f;
 };
@@ -649,6 +691,11 @@ bool HostChain::bytes(HostFrame &host, float dispersion[3], ChainTimes &times) {
                                                 up_count.data(), nullptr) != PT_OK)
             return false;
         m = up_mean.data(); n = up_count.data();
+    }
+    if (o.optical) {   // optics: what follows reads the image the lens delivers, and its count
+        lens_mean.resize(3 * static_cast<size_t>(w) * h); lens_count.resize(static_cast<size_t>(w) * h);
+        if (pt_optics_host(dev, w, h, m, n, &o.optics, lens_mean.data(), lens_count.data(), nullptr) != PT_OK) return false;
+        m = lens_mean.data(); n = lens_count.data();
     }
     rgb.resize(3 * static_cast<size_t>(w) * h);
     if (o.grading) {   // meter (a sequence's frame starts from the previous frame's exposure), bloom, local exposure, grade
