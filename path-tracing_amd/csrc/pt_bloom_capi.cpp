@@ -5,8 +5,6 @@
 #include <cmath>
 #include <cstring>
 
-#include "pt_bloom.hpp"
-
 using ptc::fail;
 using ptc::guarded;
 using ptc::hip_fail;
@@ -46,24 +44,16 @@ int bloom_host_impl(int device, int32_t width, int32_t height, const float *mean
     }
     ptc::PlaneLayout l;
     ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
-    const size_t o_e = l.add(4), o_out = l.add(12 * n);
-    const size_t o_pyr = l.add(16 * pt::bloom_pyramid_records(width, height, setup.levels));
+    const size_t o_e = l.add(4);
+    ptc::BloomPlanes work = ptc::BloomPlanes::in(l, n, pt::bloom_pyramid_records(width, height, setup.levels));
     ptc::DeviceBuffer d;
-    ptc::DeviceTimer timer;
-    if ((rc = d.alloc(l, "pt_bloom_host")) != PT_OK || (rc = timer.create("pt_bloom_host")) != PT_OK) return rc;
-    in.bind(d);
+    if ((rc = d.alloc(l, "pt_bloom_host")) != PT_OK) return rc;
+    in.bind(d); work.bind(d);
     if ((rc = in.upload(mean_rgb, count)) != PT_OK) return rc;
     PT_HIP_TRY(hipMemcpy(d.at<void>(o_e), &exposure, 4, hipMemcpyHostToDevice));
-    pt::BloomArgs a;
-    a.width = width; a.height = height; a.levels = setup.levels; a.divide = 0;
-    a.rgb = in.rgb; a.count = in.count; a.exposure = d.at<float>(o_e);
-    a.threshold = setup.threshold; a.weight = setup.weight;
-    a.pyramid = d.at<void>(o_pyr); a.out_rgb = d.at<float>(o_out);
-    PT_HIP_TRY(timer.begin(nullptr));
-    PT_HIP_TRY(pt::launch_bloom(a, nullptr));
-    PT_HIP_TRY(timer.end(nullptr));
+    const auto a = ptc::bloom_args(setup, {in.rgb, in.count, false, width, height}, d.at<float>(o_e), work);
     float ms = 0.0f;
-    PT_HIP_TRY(timer.wait_ms(&ms));
+    if ((rc = ptc::timed(nullptr, "pt_bloom_host", &ms, [&]() -> int { PT_HIP_TRY(pt::launch_bloom(a, nullptr)); return PT_OK; })) != PT_OK) return rc;
     PT_HIP_TRY(hipMemcpy(out_rgb, a.out_rgb, 12 * n, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;

@@ -2,7 +2,8 @@
 // multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
 // pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
 // display path, which chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
-// arguments, and the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments.
+// arguments, the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments, and the timed region
+// of a one-shot entry point.
 // Nothing here is part of the ABI.
 #pragma once
 #include "../../include/pt_hip.h"
@@ -16,11 +17,15 @@
 #include <string>
 #include <vector>
 
+#include "pt_bloom.hpp"
 #include "pt_colour.hpp"
 #include "pt_denoise.hpp"
 #include "pt_device_mem.hpp"
 #include "pt_grade.hpp"
 #include "pt_kernels.hpp"
+#include "pt_local.hpp"
+#include "pt_meter.hpp"
+#include "pt_optics.hpp"
 #include "pt_scene.hpp"
 #include "pt_upsample.hpp"
 
@@ -143,6 +148,21 @@ int guarded(F &&f) noexcept {
     }
 }
 
+// A timed region of a one-shot entry point: the two events made, begin recorded on `stream`, what `enqueue` puts there (it answers
+// a status; a failure is returned as it is, with no end recorded and no wait), end recorded, the wait, the milliseconds between.
+// The events go with the call.  (The texts are those of the entry points that spelled this out, each on the null stream.)
+template <class F>
+int timed(hipStream_t stream, const char *what, float *ms, F &&enqueue) {
+    DeviceTimer timer;
+    int rc = timer.create(what);
+    if (rc != PT_OK) return rc;
+    if (const hipError_t e = timer.begin(stream)) return hip_fail(e, "timer.begin(nullptr)");
+    if ((rc = enqueue()) != PT_OK) return rc;
+    if (const hipError_t e = timer.end(stream)) return hip_fail(e, "timer.end(nullptr)");
+    if (const hipError_t e = timer.wait_ms(ms)) return hip_fail(e, "timer.wait_ms(&ms)");
+    return PT_OK;
+}
+
 // The two checks whose text every stage shares: `prefix` names the stage ("bloom: "), `tail` is what a handle's creation adds.
 inline int check_image_size(int32_t width, int32_t height, const char *prefix = "") {
     if (static_cast<long long>(width) * height > 0x7fffffffLL / 4) return fail(PT_ERR_INVALID_ARGUMENT, std::string(prefix) + "image too large");
@@ -247,6 +267,36 @@ struct OpticsSetup {
     float vignette = 0.0f;
 };
 int optics_params_check(const pt_optics_params *o, OpticsSetup &out);
+
+// The image a chain has reached: planes on the device, sums still (divide) or means, and its size.
+struct Image { const float *rgb; const int32_t *count; bool divide; int32_t width, height; };
+// One image-space stage's launch arguments -- the only place each of these structs is filled: its checked parameters, the image it
+// reads, the device scalar e where it has one, and where it writes (its view of pt_device_mem.hpp).
+inline pt::OpticsArgs optics_args(const OpticsSetup &s, const Image &in, const MeanPlanes &out) {
+    pt::OpticsArgs a;
+    a.width = in.width; a.height = in.height; a.divide = in.divide ? 1 : 0; a.rgb = in.rgb; a.count = in.count;
+    a.k1 = s.k1; a.k2 = s.k2; a.vignette = s.vignette; a.out_rgb = out.rgb; a.out_count = out.count;
+    for (int k = 0; k < 3; ++k) a.mag[k] = s.mag[k];
+    return a;
+}
+inline pt::MeterArgs meter_args(const Image &in, uint32_t *hist) {
+    pt::MeterArgs a;
+    a.n = in.width * in.height; a.divide = in.divide ? 1 : 0; a.rgb = in.rgb; a.count = in.count; a.hist = hist;
+    return a;
+}
+inline pt::BloomArgs bloom_args(const BloomSetup &s, const Image &in, const float *exposure, const BloomPlanes &w) {
+    pt::BloomArgs a;
+    a.width = in.width; a.height = in.height; a.divide = in.divide ? 1 : 0; a.rgb = in.rgb; a.count = in.count; a.exposure = exposure;
+    a.levels = s.levels; a.threshold = s.threshold; a.weight = s.weight; a.pyramid = w.pyramid; a.out_rgb = w.out_rgb;
+    return a;
+}
+inline pt::LocalArgs local_args(const LocalSetup &s, const Image &in, const float *exposure, const LocalPlanes &w) {
+    pt::LocalArgs a;
+    a.width = in.width; a.height = in.height; a.divide = in.divide ? 1 : 0; a.rgb = in.rgb; a.count = in.count; a.exposure = exposure;
+    a.levels = s.levels; a.strength = s.strength; a.pivot = s.pivot; a.sigma = s.sigma;
+    a.base[0] = w.base[0]; a.base[1] = w.base[1]; a.out_rgb = w.out_rgb;
+    return a;
+}
 
 // pt_temporal_push_host in two halves, for a chain whose frame already lies on the device (pt_display_present).
 // temporal_enqueue checks the parameters and enqueues features -> merge -> filter on `stream`, reading the frame's accumulators

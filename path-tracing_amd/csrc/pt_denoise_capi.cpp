@@ -108,13 +108,8 @@ static int denoise_host_impl(int device, int32_t width, int32_t height, const fl
     a.width = width; a.height = height;
     ptc::bind_planes(a, acc, f, work);
     if ((rc = acc.upload(sum, sum2, count)) != PT_OK || (rc = f.upload(position, normal, albedo, hit_index)) != PT_OK) return rc;
-    ptc::DeviceTimer timer;
-    if ((rc = timer.create("pt_denoise_host")) != PT_OK) return rc;
-    PT_HIP_TRY(timer.begin(nullptr));
-    PT_HIP_TRY(pt::launch_denoise(a, nullptr));
-    PT_HIP_TRY(timer.end(nullptr));
     float ms = 0.0f;
-    PT_HIP_TRY(timer.wait_ms(&ms));
+    if ((rc = ptc::timed(nullptr, "pt_denoise_host", &ms, [&]() -> int { PT_HIP_TRY(pt::launch_denoise(a, nullptr)); return PT_OK; })) != PT_OK) return rc;
     if ((rc = work.out.download(mean_rgb, count_out)) != PT_OK) return rc;
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;

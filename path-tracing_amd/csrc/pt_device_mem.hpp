@@ -1,6 +1,6 @@
-// Owners of what the host layer holds on a device: one hipMalloc, one event, one stream, the event pair of a timed region -- and
-// the one spelling of "one allocation cut into 256-byte aligned planes": PlaneLayout, and a view for every set of planes that
-// more than one place lays out (accumulators, mean and count, first-hit features, the denoiser's and the upsampler's work planes).
+// Owners of what the host layer holds on a device: one hipMalloc, one event, one stream, the event pair of a timed region -- and the
+// one spelling of "one allocation cut into 256-byte aligned planes": PlaneLayout, and a view for every set of planes that more than one
+// place lays out (accumulators, mean and count, first-hit features, the work planes of the denoiser, the upsampler, bloom, local exposure).
 // Host only; nothing here is part of the ABI.
 // An owner frees in its destructor, on whatever device is current: the handle that holds it (pt_scene, pt_session, pt_frame,
 // pt_temporal) makes its own device current first -- in its destructor's body, which runs before the members go.  An empty
@@ -254,6 +254,35 @@ struct UpsamplePlanes {
         rec_a = b.at<void>(offset[0]); rec_b = b.at<void>(offset[1]); rec_c = b.at<void>(offset[2]);
         if (own_mean) mean_lo = b.at<float>(offset[3]);
     }
+};
+
+// What bloom works in: the plane of bloomed means it writes and the pyramid, `records` records of 16 bytes -- what
+// pt::bloom_pyramid_records gives for the image and the levels; the caller's to ask, this header knows no kernel's.
+struct BloomPlanes {
+    float *out_rgb = nullptr;
+    void *pyramid = nullptr;
+    size_t n = 0;
+    size_t offset[2] = {0, 0};
+    static BloomPlanes in(PlaneLayout &l, size_t n, size_t records) {
+        BloomPlanes w;
+        w.n = n; w.offset[0] = l.add(12 * n); w.offset[1] = l.add(16 * records);
+        return w;
+    }
+    void bind(const DeviceBuffer &b) { out_rgb = b.at<float>(offset[0]); pyramid = b.at<void>(offset[1]); }
+};
+
+// What local exposure works in: the plane of locally exposed means it writes and the two planes of the base (a float per pixel each).
+struct LocalPlanes {
+    float *out_rgb = nullptr, *base[2] = {nullptr, nullptr};
+    size_t n = 0;
+    size_t offset[3] = {0, 0, 0};
+    static LocalPlanes in(PlaneLayout &l, size_t n) {
+        LocalPlanes w;
+        w.n = n;
+        for (int k = 0; k < 3; ++k) w.offset[k] = l.add((k < 1 ? 12 : 4) * n);
+        return w;
+    }
+    void bind(const DeviceBuffer &b) { out_rgb = b.at<float>(offset[0]); base[0] = b.at<float>(offset[1]); base[1] = b.at<float>(offset[2]); }
 };
 
 }  // namespace ptc

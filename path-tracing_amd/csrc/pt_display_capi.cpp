@@ -14,12 +14,8 @@
 #include <cmath>
 #include <cstring>
 
-#include "pt_bloom.hpp"
 #include "pt_display.hpp"
 #include "pt_display_table.hpp"
-#include "pt_local.hpp"
-#include "pt_meter.hpp"
-#include "pt_optics.hpp"
 
 using ptc::fail;
 using ptc::guarded;
@@ -50,34 +46,6 @@ std::shared_ptr<const DisplayTable> display_table(float gamma) {
     return t;
 }
 
-// What the kernel would have written for a pixel it deferred: the host's own two steps.
-void finish_on_host(const std::vector<pt::DisplayDeferred> &list, float gamma, uint8_t *bgr) {
-    for (const pt::DisplayDeferred &d : list) {
-        const size_t p = static_cast<size_t>(d.pixel);
-        bgr[3 * p + 0] = ptc::quantize_value(ptc::tonemap_value(d.mean[2], gamma));
-        bgr[3 * p + 1] = ptc::quantize_value(ptc::tonemap_value(d.mean[1], gamma));
-        bgr[3 * p + 2] = ptc::quantize_value(ptc::tonemap_value(d.mean[0], gamma));
-    }
-}
-// The same for a graded image: the list carries the ungraded mean, the grade is the host chain's own (pt_grade.hpp).
-void finish_on_host_graded(const std::vector<pt::DisplayDeferred> &list, float gamma, int curve, float e, uint8_t *bgr) {
-    for (const pt::DisplayDeferred &d : list) {
-        const size_t p = static_cast<size_t>(d.pixel);
-        for (int k = 0; k < 3; ++k)
-            bgr[3 * p + k] = ptc::quantize_value(ptc::tonemap_value(pt::grade_value(curve, d.mean[2 - k], e), gamma));
-    }
-}
-
-// The same with the colour stage: matrix -> exposure -> curve -> LUT on the mean the list carries (pt_colour.hpp, on the host's LUT).
-void finish_on_host_colour(const std::vector<pt::DisplayDeferred> &list, float gamma, int curve, float e, const pt::ColourStep &step, uint8_t *bgr) {
-    for (const pt::DisplayDeferred &d : list) {
-        const size_t p = static_cast<size_t>(d.pixel);
-        float v[3] = {d.mean[0], d.mean[1], d.mean[2]};
-        pt::colour_pixel(step, curve, e, v[0], v[1], v[2]);
-        for (int k = 0; k < 3; ++k) bgr[3 * p + k] = ptc::quantize_value(ptc::tonemap_value(v[2 - k], gamma));
-    }
-}
-
 // What a graded present is asked for: the checked parameters, and the display's previous metered exposure.
 struct GradeRequest {
     ptc::GradeSetup setup;
@@ -87,11 +55,26 @@ struct GradeRequest {
     ptc::LocalSetup local;   // on: the local exposure kernels run behind them
     ptc::ColourSetup colour; // on: the colour display kernel takes the graded one's place
     ptc::OpticsSetup optics; // on: the optics kernel runs ahead of the meter, and everything behind it reads what it wrote
-    int32_t width = 0, height = 0;   // of the image the display kernel reads (bloom and local exposure need its shape)
 };
 
-// The image a chain has reached: planes on the device, sums still (divide) or means.
-struct Image { const float *rgb; const int32_t *count; bool divide; };
+// What the tone map gets for a pixel the kernel deferred, from the mean its entry carries: the mean itself (no exposure is
+// multiplied in), the host chain's own grade of it (pt_grade.hpp), or matrix -> exposure -> curve -> LUT (pt_colour.hpp, on the
+// host's LUT).  Three computations, none made of another: NaN payloads and -0 come out as each kernel's.
+void deferred_value(const float *mean, const GradeRequest *grade, float e, float *v) {
+    for (int k = 0; k < 3; ++k) v[k] = mean[k];
+    if (!grade) return;
+    if (grade->colour.on) pt::colour_pixel(grade->colour.step, grade->setup.curve, e, v[0], v[1], v[2]);
+    else for (int k = 0; k < 3; ++k) v[k] = pt::grade_value(grade->setup.curve, mean[k], e);
+}
+// What the kernel would have written for the pixels it deferred: the host's own two steps on that value.
+void finish_on_host(const std::vector<pt::DisplayDeferred> &list, float gamma, const GradeRequest *grade, float e, uint8_t *bgr) {
+    for (const pt::DisplayDeferred &d : list) {
+        const size_t p = static_cast<size_t>(d.pixel);
+        float v[3];
+        deferred_value(d.mean, grade, e, v);
+        for (int k = 0; k < 3; ++k) bgr[3 * p + k] = ptc::quantize_value(ptc::tonemap_value(v[2 - k], gamma));
+    }
+}
 // What collect brings back besides the bytes (used: of a graded image).
 struct Presented { int32_t n_deferred = 0; pt_grade_info used{}; };
 
@@ -110,12 +93,10 @@ struct DisplayDevice {
     size_t band_room = 0;
     // bloom: the deepest pyramid of the image and the plane of bloomed means, allocated by the first bloomed present
     ptc::DeviceBuffer d_bloom;
-    void *pyramid = nullptr;
-    float *bloomed = nullptr;
+    ptc::BloomPlanes bloom;
     // local exposure: the two planes of the base and the plane of locally exposed means, allocated by the first present with the stage
     ptc::DeviceBuffer d_local;
-    float *local_base[2] = {nullptr, nullptr};
-    float *localised = nullptr;
+    ptc::LocalPlanes local;
     // colour grading: the LUT of the last present with one, and the generation of the pt_lut it was copied from (0: none)
     ptc::DeviceBuffer d_lut;
     uint64_t lut_generation = 0;
@@ -141,33 +122,21 @@ struct DisplayDevice {
         n_deferred = d_out.at<uint32_t>(o_len);
         return PT_OK;
     }
+    // A lazily made plane set: laid out, allocated and bound by the first present that needs it.
+    template <class View, class... Sizes>
+    static int ensure(ptc::DeviceBuffer &buffer, View &view, const char *what, Sizes... sizes) {
+        if (buffer) return PT_OK;
+        ptc::PlaneLayout l;
+        view = View::in(l, sizes...);
+        const int rc = buffer.alloc(l, what);
+        if (rc == PT_OK) view.bind(buffer);
+        return rc;
+    }
     int ensure_bloom(int32_t width, int32_t height, const char *what) {
-        if (d_bloom) return PT_OK;
-        ptc::PlaneLayout l;
-        const size_t o_out = l.add(12 * n), o_pyr = l.add(16 * pt::bloom_pyramid_records(width, height, pt::kBloomMaxLevels));
-        const int rc = d_bloom.alloc(l, what);
-        if (rc != PT_OK) return rc;
-        bloomed = d_bloom.at<float>(o_out); pyramid = d_bloom.at<void>(o_pyr);
-        return PT_OK;
+        return ensure(d_bloom, bloom, what, n, pt::bloom_pyramid_records(width, height, pt::kBloomMaxLevels));
     }
-    int ensure_local(const char *what) {
-        if (d_local) return PT_OK;
-        ptc::PlaneLayout l;
-        const size_t o_out = l.add(12 * n), o_b0 = l.add(4 * n), o_b1 = l.add(4 * n);
-        const int rc = d_local.alloc(l, what);
-        if (rc != PT_OK) return rc;
-        localised = d_local.at<float>(o_out); local_base[0] = d_local.at<float>(o_b0); local_base[1] = d_local.at<float>(o_b1);
-        return PT_OK;
-    }
-    int ensure_optics(const char *what) {
-        if (d_optics) return PT_OK;
-        ptc::PlaneLayout l;
-        optics_out = ptc::MeanPlanes::in(l, n);
-        const int rc = d_optics.alloc(l, what);
-        if (rc != PT_OK) return rc;
-        optics_out.bind(d_optics);
-        return PT_OK;
-    }
+    int ensure_local(const char *what) { return ensure(d_local, local, what, n); }
+    int ensure_optics(const char *what) { return ensure(d_optics, optics_out, what, n); }
     // (no kernel of this object is in flight: every call that launches one waits for it)
     int use_lut(const pt_lut *lut, const char *what) {
         if (lut_generation == lut->generation) return PT_OK;
@@ -206,9 +175,35 @@ struct DisplayDevice {
         host = t;
         return PT_OK;
     }
-    // Zero the list's length and launch the kernel on `stream`; with `grade`, the exposure first -- metered from the image the
-    // kernel is about to read, or the manual one written into the device scalar -- and then the graded kernel.
-    int enqueue(const Image &image, hipStream_t stream, const GradeRequest *grade) {
+    // Zero the list's length and launch the kernel on `stream`; with `grade`, the stages ahead of the graded or the colour kernel first, each
+    // on the image the one before it left: the lens, the exposure (metered from the image, or the manual one), bloom, local exposure.
+    int enqueue(ptc::Image image, hipStream_t stream, const GradeRequest *grade) {
+        PT_HIP_TRY(hipMemsetAsync(n_deferred, 0, 4, stream));
+        if (grade && grade->optics.on) {   // the meter and everything behind it read mean' and count'
+            const auto o = ptc::optics_args(grade->optics, image, optics_out);
+            PT_HIP_TRY(pt::launch_optics(o, stream));
+            image.rgb = optics_out.rgb; image.count = optics_out.count; image.divide = false;
+        }
+        if (grade) PT_HIP_TRY(hipMemsetAsync(hist, 0, kGradeBytes, stream));
+        if (grade && grade->setup.automatic) {
+            const auto m = ptc::meter_args(image, hist);
+            PT_HIP_TRY(pt::launch_meter(m, stream));
+            PT_HIP_TRY(pt::launch_exposure(hist, grade->setup.rule, grade->has_prev, grade->e_prev, exposure, stream));
+        } else if (grade) {
+            uint32_t bits;
+            std::memcpy(&bits, &grade->setup.exposure, sizeof bits);
+            PT_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&exposure->exposure), static_cast<int>(bits), 1, stream));
+        }
+        if (grade && grade->bloom.on) {   // m + A * weight, a plane of means, with the count as it is
+            const auto b = ptc::bloom_args(grade->bloom, image, &exposure->exposure, bloom);
+            PT_HIP_TRY(pt::launch_bloom(b, stream));
+            image.rgb = bloom.out_rgb; image.divide = false;
+        }
+        if (grade && grade->local.on) {   // ... and then m * g of that plane, or of the image so far
+            const auto l = ptc::local_args(grade->local, image, &exposure->exposure, local);
+            PT_HIP_TRY(pt::launch_local(l, stream));
+            image.rgb = local.out_rgb; image.divide = false;
+        }
         pt::DisplayArgs a;
         a.n = static_cast<int>(n);
         a.divide = image.divide ? 1 : 0;
@@ -218,57 +213,13 @@ struct DisplayDevice {
         a.n_bands = static_cast<int>(host->band_lo.size());
         a.band_lo = band_lo; a.band_hi = band_hi;
         a.bgr = bgr; a.deferred = deferred; a.n_deferred = n_deferred;
-        PT_HIP_TRY(hipMemsetAsync(n_deferred, 0, 4, stream));
-        if (!grade) {
-            PT_HIP_TRY(pt::launch_display(a, stream));
-            return PT_OK;
-        }
-        if (grade->optics.on) {   // the lens first: the meter and everything behind it read mean' and count'
-            pt::OpticsArgs o;
-            o.width = grade->width; o.height = grade->height; o.divide = a.divide;
-            o.rgb = a.rgb; o.count = a.count;
-            o.k1 = grade->optics.k1; o.k2 = grade->optics.k2; o.vignette = grade->optics.vignette;
-            for (int k = 0; k < 3; ++k) o.mag[k] = grade->optics.mag[k];
-            o.out_rgb = optics_out.rgb; o.out_count = optics_out.count;
-            PT_HIP_TRY(pt::launch_optics(o, stream));
-            a.rgb = optics_out.rgb; a.count = optics_out.count; a.divide = 0;
-        }
-        PT_HIP_TRY(hipMemsetAsync(hist, 0, kGradeBytes, stream));
-        if (grade->setup.automatic) {
-            pt::MeterArgs m;
-            m.n = a.n; m.divide = a.divide; m.rgb = a.rgb; m.count = a.count; m.hist = hist;
-            PT_HIP_TRY(pt::launch_meter(m, stream));
-            PT_HIP_TRY(pt::launch_exposure(hist, grade->setup.rule, grade->has_prev, grade->e_prev, exposure, stream));
-        } else {
-            uint32_t bits;
-            std::memcpy(&bits, &grade->setup.exposure, sizeof bits);
-            PT_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&exposure->exposure), static_cast<int>(bits), 1, stream));
-        }
-        if (grade->bloom.on) {   // the display kernel reads m + A * weight, a plane of means, with the chain's count
-            pt::BloomArgs b;
-            b.width = grade->width; b.height = grade->height; b.levels = grade->bloom.levels; b.divide = a.divide;
-            b.rgb = a.rgb; b.count = a.count; b.exposure = &exposure->exposure;
-            b.threshold = grade->bloom.threshold; b.weight = grade->bloom.weight;
-            b.pyramid = pyramid; b.out_rgb = bloomed;
-            PT_HIP_TRY(pt::launch_bloom(b, stream));
-            a.rgb = bloomed; a.divide = 0;
-        }
-        if (grade->local.on) {   // ... and then m * g of that plane, or of the chain's image
-            pt::LocalArgs l;
-            l.width = grade->width; l.height = grade->height; l.levels = grade->local.levels; l.divide = a.divide;
-            l.rgb = a.rgb; l.count = a.count; l.exposure = &exposure->exposure;
-            l.strength = grade->local.strength; l.pivot = grade->local.pivot; l.sigma = grade->local.sigma;
-            l.base[0] = local_base[0]; l.base[1] = local_base[1]; l.out_rgb = localised;
-            PT_HIP_TRY(pt::launch_local(l, stream));
-            a.rgb = localised; a.divide = 0;
-        }
-        if (grade->colour.on) {   // (use_lut has brought the LUT of this request to the device)
+        if (!grade) PT_HIP_TRY(pt::launch_display(a, stream));
+        else if (!grade->colour.on) PT_HIP_TRY(pt::launch_display_graded(a, grade->setup.curve, &exposure->exposure, stream));
+        else {   // (use_lut has brought the LUT of this request to the device)
             pt::ColourStep step = grade->colour.step;
             step.lut = step.lut_n ? d_lut.at<pt::LutVertex>(0) : nullptr;
             PT_HIP_TRY(pt::launch_display_colour(a, grade->setup.curve, &exposure->exposure, step, stream));
-            return PT_OK;
         }
-        PT_HIP_TRY(pt::launch_display_graded(a, grade->setup.curve, &exposure->exposure, stream));
         return PT_OK;
     }
     // The kernel has finished: 3 bytes per pixel and the deferred list come to the host, which finishes the list's pixels.
@@ -289,9 +240,7 @@ struct DisplayDevice {
             PT_HIP_TRY(hipMemcpy(list.data(), deferred, sizeof(pt::DisplayDeferred) * len, hipMemcpyDeviceToHost));
             for (const pt::DisplayDeferred &d : list)
                 if (d.pixel < 0 || static_cast<size_t>(d.pixel) >= n) return fail(PT_ERR_HIP, "display: a deferred pixel lies outside the image");
-            if (grade && grade->colour.on) finish_on_host_colour(list, gamma, grade->setup.curve, got.used.exposure, grade->colour.step, out);
-            else if (grade) finish_on_host_graded(list, gamma, grade->setup.curve, got.used.exposure, out);
-            else finish_on_host(list, gamma, out);
+            finish_on_host(list, gamma, grade, got.used.exposure, out);
         }
         got.n_deferred = static_cast<int32_t>(len);
         return PT_OK;
@@ -397,14 +346,14 @@ int null_argument() { return fail(PT_ERR_INVALID_ARGUMENT, "null handle, params 
 
 // What one present is asked for.  A NULL stage is off: the entry point that requires one has refused its absence already.
 struct PresentRequest {
-    const pt_display_params *display;
-    const pt_upsample_params *upsample;   // the same chain at the display's size, then the upsample to scale times it
-    const pt_grade_params *grade;         // the exposure and the graded kernel in place of the display kernel
-    const pt_bloom_params *bloom;         // with grade only
-    const pt_local_params *local;         // with grade only
-    pt_grade_info *grade_info;            // with grade only; may be NULL
-    const pt_colour_params *colour;       // with grade only
-    const pt_optics_params *optics;       // with grade only
+    const pt_display_params *display = nullptr;
+    const pt_upsample_params *upsample = nullptr;   // the same chain at the display's size, then the upsample to scale times it
+    const pt_grade_params *grade = nullptr;         // the exposure and the graded kernel in place of the display kernel
+    pt_grade_info *grade_info = nullptr;            // with grade only; may be NULL
+    const pt_bloom_params *bloom = nullptr;         // with grade only, and so are the stages below
+    const pt_local_params *local = nullptr;
+    const pt_colour_params *colour = nullptr;
+    const pt_optics_params *optics = nullptr;
 };
 
 int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, pt_display_info *info) {
@@ -447,8 +396,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     DisplayDevice &dev = scaled ? d->dev_up : d->dev;
     if (scaled && (rc = ensure_scaled(d, ua.scale)) != PT_OK) return rc;
     if ((rc = dev.use_table(table, "pt_display_present")) != PT_OK) return rc;
-    grade.width = scaled ? ua.width : d->width; grade.height = scaled ? ua.height : d->height;
-    if (grade.bloom.on && (rc = dev.ensure_bloom(grade.width, grade.height, "pt_display_present_bloom")) != PT_OK) return rc;
+    if (grade.bloom.on && (rc = dev.ensure_bloom(scaled ? ua.width : d->width, scaled ? ua.height : d->height, "pt_display_present_bloom")) != PT_OK) return rc;
     if (grade.local.on && (rc = dev.ensure_local("pt_display_present_local")) != PT_OK) return rc;
     if (grade.colour.lut && (rc = dev.use_lut(grade.colour.lut, "pt_display_present_colour")) != PT_OK) return rc;
     if (grade.optics.on && (rc = dev.ensure_optics("pt_display_present_optics")) != PT_OK) return rc;
@@ -458,18 +406,19 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
         std::unique_lock<std::mutex> ctx_lock;
         if (d->session) ctx_lock = std::unique_lock<std::mutex>(d->session->ctx.mutex);
         PT_HIP_TRY(d->timer.begin(stream));
-        Image image = {planes.sum, planes.count, true};
+        ptc::Image image = {planes.sum, planes.count, true, d->width, d->height};
         if (temporal) {
             ptc::TemporalPlanes merged;
             if ((rc = ptc::temporal_enqueue(d->history, planes, &p->temporal_params, filter ? &p->denoise : nullptr, stream, &merged)) != PT_OK) return rc;
-            image = filter ? Image{merged.mean, merged.mean_count, false} : Image{merged.merged.sum, merged.merged.count, true};
+            if (filter) image.rgb = merged.mean, image.count = merged.mean_count, image.divide = false;
+            else image.rgb = merged.merged.sum, image.count = merged.merged.count;
         } else if (filter) {
             std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);
             if ((rc = enqueue_view_first_hits(scene, d->eps, d->width, d->height, d->features, stream)) != PT_OK) return rc;
             da.width = d->width; da.height = d->height;
             ptc::bind_planes(da, planes, d->features, d->denoise);
             PT_HIP_TRY(pt::launch_denoise(da, stream));
-            image = {d->denoise.out.rgb, d->denoise.out.count, false};
+            image.rgb = d->denoise.out.rgb; image.count = d->denoise.out.count; image.divide = false;
         }
         if (scaled) {
             // the low mean (levels = 0: sum / n of the accumulators as they are, or merged), the output image's features from the
@@ -484,7 +433,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
             }
             ptc::bind_planes(ua, image.rgb, image.count, d->up_features, d->up_work, d->up_out);
             PT_HIP_TRY(pt::launch_upsample(ua, stream));
-            image = {d->up_out.rgb, d->up_out.count, false};
+            image = {d->up_out.rgb, d->up_out.count, false, ua.width, ua.height};
         }
         if ((rc = dev.enqueue(image, stream, graded ? &grade : nullptr)) != PT_OK) return rc;
         PT_HIP_TRY(d->timer.end(stream));
@@ -502,6 +451,11 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (graded && rq.grade_info) *rq.grade_info = got.used;
     dev.fill(info, ms, got);
     return PT_OK;
+}
+
+// An entry point's present: `complete` is its own condition, that no stage its signature requires is NULL.
+int present(pt_display *d, bool complete, const PresentRequest &rq, uint8_t *bgr, pt_display_info *info) {
+    return guarded([&] { return complete ? display_present_impl(d, rq, bgr, info) : null_argument(); });
 }
 
 // A mean image in host memory, and how it is to be graded (pt_display_bytes_graded_host).
@@ -525,18 +479,15 @@ int display_bytes_host_impl(const HostImage &image, float gamma, const HostGrade
     ptc::PlaneLayout l;
     ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
     ptc::DeviceBuffer d_in;
-    ptc::DeviceTimer timer;
     if ((rc = d_in.alloc(l, "pt_display_bytes_host")) != PT_OK || (rc = dev.alloc(n, "pt_display_bytes_host")) != PT_OK ||
-        (rc = dev.use_table(table, "pt_display_bytes_host")) != PT_OK || (rc = timer.create("pt_display_bytes_host")) != PT_OK)
+        (rc = dev.use_table(table, "pt_display_bytes_host")) != PT_OK)
         return rc;
     if (grade.colour.lut && (rc = dev.use_lut(grade.colour.lut, "pt_display_bytes_colour_host")) != PT_OK) return rc;
     in.bind(d_in);
     if ((rc = in.upload(image.mean_rgb, image.count)) != PT_OK) return rc;
-    PT_HIP_TRY(timer.begin(nullptr));
-    if ((rc = dev.enqueue({in.rgb, in.count, false}, nullptr, g ? &grade : nullptr)) != PT_OK) return rc;
-    PT_HIP_TRY(timer.end(nullptr));
     float ms = 0.0f;
-    PT_HIP_TRY(timer.wait_ms(&ms));
+    rc = ptc::timed(nullptr, "pt_display_bytes_host", &ms, [&] { return dev.enqueue({in.rgb, in.count, false, image.width, image.height}, nullptr, g ? &grade : nullptr); });
+    if (rc != PT_OK) return rc;
     Presented got;
     if ((rc = dev.collect(gamma, bgr, g ? &grade : nullptr, got)) != PT_OK) return rc;
     if (g && g->info) *g->info = got.used;
@@ -598,38 +549,52 @@ int pt_display_create_frame(pt_frame *frame, float eps, pt_display **out) {
 }
 
 int pt_display_present(pt_display *d, const pt_display_params *p, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return display_present_impl(d, {p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info); });
+    PresentRequest rq;
+    rq.display = p;
+    return present(d, true, rq, bgr, info);
 }
 
 int pt_display_present_scaled(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, uint8_t *bgr, pt_display_info *info) {
-    return guarded([&] { return u ? display_present_impl(d, {p, u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, bgr, info) : null_argument(); });
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u;
+    return present(d, u != nullptr, rq, bgr, info);
 }
 
 int pt_display_present_graded(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g, uint8_t *bgr,
                               pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g ? display_present_impl(d, {p, u, g, nullptr, nullptr, grade_info, nullptr, nullptr}, bgr, info) : null_argument(); });
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info;
+    return present(d, g != nullptr, rq, bgr, info);
 }
 
 int pt_display_present_bloom(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                              const pt_bloom_params *b, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g && b ? display_present_impl(d, {p, u, g, b, nullptr, grade_info, nullptr, nullptr}, bgr, info) : null_argument(); });
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info; rq.bloom = b;
+    return present(d, g && b, rq, bgr, info);
 }
 
 int pt_display_present_local(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                              const pt_bloom_params *b, const pt_local_params *l, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g && b && l ? display_present_impl(d, {p, u, g, b, l, grade_info, nullptr, nullptr}, bgr, info) : null_argument(); });
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info; rq.bloom = b; rq.local = l;
+    return present(d, g && b && l, rq, bgr, info);
 }
 
 int pt_display_present_colour(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                               const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c, uint8_t *bgr, pt_display_info *info,
                               pt_grade_info *grade_info) {
-    return guarded([&] { return g && b && l && c ? display_present_impl(d, {p, u, g, b, l, grade_info, c, nullptr}, bgr, info) : null_argument(); });
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info; rq.bloom = b; rq.local = l; rq.colour = c;
+    return present(d, g && b && l && c, rq, bgr, info);
 }
 
 int pt_display_present_optics(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
                               const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c, const pt_optics_params *o,
                               uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
-    return guarded([&] { return g && b && l && c && o ? display_present_impl(d, {p, u, g, b, l, grade_info, c, o}, bgr, info) : null_argument(); });
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info; rq.bloom = b; rq.local = l; rq.colour = c; rq.optics = o;
+    return present(d, g && b && l && c && o, rq, bgr, info);
 }
 
 int pt_display_reset(pt_display *d) {

@@ -5,8 +5,6 @@
 
 #include <cmath>
 
-#include "pt_meter.hpp"
-
 using ptc::fail;
 using ptc::guarded;
 using ptc::hip_fail;
@@ -71,19 +69,13 @@ int meter_host_impl(int device, int32_t width, int32_t height, const float *mean
     ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
     const size_t o_hist = l.add(4 * pt::kMeterEntries);
     ptc::DeviceBuffer d;
-    ptc::DeviceTimer timer;
-    if ((rc = d.alloc(l, "pt_meter_host")) != PT_OK || (rc = timer.create("pt_meter_host")) != PT_OK) return rc;
+    if ((rc = d.alloc(l, "pt_meter_host")) != PT_OK) return rc;
     in.bind(d);
     if ((rc = in.upload(mean_rgb, count)) != PT_OK) return rc;
     PT_HIP_TRY(hipMemset(d.at<void>(o_hist), 0, 4 * pt::kMeterEntries));
-    pt::MeterArgs a;
-    a.n = static_cast<int>(n); a.divide = 0;
-    a.rgb = in.rgb; a.count = in.count; a.hist = d.at<uint32_t>(o_hist);
-    PT_HIP_TRY(timer.begin(nullptr));
-    PT_HIP_TRY(pt::launch_meter(a, nullptr));
-    PT_HIP_TRY(timer.end(nullptr));
+    const auto a = ptc::meter_args({in.rgb, in.count, false, width, height}, d.at<uint32_t>(o_hist));
     float ms = 0.0f;
-    PT_HIP_TRY(timer.wait_ms(&ms));
+    if ((rc = ptc::timed(nullptr, "pt_meter_host", &ms, [&]() -> int { PT_HIP_TRY(pt::launch_meter(a, nullptr)); return PT_OK; })) != PT_OK) return rc;
     PT_HIP_TRY(hipMemcpy(hist, a.hist, 4 * pt::kMeterEntries, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;

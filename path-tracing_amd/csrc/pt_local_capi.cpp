@@ -6,8 +6,6 @@
 #include <cmath>
 #include <cstring>
 
-#include "pt_local.hpp"
-
 using ptc::fail;
 using ptc::guarded;
 using ptc::hip_fail;
@@ -49,23 +47,16 @@ int local_host_impl(int device, int32_t width, int32_t height, const float *mean
     }
     ptc::PlaneLayout l;
     ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
-    const size_t o_e = l.add(4), o_out = l.add(12 * n), o_b0 = l.add(4 * n), o_b1 = l.add(4 * n);
+    const size_t o_e = l.add(4);
+    ptc::LocalPlanes work = ptc::LocalPlanes::in(l, n);
     ptc::DeviceBuffer d;
-    ptc::DeviceTimer timer;
-    if ((rc = d.alloc(l, "pt_local_host")) != PT_OK || (rc = timer.create("pt_local_host")) != PT_OK) return rc;
-    in.bind(d);
+    if ((rc = d.alloc(l, "pt_local_host")) != PT_OK) return rc;
+    in.bind(d); work.bind(d);
     if ((rc = in.upload(mean_rgb, count)) != PT_OK) return rc;
     PT_HIP_TRY(hipMemcpy(d.at<void>(o_e), &exposure, 4, hipMemcpyHostToDevice));
-    pt::LocalArgs a;
-    a.width = width; a.height = height; a.levels = setup.levels; a.divide = 0;
-    a.rgb = in.rgb; a.count = in.count; a.exposure = d.at<float>(o_e);
-    a.strength = setup.strength; a.pivot = setup.pivot; a.sigma = setup.sigma;
-    a.base[0] = d.at<float>(o_b0); a.base[1] = d.at<float>(o_b1); a.out_rgb = d.at<float>(o_out);
-    PT_HIP_TRY(timer.begin(nullptr));
-    PT_HIP_TRY(pt::launch_local(a, nullptr));
-    PT_HIP_TRY(timer.end(nullptr));
+    const auto a = ptc::local_args(setup, {in.rgb, in.count, false, width, height}, d.at<float>(o_e), work);
     float ms = 0.0f;
-    PT_HIP_TRY(timer.wait_ms(&ms));
+    if ((rc = ptc::timed(nullptr, "pt_local_host", &ms, [&]() -> int { PT_HIP_TRY(pt::launch_local(a, nullptr)); return PT_OK; })) != PT_OK) return rc;
     PT_HIP_TRY(hipMemcpy(out_rgb, a.out_rgb, 12 * n, hipMemcpyDeviceToHost));
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;

@@ -6,8 +6,6 @@
 #include <cmath>
 #include <cstring>
 
-#include "pt_optics.hpp"
-
 using ptc::fail;
 using ptc::guarded;
 using ptc::hip_fail;
@@ -55,21 +53,12 @@ int optics_host_impl(int device, int32_t width, int32_t height, const float *mea
     ptc::PlaneLayout l;
     ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n), out = ptc::MeanPlanes::in(l, n);
     ptc::DeviceBuffer d;
-    ptc::DeviceTimer timer;
-    if ((rc = d.alloc(l, "pt_optics_host")) != PT_OK || (rc = timer.create("pt_optics_host")) != PT_OK) return rc;
+    if ((rc = d.alloc(l, "pt_optics_host")) != PT_OK) return rc;
     in.bind(d); out.bind(d);
     if ((rc = in.upload(mean_rgb, count)) != PT_OK) return rc;
-    pt::OpticsArgs a;
-    a.width = width; a.height = height; a.divide = 0;
-    a.rgb = in.rgb; a.count = in.count;
-    a.k1 = setup.k1; a.k2 = setup.k2; a.vignette = setup.vignette;
-    for (int k = 0; k < 3; ++k) a.mag[k] = setup.mag[k];
-    a.out_rgb = out.rgb; a.out_count = out.count;
-    PT_HIP_TRY(timer.begin(nullptr));
-    PT_HIP_TRY(pt::launch_optics(a, nullptr));
-    PT_HIP_TRY(timer.end(nullptr));
+    const auto a = ptc::optics_args(setup, {in.rgb, in.count, false, width, height}, out);
     float ms = 0.0f;
-    PT_HIP_TRY(timer.wait_ms(&ms));
+    if ((rc = ptc::timed(nullptr, "pt_optics_host", &ms, [&]() -> int { PT_HIP_TRY(pt::launch_optics(a, nullptr)); return PT_OK; })) != PT_OK) return rc;
     if ((rc = out.download(out_rgb, out_count)) != PT_OK) return rc;
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;

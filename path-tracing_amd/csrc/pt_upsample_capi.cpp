@@ -51,13 +51,8 @@ static int upsample_host_impl(int device, int32_t width, int32_t height, const f
     lo.bind(d); f.bind(d); out.bind(d); work.bind(d);
     ptc::bind_planes(a, lo.rgb, lo.count, f, work, out);
     if ((rc = lo.upload(mean_lo, count_lo)) != PT_OK || (rc = f.upload(position, normal, albedo, hit_index)) != PT_OK) return rc;
-    ptc::DeviceTimer timer;
-    if ((rc = timer.create("pt_upsample_host")) != PT_OK) return rc;
-    PT_HIP_TRY(timer.begin(nullptr));
-    PT_HIP_TRY(pt::launch_upsample(a, nullptr));
-    PT_HIP_TRY(timer.end(nullptr));
     float ms = 0.0f;
-    PT_HIP_TRY(timer.wait_ms(&ms));
+    if ((rc = ptc::timed(nullptr, "pt_upsample_host", &ms, [&]() -> int { PT_HIP_TRY(pt::launch_upsample(a, nullptr)); return PT_OK; })) != PT_OK) return rc;
     if ((rc = out.download(mean_rgb, count_out)) != PT_OK) return rc;
     if (kernel_ms) *kernel_ms = ms;
     return PT_OK;

@@ -1,8 +1,9 @@
 // pt_device_mem.hpp on the CPU, under AddressSanitizer + UBSan: the plane layout is a pure function of sizes and gives the
 // allocation sizes the host layer had when they were written out by hand; the owners free exactly once, an empty owner makes
-// no HIP call, a failed allocation leaves nothing behind; the views of the plane sets lay out what the entry points had, and the
-// timer owns its two events.  Built and run by tests/test_device_mem_host.py; the HIP calls the header makes are stubbed here
-// and count themselves.
+// no HIP call, a failed allocation leaves nothing behind; the views of the plane sets lay out what the entry points had, the
+// timer owns its two events, and the timed region of pt_capi_internal.hpp records one event on each side of what it is given.
+// Built and run by tests/test_device_mem_host.py; the HIP calls the headers make are stubbed here and count themselves.
+#include "pt_capi_internal.hpp"
 #include "pt_device_mem.hpp"
 
 #include <algorithm>
@@ -15,38 +16,50 @@ static int g_mallocs = 0, g_frees = 0, g_event_destroys = 0, g_stream_destroys =
 static bool g_fail_malloc = false;
 static std::set<void *> g_blocks;   // what the stubbed hipMalloc handed out and hipFree has not seen yet
 static char g_arena[8192];          // tagged pointers: block k is &g_arena[k] (never dereferenced); room for the views of one pixel
-static int g_records = 0, g_syncs = 0, g_copies = 0;
+static int g_records = 0, g_syncs = 0, g_copies = 0, g_events = 0, g_calls = 0;   // g_calls: every stubbed call
+struct Recorded { hipEvent_t event; hipStream_t stream; };
+static std::vector<Recorded> g_recorded;        // hipEventRecord, in order
+static hipEvent_t g_synced = nullptr, g_elapsed[2] = {nullptr, nullptr};
 
 extern "C" {
 hipError_t hipMalloc(void **p, size_t) {
+    ++g_calls;
     if (g_fail_malloc) return hipErrorOutOfMemory;
     *p = &g_arena[++g_mallocs];
     g_blocks.insert(*p);
     return hipSuccess;
 }
 hipError_t hipFree(void *p) {
+    ++g_calls;
     ++g_frees;
     if (!g_blocks.erase(p)) ++g_double_frees;
     return hipSuccess;
 }
-hipError_t hipMemcpy(void *, const void *, size_t, hipMemcpyKind) { return ++g_copies, hipSuccess; }
+hipError_t hipMemcpy(void *, const void *, size_t, hipMemcpyKind) { return ++g_calls, ++g_copies, hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
-    *e = reinterpret_cast<hipEvent_t>(&g_arena[1]);
-    return hipSuccess;
+    *e = reinterpret_cast<hipEvent_t>(&g_arena[1 + ++g_events % 4096]);   // (no two live events of a test share a tag)
+    return ++g_calls, hipSuccess;
 }
-hipError_t hipEventDestroy(hipEvent_t) { return ++g_event_destroys, hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return ++g_records, hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return ++g_syncs, hipSuccess; }
-hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { return *ms = 2.5f, hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t) { return ++g_calls, ++g_event_destroys, hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    g_recorded.push_back({e, s});
+    return ++g_calls, ++g_records, hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e) { return g_synced = e, ++g_calls, ++g_syncs, hipSuccess; }
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) {
+    g_elapsed[0] = a; g_elapsed[1] = b;
+    return ++g_calls, *ms = 2.5f, hipSuccess;
+}
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) {
     *s = reinterpret_cast<hipStream_t>(&g_arena[2]);
-    return hipSuccess;
+    return ++g_calls, hipSuccess;
 }
-hipError_t hipStreamDestroy(hipStream_t) { return ++g_stream_destroys, hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t) { return ++g_calls, ++g_stream_destroys, hipSuccess; }
 }
 
 namespace ptc {
 std::atomic<long> g_live_device_objects{0};
+int fail(int code, const std::string &) { return code; }
 int hip_fail(hipError_t e, const char *) {   // pt_capi.cpp's mapping
     return e == hipErrorNoDevice || e == hipErrorInvalidDevice || e == hipErrorInsufficientDriver ? PT_ERR_NO_DEVICE
            : e == hipErrorOutOfMemory                                                            ? PT_ERR_OUT_OF_MEMORY
@@ -63,12 +76,14 @@ int hip_fail(hipError_t e, const char *) {   // pt_capi.cpp's mapping
     } while (0)
 
 using ptc::AccumPlanes;
+using ptc::BloomPlanes;
 using ptc::DenoisePlanes;
 using ptc::DeviceBuffer;
 using ptc::DeviceEvent;
 using ptc::DeviceStream;
 using ptc::DeviceTimer;
 using ptc::FeaturePlanes;
+using ptc::LocalPlanes;
 using ptc::MeanPlanes;
 using ptc::PlaneLayout;
 using ptc::UpsamplePlanes;
@@ -215,6 +230,106 @@ static int test_views() {
     return 0;
 }
 
+// Bloom's and local exposure's views against what ensure_bloom / bloom_host_impl and ensure_local / local_host_impl laid out by
+// hand before the views existed: `12 n | 16 records` and `12 n | 4 n | 4 n`, for the one-shot entry points behind the uploaded
+// mean image `12 n | 4 n` and the exposure scalar `4`.  Every expected number is written out here (each a multiple of 256 at or
+// behind the end of the plane before it); the record counts are what pt::bloom_pyramid_records gave for the image and the levels.
+static int test_stage_views() {
+    struct BloomCase { size_t n, records, display_pyramid, display_total, host_count, host_e, host_out, host_pyramid, host_total; };
+    const BloomCase bloom[] = {
+        {1, 1, 256, 512, 256, 512, 768, 1024, 1280},                          // 1 x 1, one level
+        {1, 8, 256, 512, 256, 512, 768, 1024, 1280},                          // 1 x 1, eight levels
+        {35, 12, 512, 768, 512, 768, 1024, 1536, 1792},                       // 7 x 5, one level: 4 x 3
+        {35, 22, 512, 1024, 512, 768, 1024, 1536, 2048},                      // 7 x 5, eight levels: 12 + 4 + 6 x 1
+        {2150, 751, 25856, 37888, 25856, 34560, 34816, 60672, 72704},         // 50 x 43, five levels: 550 + 143 + 42 + 12 + 4
+        {2150, 754, 25856, 38144, 25856, 34560, 34816, 60672, 72960},         // 50 x 43, eight levels: ... + 3 x 1
+    };
+    const int calls = g_calls;
+    for (const BloomCase &c : bloom) {
+        {   // DisplayDevice::ensure_bloom
+            PlaneLayout l;
+            const BloomPlanes w = BloomPlanes::in(l, c.n, c.records);
+            EXPECT(w.n == c.n && w.offset[0] == 0 && w.offset[1] == c.display_pyramid && l.total() == c.display_total);
+            EXPECT(l.end == c.display_pyramid + 16 * c.records && !w.out_rgb && !w.pyramid);
+        }
+        {   // pt_bloom_host
+            PlaneLayout l;
+            const MeanPlanes in = MeanPlanes::in(l, c.n);
+            const size_t o_e = l.add(4);
+            const BloomPlanes w = BloomPlanes::in(l, c.n, c.records);
+            EXPECT(in.offset[0] == 0 && in.offset[1] == c.host_count && o_e == c.host_e);
+            EXPECT(w.offset[0] == c.host_out && w.offset[1] == c.host_pyramid && l.total() == c.host_total);
+        }
+    }
+    struct LocalCase { size_t n, display[3], display_total, host_count, host_e, host[3], host_total; };
+    const LocalCase local[] = {
+        {1, {0, 256, 512}, 768, 256, 512, {768, 1024, 1280}, 1536},
+        {35, {0, 512, 768}, 1024, 512, 768, {1024, 1536, 1792}, 2048},
+        {2150, {0, 25856, 34560}, 43264, 25856, 34560, {34816, 60672, 69376}, 78080},
+    };
+    for (const LocalCase &c : local) {
+        {   // DisplayDevice::ensure_local
+            PlaneLayout l;
+            const LocalPlanes w = LocalPlanes::in(l, c.n);
+            EXPECT(w.n == c.n && w.offset[0] == c.display[0] && w.offset[1] == c.display[1] && w.offset[2] == c.display[2]);
+            EXPECT(l.total() == c.display_total && l.end == c.display[2] + 4 * c.n && !w.out_rgb && !w.base[0] && !w.base[1]);
+        }
+        {   // pt_local_host
+            PlaneLayout l;
+            const MeanPlanes in = MeanPlanes::in(l, c.n);
+            const size_t o_e = l.add(4);
+            const LocalPlanes w = LocalPlanes::in(l, c.n);
+            EXPECT(in.offset[0] == 0 && in.offset[1] == c.host_count && o_e == c.host_e);
+            EXPECT(w.offset[0] == c.host[0] && w.offset[1] == c.host[1] && w.offset[2] == c.host[2] && l.total() == c.host_total);
+        }
+    }
+    EXPECT(g_calls == calls);   // in() is arithmetic
+    {   // bind makes pointers of the offsets, and makes no HIP call either
+        PlaneLayout l;
+        MeanPlanes in = MeanPlanes::in(l, 1);
+        l.add(4);
+        BloomPlanes b = BloomPlanes::in(l, 1, 8);
+        LocalPlanes w = LocalPlanes::in(l, 1);
+        DeviceBuffer d;
+        EXPECT(l.total() == 1280 + 768 && l.total() <= sizeof g_arena - 64 && d.alloc(l, "stage views") == PT_OK);
+        const int bound = g_calls;
+        in.bind(d); b.bind(d); w.bind(d);
+        char *const base = d.get<char>();
+        EXPECT(g_calls == bound && (char *)b.out_rgb == base + 768 && (char *)b.pyramid == base + 1024);
+        EXPECT((char *)w.out_rgb == base + 1280 && (char *)w.base[0] == base + 1536 && (char *)w.base[1] == base + 1792);
+    }
+    EXPECT(live() == 0);
+    return 0;
+}
+
+// ptc::timed: begin, the callable, end on the stream given; one wait; the two events are the call's own on both ways out.
+static int test_timed() {
+    const hipStream_t stream = reinterpret_cast<hipStream_t>(&g_arena[3]);
+    const long before = live();
+    const int destroyed = g_event_destroys;
+    g_recorded.clear();
+    g_records = g_syncs = 0;
+    float ms = 0.0f;
+    int ran = 0;
+    bool inside_ok = false;
+    int rc = ptc::timed(stream, "timed", &ms, [&]() -> int {
+        ++ran;
+        inside_ok = g_records == 1 && g_syncs == 0 && live() == before + 2;   // begin is behind us, end and the wait are not
+        return PT_OK;
+    });
+    EXPECT(rc == PT_OK && ran == 1 && inside_ok && ms == 2.5f);
+    EXPECT(g_records == 2 && g_recorded.size() == 2 && g_recorded[0].stream == stream && g_recorded[1].stream == stream);
+    EXPECT(g_recorded[0].event != g_recorded[1].event && g_syncs == 1 && g_synced == g_recorded[1].event);
+    EXPECT(g_elapsed[0] == g_recorded[0].event && g_elapsed[1] == g_recorded[1].event);
+    EXPECT(live() == before && g_event_destroys == destroyed + 2);
+    // the callable fails: its status comes back, nothing more is recorded, nothing is waited for
+    ms = -1.0f;
+    rc = ptc::timed(stream, "timed", &ms, [&]() -> int { return ++ran, static_cast<int>(PT_ERR_UNSUPPORTED); });
+    EXPECT(rc == PT_ERR_UNSUPPORTED && ran == 2 && ms == -1.0f && g_records == 3 && g_recorded[2].stream == stream && g_syncs == 1);
+    EXPECT(live() == before && g_event_destroys == destroyed + 4);
+    return 0;
+}
+
 static int test_timer() {
     const int destroyed = g_event_destroys;
     {
@@ -323,7 +438,7 @@ static int test_owners() {
 }
 
 int main() {
-    if (test_layout() || test_owners() || test_views() || test_timer()) return 1;
+    if (test_layout() || test_owners() || test_views() || test_stage_views() || test_timer() || test_timed()) return 1;
     std::printf("device mem ok\n");
     return 0;
 }

@@ -1,7 +1,9 @@
 """pt_device_mem.hpp -- the owners of device memory, events and streams and the plane layout of the host layer -- on the CPU:
 built with g++ -fsanitize=address,undefined against the HIP headers, the HIP calls stubbed (tests/native/device_mem_main.cpp).
 Pins the allocation sizes the layout gives to the expressions the host layer used to write out by hand, and that an owner frees
-exactly once, never when it is empty, and holds nothing after a failed allocation."""
+exactly once, never when it is empty, and holds nothing after a failed allocation.  The same program pins bloom's and local
+exposure's views to the offsets their two users each wrote out by hand, and the timed region of pt_capi_internal.hpp to two
+event records around its callable on the stream given, one wait, and events that go with the call whether the callable fails or not."""
 import os
 import shutil
 import subprocess

@@ -109,6 +109,31 @@ def test_one_shot_entry_points_cycle(hooks, models_dir):
         for levels in (0, 1, 3):
             rc, mean, cout = _denoise(hooks, W, H, s, s2, c, f, levels)
             assert rc == pt.PT_OK and np.isfinite(mean).all() and (levels > 0 or np.array_equal(cout, c))
+    # the image-space stages alone on a 9 x 7 mean image (one pixel without samples), each with the stage on and -- where its
+    # parameters can say so -- off: PT_OK (anything else raises), finite output, and a kernel time only where kernels ran
+    mean = (rng.random((7, 9, 3), dtype=np.float32) * np.float32(4)).astype(np.float32)
+    cnt = np.ones((7, 9), np.int32)
+    cnt[3, 4] = 0
+    stages = {"bloom": lambda on: pt.bloom(0, mean, cnt, strength=0.5 if on else 0.0, want_ms=True, library=hooks),
+              "local": lambda on: pt.local_exposure(0, mean, cnt, strength=1.0 if on else 0.0, want_ms=True, library=hooks),
+              "optics": lambda on: pt.optics(0, mean, cnt, k1=-0.1 if on else 0.0, ca=0.01 if on else 0.0, want_ms=True, library=hooks)}
+    for name, run in stages.items():
+        for on in (True, False):
+            with balanced(hooks):
+                *out, ms = run(on)
+            assert all(np.isfinite(o).all() for o in out) and out[0].shape == mean.shape, (name, on)
+            assert (ms > 0) if on else (ms == 0 and np.array_equal(_bits(out[0]), _bits(mean))), (name, on, ms)
+    with balanced(hooks):                                           # (the meter and the upsampler have no "off")
+        hist, ms = pt.meter(mean, cnt, want_ms=True, library=hooks)
+    assert ms > 0 and int(hist.sum()) == 9 * 7 - 1
+    lo, clo = np.ascontiguousarray(mean[:4, :6].reshape(-1, 3)), np.ascontiguousarray(cnt[:4, :6].reshape(-1))
+    with balanced(hooks):
+        f = g.render_features(12, 8)
+        prm = pt.UpsampleParams(2, 0.0, 0, 0)
+        up, cup, ms = np.zeros((12 * 8, 3), np.float32), np.zeros(12 * 8, np.int32), C.c_float()
+        rc = hooks.pt_upsample_host(0, 12, 8, pt._fp(lo), pt._ip(clo), pt._fp(f["position"]), pt._fp(f["normal"]), pt._fp(f["albedo"]),
+                                    pt._ip(f["hit_index"]), C.byref(prm), pt._fp(up), pt._ip(cup), C.byref(ms))
+    assert rc == pt.PT_OK and np.isfinite(up).all() and ms.value > 0
     g.close()
 
 
@@ -179,13 +204,17 @@ def test_refused_calls_leave_the_count_alone(hooks, models_dir):
 
 def test_display_reaches_every_lazy_plane_set_of_one_handle(hooks, models_dir):
     """One display, every plane set it allocates on demand: the filter planes, the temporal stage with its denoiser planes, the
-    scaled planes at two scales (the second replaces the first), the bloom pyramids of both output sizes.  All of it goes with
-    the handle, and what an earlier present allocated does not reach a later result."""
+    scaled planes at two scales (the second replaces the first), the bloom pyramids of both output sizes, local exposure's planes,
+    the optics stage's mean image, the LUT's device copy (a larger LUT replaces it) -- and all of the stages' sets again for the
+    scaled output.  All of it goes with the handle, and what an earlier present allocated does not reach a later result."""
     W, H = 24, 16
     g = _tor(hooks, models_dir)
     ses = pt.Session(g, W, H)
     ses.render(0, 2, 8)                                             # (the scene's own cull tables exist from here on)
     look = {"grade": {"curve": "aces", "auto_exposure": True}, "bloom": {"strength": 0.5}}
+    stages, lens = {"local": {"strength": 1.0}}, {"k1": -0.1, "ca": 0.01, "vignette": 0.5}
+    grids = [np.stack(np.meshgrid(*[np.linspace(0, 1, n, dtype=np.float32)] * 3, indexing="ij")[::-1], axis=-1) for n in (2, 5)]
+    luts = [pt.Lut.create(np.sqrt(a), library=hooks) for a in grids]           # [blue, green, red] -> (r, g, b), brightened
     with balanced(hooks):
         d = pt.Display(ses)
         created = hooks.pt_test_live_device_objects()
@@ -197,11 +226,25 @@ def test_display_reaches_every_lazy_plane_set_of_one_handle(hooks, models_dir):
         d.present(**look)
         assert d.present(upsample={"scale": 2}, **look)[0].shape == (2 * H, 2 * W, 3)
         assert hooks.pt_test_live_device_objects() > created
+        held = hooks.pt_test_live_device_objects()
+        d.present(**look, **stages)                                 # local exposure's planes
+        d.present(**look, **stages, optics=lens)                    # the optics stage's mean image
+        assert hooks.pt_test_live_device_objects() == held + 2
+        assert d.present(**look, **stages, optics=lens, colour={"saturation": 0.8, "lut": luts[0]})[0].any()
+        assert hooks.pt_test_live_device_objects() == held + 3      # the LUT's device copy; the 5^3 one takes its place
+        everything, _ = d.present(**look, **stages, optics=lens, colour={"saturation": 0.8, "lut": luts[1]})
+        assert hooks.pt_test_live_device_objects() == held + 3
+        assert d.present(upsample={"scale": 2}, **look, **stages, optics=lens, colour={"lut": luts[1]})[0].shape == (2 * H, 2 * W, 3)
+        assert hooks.pt_test_live_device_objects() == held + 6      # the scaled output's local, optics and LUT sets (its bloom's exist)
         fresh = pt.Display(ses)
         want, _ = fresh.present(upsample={"scale": 2})
+        want_everything, _ = fresh.present(**look, **stages, optics=lens, colour={"saturation": 0.8, "lut": luts[1]})
         fresh.close()
         d.reset()
         d.close()
     assert scaled.shape == (2 * H, 2 * W, 3) and scaled.any() and np.array_equal(scaled, want)
+    assert everything.shape == (H, W, 3) and everything.any() and np.array_equal(everything, want_everything)
+    for lut in luts:
+        lut.close()
     ses.close()
     g.close()
