@@ -1052,6 +1052,85 @@ int pt_display_present_optics(pt_display *d, const pt_display_params *p, const p
                               const pt_optics_params *o, uint8_t *bgr, pt_display_info *info /* may be NULL */,
                               pt_grade_info *grade_info /* may be NULL */);
 
+/* ---- sharpening: a contrast-adaptive sharpen of the luminance before the grade ------------------------------------ */
+
+/* The denoiser, the temporal merge, the upsample and the optics resample each buy their speed or their look with softness, and no
+ * stage above gives acuity back.  Sharpening is one stage, mean -> mean (count unchanged), on the linear mean at the OUTPUT size,
+ * AFTER bloom and local exposure and IMMEDIATELY BEFORE the grade or the colour stage: the meter, bloom and local exposure do not
+ * see it; the matrix, the exposure, the curve and the LUT act on what it wrote.  Every pixel is multiplied by ONE gain, computed
+ * from a negative-lobe cross filter of the LUMINANCE whose lobe is as strong as the ring's headroom to black and to white allows.
+ * The filter works in a range-compressed domain y = a / (1 + a) of the exposed luminance a = l e, so that it can act on
+ * scene-linear light: a plain unsharp mask on HDR values rings for many pixels round every emitter, and has no "white" to measure
+ * headroom against.
+ *
+ * The arithmetic, exactly: every line below is ONE correctly rounded float operation in the order written (* / + -, comparisons);
+ * nothing is fused, and there is no pow, log, exp or root -- the stage is rational, for the reason the denoiser's weights are.
+ * min(p, q) is (q < p ? q : p) and max(p, q) is (q > p ? q : p).
+ *
+ * Inputs.  m = the pixel's linear mean (a chain row that ends in sums: m = sum / (float)n, as the display chain divides; behind bloom
+ * or local exposure, their output), its count, the exposure e (manual or from the meter), and the parameters strength and limit.
+ *
+ * Compressed luminance plane, at W x H.  A pixel with count == 0 is INVALID.  Otherwise
+ *   l = ((0.2126 m_r) + (0.7152 m_g)) + (0.0722 m_b)          (the meter's luminance)
+ *   a = l * e
+ *   if !(a >= 0) or !(a <= 65536):  INVALID  (negative, NaN, infinite, or too bright to compress distinctly from 1)
+ *   else  y = a / (1 + a),
+ * so 0 <= y <= Y1, where Y1 = (float)(65536.0 / 65537.0) < 1.  An invalid pixel keeps its value, NaN or infinity included, and is
+ * never a tap.
+ *
+ * Sharpen, for a valid pixel with compressed luminance c.  The ring is b, d, f, h: the pixels above (y - 1), left (x - 1), right
+ * (x + 1) and below (y + 1), in that order; a ring pixel outside the image or invalid takes the value c.
+ *   mn   = min(min(b, d), min(f, h));   mx = max(max(b, d), max(f, h))
+ *   hmin = mx > 0 ? mn / (4 * mx) : 0
+ *   hmax = (1 - mx) / ((4 * mn) - 4)            (<= 0; the denominator is <= -4 (1 - Y1) < 0)
+ *   lobe = max(-hmin, hmax);  lobe = min(lobe, 0);  lobe = max(lobe, -limit);  lobe = lobe * strength
+ *   den  = 1 + (4 * lobe)                        (>= 1 - 4 limit >= 0.25)
+ *   sd   = (((b - c) + (d - c)) + (f - c)) + (h - c)
+ *   y'   = c + ((lobe * sd) / den)
+ *   y'   = !(y' >= 0) ? 0 : (y' > Y1 ? Y1 : y')
+ * In the reals this is (c + lobe (b + d + f + h)) / (1 + 4 lobe).  It is taken about the centre for the reason the denoiser's and
+ * local exposure's sums are: differences of EQUAL values are 0, and rounded products of equal values do not sum to that value.
+ *
+ * Gain and output.
+ *   l0 = c  / (1 - c)
+ *   l1 = y' / (1 - y')
+ *   g  = l0 > 0 ? l1 / l0 : 1
+ *   out_ch = m_ch * g          per channel.
+ * Both luminances go through the same expression, so y' == c gives l1 == l0 bit for bit and g = 1 exactly: a pixel whose ring
+ * equals it (a constant region, a 1 x 1 image, a pixel whose neighbours are all outside or invalid) comes back to the bit.  One
+ * gain serves the three channels, so the ratios out_r : out_g : out_b are those of m.  For a finite mean that is not negative the
+ * output is finite and not negative, and l1 <= Y1 / (1 - Y1).
+ *
+ * Parameters; a zeroed struct means the stage does not run:
+ *   strength    0: the stage is not run (the bytes are those of pt_display_present_optics); else in (0, 1]
+ *                                                                                  (negative, above 1 or non-finite: invalid)
+ *   limit       the largest lobe; 0 = 0.1875; else in (0, 0.1875]                  (negative, above 0.1875 or non-finite: invalid)
+ * Any image size from 1 x 1 is valid. */
+typedef struct pt_sharpen_params {
+    float strength;
+    float limit;
+} pt_sharpen_params;
+
+/* The sharpening kernels alone, on a host image: out_rgb (may be mean_rgb) = the output above for (mean_rgb, count), made on HIP
+ * device `device`; kernel_ms (may be NULL) = HIP-event time of the two kernels.  Buffers, sizes, `exposure` (finite and > 0; 0 is NOT
+ * a default here, as in pt_local_host) and *s are checked BEFORE the device is looked at; PT_ERR_NO_DEVICE afterwards if that is not
+ * a usable device (there is no CPU fallback).  With strength == 0 it copies. */
+int pt_sharpen_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure,
+                    const pt_sharpen_params *s, float *out_rgb, float *kernel_ms);
+/* pt_display_present_optics with sharpening: the same chain with the two sharpening kernels between local exposure's and the
+ * display kernel, on the session's stream with no host synchronisation inside; the gain reads e from the device scalar the display
+ * kernel reads.  The bytes are DEFINED by the host chain and equal it bit for bit: ... -> pt_optics_host -> meter ->
+ * pt_bloom_host(e) -> pt_local_host(e) -> pt_sharpen_host(e) -> pt_colour_host(e, curve) -> pt_tonemap -> pt_quantize, at the
+ * output size.  The metered exposure does not depend on the stage.  *s is checked with *g, before anything is enqueued and before
+ * the device is looked at; a failed present leaves the history and the previous exposure as they were.  A deferred pixel carries the
+ * sharpened mean, which the host finishes.  The display owns one more plane, 4 bytes a pixel at the output size, and a plane of
+ * means where no stage of its own wrote the image the stage reads, allocated by the first present with the stage.  With a zeroed *s
+ * the call is pt_display_present_optics. */
+int pt_display_present_sharpen(pt_display *d, const pt_display_params *p, const pt_upsample_params *u /* NULL: not scaled */,
+                               const pt_grade_params *g, const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c,
+                               const pt_optics_params *o, const pt_sharpen_params *s, uint8_t *bgr, pt_display_info *info /* may be NULL */,
+                               pt_grade_info *grade_info /* may be NULL */);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

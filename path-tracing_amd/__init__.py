@@ -52,7 +52,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_local_host", "pt_display_present_local",
                "pt_lut_create", "pt_lut_load_cube", "pt_lut_size", "pt_lut_destroy", "pt_colour_matrix", "pt_colour_host",
                "pt_display_bytes_colour_host", "pt_display_present_colour",
-               "pt_optics_host", "pt_display_present_optics"]
+               "pt_optics_host", "pt_display_present_optics",
+               "pt_sharpen_host", "pt_display_present_sharpen"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -294,6 +295,24 @@ class OpticsParams(C.Structure):
     _fields_ = [("k1", C.c_float), ("k2", C.c_float), ("ca", C.c_float), ("vignette", C.c_float)]
 
 
+SHARPEN_MAX_LIMIT = 0.1875
+
+
+class SharpenParams(C.Structure):
+    """pt_sharpen_params: a zeroed struct is no sharpening (strength 0); strength in (0, 1], limit 0 = 0.1875, else in (0, 0.1875]."""
+    _fields_ = [("strength", C.c_float), ("limit", C.c_float)]
+
+
+def _sharpen_params(sharpen):
+    """A SharpenParams, or a dict of its fields ({"strength": 0.5, "limit": 0.1}) -> a SharpenParams."""
+    if isinstance(sharpen, dict):
+        unknown = set(sharpen) - {"strength", "limit"}
+        if unknown:
+            raise ValueError(f"sharpen: unknown fields {sorted(unknown)}")
+        return SharpenParams(sharpen.get("strength", 0.0), sharpen.get("limit", 0.0))
+    return sharpen
+
+
 def _optics_params(optics):
     """An OpticsParams, or a dict of its fields ({"k1": -0.1, "ca": 0.01, "vignette": 1.0}) -> an OpticsParams."""
     if isinstance(optics, dict):
@@ -475,6 +494,10 @@ def load_library(path):
     L.pt_optics_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.POINTER(OpticsParams), fp, ip, fp]
     L.pt_display_present_optics.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
                                             C.POINTER(LocalParams), cp, C.POINTER(OpticsParams), bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_sharpen_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(SharpenParams), fp, fp]
+    L.pt_display_present_sharpen.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
+                                             C.POINTER(LocalParams), cp, C.POINTER(OpticsParams), C.POINTER(SharpenParams), bp,
+                                             C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -823,7 +846,8 @@ class Display:
         create = self._L.pt_display_create_frame if isinstance(session_or_frame, Frame) else self._L.pt_display_create
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
-    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None, colour=None, optics=None):
+    def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None, colour=None, optics=None,
+                sharpen=None):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
         parameters.  Returns (bgr uint8 [H, W, 3], info dict).
@@ -839,7 +863,9 @@ class Display:
         matrix on the mean before the exposure and a 3D LUT behind the curve (`grade`, `bloom`, `local` None: zeroed).
         `optics`: None, an OpticsParams, or a dict of its fields ({"k1": -0.1, "ca": 0.01, "vignette": 1.0}) --
         pt_display_present_optics: distortion, chromatic aberration and vignetting of the linear mean ahead of the meter (the other
-        stages None: zeroed)."""
+        stages None: zeroed).
+        `sharpen`: None, a SharpenParams, or a dict of its fields ({"strength": 0.5, "limit": 0.0}) -- pt_display_present_sharpen: a
+        contrast-adaptive sharpen of the luminance after local exposure and before the grade (the other stages None: zeroed)."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -848,13 +874,19 @@ class Display:
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
         info = DisplayInfo()
-        if grade is not None or bloom is not None or local is not None or colour is not None or optics is not None:
+        if grade is not None or bloom is not None or local is not None or colour is not None or optics is not None or sharpen is not None:
             gp, ginfo = _grade_params(grade) if grade is not None else GradeParams(), GradeInfo()
             up = _upsample_params(upsample) if upsample is not None else None
             k = up.scale if up is not None and 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1
             bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8)
             up_arg, out = C.byref(up) if up is not None else None, bgr.ctypes.data_as(C.POINTER(C.c_uint8))
-            if optics is not None:
+            if sharpen is not None:
+                bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local) if local is not None else LocalParams()
+                cp_, op = _colour_params(colour) if colour is not None else ColourParams(), _optics_params(optics) if optics is not None else OpticsParams()
+                sp = _sharpen_params(sharpen)
+                _check(self._L.pt_display_present_sharpen(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), C.byref(lp), C.byref(cp_),
+                                                          C.byref(op), C.byref(sp), out, C.byref(info), C.byref(ginfo)), self._L)
+            elif optics is not None:
                 bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local) if local is not None else LocalParams()
                 cp_, op = _colour_params(colour) if colour is not None else ColourParams(), _optics_params(optics)
                 _check(self._L.pt_display_present_optics(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), C.byref(lp), C.byref(cp_),
@@ -963,6 +995,18 @@ def local_exposure(device, mean_rgb, count, exposure=1.0, strength=1.0, pivot=0.
     out, ms = np.zeros_like(m), C.c_float()
     prm = LocalParams(strength, pivot, levels, sigma)
     _check(L.pt_local_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), C.byref(prm), _fp(out), C.byref(ms)), L)
+    return (out, ms.value) if want_ms else out
+
+
+def sharpen(device, mean_rgb, count, exposure=1.0, strength=1.0, limit=0.0, want_ms=False, library=None):
+    """pt_sharpen_host: the sharpening kernels alone on a host image mean_rgb [H, W, 3] with count [H, W] -- mean * g, the gain g
+    from a contrast-adaptive sharpen of the compressed luminance (include/pt_hip.h states the arithmetic).  Returns the float32
+    image [H, W, 3], with want_ms=True also the HIP-event time of the two kernels."""
+    L = library or lib()
+    m, c = _image_args("sharpen", mean_rgb, count)
+    out, ms = np.empty_like(m), C.c_float(0)
+    prm = SharpenParams(strength, limit)
+    _check(L.pt_sharpen_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), C.byref(prm), _fp(out), C.byref(ms)), L)
     return (out, ms.value) if want_ms else out
 
 

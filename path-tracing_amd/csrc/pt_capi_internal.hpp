@@ -1,6 +1,6 @@
 // What the translation units behind the C ABI share (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters; pt_frame.cpp: the
 // multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
-// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
+// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp, pt_sharpen_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
 // display path, which chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
 // arguments, the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments, and the timed region
 // of a one-shot entry point.
@@ -27,6 +27,7 @@
 #include "pt_meter.hpp"
 #include "pt_optics.hpp"
 #include "pt_scene.hpp"
+#include "pt_sharpen.hpp"
 #include "pt_upsample.hpp"
 
 // The host side of a scene: parsed model, its device-independent tables and the culling hierarchies built so far (one per
@@ -268,6 +269,14 @@ struct OpticsSetup {
 };
 int optics_params_check(const pt_optics_params *o, OpticsSetup &out);
 
+// pt_sharpen_params as every entry point checks them (no device is touched), with the default filled in (pt_sharpen_capi.cpp).
+struct SharpenSetup {
+    bool on = false;          // strength > 0: the stage runs
+    float strength = 0.0f;
+    float limit = pt::kSharpenMaxLimit;
+};
+int sharpen_params_check(const pt_sharpen_params *s, SharpenSetup &out);
+
 // The image a chain has reached: planes on the device, sums still (divide) or means, and its size.
 struct Image { const float *rgb; const int32_t *count; bool divide; int32_t width, height; };
 // One image-space stage's launch arguments -- the only place each of these structs is filled: its checked parameters, the image it
@@ -295,6 +304,13 @@ inline pt::LocalArgs local_args(const LocalSetup &s, const Image &in, const floa
     a.width = in.width; a.height = in.height; a.divide = in.divide ? 1 : 0; a.rgb = in.rgb; a.count = in.count; a.exposure = exposure;
     a.levels = s.levels; a.strength = s.strength; a.pivot = s.pivot; a.sigma = s.sigma;
     a.base[0] = w.base[0]; a.base[1] = w.base[1]; a.out_rgb = w.out_rgb;
+    return a;
+}
+// (out_rgb: the stage's own plane of means, or the plane `in` names, when that is one the caller may write)
+inline pt::SharpenArgs sharpen_args(const SharpenSetup &s, const Image &in, const float *exposure, const SharpenPlanes &w, float *out_rgb) {
+    pt::SharpenArgs a;
+    a.width = in.width; a.height = in.height; a.divide = in.divide ? 1 : 0; a.rgb = in.rgb; a.count = in.count; a.exposure = exposure;
+    a.strength = s.strength; a.limit = s.limit; a.luma = w.luma; a.out_rgb = out_rgb;
     return a;
 }
 

@@ -285,4 +285,24 @@ struct LocalPlanes {
     void bind(const DeviceBuffer &b) { out_rgb = b.at<float>(offset[0]); base[0] = b.at<float>(offset[1]); base[1] = b.at<float>(offset[2]); }
 };
 
+// What sharpening works in: the plane of compressed luminance (a float per pixel) and, where the image it is given is not a plane of
+// its caller's own (own_mean), the plane of sharpened means it writes.
+struct SharpenPlanes {
+    float *luma = nullptr, *out_rgb = nullptr;
+    size_t n = 0;
+    bool own_mean = false;
+    size_t offset[2] = {0, 0};
+    static SharpenPlanes in(PlaneLayout &l, size_t n, bool own_mean) {
+        SharpenPlanes w;
+        w.n = n; w.own_mean = own_mean;
+        w.offset[0] = l.add(4 * n);
+        if (own_mean) w.offset[1] = l.add(12 * n);
+        return w;
+    }
+    void bind(const DeviceBuffer &b) {
+        luma = b.at<float>(offset[0]);
+        if (own_mean) out_rgb = b.at<float>(offset[1]);
+    }
+};
+
 }  // namespace ptc

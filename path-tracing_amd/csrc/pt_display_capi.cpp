@@ -8,6 +8,8 @@
 // display's, uploaded when the generation of the pt_lut given differs from the one held.
 // With lens optics (pt_display_present_optics): its kernel ahead of all of these, from the chain's image into a mean image of the
 // display's, which the meter and every later stage read in the chain's place.
+// With sharpening (pt_display_present_sharpen): its two kernels behind local exposure's, immediately ahead of the graded or the colour
+// kernel, in place on the plane of means a stage of the display's wrote, or from the chain's image into a plane of the display's.
 #include "pt_capi_internal.hpp"
 
 #include <algorithm>
@@ -55,6 +57,9 @@ struct GradeRequest {
     ptc::LocalSetup local;   // on: the local exposure kernels run behind them
     ptc::ColourSetup colour; // on: the colour display kernel takes the graded one's place
     ptc::OpticsSetup optics; // on: the optics kernel runs ahead of the meter, and everything behind it reads what it wrote
+    ptc::SharpenSetup sharpen;   // on: the sharpening kernels run last before the graded or the colour kernel
+    // the image the chain hands to the stages is no plane of the display's: no stage ahead of sharpening writes one it may overwrite
+    bool sharpen_own_mean() const { return !optics.on && !bloom.on && !local.on; }
 };
 
 // What the tone map gets for a pixel the kernel deferred, from the mean its entry carries: the mean itself (no exposure is
@@ -104,12 +109,17 @@ struct DisplayDevice {
     // lens optics: the mean image the stage writes, allocated by the first present with it
     ptc::DeviceBuffer d_optics;
     ptc::MeanPlanes optics_out;
+    // sharpening: the plane of compressed luminance and, for a chain in which no stage before it writes a plane of the display's, the
+    // plane of sharpened means; allocated by the first present with the stage
+    ptc::DeviceBuffer d_sharpen;
+    ptc::SharpenPlanes sharpen;
 
     int alloc(size_t pixels, const char *what) {
         n = pixels;
         d_bloom.reset();   // (of another size's image)
         d_local.reset();
         d_optics.reset();
+        d_sharpen.reset();
         ptc::PlaneLayout l;
         const size_t o_bgr = l.add((n + 3) / 4 * 12), o_list = l.add(16 * n), o_len = l.add(4);
         const size_t o_grade = l.add(kGradeBytes);
@@ -137,6 +147,10 @@ struct DisplayDevice {
     }
     int ensure_local(const char *what) { return ensure(d_local, local, what, n); }
     int ensure_optics(const char *what) { return ensure(d_optics, optics_out, what, n); }
+    int ensure_sharpen(bool own_mean, const char *what) {
+        if (d_sharpen && own_mean && !sharpen.own_mean) d_sharpen.reset();   // (made by a chain that needed the luminance alone)
+        return ensure(d_sharpen, sharpen, what, n, own_mean);
+    }
     // (no kernel of this object is in flight: every call that launches one waits for it)
     int use_lut(const pt_lut *lut, const char *what) {
         if (lut_generation == lut->generation) return PT_OK;
@@ -176,7 +190,8 @@ struct DisplayDevice {
         return PT_OK;
     }
     // Zero the list's length and launch the kernel on `stream`; with `grade`, the stages ahead of the graded or the colour kernel first, each
-    // on the image the one before it left: the lens, the exposure (metered from the image, or the manual one), bloom, local exposure.
+    // on the image the one before it left: the lens, the exposure (metered from the image, or the manual one), bloom, local exposure,
+    // sharpening.
     int enqueue(ptc::Image image, hipStream_t stream, const GradeRequest *grade) {
         PT_HIP_TRY(hipMemsetAsync(n_deferred, 0, 4, stream));
         if (grade && grade->optics.on) {   // the meter and everything behind it read mean' and count'
@@ -203,6 +218,12 @@ struct DisplayDevice {
             const auto l = ptc::local_args(grade->local, image, &exposure->exposure, local);
             PT_HIP_TRY(pt::launch_local(l, stream));
             image.rgb = local.out_rgb; image.divide = false;
+        }
+        if (grade && grade->sharpen.on) {   // ... and then m * g of that: where it lies if a stage above wrote it, else into the stage's own plane
+            float *out = grade->sharpen_own_mean() ? sharpen.out_rgb : const_cast<float *>(image.rgb);
+            const auto s = ptc::sharpen_args(grade->sharpen, image, &exposure->exposure, sharpen, out);
+            PT_HIP_TRY(pt::launch_sharpen(s, stream));
+            image.rgb = out; image.divide = false;
         }
         pt::DisplayArgs a;
         a.n = static_cast<int>(n);
@@ -354,6 +375,7 @@ struct PresentRequest {
     const pt_local_params *local = nullptr;
     const pt_colour_params *colour = nullptr;
     const pt_optics_params *optics = nullptr;
+    const pt_sharpen_params *sharpen = nullptr;
 };
 
 int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, pt_display_info *info) {
@@ -369,6 +391,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (rq.local && (rc = ptc::local_params_check(rq.local, grade.local)) != PT_OK) return rc;
     if (rq.colour && (rc = ptc::colour_params_check(rq.colour, grade.colour)) != PT_OK) return rc;
     if (rq.optics && (rc = ptc::optics_params_check(rq.optics, grade.optics)) != PT_OK) return rc;
+    if (rq.sharpen && (rc = ptc::sharpen_params_check(rq.sharpen, grade.sharpen)) != PT_OK) return rc;
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -400,6 +423,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (grade.local.on && (rc = dev.ensure_local("pt_display_present_local")) != PT_OK) return rc;
     if (grade.colour.lut && (rc = dev.use_lut(grade.colour.lut, "pt_display_present_colour")) != PT_OK) return rc;
     if (grade.optics.on && (rc = dev.ensure_optics("pt_display_present_optics")) != PT_OK) return rc;
+    if (grade.sharpen.on && (rc = dev.ensure_sharpen(grade.sharpen_own_mean(), "pt_display_present_sharpen")) != PT_OK) return rc;
     if (temporal && !d->history && (rc = pt_temporal_create(scene, d->width, d->height, d->eps, &d->history)) != PT_OK) return rc;
     if (filter && !temporal && (rc = ensure_filter(d)) != PT_OK) return rc;
     {   // the chain, behind every slice enqueued so far: no host synchronisation until its last kernel is in the queue
@@ -595,6 +619,15 @@ int pt_display_present_optics(pt_display *d, const pt_display_params *p, const p
     PresentRequest rq;
     rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info; rq.bloom = b; rq.local = l; rq.colour = c; rq.optics = o;
     return present(d, g && b && l && c && o, rq, bgr, info);
+}
+
+int pt_display_present_sharpen(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
+                               const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c, const pt_optics_params *o,
+                               const pt_sharpen_params *s, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info; rq.bloom = b; rq.local = l; rq.colour = c; rq.optics = o;
+    rq.sharpen = s;
+    return present(d, g && b && l && c && o && s, rq, bgr, info);
 }
 
 int pt_display_reset(pt_display *d) {

@@ -98,8 +98,14 @@
 // |a| <= 0.25, 0 <= v <= 64) and its message goes to stderr with exit status 2.  It works on the host path and with -DEVICE_RESOLVE 1,
 // with byte-identical files, and with every flag grading works with (alone it runs with the zeroed grade).  Without these flags
 // nothing changes.
+// Sharpening (pt_sharpen_host, pt_display_present_sharpen, not in the reference): -SHARPEN <strength in 0 .. 1, default 0: off>
+// multiplies every pixel by a gain from a contrast-adaptive sharpen of its compressed luminance against the four pixels round it,
+// whose negative lobe is at most -SHARPEN_LIMIT <in 0 .. 0.1875, default 0: 0.1875>, on the linear mean at the written size, after
+// bloom and local exposure and immediately before the colour stage or the grade (alone it runs with the zeroed grade, as -LOCAL
+// does); the meter does not see it, and previews stay as they are.  It works on the host path and with -DEVICE_RESOLVE 1, with
+// byte-identical files, and with every flag grading works with.  Without -SHARPEN, or with -SHARPEN 0, nothing changes.
 // The image chain is stated once, in HostChain::bytes, in the order the paragraphs above give: temporal merge -> first-hit
-// features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> optics -> meter, bloom, local exposure, colour / grade -> tone map
+// features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> optics -> meter, bloom, local exposure, sharpening, colour / grade -> tone map
 // -> -GAUSS / -MEDIAN -> quantize.  A single frame and every frame of a sequence go through it; with -DEVICE_RESOLVE 1 the
 // bytes come from present() instead.
 #include <algorithm>
@@ -151,6 +157,7 @@ struct Options {
     pt_temporal_params temporal{}; // -TEMPORAL: max_frames of the history, 0 = no temporal stage
     pt_bloom_params bloom{};       // -BLOOM, -BLOOM_THRESHOLD, -BLOOM_LEVELS
     pt_local_params local{};       // -LOCAL, -LOCAL_PIVOT, -LOCAL_LEVELS, -LOCAL_SIGMA
+    pt_sharpen_params sharpen{};   // -SHARPEN, -SHARPEN_LIMIT
     std::string wb, saturation, colour_matrix, lut_path;   // -WB, -SATURATION, -COLOR_MATRIX, -LUT as given
     pt_colour_params colour{};     // what they make; colour.lut is owned here
     pt_lut *lut = nullptr;
@@ -167,6 +174,7 @@ struct Options {
     bool display = false;          // -DEVICE_RESOLVE 1 and nothing that keeps the image on the host path
     bool blooming = false, localising = false, grading = false;   // -BLOOM > 0; -LOCAL > 0; either, colour, or any of the tone flags
     bool colouring = false;        // a matrix that is not the identity, or a LUT
+    bool sharpening = false;       // -SHARPEN > 0 (it makes `grading` true as well)
     bool optical = false;          // any of -DISTORTION / -CA / -VIGNETTE is not zero (it makes `grading` true as well)
     pt_camera view;                // with `camera`
     pt_lens lens{0.0f, 0.0f};
@@ -248,6 +256,8 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-LOCAL_PIVOT") o.local.pivot = static_cast<float>(std::atof(v));
         if (f == "-LOCAL_LEVELS") o.local.levels = std::atoi(v);
         if (f == "-LOCAL_SIGMA") o.local.sigma = static_cast<float>(std::atof(v));
+        if (f == "-SHARPEN") o.sharpen.strength = static_cast<float>(std::atof(v));
+        if (f == "-SHARPEN_LIMIT") o.sharpen.limit = static_cast<float>(std::atof(v));
         if (f == "-WB") o.wb = v;
         if (f == "-SATURATION") o.saturation = v;
         if (f == "-COLOR_MATRIX") o.colour_matrix = v;
@@ -427,6 +437,11 @@ int configure(int argc, char **argv, Options &o) {
         !(std::isfinite(o.local.sigma) && o.local.sigma >= 0.0f) || o.local.levels < 0 || o.local.levels > PT_LOCAL_MAX_LEVELS)
         return refuse(2, "-LOCAL, -LOCAL_PIVOT and -LOCAL_SIGMA take a number >= 0, -LOCAL_LEVELS 1 .. " + std::to_string(PT_LOCAL_MAX_LEVELS));
     o.localising = o.local.strength > 0.0f;
+    // -SHARPEN: the same, behind local exposure
+    if (!(std::isfinite(o.sharpen.strength) && o.sharpen.strength >= 0.0f && o.sharpen.strength <= 1.0f) ||
+        !(std::isfinite(o.sharpen.limit) && o.sharpen.limit >= 0.0f && o.sharpen.limit <= 0.1875f))
+        return refuse(2, "-SHARPEN takes a number in 0 .. 1, -SHARPEN_LIMIT a number in 0 .. 0.1875");
+    o.sharpening = o.sharpen.strength > 0.0f;
     // -WB / -SATURATION / -COLOR_MATRIX / -LUT: the colour stage, in the grade's place; alone it runs with the zeroed grade too.  The
     // .cube file is read here, by the library's host-only reader.
     if (!o.wb.empty() && !(parse_vec3(o.wb, o.colour.wb) && o.colour.wb[0] >= 0.0f && o.colour.wb[1] >= 0.0f && o.colour.wb[2] >= 0.0f))
@@ -463,7 +478,7 @@ int configure(int argc, char **argv, Options &o) {
             return refuse(2, std::string("-DISTORTION / -CA / -VIGNETTE (") + pt_last_error() + ")");
         o.optical = o.optics.k1 != 0.0f || o.optics.k2 != 0.0f || o.optics.ca != 0.0f || o.optics.vignette != 0.0f;
     }
-    o.grading = o.tone_flags || o.blooming || o.localising || o.colouring || o.optical;
+    o.grading = o.tone_flags || o.blooming || o.localising || o.sharpening || o.colouring || o.optical;
     // -TONE / -EXPOSURE / -AUTO_EXPOSURE: what every graded image is asked for
     if (o.tone_flags) {
         const char *names[4] = {"reference", "clamp", "reinhard", "aces"};
@@ -574,10 +589,13 @@ struct HostFrame {
     uint8_t *image() { return out_bgr.empty() ? bgr.data() : out_bgr.data(); }
 };
 
-// The device path's present: plain, scaled, or either with grading, bloom, local exposure, colour or optics
+// The device path's present: plain, scaled, or either with grading, bloom, local exposure, colour, optics or sharpening
 int present(const Run &r, HostFrame &host, pt_display_info *info) {
     const Options &o = r.o;
     const pt_upsample_params *up = o.scale > 1 ? &o.upsample : nullptr;
+    if (o.sharpening)
+        return pt_display_present_sharpen(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, &o.optics, &o.sharpen, host.image(), info,
+                                          nullptr);
     if (o.optical)
         return pt_display_present_optics(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, &o.optics, host.image(), info, nullptr);
     if (o.colouring) return pt_display_present_colour(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, host.image(), info, nullptr);
@@ -698,7 +716,7 @@ bool HostChain::bytes(HostFrame &host, float dispersion[3], ChainTimes &times) {
         m = lens_mean.data(); n = lens_count.data();
     }
     rgb.resize(3 * static_cast<size_t>(w) * h);
-    if (o.grading) {   // meter (a sequence's frame starts from the previous frame's exposure), bloom, local exposure, grade
+    if (o.grading) {   // meter (a sequence's frame starts from the previous frame's exposure), bloom, local exposure, sharpening, grade
         float e = o.grade.exposure > 0.0f ? o.grade.exposure : 1.0f, target = 0.0f;   // (0 = 1, as the library reads it)
         if (o.grade.auto_exposure) {
             uint32_t hist[PT_METER_ENTRIES];
@@ -714,6 +732,10 @@ bool HostChain::bytes(HostFrame &host, float dispersion[3], ChainTimes &times) {
         }
         if (o.localising) {
             if (pt_local_host(dev, w, h, m, n, e, &o.local, rgb.data(), nullptr) != PT_OK) return false;
+            m = rgb.data();
+        }
+        if (o.sharpening) {
+            if (pt_sharpen_host(dev, w, h, m, n, e, &o.sharpen, rgb.data(), nullptr) != PT_OK) return false;
             m = rgb.data();
         }
         if (o.colouring ? pt_colour_host(w, h, m, n, e, o.grade.curve, &o.colour, rgb.data()) != PT_OK
