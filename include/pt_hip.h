@@ -1131,6 +1131,91 @@ int pt_display_present_sharpen(pt_display *d, const pt_display_params *p, const 
                                const pt_optics_params *o, const pt_sharpen_params *s, uint8_t *bgr, pt_display_info *info /* may be NULL */,
                                pt_grade_info *grade_info /* may be NULL */);
 
+/* ---- film grain and dithered quantization: the display kernel's last step ------------------------------------------ */
+
+/* Every stage above makes the picture smoother, and the chain's last step is the reference's bare truncation to 8 bits: smooth
+ * gradients band.  Grain and dither are ONE stage with two parts, at the very end of the chain: they act on g, the value BEHIND matrix
+ * -> exposure -> curve -> LUT (pt_colour_host's output, or pt_grade_host's), per channel, and take the place of pt_tonemap ->
+ * pt_quantize.  No earlier stage sees that value, so on the device both live inside the display kernel: no plane is added.
+ *
+ * The arithmetic, exactly: every line below is ONE correctly rounded float operation in the order written (* / + -, comparisons,
+ * floor, int <-> float conversions) or integer arithmetic; nothing is fused, and there is no pow, log, exp or root beyond the
+ * threshold table's own, which is built once per gamma (pt_display_table).
+ *
+ * Random words.  Philox4x32-10 (Random123's rounds and constants) under key (seed, 0x50544831 "PTH1"), the integrator's key.  The
+ * counter's fourth word is not zero; the integrator's always is, so no stream is shared with a render of the same seed.
+ *   dither of pixel (x, y):          counter (x, y, frame, 1); words 0, 1, 2 serve r, g, b
+ *   grain lattice point (ix, iy):    counter (ix, iy, frame, 2); word 0
+ *   tri(w) = (float)((int)(w & 0xFFFF) + (int)(w >> 16) - 65535) * 2^-16
+ * tri is a triangular variate in (-1, 1) with mean 0: the integer lies in -65535 .. 65535 and is exact in a float, the product too.
+ *
+ * Grain, for pixel (x, y) with count != 0 and strength != 0 (with strength == 0 no word is drawn and g' = g).  With s = size:
+ *   fx = (float)x / s,   ix = (int)fx,   tx = fx - (float)ix;     fy, iy, ty likewise from y
+ *   v00 = tri(lattice(ix, iy)),  v10 = tri(lattice(ix + 1, iy)),  v01 = tri(lattice(ix, iy + 1)),  v11 = tri(lattice(ix + 1, iy + 1))
+ *   a = v00 + (tx * (v10 - v00)),   b = v01 + (tx * (v11 - v01)),   n = a + (ty * (b - a))
+ *   sn = strength * n
+ * At size == 1, tx = ty = 0 and n = v00 to the bit (the other three values are finite and multiplied by 0; they are not drawn).  One n
+ * serves the three channels: the grain is monochrome.  A channel takes grain only if 0 < g && g < 1 (both false for NaN):
+ *   w  = (g * (1 - g)) * 4
+ *   g' = g + (sn * w);   g' = g' < 0 ? 0 : (g' > 1 ? 1 : g')
+ * Every other channel keeps its BITS: black, clipped white, emitters, the reference curve's wrapped values above 1, negatives and NaN
+ * pass unchanged.  The weight is 1 at mid-grey and falls to 0 at both ends, as film's does.
+ *
+ * Dither, per channel of g'.  T[1 .. levels] are the thresholds of pt_display_table(gamma), T[0] stands for 0.  The table COVERS g' if
+ * g' >= 0 (false for NaN), g' < T[levels] and g' lies in no doubt band; then k, the number of thresholds <= g', is below levels, so
+ * T[k + 1] is a threshold in use.  A covered channel with dither != 0:
+ *   lo = T[k] (0 for k == 0),   hi = T[k + 1]                   (lo <= g' < hi)
+ *   f  = (g' - lo) / (hi - lo)                                   (0 <= f <= 1)
+ *   t  = f + (dither * tri(word of the channel))                 (-1 < t < 2)
+ *   j  = (int)floor(t)                                            (-1, 0 or 1)
+ *   k' = k + j;   if (k' < 0 || (k' >> 8) != (k >> 8)) k' = k    (black stays at or above 0; byte 255 and the wrapped levels stay in their block of 256)
+ *   byte = k' & 255
+ * A covered channel with dither == 0 is byte = k & 255, and a channel the table does not cover is (uint8_t)(int)(pow(g', gamma) * 255),
+ * pt_tonemap's and pt_quantize's own steps, whatever dither is.  A pixel with count == 0 is three zero bytes.
+ *
+ * The mean is kept relative to the truncation: with dither == 1 and U1, U2 the two uniform halves of the word, t = f + U1 + U2 - 1;
+ * E[floor(a + U)] = a for any a and a uniform U in [0, 1), applied twice E[j] = f + 1/2 - 1:  E[k'] = k + f - 1/2, and the variance
+ * about that mean is 1/4 whatever f is -- the property triangular dither is chosen for: neither the mean error nor the noise power
+ * shows the signal.  (The halves are 16-bit, so both hold to 2^-16.)
+ *
+ * Parameters; a zeroed struct means the stage does not run, and the bytes are those of pt_tonemap -> pt_quantize:
+ *   strength    finite, 0 .. 1; 0 = no grain                                                        (else: invalid)
+ *   size        the lattice pitch in pixels: finite, 0 (= 1) or 1 .. 8                               (else: invalid)
+ *   dither      finite, 0 .. 1, in levels; 0 = none, 1 = full triangular dither                     (else: invalid)
+ *   seed, frame any; frame is the noise's third coordinate: advance it once per presented frame
+ * The stage runs if strength > 0 or dither > 0.  Any image size from 1 x 1 is valid. */
+typedef struct pt_grain_params {
+    float    strength;  /* 0 .. 1; 0 = no grain                      */
+    float    size;      /* 1 .. 8 lattice pitch in pixels; 0 = 1     */
+    float    dither;    /* 0 .. 1 of one level, triangular; 0 = none */
+    uint32_t seed;
+    uint32_t frame;     /* the noise's third coordinate              */
+} pt_grain_params;
+
+/* Host only, no device: the last step of every host chain with the stage, in the place of pt_tonemap -> pt_quantize:
+ * ... -> pt_colour_host(e, curve) (or pt_grade_host) -> pt_grain_quantize.  graded_rgb is g; bgr gets B, G, R bytes, zero for pixels with
+ * count == 0.  It uses the threshold table the device is given (pt_display_table(gamma), built on first use of a gamma).  Checked in
+ * this order: NULL buffers and empty sizes, the image size, gamma (finite and > 0), *n as above.  With a zeroed *n the bytes are those
+ * of pt_tonemap -> pt_quantize for every input. */
+int pt_grain_quantize(int32_t width, int32_t height, const float *graded_rgb, const int32_t *count, float gamma, const pt_grain_params *n,
+                      uint8_t *bgr);
+/* pt_display_bytes_colour_host with the stage: meter (if automatic), exposure and the grain display kernel as one chain on HIP device
+ * `device`, on a host image.  Everything is checked before the device is looked at.  With a zeroed *n it is
+ * pt_display_bytes_colour_host. */
+int pt_display_bytes_grain_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
+                                const pt_grade_params *g, const pt_colour_params *c, const pt_grain_params *n, int32_t has_prev,
+                                float e_prev, uint8_t *bgr, pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
+/* pt_display_present_sharpen with the stage: the same chain with the grain display kernel in the graded or the colour kernel's place;
+ * it reads and writes what they do.  The bytes are DEFINED by the host chain and equal it bit for bit: ... -> pt_sharpen_host(e) ->
+ * pt_colour_host(e, curve) -> pt_grain_quantize, at the output size.  *n is checked with *g, before anything is enqueued and before the
+ * device is looked at; a failed present leaves the history and the previous exposure as they were.  A deferred pixel still carries the
+ * mean before the matrix: the host redoes matrix -> exposure -> curve -> LUT -> grain -> dither for it from its index, seed and frame.
+ * With a zeroed *n the call is pt_display_present_sharpen. */
+int pt_display_present_grain(pt_display *d, const pt_display_params *p, const pt_upsample_params *u /* NULL: not scaled */,
+                             const pt_grade_params *g, const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c,
+                             const pt_optics_params *o, const pt_sharpen_params *s, const pt_grain_params *n, uint8_t *bgr,
+                             pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

@@ -53,7 +53,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_lut_create", "pt_lut_load_cube", "pt_lut_size", "pt_lut_destroy", "pt_colour_matrix", "pt_colour_host",
                "pt_display_bytes_colour_host", "pt_display_present_colour",
                "pt_optics_host", "pt_display_present_optics",
-               "pt_sharpen_host", "pt_display_present_sharpen"]
+               "pt_sharpen_host", "pt_display_present_sharpen",
+               "pt_grain_quantize", "pt_display_bytes_grain_host", "pt_display_present_grain"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -313,6 +314,26 @@ def _sharpen_params(sharpen):
     return sharpen
 
 
+GRAIN_MAX_SIZE = 8.0
+
+
+class GrainParams(C.Structure):
+    """pt_grain_params: a zeroed struct is no grain and no dither; strength in 0 .. 1, size 0 (= 1) or 1 .. 8 pixels, dither in
+    0 .. 1 levels, seed and frame any uint32 (frame: the noise's third coordinate)."""
+    _fields_ = [("strength", C.c_float), ("size", C.c_float), ("dither", C.c_float), ("seed", C.c_uint32), ("frame", C.c_uint32)]
+
+
+def _grain_params(grain):
+    """A GrainParams, or a dict of its fields ({"strength": 0.2, "size": 1.5, "dither": 1.0, "seed": 7, "frame": 0}) -> a GrainParams."""
+    if isinstance(grain, dict):
+        unknown = set(grain) - {"strength", "size", "dither", "seed", "frame"}
+        if unknown:
+            raise ValueError(f"grain: unknown fields {sorted(unknown)}")
+        return GrainParams(grain.get("strength", 0.0), grain.get("size", 0.0), grain.get("dither", 0.0), int(grain.get("seed", 0)) & 0xFFFFFFFF,
+                           int(grain.get("frame", 0)) & 0xFFFFFFFF)
+    return grain
+
+
 def _optics_params(optics):
     """An OpticsParams, or a dict of its fields ({"k1": -0.1, "ca": 0.01, "vignette": 1.0}) -> an OpticsParams."""
     if isinstance(optics, dict):
@@ -498,6 +519,12 @@ def load_library(path):
     L.pt_display_present_sharpen.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
                                              C.POINTER(LocalParams), cp, C.POINTER(OpticsParams), C.POINTER(SharpenParams), bp,
                                              C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_grain_quantize.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(GrainParams), bp]
+    L.pt_display_bytes_grain_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, C.POINTER(GradeParams), cp, C.POINTER(GrainParams),
+                                              C.c_int32, C.c_float, bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_display_present_grain.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
+                                           C.POINTER(LocalParams), cp, C.POINTER(OpticsParams), C.POINTER(SharpenParams), C.POINTER(GrainParams), bp,
+                                           C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -847,7 +874,7 @@ class Display:
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
     def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None, colour=None, optics=None,
-                sharpen=None):
+                sharpen=None, grain=None):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
         parameters.  Returns (bgr uint8 [H, W, 3], info dict).
@@ -865,7 +892,10 @@ class Display:
         pt_display_present_optics: distortion, chromatic aberration and vignetting of the linear mean ahead of the meter (the other
         stages None: zeroed).
         `sharpen`: None, a SharpenParams, or a dict of its fields ({"strength": 0.5, "limit": 0.0}) -- pt_display_present_sharpen: a
-        contrast-adaptive sharpen of the luminance after local exposure and before the grade (the other stages None: zeroed)."""
+        contrast-adaptive sharpen of the luminance after local exposure and before the grade (the other stages None: zeroed).
+        `grain`: None, a GrainParams, or a dict of its fields ({"strength": 0.2, "size": 1.5, "dither": 1.0, "seed": 7, "frame": 0}) --
+        pt_display_present_grain: film grain on the graded value and a triangular dither of its level, inside the display kernel (the
+        other stages None: zeroed); advance `frame` once per presented frame."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -874,13 +904,20 @@ class Display:
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
         info = DisplayInfo()
-        if grade is not None or bloom is not None or local is not None or colour is not None or optics is not None or sharpen is not None:
+        if grade is not None or bloom is not None or local is not None or colour is not None or optics is not None or sharpen is not None or \
+                grain is not None:
             gp, ginfo = _grade_params(grade) if grade is not None else GradeParams(), GradeInfo()
             up = _upsample_params(upsample) if upsample is not None else None
             k = up.scale if up is not None and 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1
             bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8)
             up_arg, out = C.byref(up) if up is not None else None, bgr.ctypes.data_as(C.POINTER(C.c_uint8))
-            if sharpen is not None:
+            if grain is not None:
+                bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local) if local is not None else LocalParams()
+                cp_, op = _colour_params(colour) if colour is not None else ColourParams(), _optics_params(optics) if optics is not None else OpticsParams()
+                sp, np_ = _sharpen_params(sharpen) if sharpen is not None else SharpenParams(), _grain_params(grain)
+                _check(self._L.pt_display_present_grain(self._h, C.byref(prm), up_arg, C.byref(gp), C.byref(bp_), C.byref(lp), C.byref(cp_),
+                                                        C.byref(op), C.byref(sp), C.byref(np_), out, C.byref(info), C.byref(ginfo)), self._L)
+            elif sharpen is not None:
                 bp_, lp = _bloom_params(bloom) if bloom is not None else BloomParams(), _local_params(local) if local is not None else LocalParams()
                 cp_, op = _colour_params(colour) if colour is not None else ColourParams(), _optics_params(optics) if optics is not None else OpticsParams()
                 sp = _sharpen_params(sharpen)
@@ -1099,6 +1136,38 @@ def display_bytes_colour(mean_rgb, count, grade, colour, gamma=None, e_prev=None
     _check(L.pt_display_bytes_colour_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(gamma), C.byref(gp), C.byref(prm),
                                           0 if e_prev is None else 1, C.c_float(0.0 if e_prev is None else e_prev),
                                           bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info), C.byref(ginfo)), L)
+    return bgr, dict(info.as_dict(), **ginfo.as_dict())
+
+
+def grain_quantize(graded_rgb, count, gamma=None, grain=None, library=None):
+    """pt_grain_quantize (host only): the bytes of a graded image graded_rgb [H, W, 3] (pt.colour's or pt.grade's output) with count
+    [H, W] under film grain and dithered quantization -- the host chain's last step, in the place of tonemap -> quantize.  `grain`: None
+    (their bytes), a GrainParams, or a dict of its fields.  Returns bgr uint8 [H, W, 3]."""
+    L = library or lib()
+    if gamma is None:
+        gamma = np.float32(1) / np.float32(2.2)
+    m, c = _image_args("grain_quantize", graded_rgb, count)
+    prm = _grain_params(grain) if grain is not None else GrainParams()
+    bgr = np.zeros(m.shape, np.uint8)
+    _check(L.pt_grain_quantize(m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(gamma), C.byref(prm), bgr.ctypes.data_as(C.POINTER(C.c_uint8))), L)
+    return bgr
+
+
+def display_bytes_grain(mean_rgb, count, grade, colour, grain, gamma=None, e_prev=None, device=0, library=None):
+    """pt_display_bytes_grain_host: meter (if automatic), exposure and the grain display kernel on a host image.  Returns
+    (bgr uint8 [H, W, 3], info dict with the display's and the grade's fields)."""
+    L = library or lib()
+    if gamma is None:
+        gamma = np.float32(1) / np.float32(2.2)
+    m, c = _image_args("display_bytes_grain", mean_rgb, count)
+    gp = _grade_params(grade) if grade is not None else GradeParams()
+    prm = _colour_params(colour) if colour is not None else ColourParams()
+    np_ = _grain_params(grain) if grain is not None else GrainParams()
+    bgr = np.zeros(m.shape, np.uint8)
+    info, ginfo = DisplayInfo(), GradeInfo()
+    _check(L.pt_display_bytes_grain_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(gamma), C.byref(gp), C.byref(prm), C.byref(np_),
+                                         0 if e_prev is None else 1, C.c_float(0.0 if e_prev is None else e_prev),
+                                         bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info), C.byref(ginfo)), L)
     return bgr, dict(info.as_dict(), **ginfo.as_dict())
 
 

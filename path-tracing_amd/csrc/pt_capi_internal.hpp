@@ -1,6 +1,6 @@
 // What the translation units behind the C ABI share (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters; pt_frame.cpp: the
 // multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
-// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp, pt_sharpen_capi.cpp: one image-space stage each; pt_display_capi.cpp: the device-resident
+// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp, pt_sharpen_capi.cpp: one image-space stage each; pt_grain_capi.cpp: grain and dither, the host chain's last step; pt_display_capi.cpp: the device-resident
 // display path, which chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
 // arguments, the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments, and the timed region
 // of a one-shot entry point.
@@ -22,6 +22,7 @@
 #include "pt_denoise.hpp"
 #include "pt_device_mem.hpp"
 #include "pt_grade.hpp"
+#include "pt_grain.hpp"
 #include "pt_kernels.hpp"
 #include "pt_local.hpp"
 #include "pt_meter.hpp"
@@ -276,6 +277,20 @@ struct SharpenSetup {
     float limit = pt::kSharpenMaxLimit;
 };
 int sharpen_params_check(const pt_sharpen_params *s, SharpenSetup &out);
+
+// pt_grain_params as every entry point checks them (no device is touched), with the default pitch filled in (pt_grain_capi.cpp).
+// `step.width` is the caller's to set.
+struct GrainSetup {
+    bool on = false;          // strength > 0 or dither > 0: the stage runs
+    pt::GrainStep step{};
+};
+int grain_params_check(const pt_grain_params *n, GrainSetup &out);
+// The threshold table of `gamma` (pt_display_capi.cpp: one per gamma, built on first use and kept).
+struct DisplayTable;
+std::shared_ptr<const DisplayTable> display_table(float gamma);
+// The three bytes (r, g, b) of pixel (x, y) with samples from its g, the value behind matrix -> exposure -> curve -> LUT: grain, then
+// per channel the dithered level of a value the table covers, and the host's own tone map and truncation of any other.
+void grain_pixel_bytes(const pt::GrainStep &s, const DisplayTable &table, float gamma, uint32_t x, uint32_t y, const float *g, uint8_t *rgb);
 
 // The image a chain has reached: planes on the device, sums still (divide) or means, and its size.
 struct Image { const float *rgb; const int32_t *count; bool divide; int32_t width, height; };

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "pt_colour.hpp"
+#include "pt_grain.hpp"
 
 namespace pt {
 
@@ -39,5 +40,9 @@ hipError_t launch_display_graded(const DisplayArgs &args, int curve, const float
 // The same with colour grading (pt_display_colour.hip): per pixel matrix -> exposure -> curve -> LUT (pt_colour.hpp) makes the g;
 // a deferred entry carries the mean before the matrix.  `colour.lut` is device memory, valid until the kernel has finished.
 hipError_t launch_display_colour(const DisplayArgs &args, int curve, const float *exposure, const ColourStep &colour, hipStream_t stream);
+// The same with film grain and dither (pt_display_grain.hip): g takes the pixel's grain behind the LUT (pt_grain.hpp), and the level of
+// a channel the table covers is dithered between the thresholds round it.  `grain.width` is the image's, `grain.size` is in 1 .. 8.
+hipError_t launch_display_grain(const DisplayArgs &args, int curve, const float *exposure, const ColourStep &colour, const GrainStep &grain,
+                                hipStream_t stream);
 
 }  // namespace pt

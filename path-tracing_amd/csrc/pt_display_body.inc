@@ -6,6 +6,10 @@
 // mean -- the host finishes such a pixel with the same pt_grade.hpp, so a NaN's payload never has to agree between host and device.
 // With PT_DISPLAY_COLOUR defined as well (pt_display_colour.hip) also LUT (a bool) and colour (a ColourStep of pt_colour.hpp): g is
 // then what matrix -> exposure -> curve -> LUT makes of the pixel, and a deferred entry carries the mean before the matrix.
+// With PT_DISPLAY_GRAIN defined as well (pt_display_grain.hip) also SIZED (a bool) and grain (a GrainStep of pt_grain.hpp): g then
+// takes the pixel's grain before the out-of-table test, and the level of a channel the table covers is dithered between T[k - 1] and
+// T[k].  A lane's four pixels are consecutive in the flat plane: one division gives the first one's (x, y), the others follow along
+// the row and wrap at its end.
     __shared__ __attribute__((aligned(16))) float T[kDisplayTableSize];
     for (int i = threadIdx.x; i < kDisplayTableSize / 4; i += kDisplayBlock)
         reinterpret_cast<float4 *>(T)[i] = reinterpret_cast<const float4 *>(a.table)[i];
@@ -63,6 +67,20 @@
         }
 #endif
 #endif
+#ifdef PT_DISPLAY_GRAIN
+        uint32_t px_x[4], px_y[4];
+        {
+            const uint32_t width = static_cast<uint32_t>(grain.width);
+            uint32_t y = static_cast<uint32_t>(p0) / width, x = static_cast<uint32_t>(p0) - y * width;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                px_x[j] = x; px_y[j] = y;
+                if (++x == width) { x = 0; ++y; }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) grain_pixel<SIZED>(grain, px_x[j], px_y[j], m[3 * j], m[3 * j + 1], m[3 * j + 2]);
+#endif
         bool out_of_table[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) out_of_table[i] = !(m[i] >= 0.0f) || m[i] >= a.last;
@@ -77,8 +95,22 @@
         for (int j = 0; j < 4; ++j) {
             const bool samples = c[j] != 0;
             defer[j] = samples && (out_of_table[3 * j] || out_of_table[3 * j + 1] || out_of_table[3 * j + 2]);
+#ifdef PT_DISPLAY_GRAIN
+            uint32_t level[3], word[3] = {0u, 0u, 0u};
+            const bool dithered = grain.dither != 0.0f && samples && !defer[j];   // (a deferred pixel is the host's, dither and all)
+            if (dithered) grain_dither_words(grain, px_x[j], px_y[j], word[0], word[1], word[2]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float v = m[3 * j + k];
+                level[k] = display_level(T, v);
+                // covered: level[k] thresholds lie at or below v and the next one, T[level[k]], is in use (v < a.last)
+                if (dithered) level[k] = grain_dither_level(level[k], level[k] ? T[level[k] - 1] : 0.0f, T[level[k]], v, grain.dither, word[k]);
+            }
+            const uint32_t r = level[0] & 255u, gr = level[1] & 255u, bl = level[2] & 255u;
+#else
             const uint32_t r = display_level(T, m[3 * j]) & 255u, gr = display_level(T, m[3 * j + 1]) & 255u,
                            bl = display_level(T, m[3 * j + 2]) & 255u;
+#endif
             px[j] = samples && !defer[j] ? (bl | (gr << 8) | (r << 16)) : 0u;
         }
         // B G R B | G R B G | R B G R

@@ -10,6 +10,8 @@
 // display's, which the meter and every later stage read in the chain's place.
 // With sharpening (pt_display_present_sharpen): its two kernels behind local exposure's, immediately ahead of the graded or the colour
 // kernel, in place on the plane of means a stage of the display's wrote, or from the chain's image into a plane of the display's.
+// With grain or dither (pt_display_present_grain): the grain display kernel in the graded or the colour one's place, and deferred pixels
+// finished with pt_grain.hpp from their index, the seed and the frame.
 #include "pt_capi_internal.hpp"
 
 #include <algorithm>
@@ -33,8 +35,10 @@ int check_gamma(float gamma) {
     return PT_OK;
 }
 
+}  // namespace
+
 // One table per gamma (its bit pattern), built on first use: about 650 000 calls of powf.
-std::shared_ptr<const DisplayTable> display_table(float gamma) {
+std::shared_ptr<const ptc::DisplayTable> ptc::display_table(float gamma) {
     static std::mutex mutex;
     static std::vector<std::shared_ptr<const DisplayTable>> cache;   // most recent last; a handful of gammas at most
     std::lock_guard<std::mutex> lock(mutex);
@@ -48,6 +52,10 @@ std::shared_ptr<const DisplayTable> display_table(float gamma) {
     return t;
 }
 
+namespace {
+
+using ptc::display_table;
+
 // What a graded present is asked for: the checked parameters, and the display's previous metered exposure.
 struct GradeRequest {
     ptc::GradeSetup setup;
@@ -58,6 +66,7 @@ struct GradeRequest {
     ptc::ColourSetup colour; // on: the colour display kernel takes the graded one's place
     ptc::OpticsSetup optics; // on: the optics kernel runs ahead of the meter, and everything behind it reads what it wrote
     ptc::SharpenSetup sharpen;   // on: the sharpening kernels run last before the graded or the colour kernel
+    ptc::GrainSetup grain;   // on: the grain display kernel takes the graded or the colour one's place
     // the image the chain hands to the stages is no plane of the display's: no stage ahead of sharpening writes one it may overwrite
     bool sharpen_own_mean() const { return !optics.on && !bloom.on && !local.on; }
 };
@@ -71,12 +80,21 @@ void deferred_value(const float *mean, const GradeRequest *grade, float e, float
     if (grade->colour.on) pt::colour_pixel(grade->colour.step, grade->setup.curve, e, v[0], v[1], v[2]);
     else for (int k = 0; k < 3; ++k) v[k] = pt::grade_value(grade->setup.curve, mean[k], e);
 }
-// What the kernel would have written for the pixels it deferred: the host's own two steps on that value.
-void finish_on_host(const std::vector<pt::DisplayDeferred> &list, float gamma, const GradeRequest *grade, float e, uint8_t *bgr) {
+// What the kernel would have written for the pixels it deferred: the host's own two steps on that value -- or, with grain or dither,
+// pt_grain.hpp's on it and the table's or the host's on each channel of the result.
+void finish_on_host(const std::vector<pt::DisplayDeferred> &list, float gamma, const DisplayTable &table, const GradeRequest *grade, float e,
+                    uint8_t *bgr) {
     for (const pt::DisplayDeferred &d : list) {
         const size_t p = static_cast<size_t>(d.pixel);
         float v[3];
         deferred_value(d.mean, grade, e, v);
+        if (grade && grade->grain.on) {
+            const uint32_t width = static_cast<uint32_t>(grade->grain.step.width), pixel = static_cast<uint32_t>(d.pixel);
+            uint8_t rgb[3];
+            ptc::grain_pixel_bytes(grade->grain.step, table, gamma, pixel % width, pixel / width, v, rgb);
+            for (int k = 0; k < 3; ++k) bgr[3 * p + k] = rgb[2 - k];
+            continue;
+        }
         for (int k = 0; k < 3; ++k) bgr[3 * p + k] = ptc::quantize_value(ptc::tonemap_value(v[2 - k], gamma));
     }
 }
@@ -235,7 +253,13 @@ struct DisplayDevice {
         a.band_lo = band_lo; a.band_hi = band_hi;
         a.bgr = bgr; a.deferred = deferred; a.n_deferred = n_deferred;
         if (!grade) PT_HIP_TRY(pt::launch_display(a, stream));
-        else if (!grade->colour.on) PT_HIP_TRY(pt::launch_display_graded(a, grade->setup.curve, &exposure->exposure, stream));
+        else if (grade->grain.on) {   // (the colour step of a request without one is the identity and no LUT)
+            pt::ColourStep step = grade->colour.step;
+            step.lut = step.lut_n ? d_lut.at<pt::LutVertex>(0) : nullptr;
+            pt::GrainStep grain = grade->grain.step;
+            grain.width = image.width;
+            PT_HIP_TRY(pt::launch_display_grain(a, grade->setup.curve, &exposure->exposure, step, grain, stream));
+        } else if (!grade->colour.on) PT_HIP_TRY(pt::launch_display_graded(a, grade->setup.curve, &exposure->exposure, stream));
         else {   // (use_lut has brought the LUT of this request to the device)
             pt::ColourStep step = grade->colour.step;
             step.lut = step.lut_n ? d_lut.at<pt::LutVertex>(0) : nullptr;
@@ -261,7 +285,7 @@ struct DisplayDevice {
             PT_HIP_TRY(hipMemcpy(list.data(), deferred, sizeof(pt::DisplayDeferred) * len, hipMemcpyDeviceToHost));
             for (const pt::DisplayDeferred &d : list)
                 if (d.pixel < 0 || static_cast<size_t>(d.pixel) >= n) return fail(PT_ERR_HIP, "display: a deferred pixel lies outside the image");
-            finish_on_host(list, gamma, grade, got.used.exposure, out);
+            finish_on_host(list, gamma, *host, grade, got.used.exposure, out);
         }
         got.n_deferred = static_cast<int32_t>(len);
         return PT_OK;
@@ -376,6 +400,7 @@ struct PresentRequest {
     const pt_colour_params *colour = nullptr;
     const pt_optics_params *optics = nullptr;
     const pt_sharpen_params *sharpen = nullptr;
+    const pt_grain_params *grain = nullptr;
 };
 
 int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, pt_display_info *info) {
@@ -392,6 +417,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (rq.colour && (rc = ptc::colour_params_check(rq.colour, grade.colour)) != PT_OK) return rc;
     if (rq.optics && (rc = ptc::optics_params_check(rq.optics, grade.optics)) != PT_OK) return rc;
     if (rq.sharpen && (rc = ptc::sharpen_params_check(rq.sharpen, grade.sharpen)) != PT_OK) return rc;
+    if (rq.grain && (rc = ptc::grain_params_check(rq.grain, grade.grain)) != PT_OK) return rc;
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -400,6 +426,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     pt::DenoiseArgs da;
     if ((rc = ptc::denoise_params_to_args(&p->denoise, da)) != PT_OK) return rc;
     const bool temporal = p->temporal != 0, filter = da.levels > 0;
+    grade.grain.step.width = scaled ? ua.width : d->width;   // (of the image the bytes are made of)
     std::lock_guard<std::mutex> present_lock(d->mutex);
     grade.has_prev = d->has_exposure; grade.e_prev = d->exposure;
     const std::shared_ptr<const DisplayTable> table = display_table(p->gamma);
@@ -484,7 +511,9 @@ int present(pt_display *d, bool complete, const PresentRequest &rq, uint8_t *bgr
 
 // A mean image in host memory, and how it is to be graded (pt_display_bytes_graded_host).
 struct HostImage { int device; int32_t width, height; const float *mean_rgb; const int32_t *count; };
-struct HostGrade { const pt_grade_params *params; bool has_prev; float e_prev; pt_grade_info *info; const pt_colour_params *colour; };   // (info, colour may be NULL)
+struct HostGrade {   // (info, colour, grain may be NULL)
+    const pt_grade_params *params; bool has_prev; float e_prev; pt_grade_info *info; const pt_colour_params *colour; const pt_grain_params *grain;
+};
 
 // `g` = NULL: pt_display_bytes_host.
 int display_bytes_host_impl(const HostImage &image, float gamma, const HostGrade *g, uint8_t *bgr, pt_display_info *info) {
@@ -496,6 +525,8 @@ int display_bytes_host_impl(const HostImage &image, float gamma, const HostGrade
     if (g && (rc = ptc::grade_params_check(g->params, grade.setup)) != PT_OK) return rc;
     if (g) grade.has_prev = g->has_prev, grade.e_prev = g->e_prev;
     if (g && g->colour && (rc = ptc::colour_params_check(g->colour, grade.colour)) != PT_OK) return rc;
+    if (g && g->grain && (rc = ptc::grain_params_check(g->grain, grade.grain)) != PT_OK) return rc;
+    grade.grain.step.width = image.width;
     if ((rc = ptc::use_device(image.device, "display")) != PT_OK) return rc;
     const size_t n = static_cast<size_t>(image.width) * image.height;
     const std::shared_ptr<const DisplayTable> table = display_table(gamma);
@@ -630,6 +661,15 @@ int pt_display_present_sharpen(pt_display *d, const pt_display_params *p, const 
     return present(d, g && b && l && c && o && s, rq, bgr, info);
 }
 
+int pt_display_present_grain(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
+                             const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c, const pt_optics_params *o,
+                             const pt_sharpen_params *s, const pt_grain_params *n, uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info; rq.bloom = b; rq.local = l; rq.colour = c; rq.optics = o;
+    rq.sharpen = s; rq.grain = n;
+    return present(d, g && b && l && c && o && s && n, rq, bgr, info);
+}
+
 int pt_display_reset(pt_display *d) {
     return guarded([&] {
         if (!d) return fail(PT_ERR_INVALID_ARGUMENT, "null handle");
@@ -653,7 +693,7 @@ int pt_display_bytes_graded_host(int device, int32_t width, int32_t height, cons
                                  const pt_grade_params *g, int32_t has_prev, float e_prev, uint8_t *bgr, pt_display_info *info,
                                  pt_grade_info *grade_info) {
     return guarded([&] {
-        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info, nullptr};
+        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info, nullptr, nullptr};
         return display_bytes_host_impl({device, width, height, mean_rgb, count}, gamma, &grade, bgr, info);
     });
 }
@@ -663,7 +703,17 @@ int pt_display_bytes_colour_host(int device, int32_t width, int32_t height, cons
                                  pt_display_info *info, pt_grade_info *grade_info) {
     return guarded([&] {
         if (!c) return null_argument();
-        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info, c};
+        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info, c, nullptr};
+        return display_bytes_host_impl({device, width, height, mean_rgb, count}, gamma, &grade, bgr, info);
+    });
+}
+
+int pt_display_bytes_grain_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma,
+                                const pt_grade_params *g, const pt_colour_params *c, const pt_grain_params *n, int32_t has_prev, float e_prev,
+                                uint8_t *bgr, pt_display_info *info, pt_grade_info *grade_info) {
+    return guarded([&] {
+        if (!c || !n) return null_argument();
+        const HostGrade grade = {g, has_prev != 0, e_prev, grade_info, c, n};
         return display_bytes_host_impl({device, width, height, mean_rgb, count}, gamma, &grade, bgr, info);
     });
 }

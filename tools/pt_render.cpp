@@ -104,9 +104,16 @@
 // bloom and local exposure and immediately before the colour stage or the grade (alone it runs with the zeroed grade, as -LOCAL
 // does); the meter does not see it, and previews stay as they are.  It works on the host path and with -DEVICE_RESOLVE 1, with
 // byte-identical files, and with every flag grading works with.  Without -SHARPEN, or with -SHARPEN 0, nothing changes.
+// Film grain and dithered quantization (pt_grain_quantize, pt_display_present_grain, not in the reference): -GRAIN <strength in 0 .. 1,
+// default 0: off> adds monochrome grain of lattice pitch -GRAIN_SIZE <pixels in 1 .. 8, default 1> to the graded value, weighted
+// towards the mid-tones; -DITHER <amount in 0 .. 1 levels, default 0: off> dithers the 8-bit quantization with triangular noise, which
+// takes the bands out of smooth gradients; -GRAIN_SEED <n, default 0> seeds both, and a -FRAMES sequence draws new noise every frame
+// (the frame's index).  It is the chain's last step, in the place of the tone map and the quantization (alone it runs with the zeroed
+// grade); black, clipped white and emitters keep their bytes under grain.  It works on the host path and with -DEVICE_RESOLVE 1, with
+// byte-identical files, and with every flag grading works with, but not with -GAUSS / -MEDIAN.  Without -GRAIN and -DITHER nothing changes.
 // The image chain is stated once, in HostChain::bytes, in the order the paragraphs above give: temporal merge -> first-hit
 // features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> optics -> meter, bloom, local exposure, sharpening, colour / grade -> tone map
-// -> -GAUSS / -MEDIAN -> quantize.  A single frame and every frame of a sequence go through it; with -DEVICE_RESOLVE 1 the
+// -> -GAUSS / -MEDIAN -> quantize (or grain and dithered quantization in the last three's place).  A single frame and every frame of a sequence go through it; with -DEVICE_RESOLVE 1 the
 // bytes come from present() instead.
 #include <algorithm>
 #include <chrono>
@@ -158,6 +165,7 @@ struct Options {
     pt_bloom_params bloom{};       // -BLOOM, -BLOOM_THRESHOLD, -BLOOM_LEVELS
     pt_local_params local{};       // -LOCAL, -LOCAL_PIVOT, -LOCAL_LEVELS, -LOCAL_SIGMA
     pt_sharpen_params sharpen{};   // -SHARPEN, -SHARPEN_LIMIT
+    pt_grain_params grain{};       // -GRAIN, -GRAIN_SIZE, -DITHER, -GRAIN_SEED (frame: set per image)
     std::string wb, saturation, colour_matrix, lut_path;   // -WB, -SATURATION, -COLOR_MATRIX, -LUT as given
     pt_colour_params colour{};     // what they make; colour.lut is owned here
     pt_lut *lut = nullptr;
@@ -175,6 +183,7 @@ struct Options {
     bool blooming = false, localising = false, grading = false;   // -BLOOM > 0; -LOCAL > 0; either, colour, or any of the tone flags
     bool colouring = false;        // a matrix that is not the identity, or a LUT
     bool sharpening = false;       // -SHARPEN > 0 (it makes `grading` true as well)
+    bool graining = false;         // -GRAIN > 0 or -DITHER > 0 (it makes `grading` true as well)
     bool optical = false;          // any of -DISTORTION / -CA / -VIGNETTE is not zero (it makes `grading` true as well)
     pt_camera view;                // with `camera`
     pt_lens lens{0.0f, 0.0f};
@@ -258,6 +267,10 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-LOCAL_SIGMA") o.local.sigma = static_cast<float>(std::atof(v));
         if (f == "-SHARPEN") o.sharpen.strength = static_cast<float>(std::atof(v));
         if (f == "-SHARPEN_LIMIT") o.sharpen.limit = static_cast<float>(std::atof(v));
+        if (f == "-GRAIN") o.grain.strength = static_cast<float>(std::atof(v));
+        if (f == "-GRAIN_SIZE") o.grain.size = static_cast<float>(std::atof(v));
+        if (f == "-DITHER") o.grain.dither = static_cast<float>(std::atof(v));
+        if (f == "-GRAIN_SEED") o.grain.seed = static_cast<uint32_t>(std::strtoul(v, nullptr, 10));
         if (f == "-WB") o.wb = v;
         if (f == "-SATURATION") o.saturation = v;
         if (f == "-COLOR_MATRIX") o.colour_matrix = v;
@@ -442,6 +455,13 @@ int configure(int argc, char **argv, Options &o) {
         !(std::isfinite(o.sharpen.limit) && o.sharpen.limit >= 0.0f && o.sharpen.limit <= 0.1875f))
         return refuse(2, "-SHARPEN takes a number in 0 .. 1, -SHARPEN_LIMIT a number in 0 .. 0.1875");
     o.sharpening = o.sharpen.strength > 0.0f;
+    // -GRAIN / -DITHER: the same, at the chain's end
+    if (!(std::isfinite(o.grain.strength) && o.grain.strength >= 0.0f && o.grain.strength <= 1.0f) ||
+        !(std::isfinite(o.grain.size) && (o.grain.size == 0.0f || (o.grain.size >= 1.0f && o.grain.size <= 8.0f))) ||
+        !(std::isfinite(o.grain.dither) && o.grain.dither >= 0.0f && o.grain.dither <= 1.0f))
+        return refuse(2, "-GRAIN and -DITHER take a number in 0 .. 1, -GRAIN_SIZE a number in 1 .. 8");
+    o.graining = o.grain.strength > 0.0f || o.grain.dither > 0.0f;
+    if (o.graining && (o.gauss || o.median)) return refuse(2, "-GRAIN and -DITHER do not work with -GAUSS / -MEDIAN");
     // -WB / -SATURATION / -COLOR_MATRIX / -LUT: the colour stage, in the grade's place; alone it runs with the zeroed grade too.  The
     // .cube file is read here, by the library's host-only reader.
     if (!o.wb.empty() && !(parse_vec3(o.wb, o.colour.wb) && o.colour.wb[0] >= 0.0f && o.colour.wb[1] >= 0.0f && o.colour.wb[2] >= 0.0f))
@@ -478,7 +498,7 @@ int configure(int argc, char **argv, Options &o) {
             return refuse(2, std::string("-DISTORTION / -CA / -VIGNETTE (") + pt_last_error() + ")");
         o.optical = o.optics.k1 != 0.0f || o.optics.k2 != 0.0f || o.optics.ca != 0.0f || o.optics.vignette != 0.0f;
     }
-    o.grading = o.tone_flags || o.blooming || o.localising || o.sharpening || o.colouring || o.optical;
+    o.grading = o.tone_flags || o.blooming || o.localising || o.sharpening || o.graining || o.colouring || o.optical;
     // -TONE / -EXPOSURE / -AUTO_EXPOSURE: what every graded image is asked for
     if (o.tone_flags) {
         const char *names[4] = {"reference", "clamp", "reinhard", "aces"};
@@ -537,6 +557,7 @@ struct Run {
     pt_display *display = nullptr;   // -DEVICE_RESOLVE: the display of the frame
     pt_render_params rp{};
     int n_dev = 0;
+    uint32_t frame_index = 0;        // of the image to come in a sequence: the grain's frame
     const char *transport_name = "none";
     clk::time_point t_begin, t_parse, t_hip, t_load;
     double pre_main_s = 0;   // exec + dynamic linking, when the parent told us when it started us
@@ -589,10 +610,16 @@ struct HostFrame {
     uint8_t *image() { return out_bgr.empty() ? bgr.data() : out_bgr.data(); }
 };
 
-// The device path's present: plain, scaled, or either with grading, bloom, local exposure, colour, optics or sharpening
+// The device path's present: plain, scaled, or either with grading, bloom, local exposure, colour, optics, sharpening or grain
 int present(const Run &r, HostFrame &host, pt_display_info *info) {
     const Options &o = r.o;
     const pt_upsample_params *up = o.scale > 1 ? &o.upsample : nullptr;
+    if (o.graining) {
+        pt_grain_params grain = o.grain;
+        grain.frame = r.frame_index;
+        return pt_display_present_grain(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, &o.optics, &o.sharpen, &grain, host.image(),
+                                        info, nullptr);
+    }
     if (o.sharpening)
         return pt_display_present_sharpen(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, &o.optics, &o.sharpen, host.image(), info,
                                           nullptr);
@@ -627,7 +654,7 @@ public:
         moved = true;
         return !view || pt_scene_set_camera(view, &camera) == PT_OK;
     }
-    bool bytes(HostFrame &host, float dispersion[3], ChainTimes &times);
+    bool bytes(HostFrame &host, uint32_t frame_index, float dispersion[3], ChainTimes &times);
 
 private:
     bool features(int w, int h) {   // the first hits of the pinhole view at w x h
@@ -652,7 +679,7 @@ private:
 
 // host.sum / sum2 / count -> host.image(), and the dispersion figures of the frame as rendered (they go into the output's name:
 // neither the history nor any filter changes them).  Every stage appears once, in the chain's order.
-bool HostChain::bytes(HostFrame &host, float dispersion[3], ChainTimes &times) {
+bool HostChain::bytes(HostFrame &host, uint32_t frame_index, float dispersion[3], ChainTimes &times) {
     const int dev = o.devices[0], tw = o.tw, th = o.th;
     const size_t px = host.px;
     const bool denoising = o.denoise.levels > 0, filtering = o.gauss || o.median;
@@ -743,9 +770,15 @@ bool HostChain::bytes(HostFrame &host, float dispersion[3], ChainTimes &times) {
             return false;
         m = rgb.data();
     }
-    pt_tonemap(w, h, m, n, o.gamma_correction, rgb.data());
-    if (filtering && pt_post_filter_host(dev, w, h, rgb.data(), o.gauss, o.median) != PT_OK) return false;
-    if (pt_quantize(w, h, rgb.data(), n, host.image()) != PT_OK) return false;
+    if (o.graining) {   // grain and dithered quantization, in the last three steps' place
+        pt_grain_params grain = o.grain;
+        grain.frame = frame_index;
+        if (pt_grain_quantize(w, h, m, n, o.gamma_correction, &grain, host.image()) != PT_OK) return false;
+    } else {
+        pt_tonemap(w, h, m, n, o.gamma_correction, rgb.data());
+        if (filtering && pt_post_filter_host(dev, w, h, rgb.data(), o.gauss, o.median) != PT_OK) return false;
+        if (pt_quantize(w, h, rgb.data(), n, host.image()) != PT_OK) return false;
+    }
     if (o.scale > 1) {   // the scaled chain is timed as one: the mean, the upsample and what follows it
         times.denoise_s = secs(t_denoise, clk::now());
     } else if (denoising) {   // (the view's clone is part of the features' time)
@@ -782,7 +815,7 @@ int write_outputs(const Options &o, const std::string &name, const uint8_t *imag
 // dispersion figures, where they are wanted, come from the reference's resolve on the host.
 bool make_image(Run &r, HostFrame &host, HostChain &chain, bool want_stats, float dispersion[3], ChainTimes &times) {
     const Options &o = r.o;
-    if (!r.display) return chain.bytes(host, dispersion, times);
+    if (!r.display) return chain.bytes(host, r.frame_index, dispersion, times);
     if (want_stats) pt_resolve(o.tw, o.th, host.sum, host.sum2, host.count, o.gamma_correction, host.bgr.data(), dispersion);
     const clk::time_point a = clk::now();
     pt_display_info shown;
@@ -863,6 +896,7 @@ int run_sequence(Run &r) {
         }
         rp.pass_begin = i * o.rays_per_pixel;
         rp.pass_count = o.rays_per_pixel;
+        r.frame_index = static_cast<uint32_t>(i);
         if (pt_frame_clear(r.frame) != PT_OK || pt_frame_render(r.frame, &rp, nullptr) != PT_OK) return die("pt_render");
         // on the device path only the last frame is also read back, for the statistics in the output's name
         const bool last = i == o.frames - 1;
