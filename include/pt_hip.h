@@ -1216,6 +1216,76 @@ int pt_display_present_grain(pt_display *d, const pt_display_params *p, const pt
                              const pt_optics_params *o, const pt_sharpen_params *s, const pt_grain_params *n, uint8_t *bgr,
                              pt_display_info *info /* may be NULL */, pt_grade_info *grade_info /* may be NULL */);
 
+/* ---- scene-linear output: PFM and Radiance .hdr from the display chain --------------------------------------------- */
+
+/* Every output above is 24-bit bytes behind the display curve.  This stage encodes the LINEAR mean the display kernel would read -- the
+ * image after optics, bloom, local exposure and sharpening, and before the colour matrix, exposure, curve, LUT and grain -- as the body
+ * of a float picture file, on the device where it lies.  It reads that image and writes a buffer of its own: no stage sees what it
+ * wrote, and the bytes of the BMP are the same with and without it.
+ *
+ * The input of a pixel is its mean m = (r, g, b) and its count.  With exposed != 0 every channel is first m * e, ONE float multiply, e
+ * being the exposure the present used (metered or manual); with exposed == 0 it is m, bits untouched.  A pixel with count == 0 is
+ * all-zero bytes in both formats, whatever its mean holds.
+ *
+ * PT_LINEAR_PFM: 12 bytes per pixel, the three floats little-endian r, g, b with their BITS unchanged (NaN payloads, -0, inf and
+ * negatives are kept), rows BOTTOM-UP as PFM has them: the pixel (x, y) of the image lies at byte 12 * ((height - 1 - y) * width + x).
+ * The buffer is the file's body as it stands; pt_write_pfm prepends "PF\n<W> <H>\n-1.0\n" (the negative scale says little-endian).
+ *
+ * PT_LINEAR_RGBE: 4 bytes per pixel R, G, B, E, rows top-down: a FLAT (not run-length encoded) Radiance picture, which pt_write_hdr
+ * gives the header "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y <H> +X <W>\n".  Per pixel, in integer arithmetic, comparisons and one exact
+ * multiply per channel -- no frexp, ldexp or log:
+ *   c'    = (c > 0) ? (c < 2^126 ? c : 2^126) : 0     per channel: NaN, -0 and negatives give 0, +inf gives 2^126
+ *   v     = max(r', g', b');   be = (bits(v) >> 23) & 255
+ *   if (be < 27) the pixel is 0, 0, 0, 0               (v < 2^-100, subnormals among them)
+ *   scale = the float whose bits are (261 - be) << 23  (2^(8 - e) with e = be - 126; its exponent field lies in 8 .. 234: a normal float)
+ *   byte_c = (int)(c' * scale)                         (the product is exact, or below 1 and truncated to 0; it is always below 256)
+ *   E     = be + 2                                     (29 .. 255)
+ * The largest channel's byte lies in 128 .. 255.  This is not Radiance's own m * 256 / v, from which it differs in rare last-step
+ * roundings; what holds for every channel, and what a reader may rely on, is
+ *   | (byte + 0.5) * 2^(E - 136) - c' | <= 2^(E - 137).
+ * Flat scanlines are legal in a Radiance picture, and a reader cannot take one of these pixels for a run-length marker: the marker of the
+ * new encoding is a pixel with R = G = 2 and bit 7 of B clear, and here a pixel with R = G = 2 has its largest byte, at least 128, in B;
+ * the marker of the old one is R = G = B = 1, and no pixel here has all three below 128 unless it is 0, 0, 0, 0.
+ *
+ * format 0 means the stage does not run; any other value than PT_LINEAR_PFM and PT_LINEAR_RGBE is invalid, and so is an exposed other
+ * than 0 or 1.  Any image size from 1 x 1 is valid. */
+#define PT_LINEAR_PFM 1
+#define PT_LINEAR_RGBE 2
+typedef struct pt_linear_params {
+    int32_t format;     /* 0 = stage off, PT_LINEAR_PFM 1, PT_LINEAR_RGBE 2 */
+    int32_t exposed;    /* 0: m as it is; 1: m * e                           */
+} pt_linear_params;
+
+/* The size of the body in bytes: 12 or 4 per pixel.  0 for a format that is neither of the two, or a size that is empty or too large. */
+size_t pt_linear_bytes(int32_t width, int32_t height, int32_t format);
+/* Host only, no device: THE DEFINITION of the bytes.  mean_rgb is the mean (r, g, b per pixel, rows top-down), out has room for
+ * pt_linear_bytes.  `exposure` is read only with exposed != 0.  Checked in this order: NULL buffers and empty sizes, the image size,
+ * *lin (format 1 or 2 -- 0 encodes nothing and is refused here --, exposed 0 or 1), and with exposed != 0 the exposure (finite and > 0). */
+int pt_linear_encode(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure,
+                     const pt_linear_params *lin, uint8_t *out);
+/* The kernel alone on a host image, on HIP device `device`; the bytes are pt_linear_encode's.  Everything is checked, as there, before
+ * the device is looked at; PT_ERR_NO_DEVICE afterwards if that is not a usable device (there is no CPU fallback).  info->kernel_ms is the
+ * HIP-event time of the kernel; deferred_pixels is 0: the kernel finishes every pixel. */
+int pt_linear_encode_device_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure,
+                                 const pt_linear_params *lin, uint8_t *out, pt_display_info *info /* may be NULL */);
+/* pt_display_present_grain with the stage: the same chain, plus one encode kernel on the image the display kernel reads, enqueued
+ * immediately before it inside the timed chain.  ONE present makes both outputs, and a present with a temporal stage pushes the history
+ * exactly once.  `linear` gets pt_linear_bytes at the output size, DEFINED by the host chain: ... -> pt_sharpen_host(e) ->
+ * pt_linear_encode(e).  g may be NULL for a chain with no grade at all (the bytes of pt_display_present / _scaled): then b, l, c, o, s
+ * and n must be NULL too and exposed must be 0, else PT_ERR_INVALID_ARGUMENT.  bgr may be NULL: the display kernel and its copy are
+ * skipped.  *lin is checked with the other blocks, before anything is enqueued and before the device is looked at; a failed present
+ * leaves the history and the previous exposure as they were.  With format 0 `linear` is not written and may be NULL, bgr may not, and
+ * the call is pt_display_present_grain (or, with g NULL, pt_display_present_scaled / pt_display_present). */
+int pt_display_present_linear(pt_display *d, const pt_display_params *p, const pt_upsample_params *u /* NULL: not scaled */,
+                              const pt_grade_params *g, const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c,
+                              const pt_optics_params *o, const pt_sharpen_params *s, const pt_grain_params *n, const pt_linear_params *lin,
+                              uint8_t *bgr /* may be NULL */, uint8_t *linear, pt_display_info *info /* may be NULL */,
+                              pt_grade_info *grade_info /* may be NULL */);
+/* The header stated above, then the body (pt_linear_bytes of it).  PT_ERR_INVALID_ARGUMENT: a NULL pointer, an empty or too large size;
+ * PT_ERR_IO, with the reason in pt_last_error: the file cannot be opened or written. */
+int pt_write_pfm(const char *path, int32_t width, int32_t height, const uint8_t *body);
+int pt_write_hdr(const char *path, int32_t width, int32_t height, const uint8_t *body);
+
 /* main.cpp:179-182 alone, on the host: rgb = pow(mean_rgb, gamma) * 255 per channel for pixels with count != 0, the others keep
  * their value.  With mean_rgb = sum / n it gives the image of pt_resolve_float bit for bit. */
 int pt_tonemap(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float gamma, float *rgb);

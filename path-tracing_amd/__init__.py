@@ -54,7 +54,9 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_display_bytes_colour_host", "pt_display_present_colour",
                "pt_optics_host", "pt_display_present_optics",
                "pt_sharpen_host", "pt_display_present_sharpen",
-               "pt_grain_quantize", "pt_display_bytes_grain_host", "pt_display_present_grain"]
+               "pt_grain_quantize", "pt_display_bytes_grain_host", "pt_display_present_grain",
+               "pt_linear_bytes", "pt_linear_encode", "pt_linear_encode_device_host", "pt_display_present_linear", "pt_write_pfm",
+               "pt_write_hdr"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -334,6 +336,32 @@ def _grain_params(grain):
     return grain
 
 
+class LinearParams(C.Structure):
+    """pt_linear_params: format 0 (no linear output), LINEAR_PFM or LINEAR_RGBE; exposed 1 multiplies the mean by the present's exposure."""
+    _fields_ = [("format", C.c_int32), ("exposed", C.c_int32)]
+
+
+LINEAR_PFM, LINEAR_RGBE = 1, 2
+LINEAR_FORMATS = {"pfm": LINEAR_PFM, "hdr": LINEAR_RGBE}
+
+
+def _linear_params(linear=None, format=None, exposed=False):
+    """A LinearParams from one, from a dict of its fields ({"format": "hdr", "exposed": False}), or from the two values; a format may
+    be "pfm", "hdr" or the number the library is to judge."""
+    if isinstance(linear, LinearParams):
+        return linear
+    if isinstance(linear, dict):
+        unknown = set(linear) - {"format", "exposed"}
+        if unknown:
+            raise ValueError(f"linear: unknown fields {sorted(unknown)}")
+        format, exposed = linear.get("format", "pfm"), linear.get("exposed", False)
+    if isinstance(format, str):
+        if format not in LINEAR_FORMATS:
+            raise ValueError(f"linear: format must be one of {sorted(LINEAR_FORMATS)}")
+        format = LINEAR_FORMATS[format]
+    return LinearParams(int(format), int(exposed))
+
+
 def _optics_params(optics):
     """An OpticsParams, or a dict of its fields ({"k1": -0.1, "ca": 0.01, "vignette": 1.0}) -> an OpticsParams."""
     if isinstance(optics, dict):
@@ -525,6 +553,16 @@ def load_library(path):
     L.pt_display_present_grain.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
                                            C.POINTER(LocalParams), cp, C.POINTER(OpticsParams), C.POINTER(SharpenParams), C.POINTER(GrainParams), bp,
                                            C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    lin = C.POINTER(LinearParams)
+    L.pt_linear_bytes.restype = C.c_size_t
+    L.pt_linear_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.pt_linear_encode.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, lin, bp]
+    L.pt_linear_encode_device_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, ip, C.c_float, lin, bp, C.POINTER(DisplayInfo)]
+    L.pt_display_present_linear.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(UpsampleParams), C.POINTER(GradeParams), C.POINTER(BloomParams),
+                                            C.POINTER(LocalParams), cp, C.POINTER(OpticsParams), C.POINTER(SharpenParams), C.POINTER(GrainParams), lin,
+                                            bp, bp, C.POINTER(DisplayInfo), C.POINTER(GradeInfo)]
+    L.pt_write_pfm.argtypes = [C.c_char_p, C.c_int32, C.c_int32, bp]
+    L.pt_write_hdr.argtypes = [C.c_char_p, C.c_int32, C.c_int32, bp]
     if hasattr(L, "pt_test_set_mutation"):
         L.pt_test_set_mutation.argtypes = [C.c_char_p, C.c_double]
     if hasattr(L, "pt_test_live_device_objects"):
@@ -874,7 +912,7 @@ class Display:
         _check(create(session_or_frame._h, eps, C.byref(self._h)), self._L)
 
     def present(self, gamma=None, temporal=None, denoise=None, upsample=None, grade=None, bloom=None, local=None, colour=None, optics=None,
-                sharpen=None, grain=None):
+                sharpen=None, grain=None, linear=None, want_bgr=True):
         """pt_display_present.  `temporal`: None (no temporal stage), True, a TemporalParams, or a dict of Temporal.push's
         parameters (max_frames, sigma_plane, min_normal_dot); `denoise`: None, a DenoiseParams, or a dict of pt.denoise's
         parameters.  Returns (bgr uint8 [H, W, 3], info dict).
@@ -895,7 +933,11 @@ class Display:
         contrast-adaptive sharpen of the luminance after local exposure and before the grade (the other stages None: zeroed).
         `grain`: None, a GrainParams, or a dict of its fields ({"strength": 0.2, "size": 1.5, "dither": 1.0, "seed": 7, "frame": 0}) --
         pt_display_present_grain: film grain on the graded value and a triangular dither of its level, inside the display kernel (the
-        other stages None: zeroed); advance `frame` once per presented frame."""
+        other stages None: zeroed); advance `frame` once per presented frame.
+        `linear`: None, a LinearParams, or a dict {"format": "pfm" | "hdr", "exposed": False} -- pt_display_present_linear: the same
+        present also encodes the linear mean the display kernel reads; info["linear"] then holds the body as bytes (pt.write_pfm /
+        pt.write_hdr make a file of it).  With every grading stage None the chain has no grade at all.  `want_bgr` False (with
+        `linear` only) leaves the display kernel out: the image returned is None."""
         if gamma is None:
             gamma = np.float32(1) / np.float32(2.2)   # config.h:25
         if isinstance(temporal, dict):
@@ -904,6 +946,29 @@ class Display:
         prm = DisplayParams(gamma, 1 if on else 0, temporal if isinstance(temporal, TemporalParams) else TemporalParams(),
                             _denoise_params(denoise))
         info = DisplayInfo()
+        if linear is not None:
+            graded = any(x is not None for x in (grade, bloom, local, colour, optics, sharpen, grain))
+            up = _upsample_params(upsample) if upsample is not None else None
+            k = up.scale if up is not None and 1 <= up.scale <= UPSAMPLE_MAX_SCALE else 1
+            bgr = np.zeros((k * self.height, k * self.width, 3), np.uint8) if want_bgr else None
+            lin, ginfo = _linear_params(linear), GradeInfo()
+            body = np.zeros(12 * k * k * self.height * self.width, np.uint8)   # (room for either format, whatever the library makes of *lin)
+            stages = [None] * 7
+            if graded:
+                stages = [_grade_params(grade) if grade is not None else GradeParams(), _bloom_params(bloom) if bloom is not None else BloomParams(),
+                          _local_params(local) if local is not None else LocalParams(), _colour_params(colour) if colour is not None else ColourParams(),
+                          _optics_params(optics) if optics is not None else OpticsParams(), _sharpen_params(sharpen) if sharpen is not None else SharpenParams(),
+                          _grain_params(grain) if grain is not None else GrainParams()]
+            u8 = C.POINTER(C.c_uint8)
+            _check(self._L.pt_display_present_linear(self._h, C.byref(prm), C.byref(up) if up is not None else None,
+                                                     *[C.byref(x) if x is not None else None for x in stages], C.byref(lin),
+                                                     bgr.ctypes.data_as(u8) if want_bgr else None, body.ctypes.data_as(u8), C.byref(info),
+                                                     C.byref(ginfo)), self._L)
+            size = self._L.pt_linear_bytes(k * self.width, k * self.height, lin.format)
+            out = dict(info.as_dict(), linear=body[:size].tobytes())
+            return bgr, dict(out, **ginfo.as_dict()) if graded else out
+        if not want_bgr:
+            raise ValueError("present: want_bgr=False needs linear=")
         if grade is not None or bloom is not None or local is not None or colour is not None or optics is not None or sharpen is not None or \
                 grain is not None:
             gp, ginfo = _grade_params(grade) if grade is not None else GradeParams(), GradeInfo()
@@ -1169,6 +1234,50 @@ def display_bytes_grain(mean_rgb, count, grade, colour, grain, gamma=None, e_pre
                                          0 if e_prev is None else 1, C.c_float(0.0 if e_prev is None else e_prev),
                                          bgr.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info), C.byref(ginfo)), L)
     return bgr, dict(info.as_dict(), **ginfo.as_dict())
+
+
+def linear_encode(mean_rgb, count, exposure=1.0, format="pfm", exposed=False, library=None):
+    """pt_linear_encode (host only): the body of a PFM ("pfm": 12 bytes per pixel, rows bottom-up) or of a flat Radiance picture ("hdr":
+    4 bytes per pixel R, G, B, E) from the linear mean mean_rgb [H, W, 3] with count [H, W]; with `exposed` every channel is multiplied
+    by `exposure` first.  Returns bytes."""
+    L = library or lib()
+    m, c = _image_args("linear_encode", mean_rgb, count)
+    prm = _linear_params(None, format, exposed)
+    out = np.zeros(12 * m.shape[0] * m.shape[1], np.uint8)
+    _check(L.pt_linear_encode(m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), C.byref(prm), out.ctypes.data_as(C.POINTER(C.c_uint8))), L)
+    return out[:L.pt_linear_bytes(m.shape[1], m.shape[0], prm.format)].tobytes()
+
+
+def linear_encode_device(device, mean_rgb, count, exposure=1.0, format="pfm", exposed=False, want_info=False, library=None):
+    """pt_linear_encode_device_host: the encode kernel alone on a host image; the bytes are pt.linear_encode's.  Returns bytes (and the
+    info dict with `want_info`)."""
+    L = library or lib()
+    m, c = _image_args("linear_encode_device", mean_rgb, count)
+    prm = _linear_params(None, format, exposed)
+    out = np.zeros(12 * m.shape[0] * m.shape[1], np.uint8)
+    info = DisplayInfo()
+    _check(L.pt_linear_encode_device_host(device, m.shape[1], m.shape[0], _fp(m), _ip(c), C.c_float(exposure), C.byref(prm),
+                                          out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)), L)
+    body = out[:L.pt_linear_bytes(m.shape[1], m.shape[0], prm.format)].tobytes()
+    return (body, info.as_dict()) if want_info else body
+
+
+def _write_linear(name, path, width, height, body, format, library):
+    L = library or lib()
+    b = np.frombuffer(bytes(body), np.uint8)
+    if b.size != L.pt_linear_bytes(width, height, format):
+        raise ValueError(f"{name}: the body does not hold width x height pixels")
+    _check(getattr(L, name)(os.fsencode(path), width, height, b.ctypes.data_as(C.POINTER(C.c_uint8))), L)
+
+
+def write_pfm(path, width, height, body, library=None):
+    """pt_write_pfm: "PF", the size and the scale -1.0 (little-endian), then the body pt.linear_encode(format="pfm") made."""
+    _write_linear("pt_write_pfm", path, width, height, body, LINEAR_PFM, library)
+
+
+def write_hdr(path, width, height, body, library=None):
+    """pt_write_hdr: the header of a flat Radiance picture, then the body pt.linear_encode(format="hdr") made."""
+    _write_linear("pt_write_hdr", path, width, height, body, LINEAR_RGBE, library)
 
 
 def display_table(gamma, library=None):

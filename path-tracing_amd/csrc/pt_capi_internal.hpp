@@ -1,6 +1,6 @@
 // What the translation units behind the C ABI share (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters; pt_frame.cpp: the
 // multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
-// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp, pt_sharpen_capi.cpp: one image-space stage each; pt_grain_capi.cpp: grain and dither, the host chain's last step; pt_display_capi.cpp: the device-resident
+// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp, pt_sharpen_capi.cpp: one image-space stage each; pt_grain_capi.cpp: grain and dither, the host chain's last step; pt_linear_capi.cpp: scene-linear output; pt_display_capi.cpp: the device-resident
 // display path, which chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
 // arguments, the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments, and the timed region
 // of a one-shot entry point.
@@ -24,6 +24,7 @@
 #include "pt_grade.hpp"
 #include "pt_grain.hpp"
 #include "pt_kernels.hpp"
+#include "pt_linear.hpp"
 #include "pt_local.hpp"
 #include "pt_meter.hpp"
 #include "pt_optics.hpp"
@@ -292,6 +293,18 @@ std::shared_ptr<const DisplayTable> display_table(float gamma);
 // per channel the dithered level of a value the table covers, and the host's own tone map and truncation of any other.
 void grain_pixel_bytes(const pt::GrainStep &s, const DisplayTable &table, float gamma, uint32_t x, uint32_t y, const float *g, uint8_t *rgb);
 
+// pt_linear_params as every entry point checks them (no device is touched) (pt_linear_capi.cpp).
+struct LinearSetup {
+    bool on = false;          // format != 0: the stage runs
+    int format = 0;           // PT_LINEAR_PFM or PT_LINEAR_RGBE
+    bool exposed = false;
+};
+int linear_params_check(const pt_linear_params *lin, LinearSetup &out);
+// What pt_linear_encode and pt_linear_encode_device_host check, in the order pt_hip.h states: buffers and sizes, the image size, *lin
+// (which must name a format), the exposure where it is used.
+int linear_image_check(int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure, const pt_linear_params *lin,
+                       const uint8_t *out, LinearSetup &setup);
+
 // The image a chain has reached: planes on the device, sums still (divide) or means, and its size.
 struct Image { const float *rgb; const int32_t *count; bool divide; int32_t width, height; };
 // One image-space stage's launch arguments -- the only place each of these structs is filled: its checked parameters, the image it
@@ -326,6 +339,12 @@ inline pt::SharpenArgs sharpen_args(const SharpenSetup &s, const Image &in, cons
     pt::SharpenArgs a;
     a.width = in.width; a.height = in.height; a.divide = in.divide ? 1 : 0; a.rgb = in.rgb; a.count = in.count; a.exposure = exposure;
     a.strength = s.strength; a.limit = s.limit; a.luma = w.luma; a.out_rgb = out_rgb;
+    return a;
+}
+inline pt::LinearArgs linear_args(const LinearSetup &s, const Image &in, const float *exposure, uint32_t *out) {
+    pt::LinearArgs a;
+    a.width = in.width; a.height = in.height; a.divide = in.divide ? 1 : 0; a.format = s.format; a.exposed = s.exposed ? 1 : 0;
+    a.rgb = in.rgb; a.count = in.count; a.exposure = exposure; a.out = out;
     return a;
 }
 

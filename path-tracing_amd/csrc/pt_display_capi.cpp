@@ -12,6 +12,8 @@
 // kernel, in place on the plane of means a stage of the display's wrote, or from the chain's image into a plane of the display's.
 // With grain or dither (pt_display_present_grain): the grain display kernel in the graded or the colour one's place, and deferred pixels
 // finished with pt_grain.hpp from their index, the seed and the frame.
+// With scene-linear output (pt_display_present_linear): the encode kernel (pt_linear.hip) immediately ahead of the display kernel, on the
+// image that one reads, into a buffer of the display's that one more copy brings to the host.
 #include "pt_capi_internal.hpp"
 
 #include <algorithm>
@@ -98,6 +100,18 @@ void finish_on_host(const std::vector<pt::DisplayDeferred> &list, float gamma, c
         for (int k = 0; k < 3; ++k) bgr[3 * p + k] = ptc::quantize_value(ptc::tonemap_value(v[2 - k], gamma));
     }
 }
+// Where scene-linear output goes on the device: the body, padded to the whole 16-byte groups the kernel writes (PFM's 12 bytes per pixel
+// hold either format).
+struct LinearPlane {
+    uint32_t *out = nullptr;
+    size_t offset = 0;
+    static LinearPlane in(ptc::PlaneLayout &l, size_t n) {
+        LinearPlane w;
+        w.offset = l.add(pt::linear_room(n, pt::kLinearPfm));
+        return w;
+    }
+    void bind(const ptc::DeviceBuffer &b) { out = b.at<uint32_t>(offset); }
+};
 // What collect brings back besides the bytes (used: of a graded image).
 struct Presented { int32_t n_deferred = 0; pt_grade_info used{}; };
 
@@ -131,6 +145,9 @@ struct DisplayDevice {
     // plane of sharpened means; allocated by the first present with the stage
     ptc::DeviceBuffer d_sharpen;
     ptc::SharpenPlanes sharpen;
+    // scene-linear output: the encoded body, allocated by the first present with the stage
+    ptc::DeviceBuffer d_linear;
+    LinearPlane linear;
 
     int alloc(size_t pixels, const char *what) {
         n = pixels;
@@ -138,6 +155,7 @@ struct DisplayDevice {
         d_local.reset();
         d_optics.reset();
         d_sharpen.reset();
+        d_linear.reset();
         ptc::PlaneLayout l;
         const size_t o_bgr = l.add((n + 3) / 4 * 12), o_list = l.add(16 * n), o_len = l.add(4);
         const size_t o_grade = l.add(kGradeBytes);
@@ -169,6 +187,7 @@ struct DisplayDevice {
         if (d_sharpen && own_mean && !sharpen.own_mean) d_sharpen.reset();   // (made by a chain that needed the luminance alone)
         return ensure(d_sharpen, sharpen, what, n, own_mean);
     }
+    int ensure_linear(const char *what) { return ensure(d_linear, linear, what, n); }
     // (no kernel of this object is in flight: every call that launches one waits for it)
     int use_lut(const pt_lut *lut, const char *what) {
         if (lut_generation == lut->generation) return PT_OK;
@@ -209,8 +228,9 @@ struct DisplayDevice {
     }
     // Zero the list's length and launch the kernel on `stream`; with `grade`, the stages ahead of the graded or the colour kernel first, each
     // on the image the one before it left: the lens, the exposure (metered from the image, or the manual one), bloom, local exposure,
-    // sharpening.
-    int enqueue(ptc::Image image, hipStream_t stream, const GradeRequest *grade) {
+    // sharpening.  With `lin` on, the encode of the image these leave goes immediately ahead of the display kernel; without `want_bgr`
+    // that one is left out.
+    int enqueue(ptc::Image image, hipStream_t stream, const GradeRequest *grade, const ptc::LinearSetup *lin = nullptr, bool want_bgr = true) {
         PT_HIP_TRY(hipMemsetAsync(n_deferred, 0, 4, stream));
         if (grade && grade->optics.on) {   // the meter and everything behind it read mean' and count'
             const auto o = ptc::optics_args(grade->optics, image, optics_out);
@@ -243,6 +263,11 @@ struct DisplayDevice {
             PT_HIP_TRY(pt::launch_sharpen(s, stream));
             image.rgb = out; image.divide = false;
         }
+        if (lin && lin->on) {   // (without a grade nothing wrote an exposure, and `exposed` was refused)
+            const auto e = ptc::linear_args(*lin, image, grade ? &exposure->exposure : nullptr, linear.out);
+            PT_HIP_TRY(pt::launch_linear_encode(e, stream));
+        }
+        if (!want_bgr) return PT_OK;
         pt::DisplayArgs a;
         a.n = static_cast<int>(n);
         a.divide = image.divide ? 1 : 0;
@@ -268,8 +293,10 @@ struct DisplayDevice {
         return PT_OK;
     }
     // The kernel has finished: 3 bytes per pixel and the deferred list come to the host, which finishes the list's pixels.
-    int collect(float gamma, uint8_t *out, const GradeRequest *grade, Presented &got) {
-        PT_HIP_TRY(hipMemcpy(out, bgr, 3 * n, hipMemcpyDeviceToHost));
+    // `out` NULL: no display kernel ran.  With `lin` on, the encoded body comes to `linear_out` as it stands.
+    int collect(float gamma, uint8_t *out, const GradeRequest *grade, Presented &got, const ptc::LinearSetup *lin = nullptr, uint8_t *linear_out = nullptr) {
+        if (lin && lin->on) PT_HIP_TRY(hipMemcpy(linear_out, linear.out, (lin->format == pt::kLinearPfm ? 12 : 4) * n, hipMemcpyDeviceToHost));
+        if (out) PT_HIP_TRY(hipMemcpy(out, bgr, 3 * n, hipMemcpyDeviceToHost));
         if (grade) {
             pt::ExposureOut o;
             PT_HIP_TRY(hipMemcpy(&o, exposure, sizeof o, hipMemcpyDeviceToHost));
@@ -277,6 +304,7 @@ struct DisplayDevice {
             got.used.target = grade->setup.automatic ? o.target : o.exposure;
             got.used.metered = o.metered; got.used.dark = o.dark;
         }
+        if (!out) return PT_OK;
         uint32_t len = 0;
         PT_HIP_TRY(hipMemcpy(&len, n_deferred, 4, hipMemcpyDeviceToHost));
         if (len > n) return fail(PT_ERR_HIP, "display: the deferred list is longer than the image");
@@ -401,12 +429,14 @@ struct PresentRequest {
     const pt_optics_params *optics = nullptr;
     const pt_sharpen_params *sharpen = nullptr;
     const pt_grain_params *grain = nullptr;
+    const pt_linear_params *linear = nullptr;       // with or without grade; its body goes to linear_out
+    uint8_t *linear_out = nullptr;
 };
 
 int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, pt_display_info *info) {
     const pt_display_params *p = rq.display;
     const pt_upsample_params *u = rq.upsample;
-    if (!d || !p || !bgr) return null_argument();
+    if (!d || !p) return null_argument();
     const bool scaled = u != nullptr, graded = rq.grade != nullptr;
     int rc = check_gamma(p->gamma);
     if (rc != PT_OK) return rc;
@@ -418,6 +448,10 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (rq.optics && (rc = ptc::optics_params_check(rq.optics, grade.optics)) != PT_OK) return rc;
     if (rq.sharpen && (rc = ptc::sharpen_params_check(rq.sharpen, grade.sharpen)) != PT_OK) return rc;
     if (rq.grain && (rc = ptc::grain_params_check(rq.grain, grade.grain)) != PT_OK) return rc;
+    ptc::LinearSetup lin;
+    if (rq.linear && (rc = ptc::linear_params_check(rq.linear, lin)) != PT_OK) return rc;
+    if (lin.exposed && !graded) return fail(PT_ERR_INVALID_ARGUMENT, "linear: exposed needs a grade: a chain without one has no exposure");
+    if (lin.on ? !rq.linear_out : !bgr) return null_argument();   // (bgr may be NULL where there is a linear body to make)
     pt::UpsampleArgs ua;
     if (scaled) {
         if (u->scale < pt::kUpsampleMinScale || u->scale > pt::kUpsampleMaxScale) return fail(PT_ERR_INVALID_ARGUMENT, "upsample: scale must be 2, 3 or 4");
@@ -451,6 +485,7 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
     if (grade.colour.lut && (rc = dev.use_lut(grade.colour.lut, "pt_display_present_colour")) != PT_OK) return rc;
     if (grade.optics.on && (rc = dev.ensure_optics("pt_display_present_optics")) != PT_OK) return rc;
     if (grade.sharpen.on && (rc = dev.ensure_sharpen(grade.sharpen_own_mean(), "pt_display_present_sharpen")) != PT_OK) return rc;
+    if (lin.on && (rc = dev.ensure_linear("pt_display_present_linear")) != PT_OK) return rc;
     if (temporal && !d->history && (rc = pt_temporal_create(scene, d->width, d->height, d->eps, &d->history)) != PT_OK) return rc;
     if (filter && !temporal && (rc = ensure_filter(d)) != PT_OK) return rc;
     {   // the chain, behind every slice enqueued so far: no host synchronisation until its last kernel is in the queue
@@ -486,14 +521,14 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
             PT_HIP_TRY(pt::launch_upsample(ua, stream));
             image = {d->up_out.rgb, d->up_out.count, false, ua.width, ua.height};
         }
-        if ((rc = dev.enqueue(image, stream, graded ? &grade : nullptr)) != PT_OK) return rc;
+        if ((rc = dev.enqueue(image, stream, graded ? &grade : nullptr, &lin, bgr != nullptr)) != PT_OK) return rc;
         PT_HIP_TRY(d->timer.end(stream));
     }
     // (an error return from here on leaves the history and the metered exposure as they were: they were only read)
     float ms = 0.0f;
     PT_HIP_TRY(d->timer.wait_ms(&ms));
     Presented got;
-    if ((rc = dev.collect(p->gamma, bgr, graded ? &grade : nullptr, got)) != PT_OK) return rc;
+    if ((rc = dev.collect(p->gamma, bgr, graded ? &grade : nullptr, got, &lin, rq.linear_out)) != PT_OK) return rc;
     if (temporal) ptc::temporal_commit(d->history);
     if (graded && grade.setup.automatic) {
         d->has_exposure = true;
@@ -547,6 +582,37 @@ int display_bytes_host_impl(const HostImage &image, float gamma, const HostGrade
     if ((rc = dev.collect(gamma, bgr, g ? &grade : nullptr, got)) != PT_OK) return rc;
     if (g && g->info) *g->info = got.used;
     dev.fill(info, ms, got);
+    return PT_OK;
+}
+
+// The encode kernel alone on a host image (pt_linear_encode_device_host).
+int linear_encode_device_host_impl(const HostImage &image, float exposure, const pt_linear_params *lin, uint8_t *out, pt_display_info *info) {
+    ptc::LinearSetup setup;
+    int rc = ptc::linear_image_check(image.width, image.height, image.mean_rgb, image.count, exposure, lin, out, setup);
+    if (rc != PT_OK || (rc = ptc::use_device(image.device, "linear")) != PT_OK) return rc;
+    const size_t n = static_cast<size_t>(image.width) * image.height;
+    ptc::PlaneLayout l;
+    ptc::MeanPlanes in = ptc::MeanPlanes::in(l, n);
+    LinearPlane body = LinearPlane::in(l, n);
+    const size_t o_e = l.add(4);
+    ptc::DeviceBuffer d_in;
+    if ((rc = d_in.alloc(l, "pt_linear_encode_device_host")) != PT_OK) return rc;
+    in.bind(d_in); body.bind(d_in);
+    float *e = d_in.at<float>(o_e);
+    if ((rc = in.upload(image.mean_rgb, image.count)) != PT_OK) return rc;
+    PT_HIP_TRY(hipMemcpy(e, &exposure, 4, hipMemcpyHostToDevice));
+    float ms = 0.0f;
+    rc = ptc::timed(nullptr, "pt_linear_encode_device_host", &ms, [&] {
+        const auto a = ptc::linear_args(setup, {in.rgb, in.count, false, image.width, image.height}, e, body.out);
+        PT_HIP_TRY(pt::launch_linear_encode(a, nullptr));
+        return static_cast<int>(PT_OK);
+    });
+    if (rc != PT_OK) return rc;
+    PT_HIP_TRY(hipMemcpy(out, body.out, pt_linear_bytes(image.width, image.height, setup.format), hipMemcpyDeviceToHost));
+    if (info) {
+        *info = pt_display_info{};
+        info->kernel_ms = ms;   // (no pixel is deferred, and the kernel searches no table)
+    }
     return PT_OK;
 }
 
@@ -670,6 +736,18 @@ int pt_display_present_grain(pt_display *d, const pt_display_params *p, const pt
     return present(d, g && b && l && c && o && s && n, rq, bgr, info);
 }
 
+int pt_display_present_linear(pt_display *d, const pt_display_params *p, const pt_upsample_params *u, const pt_grade_params *g,
+                              const pt_bloom_params *b, const pt_local_params *l, const pt_colour_params *c, const pt_optics_params *o,
+                              const pt_sharpen_params *s, const pt_grain_params *n, const pt_linear_params *lin, uint8_t *bgr, uint8_t *linear,
+                              pt_display_info *info, pt_grade_info *grade_info) {
+    PresentRequest rq;
+    rq.display = p; rq.upsample = u; rq.grade = g; rq.grade_info = grade_info; rq.bloom = b; rq.local = l; rq.colour = c; rq.optics = o;
+    rq.sharpen = s; rq.grain = n; rq.linear = lin; rq.linear_out = linear;
+    // every stage of the graded chain, or -- a chain with no grade at all -- none of them
+    const bool complete = lin && (g ? b && l && c && o && s && n : !b && !l && !c && !o && !s && !n);
+    return present(d, complete, rq, bgr, info);
+}
+
 int pt_display_reset(pt_display *d) {
     return guarded([&] {
         if (!d) return fail(PT_ERR_INVALID_ARGUMENT, "null handle");
@@ -716,6 +794,11 @@ int pt_display_bytes_grain_host(int device, int32_t width, int32_t height, const
         const HostGrade grade = {g, has_prev != 0, e_prev, grade_info, c, n};
         return display_bytes_host_impl({device, width, height, mean_rgb, count}, gamma, &grade, bgr, info);
     });
+}
+
+int pt_linear_encode_device_host(int device, int32_t width, int32_t height, const float *mean_rgb, const int32_t *count, float exposure,
+                                 const pt_linear_params *lin, uint8_t *out, pt_display_info *info) {
+    return guarded([&] { return linear_encode_device_host_impl({device, width, height, mean_rgb, count}, exposure, lin, out, info); });
 }
 
 int pt_display_table(float gamma, int32_t *levels, float *thresholds, float *doubt_lo, float *doubt_hi) {

@@ -111,6 +111,15 @@
 // (the frame's index).  It is the chain's last step, in the place of the tone map and the quantization (alone it runs with the zeroed
 // grade); black, clipped white and emitters keep their bytes under grain.  It works on the host path and with -DEVICE_RESOLVE 1, with
 // byte-identical files, and with every flag grading works with, but not with -GAUSS / -MEDIAN.  Without -GRAIN and -DITHER nothing changes.
+// Scene-linear output (pt_linear_encode, pt_display_present_linear, not in the reference): -LINEAR_OUT <file.pfm | file.hdr> also writes
+// the LINEAR mean of the final image -- after optics, bloom, local exposure and sharpening, before the colour stage, the exposure, the
+// curve and the grain -- as a PFM (three floats per pixel) or a flat Radiance picture (RGBE); the extension picks the format and any
+// other is refused.  -LINEAR_EXPOSED 1 multiplies it by the exposure the grade used (metered or -EXPOSURE) and needs one of the flags
+// that make a grade.  The file goes beside the final BMP, never beside a preview; in a -FRAMES sequence every frame_%04d.bmp has its
+// frame_%04d.pfm / .hdr too.  -GAUSS / -MEDIAN act behind the tone map and do not touch it.  It works on the host path and with
+// -DEVICE_RESOLVE 1, with byte-identical files; the BMPs are those of a run without the flag.  PT_RENDER_PRINT_CONFIG=1 prints
+// linear_out, linear_format and linear_exposed behind the reference's fields when the flags are given.  Without -LINEAR_OUT nothing
+// changes.
 // The image chain is stated once, in HostChain::bytes, in the order the paragraphs above give: temporal merge -> first-hit
 // features and denoise (else sum / n where a mean is needed) -> upsample to the written size -> optics -> meter, bloom, local exposure, sharpening, colour / grade -> tone map
 // -> -GAUSS / -MEDIAN -> quantize (or grain and dithered quantization in the last three's place).  A single frame and every frame of a sequence go through it; with -DEVICE_RESOLVE 1 the
@@ -171,6 +180,9 @@ struct Options {
     pt_lut *lut = nullptr;
     std::string distortion, ca, vignette;   // -DISTORTION, -CA, -VIGNETTE as given
     pt_optics_params optics{};     // what they make
+    std::string linear_out;        // -LINEAR_OUT as given
+    int linear_exposed = 0;        // -LINEAR_EXPOSED as given
+    pt_linear_params linear{};     // what they make; format 0 without -LINEAR_OUT
     pt_upsample_params upsample{};
     pt_grade_params grade{};       // zeroed without -TONE / -EXPOSURE / -AUTO_EXPOSURE: the reference's bytes
     pt_display_params show{};      // what a present of the device path is asked for
@@ -278,6 +290,8 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-DISTORTION") o.distortion = v;
         if (f == "-CA") o.ca = v;
         if (f == "-VIGNETTE") o.vignette = v;
+        if (f == "-LINEAR_OUT") o.linear_out = v;
+        if (f == "-LINEAR_EXPOSED") o.linear_exposed = std::atoi(v);
     }
 }
 
@@ -373,7 +387,19 @@ bool shutter_poses(Options &o) {
 int configure(int argc, char **argv, Options &o) {
     parse(argc, argv, o);
     o.rng_seed = o.seed < 0 ? static_cast<unsigned>(std::time(nullptr)) : static_cast<unsigned>(o.seed);
-    if (std::getenv("PT_RENDER_PRINT_CONFIG")) {   // tests/test_ref_parts.py: the parsed Config fields, as the reference's own parser is asked for them
+    // -LINEAR_OUT: the extension is the format
+    if (!o.linear_out.empty()) {
+        const size_t dot = o.linear_out.rfind('.');
+        const std::string ext = dot == std::string::npos ? "" : o.linear_out.substr(dot);
+        o.linear.format = ext == ".pfm" ? PT_LINEAR_PFM : ext == ".hdr" ? PT_LINEAR_RGBE : 0;
+        if (!o.linear.format || dot == 0) return refuse(2, "-LINEAR_OUT takes a file name that ends in .pfm or .hdr");
+    }
+    if (o.linear_exposed != 0 && o.linear_exposed != 1) return refuse(2, "-LINEAR_EXPOSED takes 0 or 1");
+    if (o.linear_exposed && o.linear_out.empty()) return refuse(2, "-LINEAR_EXPOSED needs -LINEAR_OUT");
+    o.linear.exposed = o.linear_exposed;
+    // with the linear flags the printout waits for every refusal below: the ones that depend on the other flags are among them
+    const bool print_config = std::getenv("PT_RENDER_PRINT_CONFIG") != nullptr;
+    if (print_config && o.linear_out.empty()) {   // tests/test_ref_parts.py: the parsed Config fields, as the reference's own parser is asked for them
         std::printf("height %d\nwidth %d\nrays_per_pixel %d\nmax_ray_reflections %d\nmedian %d\ngauss %d\neps %.9g\nerror %.9g\nupdate %d\n"
                     "gamma_correction %.9g\nmodel_path %s\nmodel_name %s\nskybox %s\ntime_limit %d\nseed %u\n",
                     o.height, o.width, o.rays_per_pixel, o.max_ray_reflections, o.median, o.gauss, static_cast<double>(o.eps),
@@ -400,7 +426,7 @@ int configure(int argc, char **argv, Options &o) {
         return refuse(2, "-SHUTTER takes the open fraction of a frame interval, 0 .. 1");
     const bool travels = !o.eye_end.empty() || !o.lookat_end.empty();
     o.blurring = o.shutter > 0.0f && travels;
-    if (std::getenv("PT_RENDER_PRINT_CAMERA")) {
+    if (!print_config && std::getenv("PT_RENDER_PRINT_CAMERA")) {
         if (!o.camera) {
             std::printf("camera none\n");
         } else {
@@ -520,6 +546,18 @@ int configure(int argc, char **argv, Options &o) {
             return refuse(2, "-EYE / -EYE_END / -LOOKAT / -LOOKAT_END / -UP take three comma-separated numbers, x,y,z");
         o.moving = o.sequence && (o.camera || travels);
     }
+    if (o.linear.exposed && !o.grading)
+        return refuse(2, "-LINEAR_EXPOSED needs a grade (-TONE, -EXPOSURE, -AUTO_EXPOSURE or a stage that runs with one): without one there is no exposure");
+    if (print_config) {   // the reference's fields, then the linear output's
+        std::printf("height %d\nwidth %d\nrays_per_pixel %d\nmax_ray_reflections %d\nmedian %d\ngauss %d\neps %.9g\nerror %.9g\nupdate %d\n"
+                    "gamma_correction %.9g\nmodel_path %s\nmodel_name %s\nskybox %s\ntime_limit %d\nseed %u\n"
+                    "linear_out %s\nlinear_format %s\nlinear_exposed %d\n",
+                    o.height, o.width, o.rays_per_pixel, o.max_ray_reflections, o.median, o.gauss, static_cast<double>(o.eps),
+                    static_cast<double>(o.error), o.update, static_cast<double>(o.gamma_correction), o.model_path.c_str(),
+                    o.model_name.c_str(), o.skybox.c_str(), o.time_limit, o.rng_seed, o.linear_out.c_str(),
+                    o.linear.format == PT_LINEAR_PFM ? "pfm" : "hdr", o.linear.exposed);
+        return 0;
+    }
     return -1;
 }
 
@@ -578,9 +616,11 @@ struct HostFrame {
     int32_t *count = nullptr;
     std::vector<uint8_t> bgr;      // the traced frame's bytes: previews, the dispersion resolve, the unscaled image
     std::vector<uint8_t> out_bgr;  // -RENDER_SCALE s > 1: the written image
+    std::vector<uint8_t> linear;   // -LINEAR_OUT: the body of the written image's linear file
     double alloc_s = 0, read_s = 0;
     explicit HostFrame(const Options &o) : px(static_cast<size_t>(o.tw) * o.th) {
         if (o.scale > 1) out_bgr.resize(3 * static_cast<size_t>(o.width) * o.height);
+        linear.resize(pt_linear_bytes(o.width, o.height, o.linear.format));   // (nothing without -LINEAR_OUT)
     }
     HostFrame(const HostFrame &) = delete;
     ~HostFrame() {
@@ -614,6 +654,15 @@ struct HostFrame {
 int present(const Run &r, HostFrame &host, pt_display_info *info) {
     const Options &o = r.o;
     const pt_upsample_params *up = o.scale > 1 ? &o.upsample : nullptr;
+    if (o.linear.format) {   // one present makes the bytes and the linear body: the history is pushed once
+        pt_grain_params grain = o.grain;
+        grain.frame = r.frame_index;
+        if (o.grading)
+            return pt_display_present_linear(r.display, &o.show, up, &o.grade, &o.bloom, &o.local, &o.colour, &o.optics, &o.sharpen, &grain, &o.linear,
+                                             host.image(), host.linear.data(), info, nullptr);
+        return pt_display_present_linear(r.display, &o.show, up, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &o.linear,
+                                         host.image(), host.linear.data(), info, nullptr);
+    }
     if (o.graining) {
         pt_grain_params grain = o.grain;
         grain.frame = r.frame_index;
@@ -683,7 +732,7 @@ bool HostChain::bytes(HostFrame &host, uint32_t frame_index, float dispersion[3]
     const int dev = o.devices[0], tw = o.tw, th = o.th;
     const size_t px = host.px;
     const bool denoising = o.denoise.levels > 0, filtering = o.gauss || o.median;
-    const bool need_mean = denoising || o.scale > 1 || o.grading;   // else the reference's resolve does the whole image
+    const bool need_mean = denoising || o.scale > 1 || o.grading || o.linear.format != 0;   // else the reference's resolve does the whole image
     const float *fs = host.sum, *fs2 = host.sum2;
     const int32_t *fc = host.count;
     // The statistics -- and with no stage at all the image: nothing else runs on the plain path.  -GAUSS / -MEDIAN alone, on the
@@ -743,8 +792,9 @@ bool HostChain::bytes(HostFrame &host, uint32_t frame_index, float dispersion[3]
         m = lens_mean.data(); n = lens_count.data();
     }
     rgb.resize(3 * static_cast<size_t>(w) * h);
-    if (o.grading) {   // meter (a sequence's frame starts from the previous frame's exposure), bloom, local exposure, sharpening, grade
-        float e = o.grade.exposure > 0.0f ? o.grade.exposure : 1.0f, target = 0.0f;   // (0 = 1, as the library reads it)
+    float e = o.grade.exposure > 0.0f ? o.grade.exposure : 1.0f;   // (0 = 1, as the library reads it)
+    if (o.grading) {   // meter (a sequence's frame starts from the previous frame's exposure), bloom, local exposure, sharpening
+        float target = 0.0f;
         if (o.grade.auto_exposure) {
             uint32_t hist[PT_METER_ENTRIES];
             if (pt_meter_host(dev, w, h, m, n, hist, nullptr) != PT_OK ||
@@ -765,6 +815,10 @@ bool HostChain::bytes(HostFrame &host, uint32_t frame_index, float dispersion[3]
             if (pt_sharpen_host(dev, w, h, m, n, e, &o.sharpen, rgb.data(), nullptr) != PT_OK) return false;
             m = rgb.data();
         }
+    }
+    // the linear file's body: the mean every stage above left, before the colour stage or the grade sees it
+    if (o.linear.format && pt_linear_encode(w, h, m, n, e, &o.linear, host.linear.data()) != PT_OK) return false;
+    if (o.grading) {   // colour / grade
         if (o.colouring ? pt_colour_host(w, h, m, n, e, o.grade.curve, &o.colour, rgb.data()) != PT_OK
                         : pt_grade_host(w, h, m, n, e, o.grade.curve, rgb.data()) != PT_OK)
             return false;
@@ -798,9 +852,15 @@ std::string result_name(long long elapsed_ms, int rays_done, int rays_asked, con
            "  max_disp " + std::to_string(dispersion[0]) + "  min_disp " + std::to_string(dispersion[1]) + "  aver_disp " + std::to_string(dispersion[2]);
 }
 
-// -OUT, or the named file and ../result.bmp; the name goes to stdout either way.  Returns the exit status.
-int write_outputs(const Options &o, const std::string &name, const uint8_t *image) {
+// -LINEAR_OUT's picture, under `path`
+int write_linear(const Options &o, const std::string &path, const uint8_t *body) {
+    return o.linear.format == PT_LINEAR_PFM ? pt_write_pfm(path.c_str(), o.width, o.height, body) : pt_write_hdr(path.c_str(), o.width, o.height, body);
+}
+
+// -OUT, or the named file and ../result.bmp, and -LINEAR_OUT's file; the name goes to stdout either way.  Returns the exit status.
+int write_outputs(const Options &o, const std::string &name, const uint8_t *image, const uint8_t *linear) {
     int rc = 0;
+    if (o.linear.format && write_linear(o, o.linear_out, linear) != PT_OK) rc = die("pt_render");
     if (!o.out.empty()) {
         if (pt_write_bmp(o.out.c_str(), o.width, o.height, image) != PT_OK) rc = die("pt_render");
     } else {
@@ -906,10 +966,14 @@ int run_sequence(Run &r) {
             char frame_name[32];
             std::snprintf(frame_name, sizeof frame_name, "frame_%04d.bmp", i);
             if (pt_write_bmp(frame_name, o.width, o.height, host.image()) != PT_OK) return die("pt_render");
+            if (o.linear.format) {   // the frame's BMP name with the extension replaced
+                std::snprintf(frame_name, sizeof frame_name, "frame_%04d.%s", i, o.linear.format == PT_LINEAR_PFM ? "pfm" : "hdr");
+                if (write_linear(o, frame_name, host.linear.data()) != PT_OK) return die("pt_render");
+            }
         }
         if (!o.quiet) std::cerr << "frame " << i + 1 << " of " << o.frames << std::endl;
     }
-    return write_outputs(o, result_name(now_ms() - r.start_time, o.rays_per_pixel, o.rays_per_pixel, dispersion), host.image());
+    return write_outputs(o, result_name(now_ms() - r.start_time, o.rays_per_pixel, o.rays_per_pixel, dispersion), host.image(), host.linear.data());
 }
 
 // One frame: the pass slices with previews and -TL, then the chain, the outputs and the -TIMING line.
@@ -978,7 +1042,7 @@ int run_frame(Run &r) {
     ChainTimes times;
     if (!make_image(r, host, chain, true, dispersion, times)) return die("pt_render");
     const clk::time_point t_resolve = clk::now();
-    const int rc = write_outputs(o, result_name(now_ms() - r.start_time, rays_count, o.rays_per_pixel, dispersion), host.image());
+    const int rc = write_outputs(o, result_name(now_ms() - r.start_time, rays_count, o.rays_per_pixel, dispersion), host.image(), host.linear.data());
     if (o.timing) {
         const clk::time_point t_end = clk::now();
         double host_s[2] = {0, 0};
