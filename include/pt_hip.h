@@ -250,6 +250,76 @@ int pt_scene_set_camera_motion(pt_scene *scene, const pt_camera *end);
 /* The handle's end pose; *is_set = 0 (and the start pose in *end) if it has no motion.  Either pointer may be NULL. */
 int pt_scene_get_camera_motion(const pt_scene *scene, pt_camera *end, int32_t *is_set);
 
+/* ---- projection (orthographic, fisheye, equirectangular) ------------------------------------------- */
+
+/* How a pixel becomes a primary ray.  pt_camera states the perspective projection; the other three kinds change only the primary
+ * ray, from the same u, v:
+ *   u = float((x + jx) / W - 0.5),  v = float(-(y + jy) / H + 0.5)          (in double, then rounded, as pt_camera forms them)
+ * With o, r, p, f = the camera's origin, right, up, forward (on a handle without a camera: the reference camera's) and
+ *   r^ = r / |r|,  u^ = p / |p|,  f^ = f / |f|                              (in double, rounded to float once, as pt_lens defines them)
+ * everything below is float, each operation rounded to nearest, nothing fused.  normalize3(D) = D * (1 / sqrt((D_x^2 + D_y^2) +
+ * D_z^2)) with the correctly rounded root and reciprocal, as for every bounce.  sincos is the portable sine and cosine of the
+ * diffuse lobe; its domain is [0, 2 pi], so it is called on |angle| and the sign of the angle is put back on the sine by flipping
+ * the sine's sign bit where the angle's is set.
+ *   PERSPECTIVE      exactly what pt_camera states, through the same kernels: a handle with kind 0 is a handle without a projection.
+ *   ORTHOGRAPHIC     origin_i  = o_i + (u * r_i + v * p_i)                  (i = x, y, z)
+ *                    direction = normalize3(f), the same for every pixel
+ *                    right and up are the extent of the view in scene units.
+ *   FISHEYE          a = u * span_x,  b = v * span_y,  theta = sqrt(a * a + b * b)      (correctly rounded root)
+ *                    (sn, cs) = sincos(theta);   k = theta == 0 ? 1 : sn / theta
+ *                    D_i = ((k * a) * r^_i + (k * b) * u^_i) + cs * f^_i
+ *                    direction = normalize3(D),  origin = o
+ *                    Equidistant: the image radius is proportional to the angle from forward.  Angles beyond pi simply wrap; there
+ *                    is no mask: a pixel outside the image circle is a ray like any other.
+ *   EQUIRECTANGULAR  phi = u * span_x,  psi = v * span_y
+ *                    (s_phi, c_phi) = sincos(|phi|) with the sign of phi put back on s_phi; the same for psi
+ *                    D_i = ((c_psi * s_phi) * r^_i + s_psi * u^_i) + (c_psi * c_phi) * f^_i
+ *                    direction = normalize3(D),  origin = o
+ * span_x / span_y are the angles, in radians, the image's width / height cover; kinds 0 and 1 ignore them (pt_scene_get_projection
+ * reports them as 0).  The random numbers are those of the pinhole: with the same seed, frames of different kinds draw the same words.
+ * First-hit features (pt_render_features_host, and with it the denoiser, the upsampler and every pt_display stage that reads
+ * features) use the same formulas with jitter 0.  The temporal reprojection inverts a pinhole: pt_temporal_push_host and a display
+ * present with a temporal stage fail with PT_ERR_UNSUPPORTED on a handle with a non-perspective projection.
+ * The projection belongs to the scene HANDLE, like the camera: copies made from it afterwards (pt_scene_clone_to_device,
+ * pt_frame_create) inherit it, and a launch uses the projection its handle has when it is enqueued.  Setting it must not race with
+ * a render of the same handle. */
+#define PT_PROJECTION_PERSPECTIVE     0   /* pt_camera's, the default */
+#define PT_PROJECTION_ORTHOGRAPHIC    1
+#define PT_PROJECTION_FISHEYE         2   /* equidistant: image radius proportional to the angle from forward */
+#define PT_PROJECTION_EQUIRECTANGULAR 3
+typedef struct pt_projection {
+    int32_t kind;
+    float span_x;
+    float span_y;
+} pt_projection;   /* 12 bytes */
+
+/* A projection of `kind` from a field of view, computed in double and rounded to float once.  With rad = fov_y_degrees * (pi / 180)
+ * and a = aspect > 0 ? aspect : 1:  FISHEYE: span_y = rad, span_x = rad * a (fov_y_degrees > 0).  EQUIRECTANGULAR: the same, and
+ * fov_y_degrees <= 0 means the full sphere, span_x = 2 pi, span_y = pi.  PERSPECTIVE, ORTHOGRAPHIC: both spans 0, the other
+ * arguments are ignored.  PT_ERR_INVALID_ARGUMENT: an unknown kind, non-finite input or fov_y_degrees <= 0 for a fisheye (what
+ * pt_scene_set_projection refuses is refused there). */
+int pt_projection_make(int32_t kind, float fov_y_degrees, float aspect, pt_projection *out);
+/* A camera for an orthographic view at `eye` looking at `target`, computed as pt_camera_look_at computes its own with s =
+ * view_height: right and up have the lengths view_height * a and view_height (a = aspect > 0 ? aspect : 1), forward is a unit
+ * vector.  PT_ERR_INVALID_ARGUMENT as there, and for view_height <= 0. */
+int pt_camera_ortho(const float eye[3], const float target[3], const float up[3], float view_height, float aspect, pt_camera *out);
+/* Sets the handle's projection; NULL or kind PT_PROJECTION_PERSPECTIVE returns to the pinhole.
+ *   PT_ERR_INVALID_ARGUMENT  an unknown kind; for kinds 2 / 3 a span that is not finite or not positive; a fisheye with
+ *                            0.5 * sqrt(span_x^2 + span_y^2) > 2 pi (the corner angle leaves the sincos's domain); an equirectangular
+ *                            view with span_x > 4 pi or span_y > 4 pi (compared in double)
+ *   PT_ERR_UNSUPPORTED       a non-perspective projection on a handle that has a lens (radius > 0) or a camera motion -- and the
+ *                            reverse: pt_scene_set_lens / pt_scene_set_camera_motion with a lens / an end pose on a handle with a
+ *                            non-perspective projection; clear one of the two first.  An orthographic view with an origin that
+ *                            could leave the envelope: max_i(|o_i| + 0.5 (|r_i| + |p_i|)) * (1 + 2^-18) beyond PT_CAMERA_MAX_ORIGIN
+ *                            and beyond the scene's largest |vertex coordinate|; pt_scene_set_camera applies the same check against
+ *                            the projection the handle already has.
+ * A failed call leaves the handle as it was.  (u and v reach 0.5 plus half a pixel at the left and the top edge.  The culling
+ * envelope's slack of one scene unit covers that for the orthographic origins as long as |r_i| / W + |p_i| / H <= 1 for i = x, y, z;
+ * a render of an image with coarser pixels fails with PT_ERR_UNSUPPORTED.) */
+int pt_scene_set_projection(pt_scene *scene, const pt_projection *projection);
+/* The handle's projection; *is_set = 0 (and kind 0, spans 0) if it has none.  Either pointer may be NULL. */
+int pt_scene_get_projection(const pt_scene *scene, pt_projection *projection, int32_t *is_set);
+
 int pt_scene_counts(const pt_scene *scene, int32_t *n_triangles, int32_t *n_materials);
 int pt_scene_get_triangles(const pt_scene *scene, float *triangles, int32_t *triangle_material);
 int pt_scene_get_materials(const pt_scene *scene, float *materials);
@@ -339,6 +409,8 @@ int pt_frame_set_camera(pt_frame *frame, const pt_camera *camera);
 int pt_frame_set_lens(pt_frame *frame, const pt_lens *lens);
 /* pt_scene_set_camera_motion on every device's copy of the frame's scene (NULL: no motion), likewise. */
 int pt_frame_set_camera_motion(pt_frame *frame, const pt_camera *end);
+/* pt_scene_set_projection on every device's copy of the frame's scene (NULL: the pinhole), likewise. */
+int pt_frame_set_projection(pt_frame *frame, const pt_projection *projection);
 void pt_frame_destroy(pt_frame *frame);
 /* Can RCCL be loaded and does it export what the gather calls?  version = ncclGetVersion's.  Needs no GPU. */
 int pt_rccl_available(int32_t *version);

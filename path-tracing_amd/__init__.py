@@ -41,6 +41,7 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_camera_look_at", "pt_scene_set_camera", "pt_scene_get_camera", "pt_frame_set_camera",
                "pt_scene_set_lens", "pt_scene_get_lens", "pt_frame_set_lens",
                "pt_scene_set_camera_motion", "pt_scene_get_camera_motion", "pt_frame_set_camera_motion",
+               "pt_projection_make", "pt_camera_ortho", "pt_scene_set_projection", "pt_scene_get_projection", "pt_frame_set_projection",
                "pt_render_features_host", "pt_denoise_host", "pt_tonemap",
                "pt_temporal_create", "pt_temporal_push_host", "pt_temporal_reset", "pt_temporal_destroy",
                "pt_display_create", "pt_display_create_frame", "pt_display_present", "pt_display_reset", "pt_display_destroy",
@@ -120,6 +121,23 @@ class Lens(C.Structure):
 
     def __repr__(self):
         return "Lens(radius=%r, focus_distance=%r)" % (self.radius, self.focus_distance)
+
+
+PROJECTION_PERSPECTIVE, PROJECTION_ORTHOGRAPHIC, PROJECTION_FISHEYE, PROJECTION_EQUIRECTANGULAR = 0, 1, 2, 3
+PROJECTION_KINDS = {"perspective": 0, "ortho": 1, "orthographic": 1, "fisheye": 2, "equirect": 3, "equirectangular": 3}
+
+
+class Projection(C.Structure):
+    """pt_projection: how a pixel becomes a primary ray (pt_hip.h states each kind exactly).  span_x / span_y: the angles, in
+    radians, the image's width / height cover under a fisheye or an equirectangular projection."""
+    _fields_ = [("kind", C.c_int32), ("span_x", C.c_float), ("span_y", C.c_float)]
+
+    def __eq__(self, other):
+        return isinstance(other, Projection) and self.kind == other.kind and np.array_equal(
+            np.array([self.span_x, self.span_y], np.float32).view(np.uint32), np.array([other.span_x, other.span_y], np.float32).view(np.uint32))
+
+    def __repr__(self):
+        return "Projection(kind=%r, span_x=%r, span_y=%r)" % (self.kind, self.span_x, self.span_y)
 
 
 class DenoiseParams(C.Structure):
@@ -393,6 +411,43 @@ def look_at(eye, target, up=(0.0, 1.0, 0.0), fov_y=REFERENCE_FOV_Y, aspect=0.0, 
     return cam
 
 
+def _projection_kind(kind):
+    if isinstance(kind, str):
+        if kind not in PROJECTION_KINDS:
+            raise ValueError(f"projection: unknown kind {kind!r} (one of {sorted(PROJECTION_KINDS)})")
+        return PROJECTION_KINDS[kind]
+    return int(kind)
+
+
+def projection(kind, fov_y=0.0, aspect=0.0, library=None):
+    """pt_projection_make: a Projection of `kind` (a PROJECTION_* number or "perspective", "ortho", "fisheye", "equirect").
+    fov_y, in degrees, is the angle across the image height of a fisheye or an equirectangular view and aspect = W / H the ratio of
+    the angle across its width to it; an equirectangular view with fov_y <= 0 is the full sphere."""
+    L = library or lib()
+    p = Projection()
+    _check(L.pt_projection_make(_projection_kind(kind), fov_y, aspect, C.byref(p)), L)
+    return p
+
+
+def ortho_camera(eye, target, up=(0.0, 1.0, 0.0), view_height=20.0, aspect=0.0, library=None):
+    """pt_camera_ortho: a Camera for an orthographic view at `eye` looking at `target`, whose image is view_height scene units high
+    and view_height * aspect wide (aspect 0: as high as wide)."""
+    L = library or lib()
+    f3 = C.c_float * 3
+    cam = Camera()
+    _check(L.pt_camera_ortho(f3(*eye), f3(*target), f3(*up), view_height, aspect, C.byref(cam)), L)
+    return cam
+
+
+def _projection_arg(projection_, library):
+    """A Projection, a kind (number or name) or None -> a pointer argument for pt_scene_set_projection / pt_frame_set_projection."""
+    if projection_ is None:
+        return None
+    if not isinstance(projection_, Projection):
+        projection_ = projection(projection_, library=library)
+    return C.byref(projection_)
+
+
 def build(force=False):
     """Compile libpt_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
     if force:
@@ -495,6 +550,11 @@ def load_library(path):
     L.pt_scene_set_camera_motion.argtypes = [vp, C.POINTER(Camera)]
     L.pt_scene_get_camera_motion.argtypes = [vp, C.POINTER(Camera), ip]
     L.pt_frame_set_camera_motion.argtypes = [vp, C.POINTER(Camera)]
+    L.pt_projection_make.argtypes = [C.c_int32, C.c_float, C.c_float, C.POINTER(Projection)]
+    L.pt_camera_ortho.argtypes = [fp, fp, fp, C.c_float, C.c_float, C.POINTER(Camera)]
+    L.pt_scene_set_projection.argtypes = [vp, C.POINTER(Projection)]
+    L.pt_scene_get_projection.argtypes = [vp, C.POINTER(Projection), ip]
+    L.pt_frame_set_projection.argtypes = [vp, C.POINTER(Projection)]
     L.pt_render_features_host.argtypes = [vp, C.POINTER(RenderParams), ip, fp, fp, fp, fp]
     L.pt_denoise_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, fp, ip, fp, fp, fp, ip, C.POINTER(DenoiseParams), fp, ip, fp]
     L.pt_tonemap.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, fp]
@@ -707,6 +767,17 @@ class Scene:
         end, is_set = Camera(), C.c_int32()
         _check(self._L.pt_scene_get_camera_motion(self._h, C.byref(end), C.byref(is_set)), self._L)
         return end if is_set.value else None
+
+    def set_projection(self, projection_):
+        """pt_scene_set_projection: a Projection (pt.projection), or a kind that needs no angles ("ortho", "equirect" = the full
+        sphere); None or "perspective" = the pinhole.  Not together with a lens or a camera motion: clear those first."""
+        _check(self._L.pt_scene_set_projection(self._h, _projection_arg(projection_, self._L)), self._L)
+
+    def get_projection(self):
+        """The handle's Projection, or None if it has none (the pinhole)."""
+        p, is_set = Projection(), C.c_int32()
+        _check(self._L.pt_scene_get_projection(self._h, C.byref(p), C.byref(is_set)), self._L)
+        return p if is_set.value else None
 
     def cull_tables(self, eps=1e-4):
         """The culling hierarchy for `eps` (diagnostics): dict of clusters, spheres, bary records, constants."""
@@ -1348,6 +1419,10 @@ class Frame:
         if end_camera is not None and not isinstance(end_camera, Camera):
             end_camera = Camera.of(*end_camera)
         _check(self._L.pt_frame_set_camera_motion(self._h, C.byref(end_camera) if end_camera is not None else None), self._L)
+
+    def set_projection(self, projection_):
+        """pt_frame_set_projection: the projection of every device's copy of the frame's scene (None = the pinhole)."""
+        _check(self._L.pt_frame_set_projection(self._h, _projection_arg(projection_, self._L)), self._L)
 
     def band_kernel_ms(self):
         """Kernel time of every band of the last render(want_stats=True), -1 where there is none."""

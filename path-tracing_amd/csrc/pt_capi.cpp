@@ -185,9 +185,22 @@ double motion_extent(const pt_camera &a, const pt_camera &b, const pt_lens *l) {
     return e;
 }
 
+// Largest |component| an origin of the orthographic view of camera c can have (pt_hip.h: pt_projection): origin_i = o_i +
+// (u r_i + v p_i) with |u|, |v| <= 0.5 up to half a pixel of jitter, which the factor 1 + 2^-18 covers for every image at least two
+// pixels wide together with the three roundings -- as stated in the header: max_i(|o_i| + 0.5 (|r_i| + |p_i|)) (1 + 2^-18).
+double ortho_extent(const pt_camera &c) {
+    double e = 0.0;
+    for (int i = 0; i < 3; ++i)
+        e = std::max(e, std::fabs(static_cast<double>(c.origin[i])) + 0.5 * (std::fabs(static_cast<double>(c.right[i])) + std::fabs(static_cast<double>(c.up[i]))));
+    return e * (1.0 + 0x1p-18);
+}
+
 // The envelope radius for the cull tables (get_cull): the largest |component| of every origin a primary ray can have -- 20 for
-// the reference's camera at (0, 0, -20).
+// the reference's camera at (0, 0, -20).  Only origins matter: the culling is direction-agnostic, so a fisheye or an
+// equirectangular view, whose rays start at the eye, has its camera's radius, and an orthographic view adds the extent of its image
+// plane.  The cull cache is keyed on (eps, radius): an orthographic view whose origins stay within 20 shares the camera-free tables.
 double camera_radius(const pt_scene *s) {
+    if (s->has_projection && s->projection.kind == PT_PROJECTION_ORTHOGRAPHIC) return std::max(20.0, ortho_extent(view_camera(s)));
     if (motion_active(s)) return std::max(20.0, motion_extent(view_camera(s), s->motion_end, s->has_lens ? &s->lens : nullptr));
     if (s->has_lens) return std::max(20.0, lens_extent(view_camera(s), s->lens));
     if (!s->has_camera) return 20.0;
@@ -286,6 +299,14 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
         a.lns[1] = scene->lens.focus_distance;
         lens_axes(view_camera(scene), a.lns + 2);
     }
+    if (scene->has_projection) {   // the projection kernels of the camera twins (integrate_kernel_projection); never with a lens or a motion
+        a.camera = 1;
+        std::memcpy(a.cam, &view_camera(scene), sizeof a.cam);
+        a.projection = scene->projection.kind;
+        a.prj_span[0] = scene->projection.span_x;
+        a.prj_span[1] = scene->projection.span_y;
+        lens_axes(view_camera(scene), a.lns + 2);   // r^, u^, f^ in the slots a lens would fill (a.lens stays 0)
+    }
     if (moving) {   // the motion twins of either (integrate_kernel_motion, integrate_kernel_motion_lens): end - start, one float subtraction each
         a.motion = 1;
         float end_pose[12];
@@ -331,6 +352,13 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     a.error = p->error; a.seed = p->seed;
     if (p->row_end == p->row_begin) return PT_OK;
     int rc;
+    if (a.projection == PT_PROJECTION_ORTHOGRAPHIC) {
+        // u and v reach 0.5 + half a pixel at the left and the top edge (the jitter of column 0 and row 0): origins may leave
+        // ortho_extent by 0.5 (|r_i| / W + |p_i| / H), which must stay within half of the envelope's slack of one scene unit
+        for (int i = 0; i < 3; ++i)
+            if (!(0.5 * (std::fabs(static_cast<double>(a.cam[3 + i])) / a.width + std::fabs(static_cast<double>(a.cam[6 + i])) / a.height) <= 0.5))
+                return fail(PT_ERR_UNSUPPORTED, "orthographic projection: a pixel of this image is wider than one scene unit (|right_i| / width + |up_i| / height > 1)");
+    }
     if (!ctx.ev_done && (rc = ctx.ev_done.create("launch context", hipEventDisableTiming)) != PT_OK) return rc;
     if (want_stats) {
         if ((rc = ctx_stats_ready(ctx)) != PT_OK) return rc;
@@ -345,7 +373,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     a.blocks_x = tiles.blocks_x;
     const uint32_t n_tiles = tiles.n_tiles;
     int waves_per_cu = 24;
-    PT_HIP_TRY(pt::integrator_waves_per_cu(tiles.variant, &waves_per_cu));
+    PT_HIP_TRY(pt::integrator_waves_per_cu(tiles.variant, &waves_per_cu));   // (a projection launch: its camera twin's, which are its own)
     const uint32_t slots = static_cast<uint32_t>(scene->cu_count) * static_cast<uint32_t>(std::max(1, waves_per_cu));
     const auto [n_chunks, chunk_passes] = pt::plan::plan_chunks(n_tiles, slots, p->pass_count, a.sky != nullptr, a.narrow != 0, want_stats, ov);
     if (static_cast<unsigned long long>(n_tiles) * n_chunks > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "too many work items");
@@ -593,6 +621,8 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->lens = src->lens;
     s->has_motion = src->has_motion;   // and camera motion
     s->motion_end = src->motion_end;
+    s->has_projection = src->has_projection;   // and projection
+    s->projection = src->projection;
     if (device >= 0) {
         const int rc = upload(s.get(), device);
         if (rc != PT_OK) return rc;
@@ -666,12 +696,9 @@ static int scene_set_skybox_bmp_impl(pt_scene *scene, const char *path) {
 
 static bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
-static int camera_look_at_impl(const float eye[3], const float target[3], const float up[3], float fov_y_degrees, float aspect,
-                               pt_camera *out) {
-    if (!eye || !target || !up || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    if (!finite3(eye) || !finite3(target) || !finite3(up) || !std::isfinite(fov_y_degrees) || !std::isfinite(aspect))
-        return fail(PT_ERR_INVALID_ARGUMENT, "look_at: non-finite input");
-    if (!(fov_y_degrees > 0.0f && fov_y_degrees < 180.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "look_at: fov_y must lie in (0, 180) degrees");
+// The camera at `eye` looking at `target` whose up vector has length sy and whose right vector sy * aspect (pt_camera_look_at:
+// sy = 2 tan(fov_y / 2); pt_camera_ortho: sy = the view height), in double, rounded to float once.  `who` names the caller.
+static int camera_frame(const std::string &who, const float eye[3], const float target[3], const float up[3], double sy, float aspect, pt_camera *out) {
     double f[3], u[3], r[3];
     for (int i = 0; i < 3; ++i) {
         f[i] = static_cast<double>(target[i]) - static_cast<double>(eye[i]);
@@ -679,15 +706,14 @@ static int camera_look_at_impl(const float eye[3], const float target[3], const 
     }
     const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
     const double ul = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    if (!(fl > 0.0) || !(ul > 0.0)) return fail(PT_ERR_INVALID_ARGUMENT, "look_at: eye == target or a zero up vector");
+    if (!(fl > 0.0) || !(ul > 0.0)) return fail(PT_ERR_INVALID_ARGUMENT, who + ": eye == target or a zero up vector");
     for (double &x : f) x /= fl;
     r[0] = u[1] * f[2] - u[2] * f[1];   // cross(up, forward)
     r[1] = u[2] * f[0] - u[0] * f[2];
     r[2] = u[0] * f[1] - u[1] * f[0];
     const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    if (!(rl > 1e-6 * ul)) return fail(PT_ERR_INVALID_ARGUMENT, "look_at: up is parallel to the view direction");
+    if (!(rl > 1e-6 * ul)) return fail(PT_ERR_INVALID_ARGUMENT, who + ": up is parallel to the view direction");
     for (double &x : r) x /= rl;
-    const double sy = 2.0 * std::tan(static_cast<double>(fov_y_degrees) * (M_PI / 360.0));
     const double sx = sy * (aspect > 0.0f ? static_cast<double>(aspect) : 1.0);
     const double v[3] = {f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]};   // cross(forward, right)
     for (int i = 0; i < 3; ++i) {
@@ -696,6 +722,44 @@ static int camera_look_at_impl(const float eye[3], const float target[3], const 
         out->up[i] = static_cast<float>(v[i] * sy);
         out->forward[i] = static_cast<float>(f[i]);
     }
+    return PT_OK;
+}
+
+static int camera_look_at_impl(const float eye[3], const float target[3], const float up[3], float fov_y_degrees, float aspect,
+                               pt_camera *out) {
+    if (!eye || !target || !up || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!finite3(eye) || !finite3(target) || !finite3(up) || !std::isfinite(fov_y_degrees) || !std::isfinite(aspect))
+        return fail(PT_ERR_INVALID_ARGUMENT, "look_at: non-finite input");
+    if (!(fov_y_degrees > 0.0f && fov_y_degrees < 180.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "look_at: fov_y must lie in (0, 180) degrees");
+    return camera_frame("look_at", eye, target, up, 2.0 * std::tan(static_cast<double>(fov_y_degrees) * (M_PI / 360.0)), aspect, out);
+}
+
+static int camera_ortho_impl(const float eye[3], const float target[3], const float up[3], float view_height, float aspect, pt_camera *out) {
+    if (!eye || !target || !up || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!finite3(eye) || !finite3(target) || !finite3(up) || !std::isfinite(view_height) || !std::isfinite(aspect))
+        return fail(PT_ERR_INVALID_ARGUMENT, "camera_ortho: non-finite input");
+    if (!(view_height > 0.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "camera_ortho: the view height must be positive");
+    return camera_frame("camera_ortho", eye, target, up, static_cast<double>(view_height), aspect, out);
+}
+
+// pt_projection_make: the spans in double, rounded to float once.
+static int projection_make_impl(int32_t kind, float fov_y_degrees, float aspect, pt_projection *out) {
+    if (!out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
+    if (kind < PT_PROJECTION_PERSPECTIVE || kind > PT_PROJECTION_EQUIRECTANGULAR) return fail(PT_ERR_INVALID_ARGUMENT, "projection: unknown kind " + std::to_string(kind));
+    pt_projection p = {kind, 0.0f, 0.0f};
+    if (kind == PT_PROJECTION_FISHEYE || kind == PT_PROJECTION_EQUIRECTANGULAR) {
+        if (!std::isfinite(fov_y_degrees) || !std::isfinite(aspect)) return fail(PT_ERR_INVALID_ARGUMENT, "projection: non-finite input");
+        if (kind == PT_PROJECTION_EQUIRECTANGULAR && fov_y_degrees <= 0.0f) {   // the full sphere
+            p.span_x = static_cast<float>(2.0 * M_PI);
+            p.span_y = static_cast<float>(M_PI);
+        } else {
+            if (!(fov_y_degrees > 0.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "projection: fov_y must be positive");
+            const double rad = static_cast<double>(fov_y_degrees) * (M_PI / 180.0);
+            p.span_y = static_cast<float>(rad);
+            p.span_x = static_cast<float>(rad * (aspect > 0.0f ? static_cast<double>(aspect) : 1.0));
+        }
+    }
+    *out = p;
     return PT_OK;
 }
 
@@ -737,6 +801,7 @@ static int scene_set_lens_impl(pt_scene *scene, const pt_lens *lens) {
         return PT_OK;
     }
     if (!(lens->focus_distance > 0.0f)) return fail(PT_ERR_INVALID_ARGUMENT, "lens: the focus distance must be positive");
+    if (scene->has_projection) return fail(PT_ERR_UNSUPPORTED, "lens: the handle has a non-perspective projection; clear one of the two first");
     int rc = check_lens_on(view_camera(scene), *lens);
     if (rc != PT_OK) return rc;
     if (scene->has_motion && (rc = check_lens_on(scene->motion_end, *lens)) != PT_OK) return rc;
@@ -798,6 +863,17 @@ static int check_motion(const pt_scene *scene, const pt_camera &a, const pt_lens
 
 static int check_camera(const pt_scene *scene, const pt_camera *cam);
 
+// Can camera c carry an orthographic projection on this scene?  Every origin of its image plane must lie within the bound a camera
+// origin has (check_camera).
+static int check_ortho_on(const pt_scene *scene, const pt_camera &c) {
+    const double max_origin = std::max(static_cast<double>(PT_CAMERA_MAX_ORIGIN), scene->shared->vertex_extent);
+    if (!(ortho_extent(c) <= max_origin))
+        return fail(PT_ERR_UNSUPPORTED, "orthographic projection: an origin of the image plane could lie beyond PT_CAMERA_MAX_ORIGIN (" +
+                                            std::to_string(PT_CAMERA_MAX_ORIGIN) + ") and beyond the scene's largest |vertex coordinate|");
+    return PT_OK;
+}
+static bool ortho_on(const pt_scene *scene) { return scene->has_projection && scene->projection.kind == PT_PROJECTION_ORTHOGRAPHIC; }
+
 // The motion the handle has against a camera and lens it is about to get (an end pose equal to the new camera is no motion).
 static int recheck_motion(const pt_scene *scene, const pt_camera &cam, const pt_lens *l) {
     if (!scene->has_motion || std::memcmp(&cam, &scene->motion_end, sizeof cam) == 0) return PT_OK;
@@ -814,6 +890,10 @@ static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
         }
         const int mrc = recheck_motion(scene, kReferenceCamera, scene->has_lens ? &scene->lens : nullptr);
         if (mrc != PT_OK) return mrc;
+        if (ortho_on(scene)) {
+            const int orc = check_ortho_on(scene, kReferenceCamera);
+            if (orc != PT_OK) return orc;
+        }
         scene->has_camera = false;
         scene->camera = pt_camera{};
         return PT_OK;
@@ -822,6 +902,7 @@ static int scene_set_camera_impl(pt_scene *scene, const pt_camera *cam) {
     if (rc != PT_OK) return rc;
     if (scene->has_lens && (rc = check_lens_on(*cam, scene->lens)) != PT_OK) return rc;
     if ((rc = recheck_motion(scene, *cam, scene->has_lens ? &scene->lens : nullptr)) != PT_OK) return rc;
+    if (ortho_on(scene) && (rc = check_ortho_on(scene, *cam)) != PT_OK) return rc;
     scene->camera = *cam;
     scene->has_camera = true;
     return PT_OK;
@@ -865,6 +946,7 @@ static int scene_set_camera_motion_impl(pt_scene *scene, const pt_camera *end) {
         scene->motion_end = pt_camera{};
         return PT_OK;
     }
+    if (scene->has_projection) return fail(PT_ERR_UNSUPPORTED, "camera motion: the handle has a non-perspective projection; clear one of the two first");
     const int rc = check_motion(scene, view_camera(scene), scene->has_lens ? &scene->lens : nullptr, *end);
     if (rc != PT_OK) return rc;
     scene->motion_end = *end;
@@ -890,6 +972,46 @@ static int scene_get_camera_impl(const pt_scene *scene, pt_camera *cam, int32_t 
         }
     }
     if (is_set) *is_set = scene->has_camera ? 1 : 0;
+    return PT_OK;
+}
+
+// NULL or kind perspective: back to the pinhole.  Checks everything before it changes anything.
+static int scene_set_projection_impl(pt_scene *scene, const pt_projection *prj) {
+    if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (!prj || prj->kind == PT_PROJECTION_PERSPECTIVE) {
+        scene->has_projection = false;
+        scene->projection = pt_projection{};
+        return PT_OK;
+    }
+    if (prj->kind < PT_PROJECTION_PERSPECTIVE || prj->kind > PT_PROJECTION_EQUIRECTANGULAR)
+        return fail(PT_ERR_INVALID_ARGUMENT, "projection: unknown kind " + std::to_string(prj->kind));
+    pt_projection p = {prj->kind, 0.0f, 0.0f};   // (the spans of an orthographic view are ignored)
+    if (p.kind != PT_PROJECTION_ORTHOGRAPHIC) {
+        const double sx = prj->span_x, sy = prj->span_y;
+        if (!std::isfinite(prj->span_x) || !std::isfinite(prj->span_y) || !(sx > 0.0) || !(sy > 0.0))
+            return fail(PT_ERR_INVALID_ARGUMENT, "projection: span_x and span_y must be finite and positive");
+        if (p.kind == PT_PROJECTION_FISHEYE && 0.5 * std::sqrt(sx * sx + sy * sy) > 2.0 * M_PI)
+            return fail(PT_ERR_INVALID_ARGUMENT, "projection: the fisheye's corner angle, sqrt(span_x^2 + span_y^2) / 2, exceeds 2 pi");
+        if (p.kind == PT_PROJECTION_EQUIRECTANGULAR && (sx > 4.0 * M_PI || sy > 4.0 * M_PI))
+            return fail(PT_ERR_INVALID_ARGUMENT, "projection: an equirectangular span exceeds 4 pi");
+        p.span_x = prj->span_x;
+        p.span_y = prj->span_y;
+    }
+    if (scene->has_lens) return fail(PT_ERR_UNSUPPORTED, "projection: the handle has a lens; a non-perspective projection has a pinhole only -- clear the lens first");
+    if (scene->has_motion) return fail(PT_ERR_UNSUPPORTED, "projection: the handle has a camera motion; a non-perspective projection stands still -- clear the motion first");
+    if (p.kind == PT_PROJECTION_ORTHOGRAPHIC) {
+        const int rc = check_ortho_on(scene, view_camera(scene));
+        if (rc != PT_OK) return rc;
+    }
+    scene->projection = p;
+    scene->has_projection = true;
+    return PT_OK;
+}
+
+static int scene_get_projection_impl(const pt_scene *scene, pt_projection *prj, int32_t *is_set) {
+    if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (prj) *prj = scene->has_projection ? scene->projection : pt_projection{};
+    if (is_set) *is_set = scene->has_projection ? 1 : 0;
     return PT_OK;
 }
 
@@ -1302,6 +1424,26 @@ int pt_scene_set_camera_motion(pt_scene *scene, const pt_camera *end) {
 
 int pt_scene_get_camera_motion(const pt_scene *scene, pt_camera *end, int32_t *is_set) {
     return guarded([&] { return scene_get_camera_motion_impl(scene, end, is_set); });
+}
+
+int pt_projection_make(int32_t kind, float fov_y_degrees, float aspect, pt_projection *out) {
+    return guarded([&] { return projection_make_impl(kind, fov_y_degrees, aspect, out); });
+}
+
+int pt_camera_ortho(const float eye[3], const float target[3], const float up[3], float view_height, float aspect, pt_camera *out) {
+    return guarded([&] { return camera_ortho_impl(eye, target, up, view_height, aspect, out); });
+}
+
+int pt_scene_set_projection(pt_scene *scene, const pt_projection *projection) {
+    return guarded([&] {
+        if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+        std::lock_guard<std::mutex> launch_lock(scene->launch_mutex);   // (a launch being enqueued reads the projection under it)
+        return scene_set_projection_impl(scene, projection);
+    });
+}
+
+int pt_scene_get_projection(const pt_scene *scene, pt_projection *projection, int32_t *is_set) {
+    return guarded([&] { return scene_get_projection_impl(scene, projection, is_set); });
 }
 
 int pt_render_device(pt_scene *scene, const pt_render_params *p, float *d_sum, float *d_sum2, int32_t *d_count, void *hip_stream, pt_render_stats *stats) {

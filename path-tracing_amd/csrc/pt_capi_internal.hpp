@@ -90,6 +90,8 @@ struct pt_scene {
     pt_lens lens{};
     bool has_motion = false;       // this handle's camera motion (pt_scene_set_camera_motion): the END pose; copies inherit it
     pt_camera motion_end{};
+    bool has_projection = false;   // this handle's projection (pt_scene_set_projection; a kind other than perspective); copies inherit it
+    pt_projection projection{};
     // ensure_cull + the enqueue of a launch happen under launch_mutex (a concurrent render with another eps must not free
     // the tables in between); nothing waits for the device while holding it.
     std::mutex launch_mutex;

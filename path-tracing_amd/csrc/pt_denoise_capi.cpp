@@ -16,7 +16,10 @@ int ptc::enqueue_first_hits(pt_scene *scene, const pt::RenderArgs &a, const pt_c
     pt::FeatureCamera cam;
     std::memcpy(cam.v, &camera, sizeof cam.v);
     const int n = rows * width;
-    PT_HIP_TRY(pt::launch_feature_rays(cam, width, height, row_begin, rows, out.origins, out.directions, stream));
+    // (a.projection != 0: the handle's non-perspective projection, of the handle's own camera -- the one spelling of its ray,
+    // pt_projection.hpp, which the integrator traced; the temporal stage, the one caller with another camera, refuses such a handle)
+    if (a.projection != 0) PT_HIP_TRY(pt::launch_projection_rays(a, width, height, row_begin, rows, out.origins, out.directions, stream));
+    else PT_HIP_TRY(pt::launch_feature_rays(cam, width, height, row_begin, rows, out.origins, out.directions, stream));
     PT_HIP_TRY(pt::launch_trace_rays(a, out.origins, out.directions, n, out.hit, out.hit_t, stream));
     PT_HIP_TRY(pt::launch_feature_gather(scene->d_exact.get<pt::ExactRec>(), scene->d_mats.get<pt::MatRec>(), out.origins, out.directions, out.hit,
                                          out.hit_t, n, out.position, out.normal, out.albedo, stream));

@@ -476,6 +476,8 @@ int display_present_impl(pt_display *d, const PresentRequest &rq, uint8_t *bgr, 
         stream = d->session->stream.get();
     }
     pt_scene *scene = d->scene;
+    if (temporal && scene->has_projection)   // (the reprojection inverts a pinhole: pt_hip.h, pt_projection)
+        return fail(PT_ERR_UNSUPPORTED, "temporal: the scene handle has a non-perspective projection, which the reprojection does not invert");
     PT_HIP_TRY(hipSetDevice(scene->device));
     DisplayDevice &dev = scaled ? d->dev_up : d->dev;
     if (scaled && (rc = ensure_scaled(d, ua.scale)) != PT_OK) return rc;

@@ -517,6 +517,18 @@ int pt_frame_set_camera_motion(pt_frame *f, const pt_camera *end) {
     });
 }
 
+int pt_frame_set_projection(pt_frame *f, const pt_projection *projection) {
+    return guarded([&] {
+        if (!f) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
+        // every device's copy of the scene takes it; they share one camera, lens and motion, so a projection the first refuses changes none of them
+        for (pt_scene *s : f->scenes) {
+            const int rc = pt_scene_set_projection(s, projection);
+            if (rc != PT_OK) return rc;
+        }
+        return static_cast<int>(PT_OK);
+    });
+}
+
 void pt_frame_destroy(pt_frame *f) {
     if (!f) return;
     // a gather may still be in flight: its sends sit on the bands' streams, its receives on the root's gather stream -- both are

@@ -1,9 +1,11 @@
-// The body of pt::integrate_kernel, pt::integrate_kernel_lens and their motion twins (pt_kernels.hip), included inside each.  It sees
-// the kernel's template arguments, its argument `a` and `constexpr bool LENS` and `MOTION`, which the including kernel defines.
+// The body of pt::integrate_kernel, pt::integrate_kernel_lens, their motion twins and pt::integrate_kernel_projection (pt_kernels.hip),
+// included inside each.  It sees the kernel's template arguments, its argument `a` and `constexpr bool LENS`, `MOTION` and `PROJ`,
+// which the including kernel defines.
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
     static_assert(!MOTION || CAM, "a motion kernel is the motion variant of a camera twin or of its lens kernel");
+    static_assert(!PROJ || (CAM && !LENS && !MOTION), "a projection kernel is the projection variant of a camera twin; the host refuses a lens or a motion with it");
     static_assert(!NARROW || (!SKY && !STATS), "only the statistics-free, skybox-free kernels have a narrow variant");
     constexpr int R = NARROW ? 1 : rays_per_lane<SKY, BIG, STATS>();   // pixels per lane: the wave's tile is kTileW * R x kTileH
     static_assert(POOL == 0 || ((POOL == 2 || POOL == 4) && (R == 2 || BIG) && !STATS && !SKY), "batches of the tile's pixels (a pixel's number takes 8 bits): the two-pixel kernel and the box-tree kernel");
@@ -390,7 +392,16 @@
                 asm volatile("" : "+v"(xi), "+v"(yi), "+s"(wi), "+s"(hi));
                 const float ddx = static_cast<float>((xi + jx) / wi - 0.5f);
                 const float ddy = static_cast<float>(-(yi + jy) / hi + 0.5f);
-                if constexpr (CAM) {
+                if constexpr (PROJ) {
+                    // a non-perspective projection (pt_hip.h: pt_projection; pt_projection.hpp spells the ray): from here on the
+                    // jitter's doubles are dead, so the angular work (sincos, root, divide) does not meet them.  The kind is a kernel
+                    // argument: a scalar branch.  The origin goes straight into the ray slot, one component at a time, as the lens's does.
+                    const ProjectionView pv = projection_view();
+                    projection_primary_ray(pv.kind(), ddx, ddy, camera_view(), lens_view() + 2, pv.span(),
+                                           [](float ang, float &sn, float &cs) { portable_sincos(ang, sn, cs); },
+                                           [](float &vx, float &vy, float &vz) { normalize3(vx, vy, vz); },
+                                           q[k].ox, q[k].oy, q[k].oz, out_dx, out_dy, out_dz);
+                } else if constexpr (CAM) {
                     // u right + v up + forward, componentwise, unfused (-ffp-contract=off); with the reference camera every step
                     // is exact (x 1, + 0) and |d|^2 is the sum below, so the twin's frame is the camera-free kernel's bit for bit
                     const CameraView c = camera_view();
@@ -439,8 +450,8 @@
         // starts slot k's path along a primary direction (eye fixed at (0, 0, -20), main.cpp:129 -- or the camera's; Ray::color_ = 1, ray.h:17)
         auto start_path = [&](int k, float ddx, float ddy, float ddz, float t) {
             q[k].dx = ddx; q[k].dy = ddy; q[k].dz = ddz;
-            if constexpr (LENS) {
-                // (the origin, camera origin + lens point: primary_dir wrote it)
+            if constexpr (LENS || PROJ) {
+                // (the origin, camera origin + lens point -- or the projection's: primary_dir wrote it)
             } else if constexpr (MOTION) {
                 const CameraView c = camera_view();
                 const MotionView cd = camera_delta_view();

@@ -35,6 +35,7 @@
 
 #include "pt_fastfp.hpp"
 #include "pt_kernels.hpp"
+#include "pt_projection.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1307,6 +1308,19 @@ __device__ __forceinline__ MotionView lens_delta_view() {
     asm volatile("" : "+s"(p));
     return reinterpret_cast<MotionView>(p);
 }
+// The projection of a projection-kernel launch (RenderArgs::projection, prj_span), likewise; its r^, u^, f^ are lens_view() + 2.
+struct ProjectionView {
+    uint64_t p;
+    __device__ __forceinline__ int32_t kind() const { return *reinterpret_cast<const __attribute__((address_space(4))) int32_t *>(p); }
+    __device__ __forceinline__ const __attribute__((address_space(4))) float *span() const {
+        return reinterpret_cast<const __attribute__((address_space(4))) float *>(p + (offsetof(RenderArgs, prj_span) - offsetof(RenderArgs, projection)));
+    }
+};
+__device__ __forceinline__ ProjectionView projection_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, projection);
+    asm volatile("" : "+s"(p));
+    return {p};
+}
 
 // What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
 // in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
@@ -1343,7 +1357,7 @@ constexpr int integrator_waves() {
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = false;
 #include "pt_integrator_body.inc"
 }
 // The lens kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary ray
@@ -1359,7 +1373,7 @@ constexpr int lens_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (lens_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = false;
+    constexpr bool LENS = true, MOTION = false, PROJ = false;
 #include "pt_integrator_body.inc"
 }
 // The motion twins (pt_hip.h: camera motion): the camera twin and its lens kernel with the camera -- and the lens axes -- interpolated
@@ -1375,13 +1389,55 @@ constexpr int motion_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, false>())) void integrate_kernel_motion(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = true;
+    constexpr bool LENS = false, MOTION = true, PROJ = false;
 #include "pt_integrator_body.inc"
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, true>())) void integrate_kernel_motion_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = true;
+    constexpr bool LENS = true, MOTION = true, PROJ = false;
 #include "pt_integrator_body.inc"
+}
+// The projection kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary
+// ray from the handle's non-perspective projection (pt_hip.h: pt_projection; pt_projection.hpp spells it once, for this kernel and
+// for the first-hit feature pass below).  One kernel for the three kinds: the kind is a kernel argument and primary_dir branches on
+// it with scalar branches.  A kernel of its own for the reason the lens kernel is one.  Waves per SIMD: projection_waves, the twin's
+// for every kernel (tests/test_projection_resources.py pins them, with the twin's LDS) -- which is why the launch
+// planner may ask integrator_waves_per_cu for the TWIN's wave slots: the runtime's answer depends on nothing else.
+template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW>
+constexpr int projection_waves() {
+    return integrator_waves<SKY, BIG, STATS, ENV, NARROW>();
+}
+template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
+__global__ __launch_bounds__(kBlock, (projection_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_projection(const RenderArgs a) {
+    constexpr bool LENS = false, MOTION = false, PROJ = true;
+#include "pt_integrator_body.inc"
+}
+
+// First-hit feature pass under a projection (pt_hip.h: pt_render_features_host): the ray pt_projection states for pixel (x, y) with
+// jitter 0, for launch_trace_rays.  (Here and not beside the pinhole's feature_rays_kernel in pt_denoise.hip: the ray needs this
+// file's portable_sincos and normalize3.)
+__global__ __launch_bounds__(256) void projection_rays_kernel(const RenderArgs a, int width, int height, int row_begin, int n,
+                                                              float *__restrict__ origins, float *__restrict__ directions) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int y = row_begin + p / width, x = p % width;
+    const float u = static_cast<float>(static_cast<double>(x) / width - 0.5);
+    const float v = static_cast<float>(-static_cast<double>(y) / height + 0.5);
+    float ox, oy, oz, dx, dy, dz;
+    projection_primary_ray(a.projection, u, v, a.cam, a.lns + 2, a.prj_span,
+                           [](float ang, float &sn, float &cs) { portable_sincos(ang, sn, cs); },
+                           [](float &vx, float &vy, float &vz) { normalize3(vx, vy, vz); }, ox, oy, oz, dx, dy, dz);
+    const size_t o = 3 * static_cast<size_t>(p);
+    origins[o] = ox; origins[o + 1] = oy; origins[o + 2] = oz;
+    directions[o] = dx; directions[o + 1] = dy; directions[o + 2] = dz;
+}
+hipError_t launch_projection_rays(const RenderArgs &args, int width, int height, int row_begin, int rows, float *d_origins, float *d_directions,
+                                  hipStream_t stream) {
+    const int n = rows * width;
+    if (n <= 0) return hipSuccess;
+    if (args.projection == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(projection_rays_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, args, width, height, row_begin, n, d_origins, d_directions);
+    return hipGetLastError();
 }
 
 // Closest hit for caller-supplied rays (the intersection half of Scene::TraceRay, scene.cpp:114-120).
@@ -1473,7 +1529,7 @@ hipError_t launch_integrator(const RenderArgs &args0, const plan::Variant &v, hi
     static uint32_t *d_cnt = nullptr;
     const int rows = args0.row_end - args0.row_begin;
     if (rows <= 0 || args0.width <= 0) return hipSuccess;
-    if (!plan::variant_exists(v, kBuild)) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin or lens kernel: refuse rather than run another)
+    if (!plan::variant_exists(v, kBuild) || args0.projection != 0) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
     if (!mod) {
         const char *path = std::getenv("PT_BLOCKPROF_HSACO");
         if (!path) return hipErrorInvalidValue;
@@ -1530,12 +1586,28 @@ template <int... I>
 std::array<Kernel, sizeof...(I)> kernel_table(std::integer_sequence<int, I...>) { return {kernel_of<I>()...}; }
 const auto kKernels = kernel_table(std::make_integer_sequence<int, plan::kAllVariants>());   // by plan::variant_id
 static_assert(plan::variant_id({true, true, true, true, false, 0, plan::kViews - 1}) < plan::kAllVariants, "every view's ids fit the table");
+// The projection kernels have no ids in the plan (a projection launch is planned as its camera twin, view 1): a table of their
+// own, indexed by the twin's id within its view.
+template <int R>
+Kernel projection_kernel_of() {
+    constexpr plan::Variant v = plan::variant_of(plan::kVariantsPerView + R);
+    if constexpr (!plan::variant_exists(v, kBuild)) return nullptr;
+    else return &integrate_kernel_projection<v.sky, v.big, v.stats, v.env, v.narrow, v.pool | 1>;
+}
+template <int... R>
+std::array<Kernel, sizeof...(R)> projection_kernel_table(std::integer_sequence<int, R...>) { return {projection_kernel_of<R>()...}; }
+const auto kProjectionKernels = projection_kernel_table(std::make_integer_sequence<int, plan::kVariantsPerView>());
+// the kernel of a launch: variant v's, or with a projection the projection kernel of camera twin v
+Kernel kernel_for(const plan::Variant &v, bool projection) {
+    if (!projection) return kKernels[plan::variant_id(v)];
+    return v.view == 1 ? kProjectionKernels[plan::variant_id(v) - plan::kVariantsPerView] : nullptr;
+}
 }  // namespace
 
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
     const int rows = args.row_end - args.row_begin;
     if (rows <= 0 || args.width <= 0) return hipSuccess;
-    const Kernel kernel = kKernels[plan::variant_id(v)];
+    const Kernel kernel = kernel_for(v, args.projection != 0);
     if (!kernel) return hipErrorInvalidDeviceFunction;
     hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
     return hipGetLastError();

@@ -75,6 +75,12 @@ struct RenderArgs {
     int32_t motion;
     float cam_d[12];
     float lns_d[9];
+    // The handle's projection (pt_hip.h: pt_projection), appended likewise.  projection != 0 (only with camera != 0, lens == 0 and
+    // motion == 0: the host refuses the combinations): the launch runs the projection kernels (integrate_kernel_projection), planned
+    // as their camera twins (plan::Variant::view == 1), which read the kind here, prj_span = span_x, span_y, and r^, u^, f^ from the
+    // slots a lens would fill, lns[2 .. 10] (lns[0], lns[1] stay zero).
+    int32_t projection;
+    float prj_span[2];
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif
@@ -82,10 +88,16 @@ struct RenderArgs {
 
 // The constants the kernels of this library were compiled with: what plan::plan_tiles needs to know of the build.
 const plan::Build &integrator_build();
-// launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds)
+// launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds) -- with args.projection != 0
+// the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
-// waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached)
+// waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached).  A projection launch asks for its
+// camera twin's: the projection kernels are compiled for their twins' waves per SIMD and LDS (tests/test_projection_resources.py)
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);
+// First-hit feature pass under a projection (args.projection != 0; cam, lns and prj_span as for the integrator): the rays through
+// the pixels of rows [row_begin, row_begin + rows) with jitter 0, origins / directions 3 floats per pixel.
+hipError_t launch_projection_rays(const RenderArgs &args, int width, int height, int row_begin, int rows, float *d_origins, float *d_directions,
+                                  hipStream_t stream);
 // diagnostic: the box tree's child test on n (node, ray, t_best) items; out[i] = the mask of item i's kept children
 hipError_t launch_box_masks(const BvhNode *d_nodes, const float *d_rays, const float *d_t_best, float err, int n, uint32_t *d_out, hipStream_t stream);
 hipError_t launch_trace_rays(const RenderArgs &args, const float *d_origins, const float *d_directions, int n_rays,

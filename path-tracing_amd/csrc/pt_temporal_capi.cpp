@@ -102,6 +102,8 @@ int enqueue_chain(pt_temporal *t, const ptc::AccumPlanes &frame, const pt_tempor
                   hipStream_t stream, const ptc::DeviceTimer *timer, int *levels) {
     int rc = check_temporal_params(prm);
     if (rc != PT_OK) return rc;
+    // (the reprojection inverts a pinhole: pt_hip.h, pt_projection)
+    if (t->scene->has_projection) return fail(PT_ERR_UNSUPPORTED, "temporal: the scene handle has a non-perspective projection, which the reprojection does not invert");
     pt::DenoiseArgs da;
     da.levels = 0;
     if (dn && (rc = ptc::denoise_params_to_args(dn, da)) != PT_OK) return rc;

@@ -32,6 +32,13 @@
 // A thin lens (pt_scene_set_lens, not in the reference): -APERTURE <radius> (default 0: no lens, a pinhole), -FOCUS <distance of
 // the focal plane> (default |LOOKAT - EYE|, 20 for the reference's camera).  PT_RENDER_PRINT_CAMERA=1 then also prints
 // "lens <radius> <focus distance>".
+// A projection (pt_scene_set_projection, not in the reference): -PROJECTION perspective|ortho|fisheye|equirect (default perspective:
+// nothing changes).  ortho: parallel rays along the view direction from a plane -ORTHO_HEIGHT <h> scene units high and h x -ASPECT
+// wide around -EYE (default: the height the perspective view of -FOV has at the distance |LOOKAT - EYE|, 2 tan(FOV / 2) times it).
+// fisheye: equidistant, -FOV is the angle across the image height (and FOV x ASPECT across its width; it may exceed 180).  equirect:
+// the full sphere, 360 x 180 degrees.  An unknown name ends the program; -APERTURE, -SHUTTER and -TEMPORAL are refused with a
+// projection other than perspective, with the library's message.  PT_RENDER_PRINT_CAMERA=1 then also prints
+// "projection <kind> <span_x> <span_y>".
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -157,6 +164,9 @@ struct Options {
     bool camera = false;   // any of -EYE / -LOOKAT / -UP / -FOV / -ASPECT given
     std::string eye = "0,0,-20", lookat = "0,0,0", up = "0,1,0", eye_end, lookat_end;   // as given ("" = the start value)
     float fov = 53.13010235415598f, aspect = 0.0f;
+    std::string projection_name = "perspective", ortho_height;   // -PROJECTION / -ORTHO_HEIGHT as given
+    pt_projection projection{};    // what they make; kind 0 (perspective) = none is set
+    float view_height = 0.0f;      // -PROJECTION ortho: the height of the view in scene units
     std::string aperture, focus;   // -APERTURE / -FOCUS as given
     std::string shutter_text;      // -SHUTTER as given
     float shutter = 0.0f;          // the fraction of a frame interval the shutter is open; 0 = off
@@ -252,6 +262,8 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-UP") { o.up = v; o.camera = true; }
         if (f == "-FOV") { o.fov = static_cast<float>(std::atof(v)); o.camera = true; }
         if (f == "-ASPECT") { o.aspect = static_cast<float>(std::atof(v)); o.camera = true; }
+        if (f == "-PROJECTION") o.projection_name = v;
+        if (f == "-ORTHO_HEIGHT") o.ortho_height = v;
         if (f == "-APERTURE") { o.aperture = v; o.aperture_given = true; }
         if (f == "-FOCUS") { o.focus = v; o.focus_given = true; }
         if (f == "-SHUTTER") o.shutter_text = v;
@@ -347,6 +359,15 @@ int refuse(int status, const std::string &why) {
     return status;
 }
 
+// The camera at `eye` looking at `at` under the run's projection: pt_camera_look_at with -FOV, or for ortho pt_camera_ortho with the
+// view's height; a fisheye or an equirectangular view takes its angles from the projection, so its camera is made with the default
+// -FOV (only the axes' directions matter, and a fisheye's -FOV may exceed what a pinhole can have).
+bool view_from(const Options &o, const float eye[3], const float at[3], pt_camera &out) {
+    if (o.projection.kind == PT_PROJECTION_ORTHOGRAPHIC) return pt_camera_ortho(eye, at, o.up0, o.view_height, o.aspect, &out) == PT_OK;
+    const float fov = o.projection.kind == PT_PROJECTION_PERSPECTIVE ? o.fov : Options().fov;
+    return pt_camera_look_at(eye, at, o.up0, fov, o.aspect, &out) == PT_OK;
+}
+
 // The camera at time `i` of the sequence, in frames: start + (end - start) i / (n - 1), in double, through pt_camera_look_at.  Frame i
 // starts at i and, with -SHUTTER f, ends at i + f (the last frame's end pose lies beyond -EYE_END; with -FRAMES 1 it is EYE + f (EYE_END - EYE)).
 bool pose_at(const Options &o, double i, pt_camera &out) {
@@ -355,7 +376,7 @@ bool pose_at(const Options &o, double i, pt_camera &out) {
         eye[k] = static_cast<float>(o.eye0[k] + (static_cast<double>(o.eye1[k]) - o.eye0[k]) * i / std::max(1, o.frames - 1));
         at[k] = static_cast<float>(o.at0[k] + (static_cast<double>(o.at1[k]) - o.at0[k]) * i / std::max(1, o.frames - 1));
     }
-    return pt_camera_look_at(eye, at, o.up0, o.fov, o.aspect, &out) == PT_OK;
+    return view_from(o, eye, at, out);
 }
 
 // PT_RENDER_PRINT_CAMERA with an open shutter: every frame's two poses as the run would set them (no device needed).
@@ -409,9 +430,29 @@ int configure(int argc, char **argv, Options &o) {
     }
     // the camera's vectors, parsed here and nowhere else (without -EYE / -LOOKAT / -UP they are the defaults, which parse)
     const bool vectors = parse_vec3(o.eye, o.eye0) && parse_vec3(o.lookat, o.at0) && parse_vec3(o.up, o.up0);
+    // -PROJECTION: the kind by name, its angles from -FOV and -ASPECT; ortho needs a camera of its own (right and up are the view's extent)
+    if (o.projection_name == "perspective") o.projection.kind = PT_PROJECTION_PERSPECTIVE;
+    else if (o.projection_name == "ortho") o.projection.kind = PT_PROJECTION_ORTHOGRAPHIC;
+    else if (o.projection_name == "fisheye") o.projection.kind = PT_PROJECTION_FISHEYE;
+    else if (o.projection_name == "equirect") o.projection.kind = PT_PROJECTION_EQUIRECTANGULAR;
+    else return refuse(2, "-PROJECTION takes perspective, ortho, fisheye or equirect, not '" + o.projection_name + "'");
+    if (!o.ortho_height.empty() && o.projection.kind != PT_PROJECTION_ORTHOGRAPHIC) return refuse(2, "-ORTHO_HEIGHT needs -PROJECTION ortho");
+    if (o.projection.kind == PT_PROJECTION_ORTHOGRAPHIC) {
+        if (!vectors) return refuse(2, "-EYE / -LOOKAT / -UP take three comma-separated numbers, x,y,z");
+        if (!o.ortho_height.empty()) {
+            if (!(parse_float(o.ortho_height, o.view_height) && o.view_height > 0.0f)) return refuse(2, "-ORTHO_HEIGHT takes a height > 0");
+        } else {   // what the perspective view of -FOV shows at the distance of the point looked at
+            double d2 = 0.0;
+            for (int i = 0; i < 3; ++i) d2 += (static_cast<double>(o.at0[i]) - o.eye0[i]) * (static_cast<double>(o.at0[i]) - o.eye0[i]);
+            o.view_height = static_cast<float>(2.0 * std::tan(static_cast<double>(o.fov) * (M_PI / 360.0)) * std::sqrt(d2));
+        }
+        o.camera = true;
+    } else if (o.projection.kind != PT_PROJECTION_PERSPECTIVE) {
+        if (pt_projection_make(o.projection.kind, o.projection.kind == PT_PROJECTION_FISHEYE ? o.fov : 0.0f, o.aspect, &o.projection) != PT_OK) return die("pt_render");
+    }
     if (o.camera) {
         if (!vectors) return refuse(2, "-EYE / -LOOKAT / -UP take three comma-separated numbers, x,y,z");
-        if (pt_camera_look_at(o.eye0, o.at0, o.up0, o.fov, o.aspect, &o.view) != PT_OK) return die("pt_render");
+        if (!view_from(o, o.eye0, o.at0, o.view)) return die("pt_render");
     }
     if (o.aperture_given && !(parse_float(o.aperture, o.lens.radius) && o.lens.radius >= 0.0f)) return refuse(2, "-APERTURE takes a radius >= 0");
     if (o.focus_given) {
@@ -437,6 +478,8 @@ int configure(int argc, char **argv, Options &o) {
                             static_cast<double>(rows[r][2]));
         }
         if (o.has_lens) std::printf("lens %.9g %.9g\n", static_cast<double>(o.lens.radius), static_cast<double>(o.lens.focus_distance));
+        if (o.projection.kind != PT_PROJECTION_PERSPECTIVE)
+            std::printf("projection %d %.9g %.9g\n", o.projection.kind, static_cast<double>(o.projection.span_x), static_cast<double>(o.projection.span_y));
         // with -SHUTTER > 0 and a camera that travels: the start and the end pose of every frame, "shutter <frame> start|end <12 numbers>"
         if (!shutter_poses(o)) return 2;
         return 0;
@@ -1087,8 +1130,14 @@ int main(int argc, char **argv) {
     if (pt_scene_load_obj(o.model_path.c_str(), o.model_name.c_str(), -1, &r.scene) != PT_OK) return die("pt_render");
     if (!o.skybox.empty() && pt_scene_set_skybox_bmp(r.scene, o.skybox.c_str()) != PT_OK) return die("pt_render");   // scene.cpp:20-22
     if (o.camera && pt_scene_set_camera(r.scene, &o.view) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
+    // and its projection -- set before the lens and the motion, which the library refuses on a handle with one, as it refuses the
+    // temporal stage when the first frame reaches it: asked here, before any device is looked at, with the library's own words
+    if (o.projection.kind != PT_PROJECTION_PERSPECTIVE) {
+        if (pt_scene_set_projection(r.scene, &o.projection) != PT_OK) return die("pt_render");
+        if (o.merging) return refuse(1, "temporal: the scene handle has a non-perspective projection, which the reprojection does not invert");
+    }
     if (o.has_lens && pt_scene_set_lens(r.scene, &o.lens) != PT_OK) return die("pt_render");   // and its lens
-    if (o.blurring && !o.sequence) {   // one frame with an open shutter: from -EYE / -LOOKAT towards -EYE_END / -LOOKAT_END
+    if (o.blurring && (!o.sequence || o.projection.kind != PT_PROJECTION_PERSPECTIVE)) {   // one frame with an open shutter: from -EYE / -LOOKAT towards -EYE_END / -LOOKAT_END
         pt_camera end;
         if (!pose_at(o, static_cast<double>(o.shutter), end) || pt_scene_set_camera_motion(r.scene, &end) != PT_OK) return die("pt_render");
     }
