@@ -1426,6 +1426,86 @@ int pt_scene_timings(const pt_scene *scene, double *seconds);
 void *pt_host_alloc(size_t bytes);
 void pt_host_free(void *p);
 
+/* ---- environment lighting: an HDR panorama as a light source ------------------------------------------------------- */
+
+/* A scene handle may carry an ENVIRONMENT: a high-dynamic-range radiance map over the whole sphere.  A ray that hits nothing adds
+ * throughput x L(direction) to its pixel -- one contribution like every other: sum, sum of squares, count -- and its path ends.  That
+ * holds for primary rays too, so the map is also the background.  Unlike the skybox (pt_scene_set_skybox_bmp: 8-bit texels, the path
+ * throughput not applied, the reference's rule) it lights the scene.  Without an environment every output is what it was.
+ *
+ * An environment belongs to the handle, as the skybox does: pt_scene_clone_to_device and pt_frame_create inherit it.  A handle has a
+ * skybox OR an environment: setting one while the other is set is PT_ERR_INVALID_ARGUMENT.  It works with every view (camera-free,
+ * camera, lens, motion, lens + motion, the projections), with statistics, on small and box-tree scenes.  Launches are planned as
+ * under a skybox (path regeneration, the same tiles and chunks).  The first-hit feature pass does not look at it: a miss pixel's
+ * features are what they are under a skybox.
+ *
+ * THE MAP.  The device does not look up the panorama.  It is resampled once, on the host, into an OCTAHEDRAL map of N x N texels
+ * (r, g, b), 8 <= N <= 4096, stored with a one-texel apron so that the bilinear lookup never wraps an index:
+ *   texel (-1, j) = texel (0, N-1-j)        texel (N, j) = texel (N-1, N-1-j)
+ *   texel (i, -1) = texel (N-1-i, 0)        texel (i, N) = texel (N-1-i, N-1)
+ * and the four corners by the two rules in turn (the octahedral fold: a point just outside an edge is the point mirrored about that
+ * edge's midpoint).  pt_scene_set_environment_map takes the N x N x 3 interior, row j after row j - 1, and builds the apron.
+ *
+ * THE LOOKUP of unit direction d = (dx, dy, dz), y being the pole axis; every operation is a float operation rounded once, in the order
+ * written, nothing fused:
+ *   s  = (|dx| + |dy|) + |dz|;   px = dx / s;   pz = dz / s
+ *   if dy < 0:  qx = (1 - |pz|) with the sign bit of px,  qz = (1 - |px|) with the sign bit of pz   (both from the unfolded px, pz)
+ *   else        qx = px, qz = pz                                                                    (dy = -0 is not < 0)
+ *   fx = (qx * 0.5 + 0.5) * N - 0.5;   x0 = floor(fx) clamped to -1 .. N-1 (a NaN goes to -1);   ax = fx - x0
+ *   fy, y0, ay likewise from qz
+ *   L  = (T(x0, y0) * (1 - ax) + T(x0+1, y0) * ax) * (1 - ay) + (T(x0, y0+1) * (1 - ax) + T(x0+1, y0+1) * ax) * ay     per channel
+ * No trigonometry and no double precision; pt_environment_lookup is this on the host, and the kernels run the same code.
+ *
+ * THE CONVERSION of an equirectangular picture, w x h x 3 floats, rows top-down, at most 16384 x 8192, every sample finite and >= 0, into
+ * the map; all in double, rounded to float once at the end.  With k = clamp(ceil(w / N), 1, 8), texel (i, j) is the mean over the
+ * k x k sub-cell centres  qx = 2 (i + (a + 0.5) / k) / N - 1,  qz = 2 (j + (b + 0.5) / k) / N - 1  of the picture looked up at:
+ *   dy = 1 - |qx| - |qz|;  (dx, dz) = (qx, qz) if dy >= 0, else ((1 - |qz|) with qx's sign, (1 - |qx|) with qz's sign);  u = d / |d|
+ *   rotation about +y by r = rotate_y_degrees:  vx = cos r * ux + sin r * uz,  vy = uy,  vz = -sin r * ux + cos r * uz
+ *   the skybox's own convention:  theta = acos(vy) / pi down the rows,  phi = atan2(vz, -vx) / (2 pi) + 0.5 along the columns
+ *   fx = phi * w,  fy = theta * h;  x0 = floor(fx), ax = fx - x0, likewise y0, ay;  columns x0, x0 + 1 WRAP, rows y0, y0 + 1 are CLAMPED
+ *   (P(x0, y0) (1 - ax) + P(x0+1, y0) ax) (1 - ay) + (P(x0, y0+1) (1 - ax) + P(x0+1, y0+1) ax) ay
+ * and the mean is multiplied by gain.  The same panorama as skybox and as environment has the same orientation; a picture rendered with
+ * PT_PROJECTION_EQUIRECT by the camera at the origin with forward (-1, 0, 0) and up (0, 1, 0) is in the picture's own frame (column
+ * w / 2 lies in direction -x, columns grow from -x towards +z).  Default N (size 0): the smallest power of two >= h, clamped to 8 .. 2048.
+ *
+ * FILES.  The format is chosen by content.  Radiance: first line "#?RADIANCE" or "#?RGBE", a header line "FORMAT=32-bit_rle_rgbe",
+ * an empty line, the resolution "-Y h +X w" (no other orientation); scanlines flat (what pt_write_hdr writes) or in the new-style
+ * run-length coding (2, 2, w >> 8, w & 255, then each channel as runs: a count above 128 repeats the next byte count - 128 times,
+ * a count of 1 .. 128 copies that many bytes).  A pixel decodes to (byte + 0.5) * 2^(E - 136) per channel, the inverse stated for
+ * PT_LINEAR_RGBE; the pixel 0, 0, 0, 0 is black.  PFM: "PF", width, height, scale, one whitespace byte, rows bottom-up; little-endian
+ * if the scale is negative, big-endian if positive; its magnitude is not applied.  PT_ERR_IO: the file cannot be read.  PT_ERR_PARSE:
+ * anything else than these, a truncated file or bytes after the last row, a run that overruns its scanline or has length 0, another
+ * orientation, "Pf", a non-finite or negative sample, a size above 16384 x 8192.
+ *
+ * PT_ERR_INVALID_ARGUMENT: NULL pointers, gain not finite or < 0, rotate_y_degrees not finite, a size other than 0 and outside
+ * 8 .. 4096, a handle with a skybox.  A sample of a picture or a map handed over in memory that is not finite or negative is
+ * PT_ERR_PARSE as in a file.  The conversion runs on one host thread and takes a double-precision acos, atan2 and root per
+ * sub-sample, N^2 k^2 of them: a fraction of a second for a 2048 x 1024 picture (N = 1024, k = 2), on the order of ten seconds for
+ * 8192 x 4096 at the default N = 2048 (k = 4); -ENV_SIZE / size trades that time for resolution.  params may be NULL: gain 1, no rotation, the default size.  A failed call leaves the handle as it was. */
+typedef struct pt_environment_params {
+    float gain;
+    float rotate_y_degrees;
+    int32_t size; /* 0 = default */
+} pt_environment_params;
+
+/* NULL or "" removes the environment. */
+int pt_scene_set_environment_file(pt_scene *scene, const char *path, const pt_environment_params *params);
+int pt_scene_set_environment_equirect(pt_scene *scene, int32_t w, int32_t h, const float *rgb, const pt_environment_params *params);
+/* An octahedral map given directly: n x n x 3. */
+int pt_scene_set_environment_map(pt_scene *scene, int32_t n, const float *rgb);
+/* *n = the map's size, 0 without an environment; rgb (may be NULL) gets its n x n x 3 floats. */
+int pt_scene_get_environment(const pt_scene *scene, int32_t *n, float *rgb);
+/* The same on a frame: every device's copy of the frame's scene takes the map, which is read and converted once; a refused call
+ * changes none of them.  pt_frame_get_environment answers for the root device's copy. */
+int pt_frame_set_environment_file(pt_frame *frame, const char *path, const pt_environment_params *params);
+int pt_frame_set_environment_equirect(pt_frame *frame, int32_t w, int32_t h, const float *rgb, const pt_environment_params *params);
+int pt_frame_set_environment_map(pt_frame *frame, int32_t n, const float *rgb);
+int pt_frame_get_environment(pt_frame *frame, int32_t *n, float *rgb);
+/* The conversion alone, on the host: map_rgb gets n x n x 3 floats (n in 8 .. 4096; params->size is checked and not used). */
+int pt_environment_from_equirect(int32_t w, int32_t h, const float *rgb, const pt_environment_params *params, int32_t n, float *map_rgb);
+/* The lookup alone, on the host: rgb[3 i ..] = L(directions[3 i ..]). */
+int pt_environment_lookup(int32_t n, const float *map_rgb, int32_t n_dirs, const float *directions, float *rgb);
+
 /* ---- misc ------------------------------------------------------------------------------------------- */
 int pt_abi_version(void);
 int pt_device_count(void);

@@ -57,7 +57,11 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_sharpen_host", "pt_display_present_sharpen",
                "pt_grain_quantize", "pt_display_bytes_grain_host", "pt_display_present_grain",
                "pt_linear_bytes", "pt_linear_encode", "pt_linear_encode_device_host", "pt_display_present_linear", "pt_write_pfm",
-               "pt_write_hdr"]
+               "pt_write_hdr",
+               "pt_scene_set_environment_file", "pt_scene_set_environment_equirect", "pt_scene_set_environment_map",
+               "pt_scene_get_environment", "pt_environment_from_equirect", "pt_environment_lookup",
+               "pt_frame_set_environment_file", "pt_frame_set_environment_equirect", "pt_frame_set_environment_map",
+               "pt_frame_get_environment"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -439,6 +443,35 @@ def ortho_camera(eye, target, up=(0.0, 1.0, 0.0), view_height=20.0, aspect=0.0, 
     return cam
 
 
+class EnvironmentParams(C.Structure):
+    """pt_environment_params: gain, rotation about +y in degrees, N of the octahedral map (0 = the default for the picture)."""
+    _fields_ = [("gain", C.c_float), ("rotate_y_degrees", C.c_float), ("size", C.c_int32)]
+
+
+def environment_from_equirect(picture, size, gain=1.0, rotate=0.0, library=None):
+    """pt_environment_from_equirect: an (h, w, 3) equirectangular picture -> the (size, size, 3) octahedral map, on the host."""
+    L = library or lib()
+    pic = np.ascontiguousarray(picture, np.float32)
+    if pic.ndim != 3 or pic.shape[2] != 3:
+        raise ValueError("environment_from_equirect: picture must be (h, w, 3)")
+    out = np.zeros((max(int(size), 0), max(int(size), 0), 3), np.float32)
+    prm = EnvironmentParams(gain, rotate, 0)
+    _check(L.pt_environment_from_equirect(pic.shape[1], pic.shape[0], _fp(pic), C.byref(prm), int(size), _fp(out)), L)
+    return out
+
+
+def environment_lookup(env_map, directions, library=None):
+    """pt_environment_lookup: the radiance an (n, n, 3) octahedral map holds for each unit direction, [..., 3] -> [..., 3]."""
+    L = library or lib()
+    m = np.ascontiguousarray(env_map, np.float32)
+    if m.ndim != 3 or m.shape[0] != m.shape[1] or m.shape[2] != 3:
+        raise ValueError("environment_lookup: env_map must be (n, n, 3)")
+    d = np.ascontiguousarray(directions, np.float32)
+    out = np.zeros(d.shape, np.float32)
+    _check(L.pt_environment_lookup(m.shape[0], _fp(m), d.size // 3, _fp(d), _fp(out)), L)
+    return out
+
+
 def _projection_arg(projection_, library):
     """A Projection, a kind (number or name) or None -> a pointer argument for pt_scene_set_projection / pt_frame_set_projection."""
     if projection_ is None:
@@ -555,6 +588,17 @@ def load_library(path):
     L.pt_scene_set_projection.argtypes = [vp, C.POINTER(Projection)]
     L.pt_scene_get_projection.argtypes = [vp, C.POINTER(Projection), ip]
     L.pt_frame_set_projection.argtypes = [vp, C.POINTER(Projection)]
+    ep = C.POINTER(EnvironmentParams)
+    L.pt_scene_set_environment_file.argtypes = [vp, C.c_char_p, ep]
+    L.pt_scene_set_environment_equirect.argtypes = [vp, C.c_int32, C.c_int32, fp, ep]
+    L.pt_scene_set_environment_map.argtypes = [vp, C.c_int32, fp]
+    L.pt_scene_get_environment.argtypes = [vp, ip, fp]
+    L.pt_frame_set_environment_file.argtypes = [vp, C.c_char_p, ep]
+    L.pt_frame_set_environment_equirect.argtypes = [vp, C.c_int32, C.c_int32, fp, ep]
+    L.pt_frame_set_environment_map.argtypes = [vp, C.c_int32, fp]
+    L.pt_frame_get_environment.argtypes = [vp, ip, fp]
+    L.pt_environment_from_equirect.argtypes = [C.c_int32, C.c_int32, fp, ep, C.c_int32, fp]
+    L.pt_environment_lookup.argtypes = [C.c_int32, fp, C.c_int32, fp, fp]
     L.pt_render_features_host.argtypes = [vp, C.POINTER(RenderParams), ip, fp, fp, fp, fp]
     L.pt_denoise_host.argtypes = [C.c_int, C.c_int32, C.c_int32, fp, fp, ip, fp, fp, fp, ip, C.POINTER(DenoiseParams), fp, ip, fp]
     L.pt_tonemap.argtypes = [C.c_int32, C.c_int32, fp, ip, C.c_float, fp]
@@ -655,7 +699,46 @@ def device_count():
     return lib().pt_device_count()
 
 
-class Scene:
+class _EnvironmentMethods:
+    """set_environment / set_environment_map / environment of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
+    _env_prefix = "pt_scene_"
+
+    def _env_fn(self, name):
+        return getattr(self._L, self._env_prefix + name)
+
+    def set_environment(self, source, gain=1.0, rotate=0.0, size=0):
+        """-ENV: an HDR panorama as a light source.  `source` is the path of a Radiance .hdr or a PFM, or an (h, w, 3) equirectangular
+        picture; None or "" removes the environment.  gain scales it, rotate turns it about +y (degrees), size is N of the octahedral
+        map it is resampled into (0 = by the picture's height).  Not together with a skybox."""
+        prm = EnvironmentParams(gain, rotate, size)
+        if source is None or isinstance(source, (str, bytes, os.PathLike)):
+            path = os.fsencode(source) if source else b""
+            _check(self._env_fn("set_environment_file")(self._h, path, C.byref(prm)), self._L)
+            return
+        pic = np.ascontiguousarray(source, np.float32)
+        if pic.ndim != 3 or pic.shape[2] != 3:
+            raise ValueError("set_environment: a picture must be (h, w, 3)")
+        _check(self._env_fn("set_environment_equirect")(self._h, pic.shape[1], pic.shape[0], _fp(pic), C.byref(prm)), self._L)
+
+    def set_environment_map(self, env_map):
+        """pt_scene_set_environment_map / pt_frame_set_environment_map: an (n, n, 3) octahedral map given directly."""
+        m = np.ascontiguousarray(env_map, np.float32)
+        if m.ndim != 3 or m.shape[0] != m.shape[1] or m.shape[2] != 3:
+            raise ValueError("set_environment_map: env_map must be (n, n, 3)")
+        _check(self._env_fn("set_environment_map")(self._h, m.shape[0], _fp(m)), self._L)
+
+    def environment(self):
+        """The handle's octahedral map, (n, n, 3), or None if it has no environment."""
+        n = C.c_int32()
+        _check(self._env_fn("get_environment")(self._h, C.byref(n), None), self._L)
+        if n.value == 0:
+            return None
+        m = np.zeros((n.value, n.value, 3), np.float32)
+        _check(self._env_fn("get_environment")(self._h, C.byref(n), _fp(m)), self._L)
+        return m
+
+
+class Scene(_EnvironmentMethods):
     """Owns a pt_scene handle (Scene + LoadModel of the reference, scene.h:17-19)."""
 
     def __init__(self, handle, library=None):
@@ -1378,8 +1461,9 @@ def bvh_depth(nodes):
     return int(level.max())
 
 
-class Frame:
+class Frame(_EnvironmentMethods):
     """pt_frame: one image on several devices from one host program -- row bands, one gather to the first device."""
+    _env_prefix = "pt_frame_"
 
     def __init__(self, scene, devices, width, height, flags=0):
         self._scene, self._L = scene, scene._L

@@ -114,6 +114,7 @@ int upload(pt_scene *s, int device) {
         s->sky_w = s->sky->w;
         s->sky_h = s->sky->h;
     }
+    if (s->env && (rc = s->d_env.upload(pt::env_with_apron(s->env->n, s->env->rgb.data()), "environment map", 64)) != PT_OK) return rc;
     return PT_OK;
 }
 
@@ -272,6 +273,10 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
     a.sky = scene->d_sky.get<uint8_t>();
     a.sky_w = scene->d_sky ? scene->sky_w : 0;
     a.sky_h = scene->d_sky ? scene->sky_h : 0;
+    if (scene->env && scene->d_env) {   // the environment kernels of the skybox kernels (integrate_kernel_environment); never with a skybox
+        a.env_map = scene->d_env.get<void>();
+        a.env_n = scene->env->n;
+    }
     a.n_clusters = static_cast<int32_t>(t.clusters.size());
     a.n_tri = scene->shared->host.n_tri();
     a.big = t.big ? 1 : 0;
@@ -365,7 +370,8 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
         a.stats = ctx.d_stats.get<unsigned long long>();
     }
     // one wave = one tile of 8 rows; how many pixels wide depends on the kernel this launch runs
-    const pt::plan::Tiles tiles = pt::plan::plan_tiles({a.width, a.band_rows, a.sky != nullptr, a.big != 0, want_stats, a.may_leave_envelope != 0, a.error,
+    const bool sky = a.sky != nullptr || a.env_map != nullptr;   // (an environment launch is planned as the skybox launch it would be)
+    const pt::plan::Tiles tiles = pt::plan::plan_tiles({a.width, a.band_rows, sky, a.big != 0, want_stats, a.may_leave_envelope != 0, a.error,
                                                         a.pass_begin, a.pass_count, pt::plan::view_of(a.camera != 0, a.lens != 0, a.motion != 0), scene->cu_count},
                                                        pt::integrator_build(), ov);
     a.narrow = tiles.narrow;
@@ -375,7 +381,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     int waves_per_cu = 24;
     PT_HIP_TRY(pt::integrator_waves_per_cu(tiles.variant, &waves_per_cu));   // (a projection launch: its camera twin's, which are its own)
     const uint32_t slots = static_cast<uint32_t>(scene->cu_count) * static_cast<uint32_t>(std::max(1, waves_per_cu));
-    const auto [n_chunks, chunk_passes] = pt::plan::plan_chunks(n_tiles, slots, p->pass_count, a.sky != nullptr, a.narrow != 0, want_stats, ov);
+    const auto [n_chunks, chunk_passes] = pt::plan::plan_chunks(n_tiles, slots, p->pass_count, sky, a.narrow != 0, want_stats, ov);
     if (static_cast<unsigned long long>(n_tiles) * n_chunks > 0x7fffffffull) return fail(PT_ERR_INVALID_ARGUMENT, "too many work items");
     if (ctx.has_prev && ctx.prev_stream != stream) PT_HIP_TRY(hipStreamWaitEvent(stream, ctx.ev_done.get(), 0));
     const size_t sched_bytes = (1 + static_cast<size_t>(n_tiles)) * sizeof(uint32_t);
@@ -615,6 +621,7 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     ScenePtr s(new pt_scene);
     s->shared = src->shared;   // parsed model, tables, hierarchies built so far
     s->sky = src->sky;         // the skybox of the handle the copy is made from
+    s->env = src->env;         // or its environment
     s->has_camera = src->has_camera;   // and its camera
     s->camera = src->camera;
     s->has_lens = src->has_lens;       // and lens
@@ -633,6 +640,7 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
 
 static int scene_set_skybox_bmp_impl(pt_scene *scene, const char *path) {
     if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (path && *path && scene->env) return fail(PT_ERR_INVALID_ARGUMENT, "skybox: the scene handle has an environment; a handle has a skybox or an environment");
     std::vector<uint8_t> texels;
     int w = 0, h = 0;
     if (path && *path) {

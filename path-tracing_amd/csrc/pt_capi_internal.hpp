@@ -20,6 +20,7 @@
 #include "pt_bloom.hpp"
 #include "pt_colour.hpp"
 #include "pt_denoise.hpp"
+#include "pt_environment.hpp"
 #include "pt_device_mem.hpp"
 #include "pt_grade.hpp"
 #include "pt_grain.hpp"
@@ -50,6 +51,13 @@ struct pt_scene_host {
 struct pt_sky_texels {
     std::vector<uint8_t> texels;
     int w = 0, h = 0;
+};
+
+// The environment of a handle (pt_hip.h: pt_environment_*): the octahedral map, n x n x 3 floats as given or converted.  Belongs to
+// the handle as the skybox does; immutable once set.
+struct pt_env_map {
+    std::vector<float> rgb;
+    int n = 0;
 };
 
 // Device copy of one CullTables (they depend on eps and on the envelope the camera needs; a scene keeps the one of its last
@@ -84,6 +92,8 @@ struct pt_scene {
     std::shared_ptr<const pt_sky_texels> sky;   // this handle's skybox (nullptr = none); copies made from it inherit it
     ptc::DeviceBuffer d_sky;       // the same texels on this copy's device
     int sky_w = 0, sky_h = 0;
+    std::shared_ptr<const pt_env_map> env;      // this handle's environment (nullptr = none; never with a skybox); copies inherit it
+    ptc::DeviceBuffer d_env;       // its (n + 2)^2 texels with the apron (pt_environment.hpp: EnvTexel) on this copy's device
     bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
     pt_camera camera{};
     bool has_lens = false;         // this handle's lens (pt_scene_set_lens; radius > 0); copies made from it inherit it
@@ -366,6 +376,8 @@ void temporal_commit(pt_temporal *t);
 
 // What a display needs of a frame: gathers if a band changed and waits, as pt_frame_read does; then the root device's copy of
 // the scene, its full-frame planes and the root band's stream.
+// Every device's copy of a frame's scene (owned by the frame), for the setters that live outside pt_frame.cpp (pt_environment_capi.cpp).
+const std::vector<pt_scene *> &frame_scenes(pt_frame *f);
 int frame_root_planes(pt_frame *f, pt_scene **scene, AccumPlanes *planes, hipStream_t *stream, int32_t *width, int32_t *height);
 
 }  // namespace ptc

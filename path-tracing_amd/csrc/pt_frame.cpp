@@ -409,6 +409,8 @@ int frame_clear_impl(pt_frame *f) {
 
 }  // namespace
 
+const std::vector<pt_scene *> &ptc::frame_scenes(pt_frame *f) { return f->scenes; }
+
 int ptc::frame_root_planes(pt_frame *f, pt_scene **scene, AccumPlanes *planes, hipStream_t *stream, int32_t *width, int32_t *height) {
     if (!f) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
     int rc;

@@ -1,12 +1,14 @@
 // The body of pt::integrate_kernel, pt::integrate_kernel_lens, their motion twins and pt::integrate_kernel_projection (pt_kernels.hip),
-// included inside each.  It sees the kernel's template arguments, its argument `a` and `constexpr bool LENS`, `MOTION` and `PROJ`,
-// which the including kernel defines.
+// included inside each.  It sees the kernel's template arguments, its argument `a` and `constexpr bool LENS`, `MOTION`, `PROJ` and
+// `ENVMAP`, which the including kernel defines.  ENVMAP (only pt::integrate_kernel_environment: false in every other kernel) = a miss
+// adds throughput x the handle's environment map (pt_hip.h: pt_environment_*; pt_environment.hpp spells the lookup) instead of the skybox.
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
     static_assert(!MOTION || CAM, "a motion kernel is the motion variant of a camera twin or of its lens kernel");
     static_assert(!PROJ || (CAM && !LENS && !MOTION), "a projection kernel is the projection variant of a camera twin; the host refuses a lens or a motion with it");
     static_assert(!NARROW || (!SKY && !STATS), "only the statistics-free, skybox-free kernels have a narrow variant");
+    static_assert(!ENVMAP || SKY, "an environment kernel is the environment variant of a skybox kernel: regeneration, no last-segment filter");
     constexpr int R = NARROW ? 1 : rays_per_lane<SKY, BIG, STATS>();   // pixels per lane: the wave's tile is kTileW * R x kTileH
     static_assert(POOL == 0 || ((POOL == 2 || POOL == 4) && (R == 2 || BIG) && !STATS && !SKY), "batches of the tile's pixels (a pixel's number takes 8 bits): the two-pixel kernel and the box-tree kernel");
     // REGEN = path regeneration: a lane whose path has ended starts its pixel's NEXT pass at once instead of idling until the
@@ -660,7 +662,13 @@
             bool contributed = false;
             if (PT_SLOT_ON(k) && valid[k]) {
                 if (hit[k] < 0) {
-                    if (SKY) {   // skybox miss shader, scene.cpp:126-154 (note: the path throughput is NOT applied)
+                    if constexpr (ENVMAP) {   // environment miss shader: throughput x L(direction), four 16-byte loads, no double
+                        const EnvironmentView ev = environment_view();
+                        float lr, lg, lb;
+                        env_lookup(ev.map(), ev.n(), q[k].dx, q[k].dy, q[k].dz, lr, lg, lb);
+                        contribute(k, tr[k] * lr, tg[k] * lg, tb[k] * lb);
+                        contributed = true;
+                    } else if (SKY) {   // skybox miss shader, scene.cpp:126-154 (note: the path throughput is NOT applied)
                         const float pi = 3.141593f;
                         const float theta = portable_acosf(q[k].dy) / pi;
                         const float phi = portable_atan2f(q[k].dz, -q[k].dx) / pi / 2 + 0.5f;

@@ -36,6 +36,7 @@
 #include "pt_fastfp.hpp"
 #include "pt_kernels.hpp"
 #include "pt_projection.hpp"
+#include "pt_environment.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1321,6 +1322,19 @@ __device__ __forceinline__ ProjectionView projection_view() {
     asm volatile("" : "+s"(p));
     return {p};
 }
+// The environment of an environment-kernel launch (RenderArgs::env_map, env_n), likewise: read where a ray has missed.
+struct EnvironmentView {
+    uint64_t p;
+    __device__ __forceinline__ const EnvTexel *map() const { return *reinterpret_cast<const EnvTexel *const __attribute__((address_space(4))) *>(p); }
+    __device__ __forceinline__ int32_t n() const {
+        return *reinterpret_cast<const __attribute__((address_space(4))) int32_t *>(p + (offsetof(RenderArgs, env_n) - offsetof(RenderArgs, env_map)));
+    }
+};
+__device__ __forceinline__ EnvironmentView environment_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, env_map);
+    asm volatile("" : "+s"(p));
+    return {p};
+}
 
 // What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
 // in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
@@ -1357,7 +1371,7 @@ constexpr int integrator_waves() {
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false;
 #include "pt_integrator_body.inc"
 }
 // The lens kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary ray
@@ -1373,7 +1387,7 @@ constexpr int lens_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (lens_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = false, PROJ = false;
+    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false;
 #include "pt_integrator_body.inc"
 }
 // The motion twins (pt_hip.h: camera motion): the camera twin and its lens kernel with the camera -- and the lens axes -- interpolated
@@ -1389,12 +1403,12 @@ constexpr int motion_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, false>())) void integrate_kernel_motion(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = true, PROJ = false;
+    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false;
 #include "pt_integrator_body.inc"
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, true>())) void integrate_kernel_motion_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = true, PROJ = false;
+    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false;
 #include "pt_integrator_body.inc"
 }
 // The projection kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary
@@ -1409,10 +1423,55 @@ constexpr int projection_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (projection_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_projection(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = true;
+    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false;
 #include "pt_integrator_body.inc"
 }
 
+#ifdef PT_ENVIRONMENT_UNIT
+// ---------------------------------------------------------------------------------------------------------------
+// The environment kernels (pt_environment_kernels.hip: this file compiled with PT_ENVIRONMENT_UNIT, a translation unit of its own,
+// so that the build of the kernels above takes no longer).  One per skybox kernel (BIG, STATS, ENV) and VIEW: plan views 0 .. 4 and
+// 5 = the projection kernel of view 1.  The body with SKY = true (path regeneration, the sky chunking, no last-segment filter) and
+// ENVMAP = true: a miss adds throughput x the octahedral map's radiance (pt_environment.hpp) instead of the skybox texel.
+// Waves per SIMD: the skybox twin's -- the lookup (a division, a dozen float operations, four 16-byte loads) peaks below the
+// skybox's double-precision acos and atan2 -- except where environment_waves says otherwise (tests/test_environment_resources.py
+// pins the list).
+template <bool BIG, bool STATS, bool ENV, int VIEW>
+constexpr int environment_waves() {
+    constexpr bool kLens = VIEW == 2 || VIEW == 4;
+    if constexpr (VIEW == 5) return projection_waves<true, BIG, STATS, ENV, false>();
+    else if constexpr (VIEW >= 3) return motion_waves<true, BIG, STATS, ENV, false, kLens>();
+    else if constexpr (VIEW == 2) return lens_waves<true, BIG, STATS, ENV, false>();
+    else return integrator_waves<true, BIG, STATS, ENV, false>();
+}
+template <bool BIG, bool STATS, bool ENV, int VIEW>
+__global__ __launch_bounds__(kBlock, (environment_waves<BIG, STATS, ENV, VIEW>())) void integrate_kernel_environment(const RenderArgs a) {
+    constexpr bool SKY = true, NARROW = false;
+    constexpr int ADAPT = VIEW != 0 ? 1 : 0;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true;
+#include "pt_integrator_body.inc"
+}
+namespace {
+using Kernel = void (*)(const RenderArgs);
+constexpr int kEnvironmentViews = plan::kViews + 1;
+template <int I>
+Kernel environment_kernel_of() {   // I = VIEW * 8 + (big, stats, env) as bits 2..0
+    return &integrate_kernel_environment<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0, I / 8>;
+}
+template <int... I>
+std::array<Kernel, sizeof...(I)> environment_kernel_table(std::integer_sequence<int, I...>) { return {environment_kernel_of<I>()...}; }
+const auto kEnvironmentKernels = environment_kernel_table(std::make_integer_sequence<int, 8 * kEnvironmentViews>());
+}  // namespace
+hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
+    if (!v.sky || v.narrow || v.pool || args.env_map == nullptr || args.env_n < kEnvMinSize || args.env_n > kEnvMaxSize || args.sky != nullptr)
+        return hipErrorInvalidValue;
+    if (args.projection != 0 && v.view != 1) return hipErrorInvalidDeviceFunction;
+    const int view = args.projection != 0 ? 5 : v.view;
+    const Kernel kernel = kEnvironmentKernels[view * 8 + (v.big ? 4 : 0) + (v.stats ? 2 : 0) + (v.env ? 1 : 0)];
+    hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
+    return hipGetLastError();
+}
+#else
 // First-hit feature pass under a projection (pt_hip.h: pt_render_features_host): the ray pt_projection states for pixel (x, y) with
 // jitter 0, for launch_trace_rays.  (Here and not beside the pinhole's feature_rays_kernel in pt_denoise.hip: the ray needs this
 // file's portable_sincos and normalize3.)
@@ -1529,7 +1588,7 @@ hipError_t launch_integrator(const RenderArgs &args0, const plan::Variant &v, hi
     static uint32_t *d_cnt = nullptr;
     const int rows = args0.row_end - args0.row_begin;
     if (rows <= 0 || args0.width <= 0) return hipSuccess;
-    if (!plan::variant_exists(v, kBuild) || args0.projection != 0) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
+    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
     if (!mod) {
         const char *path = std::getenv("PT_BLOCKPROF_HSACO");
         if (!path) return hipErrorInvalidValue;
@@ -1607,6 +1666,7 @@ Kernel kernel_for(const plan::Variant &v, bool projection) {
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
     const int rows = args.row_end - args.row_begin;
     if (rows <= 0 || args.width <= 0) return hipSuccess;
+    if (args.env_map != nullptr) return launch_environment_integrator(args, v, stream);   // (pt_environment_kernels.hip)
     const Kernel kernel = kernel_for(v, args.projection != 0);
     if (!kernel) return hipErrorInvalidDeviceFunction;
     hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
@@ -1649,5 +1709,6 @@ hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves) {
 #endif
 
 const plan::Build &integrator_build() { return kBuild; }
+#endif   // PT_ENVIRONMENT_UNIT
 
 }  // namespace pt

@@ -81,6 +81,11 @@ struct RenderArgs {
     // slots a lens would fill, lns[2 .. 10] (lns[0], lns[1] stay zero).
     int32_t projection;
     float prj_span[2];
+    // The handle's environment (pt_hip.h: pt_environment_*), appended likewise.  env_map != nullptr (never with sky): the launch runs
+    // the environment kernels (integrate_kernel_environment), planned as the skybox kernels of the same view (plan::Variant::sky;
+    // no ids of their own in the plan).  env_map = the (env_n + 2)^2 texels of the octahedral map with its apron, 16 bytes each.
+    const void *env_map;
+    int32_t env_n;
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif
@@ -89,8 +94,11 @@ struct RenderArgs {
 // The constants the kernels of this library were compiled with: what plan::plan_tiles needs to know of the build.
 const plan::Build &integrator_build();
 // launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds) -- with args.projection != 0
-// the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan
+// the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan;
+// with args.env_map != nullptr the environment kernel of skybox kernel `v` (v.sky), likewise
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+// the environment kernels' translation unit (pt_environment_kernels.hip); launch_integrator calls it, nothing else does
+hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached).  A projection launch asks for its
 // camera twin's: the projection kernels are compiled for their twins' waves per SIMD and LDS (tests/test_projection_resources.py)
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);

@@ -39,6 +39,10 @@
 // the full sphere, 360 x 180 degrees.  An unknown name ends the program; -APERTURE, -SHUTTER and -TEMPORAL are refused with a
 // projection other than perspective, with the library's message.  PT_RENDER_PRINT_CAMERA=1 then also prints
 // "projection <kind> <span_x> <span_y>".
+// An environment (pt_scene_set_environment_file, not in the reference): -ENV <file.hdr|file.pfm> lights the scene with an HDR panorama
+// (a miss adds throughput x radiance; it is the background too), -ENV_GAIN <g> scales it (default 1), -ENV_ROTATE <degrees> turns it
+// about +y (default 0), -ENV_SIZE <n> is the size of the octahedral map it is resampled into (default 0: by the picture's height).
+// -ENV together with -SKYBOX is refused; -ENV_GAIN, -ENV_ROTATE and -ENV_SIZE need -ENV.  Every other flag combines.
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -164,6 +168,8 @@ struct Options {
     bool camera = false;   // any of -EYE / -LOOKAT / -UP / -FOV / -ASPECT given
     std::string eye = "0,0,-20", lookat = "0,0,0", up = "0,1,0", eye_end, lookat_end;   // as given ("" = the start value)
     float fov = 53.13010235415598f, aspect = 0.0f;
+    std::string env, env_gain, env_rotate, env_size;   // -ENV / -ENV_GAIN / -ENV_ROTATE / -ENV_SIZE as given
+    pt_environment_params env_params = {1.0f, 0.0f, 0};
     std::string projection_name = "perspective", ortho_height;   // -PROJECTION / -ORTHO_HEIGHT as given
     pt_projection projection{};    // what they make; kind 0 (perspective) = none is set
     float view_height = 0.0f;      // -PROJECTION ortho: the height of the view in scene units
@@ -263,6 +269,10 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-FOV") { o.fov = static_cast<float>(std::atof(v)); o.camera = true; }
         if (f == "-ASPECT") { o.aspect = static_cast<float>(std::atof(v)); o.camera = true; }
         if (f == "-PROJECTION") o.projection_name = v;
+        if (f == "-ENV") o.env = v;
+        if (f == "-ENV_GAIN") o.env_gain = v;
+        if (f == "-ENV_ROTATE") o.env_rotate = v;
+        if (f == "-ENV_SIZE") o.env_size = v;
         if (f == "-ORTHO_HEIGHT") o.ortho_height = v;
         if (f == "-APERTURE") { o.aperture = v; o.aperture_given = true; }
         if (f == "-FOCUS") { o.focus = v; o.focus_given = true; }
@@ -430,6 +440,16 @@ int configure(int argc, char **argv, Options &o) {
     }
     // the camera's vectors, parsed here and nowhere else (without -EYE / -LOOKAT / -UP they are the defaults, which parse)
     const bool vectors = parse_vec3(o.eye, o.eye0) && parse_vec3(o.lookat, o.at0) && parse_vec3(o.up, o.up0);
+    // -ENV: an environment or a skybox, not both; its three knobs only with it
+    if (!o.env.empty() && !o.skybox.empty()) return refuse(2, "-ENV and -SKYBOX exclude each other: a scene has a skybox or an environment");
+    if (o.env.empty() && !(o.env_gain.empty() && o.env_rotate.empty() && o.env_size.empty())) return refuse(2, "-ENV_GAIN, -ENV_ROTATE and -ENV_SIZE need -ENV");
+    if (!o.env_gain.empty() && !(parse_float(o.env_gain, o.env_params.gain) && o.env_params.gain >= 0.0f)) return refuse(2, "-ENV_GAIN takes a gain >= 0");
+    if (!o.env_rotate.empty() && !parse_float(o.env_rotate, o.env_params.rotate_y_degrees)) return refuse(2, "-ENV_ROTATE takes an angle in degrees");
+    if (!o.env_size.empty()) {
+        float n = 0.0f;
+        if (!(parse_float(o.env_size, n) && n >= 8.0f && n <= 4096.0f && n == static_cast<float>(static_cast<int>(n)))) return refuse(2, "-ENV_SIZE takes a whole number in 8 .. 4096");
+        o.env_params.size = static_cast<int32_t>(n);
+    }
     // -PROJECTION: the kind by name, its angles from -FOV and -ASPECT; ortho needs a camera of its own (right and up are the view's extent)
     if (o.projection_name == "perspective") o.projection.kind = PT_PROJECTION_PERSPECTIVE;
     else if (o.projection_name == "ortho") o.projection.kind = PT_PROJECTION_ORTHOGRAPHIC;
@@ -1129,6 +1149,7 @@ int main(int argc, char **argv) {
     // to here may start the HIP runtime.
     if (pt_scene_load_obj(o.model_path.c_str(), o.model_name.c_str(), -1, &r.scene) != PT_OK) return die("pt_render");
     if (!o.skybox.empty() && pt_scene_set_skybox_bmp(r.scene, o.skybox.c_str()) != PT_OK) return die("pt_render");   // scene.cpp:20-22
+    if (!o.env.empty() && pt_scene_set_environment_file(r.scene, o.env.c_str(), &o.env_params) != PT_OK) return die("pt_render");
     if (o.camera && pt_scene_set_camera(r.scene, &o.view) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
     // and its projection -- set before the lens and the motion, which the library refuses on a handle with one, as it refuses the
     // temporal stage when the first frame reaches it: asked here, before any device is looked at, with the library's own words
