@@ -1506,6 +1506,65 @@ int pt_environment_from_equirect(int32_t w, int32_t h, const float *rgb, const p
 /* The lookup alone, on the host: rgb[3 i ..] = L(directions[3 i ..]). */
 int pt_environment_lookup(int32_t n, const float *map_rgb, int32_t n_dirs, const float *directions, float *rgb);
 
+/* ---- dielectric materials: refraction and Fresnel reflection (glass) ------------------------------------------------ */
+
+/* A scene handle may carry a list of DIELECTRICS.  It marks some of the scene's materials, addressed by index as usemtl addresses
+ * them, as smooth dielectrics: each entry has the material's index, a refractive index ior in 0.125 .. 8 (ior < 1: an air pocket seen
+ * from inside the denser medium; ior == 1 is allowed) and a transmission tint, each component in 0 .. 1.  A marked material is a
+ * dielectric and nothing else: the integrator does not look at its MTL lobes (Kd, Ks, Ns).  Without a list every output is what it was,
+ * and the launches go to the kernels they went to.
+ *
+ * The list belongs to the handle, as a skybox or an environment does: pt_scene_clone_to_device and pt_frame_create inherit it.  It
+ * works with every view, with a skybox, an environment or neither, with statistics, adaptive sampling and pass windows, in bands and
+ * frames, on small and box-tree scenes; launches are planned as without the list (the same tiles and chunks).  The diagnostic builds
+ * (phase timers, block profile) have no dielectric kernels: a render of a handle with a list is PT_ERR_UNSUPPORTED there.
+ * The first-hit feature pass, the temporal reprojection and every display stage are unchanged: a dielectric pixel's features are what
+ * its material's MTL fields give without the list.
+ *
+ * THE SHADING STEP of a segment whose ray (unit direction d, origin o) hits a triangle of a dielectric material at distance t.  N is
+ * the triangle's stored unit normal, p = o + d * t (per component, one product and one sum), col the path's throughput, eps the
+ * render's eps.  Every operation is a float operation rounded once, in the order written; nothing is fused; the root is correctly
+ * rounded, the divisions are IEEE divisions.  inv_ior = 1.0f / ior is formed once on the host.
+ *   c  = (N.x * d.x + N.y * d.y) + N.z * d.z
+ *   if c < 0:  n = N,   ci = -c,  eta = inv_ior        (entering)
+ *   else:      n = -N,  ci = c,   eta = ior            (leaving)
+ *   ci = ci < 1 ? ci : 1
+ *   s2 = (eta * eta) * (1 - ci * ci)
+ *   if !(s2 < 1):  F = 1                               (total internal reflection)
+ *   else:          ct = sqrt(1 - s2)
+ *                  rs = (eta * ci - ct) / (eta * ci + ct)
+ *                  rp = (ci - eta * ct) / (ci + eta * ct)
+ *                  F  = 0.5 * (rs * rs + rp * rp)      (unpolarised Fresnel reflectance)
+ *   u = ((w3 >> 9) << 1 | 1) * 2^-24                   (w3: the fourth word of the segment's own Philox call, whose first three
+ *                                                       words serve the lobes; u is the unit float every lobe uses)
+ *   if u < F:  r = d + n * (2 * ci),                 origin = p + n * eps,  col unchanged            (reflected)
+ *   else:      r = d * eta + n * (eta * ci - ct),    origin = p - n * eps,  col *= (tr, tg, tb)      (transmitted)
+ *   per component: r.x = d.x + n.x * (2 * ci), r.x = d.x * eta + n.x * (eta * ci - ct), origin.x = p.x + n.x * eps (or -), likewise y, z.
+ *   direction = r / |r| as every scattered ray is normalised: r * (1 / sqrt((r.x * r.x + r.y * r.y) + r.z * r.z)); depth + 1.
+ * The transmitted direction is the reference's own Refract (main.cpp:35-47) with eta in place of its constant.  A dielectric hit
+ * never contributes.  On a path's last segment (depth + 1 == max_ray_reflections) nothing of this is computed, as for the other
+ * scattering lobes, and the Philox call is made under the condition it is made under without the list.  There is no eta^2 radiance
+ * scaling and no absorption along the interior path: the tint is applied per transmission.
+ *
+ * PT_ERR_INVALID_ARGUMENT: a NULL handle, a NULL list with n > 0, n < 0, a material index outside the scene, an index listed twice,
+ * ior not finite or outside 0.125 .. 8, a tint component not finite or outside 0 .. 1, a material with an emissive lobe.  A setter
+ * validates, builds and uploads first and swaps last: a refused call leaves the handle as it was.  A host-only scene (device < 0)
+ * accepts and returns the list. */
+typedef struct pt_dielectric {
+    int32_t material;
+    float ior;
+    float tint[3];
+} pt_dielectric;
+
+/* NULL or n == 0 clears the list. */
+int pt_scene_set_dielectrics(pt_scene *scene, const pt_dielectric *list, int32_t n);
+/* *n = the number of entries (0 without a list); list (may be NULL) gets them, in the order given. */
+int pt_scene_get_dielectrics(const pt_scene *scene, pt_dielectric *list, int32_t *n);
+/* The same on a frame: every device's copy of the frame's scene takes the list; a refused call changes none of them.
+ * pt_frame_get_dielectrics answers for the root device's copy. */
+int pt_frame_set_dielectrics(pt_frame *frame, const pt_dielectric *list, int32_t n);
+int pt_frame_get_dielectrics(pt_frame *frame, pt_dielectric *list, int32_t *n);
+
 /* ---- misc ------------------------------------------------------------------------------------------- */
 int pt_abi_version(void);
 int pt_device_count(void);

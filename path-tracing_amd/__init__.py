@@ -61,7 +61,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_scene_set_environment_file", "pt_scene_set_environment_equirect", "pt_scene_set_environment_map",
                "pt_scene_get_environment", "pt_environment_from_equirect", "pt_environment_lookup",
                "pt_frame_set_environment_file", "pt_frame_set_environment_equirect", "pt_frame_set_environment_map",
-               "pt_frame_get_environment"]
+               "pt_frame_get_environment",
+               "pt_scene_set_dielectrics", "pt_scene_get_dielectrics", "pt_frame_set_dielectrics", "pt_frame_get_dielectrics"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -472,6 +473,20 @@ def environment_lookup(env_map, directions, library=None):
     return out
 
 
+class Dielectric(C.Structure):
+    """pt_dielectric: a material's index, its refractive index and its transmission tint."""
+    _fields_ = [("material", C.c_int32), ("ior", C.c_float), ("tint", C.c_float * 3)]
+
+    def __repr__(self):
+        return f"dielectric({self.material}, {self.ior!r}, tint={tuple(self.tint)!r})"
+
+
+def dielectric(material, ior, tint=(1.0, 1.0, 1.0)):
+    """One entry of a handle's dielectrics (-GLASS m:ior[:r:g:b]): material `material` is smooth glass of refractive index `ior`
+    whose transmitted light is multiplied by `tint`."""
+    return Dielectric(int(material), float(ior), (C.c_float * 3)(*tint))
+
+
 def _projection_arg(projection_, library):
     """A Projection, a kind (number or name) or None -> a pointer argument for pt_scene_set_projection / pt_frame_set_projection."""
     if projection_ is None:
@@ -597,6 +612,11 @@ def load_library(path):
     L.pt_frame_set_environment_equirect.argtypes = [vp, C.c_int32, C.c_int32, fp, ep]
     L.pt_frame_set_environment_map.argtypes = [vp, C.c_int32, fp]
     L.pt_frame_get_environment.argtypes = [vp, ip, fp]
+    dp = C.POINTER(Dielectric)
+    L.pt_scene_set_dielectrics.argtypes = [vp, dp, C.c_int32]
+    L.pt_scene_get_dielectrics.argtypes = [vp, dp, ip]
+    L.pt_frame_set_dielectrics.argtypes = [vp, dp, C.c_int32]
+    L.pt_frame_get_dielectrics.argtypes = [vp, dp, ip]
     L.pt_environment_from_equirect.argtypes = [C.c_int32, C.c_int32, fp, ep, C.c_int32, fp]
     L.pt_environment_lookup.argtypes = [C.c_int32, fp, C.c_int32, fp, fp]
     L.pt_render_features_host.argtypes = [vp, C.POINTER(RenderParams), ip, fp, fp, fp, fp]
@@ -738,7 +758,29 @@ class _EnvironmentMethods:
         return m
 
 
-class Scene(_EnvironmentMethods):
+class _DielectricMethods:
+    """set_dielectrics / dielectrics of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
+    _glass_prefix = "pt_scene_"
+
+    def set_dielectrics(self, entries):
+        """-GLASS: marks materials as smooth dielectrics.  `entries` is a list of pt.dielectric(material, ior, tint); None or an
+        empty list clears it.  Refused: an index outside the scene or listed twice, an ior outside 0.125 .. 8, a tint component
+        outside 0 .. 1, an emissive material."""
+        entries = list(entries or [])
+        arr = (Dielectric * len(entries))(*entries) if entries else None
+        _check(getattr(self._L, self._glass_prefix + "set_dielectrics")(self._h, arr, len(entries)), self._L)
+
+    def dielectrics(self):
+        """The handle's dielectrics, a list of Dielectric in the order given ([] without any)."""
+        get = getattr(self._L, self._glass_prefix + "get_dielectrics")
+        n = C.c_int32()
+        _check(get(self._h, None, C.byref(n)), self._L)
+        arr = (Dielectric * max(n.value, 1))()
+        _check(get(self._h, arr, C.byref(n)), self._L)
+        return [dielectric(e.material, e.ior, tuple(e.tint)) for e in arr[:n.value]]
+
+
+class Scene(_EnvironmentMethods, _DielectricMethods):
     """Owns a pt_scene handle (Scene + LoadModel of the reference, scene.h:17-19)."""
 
     def __init__(self, handle, library=None):
@@ -1461,9 +1503,9 @@ def bvh_depth(nodes):
     return int(level.max())
 
 
-class Frame(_EnvironmentMethods):
+class Frame(_EnvironmentMethods, _DielectricMethods):
     """pt_frame: one image on several devices from one host program -- row bands, one gather to the first device."""
-    _env_prefix = "pt_frame_"
+    _env_prefix = _glass_prefix = "pt_frame_"
 
     def __init__(self, scene, devices, width, height, flags=0):
         self._scene, self._L = scene, scene._L

@@ -115,6 +115,7 @@ int upload(pt_scene *s, int device) {
         s->sky_h = s->sky->h;
     }
     if (s->env && (rc = s->d_env.upload(pt::env_with_apron(s->env->n, s->env->rgb.data()), "environment map", 64)) != PT_OK) return rc;
+    if (s->glass && (rc = s->d_glass.upload(s->glass->table, "dielectric table", 64)) != PT_OK) return rc;
     return PT_OK;
 }
 
@@ -277,6 +278,7 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
         a.env_map = scene->d_env.get<void>();
         a.env_n = scene->env->n;
     }
+    if (scene->glass && scene->d_glass) a.glass = scene->d_glass.get<void>();   // the dielectric kernels of whichever kernels the launch is planned as (integrate_kernel_glass)
     a.n_clusters = static_cast<int32_t>(t.clusters.size());
     a.n_tri = scene->shared->host.n_tri();
     a.big = t.big ? 1 : 0;
@@ -398,7 +400,9 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
         PT_HIP_TRY(hipMemsetAsync(ctx.d_stats.get<void>(), 0, 24 * sizeof(unsigned long long), stream));
         PT_HIP_TRY(hipEventRecord(ctx.ev0.get(), stream));
     }
-    PT_HIP_TRY(pt::launch_integrator(a, tiles.variant, stream));
+    const hipError_t launched = pt::launch_integrator(a, tiles.variant, stream);
+    if (launched == hipErrorNotSupported && a.glass != nullptr) return fail(PT_ERR_UNSUPPORTED, "dielectrics: this diagnostic build of the library has no dielectric kernels");
+    PT_HIP_TRY(launched);
     if (want_stats) PT_HIP_TRY(hipEventRecord(ctx.ev1.get(), stream));
     PT_HIP_TRY(hipEventRecord(ctx.ev_done.get(), stream));
     ctx.has_prev = true;
@@ -622,6 +626,7 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->shared = src->shared;   // parsed model, tables, hierarchies built so far
     s->sky = src->sky;         // the skybox of the handle the copy is made from
     s->env = src->env;         // or its environment
+    s->glass = src->glass;     // and its dielectrics
     s->has_camera = src->has_camera;   // and its camera
     s->camera = src->camera;
     s->has_lens = src->has_lens;       // and lens

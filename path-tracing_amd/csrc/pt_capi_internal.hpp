@@ -60,6 +60,13 @@ struct pt_env_map {
     int n = 0;
 };
 
+// The dielectrics of a handle (pt_hip.h: pt_dielectric): the list as given and the per-material table the kernels read
+// (pt_kernels.hpp: GlassRec, one per material of the scene).  Belongs to the handle as the environment does; immutable once set.
+struct pt_glass_list {
+    std::vector<pt_dielectric> list;
+    std::vector<pt::GlassRec> table;
+};
+
 // Device copy of one CullTables (they depend on eps and on the envelope the camera needs; a scene keeps the one of its last
 // render).
 struct DeviceCull {
@@ -94,6 +101,8 @@ struct pt_scene {
     int sky_w = 0, sky_h = 0;
     std::shared_ptr<const pt_env_map> env;      // this handle's environment (nullptr = none; never with a skybox); copies inherit it
     ptc::DeviceBuffer d_env;       // its (n + 2)^2 texels with the apron (pt_environment.hpp: EnvTexel) on this copy's device
+    std::shared_ptr<const pt_glass_list> glass; // this handle's dielectrics (nullptr = none); copies inherit them
+    ptc::DeviceBuffer d_glass;     // their table on this copy's device
     bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
     pt_camera camera{};
     bool has_lens = false;         // this handle's lens (pt_scene_set_lens; radius > 0); copies made from it inherit it
@@ -376,7 +385,7 @@ void temporal_commit(pt_temporal *t);
 
 // What a display needs of a frame: gathers if a band changed and waits, as pt_frame_read does; then the root device's copy of
 // the scene, its full-frame planes and the root band's stream.
-// Every device's copy of a frame's scene (owned by the frame), for the setters that live outside pt_frame.cpp (pt_environment_capi.cpp).
+// Every device's copy of a frame's scene (owned by the frame), for the setters that live outside pt_frame.cpp (pt_environment_capi.cpp, pt_glass_capi.cpp).
 const std::vector<pt_scene *> &frame_scenes(pt_frame *f);
 int frame_root_planes(pt_frame *f, pt_scene **scene, AccumPlanes *planes, hipStream_t *stream, int32_t *width, int32_t *height);
 

@@ -2,6 +2,8 @@
 // included inside each.  It sees the kernel's template arguments, its argument `a` and `constexpr bool LENS`, `MOTION`, `PROJ` and
 // `ENVMAP`, which the including kernel defines.  ENVMAP (only pt::integrate_kernel_environment: false in every other kernel) = a miss
 // adds throughput x the handle's environment map (pt_hip.h: pt_environment_*; pt_environment.hpp spells the lookup) instead of the skybox.
+// GLASS (only pt::integrate_kernel_glass: false in every other kernel) = a hit on a material the handle's dielectric table marks
+// (pt_hip.h: pt_dielectric) reflects or refracts by the Fresnel term instead of running the material's lobes.
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
@@ -733,6 +735,15 @@
                         const float sample = unit_float(w0);
                         kind = (sample - m0v.w > 0) ? m2v.z : m2v.y;
                     }
+                    // GLASS: a material the handle's table marks is a dielectric and nothing else (kind 3; never emissive: the setter
+                    // refuses that, so the Philox call above was made under the condition it is made under without the table)
+                    [[maybe_unused]] const GlassRec *grec = nullptr;
+                    [[maybe_unused]] float g_ior = 0.0f;
+                    if constexpr (GLASS) {
+                        grec = glass_view() + mi;
+                        g_ior = grec->ior;
+                        if (g_ior != 0.0f) kind = 3;
+                    }
                     if (kind < 0) {
                         depth[k] = mrr;
                     } else if (kind == 0) {   // emissive, material.h:68-79
@@ -750,6 +761,41 @@
                         // (Ray::IsValid, ray.h:52-54), so it is not computed either.
                         if (depth[k] + 1 < mrr) {
                         float rx, ry, rz, fr, fg, fb;
+                        [[maybe_unused]] float oe = eps;   // GLASS: +-eps, the side of the surface the next ray starts on
+                        bool dielectric = false;
+                        if constexpr (GLASS) dielectric = kind == 3;
+                        if (dielectric) {   // smooth dielectric (pt_hip.h: pt_dielectric states this operation by operation)
+                            if constexpr (GLASS) {
+                                const float c = (pl.x * q[k].dx + pl.y * q[k].dy) + pl.z * q[k].dz;
+                                const bool entering = c < 0;   // n = N entering, -N leaving: below, n's sign rides on the factors of N
+                                const float eta = entering ? grec->inv_ior : g_ior;
+                                float ci = entering ? -c : c;
+                                ci = ci < 1 ? ci : 1;
+                                const float s2 = (eta * eta) * (1 - ci * ci);
+                                const float ec = eta * ci;
+                                float fresnel = 1.0f, ct = 0.0f;
+                                if (s2 < 1) {   // (else total internal reflection; 1 - s2 is in [2^-24, 1])
+                                    ct = sqrt_rn_normal(1 - s2);
+                                    const float et = eta * ct;
+                                    const float rs = (ec - ct) / (ec + ct), rp = (ci - et) / (ci + et);
+                                    fresnel = 0.5f * (rs * rs + rp * rp);
+                                }
+                                float dm, nk;   // the new direction d * dm + n * nk
+                                if (unit_float(w3) < fresnel) {   // reflected: from the side the ray came from, throughput unchanged
+                                    dm = 1.0f; nk = 2 * ci;
+                                    oe = entering ? eps : -eps;
+                                    fr = fg = fb = 1.0f;
+                                } else {   // transmitted: the reference's Refract (main.cpp:35-47) with eta; from the far side, tinted
+                                    dm = eta; nk = ec - ct;
+                                    oe = entering ? -eps : eps;
+                                    fr = grec->tint[0]; fg = grec->tint[1]; fb = grec->tint[2];
+                                }
+                                if (!entering) nk = -nk;
+                                rx = q[k].dx * dm + pl.x * nk; ry = q[k].dy * dm + pl.y * nk; rz = q[k].dz * dm + pl.z * nk;
+                            } else {
+                                __builtin_unreachable();
+                            }
+                        } else
                         if (kind == 1) {   // glossy, material.h:83-85
                             const float dn = (pl.x * q[k].dx + pl.y * q[k].dy) + pl.z * q[k].dz;
                             rx = q[k].dx - pl.x * dn * 2.0f; ry = q[k].dy - pl.y * dn * 2.0f; rz = q[k].dz - pl.z * dn * 2.0f;
@@ -768,7 +814,11 @@
                             fr = m0v.x * dt; fg = m0v.y * dt; fb = m0v.z * dt;
                         }
                         normalize3(rx, ry, rz);   // Ray::Reflect normalises (again), ray.h:47
+                        if constexpr (GLASS) {   // p + n eps or p - n eps: the sign is exact, N * (-eps) = -(N * eps)
+                            q[k].ox = px + pl.x * oe; q[k].oy = py + pl.y * oe; q[k].oz = pz + pl.z * oe;
+                        } else {
                         q[k].ox = px + pl.x * eps; q[k].oy = py + pl.y * eps; q[k].oz = pz + pl.z * eps;
+                        }
                         q[k].dx = rx; q[k].dy = ry; q[k].dz = rz;
                         tr[k] *= fr; tg[k] *= fg; tb[k] *= fb;
                         }

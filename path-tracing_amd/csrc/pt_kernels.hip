@@ -1335,6 +1335,12 @@ __device__ __forceinline__ EnvironmentView environment_view() {
     asm volatile("" : "+s"(p));
     return {p};
 }
+// The dielectric table of a dielectric-kernel launch (RenderArgs::glass), likewise: read where a ray has hit a triangle.
+__device__ __forceinline__ const GlassRec *glass_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, glass);
+    asm volatile("" : "+s"(p));
+    return *reinterpret_cast<const GlassRec *const __attribute__((address_space(4))) *>(p);
+}
 
 // What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
 // in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
@@ -1371,7 +1377,7 @@ constexpr int integrator_waves() {
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false;
 #include "pt_integrator_body.inc"
 }
 // The lens kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary ray
@@ -1387,7 +1393,7 @@ constexpr int lens_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (lens_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false;
+    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false;
 #include "pt_integrator_body.inc"
 }
 // The motion twins (pt_hip.h: camera motion): the camera twin and its lens kernel with the camera -- and the lens axes -- interpolated
@@ -1403,12 +1409,12 @@ constexpr int motion_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, false>())) void integrate_kernel_motion(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false;
+    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false;
 #include "pt_integrator_body.inc"
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, true>())) void integrate_kernel_motion_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false;
+    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false;
 #include "pt_integrator_body.inc"
 }
 // The projection kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary
@@ -1423,7 +1429,7 @@ constexpr int projection_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (projection_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_projection(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false;
 #include "pt_integrator_body.inc"
 }
 
@@ -1448,7 +1454,7 @@ template <bool BIG, bool STATS, bool ENV, int VIEW>
 __global__ __launch_bounds__(kBlock, (environment_waves<BIG, STATS, ENV, VIEW>())) void integrate_kernel_environment(const RenderArgs a) {
     constexpr bool SKY = true, NARROW = false;
     constexpr int ADAPT = VIEW != 0 ? 1 : 0;
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false;
 #include "pt_integrator_body.inc"
 }
 namespace {
@@ -1468,6 +1474,74 @@ hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Var
     if (args.projection != 0 && v.view != 1) return hipErrorInvalidDeviceFunction;
     const int view = args.projection != 0 ? 5 : v.view;
     const Kernel kernel = kEnvironmentKernels[view * 8 + (v.big ? 4 : 0) + (v.stats ? 2 : 0) + (v.env ? 1 : 0)];
+    hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
+    return hipGetLastError();
+}
+#elif defined(PT_GLASS_UNIT)
+// ---------------------------------------------------------------------------------------------------------------
+// The dielectric kernels (pt_glass_kernels.hip: this file compiled with PT_GLASS_UNIT, a translation unit of its own).  The body
+// with GLASS = true: a hit on a material the handle's table marks (RenderArgs::glass, pt_hip.h: pt_dielectric) reflects or refracts.
+// One per kernel a launch can be planned as, and VIEW (plan views 0 .. 4 and 5 = the projection kernel of view 1):
+//   MISS  0 = no miss shader, 1 = skybox, 2 = environment (the body with SKY and ENVMAP as in integrate_kernel_environment)
+//   FORM  0 = the wide kernel, 1 = its 8 x 8 form, 2 / 3 = the batch kernel over 16 x 8 / 32 x 8 tiles (forms 1 - 3: MISS 0, no statistics)
+// The envelope test is not a parameter: forms 0 and 1 always carry it (ENV = true).  A launch planned as the twin without it runs
+// the kernel with it -- the same tiles, one compare per segment more, and nothing is culled for an origin outside the envelope, so the
+// closest hit is the same by construction.  The batch kernels are not built with the test (plan::variant_exists) and never planned
+// for a scene that needs it.  Waves per SIMD: the twin's (with ENV as instantiated here) minus glass_fewer_waves
+// (tests/test_glass_resources.py pins every kernel).
+template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int VIEW>
+constexpr int view_waves() {
+    constexpr bool kLens = VIEW == 2 || VIEW == 4;
+    if constexpr (VIEW == 5) return projection_waves<SKY, BIG, STATS, ENV, NARROW>();
+    else if constexpr (VIEW >= 3) return motion_waves<SKY, BIG, STATS, ENV, NARROW, kLens>();
+    else if constexpr (VIEW == 2) return lens_waves<SKY, BIG, STATS, ENV, NARROW>();
+    else return integrator_waves<SKY, BIG, STATS, ENV, NARROW>();
+}
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+constexpr int glass_fewer_waves() {
+    // At their twins' 5 waves and 96 VGPRs these spilled vector registers to scratch: the skybox kernels that are not compiled for 4
+    // anyway (6 VGPRs: the dielectric's operands meet the skybox lookup's double-precision registers), and the lens, motion and
+    // projection forms of the two-pixel small-scene kernel (1 VGPR).  They are compiled for a wave fewer.
+    if constexpr (MISS == 1 && !(BIG && STATS)) return (VIEW == 0 || VIEW == 1 || VIEW == 3 || VIEW == 5) ? 1 : 0;
+    else if constexpr (MISS == 0 && !BIG && !STATS && FORM == 0) return (VIEW == 2 || VIEW == 3 || VIEW == 5) ? 1 : 0;
+    else return 0;
+}
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+__global__ __launch_bounds__(kBlock, (view_waves<MISS != 0, BIG, STATS, FORM < 2, FORM == 1, VIEW>() - glass_fewer_waves<MISS, BIG, STATS, FORM, VIEW>()))
+void integrate_kernel_glass(const RenderArgs a) {
+    constexpr bool SKY = MISS != 0, ENV = FORM < 2, NARROW = FORM == 1;
+    constexpr int ADAPT = (FORM == 2 ? 2 : FORM == 3 ? 4 : 0) | (VIEW != 0 ? 1 : 0);
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true;
+#include "pt_integrator_body.inc"
+}
+namespace {
+using Kernel = void (*)(const RenderArgs);
+constexpr int kGlassViews = plan::kViews + 1, kGlassPerView = 3 * 2 * 2 * 4;
+// does the build have the twin of that kernel?  (the 8 x 8 form and the batch kernels: plan::variant_exists)
+template <int MISS, bool BIG, bool STATS, int FORM>
+constexpr bool glass_kernel_exists() {
+    if constexpr (FORM == 0) return true;
+    else if constexpr (MISS != 0 || STATS) return false;
+    else return plan::variant_exists({false, BIG, false, FORM == 1, FORM == 1, FORM == 2 ? 2 : FORM == 3 ? 4 : 0, 1}, kBuild);
+}
+template <int I>
+Kernel glass_kernel_of() {   // I = (VIEW * 3 + MISS) * 16 + (big, stats) as bits 3..2 + FORM
+    constexpr int kMiss = (I / 16) % 3, kForm = I & 3;
+    constexpr bool kBig = (I & 8) != 0, kStats = (I & 4) != 0;
+    if constexpr (!glass_kernel_exists<kMiss, kBig, kStats, kForm>()) return nullptr;
+    else return &integrate_kernel_glass<kMiss, kBig, kStats, kForm, I / 48>;
+}
+template <int... I>
+std::array<Kernel, sizeof...(I)> glass_kernel_table(std::integer_sequence<int, I...>) { return {glass_kernel_of<I>()...}; }
+const auto kGlassKernels = glass_kernel_table(std::make_integer_sequence<int, kGlassPerView * kGlassViews>());
+}  // namespace
+hipError_t launch_glass_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
+    if (args.glass == nullptr || (args.env_map != nullptr && (!v.sky || args.sky != nullptr))) return hipErrorInvalidValue;
+    if (args.projection != 0 && v.view != 1) return hipErrorInvalidDeviceFunction;
+    const int view = args.projection != 0 ? 5 : v.view;
+    const int miss = args.env_map != nullptr ? 2 : v.sky ? 1 : 0, form = v.narrow ? 1 : v.pool == 2 ? 2 : v.pool == 4 ? 3 : 0;
+    const Kernel kernel = kGlassKernels[(view * 3 + miss) * 16 + (v.big ? 8 : 0) + (v.stats ? 4 : 0) + form];
+    if (!kernel) return hipErrorInvalidDeviceFunction;
     hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
     return hipGetLastError();
 }
@@ -1588,7 +1662,7 @@ hipError_t launch_integrator(const RenderArgs &args0, const plan::Variant &v, hi
     static uint32_t *d_cnt = nullptr;
     const int rows = args0.row_end - args0.row_begin;
     if (rows <= 0 || args0.width <= 0) return hipSuccess;
-    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
+    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr || args0.glass != nullptr) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
     if (!mod) {
         const char *path = std::getenv("PT_BLOCKPROF_HSACO");
         if (!path) return hipErrorInvalidValue;
@@ -1666,6 +1740,7 @@ Kernel kernel_for(const plan::Variant &v, bool projection) {
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
     const int rows = args.row_end - args.row_begin;
     if (rows <= 0 || args.width <= 0) return hipSuccess;
+    if (args.glass != nullptr) return launch_glass_integrator(args, v, stream);   // (pt_glass_kernels.hip)
     if (args.env_map != nullptr) return launch_environment_integrator(args, v, stream);   // (pt_environment_kernels.hip)
     const Kernel kernel = kernel_for(v, args.projection != 0);
     if (!kernel) return hipErrorInvalidDeviceFunction;
@@ -1706,6 +1781,11 @@ hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves) {
     if (n > 0) *waves = n;
     return e;
 }
+#endif
+
+#if defined(PT_PHASE_TIMERS) || defined(PT_BLOCK_PROFILE)
+// the diagnostic builds are linked without the dielectric kernels' unit: a handle with dielectrics is refused (PT_ERR_UNSUPPORTED)
+hipError_t launch_glass_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
 const plan::Build &integrator_build() { return kBuild; }

@@ -18,6 +18,12 @@ constexpr uint32_t kPhiloxKey1 = 0x50544831u;   // "PTH1": second Philox key wor
 // of running that code in every other iteration (5 753 against 5 287 at 1, 5 790 at 8; r04_ab_logs.txt regen3).
 constexpr uint32_t regen_min_dead_for(int mrr) { return mrr >= 5 ? 4u : 64u; }
 
+// One material's entry of the dielectric table (RenderArgs::glass): ior == 0 = not a dielectric.  inv_ior = 1.0f / ior, formed once on the host.
+struct GlassRec {
+    float ior, inv_ior, pad0, pad1;
+    float tint[3], pad2;
+};
+
 struct RenderArgs {
     const ClusterDesc *clusters;   // cull hierarchy (pt_scene.hpp: CullTables), read through the scalar cache
     const SphereRec *spheres;
@@ -86,6 +92,10 @@ struct RenderArgs {
     // no ids of their own in the plan).  env_map = the (env_n + 2)^2 texels of the octahedral map with its apron, 16 bytes each.
     const void *env_map;
     int32_t env_n;
+    // The handle's dielectrics (pt_hip.h: pt_dielectric), appended likewise.  glass != nullptr: the launch runs the dielectric kernels
+    // (integrate_kernel_glass, pt_glass_kernels.hip), planned as the kernels the same launch would run without the list (no ids of
+    // their own in the plan).  glass = n_mats records of 32 bytes (GlassRec below), read only where a ray has hit a triangle.
+    const void *glass;
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif
@@ -95,10 +105,13 @@ struct RenderArgs {
 const plan::Build &integrator_build();
 // launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds) -- with args.projection != 0
 // the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan;
-// with args.env_map != nullptr the environment kernel of skybox kernel `v` (v.sky), likewise
+// with args.env_map != nullptr the environment kernel of skybox kernel `v` (v.sky), likewise; with args.glass != nullptr the dielectric
+// kernel of whichever of those the launch would run (hipErrorNotSupported from a diagnostic build, which has none)
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the environment kernels' translation unit (pt_environment_kernels.hip); launch_integrator calls it, nothing else does
 hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+// the dielectric kernels' translation unit (pt_glass_kernels.hip), likewise
+hipError_t launch_glass_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached).  A projection launch asks for its
 // camera twin's: the projection kernels are compiled for their twins' waves per SIMD and LDS (tests/test_projection_resources.py)
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);

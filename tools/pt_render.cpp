@@ -43,6 +43,10 @@
 // (a miss adds throughput x radiance; it is the background too), -ENV_GAIN <g> scales it (default 1), -ENV_ROTATE <degrees> turns it
 // about +y (default 0), -ENV_SIZE <n> is the size of the octahedral map it is resampled into (default 0: by the picture's height).
 // -ENV together with -SKYBOX is refused; -ENV_GAIN, -ENV_ROTATE and -ENV_SIZE need -ENV.  Every other flag combines.
+// Dielectric materials (pt_scene_set_dielectrics, not in the reference): -GLASS m:ior[:r:g:b][,m:ior[:r:g:b]...] makes material m of
+// the model (counted as usemtl counts them) smooth glass of refractive index ior (0.125 .. 8) whose transmitted light is multiplied
+// by the tint r:g:b (each 0 .. 1, default 1:1:1), e.g. -GLASS 4:1.5 or -GLASS 4:1.5:0.9:1:0.9,2:1.33.  A malformed entry, a value out
+// of range, an index outside the model and an emissive material end the program with status 2.  Every other flag combines.
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -170,6 +174,8 @@ struct Options {
     float fov = 53.13010235415598f, aspect = 0.0f;
     std::string env, env_gain, env_rotate, env_size;   // -ENV / -ENV_GAIN / -ENV_ROTATE / -ENV_SIZE as given
     pt_environment_params env_params = {1.0f, 0.0f, 0};
+    std::string glass_text;                // -GLASS as given
+    std::vector<pt_dielectric> glass;      // what it makes
     std::string projection_name = "perspective", ortho_height;   // -PROJECTION / -ORTHO_HEIGHT as given
     pt_projection projection{};    // what they make; kind 0 (perspective) = none is set
     float view_height = 0.0f;      // -PROJECTION ortho: the height of the view in scene units
@@ -273,6 +279,7 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-ENV_GAIN") o.env_gain = v;
         if (f == "-ENV_ROTATE") o.env_rotate = v;
         if (f == "-ENV_SIZE") o.env_size = v;
+        if (f == "-GLASS") o.glass_text = v;
         if (f == "-ORTHO_HEIGHT") o.ortho_height = v;
         if (f == "-APERTURE") { o.aperture = v; o.aperture_given = true; }
         if (f == "-FOCUS") { o.focus = v; o.focus_given = true; }
@@ -449,6 +456,29 @@ int configure(int argc, char **argv, Options &o) {
         float n = 0.0f;
         if (!(parse_float(o.env_size, n) && n >= 8.0f && n <= 4096.0f && n == static_cast<float>(static_cast<int>(n)))) return refuse(2, "-ENV_SIZE takes a whole number in 8 .. 4096");
         o.env_params.size = static_cast<int32_t>(n);
+    }
+    // -GLASS: entries m:ior or m:ior:r:g:b, separated by commas; the values' ranges are the library's (pt_hip.h: pt_dielectric)
+    for (size_t at = 0; !o.glass_text.empty() && at <= o.glass_text.size();) {
+        const size_t comma = std::min(o.glass_text.find(',', at), o.glass_text.size());
+        const std::string entry = o.glass_text.substr(at, comma - at);
+        at = comma + 1;
+        std::vector<std::string> part;
+        for (size_t b = 0; b <= entry.size();) {
+            const size_t colon = std::min(entry.find(':', b), entry.size());
+            part.push_back(entry.substr(b, colon - b));
+            b = colon + 1;
+        }
+        float m = 0.0f;
+        pt_dielectric d = {0, 0.0f, {1.0f, 1.0f, 1.0f}};
+        bool ok = (part.size() == 2 || part.size() == 5) && parse_float(part[0], m) && m >= 0.0f && m <= 16777216.0f &&
+                  m == static_cast<float>(static_cast<int32_t>(m)) && part[0].find_first_not_of("0123456789") == std::string::npos && parse_float(part[1], d.ior);
+        for (size_t c = 2; ok && c < part.size(); ++c) ok = parse_float(part[c], d.tint[c - 2]);
+        if (!ok) return refuse(2, "-GLASS takes m:ior or m:ior:r:g:b entries separated by commas, not \"" + entry + "\"");
+        if (!(d.ior >= 0.125f && d.ior <= 8.0f)) return refuse(2, "-GLASS: ior must lie in 0.125 .. 8, not " + part[1]);
+        for (float t : d.tint)
+            if (!(t >= 0.0f && t <= 1.0f)) return refuse(2, "-GLASS: a tint component must lie in 0 .. 1 (\"" + entry + "\")");
+        d.material = static_cast<int32_t>(m);
+        o.glass.push_back(d);
     }
     // -PROJECTION: the kind by name, its angles from -FOV and -ASPECT; ortho needs a camera of its own (right and up are the view's extent)
     if (o.projection_name == "perspective") o.projection.kind = PT_PROJECTION_PERSPECTIVE;
@@ -1150,6 +1180,8 @@ int main(int argc, char **argv) {
     if (pt_scene_load_obj(o.model_path.c_str(), o.model_name.c_str(), -1, &r.scene) != PT_OK) return die("pt_render");
     if (!o.skybox.empty() && pt_scene_set_skybox_bmp(r.scene, o.skybox.c_str()) != PT_OK) return die("pt_render");   // scene.cpp:20-22
     if (!o.env.empty() && pt_scene_set_environment_file(r.scene, o.env.c_str(), &o.env_params) != PT_OK) return die("pt_render");
+    // -GLASS: what only the model can decide -- an index outside it, listed twice, an emissive material -- is refused here, with the library's words
+    if (!o.glass.empty() && pt_scene_set_dielectrics(r.scene, o.glass.data(), static_cast<int32_t>(o.glass.size())) != PT_OK) return refuse(2, pt_last_error());
     if (o.camera && pt_scene_set_camera(r.scene, &o.view) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
     // and its projection -- set before the lens and the motion, which the library refuses on a handle with one, as it refuses the
     // temporal stage when the first frame reaches it: asked here, before any device is looked at, with the library's own words
