@@ -550,6 +550,31 @@ void orc_closest_hit_batch(const orc_scene *s, int n, const float *o, const floa
     }
 }
 
+/* What the strict '<' of triangles.h:51 decides silently: for each ray the closest hit (idx, t: the lowest index among the
+ * triangles accepted at the smallest distance), the HIGHEST index accepted at the bit-identical distance (last; = idx when
+ * there is no tie, -1 on a miss), and whether a triangle of another material is among those tied (other_material). */
+void orc_closest_hit_ties(const orc_scene *s, int n, const float *o, const float *d, float eps, int *idx, float *t, int *last,
+                          unsigned char *other_material, int threads) {
+#ifdef _OPENMP
+    if (threads <= 0) threads = omp_get_max_threads();
+#else
+    threads = 1;
+#endif
+#pragma omp parallel for schedule(static, 256) num_threads(threads)
+    for (int i = 0; i < n; ++i) {
+        const float *oi = o + 3 * (size_t)i, *di = d + 3 * (size_t)i;
+        idx[i] = last[i] = orc_closest_hit(s, oi, di, eps, t + i);
+        other_material[i] = 0;
+        if (idx[i] < 0 || t[i] != t[i]) continue;
+        for (int j = idx[i] + 1; j < s->n_tri; ++j) {
+            float dist = nextafterf(t[i], INFINITY);      /* Intersect rejects nd >= dist: only nd <= t passes, and t is the minimum */
+            if (tri_intersect(&s->tri[j], oi, di, eps, &dist) != 4 || dist != t[i]) continue;
+            last[i] = j;
+            if (s->tri[j].material != s->tri[idx[i]].material) other_material[i] = 1;
+        }
+    }
+}
+
 /* ------------------------------------------------------------------ */
 /* Path state and shading                                               */
 /* ------------------------------------------------------------------ */

@@ -64,6 +64,8 @@ def lib():
         L.orc_write_bmp.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]
         L.orc_closest_hit.argtypes = [vp, fp, fp, C.c_float, fp]
         L.orc_closest_hit_batch.argtypes = [vp, C.c_int, fp, fp, C.c_float, ip, fp, C.POINTER(C.c_ubyte), C.c_int]
+        L.orc_closest_hit_ties.restype = None
+        L.orc_closest_hit_ties.argtypes = [vp, C.c_int, fp, fp, C.c_float, ip, fp, ip, C.POINTER(C.c_ubyte), C.c_int]
         L.orc_probe_minstd.argtypes = [C.c_uint32, C.c_int, C.POINTER(C.c_uint32), fp, C.POINTER(C.c_double)]
         L.orc_probe_philox.argtypes = [C.POINTER(C.c_uint32)] * 3
         L.orc_probe_unit_float.restype = C.c_float
@@ -174,6 +176,18 @@ class Scene:
         lib().orc_closest_hit_batch(self.h, len(o), _fp(o), _fp(d), eps, _ip(idx), _fp(t),
                                     nan_seen.ctypes.data_as(C.POINTER(C.c_ubyte)), threads)
         return idx, t, nan_seen.astype(bool)
+
+    def closest_hit_ties(self, origins, directions, eps=1e-4, threads=0):
+        """closest_hits' idx and t, then the HIGHEST index accepted at the bit-identical distance (idx where nothing ties, -1 on a
+        miss) and whether a triangle of another material is among the tied ones."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        idx, last = np.zeros(len(o), np.int32), np.zeros(len(o), np.int32)
+        t = np.zeros(len(o), np.float32)
+        other = np.zeros(len(o), np.uint8)
+        lib().orc_closest_hit_ties(self.h, len(o), _fp(o), _fp(d), eps, _ip(idx), _fp(t), _ip(last),
+                                   other.ctypes.data_as(C.POINTER(C.c_ubyte)), threads)
+        return idx, t, last, other.astype(bool)
 
     def __del__(self):
         try:

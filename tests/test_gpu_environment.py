@@ -14,6 +14,7 @@ import pytest
 import environment_composition as EC
 import environment_restatement as E
 import oracle_lib as O
+from glass_fuzz_scenes import _sliver_scene
 
 pt = importlib.import_module("path-tracing_amd")
 pytestmark = pytest.mark.gpu
@@ -173,30 +174,6 @@ def test_box_tree_frames_equal_the_composition(gpu, tmp_path):
     _check(scene, osc, env, _sample(W, H, n=20), 3, 3, **_set_view(scene, "camera"))
     _check(scene, osc, env, _sample(W, H, n=20), 3, 3, stats=True, **_set_view(scene, "free"))
     scene.close()
-
-
-def _sliver_scene(d, n_small, seed):
-    """An OPEN scene whose paths can leave the culling envelope: n_small random triangles around (0, 0, -6), every 17th a sliver (the
-    recipe of tests/test_gpu_fuzz.py), one triangle whose vertices are exactly collinear, six large ones, an emitter among them."""
-    rng = np.random.default_rng(seed)
-    open(d + "f.mtl", "w").write("newmtl 0\nKe 1 1 1\nKd 0.9 0.7 0.5\nnewmtl 1\nNs 300\nKs 0.7 0.7 0.7\nKd 0.6 0.6 0.6\nnewmtl 2\nNs 0\nKd 0.8 0.3 0.3\n")
-    tris = [((1.0, 1.0, -6.0), (2.0, 1.0, -6.0), (1.5, 1.0, -6.0), 2)]
-    for k in range(n_small):
-        p = rng.uniform(-6, 6, 3) + [0, 0, -6]
-        size = rng.choice([0.05, 0.3, 1.0])
-        q, r = p + rng.normal(size=3) * size, p + rng.normal(size=3) * size
-        if k % 17 == 0:
-            r = p + (q - p) * rng.uniform(0.2, 0.8) + rng.normal(size=3) * 1e-4
-        tris.append((p, q, r, int(rng.integers(1, 3))))
-    for k in range(6):
-        p = rng.uniform(-8, 8, 3) + [0, 0, -4]
-        tris.append((p, p + rng.normal(size=3) * 6, p + rng.normal(size=3) * 6, 0 if k == 0 else int(rng.integers(1, 3))))
-    lines = ["mtllib f.mtl", "vn 0.0 0.0 -1.0"]
-    for i, (p, q, r, m) in enumerate(tris):
-        lines += ["v %.6f %.6f %.6f" % tuple(v) for v in (p, q, r)] + ["usemtl %d" % m]
-        lines.append("f %d//1 %d//1 %d//1" % (3 * i + 1, 3 * i + 2, 3 * i + 3) if i == 0 else "f %d %d %d" % (3 * i + 1, 3 * i + 2, 3 * i + 3))
-    open(d + "f.obj", "w").write("\n".join(lines) + "\n")
-    return len(tris)
 
 
 @pytest.mark.parametrize("n_small,stats", [(300, False), (300, True), (3000, False), (3000, True)], ids=["small", "small_stats", "box_tree", "box_tree_stats"])

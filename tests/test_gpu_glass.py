@@ -13,6 +13,7 @@ import pytest
 
 import glass_composition as GC
 import oracle_lib as O
+from glass_fuzz_scenes import _box, _quad, _room, _write_obj
 
 pt = importlib.import_module("path-tracing_amd")
 pytestmark = pytest.mark.gpu
@@ -56,53 +57,6 @@ def _check(scene, osc, glass, w, h, spp, mrr, *, env=None, px=None, error=-1.0, 
 
 
 # ---- scenes --------------------------------------------------------------------------------------------------------------------------
-MTL = ("newmtl 0\nKe 3 3 3\nKd 1 1 1\nnewmtl 1\nNs 0\nKd 0.8 0.8 0.8\nnewmtl 2\nNs 300\nKs 0.7 0.7 0.7\nKd 0.6 0.6 0.9\n"
-       "newmtl 3\nNs 0\nKd 0.9 0.3 0.3\n")      # 0 the emitter, 1 the walls, 2 and 3 to be glass (their lobes are not looked at)
-
-
-def _quad(a, b, c, d, m):
-    return [(a, b, c, m), (a, c, d, m)]
-
-
-def _box(lo, hi, m, split=1, inward=False):
-    """The six faces of a box, each cut into split x split quads.  inward: the stored normals point into the box, as a room's must --
-    a scattered ray starts at p + N eps, whichever way N points."""
-    x0, y0, z0 = lo
-    x1, y1, z1 = hi
-    v = np.array([(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0), (x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)], np.float64)
-    faces = [(0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 5, 4), (3, 2, 6, 7), (0, 3, 7, 4), (1, 2, 6, 5)]
-    tris = []
-    for f in faces:
-        a, b, c, d = v[list(f)]
-        at = lambda i, j: tuple(a + (b - a) * (i / split) + (d - a) * (j / split))      # (a face is a parallelogram)
-        for i in range(split):
-            for j in range(split):
-                tris += _quad(at(i, j), at(i + 1, j), at(i + 1, j + 1), at(i, j + 1), m)
-    centre = (np.asarray(lo, np.float64) + np.asarray(hi, np.float64)) / 2
-    out = []
-    for p, q, r, mm in tris:      # (the reference's normal is (q - p) x (r - p), normalised)
-        n = np.cross(np.subtract(q, p), np.subtract(r, p))
-        points_in = np.dot(n, centre - np.asarray(p)) > 0
-        out.append((p, q, r, mm) if points_in == inward else (p, r, q, mm))
-    return out
-
-
-def _write_obj(d, name, tris):
-    open(d + "g.mtl", "w").write(MTL)
-    p, q, r, _ = tris[0]          # (the first face names a normal, as the parser wants one: the one its winding gives)
-    n = np.cross(np.subtract(q, p), np.subtract(r, p))
-    lines = ["mtllib g.mtl", "vn %.6f %.6f %.6f" % tuple(n / np.linalg.norm(n))]
-    for i, (p, q, r, m) in enumerate(tris):
-        lines += ["v %.6f %.6f %.6f" % tuple(v) for v in (p, q, r)] + ["usemtl %d" % m]
-        lines.append("f %d//1 %d//1 %d//1" % (3 * i + 1, 3 * i + 2, 3 * i + 3) if i == 0 else "f %d %d %d" % (3 * i + 1, 3 * i + 2, 3 * i + 3))
-    open(d + name, "w").write("\n".join(lines) + "\n")
-
-
-def _room():
-    """A closed room of 12 x 12 x 28 units around the reference eye (0, 0, -20), its normals inward, with an emitter of 6 x 6 units
-    under its ceiling that shines down."""
-    return _box((-6.0, -6.0, -22.0), (6.0, 6.0, 6.0), 1, split=2, inward=True) + \
-        _quad((-3.0, 5.5, -9.0), (3.0, 5.5, -9.0), (3.0, 5.5, -3.0), (-3.0, 5.5, -3.0), 0)      # (its normal points down)
 
 
 @pytest.fixture(scope="module")
