@@ -1565,6 +1565,111 @@ int pt_scene_get_dielectrics(const pt_scene *scene, pt_dielectric *list, int32_t
 int pt_frame_set_dielectrics(pt_frame *frame, const pt_dielectric *list, int32_t n);
 int pt_frame_get_dielectrics(pt_frame *frame, pt_dielectric *list, int32_t *n);
 
+/* ---- albedo textures: texture coordinates, map_Kd and texture lists ------------------------------------------------- */
+
+/* A scene handle may carry TEXTURE COORDINATES, three (u, v) pairs per triangle in the order of its vertices -- 6 x n_tri floats,
+ * u0 v0 u1 v1 u2 v2 per triangle, triangles in the order the scene holds them -- and, with them, a list of TEXTURES.  An entry of the
+ * list gives one material, addressed by index as usemtl addresses it, a picture of width x height texels: linear RGB floats, three
+ * per texel, rows top-down (row 0 is the top of the picture, where v = 1), each finite and >= 0, and a filter.  Without a list every
+ * output is what it was and the launches go to the kernels they went to; coordinates alone change nothing.
+ *
+ * Both belong to the handle, as the dielectrics do: pt_scene_clone_to_device and pt_frame_create inherit them.  A list works with
+ * every view, with a skybox, an environment or neither, with dielectrics on other materials, with statistics, adaptive sampling and
+ * pass windows, in bands and frames, on small and box-tree scenes; launches are planned as without the list (the same tiles and
+ * chunks; the cull tables, ray origins and directions are untouched).  The diagnostic builds (phase timers, block profile) have no
+ * texture kernels: a render of a handle with a list is PT_ERR_UNSUPPORTED there.
+ *
+ * THE SHADING STEP of a segment whose ray (unit direction d, origin o) hits triangle T (vertices v0, v1, v2 as the scene stores
+ * them, corner coordinates (u0, v0') (u1, v1') (u2, v2')) of a textured material at distance t, after the lobe has been chosen as
+ * without the list (unit_float(w0) - chance0 > 0 picks the second lobe; a one-lobe material draws nothing).  Every operation is a
+ * float operation rounded once, in the order written; nothing is fused; the divisions are IEEE divisions.
+ *   If the chosen lobe is the EMISSIVE or the DIFFUSE one:  col *= texel(T, p)  per channel (one rounding each), where col is the
+ *   path's throughput entering the step and p = o + d * t (per component, one product and one sum).  Then the material's step runs
+ *   unchanged on that throughput.  The GLOSSY lobe is not textured; a dielectric is not (a material cannot be in both lists).  On a
+ *   path's last segment (depth + 1 == max_ray_reflections) only the emissive case computes anything.  No random number is drawn and
+ *   none moves.
+ * BARYCENTRICS of p, from a per-triangle RECORD of eight floats (a1.x a1.y a1.z c1 a2.x a2.y a2.z c2) that the host forms once per
+ * triangle from its vertices, in plain float, every operation rounded once, nothing fused, component-wise differences first:
+ *   e1 = v1 - v0,  e2 = v2 - v0
+ *   d11 = (e1.x * e1.x + e1.y * e1.y) + e1.z * e1.z,   d12 likewise of e1, e2,   d22 of e2, e2
+ *   den = d11 * d22 - d12 * d12
+ *   den == 0 (a collinear triangle):  the record is all zero;   else, per component k,
+ *     a1.k = (e1.k * d22 - e2.k * d12) / den,     a2.k = (e2.k * d11 - e1.k * d12) / den
+ *     c1 = -((a1.x * v0.x + a1.y * v0.y) + a1.z * v0.z),     c2 likewise of a2
+ * and at a hit
+ *   b1 = ((a1.x * p.x + a1.y * p.y) + a1.z * p.z) + c1,    b2 = ((a2.x * p.x + a2.y * p.y) + a2.z * p.z) + c2
+ *   (so den == 0 gives b1 = b2 = 0; a record that overflowed gives NaN or inf coordinates, which the wrap below sends to 0)
+ *   b0 = (1 - b1) - b2
+ *   u = (b0 * u0 + b1 * u1) + b2 * u2,    v = (b0 * v0' + b1 * v1') + b2 * v2'
+ * LOOKUP of (u, v) in a width x height texture.  Repeat wrap on both axes: wrap(x) = x - floor(x) if that lies in [0, 1), else 0
+ * -- so NaN and +-inf read as 0, and so does a negative x so small that the difference rounds to 1 (-1e-9); a magnitude of 2^23 or
+ * more is its own floor and reads as 0 as well.  v points up, as OBJ has it: picture row = height - 1 - y.  Per axis of n texels,
+ * with f = wrap(.) and x = f * n (in [0, n]):
+ *   PT_TEXTURE_NEAREST   i = min(int(x), n - 1); the texel (i_u, i_v).
+ *   PT_TEXTURE_BILINEAR  texel centres lie at (i + 0.5) / n:  c = x - 0.5,  i = floor(c) (-1 .. n - 1),  t = c - i;  the lower
+ *                        texel is i, or n - 1 for i = -1; the upper one is i + 1, or 0 for i + 1 = n.  With lerp(a, b, t) =
+ *                        a + (b - a) * t:  texel = lerp(lerp(t00, t10, tu), lerp(t01, t11, tu), tv)  per channel, where t10 is the
+ *                        upper texel in u and t01 the upper one in v.  At a texel centre this is the texel; a constant texture
+ *                        gives its constant everywhere.
+ * Every float (u, v) therefore reads inside the texture and yields no NaN the texels do not hold: wrap(NaN) = wrap(+-inf) = 0 reads,
+ * nearest, the bottom-left texel (0, 0) and, bilinear, the equal-weight mix of the four corner texels.  There are no mip maps (the
+ * integrator has no ray footprints; the sample count does the filtering), no normal, specular or emission maps (map_Ke), no clamp or
+ * mirror wrap and no texture transforms.
+ *
+ * THE FIRST-HIT FEATURE PASS of a handle with a list writes albedo = Kd * texel(T, p) per channel (one rounding), with p and the
+ * lookup as above, for a pixel whose first hit is a triangle of a textured material, whatever its lobes; position, normal and hit
+ * index are what they are without the list.  The denoiser and the upsampler therefore demodulate by the textured albedo.
+ *
+ * PT_ERR_INVALID_ARGUMENT: a NULL handle; a NULL list with n > 0, n < 0; a material index outside the scene or listed twice; width
+ * or height < 1 or above PT_TEXTURE_MAX_SIDE, or more than 2^28 texels in one list; NULL texels; a texel that is not finite or is
+ * negative; an unknown filter; a material that is a dielectric of the handle (pt_scene_set_dielectrics refuses a textured material
+ * in turn); a list on a handle without texture coordinates; clearing the coordinates while a list is set; coordinates for a scene
+ * without triangles.  Coordinates may hold any float.  A setter validates, builds and uploads first and swaps last: a refused call
+ * leaves every handle as it was.  A host-only scene (device < 0) accepts and returns both. */
+#define PT_TEXTURE_NEAREST 0
+#define PT_TEXTURE_BILINEAR 1
+#define PT_TEXTURE_MAX_SIDE 8192
+typedef struct pt_texture {
+    int32_t material;
+    int32_t width, height;
+    int32_t filter;      /* PT_TEXTURE_NEAREST or PT_TEXTURE_BILINEAR */
+    const float *rgb;    /* width * height * 3; the setter copies them */
+} pt_texture;
+
+/* uv: 6 * n_tri floats (n_tri as pt_scene_counts gives it); NULL clears.  pt_scene_load_obj gives a loaded scene the OBJ's own: the
+ * vt of each face corner, (0, 0) for a corner without one (a vt index beyond the vt lines read so far is PT_ERR_PARSE; in a file without
+ * any vt line the index means nothing, as to the reference, and the corner gets (0, 0); a negative -- OBJ's relative -- or zero vt index is
+ * not supported and reads as no index: (0, 0)). */
+int pt_scene_set_texcoords(pt_scene *scene, const float *uv);
+/* *has = 1 and uv (may be NULL) gets the 6 * n_tri floats, or *has = 0. */
+int pt_scene_get_texcoords(const pt_scene *scene, float *uv, int32_t *has);
+/* NULL or n == 0 clears the list. */
+int pt_scene_set_textures(pt_scene *scene, const pt_texture *list, int32_t n);
+/* *n = the number of entries; list (may be NULL) gets them in the order given, each rgb pointing at the handle's own copy of the
+ * texels, valid until the list is replaced or the handle destroyed. */
+int pt_scene_get_textures(const pt_scene *scene, pt_texture *list, int32_t *n);
+/* The same on a frame: every device's copy of the frame's scene; a refused call changes none.  The getters answer for the root's. */
+int pt_frame_set_texcoords(pt_frame *frame, const float *uv);
+int pt_frame_get_texcoords(pt_frame *frame, float *uv, int32_t *has);
+int pt_frame_set_textures(pt_frame *frame, const pt_texture *list, int32_t n);
+int pt_frame_get_textures(pt_frame *frame, pt_texture *list, int32_t *n);
+/* The file name the model's MTL gives material `material` in a map_Kd line (the last token of the line), "" if it has none or the
+ * scene was made from arrays; the pointer stays valid as long as the scene.  The library applies nothing by itself (the reference
+ * ignores the line): see pt_render -TEXTURE mtl.  PT_ERR_INVALID_ARGUMENT: NULL, or an index outside the scene. */
+int pt_scene_get_map_kd(const pt_scene *scene, int32_t material, const char **name);
+/* The barycentrics' records the kernels read, as stated above: records gets 8 * n_tri floats, triangles in the scene's order.  They
+ * depend on the vertices alone; a host-only scene answers too. */
+int pt_scene_get_texture_records(const pt_scene *scene, float *records);
+/* Reads a 24-bit BMP (the skybox's reader) into linear floats for a pt_texture: texel = table[byte], table[b] = (float)pow(b / 255.0,
+ * gamma) in the host's double pow (gamma == 1: b / 255.0 rounded to float), rows top-down, R G B.  gamma <= 0 or not finite: 2.2.
+ * Call once with rgb == NULL for *width and *height, then with room for width * height * 3 floats.  PT_ERR_IO: the file cannot be
+ * opened; PT_ERR_PARSE: not a 24-bit BMP, or a side above PT_TEXTURE_MAX_SIDE. */
+int pt_texture_load_bmp(const char *path, float gamma, int32_t *width, int32_t *height, float *rgb);
+/* The lookup alone, on the host: out_rgb[3 i ..] = texel at (uv[2 i], uv[2 i + 1]) of the width x height texture rgb.  indices (may
+ * be NULL) gets, four per lookup, the texel indices (row * width + column, rows top-down) read: t00, t10, t01, t11 (nearest: the
+ * one texel four times). */
+int pt_texture_lookup(int32_t width, int32_t height, const float *rgb, int32_t filter, int32_t n, const float *uv, float *out_rgb, int32_t *indices);
+
 /* ---- misc ------------------------------------------------------------------------------------------- */
 int pt_abi_version(void);
 int pt_device_count(void);

@@ -62,7 +62,10 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_scene_get_environment", "pt_environment_from_equirect", "pt_environment_lookup",
                "pt_frame_set_environment_file", "pt_frame_set_environment_equirect", "pt_frame_set_environment_map",
                "pt_frame_get_environment",
-               "pt_scene_set_dielectrics", "pt_scene_get_dielectrics", "pt_frame_set_dielectrics", "pt_frame_get_dielectrics"]
+               "pt_scene_set_dielectrics", "pt_scene_get_dielectrics", "pt_frame_set_dielectrics", "pt_frame_get_dielectrics",
+               "pt_scene_set_texcoords", "pt_scene_get_texcoords", "pt_scene_set_textures", "pt_scene_get_textures",
+               "pt_frame_set_texcoords", "pt_frame_get_texcoords", "pt_frame_set_textures", "pt_frame_get_textures",
+               "pt_scene_get_map_kd", "pt_texture_load_bmp", "pt_texture_lookup", "pt_scene_get_texture_records"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -487,6 +490,64 @@ def dielectric(material, ior, tint=(1.0, 1.0, 1.0)):
     return Dielectric(int(material), float(ior), (C.c_float * 3)(*tint))
 
 
+TEXTURE_NEAREST, TEXTURE_BILINEAR = 0, 1
+TEXTURE_MAX_SIDE = 8192
+_TEXTURE_FILTERS = {"nearest": TEXTURE_NEAREST, "bilinear": TEXTURE_BILINEAR}
+
+
+def _texture_filter(filter):
+    if isinstance(filter, str):
+        if filter not in _TEXTURE_FILTERS:
+            raise ValueError(f"texture filter {filter!r}: nearest or bilinear")
+        return _TEXTURE_FILTERS[filter]
+    return int(filter)
+
+
+class TextureEntry(C.Structure):
+    """pt_texture: a material's index, the picture's size, the filter and a pointer to width * height * 3 floats."""
+    _fields_ = [("material", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("filter", C.c_int32), ("rgb", C.POINTER(C.c_float))]
+
+
+class Texture:
+    """One entry of a handle's textures: `texels` is (height, width, 3) linear RGB, row 0 the top of the picture."""
+
+    def __init__(self, material, texels, filter=TEXTURE_BILINEAR):
+        t = np.ascontiguousarray(texels, np.float32)
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError("texture: texels must be (height, width, 3)")
+        self.material, self.texels, self.filter = int(material), t, _texture_filter(filter)
+
+    def __repr__(self):
+        return f"texture({self.material}, {self.texels.shape[1]} x {self.texels.shape[0]}, filter={self.filter})"
+
+
+def texture(material, texels, filter="bilinear"):
+    """One entry of a handle's textures (-TEXTURE m:file[:filter]): material `material` takes the (height, width, 3) picture `texels`."""
+    return Texture(material, texels, filter)
+
+
+def load_texture_bmp(path, gamma=2.2, library=None):
+    """pt_texture_load_bmp: a 24-bit BMP as (height, width, 3) linear floats, bytes decoded as pow(b / 255, gamma)."""
+    L = library or lib()
+    w, h = C.c_int32(), C.c_int32()
+    _check(L.pt_texture_load_bmp(os.fsencode(path), gamma, C.byref(w), C.byref(h), None), L)
+    out = np.zeros((h.value, w.value, 3), np.float32)
+    _check(L.pt_texture_load_bmp(os.fsencode(path), gamma, C.byref(w), C.byref(h), _fp(out)), L)
+    return out
+
+
+def texture_lookup(texels, uv, filter="bilinear", library=None, want_indices=False):
+    """pt_texture_lookup, the host's own lookup: the texel of the (height, width, 3) picture at each (u, v) of `uv` [n, 2]; with
+    want_indices also the four texel indices (row * width + column) each lookup read."""
+    L = library or lib()
+    t = np.ascontiguousarray(texels, np.float32)
+    q = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    out = np.zeros((len(q), 3), np.float32)
+    idx = np.zeros((len(q), 4), np.int32)
+    _check(L.pt_texture_lookup(t.shape[1], t.shape[0], _fp(t), _texture_filter(filter), len(q), _fp(q), _fp(out), _ip(idx)), L)
+    return (out, idx) if want_indices else out
+
+
 def _projection_arg(projection_, library):
     """A Projection, a kind (number or name) or None -> a pointer argument for pt_scene_set_projection / pt_frame_set_projection."""
     if projection_ is None:
@@ -617,6 +678,16 @@ def load_library(path):
     L.pt_scene_get_dielectrics.argtypes = [vp, dp, ip]
     L.pt_frame_set_dielectrics.argtypes = [vp, dp, C.c_int32]
     L.pt_frame_get_dielectrics.argtypes = [vp, dp, ip]
+    tp = C.POINTER(TextureEntry)
+    for who in ("scene", "frame"):
+        getattr(L, f"pt_{who}_set_texcoords").argtypes = [vp, fp]
+        getattr(L, f"pt_{who}_get_texcoords").argtypes = [vp, fp, ip]
+        getattr(L, f"pt_{who}_set_textures").argtypes = [vp, tp, C.c_int32]
+        getattr(L, f"pt_{who}_get_textures").argtypes = [vp, tp, ip]
+    L.pt_scene_get_texture_records.argtypes = [vp, fp]
+    L.pt_scene_get_map_kd.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p)]
+    L.pt_texture_load_bmp.argtypes = [C.c_char_p, C.c_float, ip, ip, fp]
+    L.pt_texture_lookup.argtypes = [C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32, fp, fp, ip]
     L.pt_environment_from_equirect.argtypes = [C.c_int32, C.c_int32, fp, ep, C.c_int32, fp]
     L.pt_environment_lookup.argtypes = [C.c_int32, fp, C.c_int32, fp, fp]
     L.pt_render_features_host.argtypes = [vp, C.POINTER(RenderParams), ip, fp, fp, fp, fp]
@@ -780,7 +851,51 @@ class _DielectricMethods:
         return [dielectric(e.material, e.ior, tuple(e.tint)) for e in arr[:n.value]]
 
 
-class Scene(_EnvironmentMethods, _DielectricMethods):
+class _TextureMethods:
+    """set_texcoords / texcoords / set_textures / textures of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
+    _tex_prefix = "pt_scene_"
+
+    def _tex_fn(self, name):
+        return getattr(self._L, self._tex_prefix + name)
+
+    def set_texcoords(self, uv):
+        """The handle's texture coordinates: (n_tri, 3, 2) -- (u, v) per corner of every triangle -- or None to clear them."""
+        if uv is None:
+            _check(self._tex_fn("set_texcoords")(self._h, None), self._L)
+            return
+        a = np.ascontiguousarray(uv, np.float32)
+        if a.size != 6 * self._n_tri():
+            raise ValueError("set_texcoords: 6 floats per triangle")
+        _check(self._tex_fn("set_texcoords")(self._h, _fp(a)), self._L)
+
+    def texcoords(self):
+        """(n_tri, 3, 2), or None if the handle has none (a scene loaded from an OBJ has the file's vt)."""
+        has = C.c_int32()
+        _check(self._tex_fn("get_texcoords")(self._h, None, C.byref(has)), self._L)
+        if not has.value:
+            return None
+        a = np.zeros((self._n_tri(), 3, 2), np.float32)
+        _check(self._tex_fn("get_texcoords")(self._h, _fp(a), C.byref(has)), self._L)
+        return a
+
+    def set_textures(self, entries):
+        """-TEXTURE: `entries` is a list of pt.texture(material, texels, filter); None or an empty list clears it.  Refused: an index
+        outside the scene or listed twice, a side above TEXTURE_MAX_SIDE, a negative or non-finite texel, an unknown filter, a
+        dielectric material, a handle without texture coordinates."""
+        entries = list(entries or [])
+        arr = (TextureEntry * len(entries))(*[TextureEntry(e.material, e.texels.shape[1], e.texels.shape[0], e.filter, _fp(e.texels)) for e in entries]) if entries else None
+        _check(self._tex_fn("set_textures")(self._h, arr, len(entries)), self._L)
+
+    def textures(self):
+        """The handle's textures, a list of Texture in the order given ([] without any)."""
+        n = C.c_int32()
+        _check(self._tex_fn("get_textures")(self._h, None, C.byref(n)), self._L)
+        arr = (TextureEntry * max(n.value, 1))()
+        _check(self._tex_fn("get_textures")(self._h, arr, C.byref(n)), self._L)
+        return [Texture(e.material, np.ctypeslib.as_array(e.rgb, (e.height, e.width, 3)).copy(), e.filter) for e in arr[:n.value]]
+
+
+class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods):
     """Owns a pt_scene handle (Scene + LoadModel of the reference, scene.h:17-19)."""
 
     def __init__(self, handle, library=None):
@@ -803,6 +918,24 @@ class Scene(_EnvironmentMethods, _DielectricMethods):
         h = C.c_void_p()
         _check(L.pt_scene_create(_fp(t), _ip(m), len(t), _fp(k), len(k), device, C.byref(h)), L)
         return cls(h, L)
+
+    def _n_tri(self):
+        return self.counts()[0]
+
+    def texture_records(self):
+        """pt_scene_get_texture_records: (n_tri, 8), the per-triangle records the texture kernels take a hit point's barycentrics from."""
+        r = np.zeros((self._n_tri(), 8), np.float32)
+        _check(self._L.pt_scene_get_texture_records(self._h, _fp(r)), self._L)
+        return r
+
+    def map_kd(self):
+        """The file name of each material's map_Kd line in the model's MTL ("" where it has none)."""
+        out = []
+        for m in range(self.counts()[1]):
+            name = C.c_char_p()
+            _check(self._L.pt_scene_get_map_kd(self._h, m, C.byref(name)), self._L)
+            out.append((name.value or b"").decode(errors="replace"))
+        return out
 
     def counts(self):
         nt, nm = C.c_int32(), C.c_int32()
@@ -1503,9 +1636,15 @@ def bvh_depth(nodes):
     return int(level.max())
 
 
-class Frame(_EnvironmentMethods, _DielectricMethods):
+class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods):
     """pt_frame: one image on several devices from one host program -- row bands, one gather to the first device."""
-    _env_prefix = _glass_prefix = "pt_frame_"
+    _env_prefix = _glass_prefix = _tex_prefix = "pt_frame_"
+
+    def _n_tri(self):
+        return self._scene.counts()[0]
+
+    def map_kd(self):
+        return self._scene.map_kd()
 
     def __init__(self, scene, devices, width, height, flags=0):
         self._scene, self._L = scene, scene._L

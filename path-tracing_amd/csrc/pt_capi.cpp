@@ -2,6 +2,7 @@
 // errors to status codes, and implements the reference's host-side resolve and BMP writer.  (pt_frame.cpp holds the
 // multi-device frame on top of what is here.)
 #include "pt_capi_internal.hpp"
+#include "pt_bmp.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -116,6 +117,7 @@ int upload(pt_scene *s, int device) {
     }
     if (s->env && (rc = s->d_env.upload(pt::env_with_apron(s->env->n, s->env->rgb.data()), "environment map", 64)) != PT_OK) return rc;
     if (s->glass && (rc = s->d_glass.upload(s->glass->table, "dielectric table", 64)) != PT_OK) return rc;
+    if (s->textures && (rc = ptc::upload_textures(*s->textures, *s->texcoords, s->shared->tables, s->d_tex)) != PT_OK) return rc;
     return PT_OK;
 }
 
@@ -246,6 +248,7 @@ int finish_scene(ScenePtr s, int device, pt_scene **out) {
         if (m < 0 || m >= h.host.n_mat()) return fail(PT_ERR_INVALID_ARGUMENT, "triangle refers to material " + std::to_string(m));
     pt::build_device_tables(h.host, h.tables);
     h.vertex_extent = pt::vertex_extent(h.host);
+    if (!h.host.tri_uv.empty()) s->texcoords = std::make_shared<const std::vector<float>>(h.host.tri_uv);   // a loaded scene: the OBJ's own
     if (device >= 0) {
         const int rc = upload(s.get(), device);
         if (rc != PT_OK) return rc;
@@ -279,6 +282,13 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
         a.env_n = scene->env->n;
     }
     if (scene->glass && scene->d_glass) a.glass = scene->d_glass.get<void>();   // the dielectric kernels of whichever kernels the launch is planned as (integrate_kernel_glass)
+    if (scene->textures && scene->d_tex.recs) {   // the texture kernels of those (integrate_kernel_texture); without dielectrics, an all-zero table
+        a.tex_recs = scene->d_tex.recs.get<void>();
+        a.tex_uv = scene->d_tex.uv.get<float>();
+        a.tex_texels = scene->d_tex.texels.get<void>();
+        a.tex_bary = scene->d_tex.bary.get<void>();
+        if (!a.glass) a.glass = scene->d_tex.no_glass.get<void>();
+    }
     a.n_clusters = static_cast<int32_t>(t.clusters.size());
     a.n_tri = scene->shared->host.n_tri();
     a.big = t.big ? 1 : 0;
@@ -401,6 +411,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
         PT_HIP_TRY(hipEventRecord(ctx.ev0.get(), stream));
     }
     const hipError_t launched = pt::launch_integrator(a, tiles.variant, stream);
+    if (launched == hipErrorNotSupported && a.tex_recs != nullptr) return fail(PT_ERR_UNSUPPORTED, "textures: this diagnostic build of the library has no texture kernels");
     if (launched == hipErrorNotSupported && a.glass != nullptr) return fail(PT_ERR_UNSUPPORTED, "dielectrics: this diagnostic build of the library has no dielectric kernels");
     PT_HIP_TRY(launched);
     if (want_stats) PT_HIP_TRY(hipEventRecord(ctx.ev1.get(), stream));
@@ -627,6 +638,8 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->sky = src->sky;         // the skybox of the handle the copy is made from
     s->env = src->env;         // or its environment
     s->glass = src->glass;     // and its dielectrics
+    s->texcoords = src->texcoords;   // and its texture coordinates and textures
+    s->textures = src->textures;
     s->has_camera = src->has_camera;   // and its camera
     s->camera = src->camera;
     s->has_lens = src->has_lens;       // and lens
@@ -649,40 +662,9 @@ static int scene_set_skybox_bmp_impl(pt_scene *scene, const char *path) {
     std::vector<uint8_t> texels;
     int w = 0, h = 0;
     if (path && *path) {
-        // bitmap_image(filename) -> load_bitmap(), bitmap_image.hpp:1508-1603: the same checks, reported instead of printed
-        FILE *f = std::fopen(path, "rb");
-        if (!f) return fail(PT_ERR_IO, std::string("skybox: cannot open ") + path);
-        uint8_t hdr[54];
-        const bool got = std::fread(hdr, 1, 54, f) == 54;
-        auto u16 = [&](int at) { return static_cast<uint32_t>(hdr[at]) | (static_cast<uint32_t>(hdr[at + 1]) << 8); };
-        auto u32 = [&](int at) { return u16(at) | (u16(at + 2) << 16); };
-        std::string why;
-        if (!got) why = "file shorter than its headers";
-        else if (u16(0) != 19778) why = "invalid type value " + std::to_string(u16(0)) + " expected 19778";
-        else if (u16(28) != 24) why = "invalid bit depth " + std::to_string(u16(28)) + " expected 24";
-        else if (u32(14) != 40) why = "invalid BIH size " + std::to_string(u32(14)) + " expected 40";
-        if (why.empty()) {
-            const uint32_t uw = u32(18), uh = u32(22);
-            const uint32_t pad = (4u - (3u * uw) % 4u) % 4u;
-            std::fseek(f, 0, SEEK_END);
-            const size_t physical = static_cast<size_t>(std::ftell(f));
-            const size_t logical = static_cast<size_t>(uh) * uw * 3 + static_cast<size_t>(uh) * pad + 54;
-            if (physical != logical || uw == 0 || uh == 0) {
-                why = "mismatch between logical (" + std::to_string(logical) + ") and physical (" + std::to_string(physical) + ") sizes";
-            } else {
-                texels.resize(static_cast<size_t>(uw) * uh * 3);
-                std::fseek(f, 54, SEEK_SET);
-                uint8_t padbuf[4];
-                for (uint32_t i = 0; i < uh && why.empty(); ++i) {   // rows are stored bottom-up
-                    if (std::fread(&texels[static_cast<size_t>(uh - i - 1) * uw * 3], 1, static_cast<size_t>(uw) * 3, f) != static_cast<size_t>(uw) * 3 ||
-                        (pad && std::fread(padbuf, 1, pad, f) != pad))
-                        why = "short read";
-                }
-                w = static_cast<int>(uw);
-                h = static_cast<int>(uh);
-            }
-        }
-        std::fclose(f);
+        std::string why;   // (pt_bmp.hpp: the reader pt_texture_load_bmp shares)
+        bool cannot_open = false;
+        if (!pt::read_bmp24(path, texels, w, h, why, cannot_open) && cannot_open) return fail(PT_ERR_IO, "skybox: " + why);
         if (!why.empty()) return fail(PT_ERR_PARSE, std::string("skybox ") + path + ": " + why);
     }
     if (scene->device >= 0) {

@@ -31,6 +31,7 @@
 #include "pt_optics.hpp"
 #include "pt_scene.hpp"
 #include "pt_sharpen.hpp"
+#include "pt_texture.hpp"
 #include "pt_upsample.hpp"
 
 // The host side of a scene: parsed model, its device-independent tables and the culling hierarchies built so far (one per
@@ -65,6 +66,23 @@ struct pt_env_map {
 struct pt_glass_list {
     std::vector<pt_dielectric> list;
     std::vector<pt::GlassRec> table;
+};
+
+// The textures of a handle (pt_hip.h: pt_texture): the list as given (with its texels) and what the kernels read -- the per-material
+// table (pt_texture.hpp: TexRec, one per material of the scene) and the pool of all the list's texels.  Belongs to the handle as the
+// dielectrics do; immutable once set.  The handle's texture coordinates (6 floats per triangle) are a vector of their own, shared likewise.
+struct pt_texture_list {
+    struct Entry {
+        int32_t material, width, height, filter;
+        std::vector<float> rgb;
+    };
+    std::vector<Entry> list;
+    std::vector<pt::TexRec> recs;
+    std::vector<pt::TexTexel> pool;
+};
+// Their device copies: table, coordinates, texels, and the all-zero dielectric table a textured handle without dielectrics passes.
+struct DeviceTextures {
+    ptc::DeviceBuffer recs, uv, texels, no_glass, bary;   // (bary: the barycentrics' record of every triangle, pt_texture.hpp: TexBary)
 };
 
 // Device copy of one CullTables (they depend on eps and on the envelope the camera needs; a scene keeps the one of its last
@@ -103,6 +121,9 @@ struct pt_scene {
     ptc::DeviceBuffer d_env;       // its (n + 2)^2 texels with the apron (pt_environment.hpp: EnvTexel) on this copy's device
     std::shared_ptr<const pt_glass_list> glass; // this handle's dielectrics (nullptr = none); copies inherit them
     ptc::DeviceBuffer d_glass;     // their table on this copy's device
+    std::shared_ptr<const std::vector<float>> texcoords;   // this handle's texture coordinates (nullptr = none; a loaded scene has the OBJ's); copies inherit them
+    std::shared_ptr<const pt_texture_list> textures;       // this handle's textures (nullptr = none; only with texcoords); copies inherit them
+    DeviceTextures d_tex;          // both on this copy's device, uploaded when a list is set
     bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
     pt_camera camera{};
     bool has_lens = false;         // this handle's lens (pt_scene_set_lens; radius > 0); copies made from it inherit it
@@ -388,5 +409,24 @@ void temporal_commit(pt_temporal *t);
 // Every device's copy of a frame's scene (owned by the frame), for the setters that live outside pt_frame.cpp (pt_environment_capi.cpp, pt_glass_capi.cpp).
 const std::vector<pt_scene *> &frame_scenes(pt_frame *f);
 int frame_root_planes(pt_frame *f, pt_scene **scene, AccumPlanes *planes, hipStream_t *stream, int32_t *width, int32_t *height);
+
+// A handle's textures onto the current device (the setters of pt_texture_capi.cpp; a clone's upload in pt_capi.cpp): the table, the
+// coordinates, the texels, the barycentrics' record of every triangle (in the original order) and an all-zero dielectric table.  `out` is only written once every upload has succeeded.
+inline std::vector<pt::TexBary> texture_bary_records(const std::vector<pt::ExactRec> &exact) {
+    std::vector<pt::TexBary> out(exact.size());
+    for (size_t i = 0; i < exact.size(); ++i) out[i] = pt::tex_bary_record(exact[i].v0, exact[i].v1, exact[i].v2);
+    return out;
+}
+inline int upload_textures(const pt_texture_list &list, const std::vector<float> &texcoords, const pt::DeviceTables &tables, DeviceTextures &out) {
+    DeviceTextures d;
+    int rc;
+    const std::vector<pt::GlassRec> zeros(tables.mats.size(), pt::GlassRec{});
+    if ((rc = d.bary.upload(texture_bary_records(tables.exact), "texture barycentric records", 64)) != PT_OK) return rc;
+    if ((rc = d.recs.upload(list.recs, "texture table", 64)) != PT_OK || (rc = d.uv.upload(texcoords, "texture coordinates", 64)) != PT_OK ||
+        (rc = d.texels.upload(list.pool, "texels", 64)) != PT_OK || (rc = d.no_glass.upload(zeros, "empty dielectric table", 64)) != PT_OK)
+        return rc;
+    out = std::move(d);
+    return PT_OK;
+}
 
 }  // namespace ptc

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "pt_denoise.hpp"
+#include "pt_texture_features.hpp"
 
 using ptc::fail;
 using ptc::guarded;
@@ -21,6 +22,10 @@ int ptc::enqueue_first_hits(pt_scene *scene, const pt::RenderArgs &a, const pt_c
     if (a.projection != 0) PT_HIP_TRY(pt::launch_projection_rays(a, width, height, row_begin, rows, out.origins, out.directions, stream));
     else PT_HIP_TRY(pt::launch_feature_rays(cam, width, height, row_begin, rows, out.origins, out.directions, stream));
     PT_HIP_TRY(pt::launch_trace_rays(a, out.origins, out.directions, n, out.hit, out.hit_t, stream));
+    if (a.tex_recs != nullptr)   // the handle's textures: the gather's twin, albedo = Kd x texel (pt_texture_features.hip)
+        PT_HIP_TRY(pt::launch_feature_gather_textured(scene->d_exact.get<pt::ExactRec>(), scene->d_mats.get<pt::MatRec>(), a.tex_recs, a.tex_uv, a.tex_texels, a.tex_bary,
+                                                      out.origins, out.directions, out.hit, out.hit_t, n, out.position, out.normal, out.albedo, stream));
+    else
     PT_HIP_TRY(pt::launch_feature_gather(scene->d_exact.get<pt::ExactRec>(), scene->d_mats.get<pt::MatRec>(), out.origins, out.directions, out.hit,
                                          out.hit_t, n, out.position, out.normal, out.albedo, stream));
     return PT_OK;

@@ -4,6 +4,8 @@
 // adds throughput x the handle's environment map (pt_hip.h: pt_environment_*; pt_environment.hpp spells the lookup) instead of the skybox.
 // GLASS (only pt::integrate_kernel_glass: false in every other kernel) = a hit on a material the handle's dielectric table marks
 // (pt_hip.h: pt_dielectric) reflects or refracts by the Fresnel term instead of running the material's lobes.
+// TEX (only pt::integrate_kernel_texture: false in every other kernel) = a hit on a triangle of a material the handle's texture table
+// marks (pt_hip.h: pt_texture) multiplies the throughput by the texel before the emissive or the diffuse lobe runs.
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
@@ -743,6 +745,29 @@
                         grec = glass_view() + mi;
                         g_ior = grec->ior;
                         if (g_ior != 0.0f) kind = 3;
+                    }
+                    // TEX: the emissive and the diffuse lobe of a textured material take the throughput times the texel at the hit
+                    // point (pt_hip.h: pt_texture; pt_texture.hpp spells barycentrics, wrap and filters); the glossy lobe and a
+                    // dielectric do not.  On a path's last segment only the emissive lobe computes anything.  hit_rec may be a record
+                    // of either table: `orig` is the triangle's index in the original order, which the coordinates are stored in.
+                    if constexpr (TEX) {
+                        if (kind == 0 || (kind == 2 && depth[k] + 1 < mrr)) {
+                            const TextureView tv = texture_view();
+                            const TexRec tm = tv.recs()[mi];
+                            if (tm.w != 0) {
+                                float xr, xg, xb;
+#ifdef PT_TEXTURE_VERTICES   // (the form that was measured against the record: DESIGN.md section 27)
+                                const float4 r1 = reinterpret_cast<const float4 *>(rec)[1], r2 = reinterpret_cast<const float4 *>(rec)[2];
+                                const float4 r3 = reinterpret_cast<const float4 *>(rec)[3];
+                                tex_at_hit(tm, tv.texels(), tv.uv() + 6 * static_cast<size_t>(rec->orig), r1.x, r1.y, r1.z, r2.x, r2.y, r2.z,
+                                           r3.x, r3.y, r3.z, px, py, pz, xr, xg, xb);
+#else
+                                const size_t ti = static_cast<size_t>(rec->orig);
+                                tex_at_hit_record(tm, tv.texels(), tv.uv() + 6 * ti, tv.bary() + ti, px, py, pz, xr, xg, xb);
+#endif
+                                tr[k] *= xr; tg[k] *= xg; tb[k] *= xb;
+                            }
+                        }
                     }
                     if (kind < 0) {
                         depth[k] = mrr;

@@ -37,6 +37,7 @@
 #include "pt_kernels.hpp"
 #include "pt_projection.hpp"
 #include "pt_environment.hpp"
+#include "pt_texture.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1341,6 +1342,25 @@ __device__ __forceinline__ const GlassRec *glass_view() {
     asm volatile("" : "+s"(p));
     return *reinterpret_cast<const GlassRec *const __attribute__((address_space(4))) *>(p);
 }
+// The textures of a texture-kernel launch (RenderArgs::tex_recs, tex_uv, tex_texels), likewise: read where a ray has hit a triangle.
+struct TextureView {
+    uint64_t p;
+    __device__ __forceinline__ const TexRec *recs() const { return *reinterpret_cast<const TexRec *const __attribute__((address_space(4))) *>(p); }
+    __device__ __forceinline__ const float *uv() const {
+        return *reinterpret_cast<const float *const __attribute__((address_space(4))) *>(p + (offsetof(RenderArgs, tex_uv) - offsetof(RenderArgs, tex_recs)));
+    }
+    __device__ __forceinline__ const TexBary *bary() const {
+        return *reinterpret_cast<const TexBary *const __attribute__((address_space(4))) *>(p + (offsetof(RenderArgs, tex_bary) - offsetof(RenderArgs, tex_recs)));
+    }
+    __device__ __forceinline__ const TexTexel *texels() const {
+        return *reinterpret_cast<const TexTexel *const __attribute__((address_space(4))) *>(p + (offsetof(RenderArgs, tex_texels) - offsetof(RenderArgs, tex_recs)));
+    }
+};
+__device__ __forceinline__ TextureView texture_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, tex_recs);
+    asm volatile("" : "+s"(p));
+    return {p};
+}
 
 // What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
 // in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
@@ -1377,7 +1397,7 @@ constexpr int integrator_waves() {
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false;
 #include "pt_integrator_body.inc"
 }
 // The lens kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary ray
@@ -1393,7 +1413,7 @@ constexpr int lens_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (lens_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false;
+    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false;
 #include "pt_integrator_body.inc"
 }
 // The motion twins (pt_hip.h: camera motion): the camera twin and its lens kernel with the camera -- and the lens axes -- interpolated
@@ -1409,12 +1429,12 @@ constexpr int motion_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, false>())) void integrate_kernel_motion(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false;
+    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false;
 #include "pt_integrator_body.inc"
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, true>())) void integrate_kernel_motion_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false;
+    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false;
 #include "pt_integrator_body.inc"
 }
 // The projection kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary
@@ -1429,7 +1449,7 @@ constexpr int projection_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (projection_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_projection(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false, TEX = false;
 #include "pt_integrator_body.inc"
 }
 
@@ -1454,7 +1474,7 @@ template <bool BIG, bool STATS, bool ENV, int VIEW>
 __global__ __launch_bounds__(kBlock, (environment_waves<BIG, STATS, ENV, VIEW>())) void integrate_kernel_environment(const RenderArgs a) {
     constexpr bool SKY = true, NARROW = false;
     constexpr int ADAPT = VIEW != 0 ? 1 : 0;
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false, TEX = false;
 #include "pt_integrator_body.inc"
 }
 namespace {
@@ -1477,7 +1497,18 @@ hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Var
     hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
     return hipGetLastError();
 }
-#elif defined(PT_GLASS_UNIT)
+#elif defined(PT_GLASS_UNIT) || defined(PT_TEXTURE_UNIT)
+// (PT_TEXTURE_UNIT -- pt_texture_kernels.hip -- compiles this same section once more, as integrate_kernel_texture: the dielectric
+// kernels' set of instantiations with TEX = true as well, see below the dielectric kernels' own description)
+#ifdef PT_TEXTURE_UNIT
+#define PT_UNIT_KERNEL integrate_kernel_texture
+#define PT_UNIT_LAUNCH launch_texture_integrator
+constexpr bool kUnitTex = true;
+#else
+#define PT_UNIT_KERNEL integrate_kernel_glass
+#define PT_UNIT_LAUNCH launch_glass_integrator
+constexpr bool kUnitTex = false;
+#endif
 // ---------------------------------------------------------------------------------------------------------------
 // The dielectric kernels (pt_glass_kernels.hip: this file compiled with PT_GLASS_UNIT, a translation unit of its own).  The body
 // with GLASS = true: a hit on a material the handle's table marks (RenderArgs::glass, pt_hip.h: pt_dielectric) reflects or refracts.
@@ -1506,12 +1537,28 @@ constexpr int glass_fewer_waves() {
     else if constexpr (MISS == 0 && !BIG && !STATS && FORM == 0) return (VIEW == 2 || VIEW == 3 || VIEW == 5) ? 1 : 0;
     else return 0;
 }
+// The texture kernels (pt_hip.h: pt_texture): the same set with TEX = true too -- a hit on a triangle of a material
+// the handle's texture table marks (RenderArgs::tex_recs) multiplies the throughput by the texel before the emissive or the diffuse
+// lobe runs.  A textured handle without dielectrics runs them with an all-zero dielectric table.  The twin of a texture kernel is the
+// dielectric kernel of the same arguments; waves per SIMD: that twin's minus texture_fewer_waves (tests/test_texture_resources.py
+// pins every kernel).
 template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
-__global__ __launch_bounds__(kBlock, (view_waves<MISS != 0, BIG, STATS, FORM < 2, FORM == 1, VIEW>() - glass_fewer_waves<MISS, BIG, STATS, FORM, VIEW>()))
-void integrate_kernel_glass(const RenderArgs a) {
+constexpr int texture_fewer_waves() {
+    // At the dielectric twin's 5 waves and 96 VGPRs these spilled vector registers to scratch (1 and 2 VGPRs: the barycentrics'
+    // operands on top of the second pixel's state): the two-pixel small-scene kernel without a miss shader, fixed eye and camera twin.
+    return (MISS == 0 && !BIG && !STATS && FORM == 0 && (VIEW == 0 || VIEW == 1)) ? 1 : 0;
+}
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+constexpr int unit_waves() {
+    return view_waves<MISS != 0, BIG, STATS, FORM < 2, FORM == 1, VIEW>() - glass_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() -
+           (kUnitTex ? texture_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0);
+}
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+__global__ __launch_bounds__(kBlock, (unit_waves<MISS, BIG, STATS, FORM, VIEW>()))
+void PT_UNIT_KERNEL(const RenderArgs a) {
     constexpr bool SKY = MISS != 0, ENV = FORM < 2, NARROW = FORM == 1;
     constexpr int ADAPT = (FORM == 2 ? 2 : FORM == 3 ? 4 : 0) | (VIEW != 0 ? 1 : 0);
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true, TEX = kUnitTex;
 #include "pt_integrator_body.inc"
 }
 namespace {
@@ -1529,13 +1576,14 @@ Kernel glass_kernel_of() {   // I = (VIEW * 3 + MISS) * 16 + (big, stats) as bit
     constexpr int kMiss = (I / 16) % 3, kForm = I & 3;
     constexpr bool kBig = (I & 8) != 0, kStats = (I & 4) != 0;
     if constexpr (!glass_kernel_exists<kMiss, kBig, kStats, kForm>()) return nullptr;
-    else return &integrate_kernel_glass<kMiss, kBig, kStats, kForm, I / 48>;
+    else return &PT_UNIT_KERNEL<kMiss, kBig, kStats, kForm, I / 48>;
 }
 template <int... I>
 std::array<Kernel, sizeof...(I)> glass_kernel_table(std::integer_sequence<int, I...>) { return {glass_kernel_of<I>()...}; }
 const auto kGlassKernels = glass_kernel_table(std::make_integer_sequence<int, kGlassPerView * kGlassViews>());
 }  // namespace
-hipError_t launch_glass_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
+hipError_t PT_UNIT_LAUNCH(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
+    if (kUnitTex != (args.tex_recs != nullptr) || (kUnitTex && (args.tex_uv == nullptr || args.tex_texels == nullptr || args.tex_bary == nullptr))) return hipErrorInvalidValue;
     if (args.glass == nullptr || (args.env_map != nullptr && (!v.sky || args.sky != nullptr))) return hipErrorInvalidValue;
     if (args.projection != 0 && v.view != 1) return hipErrorInvalidDeviceFunction;
     const int view = args.projection != 0 ? 5 : v.view;
@@ -1545,6 +1593,8 @@ hipError_t launch_glass_integrator(const RenderArgs &args, const plan::Variant &
     hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
     return hipGetLastError();
 }
+#undef PT_UNIT_KERNEL
+#undef PT_UNIT_LAUNCH
 #else
 // First-hit feature pass under a projection (pt_hip.h: pt_render_features_host): the ray pt_projection states for pixel (x, y) with
 // jitter 0, for launch_trace_rays.  (Here and not beside the pinhole's feature_rays_kernel in pt_denoise.hip: the ray needs this
@@ -1662,7 +1712,7 @@ hipError_t launch_integrator(const RenderArgs &args0, const plan::Variant &v, hi
     static uint32_t *d_cnt = nullptr;
     const int rows = args0.row_end - args0.row_begin;
     if (rows <= 0 || args0.width <= 0) return hipSuccess;
-    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr || args0.glass != nullptr) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
+    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr || args0.glass != nullptr || args0.tex_recs != nullptr) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
     if (!mod) {
         const char *path = std::getenv("PT_BLOCKPROF_HSACO");
         if (!path) return hipErrorInvalidValue;
@@ -1740,6 +1790,7 @@ Kernel kernel_for(const plan::Variant &v, bool projection) {
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
     const int rows = args.row_end - args.row_begin;
     if (rows <= 0 || args.width <= 0) return hipSuccess;
+    if (args.tex_recs != nullptr) return launch_texture_integrator(args, v, stream);   // (pt_texture_kernels.hip)
     if (args.glass != nullptr) return launch_glass_integrator(args, v, stream);   // (pt_glass_kernels.hip)
     if (args.env_map != nullptr) return launch_environment_integrator(args, v, stream);   // (pt_environment_kernels.hip)
     const Kernel kernel = kernel_for(v, args.projection != 0);
@@ -1786,6 +1837,8 @@ hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves) {
 #if defined(PT_PHASE_TIMERS) || defined(PT_BLOCK_PROFILE)
 // the diagnostic builds are linked without the dielectric kernels' unit: a handle with dielectrics is refused (PT_ERR_UNSUPPORTED)
 hipError_t launch_glass_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
+// and without the texture kernels': a handle with textures likewise
+hipError_t launch_texture_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
 const plan::Build &integrator_build() { return kBuild; }

@@ -96,6 +96,16 @@ struct RenderArgs {
     // (integrate_kernel_glass, pt_glass_kernels.hip), planned as the kernels the same launch would run without the list (no ids of
     // their own in the plan).  glass = n_mats records of 32 bytes (GlassRec below), read only where a ray has hit a triangle.
     const void *glass;
+    // The handle's albedo textures (pt_hip.h: pt_texture), appended likewise.  tex_recs != nullptr: the launch runs the texture kernels
+    // (integrate_kernel_texture, pt_texture_kernels.hip: the dielectric kernels with the texel step), planned as the kernels the same
+    // launch would run without the list; `glass` is then never null (a handle without dielectrics passes an all-zero table).
+    // tex_recs = n_mats records of 16 bytes (pt_texture.hpp: TexRec), tex_uv = 6 floats per triangle in the ORIGINAL triangle order,
+    // tex_texels = the list's texels, 16 bytes each, tex_bary = one 32-byte record per triangle (original order) that gives the hit
+    // point's barycentrics: all read only where a ray has hit a triangle of a textured material.
+    const void *tex_recs;
+    const float *tex_uv;
+    const void *tex_texels;
+    const void *tex_bary;               // 32 bytes per triangle in the original order (pt_texture.hpp: TexBary): the barycentrics' record
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif
@@ -106,12 +116,15 @@ const plan::Build &integrator_build();
 // launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds) -- with args.projection != 0
 // the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan;
 // with args.env_map != nullptr the environment kernel of skybox kernel `v` (v.sky), likewise; with args.glass != nullptr the dielectric
-// kernel of whichever of those the launch would run (hipErrorNotSupported from a diagnostic build, which has none)
+// kernel of whichever of those the launch would run (hipErrorNotSupported from a diagnostic build, which has none); with
+// args.tex_recs != nullptr the texture kernel of that one, likewise
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the environment kernels' translation unit (pt_environment_kernels.hip); launch_integrator calls it, nothing else does
 hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the dielectric kernels' translation unit (pt_glass_kernels.hip), likewise
 hipError_t launch_glass_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+// the texture kernels' translation unit (pt_texture_kernels.hip), likewise
+hipError_t launch_texture_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached).  A projection launch asks for its
 // camera twin's: the projection kernels are compiled for their twins' waves per SIMD and LDS (tests/test_projection_resources.py)
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);

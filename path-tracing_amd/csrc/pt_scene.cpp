@@ -28,16 +28,18 @@ void set_plane_from_normal(float *rec, const float *normal) {   // Triangle::Set
 }
 
 struct ObjIndex {
-    int v = -1, vn = -1;
+    int v = -1, vt = -1, vn = -1;
 };
 
-// "a/b/c" -> indices 0 and 2, each atoi()-1 (scene.cpp:6-14,90-96); missing fields give -1.
+// "a/b/c" -> indices 0 and 2, each atoi()-1 (scene.cpp:6-14,90-96); missing fields give -1.  The middle one, which the reference
+// never looks at, likewise (an empty field, "a//c", gives -1 too: atoi("") is 0).
 ObjIndex parse_face_group(const std::string &g) {
     ObjIndex r;
     const size_t s1 = g.find('/');
     r.v = std::atoi(g.substr(0, s1).c_str()) - 1;
     if (s1 != std::string::npos) {
         const size_t s2 = g.find('/', s1 + 1);
+        r.vt = std::atoi(g.substr(s1 + 1, s2 == std::string::npos ? std::string::npos : s2 - s1 - 1).c_str()) - 1;
         if (s2 != std::string::npos) {
             const size_t s3 = g.find('/', s2 + 1);
             r.vn = std::atoi(g.substr(s2 + 1, s3 == std::string::npos ? std::string::npos : s3 - s2 - 1).c_str()) - 1;
@@ -48,10 +50,13 @@ ObjIndex parse_face_group(const std::string &g) {
 
 // The MTL reader of scene.cpp:45-71: every run of the outer loop appends one material, fields are picked out of
 // a flat token stream, and the stream's eof flag (not its fail flag) ends both loops.
-void read_mtl(std::istream &in, std::vector<float> &mat) {
+// map_Kd: the token after it is recorded as the material's texture file name (HostScene::map_kd) and otherwise treated as the
+// reference treats it -- it goes through the dispatch as any token does, since the reference does not know the line.
+void read_mtl(std::istream &in, std::vector<float> &mat, std::vector<std::string> &map_kd) {
     std::string tok = "1";
     while (!in.eof()) {
         float rec[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::string kd_name;
         while (!in.eof() && tok != "newmtl") in >> tok;
         in >> tok;   // the material's name; it then goes through the same dispatch as any other token
         while (!in.eof() && tok != "newmtl") {
@@ -59,10 +64,13 @@ void read_mtl(std::istream &in, std::vector<float> &mat) {
             else if (tok == "Ke") in >> rec[3] >> rec[4] >> rec[5];
             else if (tok == "Ks") in >> rec[6] >> rec[7] >> rec[8];
             else if (tok == "Ns") in >> rec[9];
+            const bool was_map_kd = tok == "map_Kd";
             in >> tok;
+            if (was_map_kd && !in.fail()) kd_name = tok;
             if (in.fail() && !in.eof()) return;   // the reference would spin forever on a non-numeric field
         }
         mat.insert(mat.end(), rec, rec + 10);
+        map_kd.push_back(kd_name);
     }
 }
 
@@ -91,7 +99,7 @@ bool load_obj(const std::string &dir, const std::string &name, HostScene &out, s
         io_error = true;
         return false;
     }
-    std::vector<float> pos, nrm;
+    std::vector<float> pos, nrm, tex;
     int current_material = 0;
     std::string tok;
     while (!obj.eof()) {
@@ -110,14 +118,15 @@ bool load_obj(const std::string &dir, const std::string &name, HostScene &out, s
                 io_error = true;
                 return false;
             }
-            read_mtl(mtl, out.mat);
+            read_mtl(mtl, out.mat, out.map_kd);
         } else if (tok == "v") {
             float p[3] = {0, 0, 0};
             obj >> p[0] >> p[1] >> p[2];
             pos.insert(pos.end(), p, p + 3);
         } else if (tok == "vt") {
-            float uv[2];
+            float uv[2] = {0, 0};
             obj >> uv[0] >> uv[1];
+            tex.insert(tex.end(), uv, uv + 2);
         } else if (tok == "vn") {
             float n[3] = {0, 0, 0};
             obj >> n[0] >> n[1] >> n[2];
@@ -143,8 +152,19 @@ bool load_obj(const std::string &dir, const std::string &name, HostScene &out, s
                 err = "face refers to normal " + std::to_string(idx[0].vn + 1) + " of " + std::to_string(nn);
                 return false;
             }
+            const int nt = static_cast<int>(tex.size() / 2);
+            for (const auto &g : idx)
+                if (nt > 0 && g.vt >= nt) {   // (a file without vt lines: the index means nothing, as to the reference, and the corner gets (0, 0))
+                    err = "face refers to texture coordinate " + std::to_string(g.vt + 1) + " of " + std::to_string(nt);
+                    return false;
+                }
             append_triangle(out, &pos[3 * idx[0].v], &pos[3 * idx[1].v], &pos[3 * idx[2].v],
                             idx[0].vn >= 0 ? &nrm[3 * idx[0].vn] : nullptr, current_material);
+            for (const auto &g : idx) {   // each corner its own vt; (0, 0) without one
+                const bool has = g.vt >= 0 && g.vt < nt;
+                out.tri_uv.push_back(has ? tex[2 * g.vt] : 0.0f);
+                out.tri_uv.push_back(has ? tex[2 * g.vt + 1] : 0.0f);
+            }
         } else if (tok == "usemtl") {
             obj >> current_material;   // scene.cpp:105-106: an int, used directly as the index
             if (obj.fail() && !obj.eof()) {

@@ -13,6 +13,11 @@ struct HostScene {
     std::vector<float> tri;        // n_tri * 14: plane[4], v0, v1, v2, square
     std::vector<int32_t> tri_mat;  // n_tri
     std::vector<float> mat;        // n_mat * 10: Kd, Ke, Ks, Ns
+    // What the reference's loader drops (pt_hip.h: pt_texture): the texture coordinates of every face corner, n_tri * 6 (u, v per
+    // corner; (0, 0) where the face gives no vt index; empty for a scene made from arrays), and each material's map_Kd file name
+    // (n_mat entries, "" where the MTL has none).  Nothing reads them unless a handle is given a texture list.
+    std::vector<float> tri_uv;
+    std::vector<std::string> map_kd;
     int n_tri() const { return static_cast<int>(tri_mat.size()); }
     int n_mat() const { return static_cast<int>(mat.size() / 10); }
 };

@@ -47,6 +47,11 @@
 // the model (counted as usemtl counts them) smooth glass of refractive index ior (0.125 .. 8) whose transmitted light is multiplied
 // by the tint r:g:b (each 0 .. 1, default 1:1:1), e.g. -GLASS 4:1.5 or -GLASS 4:1.5:0.9:1:0.9,2:1.33.  A malformed entry, a value out
 // of range, an index outside the model and an emissive material end the program with status 2.  Every other flag combines.
+// Albedo textures (pt_scene_set_textures, not in the reference): -TEXTURE m:file.bmp[:nearest|bilinear][,m:file.bmp...] multiplies the
+// diffuse (or emissive) colour of material m of the model (counted as usemtl counts them) by the 24-bit BMP, looked up at the OBJ's vt
+// coordinates with repeat wrap (default bilinear); -TEXTURE mtl takes every map_Kd line of the model's MTL instead, the files relative
+// to -MODEL_PATH.  -TEXTURE_GAMMA <g> decodes the bytes as pow(b / 255, g) (default 2.2; 1 = linear).  A malformed entry, an unreadable
+// file, an index outside the model and a material that is also in -GLASS end the program with status 2.  Every other flag combines.
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -175,6 +180,11 @@ struct Options {
     std::string env, env_gain, env_rotate, env_size;   // -ENV / -ENV_GAIN / -ENV_ROTATE / -ENV_SIZE as given
     pt_environment_params env_params = {1.0f, 0.0f, 0};
     std::string glass_text;                // -GLASS as given
+    std::string texture_text, texture_gamma_text;   // -TEXTURE / -TEXTURE_GAMMA as given
+    struct TextureSpec { int32_t material; std::string file; int32_t filter; };
+    std::vector<TextureSpec> textures;     // what -TEXTURE makes (empty with -TEXTURE mtl: the model's MTL decides)
+    bool texture_mtl = false;
+    float texture_gamma = 2.2f;
     std::vector<pt_dielectric> glass;      // what it makes
     std::string projection_name = "perspective", ortho_height;   // -PROJECTION / -ORTHO_HEIGHT as given
     pt_projection projection{};    // what they make; kind 0 (perspective) = none is set
@@ -280,6 +290,8 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-ENV_ROTATE") o.env_rotate = v;
         if (f == "-ENV_SIZE") o.env_size = v;
         if (f == "-GLASS") o.glass_text = v;
+        if (f == "-TEXTURE") o.texture_text = v;
+        if (f == "-TEXTURE_GAMMA") o.texture_gamma_text = v;
         if (f == "-ORTHO_HEIGHT") o.ortho_height = v;
         if (f == "-APERTURE") { o.aperture = v; o.aperture_given = true; }
         if (f == "-FOCUS") { o.focus = v; o.focus_given = true; }
@@ -479,6 +491,34 @@ int configure(int argc, char **argv, Options &o) {
             if (!(t >= 0.0f && t <= 1.0f)) return refuse(2, "-GLASS: a tint component must lie in 0 .. 1 (\"" + entry + "\")");
         d.material = static_cast<int32_t>(m);
         o.glass.push_back(d);
+    }
+    // -TEXTURE: "mtl", or entries m:file[:nearest|bilinear] separated by commas (a file name may hold colons, not commas)
+    if (o.texture_text == "mtl") o.texture_mtl = true;
+    for (size_t at = 0; !o.texture_text.empty() && !o.texture_mtl && at <= o.texture_text.size();) {
+        const size_t comma = std::min(o.texture_text.find(',', at), o.texture_text.size());
+        const std::string entry = o.texture_text.substr(at, comma - at);
+        at = comma + 1;
+        const size_t c1 = entry.find(':');
+        Options::TextureSpec t = {0, "", PT_TEXTURE_BILINEAR};
+        float m = 0.0f;
+        bool ok = c1 != std::string::npos && c1 > 0 && entry.find_first_not_of("0123456789") == c1 && parse_float(entry.substr(0, c1), m) && m <= 16777216.0f;
+        if (ok) {
+            t.file = entry.substr(c1 + 1);
+            const size_t c2 = t.file.rfind(':');
+            const std::string last = c2 == std::string::npos ? "" : t.file.substr(c2 + 1);
+            if (last == "nearest" || last == "bilinear") {
+                t.filter = last == "nearest" ? PT_TEXTURE_NEAREST : PT_TEXTURE_BILINEAR;
+                t.file.resize(c2);
+            }
+            ok = !t.file.empty();
+        }
+        if (!ok) return refuse(2, "-TEXTURE takes mtl or m:file.bmp[:nearest|bilinear] entries separated by commas, not \"" + entry + "\"");
+        t.material = static_cast<int32_t>(m);
+        o.textures.push_back(t);
+    }
+    if (!o.texture_gamma_text.empty()) {
+        if (o.texture_text.empty()) return refuse(2, "-TEXTURE_GAMMA needs -TEXTURE");
+        if (!(parse_float(o.texture_gamma_text, o.texture_gamma) && o.texture_gamma > 0.0f && o.texture_gamma <= 16.0f)) return refuse(2, "-TEXTURE_GAMMA takes a number in (0, 16]");
     }
     // -PROJECTION: the kind by name, its angles from -FOV and -ASPECT; ortho needs a camera of its own (right and up are the view's extent)
     if (o.projection_name == "perspective") o.projection.kind = PT_PROJECTION_PERSPECTIVE;
@@ -1182,6 +1222,29 @@ int main(int argc, char **argv) {
     if (!o.env.empty() && pt_scene_set_environment_file(r.scene, o.env.c_str(), &o.env_params) != PT_OK) return die("pt_render");
     // -GLASS: what only the model can decide -- an index outside it, listed twice, an emissive material -- is refused here, with the library's words
     if (!o.glass.empty() && pt_scene_set_dielectrics(r.scene, o.glass.data(), static_cast<int32_t>(o.glass.size())) != PT_OK) return refuse(2, pt_last_error());
+    // -TEXTURE: the files are read and the list set here, after -GLASS, so that a material in both is refused with the library's words
+    if (o.texture_mtl) {
+        int32_t n_tri = 0, n_mat = 0;
+        if (pt_scene_counts(r.scene, &n_tri, &n_mat) != PT_OK) return die("pt_render");
+        for (int32_t m = 0; m < n_mat; ++m) {
+            const char *name = "";
+            if (pt_scene_get_map_kd(r.scene, m, &name) != PT_OK) return die("pt_render");
+            if (*name) o.textures.push_back({m, o.model_path + name, PT_TEXTURE_BILINEAR});
+        }
+        if (o.textures.empty()) std::fprintf(stderr, "pt_render: -TEXTURE mtl: the model's MTL has no map_Kd line, nothing is textured\n");
+    }
+    if (!o.textures.empty()) {
+        std::vector<std::vector<float>> texels(o.textures.size());
+        std::vector<pt_texture> list;
+        for (size_t i = 0; i < o.textures.size(); ++i) {
+            int32_t w = 0, h = 0;
+            if (pt_texture_load_bmp(o.textures[i].file.c_str(), o.texture_gamma, &w, &h, nullptr) != PT_OK) return refuse(2, std::string("-TEXTURE: ") + pt_last_error());
+            texels[i].resize(static_cast<size_t>(w) * h * 3);
+            if (pt_texture_load_bmp(o.textures[i].file.c_str(), o.texture_gamma, &w, &h, texels[i].data()) != PT_OK) return refuse(2, std::string("-TEXTURE: ") + pt_last_error());
+            list.push_back({o.textures[i].material, w, h, o.textures[i].filter, texels[i].data()});
+        }
+        if (pt_scene_set_textures(r.scene, list.data(), static_cast<int32_t>(list.size())) != PT_OK) return refuse(2, std::string("-TEXTURE: ") + pt_last_error());
+    }
     if (o.camera && pt_scene_set_camera(r.scene, &o.view) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
     // and its projection -- set before the lens and the motion, which the library refuses on a handle with one, as it refuses the
     // temporal stage when the first frame reaches it: asked here, before any device is looked at, with the library's own words
