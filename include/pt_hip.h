@@ -1670,6 +1670,75 @@ int pt_texture_load_bmp(const char *path, float gamma, int32_t *width, int32_t *
  * one texel four times). */
 int pt_texture_lookup(int32_t width, int32_t height, const float *rgb, int32_t filter, int32_t n, const float *uv, float *out_rgb, int32_t *indices);
 
+/* ---- smooth shading: per-corner shading normals ------------------------------------------------------------------- */
+
+/* A scene handle may carry SHADING NORMALS: nine floats per triangle -- n0, n1, n2 for its three corners in the order of its vertices
+ * -- triangles in the order the scene holds them.  Without them every output is what it was and the launches go to the kernels they
+ * went to.  They belong to the handle, as the dielectrics and the textures do: pt_scene_clone_to_device and pt_frame_create inherit
+ * them.  They work with every view, with a skybox, an environment or neither, with dielectrics and textures, with statistics,
+ * adaptive sampling and pass windows, in bands and frames, on small and box-tree scenes; launches are planned as without them (the
+ * same tiles and chunks).  Only directions change: ray origins, the geometry and the cull tables are untouched.  The diagnostic builds
+ * (phase timers, block profile) have no smooth kernels: a render of a handle with shading normals is PT_ERR_UNSUPPORTED there.
+ *
+ * Every operation below is a float operation rounded once, in the order written; nothing is fused; normalize3(v) is
+ * v * (1 / sqrt((v.x * v.x + v.y * v.y) + v.z * v.z)) with the correctly rounded root and division every scattered ray is normalised with.
+ *
+ * THE SHADING NORMAL Ns at a hit on triangle T at point p = o + d * t, with stored plane normal N:
+ *   b1, b2 from T's barycentric record exactly as the albedo textures state them (BARYCENTRICS above), not clamped;  b0 = (1 - b1) - b2
+ *   m = (b0 * n0 + b1 * n1) + b2 * n2  per component,      l = (m.x * m.x + m.y * m.y) + m.z * m.z
+ *   l not finite or not > 0:  Ns = N          (all-zero normals are the documented "use N"; so are corners that cancel)
+ *   else                      Ns = normalize3(m)
+ *   ((Ns.x * N.x + Ns.y * N.y) + Ns.z * N.z) < 0:  Ns = -Ns  (exact)
+ * THE SHADING STEP.  The lobe is chosen and the texel step runs as without the normals (it shares the record).  The EMISSIVE lobe is
+ * unchanged: it tests facing against N.  The GLOSSY lobe (reflection), the DIFFUSE lobe (hemisphere flip and cosine factor) and the
+ * DIELECTRIC step (c, entering, Fresnel, both directions) run with Ns wherever they use the normal without shading normals.  The
+ * next ray's ORIGIN is still p + N * oe, with the oe the step chose: +eps, or +-eps for a dielectric.  The origin never uses Ns.
+ * FALLBACK.  Let r be the step's new direction after its final normalize3.  If !(((r.x * N.x + r.y * N.y) + r.z * N.z) * oe > 0) --
+ * the direction leaves on the other side of the stored plane from the origin's offset -- the whole step is the step made with
+ * Ns = N instead: the step of a handle without shading normals, bit for bit.  No random number is drawn or moved; the same w1 .. w3
+ * are used.  On a path's last segment nothing new is computed.
+ * THE FIRST-HIT FEATURE PASS of a handle with shading normals writes normal = Ns of the first hit, after the flip and before any
+ * fallback; position, hit index and albedo (Kd x texel with a texture list) are what they are without.
+ *
+ * Not built: normal maps, and per-material smoothing groups (the OBJ's `s` lines).
+ *
+ * PT_ERR_INVALID_ARGUMENT: a NULL handle; a component that is not finite; normals for a scene without triangles.  Zeros are allowed.
+ * A setter validates and uploads first and swaps last: a refused call leaves every handle as it was.  A host-only scene (device < 0)
+ * accepts and returns them. */
+/* n9: 9 * n_tri floats (n_tri as pt_scene_counts gives it); NULL clears. */
+int pt_scene_set_shading_normals(pt_scene *scene, const float *n9);
+/* *has = 1 and n9 (may be NULL) gets the 9 * n_tri floats, or *has = 0. */
+int pt_scene_get_shading_normals(const pt_scene *scene, float *n9, int32_t *has);
+/* What pt_scene_load_obj kept of the file: the vn of each face corner as the file gives it (not normalised), the face's stored normal
+ * for a corner without a vn index (none, zero or negative).  *has = 0 for a scene made from arrays.  The library applies nothing by
+ * itself: a loaded scene renders as before until the caller passes normals to pt_scene_set_shading_normals.  A vn index beyond the
+ * vn lines read so far is PT_ERR_PARSE, on every corner. */
+int pt_scene_get_vertex_normals(const pt_scene *scene, float *n9, int32_t *has);
+/* The same on a frame: every device's copy of the frame's scene; a refused call changes none.  The getter answers for the root's. */
+int pt_frame_set_shading_normals(pt_frame *frame, const float *n9);
+int pt_frame_get_shading_normals(pt_frame *frame, float *n9, int32_t *has);
+/* The normal generator, on the host: out gets 9 floats per triangle from vertices (9 per triangle: v0, v1, v2).  Corners whose positions
+ * are bit-identical are one vertex.  A corner's normal is the sum, over the triangles at its vertex whose geometric face normal g
+ * satisfies f . g >= cos(crease_degrees) for the corner's own face normal f (its own face always counts), of g times the triangle's
+ * interior angle at that vertex (acos of the clamped cosine), normalised; accumulated in double, rounded to float last.  A degenerate
+ * triangle (no area, or a vertex that is not finite) contributes nothing and receives zeros; so does a corner whose sum has no
+ * length.  Checked to a tolerance, not bit for bit.  PT_ERR_INVALID_ARGUMENT: NULL, n_tri < 0, a crease outside 0 .. 180. */
+#define PT_SMOOTH_DEFAULT_CREASE 60.0f
+int pt_smooth_normals(int32_t n_tri, const float *vertices, float crease_degrees, float *out);
+/* pt_scene_load_obj with flags.  PT_LOAD_GEOMETRIC_PLANES: every face's plane comes from the cross product c of its edges (what a face
+ * without a vn index gets), not from the vn its first corner names -- the reference takes the plane from that vn, which tilts the planes
+ * of a file with true vertex normals.  The vn still chooses the side: where the first corner names a vn and (c . vn) < 0 (float, the
+ * three products summed left to right), the plane is made from -c, so a face whose winding disagrees with its normals (the lamp of
+ * models/Tor.obj) faces the way the file says, as it does without the flag.  A face without a vn index keeps c.  Flags 0 is
+ * pt_scene_load_obj.  An unknown flag is PT_ERR_INVALID_ARGUMENT. */
+#define PT_LOAD_GEOMETRIC_PLANES 1u
+int pt_scene_load_obj_ex(const char *model_dir, const char *model_name, int device, uint32_t flags, pt_scene **out);
+/* The interpolation alone, on the host, for n points on one triangle: vertices = v0, v1, v2 (9 floats), plane_normal = N (3), normals =
+ * n0, n1, n2 (9); out[3 i ..] = Ns at points[3 i ..] as stated above (the record is formed from the vertices as the textures state
+ * it); interpolated (may be NULL) gets 1 where Ns came from m and 0 where it is N. */
+int pt_shading_normal_at(const float *vertices, const float *plane_normal, const float *normals, int32_t n, const float *points, float *out,
+                         int32_t *interpolated);
+
 /* ---- misc ------------------------------------------------------------------------------------------- */
 int pt_abi_version(void);
 int pt_device_count(void);

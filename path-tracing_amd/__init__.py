@@ -65,7 +65,10 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_scene_set_dielectrics", "pt_scene_get_dielectrics", "pt_frame_set_dielectrics", "pt_frame_get_dielectrics",
                "pt_scene_set_texcoords", "pt_scene_get_texcoords", "pt_scene_set_textures", "pt_scene_get_textures",
                "pt_frame_set_texcoords", "pt_frame_get_texcoords", "pt_frame_set_textures", "pt_frame_get_textures",
-               "pt_scene_get_map_kd", "pt_texture_load_bmp", "pt_texture_lookup", "pt_scene_get_texture_records"]
+               "pt_scene_get_map_kd", "pt_texture_load_bmp", "pt_texture_lookup", "pt_scene_get_texture_records",
+               "pt_scene_set_shading_normals", "pt_scene_get_shading_normals", "pt_scene_get_vertex_normals",
+               "pt_frame_set_shading_normals", "pt_frame_get_shading_normals", "pt_smooth_normals", "pt_scene_load_obj_ex",
+               "pt_shading_normal_at"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -548,6 +551,38 @@ def texture_lookup(texels, uv, filter="bilinear", library=None, want_indices=Fal
     return (out, idx) if want_indices else out
 
 
+LOAD_GEOMETRIC_PLANES = 1
+SMOOTH_DEFAULT_CREASE = 60.0
+
+
+def smooth_normals(vertices, crease=SMOOTH_DEFAULT_CREASE, library=None):
+    """pt_smooth_normals, the normal generator: (n_tri, 3, 3) unit normals per corner from the triangles' vertices (n_tri, 3, 3) -- or
+    a scene's 14-float triangle records -- welded where positions are bit-identical, smoothed across faces within `crease` degrees,
+    weighted by the angle at the vertex; zeros for a degenerate triangle."""
+    L = library or lib()
+    v = np.ascontiguousarray(vertices, np.float32)
+    if v.ndim == 2 and v.shape[1] == 14:
+        v = np.ascontiguousarray(v[:, 4:13])
+    v = v.reshape(-1, 9)
+    out = np.zeros((len(v), 3, 3), np.float32)
+    _check(L.pt_smooth_normals(len(v), _fp(v), crease, _fp(out)), L)
+    return out
+
+
+def shading_normal_at(vertices, plane_normal, normals, points, library=None, want_interpolated=False):
+    """pt_shading_normal_at, the host's own interpolation: Ns [n, 3] at `points` [n, 3] on the triangle `vertices` (3, 3) with stored
+    normal `plane_normal` and corner normals `normals` (3, 3); with want_interpolated also whether each came from the corners."""
+    L = library or lib()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(9)
+    N = np.ascontiguousarray(plane_normal, np.float32).reshape(3)
+    n9 = np.ascontiguousarray(normals, np.float32).reshape(9)
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    out = np.zeros((len(p), 3), np.float32)
+    own = np.zeros(len(p), np.int32)
+    _check(L.pt_shading_normal_at(_fp(v), _fp(N), _fp(n9), len(p), _fp(p), _fp(out), _ip(own)), L)
+    return (out, own.astype(bool)) if want_interpolated else out
+
+
 def _projection_arg(projection_, library):
     """A Projection, a kind (number or name) or None -> a pointer argument for pt_scene_set_projection / pt_frame_set_projection."""
     if projection_ is None:
@@ -685,6 +720,13 @@ def load_library(path):
         getattr(L, f"pt_{who}_set_textures").argtypes = [vp, tp, C.c_int32]
         getattr(L, f"pt_{who}_get_textures").argtypes = [vp, tp, ip]
     L.pt_scene_get_texture_records.argtypes = [vp, fp]
+    for who in ("scene", "frame"):
+        getattr(L, f"pt_{who}_set_shading_normals").argtypes = [vp, fp]
+        getattr(L, f"pt_{who}_get_shading_normals").argtypes = [vp, fp, ip]
+    L.pt_scene_get_vertex_normals.argtypes = [vp, fp, ip]
+    L.pt_smooth_normals.argtypes = [C.c_int32, fp, C.c_float, fp]
+    L.pt_scene_load_obj_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(vp)]
+    L.pt_shading_normal_at.argtypes = [fp, fp, fp, C.c_int32, fp, fp, ip]
     L.pt_scene_get_map_kd.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p)]
     L.pt_texture_load_bmp.argtypes = [C.c_char_p, C.c_float, ip, ip, fp]
     L.pt_texture_lookup.argtypes = [C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32, fp, fp, ip]
@@ -895,7 +937,42 @@ class _TextureMethods:
         return [Texture(e.material, np.ctypeslib.as_array(e.rgb, (e.height, e.width, 3)).copy(), e.filter) for e in arr[:n.value]]
 
 
-class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods):
+class _SmoothMethods:
+    """set_shading_normals / shading_normals / vertex_normals of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
+    _smooth_prefix = "pt_scene_"
+
+    def set_shading_normals(self, normals):
+        """-SMOOTH: the handle's shading normals, (n_tri, 3, 3) -- a normal per corner of every triangle -- or None to clear them.
+        Zeros mean "use the stored normal"; a component that is not finite is refused."""
+        fn = getattr(self._L, self._smooth_prefix + "set_shading_normals")
+        if normals is None:
+            _check(fn(self._h, None), self._L)
+            return
+        a = np.ascontiguousarray(normals, np.float32)
+        if a.size != 9 * self._n_tri():
+            raise ValueError("set_shading_normals: 9 floats per triangle")
+        _check(fn(self._h, _fp(a)), self._L)
+
+    def _normals(self, fn):
+        has = C.c_int32()
+        _check(fn(self._h, None, C.byref(has)), self._L)
+        if not has.value:
+            return None
+        a = np.zeros((self._n_tri(), 3, 3), np.float32)
+        _check(fn(self._h, _fp(a), C.byref(has)), self._L)
+        return a
+
+    def shading_normals(self):
+        """(n_tri, 3, 3), or None if the handle has none."""
+        return self._normals(getattr(self._L, self._smooth_prefix + "get_shading_normals"))
+
+    def vertex_normals(self):
+        """pt_scene_get_vertex_normals: the vn the loader kept, (n_tri, 3, 3), or None for a scene made from arrays."""
+        scene = getattr(self, "_scene", self)
+        return scene._normals(scene._L.pt_scene_get_vertex_normals)
+
+
+class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods):
     """Owns a pt_scene handle (Scene + LoadModel of the reference, scene.h:17-19)."""
 
     def __init__(self, handle, library=None):
@@ -903,11 +980,17 @@ class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods):
         self._L = library or lib()
 
     @classmethod
-    def load_obj(cls, model_dir, model_name, device=0, library=None):
+    def load_obj(cls, model_dir, model_name, device=0, library=None, geometric_planes=False):
+        """pt_scene_load_obj; geometric_planes (PT_LOAD_GEOMETRIC_PLANES): every plane from the cross product, whatever vn the face names."""
         L = library or lib()
         h = C.c_void_p()
-        _check(L.pt_scene_load_obj(model_dir.encode(), model_name.encode(), device, C.byref(h)), L)
+        if geometric_planes:
+            _check(L.pt_scene_load_obj_ex(model_dir.encode(), model_name.encode(), device, LOAD_GEOMETRIC_PLANES, C.byref(h)), L)
+        else:
+            _check(L.pt_scene_load_obj(model_dir.encode(), model_name.encode(), device, C.byref(h)), L)
         return cls(h, L)
+
+    load = load_obj
 
     @classmethod
     def create(cls, triangles, triangle_material, materials, device=0, library=None):
@@ -1636,9 +1719,9 @@ def bvh_depth(nodes):
     return int(level.max())
 
 
-class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods):
+class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods):
     """pt_frame: one image on several devices from one host program -- row bands, one gather to the first device."""
-    _env_prefix = _glass_prefix = _tex_prefix = "pt_frame_"
+    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = "pt_frame_"
 
     def _n_tri(self):
         return self._scene.counts()[0]

@@ -118,6 +118,7 @@ int upload(pt_scene *s, int device) {
     if (s->env && (rc = s->d_env.upload(pt::env_with_apron(s->env->n, s->env->rgb.data()), "environment map", 64)) != PT_OK) return rc;
     if (s->glass && (rc = s->d_glass.upload(s->glass->table, "dielectric table", 64)) != PT_OK) return rc;
     if (s->textures && (rc = ptc::upload_textures(*s->textures, *s->texcoords, s->shared->tables, s->d_tex)) != PT_OK) return rc;
+    if (s->smooth && (rc = ptc::upload_smooth(*s->smooth, s->shared->tables, s->d_smooth)) != PT_OK) return rc;
     return PT_OK;
 }
 
@@ -289,6 +290,16 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
         a.tex_bary = scene->d_tex.bary.get<void>();
         if (!a.glass) a.glass = scene->d_tex.no_glass.get<void>();
     }
+    if (scene->smooth && scene->d_smooth.normals) {   // the smooth kernels of those (integrate_kernel_smooth); absent lists as all-zero tables
+        a.smooth_normals = scene->d_smooth.normals.get<void>();
+        if (!a.tex_recs) {   // (no entry is textured: the coordinates and the texels are never read)
+            a.tex_recs = scene->d_smooth.no_tex.get<void>();
+            a.tex_uv = scene->d_smooth.no_tex.get<float>();
+            a.tex_texels = scene->d_smooth.no_tex.get<void>();
+            a.tex_bary = scene->d_smooth.bary.get<void>();
+        }
+        if (!a.glass) a.glass = scene->d_smooth.no_glass.get<void>();
+    }
     a.n_clusters = static_cast<int32_t>(t.clusters.size());
     a.n_tri = scene->shared->host.n_tri();
     a.big = t.big ? 1 : 0;
@@ -411,6 +422,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
         PT_HIP_TRY(hipEventRecord(ctx.ev0.get(), stream));
     }
     const hipError_t launched = pt::launch_integrator(a, tiles.variant, stream);
+    if (launched == hipErrorNotSupported && a.smooth_normals != nullptr) return fail(PT_ERR_UNSUPPORTED, "shading normals: this diagnostic build of the library has no smooth kernels");
     if (launched == hipErrorNotSupported && a.tex_recs != nullptr) return fail(PT_ERR_UNSUPPORTED, "textures: this diagnostic build of the library has no texture kernels");
     if (launched == hipErrorNotSupported && a.glass != nullptr) return fail(PT_ERR_UNSUPPORTED, "dielectrics: this diagnostic build of the library has no dielectric kernels");
     PT_HIP_TRY(launched);
@@ -599,15 +611,16 @@ int pt_scene_skybox_size(const pt_scene *scene, int32_t *width, int32_t *height)
     return PT_OK;
 }
 
-static int scene_load_obj_impl(const char *model_dir, const char *model_name, int device, pt_scene **out) {
+static int scene_load_obj_impl(const char *model_dir, const char *model_name, int device, uint32_t flags, pt_scene **out) {
     if (!model_dir || !model_name || !out) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
+    if (flags & ~static_cast<uint32_t>(PT_LOAD_GEOMETRIC_PLANES)) return fail(PT_ERR_INVALID_ARGUMENT, "pt_scene_load_obj_ex: unknown flag");
     ScenePtr s(new pt_scene);
     s->shared = std::make_shared<pt_scene_host>();
     std::string err;
     bool io = false;
     const auto t0 = std::chrono::steady_clock::now();
-    if (!pt::load_obj(model_dir, model_name, s->shared->host, err, io)) return fail(io ? PT_ERR_IO : PT_ERR_PARSE, err);
+    if (!pt::load_obj(model_dir, model_name, s->shared->host, err, io, (flags & PT_LOAD_GEOMETRIC_PLANES) != 0)) return fail(io ? PT_ERR_IO : PT_ERR_PARSE, err);
     // (finish_scene destroys the pt_scene on failure -- no device, bad ordinal, upload error --: keep the host side alive here)
     const std::shared_ptr<pt_scene_host> h = s->shared;
     const int rc = finish_scene(std::move(s), device, out);
@@ -640,6 +653,7 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->glass = src->glass;     // and its dielectrics
     s->texcoords = src->texcoords;   // and its texture coordinates and textures
     s->textures = src->textures;
+    s->smooth = src->smooth;   // and its shading normals
     s->has_camera = src->has_camera;   // and its camera
     s->camera = src->camera;
     s->has_lens = src->has_lens;       // and lens
@@ -1366,7 +1380,11 @@ int pt_write_bmp(const char *path, int32_t width, int32_t height, const uint8_t 
 // ---- the guarded entry points (definitions above are the bodies) ----
 
 int pt_scene_load_obj(const char *model_dir, const char *model_name, int device, pt_scene **out) {
-    return guarded([&] { return scene_load_obj_impl(model_dir, model_name, device, out); });
+    return guarded([&] { return scene_load_obj_impl(model_dir, model_name, device, 0u, out); });
+}
+
+int pt_scene_load_obj_ex(const char *model_dir, const char *model_name, int device, uint32_t flags, pt_scene **out) {
+    return guarded([&] { return scene_load_obj_impl(model_dir, model_name, device, flags, out); });
 }
 
 int pt_scene_create(const float *triangles, const int32_t *triangle_material, int32_t n_triangles, const float *materials, int32_t n_materials, int device, pt_scene **out) {

@@ -31,6 +31,7 @@
 #include "pt_optics.hpp"
 #include "pt_scene.hpp"
 #include "pt_sharpen.hpp"
+#include "pt_smooth.hpp"
 #include "pt_texture.hpp"
 #include "pt_upsample.hpp"
 
@@ -85,6 +86,13 @@ struct DeviceTextures {
     ptc::DeviceBuffer recs, uv, texels, no_glass, bary;   // (bary: the barycentrics' record of every triangle, pt_texture.hpp: TexBary)
 };
 
+// The shading normals of a handle (pt_hip.h: shading normals) on its device: three 16-byte records per triangle in the original order
+// (pt_smooth.hpp: SmoothCorner), the barycentrics' record of every triangle, and the all-zero texture and dielectric tables a handle
+// without a texture list or dielectrics passes to the smooth kernels.
+struct DeviceSmooth {
+    ptc::DeviceBuffer normals, bary, no_tex, no_glass;
+};
+
 // Device copy of one CullTables (they depend on eps and on the envelope the camera needs; a scene keeps the one of its last
 // render).
 struct DeviceCull {
@@ -124,6 +132,8 @@ struct pt_scene {
     std::shared_ptr<const std::vector<float>> texcoords;   // this handle's texture coordinates (nullptr = none; a loaded scene has the OBJ's); copies inherit them
     std::shared_ptr<const pt_texture_list> textures;       // this handle's textures (nullptr = none; only with texcoords); copies inherit them
     DeviceTextures d_tex;          // both on this copy's device, uploaded when a list is set
+    std::shared_ptr<const std::vector<float>> smooth;   // this handle's shading normals, 9 per triangle (nullptr = none); copies inherit them
+    DeviceSmooth d_smooth;         // on this copy's device
     bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
     pt_camera camera{};
     bool has_lens = false;         // this handle's lens (pt_scene_set_lens; radius > 0); copies made from it inherit it
@@ -424,6 +434,22 @@ inline int upload_textures(const pt_texture_list &list, const std::vector<float>
     if ((rc = d.bary.upload(texture_bary_records(tables.exact), "texture barycentric records", 64)) != PT_OK) return rc;
     if ((rc = d.recs.upload(list.recs, "texture table", 64)) != PT_OK || (rc = d.uv.upload(texcoords, "texture coordinates", 64)) != PT_OK ||
         (rc = d.texels.upload(list.pool, "texels", 64)) != PT_OK || (rc = d.no_glass.upload(zeros, "empty dielectric table", 64)) != PT_OK)
+        return rc;
+    out = std::move(d);
+    return PT_OK;
+}
+
+// A handle's shading normals onto the current device (the setters of pt_smooth_capi.cpp; a clone's upload in pt_capi.cpp).  `out` is
+// only written once every upload has succeeded.
+inline int upload_smooth(const std::vector<float> &n9, const pt::DeviceTables &tables, DeviceSmooth &out) {
+    DeviceSmooth d;
+    int rc;
+    std::vector<pt::SmoothCorner> corners(n9.size() / 3);
+    for (size_t i = 0; i < corners.size(); ++i) corners[i] = pt::SmoothCorner{n9[3 * i], n9[3 * i + 1], n9[3 * i + 2], 0.0f};
+    const std::vector<pt::GlassRec> no_glass(tables.mats.size(), pt::GlassRec{});
+    const std::vector<pt::TexRec> no_tex(tables.mats.size(), pt::TexRec{0, 0, 0, 0});
+    if ((rc = d.normals.upload(corners, "shading normals", 64)) != PT_OK || (rc = d.bary.upload(texture_bary_records(tables.exact), "barycentric records", 64)) != PT_OK ||
+        (rc = d.no_tex.upload(no_tex, "empty texture table", 64)) != PT_OK || (rc = d.no_glass.upload(no_glass, "empty dielectric table", 64)) != PT_OK)
         return rc;
     out = std::move(d);
     return PT_OK;

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "pt_denoise.hpp"
+#include "pt_smooth_features.hpp"
 #include "pt_texture_features.hpp"
 
 using ptc::fail;
@@ -22,7 +23,10 @@ int ptc::enqueue_first_hits(pt_scene *scene, const pt::RenderArgs &a, const pt_c
     if (a.projection != 0) PT_HIP_TRY(pt::launch_projection_rays(a, width, height, row_begin, rows, out.origins, out.directions, stream));
     else PT_HIP_TRY(pt::launch_feature_rays(cam, width, height, row_begin, rows, out.origins, out.directions, stream));
     PT_HIP_TRY(pt::launch_trace_rays(a, out.origins, out.directions, n, out.hit, out.hit_t, stream));
-    if (a.tex_recs != nullptr)   // the handle's textures: the gather's twin, albedo = Kd x texel (pt_texture_features.hip)
+    if (a.smooth_normals != nullptr)   // the handle's shading normals: normal = Ns, and the textured albedo as below (pt_smooth_features.hip)
+        PT_HIP_TRY(pt::launch_feature_gather_smooth(scene->d_exact.get<pt::ExactRec>(), scene->d_mats.get<pt::MatRec>(), a.tex_recs, a.tex_uv, a.tex_texels, a.tex_bary,
+                                                    a.smooth_normals, out.origins, out.directions, out.hit, out.hit_t, n, out.position, out.normal, out.albedo, stream));
+    else if (a.tex_recs != nullptr)   // the handle's textures: the gather's twin, albedo = Kd x texel (pt_texture_features.hip)
         PT_HIP_TRY(pt::launch_feature_gather_textured(scene->d_exact.get<pt::ExactRec>(), scene->d_mats.get<pt::MatRec>(), a.tex_recs, a.tex_uv, a.tex_texels, a.tex_bary,
                                                       out.origins, out.directions, out.hit, out.hit_t, n, out.position, out.normal, out.albedo, stream));
     else

@@ -6,6 +6,8 @@
 // (pt_hip.h: pt_dielectric) reflects or refracts by the Fresnel term instead of running the material's lobes.
 // TEX (only pt::integrate_kernel_texture: false in every other kernel) = a hit on a triangle of a material the handle's texture table
 // marks (pt_hip.h: pt_texture) multiplies the throughput by the texel before the emissive or the diffuse lobe runs.
+// SMOOTH (only pt::integrate_kernel_smooth: false in every other kernel; with GLASS and TEX) = the glossy lobe, the diffuse lobe and
+// the dielectric step run with the interpolated shading normal of the hit point (pt_hip.h: shading normals; pt_smooth.hpp spells it).
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
@@ -750,6 +752,27 @@
                     // point (pt_hip.h: pt_texture; pt_texture.hpp spells barycentrics, wrap and filters); the glossy lobe and a
                     // dielectric do not.  On a path's last segment only the emissive lobe computes anything.  hit_rec may be a record
                     // of either table: `orig` is the triangle's index in the original order, which the coordinates are stored in.
+                    // SMOOTH: the same texel step, with the barycentrics kept for the shading normal below -- one load of the triangle's
+                    // record serves both.
+                    [[maybe_unused]] float sb1 = 0.0f, sb2 = 0.0f;
+                    if constexpr (SMOOTH) {
+                        const bool scatters = kind > 0 && depth[k] + 1 < mrr;
+                        const TextureView tv = texture_view();
+                        const size_t ti = static_cast<size_t>(rec->orig);
+                        TexRec tm = {0u, 0, 0, 0};
+                        if (kind == 0 || (kind == 2 && scatters)) tm = tv.recs()[mi];
+                        if (scatters || tm.w != 0) {
+                            const TexBary t = tv.bary()[ti];   // (two 16-byte loads)
+                            tex_barycentrics_record(t.a1[0], t.a1[1], t.a1[2], t.c1, t.a2[0], t.a2[1], t.a2[2], t.c2, px, py, pz, sb1, sb2);
+                        }
+                        if (tm.w != 0) {
+                            const float *uv = tv.uv() + 6 * ti;
+                            float tu, tvv, xr, xg, xb;
+                            tex_interpolate(uv[0], uv[1], uv[2], uv[3], uv[4], uv[5], sb1, sb2, tu, tvv);
+                            tex_lookup(tv.texels() + tm.first, tm.w, tm.h, tm.filter, tu, tvv, xr, xg, xb);
+                            tr[k] *= xr; tg[k] *= xg; tb[k] *= xb;
+                        }
+                    } else
                     if constexpr (TEX) {
                         if (kind == 0 || (kind == 2 && depth[k] + 1 < mrr)) {
                             const TextureView tv = texture_view();
@@ -789,6 +812,76 @@
                         [[maybe_unused]] float oe = eps;   // GLASS: +-eps, the side of the surface the next ray starts on
                         bool dielectric = false;
                         if constexpr (GLASS) dielectric = kind == 3;
+                        if constexpr (SMOOTH) {
+                            // The step with the shading normal Ns (pt_hip.h: shading normals), and the same step with the stored
+                            // normal N: the first is kept unless its direction leaves on the other side of the stored plane from
+                            // the origin's offset.  Both are computed and one is selected; the diffuse lobe's hemisphere sample,
+                            // which no normal enters, is drawn once.  The same w1 .. w3 serve both.
+                            const SmoothCorner *__restrict__ sc = smooth_view() + 3 * static_cast<size_t>(rec->orig);
+                            const SmoothCorner c0 = sc[0], c1 = sc[1], c2 = sc[2];   // (three 16-byte loads)
+                            float sx, sy, sz;
+                            smooth_normal(c0.x, c0.y, c0.z, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, sb1, sb2, pl.x, pl.y, pl.z,
+                                          [](float &vx, float &vy, float &vz) { normalize3(vx, vy, vz); }, sx, sy, sz);
+                            float hx = 0.0f, hy = 0.0f, hz = 0.0f;
+                            if (!dielectric && kind != 1) {   // diffuse, material.h:90-100: the sample
+                                const float xi1 = unit_float(w1), xi2 = unit_float(w2);
+                                const float ang = 2 * 3.141593f * xi2;
+                                float sn, cs;
+                                portable_sincos(ang, sn, cs);
+                                const float sq = sqrt_rn_normal(xi1);
+                                hx = sq * cs; hy = sq * sn; hz = sqrt_rn_normal(1 - xi1);
+                                normalize3(hx, hy, hz);
+                            }
+                            auto step = [&](const float nx, const float ny, const float nz, float &ux, float &uy, float &uz, float &ur, float &ug,
+                                            float &ub, float &uo) {
+                                uo = eps;
+                                if (dielectric) {
+                                    const float c = (nx * q[k].dx + ny * q[k].dy) + nz * q[k].dz;
+                                    const bool entering = c < 0;
+                                    const float eta = entering ? grec->inv_ior : g_ior;
+                                    float ci = entering ? -c : c;
+                                    ci = ci < 1 ? ci : 1;
+                                    const float s2 = (eta * eta) * (1 - ci * ci);
+                                    const float ec = eta * ci;
+                                    float fresnel = 1.0f, ct = 0.0f;
+                                    if (s2 < 1) {
+                                        ct = sqrt_rn_normal(1 - s2);
+                                        const float et = eta * ct;
+                                        const float rs = (ec - ct) / (ec + ct), rp = (ci - et) / (ci + et);
+                                        fresnel = 0.5f * (rs * rs + rp * rp);
+                                    }
+                                    float dm, nk;
+                                    if (unit_float(w3) < fresnel) {
+                                        dm = 1.0f; nk = 2 * ci;
+                                        uo = entering ? eps : -eps;
+                                        ur = ug = ub = 1.0f;
+                                    } else {
+                                        dm = eta; nk = ec - ct;
+                                        uo = entering ? -eps : eps;
+                                        ur = grec->tint[0]; ug = grec->tint[1]; ub = grec->tint[2];
+                                    }
+                                    if (!entering) nk = -nk;
+                                    ux = q[k].dx * dm + nx * nk; uy = q[k].dy * dm + ny * nk; uz = q[k].dz * dm + nz * nk;
+                                } else if (kind == 1) {
+                                    const float dn = (nx * q[k].dx + ny * q[k].dy) + nz * q[k].dz;
+                                    ux = q[k].dx - nx * dn * 2.0f; uy = q[k].dy - ny * dn * 2.0f; uz = q[k].dz - nz * dn * 2.0f;
+                                    ur = m1v.x; ug = m1v.y; ub = m1v.z;
+                                } else {
+                                    ux = hx; uy = hy; uz = hz;
+                                    if ((nx * ux + ny * uy) + nz * uz < 0) { ux *= -1; uy *= -1; uz *= -1; }
+                                    float dt = (nx * ux + ny * uy) + nz * uz;
+                                    dt = dt > 0.0f ? dt : 0.0f;
+                                    ur = m0v.x * dt; ug = m0v.y * dt; ub = m0v.z * dt;
+                                }
+                                normalize3(ux, uy, uz);
+                            };
+                            float ax, ay, az, ar, ag, ab, ao;
+                            step(sx, sy, sz, ax, ay, az, ar, ag, ab, ao);
+                            step(pl.x, pl.y, pl.z, rx, ry, rz, fr, fg, fb, oe);
+                            if (smooth_keeps(ax, ay, az, pl.x, pl.y, pl.z, ao)) {
+                                rx = ax; ry = ay; rz = az; fr = ar; fg = ag; fb = ab; oe = ao;
+                            }
+                        } else {
                         if (dielectric) {   // smooth dielectric (pt_hip.h: pt_dielectric states this operation by operation)
                             if constexpr (GLASS) {
                                 const float c = (pl.x * q[k].dx + pl.y * q[k].dy) + pl.z * q[k].dz;
@@ -839,6 +932,7 @@
                             fr = m0v.x * dt; fg = m0v.y * dt; fb = m0v.z * dt;
                         }
                         normalize3(rx, ry, rz);   // Ray::Reflect normalises (again), ray.h:47
+                        }
                         if constexpr (GLASS) {   // p + n eps or p - n eps: the sign is exact, N * (-eps) = -(N * eps)
                             q[k].ox = px + pl.x * oe; q[k].oy = py + pl.y * oe; q[k].oz = pz + pl.z * oe;
                         } else {

@@ -76,7 +76,7 @@ void read_mtl(std::istream &in, std::vector<float> &mat, std::vector<std::string
 
 }  // namespace
 
-void append_triangle(HostScene &s, const float v0[3], const float v1[3], const float v2[3], const float *vn, int material) {
+void append_triangle(HostScene &s, const float v0[3], const float v1[3], const float v2[3], const float *vn, int material, const float *toward) {
     float rec[14];
     std::memcpy(rec + 4, v0, 12);
     std::memcpy(rec + 7, v1, 12);
@@ -87,11 +87,15 @@ void append_triangle(HostScene &s, const float v0[3], const float v1[3], const f
     set_plane_from_normal(rec, c);        // triangles.h:34
     rec[13] = std::sqrt(dot3(c, c));      // triangles.h:35
     if (vn) set_plane_from_normal(rec, vn);   // scene.cpp:102-104
+    else if (toward && dot3(c, toward) < 0.0f) {   // PT_LOAD_GEOMETRIC_PLANES: the cross product, on the side the file's vn names
+        const float back[3] = {-c[0], -c[1], -c[2]};
+        set_plane_from_normal(rec, back);
+    }
     s.tri.insert(s.tri.end(), rec, rec + 14);
     s.tri_mat.push_back(material);
 }
 
-bool load_obj(const std::string &dir, const std::string &name, HostScene &out, std::string &err, bool &io_error) {
+bool load_obj(const std::string &dir, const std::string &name, HostScene &out, std::string &err, bool &io_error, bool geometric_planes) {
     io_error = false;
     std::ifstream obj(dir + name);
     if (!obj.is_open()) {
@@ -148,10 +152,11 @@ bool load_obj(const std::string &dir, const std::string &name, HostScene &out, s
                 err = "usemtl " + std::to_string(current_material) + " with " + std::to_string(out.n_mat()) + " materials";
                 return false;
             }
-            if (idx[0].vn >= nn) {
-                err = "face refers to normal " + std::to_string(idx[0].vn + 1) + " of " + std::to_string(nn);
-                return false;
-            }
+            for (const auto &g : idx)   // (the reference reads the first corner's only; the other two are kept for the shading normals)
+                if (g.vn >= nn) {
+                    err = "face refers to normal " + std::to_string(g.vn + 1) + " of " + std::to_string(nn);
+                    return false;
+                }
             const int nt = static_cast<int>(tex.size() / 2);
             for (const auto &g : idx)
                 if (nt > 0 && g.vt >= nt) {   // (a file without vt lines: the index means nothing, as to the reference, and the corner gets (0, 0))
@@ -159,7 +164,12 @@ bool load_obj(const std::string &dir, const std::string &name, HostScene &out, s
                     return false;
                 }
             append_triangle(out, &pos[3 * idx[0].v], &pos[3 * idx[1].v], &pos[3 * idx[2].v],
-                            idx[0].vn >= 0 ? &nrm[3 * idx[0].vn] : nullptr, current_material);
+                            idx[0].vn >= 0 && !geometric_planes ? &nrm[3 * idx[0].vn] : nullptr, current_material,
+                            idx[0].vn >= 0 && geometric_planes ? &nrm[3 * idx[0].vn] : nullptr);
+            for (const auto &g : idx) {   // each corner its own vn, as the file gives it; the face's stored normal without one
+                const float *n = g.vn >= 0 ? &nrm[3 * g.vn] : &out.tri[out.tri.size() - 14];
+                out.tri_vn.insert(out.tri_vn.end(), n, n + 3);
+            }
             for (const auto &g : idx) {   // each corner its own vt; (0, 0) without one
                 const bool has = g.vt >= 0 && g.vt < nt;
                 out.tri_uv.push_back(has ? tex[2 * g.vt] : 0.0f);

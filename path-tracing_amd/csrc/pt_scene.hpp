@@ -18,6 +18,9 @@ struct HostScene {
     // (n_mat entries, "" where the MTL has none).  Nothing reads them unless a handle is given a texture list.
     std::vector<float> tri_uv;
     std::vector<std::string> map_kd;
+    // Likewise the vn of every face corner (pt_hip.h: shading normals), n_tri * 9, as the file gives them; the face's stored normal
+    // where a corner gives no vn index; empty for a scene made from arrays.  Nothing reads them unless a caller asks for them.
+    std::vector<float> tri_vn;
     int n_tri() const { return static_cast<int>(tri_mat.size()); }
     int n_mat() const { return static_cast<int>(mat.size() / 10); }
 };
@@ -26,11 +29,15 @@ inline bool material_emits(const float *mat) { return mat[3] != 0.0f || mat[4] !
 
 // Scene::LoadModel (scene.cpp:26-109).  Returns false and sets `err` on I/O or index errors
 // (the reference exits or has undefined behaviour there).
-bool load_obj(const std::string &model_dir, const std::string &model_name, HostScene &out, std::string &err, bool &io_error);
+// geometric_planes (PT_LOAD_GEOMETRIC_PLANES): every face's plane comes from its vertices' cross product, negated where it points
+// away from the first corner's vn (c . vn < 0), so that a face keeps the side its file gives it whatever its winding.
+bool load_obj(const std::string &model_dir, const std::string &model_name, HostScene &out, std::string &err, bool &io_error,
+              bool geometric_planes = false);
 
-// Adds one triangle the way Triangle's constructor + SetNormal do (triangles.h:27-44).
+// Adds one triangle the way Triangle's constructor + SetNormal do (triangles.h:27-44).  Without a vn the plane is the cross
+// product's; `toward_or_null` then turns it onto that direction's side (the cross product negated where c . toward < 0).
 void append_triangle(HostScene &s, const float v0[3], const float v1[3], const float v2[3], const float *vn_or_null,
-                     int material);
+                     int material, const float *toward_or_null = nullptr);
 
 // ---------------------------------------------------------------------------------------------------
 // Device tables.

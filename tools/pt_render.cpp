@@ -52,6 +52,11 @@
 // coordinates with repeat wrap (default bilinear); -TEXTURE mtl takes every map_Kd line of the model's MTL instead, the files relative
 // to -MODEL_PATH.  -TEXTURE_GAMMA <g> decodes the bytes as pow(b / 255, g) (default 2.2; 1 = linear).  A malformed entry, an unreadable
 // file, an index outside the model and a material that is also in -GLASS end the program with status 2.  Every other flag combines.
+// Smooth shading (pt_scene_set_shading_normals, not in the reference): -SMOOTH auto generates a normal per triangle corner from the mesh
+// (pt_smooth_normals: welded vertices, angle-weighted, faces within -CREASE degrees of each other, default 60) and shades the glossy
+// and diffuse lobes and the dielectrics with the interpolated normal; -SMOOTH vn loads the model with PT_LOAD_GEOMETRIC_PLANES and takes
+// the file's own vn instead.  A malformed value, -CREASE without -SMOOTH auto or outside 0 .. 180 end the program with status 2.  Every
+// other flag combines.  Not built: normal maps and smoothing groups (`s` lines).
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -180,6 +185,9 @@ struct Options {
     std::string env, env_gain, env_rotate, env_size;   // -ENV / -ENV_GAIN / -ENV_ROTATE / -ENV_SIZE as given
     pt_environment_params env_params = {1.0f, 0.0f, 0};
     std::string glass_text;                // -GLASS as given
+    std::string smooth_text, crease_text;  // -SMOOTH / -CREASE as given
+    int smooth = 0;                        // what they make: 0 none, 1 auto, 2 vn
+    float crease = PT_SMOOTH_DEFAULT_CREASE;
     std::string texture_text, texture_gamma_text;   // -TEXTURE / -TEXTURE_GAMMA as given
     struct TextureSpec { int32_t material; std::string file; int32_t filter; };
     std::vector<TextureSpec> textures;     // what -TEXTURE makes (empty with -TEXTURE mtl: the model's MTL decides)
@@ -290,6 +298,8 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-ENV_ROTATE") o.env_rotate = v;
         if (f == "-ENV_SIZE") o.env_size = v;
         if (f == "-GLASS") o.glass_text = v;
+        if (f == "-SMOOTH") o.smooth_text = v;
+        if (f == "-CREASE") o.crease_text = v;
         if (f == "-TEXTURE") o.texture_text = v;
         if (f == "-TEXTURE_GAMMA") o.texture_gamma_text = v;
         if (f == "-ORTHO_HEIGHT") o.ortho_height = v;
@@ -491,6 +501,16 @@ int configure(int argc, char **argv, Options &o) {
             if (!(t >= 0.0f && t <= 1.0f)) return refuse(2, "-GLASS: a tint component must lie in 0 .. 1 (\"" + entry + "\")");
         d.material = static_cast<int32_t>(m);
         o.glass.push_back(d);
+    }
+    // -SMOOTH auto | vn, -CREASE degrees
+    if (!o.smooth_text.empty()) {
+        if (o.smooth_text == "auto") o.smooth = 1;
+        else if (o.smooth_text == "vn") o.smooth = 2;
+        else return refuse(2, "-SMOOTH takes auto or vn, not \"" + o.smooth_text + "\"");
+    }
+    if (!o.crease_text.empty()) {
+        if (o.smooth != 1) return refuse(2, "-CREASE needs -SMOOTH auto");
+        if (!(parse_float(o.crease_text, o.crease) && o.crease >= 0.0f && o.crease <= 180.0f)) return refuse(2, "-CREASE takes an angle in 0 .. 180 degrees");
     }
     // -TEXTURE: "mtl", or entries m:file[:nearest|bilinear] separated by commas (a file name may hold colons, not commas)
     if (o.texture_text == "mtl") o.texture_mtl = true;
@@ -1217,7 +1237,22 @@ int main(int argc, char **argv) {
     }
     // The model is parsed before the first HIP call (host-only scene): nothing up to here depends on the device, and nothing up
     // to here may start the HIP runtime.
-    if (pt_scene_load_obj(o.model_path.c_str(), o.model_name.c_str(), -1, &r.scene) != PT_OK) return die("pt_render");
+    if (pt_scene_load_obj_ex(o.model_path.c_str(), o.model_name.c_str(), -1, o.smooth == 2 ? PT_LOAD_GEOMETRIC_PLANES : 0u, &r.scene) != PT_OK) return die("pt_render");
+    if (o.smooth != 0) {   // -SMOOTH: the generator's normals, or the file's
+        int32_t n_tri = 0, n_mat = 0, has = 0;
+        if (pt_scene_counts(r.scene, &n_tri, &n_mat) != PT_OK) return die("pt_render");
+        std::vector<float> normals(9 * static_cast<size_t>(n_tri));
+        if (o.smooth == 1) {
+            std::vector<float> tri(14 * static_cast<size_t>(n_tri)), vertices(9 * static_cast<size_t>(n_tri));
+            std::vector<int32_t> tri_mat(static_cast<size_t>(n_tri));
+            if (pt_scene_get_triangles(r.scene, tri.data(), tri_mat.data()) != PT_OK) return die("pt_render");
+            for (size_t t = 0; t < static_cast<size_t>(n_tri); ++t) std::copy(&tri[14 * t + 4], &tri[14 * t + 13], &vertices[9 * t]);
+            if (pt_smooth_normals(n_tri, vertices.data(), o.crease, normals.data()) != PT_OK) return die("pt_render");
+        } else if (pt_scene_get_vertex_normals(r.scene, normals.data(), &has) != PT_OK) {
+            return die("pt_render");
+        }
+        if (n_tri > 0 && pt_scene_set_shading_normals(r.scene, normals.data()) != PT_OK) return refuse(2, std::string("-SMOOTH: ") + pt_last_error());
+    }
     if (!o.skybox.empty() && pt_scene_set_skybox_bmp(r.scene, o.skybox.c_str()) != PT_OK) return die("pt_render");   // scene.cpp:20-22
     if (!o.env.empty() && pt_scene_set_environment_file(r.scene, o.env.c_str(), &o.env_params) != PT_OK) return die("pt_render");
     // -GLASS: what only the model can decide -- an index outside it, listed twice, an emissive material -- is refused here, with the library's words
