@@ -1739,6 +1739,75 @@ int pt_scene_load_obj_ex(const char *model_dir, const char *model_name, int devi
 int pt_shading_normal_at(const float *vertices, const float *plane_normal, const float *normals, int32_t n, const float *points, float *out,
                          int32_t *interpolated);
 
+/* ---- rough specular: a GGX glossy lobe ------------------------------------------------------------------------------ */
+
+/* A scene handle may carry a ROUGHNESS LIST: entries (material, alpha).  Where a ray hits a listed material and the glossy lobe is
+ * chosen, the new direction is the reflection about a microfacet normal drawn from the GGX distribution of the normals visible from
+ * the incoming direction (Heitz 2018, "Sampling the GGX distribution of visible normals"), and the throughput factor is Ks x G1(l)
+ * with the separable Smith term of the new direction l.  A material that is not listed keeps the mirror reflect(d, N), bit for bit;
+ * without a list every output is what it was and the launches go to the kernels they went to.  The list belongs to the handle, as the
+ * dielectrics do: pt_scene_clone_to_device and pt_frame_create inherit it.  It works with every view, miss shader, dielectrics,
+ * textures and shading normals, with statistics, adaptive sampling and pass windows, in bands and frames, on small and box-tree
+ * scenes; launches are planned as without it.  Only the glossy lobe's direction and factor change: the lobe choice, the condition
+ * under which the segment's random words are drawn, the emissive and the diffuse lobe, dielectrics, texel steps, ray origins, the
+ * geometry and the cull tables are untouched, and so are the first-hit feature pass and the denoiser.  The diagnostic builds (phase
+ * timers, block profile) have no rough kernels: a render of a handle with a list is PT_ERR_UNSUPPORTED there.
+ *
+ * THE STEP, for a ray of unit direction d that hit a listed material of roughness alpha at p, with the words w1, w2 of the segment
+ * (the glossy lobe leaves them unused; no other word is used or moves) and n = the normal the glossy lobe would use: the stored N, or
+ * Ns under shading normals.  Every operation is a float operation rounded once, in the order written; nothing is fused; sqrt and /
+ * are correctly rounded; dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; normalize3 as above; unit_float(w) = float(((w >> 9) << 1)
+ * | 1) * 2^-24; sincos is the portable one of the diffuse lobe (double +, -, * only).
+ *   c = dot(n, d);   c > 0: n = -n  (exact: n is turned to the side the ray came from)
+ *   the tangent frame of Duff et al. 2017:  s = copysign(1, n.z);   a = -1 / (s + n.z);   b = (n.x * n.y) * a
+ *     t1 = (1 + ((s * n.x) * n.x) * a,  s * b,  -(s * n.x));     t2 = (b,  s + (n.y * n.y) * a,  -n.y)
+ *   v = -d in (t1, t2, n):  v.x = -dot(t1, d),  v.y = -dot(t2, d),  v.z = |c|
+ *   stretched:  e = normalize3(alpha * v.x, alpha * v.y, v.z)
+ *   q = e.x * e.x + e.y * e.y;   q >= 2^-40:  iq = 1 / sqrt(q),  T1 = (-(e.y * iq), e.x * iq, 0);   else T1 = (1, 0, 0)
+ *   T2 = (-(e.z * T1.y),  e.z * T1.x,  e.x * T1.y - e.y * T1.x)
+ *   u1 = unit_float(w1), u2 = unit_float(w2);   r = sqrt(u1);   (sn, cs) = sincos((2 * 3.141593f) * u2);   p1 = r * cs,  p2 = r * sn
+ *   the hemisphere warp:  w = 0.5 * (1 + e.z);   p2 = (1 - w) * sqrt(max(1 - p1 * p1, 0)) + w * p2
+ *   p3 = sqrt(max((1 - p1 * p1) - p2 * p2, 0))
+ *   m.x = (p1 * T1.x + p2 * T2.x) + p3 * e.x;   m.y = (p1 * T1.y + p2 * T2.y) + p3 * e.y;   m.z = p2 * T2.z + p3 * e.z
+ *   the stretch undone:  h = normalize3(alpha * m.x, alpha * m.y, max(m.z, 0))      (the microfacet normal in (t1, t2, n))
+ *   H = (h.x * t1 + h.y * t2) + h.z * n  per component;   dh = dot(H, d)
+ *   l = normalize3(d - H * dh * 2)  per component, as the mirror's:  d.x - (H.x * dh) * 2
+ *   nl = dot(n, l);   nl > 0:  a2 = alpha * alpha,  g = (2 * nl) / (nl + sqrt(a2 + (1 - a2) * (nl * nl))),  G1 = min(g, 1);   else G1 = 0
+ *   (max(x, 0) is x > 0 ? x : 0 and min(g, 1) is g < 1 ? g : 1.)
+ * The new direction is l, the throughput is multiplied by Ks * G1 per channel, and the next ray's origin is p + N * eps with the
+ * stored N, as the mirror's.  G1 = 0 gives a zero throughput, which ends the path by the rule that ends every path.  Under shading
+ * normals the existing rule holds as it is: the step with Ns and the step with N are both made from the same words, and the fallback
+ * test on the first one's direction selects.
+ *
+ * Not built: rough dielectrics, anisotropy, a Fresnel term on Ks, roughness textures.
+ *
+ * PT_ERR_INVALID_ARGUMENT: a NULL handle; a negative count; a material outside the model; a material listed twice; an alpha that is
+ * not finite or outside PT_ROUGH_ALPHA_MIN .. PT_ROUGH_ALPHA_MAX; a material without a glossy lobe (Ns == 0, Ks == 0, or emissive); a
+ * material the handle's dielectric list holds -- and pt_scene_set_dielectrics refuses a material of the roughness list in turn.  A
+ * setter validates, builds and uploads first and swaps last: a refused call leaves every handle as it was.  A host-only scene
+ * (device < 0) accepts and returns a list. */
+#define PT_ROUGH_ALPHA_MIN 0.0009765625f /* 2^-10 */
+#define PT_ROUGH_ALPHA_MAX 1.0f
+typedef struct pt_rough {
+    int32_t material;
+    float alpha;
+} pt_rough;
+/* n == 0 (or list == NULL) clears. */
+int pt_scene_set_roughness(pt_scene *scene, const pt_rough *list, int32_t n);
+/* *n = the number of entries; list (may be NULL) gets them in the order given. */
+int pt_scene_get_roughness(const pt_scene *scene, pt_rough *list, int32_t *n);
+/* The same on a frame: every device's copy of the frame's scene; a refused call changes none.  The getter answers for the root's. */
+int pt_frame_set_roughness(pt_frame *frame, const pt_rough *list, int32_t n);
+int pt_frame_get_roughness(pt_frame *frame, pt_rough *list, int32_t *n);
+/* What pt_scene_load_obj kept of the MTL: pr[m] = the value of material m's `Pr` line as the file gives it (not clamped), or -1 where
+ * it has none (or one that is not a finite number, or the scene was made from arrays).  pr: n_mat floats.  The library applies
+ * nothing by itself. */
+int pt_scene_get_mtl_roughness(const pt_scene *scene, float *pr);
+/* THE STEP alone, on the host, for n rays: normals, directions (3 n floats, unit length), alpha, w1, w2 (n each) give
+ * out_directions (3 n: l), out_g1 (n) and, where out_microfacet is not NULL, h (3 n).  An alpha outside the range is refused. */
+int pt_rough_step(int32_t n, const float *normals, const float *directions, const float *alpha, const uint32_t *w1, const uint32_t *w2,
+                  float *out_directions, float *out_g1, float *out_microfacet);
+
 /* ---- misc ------------------------------------------------------------------------------------------- */
 int pt_abi_version(void);
 int pt_device_count(void);

@@ -68,7 +68,9 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_scene_get_map_kd", "pt_texture_load_bmp", "pt_texture_lookup", "pt_scene_get_texture_records",
                "pt_scene_set_shading_normals", "pt_scene_get_shading_normals", "pt_scene_get_vertex_normals",
                "pt_frame_set_shading_normals", "pt_frame_get_shading_normals", "pt_smooth_normals", "pt_scene_load_obj_ex",
-               "pt_shading_normal_at"]
+               "pt_shading_normal_at",
+               "pt_scene_set_roughness", "pt_scene_get_roughness", "pt_frame_set_roughness", "pt_frame_get_roughness",
+               "pt_scene_get_mtl_roughness", "pt_rough_step"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -493,6 +495,40 @@ def dielectric(material, ior, tint=(1.0, 1.0, 1.0)):
     return Dielectric(int(material), float(ior), (C.c_float * 3)(*tint))
 
 
+ROUGH_ALPHA_MIN, ROUGH_ALPHA_MAX = 2.0 ** -10, 1.0
+
+
+class Rough(C.Structure):
+    """pt_rough: a material's index and the roughness alpha of its glossy lobe."""
+    _fields_ = [("material", C.c_int32), ("alpha", C.c_float)]
+
+    def __repr__(self):
+        return f"rough({self.material}, {self.alpha!r})"
+
+
+def rough(material, alpha):
+    """One entry of a handle's roughness list (-ROUGH m:alpha): the glossy lobe of material `material` is a GGX lobe of roughness
+    `alpha` in 2^-10 .. 1 instead of a mirror."""
+    return Rough(int(material), float(alpha))
+
+
+def rough_step(normals, directions, alpha, w1, w2, library=None, want_microfacet=False):
+    """pt_rough_step, the host's own evaluation of the rough glossy step: for unit normals [n, 3], unit incoming directions [n, 3],
+    alpha [n] (or one value) and the random words w1, w2 [n] the new directions [n, 3] and G1 [n]; with want_microfacet also the
+    microfacet normal [n, 3] in the frame (t1, t2, n)."""
+    L = library or lib()
+    n_ = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, np.float32), (len(n_),)))
+    u1, u2 = np.ascontiguousarray(w1, np.uint32).reshape(-1), np.ascontiguousarray(w2, np.uint32).reshape(-1)
+    if not (len(d) == len(n_) == len(u1) == len(u2)):
+        raise ValueError("rough_step: arrays of one length")
+    out, g1, h = np.zeros((len(n_), 3), np.float32), np.zeros(len(n_), np.float32), np.zeros((len(n_), 3), np.float32)
+    up = C.POINTER(C.c_uint32)
+    _check(L.pt_rough_step(len(n_), _fp(n_), _fp(d), _fp(a), u1.ctypes.data_as(up), u2.ctypes.data_as(up), _fp(out), _fp(g1), _fp(h)), L)
+    return (out, g1, h) if want_microfacet else (out, g1)
+
+
 TEXTURE_NEAREST, TEXTURE_BILINEAR = 0, 1
 TEXTURE_MAX_SIDE = 8192
 _TEXTURE_FILTERS = {"nearest": TEXTURE_NEAREST, "bilinear": TEXTURE_BILINEAR}
@@ -727,6 +763,12 @@ def load_library(path):
     L.pt_smooth_normals.argtypes = [C.c_int32, fp, C.c_float, fp]
     L.pt_scene_load_obj_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(vp)]
     L.pt_shading_normal_at.argtypes = [fp, fp, fp, C.c_int32, fp, fp, ip]
+    rp = C.POINTER(Rough)
+    for who in ("scene", "frame"):
+        getattr(L, f"pt_{who}_set_roughness").argtypes = [vp, rp, C.c_int32]
+        getattr(L, f"pt_{who}_get_roughness").argtypes = [vp, rp, ip]
+    L.pt_scene_get_mtl_roughness.argtypes = [vp, fp]
+    L.pt_rough_step.argtypes = [C.c_int32, fp, fp, fp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), fp, fp, fp]
     L.pt_scene_get_map_kd.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p)]
     L.pt_texture_load_bmp.argtypes = [C.c_char_p, C.c_float, ip, ip, fp]
     L.pt_texture_lookup.argtypes = [C.c_int32, C.c_int32, fp, C.c_int32, C.c_int32, fp, fp, ip]
@@ -893,6 +935,35 @@ class _DielectricMethods:
         return [dielectric(e.material, e.ior, tuple(e.tint)) for e in arr[:n.value]]
 
 
+class _RoughMethods:
+    """set_roughness / roughness / mtl_roughness of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
+    _rough_prefix = "pt_scene_"
+
+    def set_roughness(self, entries):
+        """-ROUGH: gives materials a rough glossy lobe.  `entries` is a list of pt.rough(material, alpha); None or an empty list clears
+        it.  Refused: an index outside the scene or listed twice, an alpha outside 2^-10 .. 1, a material without a glossy lobe, a
+        dielectric."""
+        entries = list(entries or [])
+        arr = (Rough * len(entries))(*entries) if entries else None
+        _check(getattr(self._L, self._rough_prefix + "set_roughness")(self._h, arr, len(entries)), self._L)
+
+    def roughness(self):
+        """The handle's roughness list, a list of Rough in the order given ([] without any)."""
+        get = getattr(self._L, self._rough_prefix + "get_roughness")
+        n = C.c_int32()
+        _check(get(self._h, None, C.byref(n)), self._L)
+        arr = (Rough * max(n.value, 1))()
+        _check(get(self._h, arr, C.byref(n)), self._L)
+        return [rough(e.material, e.alpha) for e in arr[:n.value]]
+
+    def mtl_roughness(self):
+        """pt_scene_get_mtl_roughness: each material's Pr value from the MTL as the file gives it, -1 without one."""
+        scene = getattr(self, "_scene", self)
+        pr = np.zeros(max(scene.counts()[1], 1), np.float32)
+        _check(scene._L.pt_scene_get_mtl_roughness(scene._h, _fp(pr)), scene._L)
+        return pr[:scene.counts()[1]]
+
+
 class _TextureMethods:
     """set_texcoords / texcoords / set_textures / textures of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
     _tex_prefix = "pt_scene_"
@@ -972,7 +1043,7 @@ class _SmoothMethods:
         return scene._normals(scene._L.pt_scene_get_vertex_normals)
 
 
-class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods):
+class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods):
     """Owns a pt_scene handle (Scene + LoadModel of the reference, scene.h:17-19)."""
 
     def __init__(self, handle, library=None):
@@ -1719,9 +1790,9 @@ def bvh_depth(nodes):
     return int(level.max())
 
 
-class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods):
+class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods):
     """pt_frame: one image on several devices from one host program -- row bands, one gather to the first device."""
-    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = "pt_frame_"
+    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = _rough_prefix = "pt_frame_"
 
     def _n_tri(self):
         return self._scene.counts()[0]

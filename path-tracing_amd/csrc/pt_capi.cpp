@@ -119,6 +119,7 @@ int upload(pt_scene *s, int device) {
     if (s->glass && (rc = s->d_glass.upload(s->glass->table, "dielectric table", 64)) != PT_OK) return rc;
     if (s->textures && (rc = ptc::upload_textures(*s->textures, *s->texcoords, s->shared->tables, s->d_tex)) != PT_OK) return rc;
     if (s->smooth && (rc = ptc::upload_smooth(*s->smooth, s->shared->tables, s->d_smooth)) != PT_OK) return rc;
+    if (s->rough && (rc = ptc::upload_rough(s->rough->table, s->shared->tables, s->d_rough)) != PT_OK) return rc;
     return PT_OK;
 }
 
@@ -300,6 +301,17 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
         }
         if (!a.glass) a.glass = scene->d_smooth.no_glass.get<void>();
     }
+    if (scene->rough && scene->d_rough.alpha) {   // the rough kernels of those (integrate_kernel_rough); absent normals and lists as all-zero tables
+        a.rough_alpha = scene->d_rough.alpha.get<float>();
+        if (!a.smooth_normals) a.smooth_normals = scene->d_rough.no_normals.get<void>();   // (all zeros: every Ns is N)
+        if (!a.tex_recs) {
+            a.tex_recs = scene->d_rough.no_tex.get<void>();
+            a.tex_uv = scene->d_rough.no_tex.get<float>();
+            a.tex_texels = scene->d_rough.no_tex.get<void>();
+            a.tex_bary = scene->d_rough.bary.get<void>();
+        }
+        if (!a.glass) a.glass = scene->d_rough.no_glass.get<void>();
+    }
     a.n_clusters = static_cast<int32_t>(t.clusters.size());
     a.n_tri = scene->shared->host.n_tri();
     a.big = t.big ? 1 : 0;
@@ -422,6 +434,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
         PT_HIP_TRY(hipEventRecord(ctx.ev0.get(), stream));
     }
     const hipError_t launched = pt::launch_integrator(a, tiles.variant, stream);
+    if (launched == hipErrorNotSupported && a.rough_alpha != nullptr) return fail(PT_ERR_UNSUPPORTED, "roughness: this diagnostic build of the library has no rough kernels");
     if (launched == hipErrorNotSupported && a.smooth_normals != nullptr) return fail(PT_ERR_UNSUPPORTED, "shading normals: this diagnostic build of the library has no smooth kernels");
     if (launched == hipErrorNotSupported && a.tex_recs != nullptr) return fail(PT_ERR_UNSUPPORTED, "textures: this diagnostic build of the library has no texture kernels");
     if (launched == hipErrorNotSupported && a.glass != nullptr) return fail(PT_ERR_UNSUPPORTED, "dielectrics: this diagnostic build of the library has no dielectric kernels");
@@ -654,6 +667,7 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->texcoords = src->texcoords;   // and its texture coordinates and textures
     s->textures = src->textures;
     s->smooth = src->smooth;   // and its shading normals
+    s->rough = src->rough;     // and its roughness list
     s->has_camera = src->has_camera;   // and its camera
     s->camera = src->camera;
     s->has_lens = src->has_lens;       // and lens

@@ -29,6 +29,7 @@
 #include "pt_local.hpp"
 #include "pt_meter.hpp"
 #include "pt_optics.hpp"
+#include "pt_rough.hpp"
 #include "pt_scene.hpp"
 #include "pt_sharpen.hpp"
 #include "pt_smooth.hpp"
@@ -93,6 +94,18 @@ struct DeviceSmooth {
     ptc::DeviceBuffer normals, bary, no_tex, no_glass;
 };
 
+// The roughness list of a handle (pt_hip.h: rough specular): the list as given and the per-material table the kernels read (one alpha
+// per material of the scene, 0 = the mirror).  Belongs to the handle as the dielectrics do; immutable once set.
+struct pt_rough_list {
+    std::vector<pt_rough> list;
+    std::vector<float> table;
+};
+// Its device copy, and what a handle without shading normals, textures or dielectrics passes to the rough kernels: all-zero corner
+// normals ("use N"), the barycentrics' record of every triangle and all-zero texture and dielectric tables.
+struct DeviceRough {
+    ptc::DeviceBuffer alpha, no_normals, bary, no_tex, no_glass;
+};
+
 // Device copy of one CullTables (they depend on eps and on the envelope the camera needs; a scene keeps the one of its last
 // render).
 struct DeviceCull {
@@ -134,6 +147,8 @@ struct pt_scene {
     DeviceTextures d_tex;          // both on this copy's device, uploaded when a list is set
     std::shared_ptr<const std::vector<float>> smooth;   // this handle's shading normals, 9 per triangle (nullptr = none); copies inherit them
     DeviceSmooth d_smooth;         // on this copy's device
+    std::shared_ptr<const pt_rough_list> rough;   // this handle's roughness list (nullptr = none); copies inherit it
+    DeviceRough d_rough;           // on this copy's device
     bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
     pt_camera camera{};
     bool has_lens = false;         // this handle's lens (pt_scene_set_lens; radius > 0); copies made from it inherit it
@@ -449,6 +464,22 @@ inline int upload_smooth(const std::vector<float> &n9, const pt::DeviceTables &t
     const std::vector<pt::GlassRec> no_glass(tables.mats.size(), pt::GlassRec{});
     const std::vector<pt::TexRec> no_tex(tables.mats.size(), pt::TexRec{0, 0, 0, 0});
     if ((rc = d.normals.upload(corners, "shading normals", 64)) != PT_OK || (rc = d.bary.upload(texture_bary_records(tables.exact), "barycentric records", 64)) != PT_OK ||
+        (rc = d.no_tex.upload(no_tex, "empty texture table", 64)) != PT_OK || (rc = d.no_glass.upload(no_glass, "empty dielectric table", 64)) != PT_OK)
+        return rc;
+    out = std::move(d);
+    return PT_OK;
+}
+
+// A handle's roughness table onto the current device (the setters of pt_rough_capi.cpp; a clone's upload in pt_capi.cpp).  `out` is
+// only written once every upload has succeeded.
+inline int upload_rough(const std::vector<float> &alpha, const pt::DeviceTables &tables, DeviceRough &out) {
+    DeviceRough d;
+    int rc;
+    const std::vector<pt::SmoothCorner> no_normals(3 * tables.exact.size(), pt::SmoothCorner{0.0f, 0.0f, 0.0f, 0.0f});
+    const std::vector<pt::GlassRec> no_glass(tables.mats.size(), pt::GlassRec{});
+    const std::vector<pt::TexRec> no_tex(tables.mats.size(), pt::TexRec{0, 0, 0, 0});
+    if ((rc = d.alpha.upload(alpha, "roughness table", 64)) != PT_OK || (rc = d.no_normals.upload(no_normals, "empty shading normals", 64)) != PT_OK ||
+        (rc = d.bary.upload(texture_bary_records(tables.exact), "barycentric records", 64)) != PT_OK ||
         (rc = d.no_tex.upload(no_tex, "empty texture table", 64)) != PT_OK || (rc = d.no_glass.upload(no_glass, "empty dielectric table", 64)) != PT_OK)
         return rc;
     out = std::move(d);

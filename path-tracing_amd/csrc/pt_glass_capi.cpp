@@ -33,6 +33,7 @@ int make_list(const pt_scene *scene, const pt_dielectric *list, int32_t n, std::
         const pt::MatRec &m = mats[d.material];
         if ((m.n_lobes >= 1 && m.kind0 == 0) || (m.n_lobes >= 2 && m.kind1 == 0)) return refuse(who + "material " + std::to_string(d.material) + " has an emissive lobe");
         if (scene->textures && scene->textures->recs[d.material].w != 0) return refuse(who + "material " + std::to_string(d.material) + " is textured");
+        if (scene->rough && scene->rough->table[d.material] != 0.0f) return refuse(who + "material " + std::to_string(d.material) + " is in the roughness list");
         pt::GlassRec &r = g->table[d.material];
         if (r.ior != 0.0f) return refuse(who + "material " + std::to_string(d.material) + " is listed twice");
         r.ior = d.ior;

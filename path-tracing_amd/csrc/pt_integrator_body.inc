@@ -8,6 +8,8 @@
 // marks (pt_hip.h: pt_texture) multiplies the throughput by the texel before the emissive or the diffuse lobe runs.
 // SMOOTH (only pt::integrate_kernel_smooth: false in every other kernel; with GLASS and TEX) = the glossy lobe, the diffuse lobe and
 // the dielectric step run with the interpolated shading normal of the hit point (pt_hip.h: shading normals; pt_smooth.hpp spells it).
+// ROUGH (only pt::integrate_kernel_rough: false in every other kernel; with SMOOTH) = the glossy lobe of a material the handle's
+// roughness table marks reflects about a GGX microfacet normal and takes Ks x G1 (pt_hip.h: rough specular; pt_rough.hpp spells it).
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
@@ -832,6 +834,11 @@
                                 hx = sq * cs; hy = sq * sn; hz = sqrt_rn_normal(1 - xi1);
                                 normalize3(hx, hy, hz);
                             }
+                            // ROUGH: the material's alpha, 0 = the mirror (RenderArgs::rough_alpha), read where the glossy lobe was chosen
+                            [[maybe_unused]] float r_alpha = 0.0f;
+                            if constexpr (ROUGH) {
+                                if (kind == 1) r_alpha = rough_view()[mi];
+                            }
                             auto step = [&](const float nx, const float ny, const float nz, float &ux, float &uy, float &uz, float &ur, float &ug,
                                             float &ub, float &uo) {
                                 uo = eps;
@@ -863,6 +870,16 @@
                                     if (!entering) nk = -nk;
                                     ux = q[k].dx * dm + nx * nk; uy = q[k].dy * dm + ny * nk; uz = q[k].dz * dm + nz * nk;
                                 } else if (kind == 1) {
+                                    if constexpr (ROUGH) {   // the GGX lobe of a listed material (pt_hip.h: rough specular; pt_rough.hpp spells it)
+                                        if (r_alpha != 0.0f) {
+                                            float g1, mhx, mhy, mhz;
+                                            rough_step(nx, ny, nz, q[k].dx, q[k].dy, q[k].dz, r_alpha, unit_float(w1), unit_float(w2),
+                                                       [](float ang, float &sn, float &cs) { portable_sincos(ang, sn, cs); },
+                                                       [](float &vx, float &vy, float &vz) { normalize3(vx, vy, vz); }, ux, uy, uz, g1, mhx, mhy, mhz);
+                                            ur = m1v.x * g1; ug = m1v.y * g1; ub = m1v.z * g1;
+                                            return;   // (the direction is normalised already)
+                                        }
+                                    }
                                     const float dn = (nx * q[k].dx + ny * q[k].dy) + nz * q[k].dz;
                                     ux = q[k].dx - nx * dn * 2.0f; uy = q[k].dy - ny * dn * 2.0f; uz = q[k].dz - nz * dn * 2.0f;
                                     ur = m1v.x; ug = m1v.y; ub = m1v.z;

@@ -112,6 +112,11 @@ struct RenderArgs {
     // without dielectrics or textures passes all-zero tables).  Three 16-byte records per triangle (pt_smooth.hpp: SmoothCorner) in
     // the ORIGINAL triangle order, read only where a ray that scatters has hit a triangle.
     const void *smooth_normals;
+    // The handle's roughness list (pt_hip.h: rough specular), appended likewise.  rough_alpha != nullptr: the launch runs the rough kernels
+    // (integrate_kernel_rough, pt_rough_kernels.hip: the smooth kernels with the GGX glossy lobe), planned as the kernels the same launch
+    // would run without it; smooth_normals, glass and the tex_ pointers are then never null (a handle without them passes all-zero
+    // tables).  One float per material: alpha, 0 = the mirror.  Read only where the glossy lobe of a ray that scatters has been chosen.
+    const float *rough_alpha;
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif
@@ -123,7 +128,8 @@ const plan::Build &integrator_build();
 // the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan;
 // with args.env_map != nullptr the environment kernel of skybox kernel `v` (v.sky), likewise; with args.glass != nullptr the dielectric
 // kernel of whichever of those the launch would run (hipErrorNotSupported from a diagnostic build, which has none); with
-// args.tex_recs != nullptr the texture kernel of that one, likewise; with args.smooth_normals != nullptr the smooth kernel of that one
+// args.tex_recs != nullptr the texture kernel of that one, likewise; with args.smooth_normals != nullptr the smooth kernel of that one;
+// with args.rough_alpha != nullptr the rough kernel of that one
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the environment kernels' translation unit (pt_environment_kernels.hip); launch_integrator calls it, nothing else does
 hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
@@ -133,6 +139,8 @@ hipError_t launch_glass_integrator(const RenderArgs &args, const plan::Variant &
 hipError_t launch_texture_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the smooth kernels' translation unit (pt_smooth_kernels.hip), likewise
 hipError_t launch_smooth_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+// the rough kernels' translation unit (pt_rough_kernels.hip), likewise
+hipError_t launch_rough_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached).  A projection launch asks for its
 // camera twin's: the projection kernels are compiled for their twins' waves per SIMD and LDS (tests/test_projection_resources.py)
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);

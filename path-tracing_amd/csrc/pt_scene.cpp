@@ -51,12 +51,14 @@ ObjIndex parse_face_group(const std::string &g) {
 // The MTL reader of scene.cpp:45-71: every run of the outer loop appends one material, fields are picked out of
 // a flat token stream, and the stream's eof flag (not its fail flag) ends both loops.
 // map_Kd: the token after it is recorded as the material's texture file name (HostScene::map_kd) and otherwise treated as the
-// reference treats it -- it goes through the dispatch as any token does, since the reference does not know the line.
-void read_mtl(std::istream &in, std::vector<float> &mat, std::vector<std::string> &map_kd) {
+// reference treats it -- it goes through the dispatch as any token does, since the reference does not know the line.  Pr likewise:
+// the token after it, where it is a finite number, is recorded as the material's roughness (HostScene::mat_pr).
+void read_mtl(std::istream &in, std::vector<float> &mat, std::vector<std::string> &map_kd, std::vector<float> &mat_pr) {
     std::string tok = "1";
     while (!in.eof()) {
         float rec[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         std::string kd_name;
+        float pr = -1.0f;
         while (!in.eof() && tok != "newmtl") in >> tok;
         in >> tok;   // the material's name; it then goes through the same dispatch as any other token
         while (!in.eof() && tok != "newmtl") {
@@ -64,13 +66,19 @@ void read_mtl(std::istream &in, std::vector<float> &mat, std::vector<std::string
             else if (tok == "Ke") in >> rec[3] >> rec[4] >> rec[5];
             else if (tok == "Ks") in >> rec[6] >> rec[7] >> rec[8];
             else if (tok == "Ns") in >> rec[9];
-            const bool was_map_kd = tok == "map_Kd";
+            const bool was_map_kd = tok == "map_Kd", was_pr = tok == "Pr";
             in >> tok;
             if (was_map_kd && !in.fail()) kd_name = tok;
+            if (was_pr && !in.fail()) {
+                char *end = nullptr;
+                const float v = std::strtof(tok.c_str(), &end);
+                if (end != tok.c_str() && *end == '\0' && std::isfinite(v)) pr = v;
+            }
             if (in.fail() && !in.eof()) return;   // the reference would spin forever on a non-numeric field
         }
         mat.insert(mat.end(), rec, rec + 10);
         map_kd.push_back(kd_name);
+        mat_pr.push_back(pr);
     }
 }
 
@@ -122,7 +130,7 @@ bool load_obj(const std::string &dir, const std::string &name, HostScene &out, s
                 io_error = true;
                 return false;
             }
-            read_mtl(mtl, out.mat, out.map_kd);
+            read_mtl(mtl, out.mat, out.map_kd, out.mat_pr);
         } else if (tok == "v") {
             float p[3] = {0, 0, 0};
             obj >> p[0] >> p[1] >> p[2];

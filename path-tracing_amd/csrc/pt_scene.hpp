@@ -21,6 +21,9 @@ struct HostScene {
     // Likewise the vn of every face corner (pt_hip.h: shading normals), n_tri * 9, as the file gives them; the face's stored normal
     // where a corner gives no vn index; empty for a scene made from arrays.  Nothing reads them unless a caller asks for them.
     std::vector<float> tri_vn;
+    // Likewise each material's Pr line of the MTL (pt_hip.h: rough specular), n_mat entries, -1 where the MTL has none or its value is
+    // not a finite number; empty for a scene made from arrays.  Nothing reads them unless a caller asks for them.
+    std::vector<float> mat_pr;
     int n_tri() const { return static_cast<int>(tri_mat.size()); }
     int n_mat() const { return static_cast<int>(mat.size() / 10); }
 };

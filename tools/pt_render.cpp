@@ -57,6 +57,11 @@
 // and diffuse lobes and the dielectrics with the interpolated normal; -SMOOTH vn loads the model with PT_LOAD_GEOMETRIC_PLANES and takes
 // the file's own vn instead.  A malformed value, -CREASE without -SMOOTH auto or outside 0 .. 180 end the program with status 2.  Every
 // other flag combines.  Not built: normal maps and smoothing groups (`s` lines).
+// Rough specular reflection (pt_scene_set_roughness, not in the reference): -ROUGH m:alpha[,m:alpha...] gives the glossy lobe of each
+// material m a GGX lobe of roughness alpha in 2^-10 .. 1 instead of the mirror; -ROUGH mtl takes every material of the model's MTL that
+// has a Pr line and a glossy lobe (Ns and Ks not zero, not emissive), with Pr clamped into that range.  A malformed entry, an alpha
+// outside the range, an index outside the model, a material listed twice, one without a glossy lobe and one that is also in -GLASS end
+// the program with status 2.  Every other flag combines.  Not built: rough dielectrics, anisotropy, a Fresnel term, roughness textures.
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -185,6 +190,9 @@ struct Options {
     std::string env, env_gain, env_rotate, env_size;   // -ENV / -ENV_GAIN / -ENV_ROTATE / -ENV_SIZE as given
     pt_environment_params env_params = {1.0f, 0.0f, 0};
     std::string glass_text;                // -GLASS as given
+    std::string rough_text;                // -ROUGH as given
+    std::vector<pt_rough> rough;           // what it makes (empty with -ROUGH mtl: the model's MTL decides)
+    bool rough_mtl = false;
     std::string smooth_text, crease_text;  // -SMOOTH / -CREASE as given
     int smooth = 0;                        // what they make: 0 none, 1 auto, 2 vn
     float crease = PT_SMOOTH_DEFAULT_CREASE;
@@ -298,6 +306,7 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-ENV_ROTATE") o.env_rotate = v;
         if (f == "-ENV_SIZE") o.env_size = v;
         if (f == "-GLASS") o.glass_text = v;
+        if (f == "-ROUGH") o.rough_text = v;
         if (f == "-SMOOTH") o.smooth_text = v;
         if (f == "-CREASE") o.crease_text = v;
         if (f == "-TEXTURE") o.texture_text = v;
@@ -501,6 +510,24 @@ int configure(int argc, char **argv, Options &o) {
             if (!(t >= 0.0f && t <= 1.0f)) return refuse(2, "-GLASS: a tint component must lie in 0 .. 1 (\"" + entry + "\")");
         d.material = static_cast<int32_t>(m);
         o.glass.push_back(d);
+    }
+    // -ROUGH: "mtl", or entries m:alpha separated by commas; alpha's range is the library's (pt_hip.h: rough specular)
+    if (o.rough_text == "mtl") o.rough_mtl = true;
+    for (size_t at = 0; !o.rough_text.empty() && !o.rough_mtl && at <= o.rough_text.size();) {
+        const size_t comma = std::min(o.rough_text.find(',', at), o.rough_text.size());
+        const std::string entry = o.rough_text.substr(at, comma - at);
+        at = comma + 1;
+        const size_t colon = entry.find(':');
+        float m = 0.0f;
+        pt_rough d = {0, 0.0f};
+        const std::string index = entry.substr(0, colon);
+        const bool ok = colon != std::string::npos && entry.find(':', colon + 1) == std::string::npos && !index.empty() &&
+                        index.find_first_not_of("0123456789") == std::string::npos && parse_float(index, m) && m <= 16777216.0f &&
+                        m == static_cast<float>(static_cast<int32_t>(m)) && parse_float(entry.substr(colon + 1), d.alpha);
+        if (!ok) return refuse(2, "-ROUGH takes mtl or m:alpha entries separated by commas, not \"" + entry + "\"");
+        if (!(d.alpha >= PT_ROUGH_ALPHA_MIN && d.alpha <= PT_ROUGH_ALPHA_MAX)) return refuse(2, "-ROUGH: alpha must lie in 2^-10 .. 1, not " + entry.substr(colon + 1));
+        d.material = static_cast<int32_t>(m);
+        o.rough.push_back(d);
     }
     // -SMOOTH auto | vn, -CREASE degrees
     if (!o.smooth_text.empty()) {
@@ -1257,6 +1284,21 @@ int main(int argc, char **argv) {
     if (!o.env.empty() && pt_scene_set_environment_file(r.scene, o.env.c_str(), &o.env_params) != PT_OK) return die("pt_render");
     // -GLASS: what only the model can decide -- an index outside it, listed twice, an emissive material -- is refused here, with the library's words
     if (!o.glass.empty() && pt_scene_set_dielectrics(r.scene, o.glass.data(), static_cast<int32_t>(o.glass.size())) != PT_OK) return refuse(2, pt_last_error());
+    // -ROUGH: after -GLASS, so that a material in both is refused with the library's words; mtl: the Pr lines of the materials with a glossy lobe
+    if (o.rough_mtl) {
+        int32_t n_tri = 0, n_mat = 0;
+        if (pt_scene_counts(r.scene, &n_tri, &n_mat) != PT_OK) return die("pt_render");
+        std::vector<float> pr(static_cast<size_t>(n_mat) + 1), mats(10 * static_cast<size_t>(n_mat) + 1);
+        if (pt_scene_get_mtl_roughness(r.scene, pr.data()) != PT_OK || pt_scene_get_materials(r.scene, mats.data()) != PT_OK) return die("pt_render");
+        for (int32_t m = 0; m < n_mat; ++m) {
+            const float *p = &mats[10 * static_cast<size_t>(m)];   // Kd, Ke, Ks, Ns
+            const bool emits = p[3] != 0.0f || p[4] != 0.0f || p[5] != 0.0f, ks = p[6] != 0.0f || p[7] != 0.0f || p[8] != 0.0f;
+            if (pr[m] < 0.0f || emits || !ks || p[9] == 0.0f) continue;
+            o.rough.push_back({m, std::min(std::max(pr[m], PT_ROUGH_ALPHA_MIN), PT_ROUGH_ALPHA_MAX)});
+        }
+        if (o.rough.empty()) std::fprintf(stderr, "pt_render: -ROUGH mtl: no material of the model's MTL has a Pr line and a glossy lobe, nothing is rough\n");
+    }
+    if (!o.rough.empty() && pt_scene_set_roughness(r.scene, o.rough.data(), static_cast<int32_t>(o.rough.size())) != PT_OK) return refuse(2, std::string("-ROUGH: ") + pt_last_error());
     // -TEXTURE: the files are read and the list set here, after -GLASS, so that a material in both is refused with the library's words
     if (o.texture_mtl) {
         int32_t n_tri = 0, n_mat = 0;
