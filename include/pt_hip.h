@@ -1808,6 +1808,94 @@ int pt_scene_get_mtl_roughness(const pt_scene *scene, float *pr);
 int pt_rough_step(int32_t n, const float *normals, const float *directions, const float *alpha, const uint32_t *w1, const uint32_t *w2,
                   float *out_directions, float *out_g1, float *out_microfacet);
 
+/* ---- direct lighting: a shadow ray to the emitters at every diffuse hit ----------------------------------------------- */
+
+/* A scene handle may have DIRECT LIGHTING switched on (next-event estimation).  Without it a path finds light only when its scattered
+ * ray happens to strike an emissive triangle; with it every scattering diffuse hit also sends one shadow ray to a sampled point of a
+ * light, and the emitters that ray has sampled are not counted a second time when the diffuse lobe's own ray reaches one.  The
+ * switch belongs to the handle, as the roughness list does: pt_scene_clone_to_device and pt_frame_create inherit it and the table.  It
+ * works with every view, miss shader, dielectrics, textures, shading normals and roughness, with statistics, adaptive sampling and
+ * pass windows, in bands and frames, on small and box-tree scenes; launches are planned as without it.  Without the switch every
+ * output is what it was and the launches go to the kernels they went to.  The first-hit feature pass, the denoiser, the temporal
+ * merge, the upsampler and the display chain read sum / count as before.  The diagnostic builds (phase timers, block profile) have
+ * no direct kernels: a render of a handle with the switch on is PT_ERR_UNSUPPORTED there.
+ *
+ * PER-PATH ACCOUNTING.  Under direct lighting a path collects its radiance in L = (Lr, Lg, Lb), which starts at +0; every term is
+ * added channel by channel in the order the terms occur.  Every traced path updates the accumulators exactly once, when it ends --
+ * a miss, an emitter, a material without lobes, the depth cap or a throughput of zero --: sum += L, sum2 += L * L, count += 1.  count
+ * is then the number of paths traced and sum / count the unbiased pixel estimate (without the switch, count is the number of
+ * contributing paths and sum / count a conditional mean).  A pixel's paths still end in pass order.
+ *
+ * THE LIGHT TABLE.  A light is a triangle of non-zero area whose material is the single emissive lobe (Ke != 0); lights are kept in the
+ * original triangle order.  Per light: v0;  e1 = v1 - v0 and e2 = v2 - v0 as float differences;  Nl, the stored plane normal;  Le, the
+ * material's Kd (what the emissive lobe multiplies the throughput by);  the triangle's original index;  cdf.  area_i = 0.5 * sqrt((cx *
+ * cx + cy * cy) + cz * cz) in double with c = e1 x e2 formed in double from the float edges (c.x = e1.y * e2.z - e1.z * e2.y, and so
+ * on); a triangle whose area is not > 0 is no light.  The areas are summed in double in table order, total first; then cum_i likewise,
+ * cdf_i = float(cum_i / total), the last entry forced to 1.0f, and A = float(total).
+ *
+ * THE DIRECT TERM, at a hit where the diffuse lobe is chosen by a ray that scatters (depth + 1 < mrr), after the texel step and
+ * before the throughput takes the lobe's factor.  Every operation is a float operation rounded once, in the order written; nothing is
+ * fused; sqrt and / are correctly rounded; dot, normalize3 and unit_float as above.
+ *   (l0, l1, l2, l3) = philox(pixel, pass, depth, 3): the fourth counter word is 3.  Every other call of the integrator -- the segment's
+ *     words, the jitter and the lens (depth 0xFFFFFFFF), the shutter time (0xFFFFFFFE) -- has 0 there, and the display's dither and
+ *     grain, which run under the same key, have 1 and 2 (pt_grain), so 1 is not free and these words are used by nothing else; the segment's own w0 .. w3 stay as
+ *     they are and no other random number moves.
+ *   i = the first light with unit_float(l0) < cdf_i
+ *   u1 = unit_float(l1), u2 = unit_float(l2);   u1 + u2 > 1:  u1 = 1 - u1, u2 = 1 - u2  (exact for multiples of 2^-24)
+ *   P = (v0 + e1 * u1) + e2 * u2  per component
+ *   O = p + N * eps, the origin the next ray gets;   w = P - O;   r2 = (w.x * w.x + w.y * w.y) + w.z * w.z;   omega = normalize3(w)
+ *   cn = dot(N, omega);   cs = dot(n, omega) with n = Ns of the hit point under shading normals (flipped onto N's side; N where the
+ *     triangle has no usable Ns), else N;   cl = -dot(Nl, omega)
+ *   no term and no shadow ray unless r2 > 0, cn > 0, cs > 0 and cl > 0
+ *   g = (((cs * |omega.z|) * cl) * A) / (3.141593f * r2)
+ *     (two factors on purpose: the diffuse lobe draws its direction cosine-weighted about the scene's z axis -- not about the normal --,
+ *     turns it onto the normal's side and multiplies by n . omega, so the function it integrates is Kd (n . omega) |omega.z| / pi per
+ *     solid angle, and the direct term has to integrate the same function or the two estimators disagree.  For a wall that faces along
+ *     z this is Kd cos^2 / pi; for any other wall cs * cs is a different function, and the agreement test of tests/test_direct_host.py
+ *     tells the two apart)
+ *   term_c = ((T_c * Kd_c) * Le_c) * g  with T the throughput entering the lobe
+ *   The term is added to L if and only if the closest hit of the ray (O, omega), found by the same search with the same eps, is light
+ *   i's triangle.  No distance bound, no tolerance: a point on a shared edge that resolves to the neighbour counts as occluded.
+ * NO DOUBLE COUNTING: a path carries one bit.  A diffuse step under direct lighting sets it (whether or not it had a term); a primary
+ * ray clears it and so does every other scattering step (mirror, GGX, dielectric).  An emitter hit adds throughput x Kd to L only
+ * when the bit is clear; the path ends there either way.  The skybox and the environment add to L as before, whatever the bit: they
+ * are not sampled.  Glossy, rough and dielectric steps get no direct term.
+ * Statistics under the switch: samples_traced, segments and misses count path segments only (no shadow ray); contributing counts the
+ * terms added to any L.
+ *
+ * Not built: multiple importance sampling, sampling by power, environment importance sampling, direct terms for the GGX lobe, textured
+ * emitters, Russian roulette.
+ *
+ * PT_ERR_INVALID_ARGUMENT: a NULL handle; switching on for a scene without a light; switching on while an emissive material is in the
+ * handle's texture list -- and pt_scene_set_textures refuses such a material in turn while the switch is on.  A setter builds and
+ * uploads first and swaps last: a refused call leaves every handle as it was.  A host-only scene (device < 0) accepts the switch. */
+typedef struct pt_light {
+    float v0[3];
+    float cdf;
+    float e1[3];
+    int32_t triangle; /* original index */
+    float e2[3];
+    float pad0;
+    float normal[3]; /* Nl */
+    float pad1;
+    float le[3];
+    float pad2;
+} pt_light;
+int pt_scene_set_direct_lighting(pt_scene *scene, int32_t on);
+int pt_scene_get_direct_lighting(const pt_scene *scene, int32_t *on);
+/* The light table the switch uses (or would use): *n = the number of lights, lights (may be NULL) gets them, *area (may be NULL) = A. */
+int pt_scene_get_lights(const pt_scene *scene, pt_light *lights, int32_t *n, float *area);
+/* The same on a frame: every device's copy of the frame's scene; a refused call changes none.  The getters answer for the root's. */
+int pt_frame_set_direct_lighting(pt_frame *frame, int32_t on);
+int pt_frame_get_direct_lighting(pt_frame *frame, int32_t *on);
+int pt_frame_get_lights(pt_frame *frame, pt_light *lights, int32_t *n, float *area);
+/* THE DIRECT TERM alone, on the host, without the visibility, for n hits: origins (O), normals (N), shading_normals (n), throughput
+ * (T), kd (3 n floats each) and the words l0, l1, l2 (n each) give out_light (the table index i), out_points (P), out_directions
+ * (omega), out_terms (3 n each; zero without a term) and out_has_term (n). */
+int pt_direct_term(int32_t n, const pt_light *lights, int32_t n_lights, float area, const float *origins, const float *normals,
+                   const float *shading_normals, const float *throughput, const float *kd, const uint32_t *l0, const uint32_t *l1,
+                   const uint32_t *l2, int32_t *out_light, float *out_points, float *out_directions, float *out_terms, int32_t *out_has_term);
+
 /* ---- misc ------------------------------------------------------------------------------------------- */
 int pt_abi_version(void);
 int pt_device_count(void);

@@ -70,7 +70,9 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_frame_set_shading_normals", "pt_frame_get_shading_normals", "pt_smooth_normals", "pt_scene_load_obj_ex",
                "pt_shading_normal_at",
                "pt_scene_set_roughness", "pt_scene_get_roughness", "pt_frame_set_roughness", "pt_frame_get_roughness",
-               "pt_scene_get_mtl_roughness", "pt_rough_step"]
+               "pt_scene_get_mtl_roughness", "pt_rough_step",
+               "pt_scene_set_direct_lighting", "pt_scene_get_direct_lighting", "pt_scene_get_lights", "pt_frame_set_direct_lighting",
+               "pt_frame_get_direct_lighting", "pt_frame_get_lights", "pt_direct_term"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -529,6 +531,30 @@ def rough_step(normals, directions, alpha, w1, w2, library=None, want_microfacet
     return (out, g1, h) if want_microfacet else (out, g1)
 
 
+# pt_light, the record of a handle's light table (pt_hip.h: direct lighting), as a numpy dtype: 80 bytes
+LIGHT_DTYPE = np.dtype([("v0", np.float32, 3), ("cdf", np.float32), ("e1", np.float32, 3), ("triangle", np.int32), ("e2", np.float32, 3),
+                        ("pad0", np.float32), ("normal", np.float32, 3), ("pad1", np.float32), ("le", np.float32, 3), ("pad2", np.float32)])
+
+
+def direct_term(lights, area, origins, normals, shading_normals, throughput, kd, l0, l1, l2, library=None):
+    """pt_direct_term, the host's own evaluation of the direct term without the visibility: for a light table (`lights` of LIGHT_DTYPE,
+    `area` = A), next origins O [n, 3], stored normals N, shading normals n, throughputs T and albedos Kd [n, 3] and the words l0, l1,
+    l2 [n]: the chosen light's table index [n], the point P [n, 3], the unit direction [n, 3], the term [n, 3] and whether there is one [n]."""
+    L = library or lib()
+    lt = np.ascontiguousarray(lights, LIGHT_DTYPE)
+    arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (origins, normals, shading_normals, throughput, kd)]
+    words = [np.ascontiguousarray(w, np.uint32).reshape(-1) for w in (l0, l1, l2)]
+    n = len(arrs[0])
+    if any(len(a) != n for a in arrs + words):
+        raise ValueError("direct_term: arrays of one length")
+    idx, has = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    pts, dirs, terms = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    up, ip = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    _check(L.pt_direct_term(n, lt.ctypes.data_as(C.c_void_p), len(lt), C.c_float(area), *[_fp(a) for a in arrs], *[w.ctypes.data_as(up) for w in words],
+                            idx.ctypes.data_as(ip), _fp(pts), _fp(dirs), _fp(terms), has.ctypes.data_as(ip)), L)
+    return idx, pts, dirs, terms, has.astype(bool)
+
+
 TEXTURE_NEAREST, TEXTURE_BILINEAR = 0, 1
 TEXTURE_MAX_SIDE = 8192
 _TEXTURE_FILTERS = {"nearest": TEXTURE_NEAREST, "bilinear": TEXTURE_BILINEAR}
@@ -768,6 +794,11 @@ def load_library(path):
         getattr(L, f"pt_{who}_set_roughness").argtypes = [vp, rp, C.c_int32]
         getattr(L, f"pt_{who}_get_roughness").argtypes = [vp, rp, ip]
     L.pt_scene_get_mtl_roughness.argtypes = [vp, fp]
+    for who in ("scene", "frame"):
+        getattr(L, f"pt_{who}_set_direct_lighting").argtypes = [vp, C.c_int32]
+        getattr(L, f"pt_{who}_get_direct_lighting").argtypes = [vp, ip]
+        getattr(L, f"pt_{who}_get_lights").argtypes = [vp, vp, ip, fp]
+    L.pt_direct_term.argtypes = [C.c_int32, vp, C.c_int32, C.c_float, fp, fp, fp, fp, fp] + [C.POINTER(C.c_uint32)] * 3 + [ip, fp, fp, fp, ip]
     L.pt_rough_step.argtypes = [C.c_int32, fp, fp, fp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), fp, fp, fp]
     L.pt_scene_get_map_kd.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p)]
     L.pt_texture_load_bmp.argtypes = [C.c_char_p, C.c_float, ip, ip, fp]
@@ -964,6 +995,30 @@ class _RoughMethods:
         return pr[:scene.counts()[1]]
 
 
+class _DirectMethods:
+    """set_direct_lighting / direct_lighting / lights of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
+    _direct_prefix = "pt_scene_"
+
+    def set_direct_lighting(self, on):
+        """-DIRECT: switches direct lighting on or off (pt_hip.h: direct lighting).  Refused: a scene without a light, an emissive
+        material in the texture list."""
+        _check(getattr(self._L, self._direct_prefix + "set_direct_lighting")(self._h, 1 if on else 0), self._L)
+
+    def direct_lighting(self):
+        on = C.c_int32()
+        _check(getattr(self._L, self._direct_prefix + "get_direct_lighting")(self._h, C.byref(on)), self._L)
+        return bool(on.value)
+
+    def lights(self):
+        """The handle's light table: (records of LIGHT_DTYPE in the original triangle order, A)."""
+        get = getattr(self._L, self._direct_prefix + "get_lights")
+        n, area = C.c_int32(), C.c_float()
+        _check(get(self._h, None, C.byref(n), C.byref(area)), self._L)
+        arr = np.zeros(max(n.value, 1), LIGHT_DTYPE)
+        _check(get(self._h, arr.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(area)), self._L)
+        return arr[:n.value], np.float32(area.value)
+
+
 class _TextureMethods:
     """set_texcoords / texcoords / set_textures / textures of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
     _tex_prefix = "pt_scene_"
@@ -1043,7 +1098,7 @@ class _SmoothMethods:
         return scene._normals(scene._L.pt_scene_get_vertex_normals)
 
 
-class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods):
+class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods):
     """Owns a pt_scene handle (Scene + LoadModel of the reference, scene.h:17-19)."""
 
     def __init__(self, handle, library=None):
@@ -1790,9 +1845,9 @@ def bvh_depth(nodes):
     return int(level.max())
 
 
-class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods):
+class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods):
     """pt_frame: one image on several devices from one host program -- row bands, one gather to the first device."""
-    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = _rough_prefix = "pt_frame_"
+    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = _rough_prefix = _direct_prefix = "pt_frame_"
 
     def _n_tri(self):
         return self._scene.counts()[0]

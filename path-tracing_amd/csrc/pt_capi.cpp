@@ -120,6 +120,7 @@ int upload(pt_scene *s, int device) {
     if (s->textures && (rc = ptc::upload_textures(*s->textures, *s->texcoords, s->shared->tables, s->d_tex)) != PT_OK) return rc;
     if (s->smooth && (rc = ptc::upload_smooth(*s->smooth, s->shared->tables, s->d_smooth)) != PT_OK) return rc;
     if (s->rough && (rc = ptc::upload_rough(s->rough->table, s->shared->tables, s->d_rough)) != PT_OK) return rc;
+    if (s->direct && (rc = ptc::upload_direct(*s->direct, s->shared->tables, s->d_direct)) != PT_OK) return rc;
     return PT_OK;
 }
 
@@ -312,6 +313,21 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
         }
         if (!a.glass) a.glass = scene->d_rough.no_glass.get<void>();
     }
+    if (scene->direct && scene->d_direct.lights) {   // the direct kernels of those (integrate_kernel_direct); absent lists as all-zero tables
+        const DeviceRough &none = scene->d_direct.none;
+        a.lights = scene->d_direct.lights.get<void>();
+        a.n_lights = static_cast<int32_t>(scene->direct->lights.size());
+        a.light_area = scene->direct->area;
+        if (!a.rough_alpha) a.rough_alpha = none.alpha.get<float>();   // (all zeros: every glossy lobe is the mirror)
+        if (!a.smooth_normals) a.smooth_normals = none.no_normals.get<void>();
+        if (!a.tex_recs) {
+            a.tex_recs = none.no_tex.get<void>();
+            a.tex_uv = none.no_tex.get<float>();
+            a.tex_texels = none.no_tex.get<void>();
+            a.tex_bary = none.bary.get<void>();
+        }
+        if (!a.glass) a.glass = none.no_glass.get<void>();
+    }
     a.n_clusters = static_cast<int32_t>(t.clusters.size());
     a.n_tri = scene->shared->host.n_tri();
     a.big = t.big ? 1 : 0;
@@ -378,6 +394,8 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     if (crc != PT_OK) return crc;
     pt::RenderArgs a;
     fill_scene_args(scene, p->eps, a);
+    // (a handle that answers 1 to get_direct_lighting never renders without its light table)
+    if (scene->direct && !a.lights) return fail(PT_ERR_INVALID_ARGUMENT, "direct lighting: the handle has the switch set and no light table on its device");
     a.vec_ok = (p->width % 4 == 0) &&
                ((reinterpret_cast<uintptr_t>(planes.sum) | reinterpret_cast<uintptr_t>(planes.sum2) | reinterpret_cast<uintptr_t>(planes.count)) % 16 == 0);
     a.sum = planes.sum;
@@ -434,6 +452,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
         PT_HIP_TRY(hipEventRecord(ctx.ev0.get(), stream));
     }
     const hipError_t launched = pt::launch_integrator(a, tiles.variant, stream);
+    if (launched == hipErrorNotSupported && a.lights != nullptr) return fail(PT_ERR_UNSUPPORTED, "direct lighting: this diagnostic build of the library has no direct kernels");
     if (launched == hipErrorNotSupported && a.rough_alpha != nullptr) return fail(PT_ERR_UNSUPPORTED, "roughness: this diagnostic build of the library has no rough kernels");
     if (launched == hipErrorNotSupported && a.smooth_normals != nullptr) return fail(PT_ERR_UNSUPPORTED, "shading normals: this diagnostic build of the library has no smooth kernels");
     if (launched == hipErrorNotSupported && a.tex_recs != nullptr) return fail(PT_ERR_UNSUPPORTED, "textures: this diagnostic build of the library has no texture kernels");
@@ -668,6 +687,7 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->textures = src->textures;
     s->smooth = src->smooth;   // and its shading normals
     s->rough = src->rough;     // and its roughness list
+    s->direct = src->direct;   // and its light table
     s->has_camera = src->has_camera;   // and its camera
     s->camera = src->camera;
     s->has_lens = src->has_lens;       // and lens

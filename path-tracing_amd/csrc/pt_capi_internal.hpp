@@ -29,6 +29,7 @@
 #include "pt_local.hpp"
 #include "pt_meter.hpp"
 #include "pt_optics.hpp"
+#include "pt_direct.hpp"
 #include "pt_rough.hpp"
 #include "pt_scene.hpp"
 #include "pt_sharpen.hpp"
@@ -106,6 +107,18 @@ struct DeviceRough {
     ptc::DeviceBuffer alpha, no_normals, bary, no_tex, no_glass;
 };
 
+// The light table of a handle with direct lighting on (pt_hip.h: direct lighting): the lights in the original triangle order and the
+// total area A.  Belongs to the handle as the roughness list does; immutable once built (a handle's triangles and materials never change).
+struct pt_light_table {
+    std::vector<pt::LightRec> lights;
+    float area = 0.0f;
+};
+// Its device copy, and what a handle without a roughness list, shading normals, textures or dielectrics passes to the direct kernels.
+struct DeviceDirect {
+    ptc::DeviceBuffer lights;
+    DeviceRough none;
+};
+
 // Device copy of one CullTables (they depend on eps and on the envelope the camera needs; a scene keeps the one of its last
 // render).
 struct DeviceCull {
@@ -149,6 +162,8 @@ struct pt_scene {
     DeviceSmooth d_smooth;         // on this copy's device
     std::shared_ptr<const pt_rough_list> rough;   // this handle's roughness list (nullptr = none); copies inherit it
     DeviceRough d_rough;           // on this copy's device
+    std::shared_ptr<const pt_light_table> direct;   // this handle's light table (nullptr = direct lighting off); copies inherit it
+    DeviceDirect d_direct;         // on this copy's device
     bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
     pt_camera camera{};
     bool has_lens = false;         // this handle's lens (pt_scene_set_lens; radius > 0); copies made from it inherit it
@@ -485,5 +500,19 @@ inline int upload_rough(const std::vector<float> &alpha, const pt::DeviceTables 
     out = std::move(d);
     return PT_OK;
 }
+
+// A handle's light table onto the current device, with the all-zero tables of upload_rough (the setters of pt_direct_capi.cpp; a
+// clone's upload in pt_capi.cpp).  `out` is only written once every upload has succeeded.
+inline int upload_direct(const pt_light_table &table, const pt::DeviceTables &tables, DeviceDirect &out) {
+    DeviceDirect d;
+    int rc;
+    if ((rc = d.lights.upload(table.lights, "light table", 64)) != PT_OK ||
+        (rc = upload_rough(std::vector<float>(tables.mats.size(), 0.0f), tables, d.none)) != PT_OK)
+        return rc;
+    out = std::move(d);
+    return PT_OK;
+}
+// Whether material `m` is what the light table takes its lights from: the single emissive lobe.
+inline bool material_is_light(const pt::MatRec &m) { return m.n_lobes == 1 && m.kind0 == 0; }
 
 }  // namespace ptc

@@ -1,0 +1,6 @@
+// The direct kernels (pt_hip.h: direct lighting): pt::integrate_kernel_direct and its launcher, compiled from pt_kernels.hip -- the
+// search, the shared integrator body, the rough kernels' set of instantiations and the waves-per-SIMD rules of the twins are all
+// there -- as a translation unit of its own, the way pt_rough_kernels.hip is.  Every flavour of the library but the diagnostic ones
+// (Makefile) builds this file with the flags of its pt_kernels object.
+#define PT_DIRECT_UNIT
+#include "pt_kernels.hip"

@@ -10,9 +10,14 @@
 // the dielectric step run with the interpolated shading normal of the hit point (pt_hip.h: shading normals; pt_smooth.hpp spells it).
 // ROUGH (only pt::integrate_kernel_rough: false in every other kernel; with SMOOTH) = the glossy lobe of a material the handle's
 // roughness table marks reflects about a GGX microfacet normal and takes Ks x G1 (pt_hip.h: rough specular; pt_rough.hpp spells it).
+// DIRECT (only pt::integrate_kernel_direct: false in every other kernel; with ROUGH) = a path collects its radiance in L and the
+// accumulators take it once, when the path ends; a scattering diffuse hit sends a shadow ray to a sampled point of the handle's light
+// table through closest_hit itself, and an emitter reached by the diffuse lobe's own ray adds nothing (pt_hip.h: direct lighting;
+// pt_direct.hpp spells the term).
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
+    static_assert(!DIRECT || (SMOOTH && ROUGH), "the direct term is written in the smooth scatter step: a direct kernel is a rough kernel with DIRECT");
     static_assert(!MOTION || CAM, "a motion kernel is the motion variant of a camera twin or of its lens kernel");
     static_assert(!PROJ || (CAM && !LENS && !MOTION), "a projection kernel is the projection variant of a camera twin; the host refuses a lens or a motion with it");
     static_assert(!NARROW || (!SKY && !STATS), "only the statistics-free, skybox-free kernels have a narrow variant");
@@ -242,6 +247,21 @@
     float tr[R], tg[R], tb[R];   // Ray::color_ (throughput), ray.h:17
     int depth[R];
     int cur_pass[R], next_pass[R];   // REGEN: the pass slot k's path belongs to / the next one its pixel has to run
+    // DIRECT: the path's radiance L; the pending shadow ray's direction (its origin is the path ray's), term and light (the triangle's
+    // original index); `lit` = the path's last step was a diffuse one, whose emitters the shadow ray has sampled.  A shadow ray is
+    // searched in the segment-loop iteration after the one that made it, alone (shadow_phase), so `pending` lives for one iteration.
+    [[maybe_unused]] float Lr[R], Lg[R], Lb[R], sdx[R], sdy[R], sdz[R], scr[R], scg[R], scb[R];
+    [[maybe_unused]] int slight[R];
+    [[maybe_unused]] bool lit[R], pending[R];
+    if constexpr (DIRECT) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            Lr[k] = Lg[k] = Lb[k] = 0.0f;
+            sdx[k] = sdy[k] = sdz[k] = scr[k] = scg[k] = scb[k] = 0.0f;
+            slight[k] = -1;
+            lit[k] = pending[k] = false;
+        }
+    }
 #pragma unroll
     for (int k = 0; k < R; ++k) {
         tr[k] = tg[k] = tb[k] = 1.0f;
@@ -474,6 +494,10 @@
             }
             tr[k] = tg[k] = tb[k] = 1.0f;
             depth[k] = 0;
+            if constexpr (DIRECT) {
+                Lr[k] = Lg[k] = Lb[k] = 0.0f;
+                lit[k] = false;
+            }
         };
         auto primary_ray = [&](int k, int pass_k) {
             float ddx, ddy, ddz;
@@ -503,11 +527,32 @@
                 if constexpr (STATS) n_traced += __builtin_popcountll(__ballot(!skip[k]));
             }
         }
+        // DIRECT: a path that has ended hands its radiance to the accumulators, once (count = the paths traced)
+        [[maybe_unused]] auto path_over = [&](int k) { return !(depth[k] < mrr && (tr[k] != 0.0f || tg[k] != 0.0f || tb[k] != 0.0f)); };
         for (;;) {
             bool valid[R];
 #pragma unroll
             for (int k = 0; k < R; ++k) valid[k] = depth[k] < mrr && (tr[k] != 0.0f || tg[k] != 0.0f || tb[k] != 0.0f);   // Ray::IsValid, ray.h:52-54
+            // DIRECT: the shadow rays the last iteration's shading left are searched first, alone: the slot's ray takes the shadow
+            // direction for this iteration (the origin is the same) and gets its own back below.
+            [[maybe_unused]] bool shadow_phase = false;
+            if constexpr (DIRECT) {
+                shadow_phase = any_of(pending);
+                if (shadow_phase) {
+#pragma unroll
+                    for (int k = 0; k < R; ++k) {
+                        valid[k] = pending[k];
+                        if (pending[k]) {
+                            float t;
+                            t = q[k].dx; q[k].dx = sdx[k]; sdx[k] = t;
+                            t = q[k].dy; q[k].dy = sdy[k]; sdy[k] = t;
+                            t = q[k].dz; q[k].dz = sdz[k]; sdz[k] = t;
+                        }
+                    }
+                }
+            }
             if constexpr (REGEN) {
+                if (!shadow_phase) {
                 // Regeneration: a slot whose path is over takes its pixel's next pass -- after the adaptive skip of
                 // main.cpp:118-125, which sits out passes > 10 that are not multiples of 4 while the variance is low: the next
                 // one that runs is then the next multiple of 4.
@@ -545,14 +590,17 @@
                         if constexpr (STATS) n_traced += __builtin_popcountll(__ballot(wants[k]));
                     }
                 }
+                }
             }
             if (!any_of(valid)) break;
 #ifdef PT_ADAPT_COUNT
             if (two) ++c_seg2; else ++c_seg1;
 #endif
             if constexpr (STATS) {
+                if (!shadow_phase) {
 #pragma unroll
                 for (int k = 0; k < R; ++k) n_segments += __builtin_popcountll(__ballot(valid[k]));
+                }
             }
 
             float best[R];
@@ -583,6 +631,7 @@
             bool all_last = last_or_dead[0];
 #pragma unroll
             for (int k = 1; k < R; ++k) all_last = all_last && last_or_dead[k];
+            if constexpr (DIRECT) all_last = all_last && !shadow_phase;   // (a shadow ray is no last segment: the full search decides it)
             constexpr bool kLastSegmentFilter = !STATS && !SKY && !BIG;   // (big scenes: the flag's scalar registers cost more than it saves)
             bool emis_phase = false;
             if constexpr (kLastSegmentFilter) emis_phase = a.last_segment_filter != 0u && __all(all_last);
@@ -663,6 +712,27 @@
             }
 #endif
 
+            // DIRECT: the shadow rays' verdicts.  The term counts if and only if the closest hit is the sampled light's triangle; the
+            // slot's path ray comes back, and a path that had ended with the step (throughput zero) is handed in now.
+            if constexpr (DIRECT) {
+                if (shadow_phase) {
+#pragma unroll
+                    for (int k = 0; k < R; ++k) {
+                        bool added = false;
+                        if (PT_SLOT_ON(k) && pending[k]) {
+                            if (hit[k] == slight[k]) {
+                                Lr[k] += scr[k]; Lg[k] += scg[k]; Lb[k] += scb[k];
+                                added = true;
+                            }
+                            q[k].dx = sdx[k]; q[k].dy = sdy[k]; q[k].dz = sdz[k];
+                            pending[k] = false;
+                            if (path_over(k)) contribute(k, Lr[k], Lg[k], Lb[k]);
+                        }
+                        if constexpr (STATS) n_contrib += __builtin_popcountll(__ballot(added));
+                    }
+                    continue;
+                }
+            }
             // ---- 3. shade (Scene::TraceRay scene.cpp:121-156, Material::Process material.h:36-50), ray after ray of the lane
 #pragma unroll
             for (int k = 0; k < R; ++k) {
@@ -674,6 +744,9 @@
                         const EnvironmentView ev = environment_view();
                         float lr, lg, lb;
                         env_lookup(ev.map(), ev.n(), q[k].dx, q[k].dy, q[k].dz, lr, lg, lb);
+                        if constexpr (DIRECT) {
+                            Lr[k] += tr[k] * lr; Lg[k] += tg[k] * lg; Lb[k] += tb[k] * lb;
+                        } else
                         contribute(k, tr[k] * lr, tg[k] * lg, tb[k] * lb);
                         contributed = true;
                     } else if (SKY) {   // skybox miss shader, scene.cpp:126-154 (note: the path throughput is NOT applied)
@@ -700,6 +773,9 @@
                             const float c34 = c3 * (1.0f - ax) + c4 * ax;
                             c[ch] = (c12 * (1.0f - ay) + c34 * ay) / 256.f;
                         }
+                        if constexpr (DIRECT) {
+                            Lr[k] += c[0]; Lg[k] += c[1]; Lb[k] += c[2];
+                        } else
                         contribute(k, c[0], c[1], c[2]);
                         contributed = true;
                     }
@@ -799,8 +875,15 @@
                     } else if (kind == 0) {   // emissive, material.h:68-79
                         if (!((q[k].dx * pl.x + q[k].dy * pl.y) + q[k].dz * pl.z > 0)) {
                             const float cr = tr[k] * m0v.x, cg = tg[k] * m0v.y, cb = tb[k] * m0v.z;
+                            if constexpr (DIRECT) {   // (an emitter the diffuse step's shadow ray has sampled already adds nothing)
+                                if (!lit[k]) {
+                                    Lr[k] += cr; Lg[k] += cg; Lb[k] += cb;
+                                    contributed = true;
+                                }
+                            } else {
                             contribute(k, cr, cg, cb);
                             contributed = true;
+                            }
                         }
                         depth[k] = mrr;
                     } else {
@@ -824,6 +907,26 @@
                             float sx, sy, sz;
                             smooth_normal(c0.x, c0.y, c0.z, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, sb1, sb2, pl.x, pl.y, pl.z,
                                           [](float &vx, float &vy, float &vz) { normalize3(vx, vy, vz); }, sx, sy, sz);
+                            // DIRECT: the direct term of a diffuse step (pt_hip.h: direct lighting; pt_direct.hpp spells it), from the
+                            // words of counter (pixel, pass, depth, 3): the light, the point on it, the shadow ray from the next origin
+                            // p + N eps and the term, which waits for the ray's verdict.
+                            if constexpr (DIRECT) {
+                                lit[k] = !dielectric && kind != 1;
+                                if (lit[k]) {
+                                    uint32_t l0, l1, l2, l3;
+                                    philox4x32_10(rng_pixel(k), static_cast<uint32_t>(pass_of(k)), static_cast<uint32_t>(depth[k]), kDirectStream, a.seed, kPhiloxKey1,
+                                                  l0, l1, l2, l3);
+                                    const DirectView dv = direct_view();
+                                    const LightRec *__restrict__ lr = dv.lights() + direct_pick(dv.lights(), dv.n(), unit_float(l0));
+                                    const LightRec lrec = *lr;   // (five 16-byte loads)
+                                    float ppx, ppy, ppz;
+                                    pending[k] = direct_term(lrec, dv.area(), unit_float(l1), unit_float(l2), px + pl.x * eps, py + pl.y * eps, pz + pl.z * eps,
+                                                             pl.x, pl.y, pl.z, sx, sy, sz, tr[k], tg[k], tb[k], m0v.x, m0v.y, m0v.z,
+                                                             [](float &vx, float &vy, float &vz) { normalize3(vx, vy, vz); }, ppx, ppy, ppz, sdx[k], sdy[k], sdz[k],
+                                                             scr[k], scg[k], scb[k]);
+                                    slight[k] = lrec.orig;
+                                }
+                            }
                             float hx = 0.0f, hy = 0.0f, hz = 0.0f;
                             if (!dielectric && kind != 1) {   // diffuse, material.h:90-100: the sample
                                 const float xi1 = unit_float(w1), xi2 = unit_float(w2);
@@ -960,6 +1063,9 @@
                         }
                         ++depth[k];
                     }
+                }
+                if constexpr (DIRECT) {
+                    if (!pending[k] && path_over(k)) contribute(k, Lr[k], Lg[k], Lb[k]);
                 }
             }
             if constexpr (STATS) n_contrib += __builtin_popcountll(__ballot(contributed));

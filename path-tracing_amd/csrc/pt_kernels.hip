@@ -40,6 +40,7 @@
 #include "pt_texture.hpp"
 #include "pt_smooth.hpp"
 #include "pt_rough.hpp"
+#include "pt_direct.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1376,6 +1377,23 @@ __device__ __forceinline__ const float *rough_view() {
     asm volatile("" : "+s"(p));
     return *reinterpret_cast<const float *const __attribute__((address_space(4))) *>(p);
 }
+// The light table of a direct-kernel launch (RenderArgs::lights, n_lights, light_area), likewise: read where the diffuse lobe of a ray
+// that scatters has been chosen.
+struct DirectView {
+    uint64_t p;
+    __device__ __forceinline__ const LightRec *lights() const { return *reinterpret_cast<const LightRec *const __attribute__((address_space(4))) *>(p); }
+    __device__ __forceinline__ int32_t n() const {
+        return *reinterpret_cast<const __attribute__((address_space(4))) int32_t *>(p + (offsetof(RenderArgs, n_lights) - offsetof(RenderArgs, lights)));
+    }
+    __device__ __forceinline__ float area() const {
+        return *reinterpret_cast<const __attribute__((address_space(4))) float *>(p + (offsetof(RenderArgs, light_area) - offsetof(RenderArgs, lights)));
+    }
+};
+__device__ __forceinline__ DirectView direct_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, lights);
+    asm volatile("" : "+s"(p));
+    return {p};
+}
 
 // What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
 // in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
@@ -1412,7 +1430,7 @@ constexpr int integrator_waves() {
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
 #include "pt_integrator_body.inc"
 }
 // The lens kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary ray
@@ -1428,7 +1446,7 @@ constexpr int lens_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (lens_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false;
+    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
 #include "pt_integrator_body.inc"
 }
 // The motion twins (pt_hip.h: camera motion): the camera twin and its lens kernel with the camera -- and the lens axes -- interpolated
@@ -1444,12 +1462,12 @@ constexpr int motion_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, false>())) void integrate_kernel_motion(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false;
+    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
 #include "pt_integrator_body.inc"
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, true>())) void integrate_kernel_motion_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false;
+    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
 #include "pt_integrator_body.inc"
 }
 // The projection kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary
@@ -1464,7 +1482,7 @@ constexpr int projection_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (projection_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_projection(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
 #include "pt_integrator_body.inc"
 }
 
@@ -1489,7 +1507,7 @@ template <bool BIG, bool STATS, bool ENV, int VIEW>
 __global__ __launch_bounds__(kBlock, (environment_waves<BIG, STATS, ENV, VIEW>())) void integrate_kernel_environment(const RenderArgs a) {
     constexpr bool SKY = true, NARROW = false;
     constexpr int ADAPT = VIEW != 0 ? 1 : 0;
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
 #include "pt_integrator_body.inc"
 }
 namespace {
@@ -1512,27 +1530,32 @@ hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Var
     hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
     return hipGetLastError();
 }
-#elif defined(PT_GLASS_UNIT) || defined(PT_TEXTURE_UNIT) || defined(PT_SMOOTH_UNIT) || defined(PT_ROUGH_UNIT)
+#elif defined(PT_GLASS_UNIT) || defined(PT_TEXTURE_UNIT) || defined(PT_SMOOTH_UNIT) || defined(PT_ROUGH_UNIT) || defined(PT_DIRECT_UNIT)
 // (PT_TEXTURE_UNIT -- pt_texture_kernels.hip -- compiles this same section once more, as integrate_kernel_texture: the dielectric
 // kernels' set of instantiations with TEX = true as well, see below the dielectric kernels' own description; PT_SMOOTH_UNIT --
 // pt_smooth_kernels.hip -- a third time, as integrate_kernel_smooth: the texture kernels' set with SMOOTH = true as well;
-// PT_ROUGH_UNIT -- pt_rough_kernels.hip -- a fourth time, as integrate_kernel_rough: the smooth kernels' set with ROUGH = true as well)
-#if defined(PT_ROUGH_UNIT)
+// PT_ROUGH_UNIT -- pt_rough_kernels.hip -- a fourth time, as integrate_kernel_rough: the smooth kernels' set with ROUGH = true as well;
+// PT_DIRECT_UNIT -- pt_direct_kernels.hip -- a fifth time, as integrate_kernel_direct: the rough kernels' set with DIRECT = true as well)
+#if defined(PT_DIRECT_UNIT)
+#define PT_UNIT_KERNEL integrate_kernel_direct
+#define PT_UNIT_LAUNCH launch_direct_integrator
+constexpr bool kUnitTex = true, kUnitSmooth = true, kUnitRough = true, kUnitDirect = true;
+#elif defined(PT_ROUGH_UNIT)
 #define PT_UNIT_KERNEL integrate_kernel_rough
 #define PT_UNIT_LAUNCH launch_rough_integrator
-constexpr bool kUnitTex = true, kUnitSmooth = true, kUnitRough = true;
+constexpr bool kUnitTex = true, kUnitSmooth = true, kUnitRough = true, kUnitDirect = false;
 #elif defined(PT_SMOOTH_UNIT)
 #define PT_UNIT_KERNEL integrate_kernel_smooth
 #define PT_UNIT_LAUNCH launch_smooth_integrator
-constexpr bool kUnitTex = true, kUnitSmooth = true, kUnitRough = false;
+constexpr bool kUnitTex = true, kUnitSmooth = true, kUnitRough = false, kUnitDirect = false;
 #elif defined(PT_TEXTURE_UNIT)
 #define PT_UNIT_KERNEL integrate_kernel_texture
 #define PT_UNIT_LAUNCH launch_texture_integrator
-constexpr bool kUnitTex = true, kUnitSmooth = false, kUnitRough = false;
+constexpr bool kUnitTex = true, kUnitSmooth = false, kUnitRough = false, kUnitDirect = false;
 #else
 #define PT_UNIT_KERNEL integrate_kernel_glass
 #define PT_UNIT_LAUNCH launch_glass_integrator
-constexpr bool kUnitTex = false, kUnitSmooth = false, kUnitRough = false;
+constexpr bool kUnitTex = false, kUnitSmooth = false, kUnitRough = false, kUnitDirect = false;
 #endif
 // ---------------------------------------------------------------------------------------------------------------
 // The dielectric kernels (pt_glass_kernels.hip: this file compiled with PT_GLASS_UNIT, a translation unit of its own).  The body
@@ -1592,18 +1615,38 @@ constexpr int rough_fewer_waves() {
     // pool's state): the small-scene batch kernel over 16 x 8 tiles with a fixed eye, with the moving lens and under a projection.
     return (MISS == 0 && !BIG && !STATS && FORM == 2 && (VIEW == 0 || VIEW == 4 || VIEW == 5)) ? 1 : 0;
 }
+// The direct kernels (pt_hip.h: direct lighting): the same set with DIRECT = true too -- a path collects its
+// radiance and is counted once when it ends, and a scattering diffuse hit sends a shadow ray to a sampled point of the handle's light
+// table (RenderArgs::lights; pt_direct.hpp) through the same closest-hit search.  A handle without the other tables runs them with
+// all-zero ones.  The twin of a direct kernel is the rough kernel of the same arguments; waves per SIMD: that twin's minus
+// direct_fewer_waves (tests/test_direct_resources.py pins every kernel).
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+constexpr int rough_unit_waves() {
+    return view_waves<MISS != 0, BIG, STATS, FORM < 2, FORM == 1, VIEW>() - glass_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() -
+           texture_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() - smooth_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() -
+           rough_fewer_waves<MISS, BIG, STATS, FORM, VIEW>();
+}
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+constexpr int direct_fewer_waves() {
+    // The path's radiance, the pending shadow ray's direction, its term and its light are ten vector registers per ray slot on top of
+    // the rough twin's.  Every twin compiled for 5 waves (96 VGPRs) or 6 (80: the 8 x 8 form) either spilled vector registers to scratch
+    // (1 to 93 of them) or was given more registers than its bound by the compiler, which is a wave fewer unsaid: every direct kernel is
+    // compiled for 4 waves per SIMD.
+    constexpr int twin = rough_unit_waves<MISS, BIG, STATS, FORM, VIEW>();
+    return twin > 4 ? twin - 4 : 0;
+}
 template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
 constexpr int unit_waves() {
     return view_waves<MISS != 0, BIG, STATS, FORM < 2, FORM == 1, VIEW>() - glass_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() -
            (kUnitTex ? texture_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) - (kUnitSmooth ? smooth_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) -
-           (kUnitRough ? rough_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0);
+           (kUnitRough ? rough_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) - (kUnitDirect ? direct_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0);
 }
 template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
 __global__ __launch_bounds__(kBlock, (unit_waves<MISS, BIG, STATS, FORM, VIEW>()))
 void PT_UNIT_KERNEL(const RenderArgs a) {
     constexpr bool SKY = MISS != 0, ENV = FORM < 2, NARROW = FORM == 1;
     constexpr int ADAPT = (FORM == 2 ? 2 : FORM == 3 ? 4 : 0) | (VIEW != 0 ? 1 : 0);
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true, TEX = kUnitTex, SMOOTH = kUnitSmooth, ROUGH = kUnitRough;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true, TEX = kUnitTex, SMOOTH = kUnitSmooth, ROUGH = kUnitRough, DIRECT = kUnitDirect;
 #include "pt_integrator_body.inc"
 }
 namespace {
@@ -1628,6 +1671,7 @@ std::array<Kernel, sizeof...(I)> glass_kernel_table(std::integer_sequence<int, I
 const auto kGlassKernels = glass_kernel_table(std::make_integer_sequence<int, kGlassPerView * kGlassViews>());
 }  // namespace
 hipError_t PT_UNIT_LAUNCH(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
+    if (kUnitDirect != (args.lights != nullptr) || (kUnitDirect && args.n_lights <= 0)) return hipErrorInvalidValue;
     if (kUnitRough != (args.rough_alpha != nullptr)) return hipErrorInvalidValue;
     if (kUnitSmooth != (args.smooth_normals != nullptr)) return hipErrorInvalidValue;
     if (kUnitTex != (args.tex_recs != nullptr) || (kUnitTex && (args.tex_uv == nullptr || args.tex_texels == nullptr || args.tex_bary == nullptr))) return hipErrorInvalidValue;
@@ -1759,7 +1803,7 @@ hipError_t launch_integrator(const RenderArgs &args0, const plan::Variant &v, hi
     static uint32_t *d_cnt = nullptr;
     const int rows = args0.row_end - args0.row_begin;
     if (rows <= 0 || args0.width <= 0) return hipSuccess;
-    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr || args0.glass != nullptr || args0.tex_recs != nullptr || args0.smooth_normals != nullptr || args0.rough_alpha != nullptr) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
+    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr || args0.glass != nullptr || args0.tex_recs != nullptr || args0.smooth_normals != nullptr || args0.rough_alpha != nullptr || args0.lights != nullptr) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
     if (!mod) {
         const char *path = std::getenv("PT_BLOCKPROF_HSACO");
         if (!path) return hipErrorInvalidValue;
@@ -1837,6 +1881,7 @@ Kernel kernel_for(const plan::Variant &v, bool projection) {
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
     const int rows = args.row_end - args.row_begin;
     if (rows <= 0 || args.width <= 0) return hipSuccess;
+    if (args.lights != nullptr) return launch_direct_integrator(args, v, stream);   // (pt_direct_kernels.hip)
     if (args.rough_alpha != nullptr) return launch_rough_integrator(args, v, stream);   // (pt_rough_kernels.hip)
     if (args.smooth_normals != nullptr) return launch_smooth_integrator(args, v, stream);   // (pt_smooth_kernels.hip)
     if (args.tex_recs != nullptr) return launch_texture_integrator(args, v, stream);   // (pt_texture_kernels.hip)
@@ -1892,6 +1937,8 @@ hipError_t launch_texture_integrator(const RenderArgs &, const plan::Variant &, 
 hipError_t launch_smooth_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
 // and without the rough kernels': a handle with a roughness list likewise
 hipError_t launch_rough_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
+// and without the direct kernels': a handle with direct lighting likewise
+hipError_t launch_direct_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
 const plan::Build &integrator_build() { return kBuild; }

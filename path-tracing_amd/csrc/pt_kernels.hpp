@@ -117,6 +117,14 @@ struct RenderArgs {
     // would run without it; smooth_normals, glass and the tex_ pointers are then never null (a handle without them passes all-zero
     // tables).  One float per material: alpha, 0 = the mirror.  Read only where the glossy lobe of a ray that scatters has been chosen.
     const float *rough_alpha;
+    // The handle's light table (pt_hip.h: direct lighting), appended likewise.  lights != nullptr: the launch runs the direct kernels
+    // (integrate_kernel_direct, pt_direct_kernels.hip: the rough kernels with per-path accounting and a shadow ray at every scattering
+    // diffuse hit), planned as the kernels the same launch would run without it; rough_alpha, smooth_normals, glass and the tex_
+    // pointers are then never null (a handle without them passes all-zero tables).  n_lights records of 80 bytes (pt_direct.hpp:
+    // LightRec) and the table's total area A.
+    const void *lights;
+    int32_t n_lights;
+    float light_area;
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif
@@ -129,7 +137,7 @@ const plan::Build &integrator_build();
 // with args.env_map != nullptr the environment kernel of skybox kernel `v` (v.sky), likewise; with args.glass != nullptr the dielectric
 // kernel of whichever of those the launch would run (hipErrorNotSupported from a diagnostic build, which has none); with
 // args.tex_recs != nullptr the texture kernel of that one, likewise; with args.smooth_normals != nullptr the smooth kernel of that one;
-// with args.rough_alpha != nullptr the rough kernel of that one
+// with args.rough_alpha != nullptr the rough kernel of that one; with args.lights != nullptr the direct kernel of that one
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the environment kernels' translation unit (pt_environment_kernels.hip); launch_integrator calls it, nothing else does
 hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
@@ -141,6 +149,8 @@ hipError_t launch_texture_integrator(const RenderArgs &args, const plan::Variant
 hipError_t launch_smooth_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the rough kernels' translation unit (pt_rough_kernels.hip), likewise
 hipError_t launch_rough_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+// the direct kernels' translation unit (pt_direct_kernels.hip), likewise
+hipError_t launch_direct_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached).  A projection launch asks for its
 // camera twin's: the projection kernels are compiled for their twins' waves per SIMD and LDS (tests/test_projection_resources.py)
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);

@@ -62,6 +62,11 @@
 // has a Pr line and a glossy lobe (Ns and Ks not zero, not emissive), with Pr clamped into that range.  A malformed entry, an alpha
 // outside the range, an index outside the model, a material listed twice, one without a glossy lobe and one that is also in -GLASS end
 // the program with status 2.  Every other flag combines.  Not built: rough dielectrics, anisotropy, a Fresnel term, roughness textures.
+// Direct lighting (pt_scene_set_direct_lighting, not in the reference): -DIRECT 1 sends a shadow ray to a sampled point of a light at
+// every scattering diffuse hit and counts every path once (pt_hip.h: direct lighting); -DIRECT 0 is a run without the flag.  Any
+// other value, a model without a light and an emissive material that -TEXTURE lists end the program with status 2.  Every other flag
+// combines.  Not built: multiple importance sampling, sampling by power, environment importance sampling, direct terms for the GGX
+// lobe, textured emitters, Russian roulette.
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -191,6 +196,8 @@ struct Options {
     pt_environment_params env_params = {1.0f, 0.0f, 0};
     std::string glass_text;                // -GLASS as given
     std::string rough_text;                // -ROUGH as given
+    std::string direct_text;               // -DIRECT as given
+    bool direct = false;
     std::vector<pt_rough> rough;           // what it makes (empty with -ROUGH mtl: the model's MTL decides)
     bool rough_mtl = false;
     std::string smooth_text, crease_text;  // -SMOOTH / -CREASE as given
@@ -307,6 +314,7 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-ENV_SIZE") o.env_size = v;
         if (f == "-GLASS") o.glass_text = v;
         if (f == "-ROUGH") o.rough_text = v;
+        if (f == "-DIRECT") o.direct_text = v;
         if (f == "-SMOOTH") o.smooth_text = v;
         if (f == "-CREASE") o.crease_text = v;
         if (f == "-TEXTURE") o.texture_text = v;
@@ -510,6 +518,11 @@ int configure(int argc, char **argv, Options &o) {
             if (!(t >= 0.0f && t <= 1.0f)) return refuse(2, "-GLASS: a tint component must lie in 0 .. 1 (\"" + entry + "\")");
         d.material = static_cast<int32_t>(m);
         o.glass.push_back(d);
+    }
+    // -DIRECT 0 | 1
+    if (!o.direct_text.empty()) {
+        if (o.direct_text != "0" && o.direct_text != "1") return refuse(2, "-DIRECT takes 0 or 1, not \"" + o.direct_text + "\"");
+        o.direct = o.direct_text == "1";
     }
     // -ROUGH: "mtl", or entries m:alpha separated by commas; alpha's range is the library's (pt_hip.h: rough specular)
     if (o.rough_text == "mtl") o.rough_mtl = true;
@@ -1322,6 +1335,8 @@ int main(int argc, char **argv) {
         }
         if (pt_scene_set_textures(r.scene, list.data(), static_cast<int32_t>(list.size())) != PT_OK) return refuse(2, std::string("-TEXTURE: ") + pt_last_error());
     }
+    // -DIRECT 1: after -TEXTURE, so that a textured emitter is refused with the library's words, as a model without a light is
+    if (o.direct && pt_scene_set_direct_lighting(r.scene, 1) != PT_OK) return refuse(2, std::string("-DIRECT: ") + pt_last_error());
     if (o.camera && pt_scene_set_camera(r.scene, &o.view) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
     // and its projection -- set before the lens and the motion, which the library refuses on a handle with one, as it refuses the
     // temporal stage when the first frame reaches it: asked here, before any device is looked at, with the library's own words
