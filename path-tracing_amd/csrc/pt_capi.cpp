@@ -116,11 +116,7 @@ int upload(pt_scene *s, int device) {
         s->sky_h = s->sky->h;
     }
     if (s->env && (rc = s->d_env.upload(pt::env_with_apron(s->env->n, s->env->rgb.data()), "environment map", 64)) != PT_OK) return rc;
-    if (s->glass && (rc = s->d_glass.upload(s->glass->table, "dielectric table", 64)) != PT_OK) return rc;
-    if (s->textures && (rc = ptc::upload_textures(*s->textures, *s->texcoords, s->shared->tables, s->d_tex)) != PT_OK) return rc;
-    if (s->smooth && (rc = ptc::upload_smooth(*s->smooth, s->shared->tables, s->d_smooth)) != PT_OK) return rc;
-    if (s->rough && (rc = ptc::upload_rough(s->rough->table, s->shared->tables, s->d_rough)) != PT_OK) return rc;
-    if (s->direct && (rc = ptc::upload_direct(*s->direct, s->shared->tables, s->d_direct)) != PT_OK) return rc;
+    if ((rc = ptc::upload_surface(s->surface, t, s->d_surface, s->d_surface)) != PT_OK) return rc;
     return PT_OK;
 }
 
@@ -251,13 +247,38 @@ int finish_scene(ScenePtr s, int device, pt_scene **out) {
         if (m < 0 || m >= h.host.n_mat()) return fail(PT_ERR_INVALID_ARGUMENT, "triangle refers to material " + std::to_string(m));
     pt::build_device_tables(h.host, h.tables);
     h.vertex_extent = pt::vertex_extent(h.host);
-    if (!h.host.tri_uv.empty()) s->texcoords = std::make_shared<const std::vector<float>>(h.host.tri_uv);   // a loaded scene: the OBJ's own
+    if (!h.host.tri_uv.empty()) s->surface.texcoords = std::make_shared<const std::vector<float>>(h.host.tri_uv);   // a loaded scene: the OBJ's own
     if (device >= 0) {
         const int rc = upload(s.get(), device);
         if (rc != PT_OK) return rc;
     }
     *out = s.release();
     return PT_OK;
+}
+
+// The surface tables of the kernel arguments (pt_kernels.hpp: SurfaceUnit).  The rule: the highest table the handle has on its device
+// picks the unit; every slot below it holds the handle's own table where it has one and the all-zero stand-in where it has none (no
+// material is a dielectric or textured, every Ns is N, every glossy lobe is the mirror); every slot above it stays null.
+void bind_surface(const pt_scene &scene, pt::RenderArgs &a) {
+    const SurfaceTables &h = scene.surface;
+    const DeviceSurface &d = scene.d_surface;
+    const bool glass = h.glass && d.glass, tex = h.textures && d.tex_recs, smooth = h.smooth && d.normals, rough = h.rough && d.alpha,
+               direct = h.direct && d.lights;
+    const int unit = direct ? pt::kDirectUnit : rough ? pt::kRoughUnit : smooth ? pt::kSmoothUnit : tex ? pt::kTextureUnit : glass ? pt::kGlassUnit : pt::kNoSurfaceUnit;
+    if (unit >= pt::kGlassUnit) a.glass = (glass ? d.glass : d.no_glass).get<void>();
+    if (unit >= pt::kTextureUnit) {   // (the stand-in marks no material: its coordinates and texels, the table itself, are never read)
+        a.tex_recs = (tex ? d.tex_recs : d.no_tex).get<void>();
+        a.tex_uv = (tex ? d.tex_uv : d.no_tex).get<float>();
+        a.tex_texels = (tex ? d.tex_texels : d.no_tex).get<void>();
+        a.tex_bary = d.bary.get<void>();
+    }
+    if (unit >= pt::kSmoothUnit) a.smooth_normals = (smooth ? d.normals : d.no_normals).get<void>();
+    if (unit >= pt::kRoughUnit) a.rough_alpha = (rough ? d.alpha : d.no_alpha).get<float>();
+    if (unit >= pt::kDirectUnit) {
+        a.lights = d.lights.get<void>();
+        a.n_lights = static_cast<int32_t>(h.direct->lights.size());
+        a.light_area = h.direct->area;
+    }
 }
 
 // The part of the kernel arguments that describes the scene (its tables for the current eps).
@@ -284,50 +305,7 @@ void fill_scene_args(const pt_scene *scene, float eps, pt::RenderArgs &a) {
         a.env_map = scene->d_env.get<void>();
         a.env_n = scene->env->n;
     }
-    if (scene->glass && scene->d_glass) a.glass = scene->d_glass.get<void>();   // the dielectric kernels of whichever kernels the launch is planned as (integrate_kernel_glass)
-    if (scene->textures && scene->d_tex.recs) {   // the texture kernels of those (integrate_kernel_texture); without dielectrics, an all-zero table
-        a.tex_recs = scene->d_tex.recs.get<void>();
-        a.tex_uv = scene->d_tex.uv.get<float>();
-        a.tex_texels = scene->d_tex.texels.get<void>();
-        a.tex_bary = scene->d_tex.bary.get<void>();
-        if (!a.glass) a.glass = scene->d_tex.no_glass.get<void>();
-    }
-    if (scene->smooth && scene->d_smooth.normals) {   // the smooth kernels of those (integrate_kernel_smooth); absent lists as all-zero tables
-        a.smooth_normals = scene->d_smooth.normals.get<void>();
-        if (!a.tex_recs) {   // (no entry is textured: the coordinates and the texels are never read)
-            a.tex_recs = scene->d_smooth.no_tex.get<void>();
-            a.tex_uv = scene->d_smooth.no_tex.get<float>();
-            a.tex_texels = scene->d_smooth.no_tex.get<void>();
-            a.tex_bary = scene->d_smooth.bary.get<void>();
-        }
-        if (!a.glass) a.glass = scene->d_smooth.no_glass.get<void>();
-    }
-    if (scene->rough && scene->d_rough.alpha) {   // the rough kernels of those (integrate_kernel_rough); absent normals and lists as all-zero tables
-        a.rough_alpha = scene->d_rough.alpha.get<float>();
-        if (!a.smooth_normals) a.smooth_normals = scene->d_rough.no_normals.get<void>();   // (all zeros: every Ns is N)
-        if (!a.tex_recs) {
-            a.tex_recs = scene->d_rough.no_tex.get<void>();
-            a.tex_uv = scene->d_rough.no_tex.get<float>();
-            a.tex_texels = scene->d_rough.no_tex.get<void>();
-            a.tex_bary = scene->d_rough.bary.get<void>();
-        }
-        if (!a.glass) a.glass = scene->d_rough.no_glass.get<void>();
-    }
-    if (scene->direct && scene->d_direct.lights) {   // the direct kernels of those (integrate_kernel_direct); absent lists as all-zero tables
-        const DeviceRough &none = scene->d_direct.none;
-        a.lights = scene->d_direct.lights.get<void>();
-        a.n_lights = static_cast<int32_t>(scene->direct->lights.size());
-        a.light_area = scene->direct->area;
-        if (!a.rough_alpha) a.rough_alpha = none.alpha.get<float>();   // (all zeros: every glossy lobe is the mirror)
-        if (!a.smooth_normals) a.smooth_normals = none.no_normals.get<void>();
-        if (!a.tex_recs) {
-            a.tex_recs = none.no_tex.get<void>();
-            a.tex_uv = none.no_tex.get<float>();
-            a.tex_texels = none.no_tex.get<void>();
-            a.tex_bary = none.bary.get<void>();
-        }
-        if (!a.glass) a.glass = none.no_glass.get<void>();
-    }
+    bind_surface(*scene, a);
     a.n_clusters = static_cast<int32_t>(t.clusters.size());
     a.n_tri = scene->shared->host.n_tri();
     a.big = t.big ? 1 : 0;
@@ -395,7 +373,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     pt::RenderArgs a;
     fill_scene_args(scene, p->eps, a);
     // (a handle that answers 1 to get_direct_lighting never renders without its light table)
-    if (scene->direct && !a.lights) return fail(PT_ERR_INVALID_ARGUMENT, "direct lighting: the handle has the switch set and no light table on its device");
+    if (scene->surface.direct && !a.lights) return fail(PT_ERR_INVALID_ARGUMENT, "direct lighting: the handle has the switch set and no light table on its device");
     a.vec_ok = (p->width % 4 == 0) &&
                ((reinterpret_cast<uintptr_t>(planes.sum) | reinterpret_cast<uintptr_t>(planes.sum2) | reinterpret_cast<uintptr_t>(planes.count)) % 16 == 0);
     a.sum = planes.sum;
@@ -452,11 +430,11 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
         PT_HIP_TRY(hipEventRecord(ctx.ev0.get(), stream));
     }
     const hipError_t launched = pt::launch_integrator(a, tiles.variant, stream);
-    if (launched == hipErrorNotSupported && a.lights != nullptr) return fail(PT_ERR_UNSUPPORTED, "direct lighting: this diagnostic build of the library has no direct kernels");
-    if (launched == hipErrorNotSupported && a.rough_alpha != nullptr) return fail(PT_ERR_UNSUPPORTED, "roughness: this diagnostic build of the library has no rough kernels");
-    if (launched == hipErrorNotSupported && a.smooth_normals != nullptr) return fail(PT_ERR_UNSUPPORTED, "shading normals: this diagnostic build of the library has no smooth kernels");
-    if (launched == hipErrorNotSupported && a.tex_recs != nullptr) return fail(PT_ERR_UNSUPPORTED, "textures: this diagnostic build of the library has no texture kernels");
-    if (launched == hipErrorNotSupported && a.glass != nullptr) return fail(PT_ERR_UNSUPPORTED, "dielectrics: this diagnostic build of the library has no dielectric kernels");
+    if (const int unit = pt::surface_unit_of(a); launched == hipErrorNotSupported && unit != pt::kNoSurfaceUnit) {
+        static const char *const kWhat[][2] = {{"dielectrics", "dielectric"}, {"textures", "texture"}, {"shading normals", "smooth"}, {"roughness", "rough"}, {"direct lighting", "direct"}};
+        const char *const *w = kWhat[unit - pt::kGlassUnit];
+        return fail(PT_ERR_UNSUPPORTED, std::string(w[0]) + ": this diagnostic build of the library has no " + w[1] + " kernels");
+    }
     PT_HIP_TRY(launched);
     if (want_stats) PT_HIP_TRY(hipEventRecord(ctx.ev1.get(), stream));
     PT_HIP_TRY(hipEventRecord(ctx.ev_done.get(), stream));
@@ -682,12 +660,7 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
     s->shared = src->shared;   // parsed model, tables, hierarchies built so far
     s->sky = src->sky;         // the skybox of the handle the copy is made from
     s->env = src->env;         // or its environment
-    s->glass = src->glass;     // and its dielectrics
-    s->texcoords = src->texcoords;   // and its texture coordinates and textures
-    s->textures = src->textures;
-    s->smooth = src->smooth;   // and its shading normals
-    s->rough = src->rough;     // and its roughness list
-    s->direct = src->direct;   // and its light table
+    s->surface = src->surface;   // and its dielectrics, texture coordinates and textures, shading normals, roughness list and light table
     s->has_camera = src->has_camera;   // and its camera
     s->camera = src->camera;
     s->has_lens = src->has_lens;       // and lens

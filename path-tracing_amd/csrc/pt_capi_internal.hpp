@@ -1,9 +1,6 @@
-// What the translation units behind the C ABI share (pt_capi.cpp: scenes, sessions, resolve, BMP, post filters; pt_frame.cpp: the
-// multi-device frame; pt_denoise_capi.cpp: first-hit features and the denoiser; pt_temporal_capi.cpp, pt_upsample_capi.cpp,
-// pt_grade_capi.cpp, pt_bloom_capi.cpp, pt_local_capi.cpp, pt_colour_capi.cpp, pt_optics_capi.cpp, pt_sharpen_capi.cpp: one image-space stage each; pt_grain_capi.cpp: grain and dither, the host chain's last step; pt_linear_capi.cpp: scene-linear output; pt_display_capi.cpp: the device-resident
-// display path, which chains them): the handles' types, the checks whose message every entry point shares, each stage's parameters into its launch
-// arguments, the plane views of pt_device_mem.hpp -- the owners of everything held on a device -- into the same arguments, and the timed region
-// of a one-shot entry point.
+// What the translation units behind the C ABI share: the handles' types, the checks and the setter skeletons whose message every entry
+// point shares, each stage's parameters into its launch arguments, the plane views of pt_device_mem.hpp -- the owners of everything held
+// on a device -- into the same arguments, and the timed region of a one-shot entry point.
 // Nothing here is part of the ABI.
 #pragma once
 #include "../../include/pt_hip.h"
@@ -83,28 +80,12 @@ struct pt_texture_list {
     std::vector<pt::TexRec> recs;
     std::vector<pt::TexTexel> pool;
 };
-// Their device copies: table, coordinates, texels, and the all-zero dielectric table a textured handle without dielectrics passes.
-struct DeviceTextures {
-    ptc::DeviceBuffer recs, uv, texels, no_glass, bary;   // (bary: the barycentrics' record of every triangle, pt_texture.hpp: TexBary)
-};
-
-// The shading normals of a handle (pt_hip.h: shading normals) on its device: three 16-byte records per triangle in the original order
-// (pt_smooth.hpp: SmoothCorner), the barycentrics' record of every triangle, and the all-zero texture and dielectric tables a handle
-// without a texture list or dielectrics passes to the smooth kernels.
-struct DeviceSmooth {
-    ptc::DeviceBuffer normals, bary, no_tex, no_glass;
-};
 
 // The roughness list of a handle (pt_hip.h: rough specular): the list as given and the per-material table the kernels read (one alpha
 // per material of the scene, 0 = the mirror).  Belongs to the handle as the dielectrics do; immutable once set.
 struct pt_rough_list {
     std::vector<pt_rough> list;
     std::vector<float> table;
-};
-// Its device copy, and what a handle without shading normals, textures or dielectrics passes to the rough kernels: all-zero corner
-// normals ("use N"), the barycentrics' record of every triangle and all-zero texture and dielectric tables.
-struct DeviceRough {
-    ptc::DeviceBuffer alpha, no_normals, bary, no_tex, no_glass;
 };
 
 // The light table of a handle with direct lighting on (pt_hip.h: direct lighting): the lights in the original triangle order and the
@@ -113,10 +94,24 @@ struct pt_light_table {
     std::vector<pt::LightRec> lights;
     float area = 0.0f;
 };
-// Its device copy, and what a handle without a roughness list, shading normals, textures or dielectrics passes to the direct kernels.
-struct DeviceDirect {
-    ptc::DeviceBuffer lights;
-    DeviceRough none;
+
+// The tables of a handle that the integrator reads only where a ray has hit a surface.  The host side: each
+// nullptr = none, immutable once set, and a copy of the handle inherits all of them (a loaded scene has the OBJ's texcoords).
+struct SurfaceTables {
+    std::shared_ptr<const pt_glass_list> glass;              // dielectrics
+    std::shared_ptr<const std::vector<float>> texcoords;     // 6 floats per triangle
+    std::shared_ptr<const pt_texture_list> textures;         // only with texcoords
+    std::shared_ptr<const std::vector<float>> smooth;        // shading normals, 9 floats per triangle
+    std::shared_ptr<const pt_rough_list> rough;
+    std::shared_ptr<const pt_light_table> direct;            // the light table: direct lighting is on
+};
+// The same on the handle's device: one buffer per table that is set, and what stands in for the absent ones below the highest that is
+// set (bind_surface) -- the barycentrics' record of every triangle (pt_texture.hpp: TexBary), which every unit from the texture
+// kernels up reads, and all-zero tables: no material is a dielectric, none is textured, every Ns is N, every glossy lobe is the mirror.
+// The stand-ins depend on the scene's immutable tables alone: each is uploaded once, when first needed, and never replaced.
+struct DeviceSurface {
+    ptc::DeviceBuffer glass, tex_recs, tex_uv, tex_texels, normals, alpha, lights;
+    ptc::DeviceBuffer bary, no_glass, no_tex, no_normals, no_alpha;
 };
 
 // Device copy of one CullTables (they depend on eps and on the envelope the camera needs; a scene keeps the one of its last
@@ -153,17 +148,8 @@ struct pt_scene {
     int sky_w = 0, sky_h = 0;
     std::shared_ptr<const pt_env_map> env;      // this handle's environment (nullptr = none; never with a skybox); copies inherit it
     ptc::DeviceBuffer d_env;       // its (n + 2)^2 texels with the apron (pt_environment.hpp: EnvTexel) on this copy's device
-    std::shared_ptr<const pt_glass_list> glass; // this handle's dielectrics (nullptr = none); copies inherit them
-    ptc::DeviceBuffer d_glass;     // their table on this copy's device
-    std::shared_ptr<const std::vector<float>> texcoords;   // this handle's texture coordinates (nullptr = none; a loaded scene has the OBJ's); copies inherit them
-    std::shared_ptr<const pt_texture_list> textures;       // this handle's textures (nullptr = none; only with texcoords); copies inherit them
-    DeviceTextures d_tex;          // both on this copy's device, uploaded when a list is set
-    std::shared_ptr<const std::vector<float>> smooth;   // this handle's shading normals, 9 per triangle (nullptr = none); copies inherit them
-    DeviceSmooth d_smooth;         // on this copy's device
-    std::shared_ptr<const pt_rough_list> rough;   // this handle's roughness list (nullptr = none); copies inherit it
-    DeviceRough d_rough;           // on this copy's device
-    std::shared_ptr<const pt_light_table> direct;   // this handle's light table (nullptr = direct lighting off); copies inherit it
-    DeviceDirect d_direct;         // on this copy's device
+    SurfaceTables surface;         // this handle's dielectrics, textures, shading normals, roughness list and light table; copies inherit them
+    DeviceSurface d_surface;       // the same on this copy's device
     bool has_camera = false;       // this handle's camera (pt_scene_set_camera); copies made from it inherit it
     pt_camera camera{};
     bool has_lens = false;         // this handle's lens (pt_scene_set_lens; radius > 0); copies made from it inherit it
@@ -446,71 +432,77 @@ void temporal_commit(pt_temporal *t);
 
 // What a display needs of a frame: gathers if a band changed and waits, as pt_frame_read does; then the root device's copy of
 // the scene, its full-frame planes and the root band's stream.
-// Every device's copy of a frame's scene (owned by the frame), for the setters that live outside pt_frame.cpp (pt_environment_capi.cpp, pt_glass_capi.cpp).
+// Every device's copy of a frame's scene (owned by the frame), for the setters that live outside pt_frame.cpp.
 const std::vector<pt_scene *> &frame_scenes(pt_frame *f);
 int frame_root_planes(pt_frame *f, pt_scene **scene, AccumPlanes *planes, hipStream_t *stream, int32_t *width, int32_t *height);
 
-// A handle's textures onto the current device (the setters of pt_texture_capi.cpp; a clone's upload in pt_capi.cpp): the table, the
-// coordinates, the texels, the barycentrics' record of every triangle (in the original order) and an all-zero dielectric table.  `out` is only written once every upload has succeeded.
+// A setter on one handle or on every device's copy of a frame's scene, all or nothing: prepare() makes the host object once (and
+// refuses what the handles do not allow), upload(i) puts it on copy i's device -- made current here -- into storage of its own, and
+// only when every copy has it, and no launch in flight can still read the old one, does commit(i) change handle i.
+template <class Prepare, class Upload, class Commit>
+int set_on_copies(pt_scene *const *scenes, size_t n, Prepare &&prepare, Upload &&upload, Commit &&commit) {
+    for (size_t i = 0; i < n; ++i)
+        if (!scenes[i]) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    int rc = prepare();
+    if (rc != PT_OK) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        if (scenes[i]->device < 0) continue;
+        PT_HIP_TRY(hipSetDevice(scenes[i]->device));
+        if ((rc = upload(i)) != PT_OK) return rc;
+        PT_HIP_TRY(hipDeviceSynchronize());
+    }
+    for (size_t i = 0; i < n; ++i) commit(i);
+    return PT_OK;
+}
+// A pt_frame_* entry point of those setters and of their getters: f(copies, count) on every device's copy of the frame's scene, or
+// f(root) on the first.
+template <class F>
+int on_frame(pt_frame *frame, F &&f) {
+    return guarded([&] {
+        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
+        const std::vector<pt_scene *> &sc = frame_scenes(frame);
+        return f(sc.data(), sc.size());
+    });
+}
+template <class F>
+int on_frame_root(pt_frame *frame, F &&f) {
+    return on_frame(frame, [&](pt_scene *const *sc, size_t) { return f(sc[0]); });
+}
+
 inline std::vector<pt::TexBary> texture_bary_records(const std::vector<pt::ExactRec> &exact) {
     std::vector<pt::TexBary> out(exact.size());
     for (size_t i = 0; i < exact.size(); ++i) out[i] = pt::tex_bary_record(exact[i].v0, exact[i].v1, exact[i].v2);
     return out;
 }
-inline int upload_textures(const pt_texture_list &list, const std::vector<float> &texcoords, const pt::DeviceTables &tables, DeviceTextures &out) {
-    DeviceTextures d;
-    int rc;
-    const std::vector<pt::GlassRec> zeros(tables.mats.size(), pt::GlassRec{});
-    if ((rc = d.bary.upload(texture_bary_records(tables.exact), "texture barycentric records", 64)) != PT_OK) return rc;
-    if ((rc = d.recs.upload(list.recs, "texture table", 64)) != PT_OK || (rc = d.uv.upload(texcoords, "texture coordinates", 64)) != PT_OK ||
-        (rc = d.texels.upload(list.pool, "texels", 64)) != PT_OK || (rc = d.no_glass.upload(zeros, "empty dielectric table", 64)) != PT_OK)
-        return rc;
-    out = std::move(d);
-    return PT_OK;
-}
-
-// A handle's shading normals onto the current device (the setters of pt_smooth_capi.cpp; a clone's upload in pt_capi.cpp).  `out` is
-// only written once every upload has succeeded.
-inline int upload_smooth(const std::vector<float> &n9, const pt::DeviceTables &tables, DeviceSmooth &out) {
-    DeviceSmooth d;
-    int rc;
-    std::vector<pt::SmoothCorner> corners(n9.size() / 3);
-    for (size_t i = 0; i < corners.size(); ++i) corners[i] = pt::SmoothCorner{n9[3 * i], n9[3 * i + 1], n9[3 * i + 2], 0.0f};
-    const std::vector<pt::GlassRec> no_glass(tables.mats.size(), pt::GlassRec{});
-    const std::vector<pt::TexRec> no_tex(tables.mats.size(), pt::TexRec{0, 0, 0, 0});
-    if ((rc = d.normals.upload(corners, "shading normals", 64)) != PT_OK || (rc = d.bary.upload(texture_bary_records(tables.exact), "barycentric records", 64)) != PT_OK ||
-        (rc = d.no_tex.upload(no_tex, "empty texture table", 64)) != PT_OK || (rc = d.no_glass.upload(no_glass, "empty dielectric table", 64)) != PT_OK)
-        return rc;
-    out = std::move(d);
-    return PT_OK;
-}
-
-// A handle's roughness table onto the current device (the setters of pt_rough_capi.cpp; a clone's upload in pt_capi.cpp).  `out` is
-// only written once every upload has succeeded.
-inline int upload_rough(const std::vector<float> &alpha, const pt::DeviceTables &tables, DeviceRough &out) {
-    DeviceRough d;
-    int rc;
-    const std::vector<pt::SmoothCorner> no_normals(3 * tables.exact.size(), pt::SmoothCorner{0.0f, 0.0f, 0.0f, 0.0f});
-    const std::vector<pt::GlassRec> no_glass(tables.mats.size(), pt::GlassRec{});
-    const std::vector<pt::TexRec> no_tex(tables.mats.size(), pt::TexRec{0, 0, 0, 0});
-    if ((rc = d.alpha.upload(alpha, "roughness table", 64)) != PT_OK || (rc = d.no_normals.upload(no_normals, "empty shading normals", 64)) != PT_OK ||
-        (rc = d.bary.upload(texture_bary_records(tables.exact), "barycentric records", 64)) != PT_OK ||
-        (rc = d.no_tex.upload(no_tex, "empty texture table", 64)) != PT_OK || (rc = d.no_glass.upload(no_glass, "empty dielectric table", 64)) != PT_OK)
-        return rc;
-    out = std::move(d);
-    return PT_OK;
-}
-
-// A handle's light table onto the current device, with the all-zero tables of upload_rough (the setters of pt_direct_capi.cpp; a
-// clone's upload in pt_capi.cpp).  `out` is only written once every upload has succeeded.
-inline int upload_direct(const pt_light_table &table, const pt::DeviceTables &tables, DeviceDirect &out) {
-    DeviceDirect d;
-    int rc;
-    if ((rc = d.lights.upload(table.lights, "light table", 64)) != PT_OK ||
-        (rc = upload_rough(std::vector<float>(tables.mats.size(), 0.0f), tables, d.none)) != PT_OK)
-        return rc;
-    out = std::move(d);
-    return PT_OK;
+// The one upload path of surface tables: every table `t` holds onto the current device, into `out`, and into `kept` those stand-ins
+// that the highest of them reads and `kept` does not hold yet (no launch in flight reads a buffer this adds).  A setter gives its
+// new table alone, storage of its own and the handle's `kept`; a new handle's upload gives all of its tables and its own buffers twice.
+inline int upload_surface(const SurfaceTables &t, const pt::DeviceTables &tables, DeviceSurface &out, DeviceSurface &kept) {
+    const int unit = t.direct ? pt::kDirectUnit : t.rough ? pt::kRoughUnit : t.smooth ? pt::kSmoothUnit : t.textures ? pt::kTextureUnit : pt::kNoSurfaceUnit;
+    const size_t n_mat = tables.mats.size(), n_tri = tables.exact.size();
+    int rc = PT_OK;
+    const auto put = [&rc](ptc::DeviceBuffer &b, const auto &v, const char *what) {
+        if (rc == PT_OK) rc = b.upload(v, what, 64);
+    };
+    if (unit >= pt::kTextureUnit && !kept.bary) put(kept.bary, texture_bary_records(tables.exact), "barycentric records");
+    if (unit >= pt::kTextureUnit && !kept.no_glass) put(kept.no_glass, std::vector<pt::GlassRec>(n_mat, pt::GlassRec{}), "empty dielectric table");
+    if (unit >= pt::kSmoothUnit && !kept.no_tex) put(kept.no_tex, std::vector<pt::TexRec>(n_mat, pt::TexRec{0, 0, 0, 0}), "empty texture table");
+    if (unit >= pt::kRoughUnit && !kept.no_normals) put(kept.no_normals, std::vector<pt::SmoothCorner>(3 * n_tri, pt::SmoothCorner{0.0f, 0.0f, 0.0f, 0.0f}), "empty shading normals");
+    if (unit >= pt::kDirectUnit && !kept.no_alpha) put(kept.no_alpha, std::vector<float>(n_mat, 0.0f), "empty roughness table");
+    if (t.glass) put(out.glass, t.glass->table, "dielectric table");
+    if (t.textures) {
+        put(out.tex_recs, t.textures->recs, "texture table");
+        put(out.tex_uv, *t.texcoords, "texture coordinates");
+        put(out.tex_texels, t.textures->pool, "texels");
+    }
+    if (t.smooth) {
+        std::vector<pt::SmoothCorner> corners(t.smooth->size() / 3);
+        for (size_t i = 0; i < corners.size(); ++i) corners[i] = pt::SmoothCorner{(*t.smooth)[3 * i], (*t.smooth)[3 * i + 1], (*t.smooth)[3 * i + 2], 0.0f};
+        put(out.normals, corners, "shading normals");
+    }
+    if (t.rough) put(out.alpha, t.rough->table, "roughness table");
+    if (t.direct) put(out.lights, t.direct->lights, "light table");
+    return rc;
 }
 // Whether material `m` is what the light table takes its lights from: the single emissive lobe.
 inline bool material_is_light(const pt::MatRec &m) { return m.n_lobes == 1 && m.kind0 == 0; }

@@ -6,6 +6,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "pt_host_math.hpp"
+
 using ptc::fail;
 using ptc::guarded;
 
@@ -55,52 +57,46 @@ std::shared_ptr<pt_light_table> build_table(const pt::DeviceTables &tables) {
 
 // One handle or every device's copy of a frame's scene (copies of one scene: the same triangles and materials).
 int set_impl(pt_scene *const *scenes, size_t n_scenes, int32_t on) {
-    for (size_t i = 0; i < n_scenes; ++i)
-        if (!scenes[i]) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
-    std::shared_ptr<pt_light_table> t;
-    if (on) {
-        t = build_table(scenes[0]->shared->tables);
-        if (t->lights.empty() || !(t->area > 0.0f) || !std::isfinite(t->area)) return refuse("the scene has no light (a triangle of non-zero area whose material is the emissive lobe alone)");
-        const std::vector<pt::MatRec> &mats = scenes[0]->shared->tables.mats;
-        for (size_t i = 0; i < n_scenes; ++i) {   // (every copy's own textures: a frame's copies may have been given different ones)
-            if (!scenes[i]->textures) continue;
-            for (size_t m = 0; m < mats.size(); ++m)
-                if (ptc::material_is_light(mats[m]) && scenes[i]->textures->recs[m].w != 0)
-                    return refuse("emissive material " + std::to_string(m) + " is in the texture list");
-        }
-    }
-    std::vector<DeviceDirect> fresh(n_scenes);
-    for (size_t i = 0; i < n_scenes; ++i) {
-        if (scenes[i]->device < 0) continue;
-        PT_HIP_TRY(hipSetDevice(scenes[i]->device));
-        int rc;
-        if (t && (rc = ptc::upload_direct(*t, scenes[i]->shared->tables, fresh[i])) != PT_OK) return rc;
-        PT_HIP_TRY(hipDeviceSynchronize());   // (a launch in flight may still read the old table)
-    }
-    for (size_t i = 0; i < n_scenes; ++i) {
-        scenes[i]->d_direct = std::move(fresh[i]);
-        scenes[i]->direct = t;
-    }
-    return PT_OK;
+    SurfaceTables made;
+    std::vector<DeviceSurface> fresh(n_scenes);
+    return ptc::set_on_copies(
+        scenes, n_scenes,
+        [&] {
+            if (!on) return static_cast<int>(PT_OK);
+            const std::shared_ptr<pt_light_table> t = build_table(scenes[0]->shared->tables);
+            if (t->lights.empty() || !(t->area > 0.0f) || !std::isfinite(t->area)) return refuse("the scene has no light (a triangle of non-zero area whose material is the emissive lobe alone)");
+            const std::vector<pt::MatRec> &mats = scenes[0]->shared->tables.mats;
+            for (size_t i = 0; i < n_scenes; ++i) {   // (every copy's own textures: a frame's copies may have been given different ones)
+                if (!scenes[i]->surface.textures) continue;
+                for (size_t m = 0; m < mats.size(); ++m)
+                    if (ptc::material_is_light(mats[m]) && scenes[i]->surface.textures->recs[m].w != 0)
+                        return refuse("emissive material " + std::to_string(m) + " is in the texture list");
+            }
+            made.direct = t;
+            return static_cast<int>(PT_OK);
+        },
+        [&](size_t i) { return ptc::upload_surface(made, scenes[i]->shared->tables, fresh[i], scenes[i]->d_surface); },
+        [&](size_t i) {
+            scenes[i]->d_surface.lights = std::move(fresh[i].lights);
+            scenes[i]->surface.direct = made.direct;
+        });
 }
 
 int get_impl(const pt_scene *scene, int32_t *on) {
     if (!scene || !on) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    *on = scene->direct ? 1 : 0;
+    *on = scene->surface.direct ? 1 : 0;
     return PT_OK;
 }
 
 int lights_impl(const pt_scene *scene, pt_light *lights, int32_t *n, float *area) {
     if (!scene || !n) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    std::shared_ptr<const pt_light_table> t = scene->direct;
+    std::shared_ptr<const pt_light_table> t = scene->surface.direct;
     if (!t) t = build_table(scene->shared->tables);   // (what the switch would build)
     *n = static_cast<int32_t>(t->lights.size());
     if (area) *area = t->area;
     if (lights && !t->lights.empty()) std::memcpy(lights, t->lights.data(), t->lights.size() * sizeof(pt_light));
     return PT_OK;
 }
-
-float host_unit_float(uint32_t w) { return static_cast<float>(((w >> 9) << 1) | 1u) * 5.9604644775390625e-08f; }
 
 }  // namespace
 
@@ -119,25 +115,15 @@ int pt_scene_get_lights(const pt_scene *scene, pt_light *lights, int32_t *n, flo
 }
 
 int pt_frame_set_direct_lighting(pt_frame *frame, int32_t on) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_impl(sc.data(), sc.size(), on);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_impl(sc, n_sc, on); });
 }
 
 int pt_frame_get_direct_lighting(pt_frame *frame, int32_t *on) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        return get_impl(ptc::frame_scenes(frame)[0], on);
-    });
+    return ptc::on_frame_root(frame, [&](const pt_scene *root) { return get_impl(root, on); });
 }
 
 int pt_frame_get_lights(pt_frame *frame, pt_light *lights, int32_t *n, float *area) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        return lights_impl(ptc::frame_scenes(frame)[0], lights, n, area);
-    });
+    return ptc::on_frame_root(frame, [&](const pt_scene *root) { return lights_impl(root, lights, n, area); });
 }
 
 int pt_direct_term(int32_t n, const pt_light *lights, int32_t n_lights, float area, const float *origins, const float *normals,
@@ -150,15 +136,12 @@ int pt_direct_term(int32_t n, const pt_light *lights, int32_t n_lights, float ar
             return refuse("null argument");
         const pt::LightRec *table = reinterpret_cast<const pt::LightRec *>(lights);
         for (int32_t i = 0; i < n; ++i) {
-            const int32_t li = pt::direct_pick(table, n_lights, host_unit_float(l0[i]));
+            const int32_t li = pt::direct_pick(table, n_lights, ptc::host_unit_float(l0[i]));
             const float *o = origins + 3 * i, *N = normals + 3 * i, *s = shading_normals + 3 * i, *t = throughput + 3 * i, *k = kd + 3 * i;
             float *p = out_points + 3 * i, *w = out_directions + 3 * i, *c = out_terms + 3 * i;
-            const bool has = pt::direct_term(table[li], area, host_unit_float(l1[i]), host_unit_float(l2[i]), o[0], o[1], o[2], N[0], N[1], N[2], s[0], s[1],
+            const bool has = pt::direct_term(table[li], area, ptc::host_unit_float(l1[i]), ptc::host_unit_float(l2[i]), o[0], o[1], o[2], N[0], N[1], N[2], s[0], s[1],
                                              s[2], t[0], t[1], t[2], k[0], k[1], k[2],
-                                             [](float &x, float &y, float &z) {
-                                                 const float inv = 1.0f / std::sqrt((x * x + y * y) + z * z);
-                                                 x = x * inv; y = y * inv; z = z * inv;
-                                             },
+                                             ptc::host_normalize3,
                                              p[0], p[1], p[2], w[0], w[1], w[2], c[0], c[1], c[2]);
             out_light[i] = li;
             out_has_term[i] = has ? 1 : 0;

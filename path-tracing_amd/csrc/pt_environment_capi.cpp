@@ -322,34 +322,19 @@ int pt_scene_get_environment(const pt_scene *scene, int32_t *n, float *rgb) {
 
 // The same on a frame: every device's copy of its scene takes the map, which is read and converted once.
 int pt_frame_set_environment_file(pt_frame *frame, const char *path, const pt_environment_params *params) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_file_impl(sc.data(), sc.size(), path, params);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_file_impl(sc, n_sc, path, params); });
 }
 
 int pt_frame_set_environment_equirect(pt_frame *frame, int32_t w, int32_t h, const float *rgb, const pt_environment_params *params) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_equirect_impl(sc.data(), sc.size(), w, h, rgb, params);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_equirect_impl(sc, n_sc, w, h, rgb, params); });
 }
 
 int pt_frame_set_environment_map(pt_frame *frame, int32_t n, const float *rgb) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_map_impl(sc.data(), sc.size(), n, rgb);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_map_impl(sc, n_sc, n, rgb); });
 }
 
 int pt_frame_get_environment(pt_frame *frame, int32_t *n, float *rgb) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        return get_impl(ptc::frame_scenes(frame)[0], n, rgb);
-    });
+    return ptc::on_frame_root(frame, [&](const pt_scene *root) { return get_impl(root, n, rgb); });
 }
 
 int pt_environment_from_equirect(int32_t w, int32_t h, const float *rgb, const pt_environment_params *params, int32_t n, float *map_rgb) {

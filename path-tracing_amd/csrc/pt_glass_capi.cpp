@@ -32,8 +32,8 @@ int make_list(const pt_scene *scene, const pt_dielectric *list, int32_t n, std::
             if (!std::isfinite(t) || t < 0.0f || t > 1.0f) return refuse(who + "a tint component must lie in 0 .. 1");
         const pt::MatRec &m = mats[d.material];
         if ((m.n_lobes >= 1 && m.kind0 == 0) || (m.n_lobes >= 2 && m.kind1 == 0)) return refuse(who + "material " + std::to_string(d.material) + " has an emissive lobe");
-        if (scene->textures && scene->textures->recs[d.material].w != 0) return refuse(who + "material " + std::to_string(d.material) + " is textured");
-        if (scene->rough && scene->rough->table[d.material] != 0.0f) return refuse(who + "material " + std::to_string(d.material) + " is in the roughness list");
+        if (scene->surface.textures && scene->surface.textures->recs[d.material].w != 0) return refuse(who + "material " + std::to_string(d.material) + " is textured");
+        if (scene->surface.rough && scene->surface.rough->table[d.material] != 0.0f) return refuse(who + "material " + std::to_string(d.material) + " is in the roughness list");
         pt::GlassRec &r = g->table[d.material];
         if (r.ior != 0.0f) return refuse(who + "material " + std::to_string(d.material) + " is listed twice");
         r.ior = d.ior;
@@ -45,32 +45,29 @@ int make_list(const pt_scene *scene, const pt_dielectric *list, int32_t n, std::
     return PT_OK;
 }
 
-// One handle or every device's copy of a frame's scene (copies of one scene: the same materials).  The list is made once, every
-// device's table is uploaded, and only then do the handles change.
+// One handle or every device's copy of a frame's scene (copies of one scene: the same materials): ptc::set_on_copies.
 int set_impl(pt_scene *const *scenes, size_t n_scenes, const pt_dielectric *list, int32_t n) {
-    for (size_t i = 0; i < n_scenes; ++i)
-        if (!scenes[i]) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
-    std::shared_ptr<pt_glass_list> g;
-    int rc = make_list(scenes[0], list, n, g);
-    if (rc != PT_OK) return rc;
-    std::vector<ptc::DeviceBuffer> fresh(n_scenes);
-    for (size_t i = 0; i < n_scenes; ++i) {
-        if (scenes[i]->device < 0) continue;
-        PT_HIP_TRY(hipSetDevice(scenes[i]->device));
-        if (g && (rc = fresh[i].upload(g->table, "dielectric table", 64)) != PT_OK) return rc;
-        PT_HIP_TRY(hipDeviceSynchronize());   // (a launch in flight may still read the old table)
-    }
-    for (size_t i = 0; i < n_scenes; ++i) {
-        scenes[i]->d_glass = std::move(fresh[i]);
-        scenes[i]->glass = g;
-    }
-    return PT_OK;
+    SurfaceTables made;
+    std::vector<DeviceSurface> fresh(n_scenes);
+    return ptc::set_on_copies(
+        scenes, n_scenes,
+        [&] {
+            std::shared_ptr<pt_glass_list> g;
+            const int rc = make_list(scenes[0], list, n, g);
+            made.glass = std::move(g);
+            return rc;
+        },
+        [&](size_t i) { return ptc::upload_surface(made, scenes[i]->shared->tables, fresh[i], scenes[i]->d_surface); },
+        [&](size_t i) {
+            scenes[i]->d_surface.glass = std::move(fresh[i].glass);
+            scenes[i]->surface.glass = made.glass;
+        });
 }
 
 int get_impl(const pt_scene *scene, pt_dielectric *list, int32_t *n) {
     if (!scene || !n) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    *n = scene->glass ? static_cast<int32_t>(scene->glass->list.size()) : 0;
-    if (list && scene->glass) std::memcpy(list, scene->glass->list.data(), scene->glass->list.size() * sizeof(pt_dielectric));
+    *n = scene->surface.glass ? static_cast<int32_t>(scene->surface.glass->list.size()) : 0;
+    if (list && scene->surface.glass) std::memcpy(list, scene->surface.glass->list.data(), scene->surface.glass->list.size() * sizeof(pt_dielectric));
     return PT_OK;
 }
 
@@ -87,18 +84,11 @@ int pt_scene_get_dielectrics(const pt_scene *scene, pt_dielectric *list, int32_t
 }
 
 int pt_frame_set_dielectrics(pt_frame *frame, const pt_dielectric *list, int32_t n) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_impl(sc.data(), sc.size(), list, n);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_impl(sc, n_sc, list, n); });
 }
 
 int pt_frame_get_dielectrics(pt_frame *frame, pt_dielectric *list, int32_t *n) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        return get_impl(ptc::frame_scenes(frame)[0], list, n);
-    });
+    return ptc::on_frame_root(frame, [&](const pt_scene *root) { return get_impl(root, list, n); });
 }
 
 }  // extern "C"

@@ -1486,6 +1486,13 @@ __global__ __launch_bounds__(kBlock, (projection_waves<SKY, BIG, STATS, ENV, NAR
 #include "pt_integrator_body.inc"
 }
 
+// launch_surface_integrator's five halves: each surface unit's translation unit defines its own
+template <int UNIT>
+hipError_t launch_surface_unit(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+#define PT_UNIT_HALF(U) template <> hipError_t launch_surface_unit<U>(const RenderArgs &, const plan::Variant &, hipStream_t);
+PT_UNIT_HALF(kGlassUnit) PT_UNIT_HALF(kTextureUnit) PT_UNIT_HALF(kSmoothUnit) PT_UNIT_HALF(kRoughUnit) PT_UNIT_HALF(kDirectUnit)
+#undef PT_UNIT_HALF
+
 #ifdef PT_ENVIRONMENT_UNIT
 // ---------------------------------------------------------------------------------------------------------------
 // The environment kernels (pt_environment_kernels.hip: this file compiled with PT_ENVIRONMENT_UNIT, a translation unit of its own,
@@ -1530,35 +1537,22 @@ hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Var
     hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
     return hipGetLastError();
 }
-#elif defined(PT_GLASS_UNIT) || defined(PT_TEXTURE_UNIT) || defined(PT_SMOOTH_UNIT) || defined(PT_ROUGH_UNIT) || defined(PT_DIRECT_UNIT)
-// (PT_TEXTURE_UNIT -- pt_texture_kernels.hip -- compiles this same section once more, as integrate_kernel_texture: the dielectric
-// kernels' set of instantiations with TEX = true as well, see below the dielectric kernels' own description; PT_SMOOTH_UNIT --
-// pt_smooth_kernels.hip -- a third time, as integrate_kernel_smooth: the texture kernels' set with SMOOTH = true as well;
-// PT_ROUGH_UNIT -- pt_rough_kernels.hip -- a fourth time, as integrate_kernel_rough: the smooth kernels' set with ROUGH = true as well;
-// PT_DIRECT_UNIT -- pt_direct_kernels.hip -- a fifth time, as integrate_kernel_direct: the rough kernels' set with DIRECT = true as well)
-#if defined(PT_DIRECT_UNIT)
-#define PT_UNIT_KERNEL integrate_kernel_direct
-#define PT_UNIT_LAUNCH launch_direct_integrator
-constexpr bool kUnitTex = true, kUnitSmooth = true, kUnitRough = true, kUnitDirect = true;
-#elif defined(PT_ROUGH_UNIT)
-#define PT_UNIT_KERNEL integrate_kernel_rough
-#define PT_UNIT_LAUNCH launch_rough_integrator
-constexpr bool kUnitTex = true, kUnitSmooth = true, kUnitRough = true, kUnitDirect = false;
-#elif defined(PT_SMOOTH_UNIT)
-#define PT_UNIT_KERNEL integrate_kernel_smooth
-#define PT_UNIT_LAUNCH launch_smooth_integrator
-constexpr bool kUnitTex = true, kUnitSmooth = true, kUnitRough = false, kUnitDirect = false;
-#elif defined(PT_TEXTURE_UNIT)
-#define PT_UNIT_KERNEL integrate_kernel_texture
-#define PT_UNIT_LAUNCH launch_texture_integrator
-constexpr bool kUnitTex = true, kUnitSmooth = false, kUnitRough = false, kUnitDirect = false;
-#else
-#define PT_UNIT_KERNEL integrate_kernel_glass
-#define PT_UNIT_LAUNCH launch_glass_integrator
-constexpr bool kUnitTex = false, kUnitSmooth = false, kUnitRough = false, kUnitDirect = false;
-#endif
+#elif defined(PT_SURFACE_UNIT)
+// A surface unit (pt_kernels.hpp: SurfaceUnit; pt_glass_kernels.hip ... pt_direct_kernels.hip each compile this file with its number as
+// PT_SURFACE_UNIT): this one section, as integrate_kernel_<name>, with the flag of every unit up to this one on.
+#define PT_UNIT_NAME_1 glass
+#define PT_UNIT_NAME_2 texture
+#define PT_UNIT_NAME_3 smooth
+#define PT_UNIT_NAME_4 rough
+#define PT_UNIT_NAME_5 direct
+#define PT_PASTE_(a, b) a##b
+#define PT_PASTE(a, b) PT_PASTE_(a, b)
+#define PT_UNIT_KERNEL PT_PASTE(integrate_kernel_, PT_PASTE(PT_UNIT_NAME_, PT_SURFACE_UNIT))
+static_assert(PT_SURFACE_UNIT >= kGlassUnit && PT_SURFACE_UNIT <= kDirectUnit, "PT_SURFACE_UNIT: a SurfaceUnit");
+constexpr bool kUnitTex = PT_SURFACE_UNIT >= kTextureUnit, kUnitSmooth = PT_SURFACE_UNIT >= kSmoothUnit, kUnitRough = PT_SURFACE_UNIT >= kRoughUnit,
+               kUnitDirect = PT_SURFACE_UNIT >= kDirectUnit;
 // ---------------------------------------------------------------------------------------------------------------
-// The dielectric kernels (pt_glass_kernels.hip: this file compiled with PT_GLASS_UNIT, a translation unit of its own).  The body
+// The dielectric kernels (pt_glass_kernels.hip: this file compiled with PT_SURFACE_UNIT 1, a translation unit of its own).  The body
 // with GLASS = true: a hit on a material the handle's table marks (RenderArgs::glass, pt_hip.h: pt_dielectric) reflects or refracts.
 // One per kernel a launch can be planned as, and VIEW (plan views 0 .. 4 and 5 = the projection kernel of view 1):
 //   MISS  0 = no miss shader, 1 = skybox, 2 = environment (the body with SKY and ENVMAP as in integrate_kernel_environment)
@@ -1670,11 +1664,11 @@ template <int... I>
 std::array<Kernel, sizeof...(I)> glass_kernel_table(std::integer_sequence<int, I...>) { return {glass_kernel_of<I>()...}; }
 const auto kGlassKernels = glass_kernel_table(std::make_integer_sequence<int, kGlassPerView * kGlassViews>());
 }  // namespace
-hipError_t PT_UNIT_LAUNCH(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
-    if (kUnitDirect != (args.lights != nullptr) || (kUnitDirect && args.n_lights <= 0)) return hipErrorInvalidValue;
-    if (kUnitRough != (args.rough_alpha != nullptr)) return hipErrorInvalidValue;
-    if (kUnitSmooth != (args.smooth_normals != nullptr)) return hipErrorInvalidValue;
-    if (kUnitTex != (args.tex_recs != nullptr) || (kUnitTex && (args.tex_uv == nullptr || args.tex_texels == nullptr || args.tex_bary == nullptr))) return hipErrorInvalidValue;
+template <>
+hipError_t launch_surface_unit<PT_SURFACE_UNIT>(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
+    if (surface_unit_of(args) != PT_SURFACE_UNIT || (kUnitDirect && args.n_lights <= 0)) return hipErrorInvalidValue;
+    if ((kUnitRough && args.rough_alpha == nullptr) || (kUnitSmooth && args.smooth_normals == nullptr)) return hipErrorInvalidValue;
+    if (kUnitTex && (args.tex_recs == nullptr || args.tex_uv == nullptr || args.tex_texels == nullptr || args.tex_bary == nullptr)) return hipErrorInvalidValue;
     if (args.glass == nullptr || (args.env_map != nullptr && (!v.sky || args.sky != nullptr))) return hipErrorInvalidValue;
     if (args.projection != 0 && v.view != 1) return hipErrorInvalidDeviceFunction;
     const int view = args.projection != 0 ? 5 : v.view;
@@ -1685,7 +1679,6 @@ hipError_t PT_UNIT_LAUNCH(const RenderArgs &args, const plan::Variant &v, hipStr
     return hipGetLastError();
 }
 #undef PT_UNIT_KERNEL
-#undef PT_UNIT_LAUNCH
 #else
 // First-hit feature pass under a projection (pt_hip.h: pt_render_features_host): the ray pt_projection states for pixel (x, y) with
 // jitter 0, for launch_trace_rays.  (Here and not beside the pinhole's feature_rays_kernel in pt_denoise.hip: the ray needs this
@@ -1803,7 +1796,7 @@ hipError_t launch_integrator(const RenderArgs &args0, const plan::Variant &v, hi
     static uint32_t *d_cnt = nullptr;
     const int rows = args0.row_end - args0.row_begin;
     if (rows <= 0 || args0.width <= 0) return hipSuccess;
-    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr || args0.glass != nullptr || args0.tex_recs != nullptr || args0.smooth_normals != nullptr || args0.rough_alpha != nullptr || args0.lights != nullptr) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
+    if (!plan::variant_exists(v, kBuild) || args0.projection != 0 || args0.env_map != nullptr || surface_unit_of(args0) != kNoSurfaceUnit) return hipErrorNotSupported;   // (the instrumented code object holds no camera-twin, lens or projection kernel: refuse rather than run another)
     if (!mod) {
         const char *path = std::getenv("PT_BLOCKPROF_HSACO");
         if (!path) return hipErrorInvalidValue;
@@ -1881,11 +1874,7 @@ Kernel kernel_for(const plan::Variant &v, bool projection) {
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
     const int rows = args.row_end - args.row_begin;
     if (rows <= 0 || args.width <= 0) return hipSuccess;
-    if (args.lights != nullptr) return launch_direct_integrator(args, v, stream);   // (pt_direct_kernels.hip)
-    if (args.rough_alpha != nullptr) return launch_rough_integrator(args, v, stream);   // (pt_rough_kernels.hip)
-    if (args.smooth_normals != nullptr) return launch_smooth_integrator(args, v, stream);   // (pt_smooth_kernels.hip)
-    if (args.tex_recs != nullptr) return launch_texture_integrator(args, v, stream);   // (pt_texture_kernels.hip)
-    if (args.glass != nullptr) return launch_glass_integrator(args, v, stream);   // (pt_glass_kernels.hip)
+    if (const int unit = surface_unit_of(args)) return launch_surface_integrator(unit, args, v, stream);
     if (args.env_map != nullptr) return launch_environment_integrator(args, v, stream);   // (pt_environment_kernels.hip)
     const Kernel kernel = kernel_for(v, args.projection != 0);
     if (!kernel) return hipErrorInvalidDeviceFunction;
@@ -1928,18 +1917,15 @@ hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves) {
 }
 #endif
 
+hipError_t launch_surface_integrator(int unit, const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
 #if defined(PT_PHASE_TIMERS) || defined(PT_BLOCK_PROFILE)
-// the diagnostic builds are linked without the dielectric kernels' unit: a handle with dielectrics is refused (PT_ERR_UNSUPPORTED)
-hipError_t launch_glass_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
-// and without the texture kernels': a handle with textures likewise
-hipError_t launch_texture_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
-// and without the smooth kernels': a handle with shading normals likewise
-hipError_t launch_smooth_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
-// and without the rough kernels': a handle with a roughness list likewise
-hipError_t launch_rough_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
-// and without the direct kernels': a handle with direct lighting likewise
-hipError_t launch_direct_integrator(const RenderArgs &, const plan::Variant &, hipStream_t) { return hipErrorNotSupported; }
+    return hipErrorNotSupported;   // the diagnostic builds are linked without the surface units: a handle with one of their tables is refused (PT_ERR_UNSUPPORTED)
+#else
+    constexpr decltype(&launch_surface_unit<kGlassUnit>) kLaunch[] = {&launch_surface_unit<kGlassUnit>, &launch_surface_unit<kTextureUnit>, &launch_surface_unit<kSmoothUnit>,
+                                                                      &launch_surface_unit<kRoughUnit>, &launch_surface_unit<kDirectUnit>};
+    return unit >= kGlassUnit && unit <= kDirectUnit ? kLaunch[unit - kGlassUnit](args, v, stream) : hipErrorInvalidValue;
 #endif
+}
 
 const plan::Build &integrator_build() { return kBuild; }
 #endif   // PT_ENVIRONMENT_UNIT

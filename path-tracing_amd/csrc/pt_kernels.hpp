@@ -132,25 +132,22 @@ struct RenderArgs {
 
 // The constants the kernels of this library were compiled with: what plan::plan_tiles needs to know of the build.
 const plan::Build &integrator_build();
+// The surface units: translation units of their own (pt_glass_kernels.hip ... pt_direct_kernels.hip), each the unit below it with
+// one more table read where a ray has hit a surface.  A launch needs the unit of the highest table its arguments hold, and every
+// table below that one is then never null (a handle without it passes an all-zero table).
+enum SurfaceUnit : int { kNoSurfaceUnit = 0, kGlassUnit, kTextureUnit, kSmoothUnit, kRoughUnit, kDirectUnit };
+inline int surface_unit_of(const RenderArgs &a) {
+    return a.lights ? kDirectUnit : a.rough_alpha ? kRoughUnit : a.smooth_normals ? kSmoothUnit : a.tex_recs ? kTextureUnit : a.glass ? kGlassUnit : kNoSurfaceUnit;
+}
 // launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds) -- with args.projection != 0
 // the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan;
-// with args.env_map != nullptr the environment kernel of skybox kernel `v` (v.sky), likewise; with args.glass != nullptr the dielectric
-// kernel of whichever of those the launch would run (hipErrorNotSupported from a diagnostic build, which has none); with
-// args.tex_recs != nullptr the texture kernel of that one, likewise; with args.smooth_normals != nullptr the smooth kernel of that one;
-// with args.rough_alpha != nullptr the rough kernel of that one; with args.lights != nullptr the direct kernel of that one
+// with args.env_map != nullptr the environment kernel of skybox kernel `v` (v.sky), likewise; with surface_unit_of(args) that unit's
+// kernel of whichever of those the launch would run
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the environment kernels' translation unit (pt_environment_kernels.hip); launch_integrator calls it, nothing else does
 hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
-// the dielectric kernels' translation unit (pt_glass_kernels.hip), likewise
-hipError_t launch_glass_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
-// the texture kernels' translation unit (pt_texture_kernels.hip), likewise
-hipError_t launch_texture_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
-// the smooth kernels' translation unit (pt_smooth_kernels.hip), likewise
-hipError_t launch_smooth_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
-// the rough kernels' translation unit (pt_rough_kernels.hip), likewise
-hipError_t launch_rough_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
-// the direct kernels' translation unit (pt_direct_kernels.hip), likewise
-hipError_t launch_direct_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+// the surface units' translation units, likewise (hipErrorNotSupported from a diagnostic build, which is linked without them)
+hipError_t launch_surface_integrator(int unit, const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached).  A projection launch asks for its
 // camera twin's: the projection kernels are compiled for their twins' waves per SIMD and LDS (tests/test_projection_resources.py)
 hipError_t integrator_waves_per_cu(const plan::Variant &v, int *waves);

@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "pt_host_math.hpp"
+
 using ptc::fail;
 using ptc::guarded;
 
@@ -31,7 +33,7 @@ int make_list(const pt_scene *scene, const pt_rough *list, int32_t n, std::share
         if (!std::isfinite(d.alpha) || d.alpha < PT_ROUGH_ALPHA_MIN || d.alpha > PT_ROUGH_ALPHA_MAX) return refuse(who + "alpha must lie in 2^-10 .. 1");
         const pt::MatRec &m = mats[d.material];
         if (!(m.n_lobes >= 1 && m.kind0 == 1)) return refuse(who + "material " + std::to_string(d.material) + " has no glossy lobe");
-        if (scene->glass && scene->glass->table[d.material].ior != 0.0f) return refuse(who + "material " + std::to_string(d.material) + " is a dielectric");
+        if (scene->surface.glass && scene->surface.glass->table[d.material].ior != 0.0f) return refuse(who + "material " + std::to_string(d.material) + " is a dielectric");
         if (g->table[d.material] != 0.0f) return refuse(who + "material " + std::to_string(d.material) + " is listed twice");
         g->table[d.material] = d.alpha;
     }
@@ -40,63 +42,32 @@ int make_list(const pt_scene *scene, const pt_rough *list, int32_t n, std::share
     return PT_OK;
 }
 
-// One handle or every device's copy of a frame's scene (copies of one scene: the same materials).  The list is made once, every
-// device's table is uploaded, and only then do the handles change.
+// One handle or every device's copy of a frame's scene (copies of one scene: the same materials): ptc::set_on_copies.
 int set_impl(pt_scene *const *scenes, size_t n_scenes, const pt_rough *list, int32_t n) {
-    for (size_t i = 0; i < n_scenes; ++i)
-        if (!scenes[i]) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
-    std::shared_ptr<pt_rough_list> g;
-    int rc = PT_OK;
-    for (size_t i = 0; i < n_scenes; ++i)   // (every copy's own dielectrics: a frame's copies may have been given different ones)
-        if ((rc = make_list(scenes[i], list, n, g)) != PT_OK) return rc;
-    std::vector<DeviceRough> fresh(n_scenes);
-    for (size_t i = 0; i < n_scenes; ++i) {
-        if (scenes[i]->device < 0) continue;
-        PT_HIP_TRY(hipSetDevice(scenes[i]->device));
-        if (g && (rc = ptc::upload_rough(g->table, scenes[i]->shared->tables, fresh[i])) != PT_OK) return rc;
-        PT_HIP_TRY(hipDeviceSynchronize());   // (a launch in flight may still read the old table)
-    }
-    for (size_t i = 0; i < n_scenes; ++i) {
-        scenes[i]->d_rough = std::move(fresh[i]);
-        scenes[i]->rough = g;
-    }
-    return PT_OK;
+    SurfaceTables made;
+    std::vector<DeviceSurface> fresh(n_scenes);
+    return ptc::set_on_copies(
+        scenes, n_scenes,
+        [&] {
+            std::shared_ptr<pt_rough_list> g;
+            int rc = PT_OK;
+            for (size_t i = 0; i < n_scenes && rc == PT_OK; ++i) rc = make_list(scenes[i], list, n, g);   // (every copy's own dielectrics: a frame's copies may have been given different ones)
+            made.rough = std::move(g);
+            return rc;
+        },
+        [&](size_t i) { return ptc::upload_surface(made, scenes[i]->shared->tables, fresh[i], scenes[i]->d_surface); },
+        [&](size_t i) {
+            scenes[i]->d_surface.alpha = std::move(fresh[i].alpha);
+            scenes[i]->surface.rough = made.rough;
+        });
 }
 
 int get_impl(const pt_scene *scene, pt_rough *list, int32_t *n) {
     if (!scene || !n) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    *n = scene->rough ? static_cast<int32_t>(scene->rough->list.size()) : 0;
-    if (list && scene->rough) std::memcpy(list, scene->rough->list.data(), scene->rough->list.size() * sizeof(pt_rough));
+    *n = scene->surface.rough ? static_cast<int32_t>(scene->surface.rough->list.size()) : 0;
+    if (list && scene->surface.rough) std::memcpy(list, scene->surface.rough->list.data(), scene->surface.rough->list.size() * sizeof(pt_rough));
     return PT_OK;
 }
-
-// The kernels' portable_sincos on the host: double +, -, * only, the same constants in the same order.
-void host_sincos(float a, float &s_out, float &c_out) {
-    static const double t[16] = {
-        0.63661977236758138, 1.57079632673412561417e+00, 6.07710050650619224932e-11, 0.5,
-        -1.66666666666666324348e-01, 8.33333333332248946124e-03, -1.98412698298579493134e-04, 2.75573137070700676789e-06,
-        -2.50507602534068634195e-08, 1.58969099521155010221e-10,
-        4.16666666666666019037e-02, -1.38888888888741095749e-03, 2.48015872894767294178e-05, -2.75573143513906633035e-07,
-        2.08757232129817482790e-09, -1.13596475577881948265e-11};
-    const double x = static_cast<double>(a);
-    const int k = static_cast<int>(x * t[0] + t[3]);
-    const double kd = static_cast<double>(k);
-    const double r = (x - kd * t[1]) - kd * t[2];
-    const double z = r * r;
-    const double ps = t[4] + z * (t[5] + z * (t[6] + z * (t[7] + z * (t[8] + z * t[9]))));
-    const double sn = r + r * (z * ps);
-    const double pc = t[10] + z * (t[11] + z * (t[12] + z * (t[13] + z * (t[14] + z * t[15]))));
-    const double cs = (1.0 - t[3] * z) + (z * z) * pc;
-    const float sf = static_cast<float>(sn), cf = static_cast<float>(cs);
-    switch (static_cast<unsigned>(k) & 3u) {
-        case 0: s_out = sf; c_out = cf; break;
-        case 1: s_out = cf; c_out = -sf; break;
-        case 2: s_out = -sf; c_out = -cf; break;
-        default: s_out = -cf; c_out = sf; break;
-    }
-}
-
-float host_unit_float(uint32_t w) { return static_cast<float>(((w >> 9) << 1) | 1u) * 5.9604644775390625e-08f; }
 
 }  // namespace
 
@@ -111,18 +82,11 @@ int pt_scene_get_roughness(const pt_scene *scene, pt_rough *list, int32_t *n) {
 }
 
 int pt_frame_set_roughness(pt_frame *frame, const pt_rough *list, int32_t n) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_impl(sc.data(), sc.size(), list, n);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_impl(sc, n_sc, list, n); });
 }
 
 int pt_frame_get_roughness(pt_frame *frame, pt_rough *list, int32_t *n) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        return get_impl(ptc::frame_scenes(frame)[0], list, n);
-    });
+    return ptc::on_frame_root(frame, [&](const pt_scene *root) { return get_impl(root, list, n); });
 }
 
 int pt_scene_get_mtl_roughness(const pt_scene *scene, float *pr) {
@@ -143,11 +107,7 @@ int pt_rough_step(int32_t n, const float *normals, const float *directions, cons
         for (int32_t i = 0; i < n; ++i) {
             float h[3];
             pt::rough_step(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2], directions[3 * i], directions[3 * i + 1], directions[3 * i + 2], alpha[i],
-                           host_unit_float(w1[i]), host_unit_float(w2[i]), host_sincos,
-                           [](float &x, float &y, float &z) {
-                               const float inv = 1.0f / std::sqrt((x * x + y * y) + z * z);
-                               x = x * inv; y = y * inv; z = z * inv;
-                           },
+                           ptc::host_unit_float(w1[i]), ptc::host_unit_float(w2[i]), ptc::host_sincos, ptc::host_normalize3,
                            out_directions[3 * i], out_directions[3 * i + 1], out_directions[3 * i + 2], out_g1[i], h[0], h[1], h[2]);
             if (out_microfacet) std::memcpy(out_microfacet + 3 * i, h, sizeof h);
         }

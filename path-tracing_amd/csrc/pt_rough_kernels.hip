@@ -2,5 +2,5 @@
 // search, the shared integrator body, the smooth kernels' set of instantiations and the waves-per-SIMD rules of the twins are all
 // there -- as a translation unit of its own, the way pt_smooth_kernels.hip is.  Every flavour of the library but the diagnostic ones
 // (Makefile) builds this file with the flags of its pt_kernels object.
-#define PT_ROUGH_UNIT
+#define PT_SURFACE_UNIT 4
 #include "pt_kernels.hip"

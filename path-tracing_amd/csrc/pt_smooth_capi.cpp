@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "pt_host_math.hpp"
 #include "pt_smooth_normals.hpp"
 
 using ptc::fail;
@@ -18,35 +19,30 @@ int refuse(const std::string &why) { return fail(PT_ERR_INVALID_ARGUMENT, "shadi
 
 // One handle or every device's copy of a frame's scene (copies of one scene: the same triangles).
 int set_impl(pt_scene *const *scenes, size_t n_scenes, const float *n9) {
-    for (size_t i = 0; i < n_scenes; ++i)
-        if (!scenes[i]) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
-    std::shared_ptr<const std::vector<float>> v;
-    if (n9) {
-        const size_t n_tri = static_cast<size_t>(scenes[0]->shared->host.n_tri());
-        if (n_tri == 0) return refuse("normals for a scene without triangles");
-        for (size_t k = 0; k < 9 * n_tri; ++k)
-            if (!std::isfinite(n9[k])) return refuse("component " + std::to_string(k % 9) + " of triangle " + std::to_string(k / 9) + " is not finite");
-        v = std::make_shared<const std::vector<float>>(n9, n9 + 9 * n_tri);
-    }
-    std::vector<DeviceSmooth> fresh(n_scenes);
-    for (size_t i = 0; i < n_scenes; ++i) {
-        if (scenes[i]->device < 0) continue;
-        PT_HIP_TRY(hipSetDevice(scenes[i]->device));
-        int rc;
-        if (v && (rc = ptc::upload_smooth(*v, scenes[i]->shared->tables, fresh[i])) != PT_OK) return rc;
-        PT_HIP_TRY(hipDeviceSynchronize());   // (a launch in flight may still read the old normals)
-    }
-    for (size_t i = 0; i < n_scenes; ++i) {
-        scenes[i]->d_smooth = std::move(fresh[i]);
-        scenes[i]->smooth = v;
-    }
-    return PT_OK;
+    SurfaceTables made;
+    std::vector<DeviceSurface> fresh(n_scenes);
+    return ptc::set_on_copies(
+        scenes, n_scenes,
+        [&] {
+            if (!n9) return static_cast<int>(PT_OK);
+            const size_t n_tri = static_cast<size_t>(scenes[0]->shared->host.n_tri());
+            if (n_tri == 0) return refuse("normals for a scene without triangles");
+            for (size_t k = 0; k < 9 * n_tri; ++k)
+                if (!std::isfinite(n9[k])) return refuse("component " + std::to_string(k % 9) + " of triangle " + std::to_string(k / 9) + " is not finite");
+            made.smooth = std::make_shared<const std::vector<float>>(n9, n9 + 9 * n_tri);
+            return static_cast<int>(PT_OK);
+        },
+        [&](size_t i) { return ptc::upload_surface(made, scenes[i]->shared->tables, fresh[i], scenes[i]->d_surface); },
+        [&](size_t i) {
+            scenes[i]->d_surface.normals = std::move(fresh[i].normals);
+            scenes[i]->surface.smooth = made.smooth;
+        });
 }
 
 int get_impl(const pt_scene *scene, float *n9, int32_t *has) {
     if (!scene || !has) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    *has = scene->smooth ? 1 : 0;
-    if (n9 && scene->smooth) std::memcpy(n9, scene->smooth->data(), scene->smooth->size() * sizeof(float));
+    *has = scene->surface.smooth ? 1 : 0;
+    if (n9 && scene->surface.smooth) std::memcpy(n9, scene->surface.smooth->data(), scene->surface.smooth->size() * sizeof(float));
     return PT_OK;
 }
 
@@ -63,18 +59,11 @@ int pt_scene_get_shading_normals(const pt_scene *scene, float *n9, int32_t *has)
 }
 
 int pt_frame_set_shading_normals(pt_frame *frame, const float *n9) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_impl(sc.data(), sc.size(), n9);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_impl(sc, n_sc, n9); });
 }
 
 int pt_frame_get_shading_normals(pt_frame *frame, float *n9, int32_t *has) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        return get_impl(ptc::frame_scenes(frame)[0], n9, has);
-    });
+    return ptc::on_frame_root(frame, [&](const pt_scene *root) { return get_impl(root, n9, has); });
 }
 
 int pt_scene_get_vertex_normals(const pt_scene *scene, float *n9, int32_t *has) {
@@ -106,10 +95,7 @@ int pt_shading_normal_at(const float *vertices, const float *plane_normal, const
             pt::tex_barycentrics_record(r.a1[0], r.a1[1], r.a1[2], r.c1, r.a2[0], r.a2[1], r.a2[2], r.c2, points[3 * i], points[3 * i + 1], points[3 * i + 2], b1, b2);
             const bool own = pt::smooth_normal(normals[0], normals[1], normals[2], normals[3], normals[4], normals[5], normals[6], normals[7], normals[8], b1, b2,
                                                plane_normal[0], plane_normal[1], plane_normal[2],
-                                               [](float &x, float &y, float &z) {
-                                                   const float inv = 1.0f / std::sqrt((x * x + y * y) + z * z);
-                                                   x = x * inv; y = y * inv; z = z * inv;
-                                               },
+                                               ptc::host_normalize3,
                                                out[3 * i], out[3 * i + 1], out[3 * i + 2]);
             if (interpolated) interpolated[i] = own ? 1 : 0;
         }

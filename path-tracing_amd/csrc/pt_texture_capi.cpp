@@ -22,7 +22,7 @@ int make_list(const pt_scene *scene, const pt_texture *list, int32_t n, std::sha
     if (n > 0 && !list) return refuse("null list");
     out.reset();
     if (n == 0 || !list) return PT_OK;
-    if (!scene->texcoords) return refuse("the scene handle has no texture coordinates");
+    if (!scene->surface.texcoords) return refuse("the scene handle has no texture coordinates");
     const std::vector<pt::MatRec> &mats = scene->shared->tables.mats;
     auto t = std::make_shared<pt_texture_list>();
     t->recs.assign(mats.size(), pt::TexRec{0, 0, 0, 0});
@@ -37,9 +37,9 @@ int make_list(const pt_scene *scene, const pt_texture *list, int32_t n, std::sha
         if (e.filter != pt::kTexNearest && e.filter != pt::kTexBilinear) return refuse(who + "unknown filter " + std::to_string(e.filter));
         if (!e.rgb) return refuse(who + "null texels");
         if (t->recs[e.material].w != 0) return refuse(who + "material " + std::to_string(e.material) + " is listed twice");
-        if (scene->glass && scene->glass->table[e.material].ior != 0.0f)
+        if (scene->surface.glass && scene->surface.glass->table[e.material].ior != 0.0f)
             return refuse(who + "material " + std::to_string(e.material) + " is a dielectric");
-        if (scene->direct && ptc::material_is_light(mats[e.material]))
+        if (scene->surface.direct && ptc::material_is_light(mats[e.material]))
             return refuse(who + "material " + std::to_string(e.material) + " is a light of the handle's direct lighting");
         const uint64_t texels = static_cast<uint64_t>(e.width) * static_cast<uint64_t>(e.height);
         if (total + texels > pt::kTexMaxTexels) return refuse(who + "the list holds more than 2^28 texels");
@@ -60,62 +60,53 @@ int make_list(const pt_scene *scene, const pt_texture *list, int32_t n, std::sha
     return PT_OK;
 }
 
-// One handle or every device's copy of a frame's scene (copies of one scene: the same materials and triangles).  `new_uv`: the
-// coordinates the handles get (set_uv) or keep.  Everything is made and uploaded first; only then do the handles change.
-int set_impl(pt_scene *const *scenes, size_t n_scenes, bool set_uv, std::shared_ptr<const std::vector<float>> new_uv, bool set_list,
-             const pt_texture *list, int32_t n) {
-    for (size_t i = 0; i < n_scenes; ++i)
-        if (!scenes[i]) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
-    std::shared_ptr<pt_texture_list> made;
-    std::shared_ptr<const pt_texture_list> t = scenes[0]->textures;
-    if (set_list) {
-        const int rc = make_list(scenes[0], list, n, made);
-        if (rc != PT_OK) return rc;
-        t = made;
-    }
-    const std::shared_ptr<const std::vector<float>> uv = set_uv ? new_uv : scenes[0]->texcoords;
-    if (t && !uv) return refuse("the texture coordinates cannot be cleared while a texture list is set");
-    std::vector<DeviceTextures> fresh(n_scenes);
-    for (size_t i = 0; i < n_scenes; ++i) {
-        if (scenes[i]->device < 0) continue;
-        PT_HIP_TRY(hipSetDevice(scenes[i]->device));
-        int rc;
-        if (t && (rc = ptc::upload_textures(*t, *uv, scenes[i]->shared->tables, fresh[i])) != PT_OK) return rc;
-        PT_HIP_TRY(hipDeviceSynchronize());   // (a launch in flight may still read the old tables)
-    }
-    for (size_t i = 0; i < n_scenes; ++i) {
-        scenes[i]->d_tex = std::move(fresh[i]);
-        scenes[i]->textures = t;
-        scenes[i]->texcoords = uv;
-    }
-    return PT_OK;
-}
-
-int set_texcoords_impl(pt_scene *const *scenes, size_t n_scenes, const float *uv) {
-    for (size_t i = 0; i < n_scenes; ++i)
-        if (!scenes[i]) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
-    std::shared_ptr<const std::vector<float>> v;
-    if (uv) {
-        const size_t n_tri = static_cast<size_t>(scenes[0]->shared->host.n_tri());
-        if (n_tri == 0) return refuse("texture coordinates for a scene without triangles");
-        v = std::make_shared<const std::vector<float>>(uv, uv + 6 * n_tri);
-    }
-    return set_impl(scenes, n_scenes, true, v, false, nullptr, 0);
+// One handle or every device's copy of a frame's scene (copies of one scene: the same materials and triangles): ptc::set_on_copies.
+// set_uv: the handles get the coordinates `uv` (nullptr: none) and keep their list; otherwise they get the list and keep their coordinates.
+int set_impl(pt_scene *const *scenes, size_t n_scenes, bool set_uv, const float *uv, const pt_texture *list, int32_t n) {
+    SurfaceTables made;
+    std::vector<DeviceSurface> fresh(n_scenes);
+    return ptc::set_on_copies(
+        scenes, n_scenes,
+        [&] {
+            made.textures = scenes[0]->surface.textures;
+            made.texcoords = scenes[0]->surface.texcoords;
+            if (set_uv) {
+                const size_t n_tri = static_cast<size_t>(scenes[0]->shared->host.n_tri());
+                if (uv && n_tri == 0) return refuse("texture coordinates for a scene without triangles");
+                made.texcoords = uv ? std::make_shared<const std::vector<float>>(uv, uv + 6 * n_tri) : nullptr;
+            } else {
+                std::shared_ptr<pt_texture_list> t;
+                const int rc = make_list(scenes[0], list, n, t);
+                if (rc != PT_OK) return rc;
+                made.textures = std::move(t);
+            }
+            if (made.textures && !made.texcoords) return refuse("the texture coordinates cannot be cleared while a texture list is set");
+            return static_cast<int>(PT_OK);
+        },
+        [&](size_t i) { return ptc::upload_surface(made, scenes[i]->shared->tables, fresh[i], scenes[i]->d_surface); },
+        [&](size_t i) {
+            DeviceSurface &d = scenes[i]->d_surface;
+            d.tex_recs = std::move(fresh[i].tex_recs);
+            d.tex_uv = std::move(fresh[i].tex_uv);
+            d.tex_texels = std::move(fresh[i].tex_texels);
+            scenes[i]->surface.textures = made.textures;
+            scenes[i]->surface.texcoords = made.texcoords;
+        });
 }
 
 int get_texcoords_impl(const pt_scene *scene, float *uv, int32_t *has) {
     if (!scene || !has) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    *has = scene->texcoords ? 1 : 0;
-    if (uv && scene->texcoords) std::memcpy(uv, scene->texcoords->data(), scene->texcoords->size() * sizeof(float));
+    *has = scene->surface.texcoords ? 1 : 0;
+    if (uv && scene->surface.texcoords) std::memcpy(uv, scene->surface.texcoords->data(), scene->surface.texcoords->size() * sizeof(float));
     return PT_OK;
 }
 
 int get_textures_impl(const pt_scene *scene, pt_texture *list, int32_t *n) {
     if (!scene || !n) return fail(PT_ERR_INVALID_ARGUMENT, "null argument");
-    *n = scene->textures ? static_cast<int32_t>(scene->textures->list.size()) : 0;
-    if (list && scene->textures)
-        for (size_t i = 0; i < scene->textures->list.size(); ++i) {
-            const pt_texture_list::Entry &e = scene->textures->list[i];
+    *n = scene->surface.textures ? static_cast<int32_t>(scene->surface.textures->list.size()) : 0;
+    if (list && scene->surface.textures)
+        for (size_t i = 0; i < scene->surface.textures->list.size(); ++i) {
+            const pt_texture_list::Entry &e = scene->surface.textures->list[i];
             list[i] = pt_texture{e.material, e.width, e.height, e.filter, e.rgb.data()};
         }
     return PT_OK;
@@ -132,7 +123,7 @@ struct RgbTexels {
 extern "C" {
 
 int pt_scene_set_texcoords(pt_scene *scene, const float *uv) {
-    return guarded([&] { return set_texcoords_impl(&scene, 1, uv); });
+    return guarded([&] { return set_impl(&scene, 1, true, uv, nullptr, 0); });
 }
 
 int pt_scene_get_texcoords(const pt_scene *scene, float *uv, int32_t *has) {
@@ -140,7 +131,7 @@ int pt_scene_get_texcoords(const pt_scene *scene, float *uv, int32_t *has) {
 }
 
 int pt_scene_set_textures(pt_scene *scene, const pt_texture *list, int32_t n) {
-    return guarded([&] { return set_impl(&scene, 1, false, nullptr, true, list, n); });
+    return guarded([&] { return set_impl(&scene, 1, false, nullptr, list, n); });
 }
 
 int pt_scene_get_textures(const pt_scene *scene, pt_texture *list, int32_t *n) {
@@ -148,33 +139,19 @@ int pt_scene_get_textures(const pt_scene *scene, pt_texture *list, int32_t *n) {
 }
 
 int pt_frame_set_texcoords(pt_frame *frame, const float *uv) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_texcoords_impl(sc.data(), sc.size(), uv);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_impl(sc, n_sc, true, uv, nullptr, 0); });
 }
 
 int pt_frame_get_texcoords(pt_frame *frame, float *uv, int32_t *has) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        return get_texcoords_impl(ptc::frame_scenes(frame)[0], uv, has);
-    });
+    return ptc::on_frame_root(frame, [&](const pt_scene *root) { return get_texcoords_impl(root, uv, has); });
 }
 
 int pt_frame_set_textures(pt_frame *frame, const pt_texture *list, int32_t n) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        const auto &sc = ptc::frame_scenes(frame);
-        return set_impl(sc.data(), sc.size(), false, nullptr, true, list, n);
-    });
+    return ptc::on_frame(frame, [&](pt_scene *const *sc, size_t n_sc) { return set_impl(sc, n_sc, false, nullptr, list, n); });
 }
 
 int pt_frame_get_textures(pt_frame *frame, pt_texture *list, int32_t *n) {
-    return guarded([&] {
-        if (!frame) return fail(PT_ERR_INVALID_ARGUMENT, "null frame");
-        return get_textures_impl(ptc::frame_scenes(frame)[0], list, n);
-    });
+    return ptc::on_frame_root(frame, [&](const pt_scene *root) { return get_textures_impl(root, list, n); });
 }
 
 int pt_scene_get_map_kd(const pt_scene *scene, int32_t material, const char **name) {

@@ -40,9 +40,9 @@ int main(int argc, char **argv) {
     bool io = false;
     EXPECT(pt::load_obj(dir, "lights_room.obj", scene.shared->host, err, io));
     pt::build_device_tables(scene.shared->host, scene.shared->tables);
-    scene.texcoords = std::make_shared<const std::vector<float>>(6 * static_cast<size_t>(scene.shared->host.n_tri()), 0.25f);
+    scene.surface.texcoords = std::make_shared<const std::vector<float>>(6 * static_cast<size_t>(scene.shared->host.n_tri()), 0.25f);
     copy.shared = scene.shared;
-    copy.texcoords = scene.texcoords;
+    copy.surface.texcoords = scene.surface.texcoords;
 
     // the table: five lights (two quads and a triangle; the degenerate emissive triangle is none), cdf ascending to exactly 1
     int32_t n = -1, on = -1;

@@ -135,10 +135,10 @@ int main(int argc, char **argv) {
     auto glass = std::make_shared<pt_glass_list>();
     glass->table.assign(3, pt::GlassRec{});
     glass->table[1].ior = 1.5f;
-    scene.glass = glass;
+    scene.surface.glass = glass;
     const pt_texture on_glass[1] = {{1, 1, 1, 0, wall.data()}};
     EXPECT(pt_scene_set_textures(&scene, on_glass, 1) == PT_ERR_INVALID_ARGUMENT && unchanged(&scene));
-    scene.glass.reset();
+    scene.surface.glass.reset();
     // the frame's setters: every copy takes coordinates and list, a refused call changes none
     g_frame_scenes = {&scene, &copy};
     pt_frame *frame = reinterpret_cast<pt_frame *>(&g_frame_scenes);   // (never dereferenced: frame_scenes above answers for it)
