@@ -1863,8 +1863,8 @@ int pt_rough_step(int32_t n, const float *normals, const float *directions, cons
  * Statistics under the switch: samples_traced, segments and misses count path segments only (no shadow ray); contributing counts the
  * terms added to any L.
  *
- * Not built: multiple importance sampling, sampling by power, environment importance sampling, direct terms for the GGX lobe, textured
- * emitters, Russian roulette.
+ * Not built: multiple importance sampling, sampling by power, direct terms for the GGX lobe, textured emitters, Russian roulette.
+ * (Sampling the environment is a switch of its own: environment sampling, below.)
  *
  * PT_ERR_INVALID_ARGUMENT: a NULL handle; switching on for a scene without a light; switching on while an emissive material is in the
  * handle's texture list -- and pt_scene_set_textures refuses such a material in turn while the switch is on.  A setter builds and
@@ -1895,6 +1895,93 @@ int pt_frame_get_lights(pt_frame *frame, pt_light *lights, int32_t *n, float *ar
 int pt_direct_term(int32_t n, const pt_light *lights, int32_t n_lights, float area, const float *origins, const float *normals,
                    const float *shading_normals, const float *throughput, const float *kd, const uint32_t *l0, const uint32_t *l1,
                    const uint32_t *l2, int32_t *out_light, float *out_points, float *out_directions, float *out_terms, int32_t *out_has_term);
+
+/* ---- environment sampling: shadow rays to the HDR environment ----------------------------------------------------------- */
+
+/* A scene handle that has an environment (pt_scene_set_environment_*) may have ENVIRONMENT SAMPLING switched on.  Every scattering
+ * diffuse hit then sends one shadow ray: with probability `share` to a direction drawn from the environment in proportion to its
+ * radiance, otherwise to a point of the scene's emitters exactly as direct lighting does.  A diffuse-lobe ray that afterwards escapes
+ * to the environment, or reaches an emitter, adds nothing: the bit of NO DOUBLE COUNTING above covers the miss too.  Accounting is
+ * per path, as under direct lighting.  The switch belongs to the handle and is independent of pt_scene_set_direct_lighting, whose
+ * value and refusals stay as they are; with both on this one picks the kernels.  Clones and a frame's copies inherit it with its
+ * table.  It works with every view, dielectrics, textures, shading normals and roughness, with statistics, adaptive sampling and
+ * pass windows, in bands and frames, on small and box-tree scenes; launches are planned as without it.  Without the switch every
+ * output is what it was and the launches go to the kernels they went to.  The diagnostic builds (phase timers, block profile) have no
+ * such kernels: a render of a handle with the switch on is PT_ERR_UNSUPPORTED there.
+ *
+ * THE TABLE is built on the host in double from the handle's N x N octahedral map, whenever the switch is set or the environment of
+ * a switched-on handle is replaced.  S = min(N, 256); the table has S x S cells over the map's square q = (qx, qz) in [-1, 1]^2, cell
+ * c = cj * S + ci with ci along qx.  k = max(2, ceil(2 N / S)).  For sub-point (si, sj), 0 <= si, sj < k, of cell (ci, cj):
+ *   qx = 2 ((ci + (si + 0.5) / k) / S) - 1,  qz likewise with cj, sj;   py = 1 - |qx| - |qz|
+ *   py >= 0: px = qx, pz = qz;  else px = copysign(1 - |qz|, qx), pz = copysign(1 - |qx|, qz)   (the unfold pt_environment_from_equirect uses)
+ *   len = sqrt(px px + py py + pz pz);   L = THE LOOKUP (float) at direction (float(px / len), float(py / len), float(pz / len))
+ *   f = ((0.2126 max(L.r, 0) + 0.7152 max(L.g, 0)) + 0.0722 max(L.b, 0)) / ((len len) len)
+ * f is summed over sj (outer) and si (inner); W_c = (4 / S^2) (sum / (k k)).  1 / |p|^3 is the exact Jacobian d omega / dq of the map
+ * (p . (dp/dpx x dp/dpz) = -(|px| + py + |pz|) = -1 on the octahedron; the fold is a reflection in q and leaves it unchanged).
+ * Phi_env = the sum of W_c in cell order; a map whose Phi_env is zero or not finite is refused.  Every cell then gets at least
+ * Phi_env / S^2 / 16, so every cell has positive probability (a texel whose bilinear footprint reaches into a dark cell is still
+ * sampled); P_c = W_c / (the sum of the floored W in cell order).
+ * The alias table (Walker / Vose) of p_c = P_c S^2: the cells with p_c < 1 go on a stack `small` and the others on a stack `large`,
+ * both in ascending cell order.  While neither is empty: s = pop(small), l = pop(large); accept_s = float(p_s), alias_s = l;
+ * p_l = (p_l + p_s) - 1; l is pushed on small if p_l < 1, else on large.  Every cell never given an alias has accept 1 and is its own
+ * alias.  pdf_self_c = float(P_c S^2 / 4), the probability per unit area of q; pdf_alias_c = pdf_self of the alias.  The probability
+ * the table gives cell c, (accept_c + the sum of (1 - accept_j) over the other cells j whose alias is c) / S^2, differs from P_c by
+ * the float rounding of those accepts: at most (1 + m_c) 2^-25 / S^2, m_c being the number of such j.
+ *
+ * SHARE.  A scene without emitters (an empty light table) has share = 1.  Otherwise the default is Phi_env / (Phi_env + Phi_em) with
+ * Phi_em = 3.14159265358979323846 x the sum over THE LIGHT TABLE, in table order, of area_i ((0.2126 Le.r + 0.7152 Le.g) + 0.0722 Le.b),
+ * all in double, rounded to float and clamped to [0.125, 0.875]; or the caller's value, 0 < share < 1.
+ *
+ * THE SAMPLE AND THE TERM, at a hit where the direct term would be formed.  Float operations rounded once in the order written,
+ * nothing fused, sqrt and / correctly rounded.
+ *   (l0, l1, l2, l3) = philox(pixel, pass, depth, 3) as under direct lighting.  The environment is chosen if and only if
+ *     unit_float(l3) < share.  Otherwise THE DIRECT TERM is formed from l0, l1, l2 and each channel is divided by (1.0f - share).
+ *   (e0, e1, e2, e3) = philox(pixel, pass, depth, 4), drawn where the environment is chosen.  No other random number moves.
+ *   d = (uint64(e0) * S^2) >> 32;   unit_float(e1) < accept_d:  c = d, pdf_q = pdf_self_d;   else  c = alias_d, pdf_q = pdf_alias_d
+ *   cj = c / S, ci = c - cj S;   cw = 2.0f / float(S)
+ *   qx = (float(ci) + unit_float(e2)) * cw - 1.0f;   qz = (float(cj) + unit_float(e3)) * cw - 1.0f
+ *   py = (1.0f - |qx|) - |qz|;   py >= 0: px = qx, pz = qz;  else px = copysign(1.0f - |qz|, qx), pz = copysign(1.0f - |qx|, qz)
+ *   len = sqrt((px * px + py * py) + pz * pz);   w = normalize3(p);   pdf_w = pdf_q * ((len * len) * len)
+ *   cn = dot(N, w);   cs = dot(n, w), n as in THE DIRECT TERM
+ *   no term and no shadow ray unless cn > 0, cs > 0 and 0 < pdf_w < infinity
+ *   L = THE LOOKUP at w, taken when the sample is drawn
+ *   g = (cs * |w.z|) / ((3.141593f * pdf_w) * share);   term_c = ((T_c * Kd_c) * L_c) * g
+ *   The shadow ray leaves O = p + N * eps; the term is added if and only if its closest hit is a miss.
+ * Statistics as under direct lighting.  Not built: multiple importance sampling with the diffuse lobe, a term for the GGX lobe,
+ * sampling emitters by power.
+ *
+ * PT_ERR_INVALID_ARGUMENT: a NULL handle; a handle without an environment; a map whose Phi_env is zero or not finite; a share outside
+ * (0, 1) on a scene with emitters, or a share other than 0 or 1 on one without; an emissive material in the handle's texture list.
+ * While the switch is on, pt_scene_set_environment_* rebuilds the table within the same call and changes nothing if the new map is
+ * refused; removing the environment, setting a skybox and giving an emissive material a texture are refused.  A refused call leaves
+ * every handle as it was. */
+typedef struct pt_env_sampling {
+    float share; /* 0 = the default */
+} pt_env_sampling;
+typedef struct pt_env_sample_record {
+    float accept;
+    int32_t alias;
+    float pdf_self;
+    float pdf_alias;
+} pt_env_sample_record;
+/* params NULL: the switch is cleared. */
+int pt_scene_set_environment_sampling(pt_scene *scene, const pt_env_sampling *params);
+/* *on = 0 or 1; params (may be NULL) gets what the setter was given. */
+int pt_scene_get_environment_sampling(const pt_scene *scene, int32_t *on, pt_env_sampling *params);
+/* The table the switch uses (or would use with the default share): *cells = S, records (may be NULL) gets S x S of them, *share (may be
+ * NULL) the share in use.  A handle without an environment has *cells = 0. */
+int pt_scene_get_environment_sampling_table(const pt_scene *scene, pt_env_sample_record *records, int32_t *cells, float *share);
+/* The same on a frame: every device's copy of the frame's scene; a refused call changes none.  The getters answer for the root's. */
+int pt_frame_set_environment_sampling(pt_frame *frame, const pt_env_sampling *params);
+int pt_frame_get_environment_sampling(pt_frame *frame, int32_t *on, pt_env_sampling *params);
+int pt_frame_get_environment_sampling_table(pt_frame *frame, pt_env_sample_record *records, int32_t *cells, float *share);
+/* THE SAMPLE AND THE TERM alone, on the host, without the visibility, for n hits: a table of cells x cells records, the share, the
+ * map_n x map_n x 3 map, normals (N), shading_normals (n), throughput (T), kd (3 n floats each) and the words e0 .. e3 (n each) give
+ * out_cell (c), out_directions (w, 3 n), out_pdf (pdf_w), out_terms (3 n; zero without a term) and out_has_term (n). */
+int pt_envdirect_term(int32_t n, const pt_env_sample_record *records, int32_t cells, float share, int32_t map_n, const float *map_rgb,
+                      const float *normals, const float *shading_normals, const float *throughput, const float *kd, const uint32_t *e0,
+                      const uint32_t *e1, const uint32_t *e2, const uint32_t *e3, int32_t *out_cell, float *out_directions, float *out_pdf,
+                      float *out_terms, int32_t *out_has_term);
 
 /* ---- misc ------------------------------------------------------------------------------------------- */
 int pt_abi_version(void);

@@ -72,7 +72,10 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_scene_set_roughness", "pt_scene_get_roughness", "pt_frame_set_roughness", "pt_frame_get_roughness",
                "pt_scene_get_mtl_roughness", "pt_rough_step",
                "pt_scene_set_direct_lighting", "pt_scene_get_direct_lighting", "pt_scene_get_lights", "pt_frame_set_direct_lighting",
-               "pt_frame_get_direct_lighting", "pt_frame_get_lights", "pt_direct_term"]
+               "pt_frame_get_direct_lighting", "pt_frame_get_lights", "pt_direct_term",
+               "pt_scene_set_environment_sampling", "pt_scene_get_environment_sampling", "pt_scene_get_environment_sampling_table",
+               "pt_frame_set_environment_sampling", "pt_frame_get_environment_sampling", "pt_frame_get_environment_sampling_table",
+               "pt_envdirect_term"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -555,6 +558,36 @@ def direct_term(lights, area, origins, normals, shading_normals, throughput, kd,
     return idx, pts, dirs, terms, has.astype(bool)
 
 
+# pt_env_sample_record, one cell of a handle's environment sampling table (pt_hip.h: environment sampling), as a numpy dtype: 16 bytes
+ENV_SAMPLE_DTYPE = np.dtype([("accept", np.float32), ("alias", np.int32), ("pdf_self", np.float32), ("pdf_alias", np.float32)])
+
+
+def envdirect_term(records, share, env_map, normals, shading_normals, throughput, kd, e0, e1, e2, e3, library=None):
+    """pt_envdirect_term, the host's own evaluation of the environment sample and its term without the visibility: for a table
+    (`records` of ENV_SAMPLE_DTYPE, [S, S] or [S * S]), the share, the (N, N, 3) map, stored normals N, shading normals n, throughputs T
+    and albedos Kd [n, 3] and the words e0 .. e3 [n]: the chosen cell [n], the unit direction [n, 3], its density per solid angle [n],
+    the term [n, 3] and whether there is one [n]."""
+    L = library or lib()
+    rec = np.ascontiguousarray(records, ENV_SAMPLE_DTYPE).reshape(-1)
+    cells = int(round(len(rec) ** 0.5))
+    if cells * cells != len(rec):
+        raise ValueError("envdirect_term: a table of S x S records")
+    m = np.ascontiguousarray(env_map, np.float32)
+    if m.ndim != 3 or m.shape[0] != m.shape[1] or m.shape[2] != 3:
+        raise ValueError("envdirect_term: an (n, n, 3) map")
+    arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (normals, shading_normals, throughput, kd)]
+    words = [np.ascontiguousarray(w, np.uint32).reshape(-1) for w in (e0, e1, e2, e3)]
+    n = len(arrs[0])
+    if any(len(a) != n for a in arrs + words):
+        raise ValueError("envdirect_term: arrays of one length")
+    cell, has = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    dirs, pdf, terms = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+    up, ip = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    _check(L.pt_envdirect_term(n, rec.ctypes.data_as(C.c_void_p), cells, C.c_float(share), m.shape[0], _fp(m), *[_fp(a) for a in arrs],
+                               *[w.ctypes.data_as(up) for w in words], cell.ctypes.data_as(ip), _fp(dirs), _fp(pdf), _fp(terms), has.ctypes.data_as(ip)), L)
+    return cell, dirs, pdf, terms, has.astype(bool)
+
+
 TEXTURE_NEAREST, TEXTURE_BILINEAR = 0, 1
 TEXTURE_MAX_SIDE = 8192
 _TEXTURE_FILTERS = {"nearest": TEXTURE_NEAREST, "bilinear": TEXTURE_BILINEAR}
@@ -798,6 +831,11 @@ def load_library(path):
         getattr(L, f"pt_{who}_set_direct_lighting").argtypes = [vp, C.c_int32]
         getattr(L, f"pt_{who}_get_direct_lighting").argtypes = [vp, ip]
         getattr(L, f"pt_{who}_get_lights").argtypes = [vp, vp, ip, fp]
+    for who in ("scene", "frame"):
+        getattr(L, f"pt_{who}_set_environment_sampling").argtypes = [vp, C.POINTER(C.c_float)]
+        getattr(L, f"pt_{who}_get_environment_sampling").argtypes = [vp, ip, C.POINTER(C.c_float)]
+        getattr(L, f"pt_{who}_get_environment_sampling_table").argtypes = [vp, vp, ip, C.POINTER(C.c_float)]
+    L.pt_envdirect_term.argtypes = [C.c_int32, vp, C.c_int32, C.c_float, C.c_int32, fp, fp, fp, fp, fp] + [C.POINTER(C.c_uint32)] * 4 + [ip, fp, fp, fp, ip]
     L.pt_direct_term.argtypes = [C.c_int32, vp, C.c_int32, C.c_float, fp, fp, fp, fp, fp] + [C.POINTER(C.c_uint32)] * 3 + [ip, fp, fp, fp, ip]
     L.pt_rough_step.argtypes = [C.c_int32, fp, fp, fp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), fp, fp, fp]
     L.pt_scene_get_map_kd.argtypes = [vp, C.c_int32, C.POINTER(C.c_char_p)]
@@ -1019,6 +1057,38 @@ class _DirectMethods:
         return arr[:n.value], np.float32(area.value)
 
 
+class _EnvDirectMethods:
+    """set_environment_sampling / environment_sampling / environment_sampling_table of a Scene (pt_scene_*) and of a Frame (pt_frame_*:
+    every device's copy)."""
+    _envdirect_prefix = "pt_scene_"
+
+    def set_environment_sampling(self, share=None):
+        """-DIRECT_ENV: switches environment sampling on (pt_hip.h: environment sampling) with the default share (None) or a share
+        strictly between 0 and 1, or off (False).  Refused: a handle without an environment, a black environment, a share out of
+        range, an emissive material in the texture list."""
+        fn = getattr(self._L, self._envdirect_prefix + "set_environment_sampling")
+        if share is False:
+            _check(fn(self._h, None), self._L)
+        else:
+            _check(fn(self._h, C.byref(C.c_float(0.0 if share is None or share is True else float(share)))), self._L)
+
+    def environment_sampling(self):
+        """None where the switch is off, else the share in use."""
+        on, given = C.c_int32(), C.c_float()
+        _check(getattr(self._L, self._envdirect_prefix + "get_environment_sampling")(self._h, C.byref(on), C.byref(given)), self._L)
+        return self.environment_sampling_table()[1] if on.value else None
+
+    def environment_sampling_table(self):
+        """The table the switch uses (or would use with the default share): (records [S, S] of ENV_SAMPLE_DTYPE, the share)."""
+        get = getattr(self._L, self._envdirect_prefix + "get_environment_sampling_table")
+        cells, share = C.c_int32(), C.c_float()
+        _check(get(self._h, None, C.byref(cells), C.byref(share)), self._L)
+        arr = np.zeros((cells.value, cells.value), ENV_SAMPLE_DTYPE)
+        if cells.value:
+            _check(get(self._h, arr.ctypes.data_as(C.c_void_p), C.byref(cells), C.byref(share)), self._L)
+        return arr, np.float32(share.value)
+
+
 class _TextureMethods:
     """set_texcoords / texcoords / set_textures / textures of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
     _tex_prefix = "pt_scene_"
@@ -1098,7 +1168,7 @@ class _SmoothMethods:
         return scene._normals(scene._L.pt_scene_get_vertex_normals)
 
 
-class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods):
+class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods, _EnvDirectMethods):
     """Owns a pt_scene handle (Scene + LoadModel of the reference, scene.h:17-19)."""
 
     def __init__(self, handle, library=None):
@@ -1845,9 +1915,9 @@ def bvh_depth(nodes):
     return int(level.max())
 
 
-class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods):
+class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods, _EnvDirectMethods):
     """pt_frame: one image on several devices from one host program -- row bands, one gather to the first device."""
-    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = _rough_prefix = _direct_prefix = "pt_frame_"
+    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = _rough_prefix = _direct_prefix = _envdirect_prefix = "pt_frame_"
 
     def _n_tri(self):
         return self._scene.counts()[0]

@@ -263,8 +263,8 @@ void bind_surface(const pt_scene &scene, pt::RenderArgs &a) {
     const SurfaceTables &h = scene.surface;
     const DeviceSurface &d = scene.d_surface;
     const bool glass = h.glass && d.glass, tex = h.textures && d.tex_recs, smooth = h.smooth && d.normals, rough = h.rough && d.alpha,
-               direct = h.direct && d.lights;
-    const int unit = direct ? pt::kDirectUnit : rough ? pt::kRoughUnit : smooth ? pt::kSmoothUnit : tex ? pt::kTextureUnit : glass ? pt::kGlassUnit : pt::kNoSurfaceUnit;
+               direct = h.direct && d.lights, envdirect = h.envdirect && d.env_alias && d.env_lights && scene.env && scene.d_env;
+    const int unit = envdirect ? pt::kEnvDirectUnit : direct ? pt::kDirectUnit : rough ? pt::kRoughUnit : smooth ? pt::kSmoothUnit : tex ? pt::kTextureUnit : glass ? pt::kGlassUnit : pt::kNoSurfaceUnit;
     if (unit >= pt::kGlassUnit) a.glass = (glass ? d.glass : d.no_glass).get<void>();
     if (unit >= pt::kTextureUnit) {   // (the stand-in marks no material: its coordinates and texels, the table itself, are never read)
         a.tex_recs = (tex ? d.tex_recs : d.no_tex).get<void>();
@@ -274,10 +274,18 @@ void bind_surface(const pt_scene &scene, pt::RenderArgs &a) {
     }
     if (unit >= pt::kSmoothUnit) a.smooth_normals = (smooth ? d.normals : d.no_normals).get<void>();
     if (unit >= pt::kRoughUnit) a.rough_alpha = (rough ? d.alpha : d.no_alpha).get<float>();
-    if (unit >= pt::kDirectUnit) {
+    if (unit == pt::kDirectUnit) {
         a.lights = d.lights.get<void>();
         a.n_lights = static_cast<int32_t>(h.direct->lights.size());
         a.light_area = h.direct->area;
+    }
+    if (unit == pt::kEnvDirectUnit) {   // (its own copy of the light table: the switch does not depend on direct lighting's)
+        a.lights = d.env_lights.get<void>();
+        a.n_lights = static_cast<int32_t>(h.envdirect->lights->lights.size());
+        a.light_area = h.envdirect->lights->area;
+        a.env_alias = d.env_alias.get<void>();
+        a.env_cells = h.envdirect->cells;
+        a.env_share = h.envdirect->share;
     }
 }
 
@@ -374,6 +382,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     fill_scene_args(scene, p->eps, a);
     // (a handle that answers 1 to get_direct_lighting never renders without its light table)
     if (scene->surface.direct && !a.lights) return fail(PT_ERR_INVALID_ARGUMENT, "direct lighting: the handle has the switch set and no light table on its device");
+    if (scene->surface.envdirect && !a.env_alias) return fail(PT_ERR_INVALID_ARGUMENT, "environment sampling: the handle has the switch set and no table on its device");
     a.vec_ok = (p->width % 4 == 0) &&
                ((reinterpret_cast<uintptr_t>(planes.sum) | reinterpret_cast<uintptr_t>(planes.sum2) | reinterpret_cast<uintptr_t>(planes.count)) % 16 == 0);
     a.sum = planes.sum;
@@ -431,7 +440,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     }
     const hipError_t launched = pt::launch_integrator(a, tiles.variant, stream);
     if (const int unit = pt::surface_unit_of(a); launched == hipErrorNotSupported && unit != pt::kNoSurfaceUnit) {
-        static const char *const kWhat[][2] = {{"dielectrics", "dielectric"}, {"textures", "texture"}, {"shading normals", "smooth"}, {"roughness", "rough"}, {"direct lighting", "direct"}};
+        static const char *const kWhat[][2] = {{"dielectrics", "dielectric"}, {"textures", "texture"}, {"shading normals", "smooth"}, {"roughness", "rough"}, {"direct lighting", "direct"}, {"environment sampling", "environment-sampling"}};
         const char *const *w = kWhat[unit - pt::kGlassUnit];
         return fail(PT_ERR_UNSUPPORTED, std::string(w[0]) + ": this diagnostic build of the library has no " + w[1] + " kernels");
     }
@@ -679,6 +688,7 @@ static int scene_clone_impl(const pt_scene *src, int device, pt_scene **out) {
 
 static int scene_set_skybox_bmp_impl(pt_scene *scene, const char *path) {
     if (!scene) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
+    if (path && *path && scene->surface.envdirect) return fail(PT_ERR_INVALID_ARGUMENT, "skybox: the scene handle has environment sampling switched on");
     if (path && *path && scene->env) return fail(PT_ERR_INVALID_ARGUMENT, "skybox: the scene handle has an environment; a handle has a skybox or an environment");
     std::vector<uint8_t> texels;
     int w = 0, h = 0;

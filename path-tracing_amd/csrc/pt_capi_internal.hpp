@@ -27,6 +27,7 @@
 #include "pt_meter.hpp"
 #include "pt_optics.hpp"
 #include "pt_direct.hpp"
+#include "pt_envdirect.hpp"
 #include "pt_rough.hpp"
 #include "pt_scene.hpp"
 #include "pt_sharpen.hpp"
@@ -95,6 +96,18 @@ struct pt_light_table {
     float area = 0.0f;
 };
 
+// The environment sampling of a handle with that switch on (pt_hip.h: environment sampling): the alias table of the handle's environment,
+// the share in use, what the setter was given, and the scene's light table (empty: no emitters, share 1).  Immutable once built; a new
+// environment makes a new one.
+struct pt_env_sampler {
+    std::vector<pt::EnvAliasRec> records;
+    int cells = 0;                    // S
+    float share = 1.0f;
+    pt_env_sampling given{};
+    double phi_env = 0.0;
+    std::shared_ptr<const pt_light_table> lights;
+};
+
 // The tables of a handle that the integrator reads only where a ray has hit a surface.  The host side: each
 // nullptr = none, immutable once set, and a copy of the handle inherits all of them (a loaded scene has the OBJ's texcoords).
 struct SurfaceTables {
@@ -104,6 +117,7 @@ struct SurfaceTables {
     std::shared_ptr<const std::vector<float>> smooth;        // shading normals, 9 floats per triangle
     std::shared_ptr<const pt_rough_list> rough;
     std::shared_ptr<const pt_light_table> direct;            // the light table: direct lighting is on
+    std::shared_ptr<const pt_env_sampler> envdirect;         // the alias table: environment sampling is on
 };
 // The same on the handle's device: one buffer per table that is set, and what stands in for the absent ones below the highest that is
 // set (bind_surface) -- the barycentrics' record of every triangle (pt_texture.hpp: TexBary), which every unit from the texture
@@ -111,6 +125,7 @@ struct SurfaceTables {
 // The stand-ins depend on the scene's immutable tables alone: each is uploaded once, when first needed, and never replaced.
 struct DeviceSurface {
     ptc::DeviceBuffer glass, tex_recs, tex_uv, tex_texels, normals, alpha, lights;
+    ptc::DeviceBuffer env_alias, env_lights;   // environment sampling: its table and its own copy of the light table (one all-zero record where the scene has no emitter)
     ptc::DeviceBuffer bary, no_glass, no_tex, no_normals, no_alpha;
 };
 
@@ -478,7 +493,7 @@ inline std::vector<pt::TexBary> texture_bary_records(const std::vector<pt::Exact
 // that the highest of them reads and `kept` does not hold yet (no launch in flight reads a buffer this adds).  A setter gives its
 // new table alone, storage of its own and the handle's `kept`; a new handle's upload gives all of its tables and its own buffers twice.
 inline int upload_surface(const SurfaceTables &t, const pt::DeviceTables &tables, DeviceSurface &out, DeviceSurface &kept) {
-    const int unit = t.direct ? pt::kDirectUnit : t.rough ? pt::kRoughUnit : t.smooth ? pt::kSmoothUnit : t.textures ? pt::kTextureUnit : pt::kNoSurfaceUnit;
+    const int unit = t.envdirect ? pt::kEnvDirectUnit : t.direct ? pt::kDirectUnit : t.rough ? pt::kRoughUnit : t.smooth ? pt::kSmoothUnit : t.textures ? pt::kTextureUnit : pt::kNoSurfaceUnit;
     const size_t n_mat = tables.mats.size(), n_tri = tables.exact.size();
     int rc = PT_OK;
     const auto put = [&rc](ptc::DeviceBuffer &b, const auto &v, const char *what) {
@@ -502,9 +517,87 @@ inline int upload_surface(const SurfaceTables &t, const pt::DeviceTables &tables
     }
     if (t.rough) put(out.alpha, t.rough->table, "roughness table");
     if (t.direct) put(out.lights, t.direct->lights, "light table");
+    if (t.envdirect) {
+        put(out.env_alias, t.envdirect->records, "environment sampling table");
+        put(out.env_lights, t.envdirect->lights->lights.empty() ? std::vector<pt::LightRec>(1, pt::LightRec{}) : t.envdirect->lights->lights, "light table");
+    }
     return rc;
 }
 // Whether material `m` is what the light table takes its lights from: the single emissive lobe.
 inline bool material_is_light(const pt::MatRec &m) { return m.n_lobes == 1 && m.kind0 == 0; }
+// The light table of a scene (pt_direct_capi.cpp; pt_hip.h: THE LIGHT TABLE).
+std::shared_ptr<pt_light_table> light_table_of(const pt::DeviceTables &tables);
+// Environment sampling's sampler and its rebuild (pt_hip.h: environment sampling), inline here: the environment's setters
+// (pt_environment_capi.cpp) rebuild the table of a switched-on handle and must not need another translation unit for it.
+// Phi_em of a light table (pt_hip.h: SHARE): areas as the table builder forms them, in double from the float edges.
+inline double envdirect_emitted_power(const pt_light_table &t) {
+    double sum = 0.0;
+    for (const pt::LightRec &l : t.lights) {
+        const double ax = l.e1[0], ay = l.e1[1], az = l.e1[2], bx = l.e2[0], by = l.e2[1], bz = l.e2[2];
+        const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+        const double area = 0.5 * std::sqrt((cx * cx + cy * cy) + cz * cz);
+        sum += area * pt::envdirect_lum(l.le[0], l.le[1], l.le[2]);
+    }
+    return 3.14159265358979323846 * sum;
+}
+
+// The sampler of `map` for a scene with light table `lights` and the setter's `given`; refuses a black map and a share out of range.
+inline int envdirect_sampler(const pt_env_map &map, std::shared_ptr<const pt_light_table> lights, const pt_env_sampling &given,
+                  std::shared_ptr<const pt_env_sampler> &out) {
+    auto s = std::make_shared<pt_env_sampler>();
+    s->given = given;
+    s->lights = std::move(lights);
+    s->cells = pt::envdirect_cells(map.n);
+    const bool emitters = !s->lights->lights.empty() && s->lights->area > 0.0f && std::isfinite(s->lights->area);
+    const float g = given.share;
+    if (emitters ? !(g == 0.0f || (g > 0.0f && g < 1.0f)) : !(g == 0.0f || g == 1.0f))
+        return fail(PT_ERR_INVALID_ARGUMENT, emitters ? "environment sampling: the share must lie strictly between 0 and 1 (0 = the default): either end leaves a source unsampled"
+                               : "environment sampling: a scene without emitters has share 1 (give 0 or 1)");
+    if (!pt::envdirect_build(map.n, pt::env_with_apron(map.n, map.rgb.data()), s->records, s->phi_env))
+        return fail(PT_ERR_INVALID_ARGUMENT, "environment sampling: the environment is black or not finite: there is nothing to sample");
+    if (!emitters) {
+        auto none = std::make_shared<pt_light_table>();
+        s->lights = none;
+        s->share = 1.0f;
+    } else if (g != 0.0f) {
+        s->share = g;
+    } else {
+        const float d = static_cast<float>(s->phi_env / (s->phi_env + envdirect_emitted_power(*s->lights)));
+        s->share = d < 0.125f ? 0.125f : d > 0.875f ? 0.875f : d;
+        if (!(s->share == s->share)) s->share = 0.875f;   // (an infinite Phi_em)
+    }
+    out = std::move(s);
+    return PT_OK;
+}
+
+// Environment sampling on handles whose environment is being replaced by `map`: the new table of those copies that have the switch, built
+// once and uploaded to each copy's device; envdirect_commit(i) then swaps copy i's.  Copies without the switch are left alone.  A map the
+// table refuses fails here, before any handle has changed.
+struct EnvSamplingRebuild {
+    std::shared_ptr<const pt_env_sampler> table;
+    std::vector<DeviceSurface> fresh;
+};
+inline int envdirect_prepare(pt_scene *const *scenes, size_t n, const pt_env_map &map, EnvSamplingRebuild &out) {
+    const pt_env_sampler *old = nullptr;
+    for (size_t i = 0; i < n && !old; ++i) old = scenes[i]->surface.envdirect.get();
+    if (!old) return PT_OK;
+    int rc = envdirect_sampler(map, old->lights, old->given, out.table);
+    if (rc != PT_OK) return rc;
+    SurfaceTables made;
+    made.envdirect = out.table;
+    out.fresh.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!scenes[i]->surface.envdirect || scenes[i]->device < 0) continue;
+        PT_HIP_TRY(hipSetDevice(scenes[i]->device));
+        if ((rc = upload_surface(made, scenes[i]->shared->tables, out.fresh[i], scenes[i]->d_surface)) != PT_OK) return rc;
+    }
+    return PT_OK;
+}
+inline void envdirect_commit(pt_scene *scene, size_t i, EnvSamplingRebuild &r) {
+    if (!scene->surface.envdirect || !r.table) return;
+    scene->d_surface.env_alias = std::move(r.fresh[i].env_alias);
+    scene->d_surface.env_lights = std::move(r.fresh[i].env_lights);
+    scene->surface.envdirect = r.table;
+}
 
 }  // namespace ptc

@@ -100,6 +100,8 @@ int lights_impl(const pt_scene *scene, pt_light *lights, int32_t *n, float *area
 
 }  // namespace
 
+std::shared_ptr<pt_light_table> ptc::light_table_of(const pt::DeviceTables &tables) { return build_table(tables); }
+
 extern "C" {
 
 int pt_scene_set_direct_lighting(pt_scene *scene, int32_t on) {

@@ -249,15 +249,25 @@ int set_on(pt_scene *const *scenes, size_t n_scenes, bool removal, Make &&make) 
         if (!scenes[i]) return fail(PT_ERR_INVALID_ARGUMENT, "null scene");
         if (scenes[i]->sky && !removal) return fail(PT_ERR_INVALID_ARGUMENT, kHasSkybox);
     }
+    // (environment sampling: the handle keeps an environment while the switch is on, and a new one brings its table with it)
+    bool sampled = false;
+    for (size_t i = 0; i < n_scenes; ++i) sampled = sampled || scenes[i]->surface.envdirect;
+    if (sampled && removal) return fail(PT_ERR_INVALID_ARGUMENT, "environment: the scene handle has environment sampling switched on; clear it first");
     std::shared_ptr<pt_env_map> map;
     if (!removal) {
         const int rc = make(map);
+        if (rc != PT_OK) return rc;
+    }
+    ptc::EnvSamplingRebuild rebuild;
+    if (sampled) {
+        const int rc = ptc::envdirect_prepare(scenes, n_scenes, *map, rebuild);
         if (rc != PT_OK) return rc;
     }
     for (size_t i = 0; i < n_scenes; ++i) {
         if (removal && scenes[i]->sky) continue;   // (there is none to remove)
         const int rc = install(scenes[i], map);
         if (rc != PT_OK) return rc;
+        if (sampled) ptc::envdirect_commit(scenes[i], i, rebuild);
     }
     return PT_OK;
 }

@@ -14,10 +14,14 @@
 // accumulators take it once, when the path ends; a scattering diffuse hit sends a shadow ray to a sampled point of the handle's light
 // table through closest_hit itself, and an emitter reached by the diffuse lobe's own ray adds nothing (pt_hip.h: direct lighting;
 // pt_direct.hpp spells the term).
+// ENVDIRECT (only pt::integrate_kernel_envdirect: false in every other kernel; with DIRECT and ENVMAP) = the shadow ray of a diffuse hit
+// goes, with probability RenderArgs::env_share, to a direction drawn from the environment's alias table, and counts if it misses; a
+// miss after a diffuse step adds nothing (pt_hip.h: environment sampling; pt_envdirect.hpp spells the sample and the term).
     constexpr int POOL = ADAPT & ~1;
     constexpr bool CAM = (ADAPT & 1) != 0;
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
     static_assert(!DIRECT || (SMOOTH && ROUGH), "the direct term is written in the smooth scatter step: a direct kernel is a rough kernel with DIRECT");
+    static_assert(!ENVDIRECT || (DIRECT && ENVMAP), "an environment-sampling kernel is a direct kernel with an environment");
     static_assert(!MOTION || CAM, "a motion kernel is the motion variant of a camera twin or of its lens kernel");
     static_assert(!PROJ || (CAM && !LENS && !MOTION), "a projection kernel is the projection variant of a camera twin; the host refuses a lens or a motion with it");
     static_assert(!NARROW || (!SKY && !STATS), "only the statistics-free, skybox-free kernels have a narrow variant");
@@ -744,11 +748,18 @@
                         const EnvironmentView ev = environment_view();
                         float lr, lg, lb;
                         env_lookup(ev.map(), ev.n(), q[k].dx, q[k].dy, q[k].dz, lr, lg, lb);
-                        if constexpr (DIRECT) {
+                        if constexpr (ENVDIRECT) {   // (an environment the diffuse step's shadow ray has sampled already adds nothing)
+                            if (!lit[k]) {
+                                Lr[k] += tr[k] * lr; Lg[k] += tg[k] * lg; Lb[k] += tb[k] * lb;
+                                contributed = true;
+                            }
+                        } else if constexpr (DIRECT) {
                             Lr[k] += tr[k] * lr; Lg[k] += tg[k] * lg; Lb[k] += tb[k] * lb;
-                        } else
+                            contributed = true;
+                        } else {
                         contribute(k, tr[k] * lr, tg[k] * lg, tb[k] * lb);
                         contributed = true;
+                        }
                     } else if (SKY) {   // skybox miss shader, scene.cpp:126-154 (note: the path throughput is NOT applied)
                         const float pi = 3.141593f;
                         const float theta = portable_acosf(q[k].dy) / pi;
@@ -916,6 +927,16 @@
                                     uint32_t l0, l1, l2, l3;
                                     philox4x32_10(rng_pixel(k), static_cast<uint32_t>(pass_of(k)), static_cast<uint32_t>(depth[k]), kDirectStream, a.seed, kPhiloxKey1,
                                                   l0, l1, l2, l3);
+                                    // ENVDIRECT: the counter's spare word chooses between the emitters (the term above over 1 - share) and the
+                                    // environment: a direction drawn from the alias table by the words of counter (pixel, pass, depth, 4), whose
+                                    // term counts if the shadow ray misses -- the slot's "light" is the miss value of the search.
+                                    [[maybe_unused]] bool to_sky = false;
+                                    [[maybe_unused]] float share = 1.0f;
+                                    if constexpr (ENVDIRECT) {
+                                        share = envdirect_view().share();
+                                        to_sky = unit_float(l3) < share;
+                                    }
+                                    if (!to_sky) {
                                     const DirectView dv = direct_view();
                                     const LightRec *__restrict__ lr = dv.lights() + direct_pick(dv.lights(), dv.n(), unit_float(l0));
                                     const LightRec lrec = *lr;   // (five 16-byte loads)
@@ -925,6 +946,30 @@
                                                              [](float &vx, float &vy, float &vz) { normalize3(vx, vy, vz); }, ppx, ppy, ppz, sdx[k], sdy[k], sdz[k],
                                                              scr[k], scg[k], scb[k]);
                                     slight[k] = lrec.orig;
+                                    if constexpr (ENVDIRECT) {
+                                        const float rest = 1.0f - share;
+                                        scr[k] = scr[k] / rest; scg[k] = scg[k] / rest; scb[k] = scb[k] / rest;
+                                    }
+                                    }
+                                    if constexpr (ENVDIRECT) {
+                                        if (to_sky) {
+                                            const EnvDirectView sv = envdirect_view();
+                                            uint32_t e0, e1, e2, e3;
+                                            philox4x32_10(rng_pixel(k), static_cast<uint32_t>(pass_of(k)), static_cast<uint32_t>(depth[k]), kEnvDirectStream, a.seed,
+                                                          kPhiloxKey1, e0, e1, e2, e3);
+                                            float pdf_w;
+                                            [[maybe_unused]] int32_t cell;
+                                            envdirect_sample(sv.table(), sv.cells(), e0, unit_float(e1), unit_float(e2), unit_float(e3),
+                                                             [](float &vx, float &vy, float &vz) { normalize3(vx, vy, vz); },
+                                                             [](float v) { return sqrt_rn_normal(v); }, cell, sdx[k], sdy[k], sdz[k], pdf_w);
+                                            const EnvironmentView ev = environment_view();
+                                            float er, eg, eb;
+                                            env_lookup(ev.map(), ev.n(), sdx[k], sdy[k], sdz[k], er, eg, eb);   // (four 16-byte loads)
+                                            pending[k] = envdirect_term(sdx[k], sdy[k], sdz[k], pdf_w, share, er, eg, eb, pl.x, pl.y, pl.z, sx, sy, sz, tr[k], tg[k],
+                                                                        tb[k], m0v.x, m0v.y, m0v.z, scr[k], scg[k], scb[k]);
+                                            slight[k] = -1;
+                                        }
+                                    }
                                 }
                             }
                             float hx = 0.0f, hy = 0.0f, hz = 0.0f;

@@ -41,6 +41,7 @@
 #include "pt_smooth.hpp"
 #include "pt_rough.hpp"
 #include "pt_direct.hpp"
+#include "pt_envdirect.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1394,6 +1395,23 @@ __device__ __forceinline__ DirectView direct_view() {
     asm volatile("" : "+s"(p));
     return {p};
 }
+// The alias table of an environment-sampling launch (RenderArgs::env_alias, env_cells, env_share), likewise: read where the diffuse lobe
+// of a ray that scatters has been chosen.
+struct EnvDirectView {
+    uint64_t p;
+    __device__ __forceinline__ const EnvAliasRec *table() const { return *reinterpret_cast<const EnvAliasRec *const __attribute__((address_space(4))) *>(p); }
+    __device__ __forceinline__ int32_t cells() const {
+        return *reinterpret_cast<const __attribute__((address_space(4))) int32_t *>(p + (offsetof(RenderArgs, env_cells) - offsetof(RenderArgs, env_alias)));
+    }
+    __device__ __forceinline__ float share() const {
+        return *reinterpret_cast<const __attribute__((address_space(4))) float *>(p + (offsetof(RenderArgs, env_share) - offsetof(RenderArgs, env_alias)));
+    }
+};
+__device__ __forceinline__ EnvDirectView envdirect_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, env_alias);
+    asm volatile("" : "+s"(p));
+    return {p};
+}
 
 // What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
 // in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
@@ -1430,7 +1448,7 @@ constexpr int integrator_waves() {
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
 #include "pt_integrator_body.inc"
 }
 // The lens kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary ray
@@ -1446,7 +1464,7 @@ constexpr int lens_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (lens_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
+    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
 #include "pt_integrator_body.inc"
 }
 // The motion twins (pt_hip.h: camera motion): the camera twin and its lens kernel with the camera -- and the lens axes -- interpolated
@@ -1462,12 +1480,12 @@ constexpr int motion_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, false>())) void integrate_kernel_motion(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
+    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
 #include "pt_integrator_body.inc"
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, true>())) void integrate_kernel_motion_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
+    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
 #include "pt_integrator_body.inc"
 }
 // The projection kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary
@@ -1482,15 +1500,15 @@ constexpr int projection_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (projection_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_projection(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
 #include "pt_integrator_body.inc"
 }
 
-// launch_surface_integrator's five halves: each surface unit's translation unit defines its own
+// launch_surface_integrator's six halves: each surface unit's translation unit defines its own
 template <int UNIT>
 hipError_t launch_surface_unit(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 #define PT_UNIT_HALF(U) template <> hipError_t launch_surface_unit<U>(const RenderArgs &, const plan::Variant &, hipStream_t);
-PT_UNIT_HALF(kGlassUnit) PT_UNIT_HALF(kTextureUnit) PT_UNIT_HALF(kSmoothUnit) PT_UNIT_HALF(kRoughUnit) PT_UNIT_HALF(kDirectUnit)
+PT_UNIT_HALF(kGlassUnit) PT_UNIT_HALF(kTextureUnit) PT_UNIT_HALF(kSmoothUnit) PT_UNIT_HALF(kRoughUnit) PT_UNIT_HALF(kDirectUnit) PT_UNIT_HALF(kEnvDirectUnit)
 #undef PT_UNIT_HALF
 
 #ifdef PT_ENVIRONMENT_UNIT
@@ -1514,7 +1532,7 @@ template <bool BIG, bool STATS, bool ENV, int VIEW>
 __global__ __launch_bounds__(kBlock, (environment_waves<BIG, STATS, ENV, VIEW>())) void integrate_kernel_environment(const RenderArgs a) {
     constexpr bool SKY = true, NARROW = false;
     constexpr int ADAPT = VIEW != 0 ? 1 : 0;
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
 #include "pt_integrator_body.inc"
 }
 namespace {
@@ -1545,12 +1563,13 @@ hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Var
 #define PT_UNIT_NAME_3 smooth
 #define PT_UNIT_NAME_4 rough
 #define PT_UNIT_NAME_5 direct
+#define PT_UNIT_NAME_6 envdirect
 #define PT_PASTE_(a, b) a##b
 #define PT_PASTE(a, b) PT_PASTE_(a, b)
 #define PT_UNIT_KERNEL PT_PASTE(integrate_kernel_, PT_PASTE(PT_UNIT_NAME_, PT_SURFACE_UNIT))
-static_assert(PT_SURFACE_UNIT >= kGlassUnit && PT_SURFACE_UNIT <= kDirectUnit, "PT_SURFACE_UNIT: a SurfaceUnit");
+static_assert(PT_SURFACE_UNIT >= kGlassUnit && PT_SURFACE_UNIT <= kEnvDirectUnit, "PT_SURFACE_UNIT: a SurfaceUnit");
 constexpr bool kUnitTex = PT_SURFACE_UNIT >= kTextureUnit, kUnitSmooth = PT_SURFACE_UNIT >= kSmoothUnit, kUnitRough = PT_SURFACE_UNIT >= kRoughUnit,
-               kUnitDirect = PT_SURFACE_UNIT >= kDirectUnit;
+               kUnitDirect = PT_SURFACE_UNIT >= kDirectUnit, kUnitEnvDirect = PT_SURFACE_UNIT >= kEnvDirectUnit;
 // ---------------------------------------------------------------------------------------------------------------
 // The dielectric kernels (pt_glass_kernels.hip: this file compiled with PT_SURFACE_UNIT 1, a translation unit of its own).  The body
 // with GLASS = true: a hit on a material the handle's table marks (RenderArgs::glass, pt_hip.h: pt_dielectric) reflects or refracts.
@@ -1629,18 +1648,29 @@ constexpr int direct_fewer_waves() {
     constexpr int twin = rough_unit_waves<MISS, BIG, STATS, FORM, VIEW>();
     return twin > 4 ? twin - 4 : 0;
 }
+// The environment-sampling kernels (pt_hip.h: environment sampling): the direct kernels of an environment
+// (MISS == 2, the wide form alone: an environment launch is planned as a skybox launch, which has no other form) with ENVDIRECT = true
+// too -- the shadow ray of a diffuse hit goes to the handle's emitters or, by the share, to a direction drawn from the environment's
+// alias table (RenderArgs::env_alias; pt_envdirect.hpp), and a miss after a diffuse step adds nothing.  The twin of such a kernel is
+// the direct kernel of the same arguments; waves per SIMD: that twin's minus envdirect_fewer_waves (tests/test_envdirect_resources.py
+// pins every kernel).
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+constexpr int envdirect_fewer_waves() {
+    return 0;
+}
 template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
 constexpr int unit_waves() {
     return view_waves<MISS != 0, BIG, STATS, FORM < 2, FORM == 1, VIEW>() - glass_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() -
            (kUnitTex ? texture_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) - (kUnitSmooth ? smooth_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) -
-           (kUnitRough ? rough_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) - (kUnitDirect ? direct_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0);
+           (kUnitRough ? rough_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) - (kUnitDirect ? direct_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) -
+           (kUnitEnvDirect ? envdirect_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0);
 }
 template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
 __global__ __launch_bounds__(kBlock, (unit_waves<MISS, BIG, STATS, FORM, VIEW>()))
 void PT_UNIT_KERNEL(const RenderArgs a) {
     constexpr bool SKY = MISS != 0, ENV = FORM < 2, NARROW = FORM == 1;
     constexpr int ADAPT = (FORM == 2 ? 2 : FORM == 3 ? 4 : 0) | (VIEW != 0 ? 1 : 0);
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true, TEX = kUnitTex, SMOOTH = kUnitSmooth, ROUGH = kUnitRough, DIRECT = kUnitDirect;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true, TEX = kUnitTex, SMOOTH = kUnitSmooth, ROUGH = kUnitRough, DIRECT = kUnitDirect, ENVDIRECT = kUnitEnvDirect;
 #include "pt_integrator_body.inc"
 }
 namespace {
@@ -1649,7 +1679,8 @@ constexpr int kGlassViews = plan::kViews + 1, kGlassPerView = 3 * 2 * 2 * 4;
 // does the build have the twin of that kernel?  (the 8 x 8 form and the batch kernels: plan::variant_exists)
 template <int MISS, bool BIG, bool STATS, int FORM>
 constexpr bool glass_kernel_exists() {
-    if constexpr (FORM == 0) return true;
+    if constexpr (kUnitEnvDirect) return MISS == 2 && FORM == 0;   // (the unit needs an environment)
+    else if constexpr (FORM == 0) return true;
     else if constexpr (MISS != 0 || STATS) return false;
     else return plan::variant_exists({false, BIG, false, FORM == 1, FORM == 1, FORM == 2 ? 2 : FORM == 3 ? 4 : 0, 1}, kBuild);
 }
@@ -1666,7 +1697,10 @@ const auto kGlassKernels = glass_kernel_table(std::make_integer_sequence<int, kG
 }  // namespace
 template <>
 hipError_t launch_surface_unit<PT_SURFACE_UNIT>(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
-    if (surface_unit_of(args) != PT_SURFACE_UNIT || (kUnitDirect && args.n_lights <= 0)) return hipErrorInvalidValue;
+    if (surface_unit_of(args) != PT_SURFACE_UNIT || (kUnitDirect && (kUnitEnvDirect ? args.n_lights < 0 : args.n_lights <= 0))) return hipErrorInvalidValue;
+    if (kUnitEnvDirect && (args.env_map == nullptr || args.env_cells < 1 || args.env_cells > kEnvSampleMaxCells || args.env_cells > args.env_n ||
+                           !(args.env_share > 0.0f && args.env_share <= 1.0f) || (args.n_lights == 0 && args.env_share != 1.0f) || args.lights == nullptr))
+        return hipErrorInvalidValue;
     if ((kUnitRough && args.rough_alpha == nullptr) || (kUnitSmooth && args.smooth_normals == nullptr)) return hipErrorInvalidValue;
     if (kUnitTex && (args.tex_recs == nullptr || args.tex_uv == nullptr || args.tex_texels == nullptr || args.tex_bary == nullptr)) return hipErrorInvalidValue;
     if (args.glass == nullptr || (args.env_map != nullptr && (!v.sky || args.sky != nullptr))) return hipErrorInvalidValue;
@@ -1922,8 +1956,8 @@ hipError_t launch_surface_integrator(int unit, const RenderArgs &args, const pla
     return hipErrorNotSupported;   // the diagnostic builds are linked without the surface units: a handle with one of their tables is refused (PT_ERR_UNSUPPORTED)
 #else
     constexpr decltype(&launch_surface_unit<kGlassUnit>) kLaunch[] = {&launch_surface_unit<kGlassUnit>, &launch_surface_unit<kTextureUnit>, &launch_surface_unit<kSmoothUnit>,
-                                                                      &launch_surface_unit<kRoughUnit>, &launch_surface_unit<kDirectUnit>};
-    return unit >= kGlassUnit && unit <= kDirectUnit ? kLaunch[unit - kGlassUnit](args, v, stream) : hipErrorInvalidValue;
+                                                                      &launch_surface_unit<kRoughUnit>, &launch_surface_unit<kDirectUnit>, &launch_surface_unit<kEnvDirectUnit>};
+    return unit >= kGlassUnit && unit <= kEnvDirectUnit ? kLaunch[unit - kGlassUnit](args, v, stream) : hipErrorInvalidValue;
 #endif
 }
 

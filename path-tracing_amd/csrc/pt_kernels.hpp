@@ -125,6 +125,14 @@ struct RenderArgs {
     const void *lights;
     int32_t n_lights;
     float light_area;
+    // The handle's environment sampling table (pt_hip.h: environment sampling), appended likewise.  env_alias != nullptr (only with
+    // env_map): the launch runs the environment-sampling kernels (integrate_kernel_envdirect, pt_envdirect_kernels.hip: the direct
+    // kernels whose shadow ray goes to the emitters or, with probability env_share, to a direction drawn from the environment).  lights
+    // is then never null: a handle without emitters passes one all-zero record with n_lights = 0 and env_share = 1.  env_cells^2
+    // records of 16 bytes (pt_envdirect.hpp: EnvAliasRec).
+    const void *env_alias;
+    int32_t env_cells;
+    float env_share;
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif
@@ -132,12 +140,12 @@ struct RenderArgs {
 
 // The constants the kernels of this library were compiled with: what plan::plan_tiles needs to know of the build.
 const plan::Build &integrator_build();
-// The surface units: translation units of their own (pt_glass_kernels.hip ... pt_direct_kernels.hip), each the unit below it with
+// The surface units: translation units of their own (pt_glass_kernels.hip ... pt_envdirect_kernels.hip), each the unit below it with
 // one more table read where a ray has hit a surface.  A launch needs the unit of the highest table its arguments hold, and every
 // table below that one is then never null (a handle without it passes an all-zero table).
-enum SurfaceUnit : int { kNoSurfaceUnit = 0, kGlassUnit, kTextureUnit, kSmoothUnit, kRoughUnit, kDirectUnit };
+enum SurfaceUnit : int { kNoSurfaceUnit = 0, kGlassUnit, kTextureUnit, kSmoothUnit, kRoughUnit, kDirectUnit, kEnvDirectUnit };
 inline int surface_unit_of(const RenderArgs &a) {
-    return a.lights ? kDirectUnit : a.rough_alpha ? kRoughUnit : a.smooth_normals ? kSmoothUnit : a.tex_recs ? kTextureUnit : a.glass ? kGlassUnit : kNoSurfaceUnit;
+    return a.env_alias ? kEnvDirectUnit : a.lights ? kDirectUnit : a.rough_alpha ? kRoughUnit : a.smooth_normals ? kSmoothUnit : a.tex_recs ? kTextureUnit : a.glass ? kGlassUnit : kNoSurfaceUnit;
 }
 // launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds) -- with args.projection != 0
 // the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan;

@@ -41,6 +41,8 @@ int make_list(const pt_scene *scene, const pt_texture *list, int32_t n, std::sha
             return refuse(who + "material " + std::to_string(e.material) + " is a dielectric");
         if (scene->surface.direct && ptc::material_is_light(mats[e.material]))
             return refuse(who + "material " + std::to_string(e.material) + " is a light of the handle's direct lighting");
+        if (scene->surface.envdirect && ptc::material_is_light(mats[e.material]))
+            return refuse(who + "material " + std::to_string(e.material) + " is a light of the handle's environment sampling");
         const uint64_t texels = static_cast<uint64_t>(e.width) * static_cast<uint64_t>(e.height);
         if (total + texels > pt::kTexMaxTexels) return refuse(who + "the list holds more than 2^28 texels");
         for (uint64_t k = 0; k < 3 * texels; ++k)

@@ -65,8 +65,14 @@
 // Direct lighting (pt_scene_set_direct_lighting, not in the reference): -DIRECT 1 sends a shadow ray to a sampled point of a light at
 // every scattering diffuse hit and counts every path once (pt_hip.h: direct lighting); -DIRECT 0 is a run without the flag.  Any
 // other value, a model without a light and an emissive material that -TEXTURE lists end the program with status 2.  Every other flag
-// combines.  Not built: multiple importance sampling, sampling by power, environment importance sampling, direct terms for the GGX
-// lobe, textured emitters, Russian roulette.
+// combines.  Not built: multiple importance sampling, sampling by power, direct terms for the GGX lobe, textured emitters, Russian
+// roulette.
+// Environment sampling (pt_scene_set_environment_sampling, not in the reference): -DIRECT_ENV 1, with -ENV, sends the shadow ray of every
+// scattering diffuse hit to a direction drawn from the environment in proportion to its radiance or -- where the model has emitters --
+// to a point of a light, the environment with probability -DIRECT_ENV_SHARE p (0 < p < 1; default: by the two sources' power, within
+// 1/8 .. 7/8), and counts every path once (pt_hip.h: environment sampling); -DIRECT_ENV 0 is a run without the flag.  A missing -ENV, a
+// -SKYBOX, a share outside the range, a black environment and an emissive material that -TEXTURE lists end the program with status 2.
+// Every other flag combines, -DIRECT too.  Not built: multiple importance sampling with the diffuse lobe, a term for the GGX lobe.
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -198,6 +204,9 @@ struct Options {
     std::string rough_text;                // -ROUGH as given
     std::string direct_text;               // -DIRECT as given
     bool direct = false;
+    std::string direct_env_text, direct_env_share_text;   // -DIRECT_ENV, -DIRECT_ENV_SHARE as given
+    bool direct_env = false;
+    float direct_env_share = 0.0f;         // 0 = the library's default
     std::vector<pt_rough> rough;           // what it makes (empty with -ROUGH mtl: the model's MTL decides)
     bool rough_mtl = false;
     std::string smooth_text, crease_text;  // -SMOOTH / -CREASE as given
@@ -315,6 +324,8 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-GLASS") o.glass_text = v;
         if (f == "-ROUGH") o.rough_text = v;
         if (f == "-DIRECT") o.direct_text = v;
+        if (f == "-DIRECT_ENV") o.direct_env_text = v;
+        if (f == "-DIRECT_ENV_SHARE") o.direct_env_share_text = v;
         if (f == "-SMOOTH") o.smooth_text = v;
         if (f == "-CREASE") o.crease_text = v;
         if (f == "-TEXTURE") o.texture_text = v;
@@ -524,6 +535,18 @@ int configure(int argc, char **argv, Options &o) {
         if (o.direct_text != "0" && o.direct_text != "1") return refuse(2, "-DIRECT takes 0 or 1, not \"" + o.direct_text + "\"");
         o.direct = o.direct_text == "1";
     }
+    // -DIRECT_ENV 0 | 1 and -DIRECT_ENV_SHARE p: the environment's share of the shadow rays, strictly between 0 and 1
+    if (!o.direct_env_text.empty()) {
+        if (o.direct_env_text != "0" && o.direct_env_text != "1") return refuse(2, "-DIRECT_ENV takes 0 or 1, not \"" + o.direct_env_text + "\"");
+        o.direct_env = o.direct_env_text == "1";
+    }
+    if (!o.direct_env_share_text.empty()) {
+        if (!o.direct_env) return refuse(2, "-DIRECT_ENV_SHARE needs -DIRECT_ENV 1");
+        if (!parse_float(o.direct_env_share_text, o.direct_env_share) || !(o.direct_env_share > 0.0f && o.direct_env_share < 1.0f))
+            return refuse(2, "-DIRECT_ENV_SHARE takes a number strictly between 0 and 1, not \"" + o.direct_env_share_text + "\"");
+    }
+    if (o.direct_env && !o.skybox.empty()) return refuse(2, "-DIRECT_ENV samples an environment (-ENV), not a -SKYBOX");
+    if (o.direct_env && o.env.empty()) return refuse(2, "-DIRECT_ENV needs -ENV");
     // -ROUGH: "mtl", or entries m:alpha separated by commas; alpha's range is the library's (pt_hip.h: rough specular)
     if (o.rough_text == "mtl") o.rough_mtl = true;
     for (size_t at = 0; !o.rough_text.empty() && !o.rough_mtl && at <= o.rough_text.size();) {
@@ -1337,6 +1360,11 @@ int main(int argc, char **argv) {
     }
     // -DIRECT 1: after -TEXTURE, so that a textured emitter is refused with the library's words, as a model without a light is
     if (o.direct && pt_scene_set_direct_lighting(r.scene, 1) != PT_OK) return refuse(2, std::string("-DIRECT: ") + pt_last_error());
+    // -DIRECT_ENV 1: likewise, after -ENV and -TEXTURE
+    if (o.direct_env) {
+        const pt_env_sampling sampling = {o.direct_env_share};
+        if (pt_scene_set_environment_sampling(r.scene, &sampling) != PT_OK) return refuse(2, std::string("-DIRECT_ENV: ") + pt_last_error());
+    }
     if (o.camera && pt_scene_set_camera(r.scene, &o.view) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
     // and its projection -- set before the lens and the motion, which the library refuses on a handle with one, as it refuses the
     // temporal stage when the first frame reaches it: asked here, before any device is looked at, with the library's own words
