@@ -5,6 +5,7 @@
 #include "pt_bmp.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -16,6 +17,8 @@
 
 // Overrides of the launch plan: set by pt_test_set_mutation in the test builds, never in the product (which has no such entry point).
 static pt::plan::Overrides g_plan_overrides;
+// plan::variant_id of the kernel the last enqueued launch took (-1: none yet); the test builds export it as pt_test_last_variant.
+static std::atomic<int> g_last_variant{-1};
 
 namespace ptc {
 
@@ -412,7 +415,9 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     // one wave = one tile of 8 rows; how many pixels wide depends on the kernel this launch runs
     const bool sky = a.sky != nullptr || a.env_map != nullptr;   // (an environment launch is planned as the skybox launch it would be)
     const pt::plan::Tiles tiles = pt::plan::plan_tiles({a.width, a.band_rows, sky, a.big != 0, want_stats, a.may_leave_envelope != 0, a.error,
-                                                        a.pass_begin, a.pass_count, pt::plan::view_of(a.camera != 0, a.lens != 0, a.motion != 0), scene->cu_count},
+                                                        a.pass_begin, a.pass_count, pt::plan::view_of(a.camera != 0, a.lens != 0, a.motion != 0), scene->cu_count,
+                                                        // (the scene's flag, and a handle with nothing a plain launch does not read)
+                                                        scene->cull.host->room && a.env_map == nullptr && a.projection == 0 && pt::surface_unit_of(a) == pt::kNoSurfaceUnit},
                                                        pt::integrator_build(), ov);
     a.narrow = tiles.narrow;
     a.adapt_pool = tiles.adapt_pool;
@@ -445,6 +450,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
         return fail(PT_ERR_UNSUPPORTED, std::string(w[0]) + ": this diagnostic build of the library has no " + w[1] + " kernels");
     }
     PT_HIP_TRY(launched);
+    g_last_variant.store(pt::plan::variant_id(tiles.variant), std::memory_order_relaxed);
     if (want_stats) PT_HIP_TRY(hipEventRecord(ctx.ev1.get(), stream));
     PT_HIP_TRY(hipEventRecord(ctx.ev_done.get(), stream));
     ctx.has_prev = true;
@@ -1540,7 +1546,8 @@ int pt_post_filter_host(int device, int32_t width, int32_t height, float *rgb, i
 // Scheduler / instantiation choices of launches enqueued afterwards: "items_per_slot" (n > 0: equal pass chunks, about n work items
 // per wave slot; < 0: the 3/4 - of - the - rest chunks always; 0: the library's rule), "chunk_min" (the smallest last chunk of that
 // scheme), "tile_width" (1: 8 x 8 tiles always; 2: 16 x 8 where the instantiation has them, batches over 16 x 8 tiles for adaptive
-// launches; 3: the same with 32 x 8 batch tiles; 0: by tile count), "regen_min_dead" (path regeneration threshold).
+// launches; 3: the same with 32 x 8 batch tiles; 0: by tile count), "regen_min_dead" (path regeneration threshold), "no_room_kernel"
+// (1: a room-shaped scene, CullTables::room, runs the generic kernel too; 0: the room kernel).
 // Test builds only: the box tree's child test (pt_kernels.hip: box_children_kept) on n caller-supplied items -- nodes:
 // n x 64 bytes (BvhNode), rays: n x 6 floats (origin, unit direction), t_best: n floats -- out: n masks, one per item.
 // Host pointers; device 0.
@@ -1564,6 +1571,10 @@ int pt_test_box_masks(const void *nodes, const float *rays, const float *t_best,
 }
 
 long pt_test_live_device_objects(void) { return ptc::g_live_device_objects.load(std::memory_order_relaxed); }
+
+// The kernel the last enqueued integrator launch took, as the plan names it: plan::variant_id (pt_launch_plan.hpp; the two room
+// kernels are kAllVariants = 120, wide, and 121, narrow), -1 before the first launch.
+int pt_test_last_variant(void) { return g_last_variant.load(std::memory_order_relaxed); }
 
 int pt_test_set_mutation(const char *family, double value) {
     if (!family) return PT_ERR_INVALID_ARGUMENT;
@@ -1590,6 +1601,7 @@ int pt_test_set_mutation(const char *family, double value) {
     else if (f == "max_clusters") m.max_clusters = static_cast<int>(value);
     else if (f == "items_per_slot") g_plan_overrides.items_per_slot = static_cast<int>(value);
     else if (f == "tile_width") g_plan_overrides.tile_width = static_cast<int>(value);
+    else if (f == "no_room_kernel") g_plan_overrides.no_room_kernel = value != 0;
     else return fail(PT_ERR_INVALID_ARGUMENT, "unknown mutation family " + f);
     return PT_OK;
 }

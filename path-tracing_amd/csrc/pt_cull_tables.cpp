@@ -1131,6 +1131,17 @@ void fill_emitter_masks(const HostScene &s, int n_small_slots, CullTables &out) 
         for (uint32_t k = 0; k < static_cast<uint32_t>(n_small_slots); ++k) out.emis_bvh = out.emis_bvh || emits(k);
 }
 
+// Clauses 1-4 of "room-shaped" (pt_scene.hpp: CullTables::room, where each clause has its reason).
+bool room_shaped(const CullTables &t) {
+    if (t.big || !t.bvh.empty()) return false;                                          // 1. a small scene
+    if (t.clusters.empty() || t.clusters.size() > 2) return false;                      // 4. the large class and at most one more cluster ...
+    const ClusterDesc &large = t.clusters.back();
+    if (large.kind != 1u || large.n_tri == 0 || large.n_tri > static_cast<uint32_t>(kChunk)) return false;   // 2. one chunk word
+    const uint32_t pair_bits = 0x55555555u & (large.n_tri >= 32u ? 0xFFFFFFFFu : ((1u << large.n_tri) - 1u));
+    if (large.level_off[0] != pair_bits) return false;                                  // 3. every record a quad (what the kernel tests as quads == pair_bits)
+    return t.clusters.size() == 1 || t.clusters.front().kind == 0u;                     // 4. ... which is a sphere tree
+}
+
 }  // namespace
 
 double vertex_extent(const HostScene &s) {
@@ -1192,6 +1203,7 @@ void build_cull_tables(const HostScene &s, float eps_f, CullTables &out, double 
     out.cc_all.t_guard = all.t_guard;
 
     fill_emitter_masks(s, n_small_slots, out);
+    out.room = room_shaped(out);
 }
 
 }  // namespace pt

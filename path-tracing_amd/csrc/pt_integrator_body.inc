@@ -17,8 +17,13 @@
 // ENVDIRECT (only pt::integrate_kernel_envdirect: false in every other kernel; with DIRECT and ENVMAP) = the shadow ray of a diffuse hit
 // goes, with probability RenderArgs::env_share, to a direction drawn from the environment's alias table, and counts if it misses; a
 // miss after a diffuse step adds nothing (pt_hip.h: environment sampling; pt_envdirect.hpp spells the sample and the term).
-    constexpr int POOL = ADAPT & ~1;
+    constexpr int POOL = ADAPT & 6;
     constexpr bool CAM = (ADAPT & 1) != 0;
+    // ROOM (bit 3 of ADAPT; only pt::integrate_kernel<false, false, false, false, NARROW, 8>, pt_room_kernels.hip): the search of a room-shaped scene
+    // (pt_scene.hpp: CullTables::room) without its generic loops -- closest_hit<..., ROOM>.  Nothing else of the body differs.
+    constexpr bool ROOM = (ADAPT & 8) != 0;
+    static_assert(!ROOM || (ADAPT == 8 && !SKY && !BIG && !STATS && !ENV && !LENS && !MOTION && !PROJ && !ENVMAP && !GLASS && !TEX && !SMOOTH && !ROUGH && !DIRECT && !ENVDIRECT),
+                  "the room instantiations are forms of the statistics-free plain small-scene kernel alone");
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
     static_assert(!DIRECT || (SMOOTH && ROUGH), "the direct term is written in the smooth scatter step: a direct kernel is a rough kernel with DIRECT");
     static_assert(!ENVDIRECT || (DIRECT && ENVMAP), "an environment-sampling kernel is a direct kernel with an environment");
@@ -674,7 +679,7 @@
             }
             for (;;) {
                 if (BIG && !any_of(searched)) break;
-                closest_hit<ENV, kLastSegmentFilter, kDynSlots>(a, lds, q, searched, inside, lane, eps, best, hit, hit_rec, wst, emis_phase, two);
+                closest_hit<ENV, kLastSegmentFilter, kDynSlots, ROOM>(a, lds, q, searched, inside, lane, eps, best, hit, hit_rec, wst, emis_phase, two);
                 if (!emis_phase) break;
                 emis_phase = false;
 #pragma unroll

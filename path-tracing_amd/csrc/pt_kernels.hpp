@@ -154,6 +154,8 @@ inline int surface_unit_of(const RenderArgs &a) {
 hipError_t launch_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // the environment kernels' translation unit (pt_environment_kernels.hip); launch_integrator calls it, nothing else does
 hipError_t launch_environment_integrator(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
+// The room kernel (pt_room_kernels.hip), wide or 8 x 8; nullptr if the build has none.
+void (*room_kernel(bool narrow))(const RenderArgs);
 // the surface units' translation units, likewise (hipErrorNotSupported from a diagnostic build, which is linked without them)
 hipError_t launch_surface_integrator(int unit, const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 // waves of kernel `v` that one compute unit holds at a time (runtime occupancy query, cached).  A projection launch asks for its

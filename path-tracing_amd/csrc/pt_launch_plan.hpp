@@ -22,12 +22,16 @@ struct Build {
 // One integrator kernel.  view: 0 = camera-free, 1 = its camera twin, 2 = the lens kernel of that twin, 3 / 4 = the motion twins
 // of 1 / 2 (pt_hip.h: camera motion -- the camera interpolated between two poses at a time drawn per path).
 // pool: 0, or 2 / 4 = the adaptive-sampling kernel that runs batches over 16 x 8 / 32 x 8 tiles.
+// room: the room instantiation of the statistics-free plain small-scene kernel (wide or narrow; everything else false / 0): the
+// search without its generic loops, for scenes whose tables say CullTables::room (pt_scene.hpp).
 struct Variant {
     bool sky, big, stats, env, narrow;
     int pool, view;
+    bool room = false;
 };
 constexpr bool operator==(const Variant &a, const Variant &b) {
-    return a.sky == b.sky && a.big == b.big && a.stats == b.stats && a.env == b.env && a.narrow == b.narrow && a.pool == b.pool && a.view == b.view;
+    return a.sky == b.sky && a.big == b.big && a.stats == b.stats && a.env == b.env && a.narrow == b.narrow && a.pool == b.pool && a.view == b.view &&
+           a.room == b.room;
 }
 
 // rays per lane of a kernel's wide form: the launch geometry (tile width) follows from it
@@ -44,10 +48,14 @@ constexpr int kStillVariants = 3 * kVariantsPerView, kVariants = kStillVariants;
 constexpr int view_of(bool camera, bool lens, bool motion) { return motion ? (lens ? 4 : 3) : lens ? 2 : camera ? 1 : 0; }
 constexpr bool view_has_lens(int view) { return view == 2 || view == 4; }
 constexpr bool view_has_motion(int view) { return view == 3 || view == 4; }
+// The two room kernels (wide, narrow) have the ids after every view's: a table indexed by id has kKernelIds entries.
+constexpr int kRoomVariants = 2, kKernelIds = kAllVariants + kRoomVariants;
 constexpr int variant_id(const Variant &v) {
+    if (v.room) return kAllVariants + v.narrow;
     return kVariantsPerView * v.view + (v.narrow ? 16 + 2 * v.big + v.env : v.pool ? 20 + 2 * v.big + (v.pool == 4) : ((v.sky * 2 + v.big) * 2 + v.stats) * 2 + v.env);
 }
 constexpr Variant variant_of(int id) {
+    if (id >= kAllVariants) return {false, false, false, false, id - kAllVariants == 1, 0, 0, true};
     const int view = id / kVariantsPerView, r = id % kVariantsPerView;
     if (r < 16) return {(r & 8) != 0, (r & 4) != 0, (r & 2) != 0, (r & 1) != 0, false, 0, view};
     if (r < 20) return {false, (r & 2) != 0, false, (r & 1) != 0, true, 0, view};
@@ -56,6 +64,10 @@ constexpr Variant variant_of(int id) {
 // Is that kernel part of a build?  The 8 x 8 form exists of the kernels with two pixels per lane; the batch kernels are not
 // built with the rare envelope test (one more spilled register there), the small-scene ones only as a form of the two-pixel kernel.
 constexpr bool variant_exists(const Variant &v, const Build &b) {
+    if (v.room) {   // a form of the plain statistics-free small-scene kernel, where the build has that one
+        if (b.wide_only || v.sky || v.big || v.stats || v.env || v.pool || v.view != 0) return false;
+        return !v.narrow || rays_per_lane(b, false, false, false) > 1;
+    }
     if (b.wide_only && (v.narrow || v.pool || v.view != 0)) return false;
     if (!v.narrow && !v.pool) return true;
     if (v.sky || v.stats || (v.pool && v.env)) return false;
@@ -68,6 +80,7 @@ struct Overrides {
     int items_per_slot = 0;   // equal chunks with about that many work items per wave slot (< 0: never equal chunks), 0 = by tile count
     int chunk_min = 0;        // passes the scheduler's last geometric chunk holds at least (0 = the library's)
     int regen_min_dead = 0;   // overrides RenderArgs::regen_min_dead (0 = the library's)
+    int no_room_kernel = 0;   // 1 = a room-shaped scene runs the generic kernel too (the A/B and the yardstick of the room kernel's tests), 0 = by the scene's flag
 };
 
 struct Launch {
@@ -77,6 +90,7 @@ struct Launch {
     int pass_begin, pass_count;
     int view;
     int cu_count;
+    bool room = false;   // the scene's tables say CullTables::room and its handle has nothing a plain launch does not read (no environment, projection or surface table)
 };
 
 struct Tiles {
@@ -120,6 +134,10 @@ inline Tiles plan_tiles(const Launch &l, const Build &b, const Overrides &o = {}
     }
     t.variant.narrow = t.narrow != 0;
     t.variant.pool = t.adapt_pool;
+    // A room-shaped scene: the room form of the plain statistics-free small-scene kernel, in whichever tile width was picked above.
+    // Statistics, adaptive sampling (error >= 0: batches or not), the envelope test and the camera twins keep the generic kernel.
+    t.variant.room = l.room && !o.no_room_kernel && !b.wide_only && !l.sky && !l.big && !stats && !l.may_leave_envelope && l.error < 0.0f &&
+                     l.view == 0 && t.adapt_pool == 0;
     const int tile_px = t.adapt_pool ? t.adapt_pool : rays;   // tile width in 8-pixel column blocks
     t.blocks_x = (l.width + b.tile_w * tile_px - 1) / (b.tile_w * tile_px);
     t.n_tiles = static_cast<uint32_t>(t.blocks_x) * rows;

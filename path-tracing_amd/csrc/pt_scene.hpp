@@ -168,6 +168,22 @@ struct CullTables {
     uint32_t emis_clusters = 0xFFFFFFFFu;  // bit c: cluster c (< 32) holds an emitter; clusters >= 32 count as holding one
     uint32_t emis_large_w0 = 0xFFFFFFFFu;  // large class of at most 32 slots: its emitters (all ones if the class is larger)
     bool emis_bvh = true;                  // the box tree of a big scene holds an emitter
+    // ROOM-SHAPED: a room with at most one object in it -- the reference's own kind of scene (Tor.obj).  Such a scene's launches run
+    // the room instantiations of the plain small-scene kernel (pt_kernels.hip: closest_hit<..., ROOM>), whose cull stage is one
+    // straight sequence with no loop over clusters, class words or record kinds.  A scene is room-shaped iff ALL of these hold:
+    //   1. it is a small scene (!big, no box tree): only the small-scene kernels have sphere trees and the last-segment filter
+    //      the room kernel is a form of;
+    //   2. it has a large class, and that class is exactly ONE chunk word (at most kChunk slots): the kernel reads one quad mask,
+    //      one emitter word (emis_large_w0) and publishes one window of candidates;
+    //   3. every record of that word is a quad record (the kernel's run-time test `quads == pair_bits`): the kernel has no
+    //      single-triangle record path and no per-record dispatch, and a class of whole quads has no ragged end to mask;
+    //   4. besides the large class (always the LAST cluster) it has at most one cluster, a sphere tree (kind 0), or none (an
+    //      empty room): the kernel walks cluster 0 if there are two clusters and has no loop;
+    //   5. it has no skybox and no environment.  The tables do not know that -- both belong to the handle -- so this clause is
+    //      the launch's: plan::plan_tiles takes the room kernel only for a launch without either (pt_launch_plan.hpp), together
+    //      with what else a launch decides (statistics, adaptive sampling, the camera, the envelope test).
+    // Clauses 1-4 are decided here, once, where the tables are built (room_shaped in pt_cull_tables.cpp).
+    bool room = false;
 };
 
 #ifdef PT_TEST_HOOKS
