@@ -1863,8 +1863,8 @@ int pt_rough_step(int32_t n, const float *normals, const float *directions, cons
  * Statistics under the switch: samples_traced, segments and misses count path segments only (no shadow ray); contributing counts the
  * terms added to any L.
  *
- * Not built: multiple importance sampling, sampling by power, direct terms for the GGX lobe, textured emitters, Russian roulette.
- * (Sampling the environment is a switch of its own: environment sampling, below.)
+ * Not built: multiple importance sampling, sampling by power, direct terms for the GGX lobe, textured emitters.
+ * (Sampling the environment and Russian roulette are switches of their own: environment sampling and Russian roulette, below.)
  *
  * PT_ERR_INVALID_ARGUMENT: a NULL handle; switching on for a scene without a light; switching on while an emissive material is in the
  * handle's texture list -- and pt_scene_set_textures refuses such a material in turn while the switch is on.  A setter builds and
@@ -1982,6 +1982,51 @@ int pt_envdirect_term(int32_t n, const pt_env_sample_record *records, int32_t ce
                       const float *normals, const float *shading_normals, const float *throughput, const float *kd, const uint32_t *e0,
                       const uint32_t *e1, const uint32_t *e2, const uint32_t *e3, int32_t *out_cell, float *out_directions, float *out_pdf,
                       float *out_terms, int32_t *out_has_term);
+
+/* ---- Russian roulette: unbiased path termination under per-path accounting ------------------------------------------------- */
+
+/* A scene handle that has direct lighting or environment sampling on may have RUSSIAN ROULETTE set: two parameters, `start`, an
+ * integer >= 1, and `floor`, a float in [2^-10, 1].  From its start on, every scattering step ends a path with a probability that
+ * follows its throughput and divides the survivors by the probability of surviving, so sum / count stays the unbiased estimate of
+ * what the same handle renders without it at the same mrr, while the depth cap can be raised until it no longer matters.  The
+ * parameters belong to the handle: pt_scene_clone_to_device and pt_frame_create inherit them.  It works with everything the two
+ * switches work with; launches are planned as without it (tiles, pass chunks), and the closed-room wide and 8 x 8 kernels regenerate
+ * paths as the skybox kernels do.  Without it every output is what it was and the launches go to the kernels they went to.  The
+ * diagnostic builds (phase timers, block profile) have no such kernels: PT_ERR_UNSUPPORTED there.
+ *
+ * THE STEP runs at the end of a scattering step -- diffuse, mirror, GGX or dielectric alike --, after the throughput T has taken the
+ * lobe's factor (tr *= fr; tg *= fg; tb *= fb) and before depth is incremented, if and only if depth + 1 >= start and a next ray will
+ * be traced (depth + 1 < mrr: the condition the scattering step itself is under).  Float operations rounded once in the order written,
+ * nothing fused, / correctly rounded:
+ *   m = max(max(|tr|, |tg|), |tb|), a NaN propagating  (absolute values: a material may carry any Kd)
+ *   !(m < 1.0f): the path survives unchanged  (a NaN lands here)
+ *   p = m < floor ? floor : m
+ *   (w0, ..) = philox(pixel, pass, depth, 5), depth as it is before the increment: the fourth counter word is 5 (0: the segment's, the
+ *     jitter's and the shutter's words; 1, 2: the display's dither and grain; 3: the direct term; 4: environment sampling).  The call
+ *     need only be made where the word is used, and no other random number moves.
+ *   unit_float(w0) < p:  tr = tr / p; tg = tg / p; tb = tb / p  (three divisions, not a reciprocal)
+ *   else:                tr = tg = tb = 0
+ * A path with throughput zero is over: its L goes to the accumulators once, as PER-PATH ACCOUNTING says -- with the verdict of a
+ * shadow ray the same hit left pending, where there is one.  The direct term of the same hit was formed from the throughput before
+ * the lobe's factor and is not touched.  With start >= mrr the step never runs and the frame is the frame without roulette, bit for
+ * bit.  Statistics as under direct lighting.
+ *
+ * Not built: multiple importance sampling, a survival probability from anything but the throughput (luminance, an estimate of the
+ * radiance ahead), path splitting.
+ *
+ * PT_ERR_INVALID_ARGUMENT: a NULL handle; start < 0; a floor outside [2^-10, 1] or not finite (with start > 0); a handle with neither
+ * direct lighting nor environment sampling on.  start == 0 clears (the floor is then not looked at).  While roulette is set, switching
+ * off the last of the two switches is refused: clear the roulette first.  A refused call leaves every handle as it was. */
+#define PT_ROULETTE_DEFAULT_FLOOR 0.0625f
+int pt_scene_set_roulette(pt_scene *scene, int32_t start, float floor);
+/* *start = 0 (not set) or the start; *floor (may be NULL) the floor, 0 where not set. */
+int pt_scene_get_roulette(const pt_scene *scene, int32_t *start, float *floor);
+/* The same on a frame: every device's copy of the frame's scene; a refused call changes none.  The getter answers for the root's. */
+int pt_frame_set_roulette(pt_frame *frame, int32_t start, float floor);
+int pt_frame_get_roulette(pt_frame *frame, int32_t *start, float *floor);
+/* THE STEP alone, on the host, for n paths: throughput (3 n floats) and the words w0 (n) under `floor` give out_throughput (3 n) and
+ * out_survives (n: 1 unless the step ended the path). */
+int pt_roulette_step(int32_t n, float floor, const float *throughput, const uint32_t *w0, float *out_throughput, int32_t *out_survives);
 
 /* ---- misc ------------------------------------------------------------------------------------------- */
 int pt_abi_version(void);

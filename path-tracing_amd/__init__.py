@@ -75,7 +75,8 @@ ABI_SYMBOLS = ["pt_scene_load_obj", "pt_scene_create", "pt_scene_counts", "pt_sc
                "pt_frame_get_direct_lighting", "pt_frame_get_lights", "pt_direct_term",
                "pt_scene_set_environment_sampling", "pt_scene_get_environment_sampling", "pt_scene_get_environment_sampling_table",
                "pt_frame_set_environment_sampling", "pt_frame_get_environment_sampling", "pt_frame_get_environment_sampling_table",
-               "pt_envdirect_term"]
+               "pt_envdirect_term",
+               "pt_scene_set_roulette", "pt_scene_get_roulette", "pt_frame_set_roulette", "pt_frame_get_roulette", "pt_roulette_step"]
 FRAME_REHEARSE, FRAME_SELF_COLLECTIVE = 1, 2
 BIG_SCENE_TRIANGLES = 1024     # csrc/pt_scene.hpp: kBigSceneTriangles -- scenes above it take the box-tree path (tests/test_abi_host.py compares)
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "device_copies"}
@@ -588,6 +589,23 @@ def envdirect_term(records, share, env_map, normals, shading_normals, throughput
     return cell, dirs, pdf, terms, has.astype(bool)
 
 
+ROULETTE_DEFAULT_FLOOR = 1.0 / 16.0   # pt_hip.h: PT_ROULETTE_DEFAULT_FLOOR
+
+
+def roulette_step(throughput, w0, floor=ROULETTE_DEFAULT_FLOOR, library=None):
+    """pt_roulette_step, the host's own evaluation of the roulette step (pt_hip.h: Russian roulette): throughputs T [n, 3] and the
+    words w0 [n] under `floor` give the throughputs after the step [n, 3] and whether each path survives [n]."""
+    L = library or lib()
+    t = np.ascontiguousarray(throughput, np.float32).reshape(-1, 3)
+    w = np.ascontiguousarray(w0, np.uint32).reshape(-1)
+    if len(t) != len(w):
+        raise ValueError("roulette_step: arrays of one length")
+    out, alive = np.zeros_like(t), np.zeros(len(t), np.int32)
+    _check(L.pt_roulette_step(len(t), C.c_float(floor), _fp(t), w.ctypes.data_as(C.POINTER(C.c_uint32)), _fp(out),
+                              alive.ctypes.data_as(C.POINTER(C.c_int32))), L)
+    return out, alive.astype(bool)
+
+
 TEXTURE_NEAREST, TEXTURE_BILINEAR = 0, 1
 TEXTURE_MAX_SIDE = 8192
 _TEXTURE_FILTERS = {"nearest": TEXTURE_NEAREST, "bilinear": TEXTURE_BILINEAR}
@@ -691,7 +709,10 @@ def build(force=False):
     """Compile libpt_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
     if force:
         subprocess.check_call(["make", "-C", CSRC_DIR, "clean", "-s"])
-    subprocess.check_call(["make", "-C", CSRC_DIR, "-s", "-j4"])   # the product library + the test / diagnostic builds
+    # the product library + the test / diagnostic builds.  Eight jobs where the machine has them: every library is ten kernel objects of one
+    # to five minutes each, and at four jobs the build took as long as the slowest library's objects in a row.
+    jobs = max(1, min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
+    subprocess.check_call(["make", "-C", CSRC_DIR, "-s", f"-j{jobs}"])
     return LIB_PATH
 
 
@@ -835,6 +856,9 @@ def load_library(path):
         getattr(L, f"pt_{who}_set_environment_sampling").argtypes = [vp, C.POINTER(C.c_float)]
         getattr(L, f"pt_{who}_get_environment_sampling").argtypes = [vp, ip, C.POINTER(C.c_float)]
         getattr(L, f"pt_{who}_get_environment_sampling_table").argtypes = [vp, vp, ip, C.POINTER(C.c_float)]
+        getattr(L, f"pt_{who}_set_roulette").argtypes = [vp, C.c_int32, C.c_float]
+        getattr(L, f"pt_{who}_get_roulette").argtypes = [vp, ip, C.POINTER(C.c_float)]
+    L.pt_roulette_step.argtypes = [C.c_int32, C.c_float, fp, C.POINTER(C.c_uint32), fp, ip]
     L.pt_envdirect_term.argtypes = [C.c_int32, vp, C.c_int32, C.c_float, C.c_int32, fp, fp, fp, fp, fp] + [C.POINTER(C.c_uint32)] * 4 + [ip, fp, fp, fp, ip]
     L.pt_direct_term.argtypes = [C.c_int32, vp, C.c_int32, C.c_float, fp, fp, fp, fp, fp] + [C.POINTER(C.c_uint32)] * 3 + [ip, fp, fp, fp, ip]
     L.pt_rough_step.argtypes = [C.c_int32, fp, fp, fp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), fp, fp, fp]
@@ -1089,6 +1113,27 @@ class _EnvDirectMethods:
         return arr, np.float32(share.value)
 
 
+class _RouletteMethods:
+    """set_roulette / roulette of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
+    _roulette_prefix = "pt_scene_"
+
+    def set_roulette(self, start=3, floor=ROULETTE_DEFAULT_FLOOR):
+        """-RR: sets Russian roulette (pt_hip.h: Russian roulette) from scattering step `start` (>= 1) on with the floor `floor` in
+        [2^-10, 1] on the survival probability; None or 0 clears it.  Refused: a handle with neither direct lighting nor environment
+        sampling on, a negative start, a floor out of range."""
+        fn = getattr(self._L, self._roulette_prefix + "set_roulette")
+        if start is None or start is False:
+            _check(fn(self._h, 0, C.c_float(0.0)), self._L)
+        else:
+            _check(fn(self._h, int(start), C.c_float(float(floor))), self._L)
+
+    def roulette(self):
+        """None where roulette is not set, else (start, floor)."""
+        start, floor = C.c_int32(), C.c_float()
+        _check(getattr(self._L, self._roulette_prefix + "get_roulette")(self._h, C.byref(start), C.byref(floor)), self._L)
+        return (start.value, np.float32(floor.value)) if start.value > 0 else None
+
+
 class _TextureMethods:
     """set_texcoords / texcoords / set_textures / textures of a Scene (pt_scene_*) and of a Frame (pt_frame_*: every device's copy)."""
     _tex_prefix = "pt_scene_"
@@ -1168,7 +1213,7 @@ class _SmoothMethods:
         return scene._normals(scene._L.pt_scene_get_vertex_normals)
 
 
-class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods, _EnvDirectMethods):
+class Scene(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods, _EnvDirectMethods, _RouletteMethods):
     """Owns a pt_scene handle (Scene + LoadModel of the reference, scene.h:17-19)."""
 
     def __init__(self, handle, library=None):
@@ -1915,9 +1960,9 @@ def bvh_depth(nodes):
     return int(level.max())
 
 
-class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods, _EnvDirectMethods):
+class Frame(_EnvironmentMethods, _DielectricMethods, _TextureMethods, _SmoothMethods, _RoughMethods, _DirectMethods, _EnvDirectMethods, _RouletteMethods):
     """pt_frame: one image on several devices from one host program -- row bands, one gather to the first device."""
-    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = _rough_prefix = _direct_prefix = _envdirect_prefix = "pt_frame_"
+    _env_prefix = _glass_prefix = _tex_prefix = _smooth_prefix = _rough_prefix = _direct_prefix = _envdirect_prefix = _roulette_prefix = "pt_frame_"
 
     def _n_tri(self):
         return self._scene.counts()[0]

@@ -290,6 +290,11 @@ void bind_surface(const pt_scene &scene, pt::RenderArgs &a) {
         a.env_cells = h.envdirect->cells;
         a.env_share = h.envdirect->share;
     }
+    // (Russian roulette is no table: two numbers of the handle, for the unit that holds the kernels of both switches with the step)
+    if ((unit == pt::kDirectUnit || unit == pt::kEnvDirectUnit) && h.rr_start > 0) {
+        a.rr_start = h.rr_start;
+        a.rr_floor = h.rr_floor;
+    }
 }
 
 // The part of the kernel arguments that describes the scene (its tables for the current eps).
@@ -385,6 +390,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     fill_scene_args(scene, p->eps, a);
     // (a handle that answers 1 to get_direct_lighting never renders without its light table)
     if (scene->surface.direct && !a.lights) return fail(PT_ERR_INVALID_ARGUMENT, "direct lighting: the handle has the switch set and no light table on its device");
+    if (scene->surface.rr_start > 0 && a.rr_start <= 0) return fail(PT_ERR_INVALID_ARGUMENT, "Russian roulette: the handle has it set and neither direct lighting nor environment sampling on its device");
     if (scene->surface.envdirect && !a.env_alias) return fail(PT_ERR_INVALID_ARGUMENT, "environment sampling: the handle has the switch set and no table on its device");
     a.vec_ok = (p->width % 4 == 0) &&
                ((reinterpret_cast<uintptr_t>(planes.sum) | reinterpret_cast<uintptr_t>(planes.sum2) | reinterpret_cast<uintptr_t>(planes.count)) % 16 == 0);
@@ -445,7 +451,7 @@ int enqueue_render(pt_scene *scene, LaunchCtx &ctx, const pt_render_params *p, c
     }
     const hipError_t launched = pt::launch_integrator(a, tiles.variant, stream);
     if (const int unit = pt::surface_unit_of(a); launched == hipErrorNotSupported && unit != pt::kNoSurfaceUnit) {
-        static const char *const kWhat[][2] = {{"dielectrics", "dielectric"}, {"textures", "texture"}, {"shading normals", "smooth"}, {"roughness", "rough"}, {"direct lighting", "direct"}, {"environment sampling", "environment-sampling"}};
+        static const char *const kWhat[][2] = {{"dielectrics", "dielectric"}, {"textures", "texture"}, {"shading normals", "smooth"}, {"roughness", "rough"}, {"direct lighting", "direct"}, {"environment sampling", "environment-sampling"}, {"Russian roulette", "roulette"}};
         const char *const *w = kWhat[unit - pt::kGlassUnit];
         return fail(PT_ERR_UNSUPPORTED, std::string(w[0]) + ": this diagnostic build of the library has no " + w[1] + " kernels");
     }

@@ -28,6 +28,7 @@
 #include "pt_optics.hpp"
 #include "pt_direct.hpp"
 #include "pt_envdirect.hpp"
+#include "pt_roulette.hpp"
 #include "pt_rough.hpp"
 #include "pt_scene.hpp"
 #include "pt_sharpen.hpp"
@@ -118,6 +119,10 @@ struct SurfaceTables {
     std::shared_ptr<const pt_rough_list> rough;
     std::shared_ptr<const pt_light_table> direct;            // the light table: direct lighting is on
     std::shared_ptr<const pt_env_sampler> envdirect;         // the alias table: environment sampling is on
+    // Russian roulette (pt_hip.h: Russian roulette): rr_start > 0 = on, only while direct or envdirect is set.  No table and nothing on
+    // the device: the two numbers travel in the kernel arguments.
+    int32_t rr_start = 0;
+    float rr_floor = 0.0f;
 };
 // The same on the handle's device: one buffer per table that is set, and what stands in for the absent ones below the highest that is
 // set (bind_surface) -- the barycentrics' record of every triangle (pt_texture.hpp: TexBary), which every unit from the texture

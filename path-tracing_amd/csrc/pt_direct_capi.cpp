@@ -62,7 +62,12 @@ int set_impl(pt_scene *const *scenes, size_t n_scenes, int32_t on) {
     return ptc::set_on_copies(
         scenes, n_scenes,
         [&] {
-            if (!on) return static_cast<int>(PT_OK);
+            if (!on) {   // (roulette needs per-path accounting: the last of the two switches that give it stays while roulette is on)
+                for (size_t i = 0; i < n_scenes; ++i)
+                    if (scenes[i]->surface.rr_start > 0 && scenes[i]->surface.direct && !scenes[i]->surface.envdirect)
+                        return refuse("the scene handle has Russian roulette set and no environment sampling; clear the roulette first");
+                return static_cast<int>(PT_OK);
+            }
             const std::shared_ptr<pt_light_table> t = build_table(scenes[0]->shared->tables);
             if (t->lights.empty() || !(t->area > 0.0f) || !std::isfinite(t->area)) return refuse("the scene has no light (a triangle of non-zero area whose material is the emissive lobe alone)");
             const std::vector<pt::MatRec> &mats = scenes[0]->shared->tables.mats;

@@ -38,7 +38,12 @@ int set_impl(pt_scene *const *scenes, size_t n_scenes, const pt_env_sampling *pa
     return ptc::set_on_copies(
         scenes, n_scenes,
         [&] {
-            if (!params) return static_cast<int>(PT_OK);
+            if (!params) {   // (roulette needs per-path accounting: the last of the two switches that give it stays while roulette is on)
+                for (size_t i = 0; i < n_scenes; ++i)
+                    if (scenes[i]->surface.rr_start > 0 && scenes[i]->surface.envdirect && !scenes[i]->surface.direct)
+                        return refuse("the scene handle has Russian roulette set and no direct lighting; clear the roulette first");
+                return static_cast<int>(PT_OK);
+            }
             for (size_t i = 0; i < n_scenes; ++i)
                 if (!scenes[i]->env) return refuse("the scene handle has no environment (pt_scene_set_environment_*)");
             if (!std::isfinite(params->share)) return refuse("the share is not finite");

@@ -2,8 +2,9 @@
 // (pt_grain_quantize), the kernel (pt_display_grain.hip) and the host's finishing of deferred pixels all call these functions.  Every
 // step is one correctly rounded float operation in the order written (* / + -, comparisons, floor, int <-> float conversions) or
 // integer arithmetic, so host and device agree bit for bit; nothing is fused.  The random words are Philox4x32-10 under the
-// integrator's key with fourth counter words of their own (1 and 2; the integrator's segments use 0 and its direct-lighting words 3,
-// pt_direct.hpp: kDirectStream -- a new stream takes the next free word); the generator is spelled here once more because the host
+// integrator's key with fourth counter words of their own (1 and 2; the integrator's segments use 0, its direct-lighting words 3, pt_direct.hpp:
+// kDirectStream, environment sampling's 4, pt_envdirect.hpp: kEnvDirectStream, and the roulette's word 5, pt_roulette.hpp:
+// kRouletteStream -- a new stream takes the next free word); the generator is spelled here once more because the host
 // needs it too.
 #pragma once
 #include <cstdint>
@@ -19,7 +20,7 @@ namespace pt {
 // pt_hip.h: the largest lattice pitch
 constexpr float kGrainMaxSize = 8.0f;
 constexpr uint32_t kGrainKey1 = 0x50544831u;   // "PTH1", the integrator's second key word (pt_kernels.hpp: kPhiloxKey1)
-constexpr uint32_t kGrainDitherStream = 1u, kGrainLatticeStream = 2u;   // the counter's fourth word; the integrator's are 0 and 3 (pt_direct.hpp)
+constexpr uint32_t kGrainDitherStream = 1u, kGrainLatticeStream = 2u;   // the counter's fourth word; the integrator's are 0, 3 (pt_direct.hpp), 4 (pt_envdirect.hpp) and 5 (pt_roulette.hpp)
 
 // What the per-pixel steps need of a pt_grain_params, by value (the kernel's argument and the host's setup), and the image's width:
 // a pixel of the flat plane is (p % width, p / width).

@@ -17,16 +17,21 @@
 // ENVDIRECT (only pt::integrate_kernel_envdirect: false in every other kernel; with DIRECT and ENVMAP) = the shadow ray of a diffuse hit
 // goes, with probability RenderArgs::env_share, to a direction drawn from the environment's alias table, and counts if it misses; a
 // miss after a diffuse step adds nothing (pt_hip.h: environment sampling; pt_envdirect.hpp spells the sample and the term).
+// ROULETTE (only pt::integrate_kernel_roulette: false in every other kernel; with DIRECT) = from depth + 1 >= RenderArgs::rr_start on,
+// every scattering step ends with the roulette step on the throughput: the path ends there with a probability that follows it, and a
+// survivor is divided by that probability (pt_hip.h: Russian roulette; pt_roulette.hpp spells the step).  Lanes then die at different
+// depths, so these kernels regenerate paths in closed rooms too (REGEN below) and have no last-segment filter.
     constexpr int POOL = ADAPT & 6;
     constexpr bool CAM = (ADAPT & 1) != 0;
     // ROOM (bit 3 of ADAPT; only pt::integrate_kernel<false, false, false, false, NARROW, 8>, pt_room_kernels.hip): the search of a room-shaped scene
     // (pt_scene.hpp: CullTables::room) without its generic loops -- closest_hit<..., ROOM>.  Nothing else of the body differs.
     constexpr bool ROOM = (ADAPT & 8) != 0;
-    static_assert(!ROOM || (ADAPT == 8 && !SKY && !BIG && !STATS && !ENV && !LENS && !MOTION && !PROJ && !ENVMAP && !GLASS && !TEX && !SMOOTH && !ROUGH && !DIRECT && !ENVDIRECT),
+    static_assert(!ROOM || (ADAPT == 8 && !SKY && !BIG && !STATS && !ENV && !LENS && !MOTION && !PROJ && !ENVMAP && !GLASS && !TEX && !SMOOTH && !ROUGH && !DIRECT && !ENVDIRECT && !ROULETTE),
                   "the room instantiations are forms of the statistics-free plain small-scene kernel alone");
     static_assert(!LENS || CAM, "a lens kernel is the lens variant of a camera twin");
     static_assert(!DIRECT || (SMOOTH && ROUGH), "the direct term is written in the smooth scatter step: a direct kernel is a rough kernel with DIRECT");
     static_assert(!ENVDIRECT || (DIRECT && ENVMAP), "an environment-sampling kernel is a direct kernel with an environment");
+    static_assert(!ROULETTE || DIRECT, "roulette needs per-path accounting: a roulette kernel is a direct kernel with ROULETTE");
     static_assert(!MOTION || CAM, "a motion kernel is the motion variant of a camera twin or of its lens kernel");
     static_assert(!PROJ || (CAM && !LENS && !MOTION), "a projection kernel is the projection variant of a camera twin; the host refuses a lens or a motion with it");
     static_assert(!NARROW || (!SKY && !STATS), "only the statistics-free, skybox-free kernels have a narrow variant");
@@ -41,7 +46,10 @@
     // adaptive-sampling answer is the one main.cpp:118-125 computes before that pass), and the RNG counter is (pixel, pass,
     // segment) whatever the other lanes are doing.  The closed-room kernels keep the pass loop: there regeneration gains
     // nothing and would cost the last-segment filter, which needs the wave's rays to reach their last segment together.
-    constexpr bool REGEN = SKY;
+    // ROULETTE: the paths of a closed room end at different depths too, and a wave without regeneration would still run until its
+    // longest path is done: the roulette kernels regenerate in closed rooms as well (one trip of the pass loop runs the chunk's passes
+    // inside the segment loop).  The batch forms keep the pass loop: roulette without regeneration, which is correct and only slower.
+    constexpr bool REGEN = SKY || (ROULETTE && !POOL);
     static_assert(!REGEN || !POOL, "the compacting instantiation keeps the pass loop");
     // kDynSlots: batches of at most 64 pixels run with the second ray slots switched off (scalar branches around every per-ray piece of
     // the search and of shading).  Only the 16 x 8 kernel (POOL == 2) has them -- a third of its batches are such.  In the 32 x 8 kernel
@@ -641,7 +649,8 @@
 #pragma unroll
             for (int k = 1; k < R; ++k) all_last = all_last && last_or_dead[k];
             if constexpr (DIRECT) all_last = all_last && !shadow_phase;   // (a shadow ray is no last segment: the full search decides it)
-            constexpr bool kLastSegmentFilter = !STATS && !SKY && !BIG;   // (big scenes: the flag's scalar registers cost more than it saves)
+            // (big scenes: the flag's scalar registers cost more than it saves; ROULETTE: the wave's rays no longer reach their last segment together)
+            constexpr bool kLastSegmentFilter = !STATS && !SKY && !BIG && !ROULETTE;
             bool emis_phase = false;
             if constexpr (kLastSegmentFilter) emis_phase = a.last_segment_filter != 0u && __all(all_last);
 #ifdef PT_VERIFY_SHIPPED
@@ -1110,6 +1119,20 @@
                         }
                         q[k].dx = rx; q[k].dy = ry; q[k].dz = rz;
                         tr[k] *= fr; tg[k] *= fg; tb[k] *= fb;
+                        // ROULETTE: the step, whatever the lobe was (pt_hip.h: Russian roulette; pt_roulette.hpp spells it), under the
+                        // word of counter (pixel, pass, depth, 5), drawn only where it decides.  A path it ends has throughput zero: it is
+                        // over by path_over and hands in its L below, or with its pending shadow ray's verdict.
+                        if constexpr (ROULETTE) {
+                            const RouletteView rv = roulette_view();
+                            if (depth[k] + 1 >= rv.start()) {
+                                roulette_step(rv.floor(), [&] {
+                                    uint32_t r0, r1, r2, r3;
+                                    philox4x32_10(rng_pixel(k), static_cast<uint32_t>(pass_of(k)), static_cast<uint32_t>(depth[k]), kRouletteStream, a.seed, kPhiloxKey1,
+                                                  r0, r1, r2, r3);
+                                    return unit_float(r0);
+                                }, tr[k], tg[k], tb[k]);
+                            }
+                        }
                         }
                         ++depth[k];
                     }

@@ -42,6 +42,7 @@
 #include "pt_rough.hpp"
 #include "pt_direct.hpp"
 #include "pt_envdirect.hpp"
+#include "pt_roulette.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1241,6 +1242,19 @@ __device__ __forceinline__ EnvDirectView envdirect_view() {
     asm volatile("" : "+s"(p));
     return {p};
 }
+// The roulette parameters of a roulette launch (RenderArgs::rr_start, rr_floor), likewise: read at the end of a scattering step.
+struct RouletteView {
+    uint64_t p;
+    __device__ __forceinline__ int32_t start() const { return *reinterpret_cast<const __attribute__((address_space(4))) int32_t *>(p); }
+    __device__ __forceinline__ float floor() const {
+        return *reinterpret_cast<const __attribute__((address_space(4))) float *>(p + (offsetof(RenderArgs, rr_floor) - offsetof(RenderArgs, rr_start)));
+    }
+};
+__device__ __forceinline__ RouletteView roulette_view() {
+    uint64_t p = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(RenderArgs, rr_start);
+    asm volatile("" : "+s"(p));
+    return {p};
+}
 
 // What the launch planner (pt_launch_plan.hpp) has to know of this build.  Statistics kernels: the diagnostic builds that count
 // in every launch run them always; PT_VERIFY_SHIPPED / PT_ADAPT_COUNT never -- the kernels a caller without pt_render_stats
@@ -1278,7 +1292,7 @@ constexpr int integrator_waves() {
 // in a forceinline function that both kernels call, the compiler scheduled and spilled 30 of these 44 kernels differently.
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW = false, int ADAPT = 0>
 __global__ __launch_bounds__(kBlock, (integrator_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false, ROULETTE = false;
 #include "pt_integrator_body.inc"
 }
 // The lens kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary ray
@@ -1294,7 +1308,7 @@ constexpr int lens_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (lens_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
+    constexpr bool LENS = true, MOTION = false, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false, ROULETTE = false;
 #include "pt_integrator_body.inc"
 }
 // The motion twins (pt_hip.h: camera motion): the camera twin and its lens kernel with the camera -- and the lens axes -- interpolated
@@ -1310,12 +1324,12 @@ constexpr int motion_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, false>())) void integrate_kernel_motion(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
+    constexpr bool LENS = false, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false, ROULETTE = false;
 #include "pt_integrator_body.inc"
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (motion_waves<SKY, BIG, STATS, ENV, NARROW, true>())) void integrate_kernel_motion_lens(const RenderArgs a) {
-    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
+    constexpr bool LENS = true, MOTION = true, PROJ = false, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false, ROULETTE = false;
 #include "pt_integrator_body.inc"
 }
 // The projection kernel of camera twin integrate_kernel<SKY, BIG, STATS, ENV, NARROW, ADAPT> (ADAPT odd): the same, with each primary
@@ -1330,15 +1344,15 @@ constexpr int projection_waves() {
 }
 template <bool SKY, bool BIG, bool STATS, bool ENV, bool NARROW, int ADAPT>
 __global__ __launch_bounds__(kBlock, (projection_waves<SKY, BIG, STATS, ENV, NARROW>())) void integrate_kernel_projection(const RenderArgs a) {
-    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
+    constexpr bool LENS = false, MOTION = false, PROJ = true, ENVMAP = false, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false, ROULETTE = false;
 #include "pt_integrator_body.inc"
 }
 
-// launch_surface_integrator's six halves: each surface unit's translation unit defines its own
+// launch_surface_integrator's seven halves: each surface unit's translation unit defines its own
 template <int UNIT>
 hipError_t launch_surface_unit(const RenderArgs &args, const plan::Variant &v, hipStream_t stream);
 #define PT_UNIT_HALF(U) template <> hipError_t launch_surface_unit<U>(const RenderArgs &, const plan::Variant &, hipStream_t);
-PT_UNIT_HALF(kGlassUnit) PT_UNIT_HALF(kTextureUnit) PT_UNIT_HALF(kSmoothUnit) PT_UNIT_HALF(kRoughUnit) PT_UNIT_HALF(kDirectUnit) PT_UNIT_HALF(kEnvDirectUnit)
+PT_UNIT_HALF(kGlassUnit) PT_UNIT_HALF(kTextureUnit) PT_UNIT_HALF(kSmoothUnit) PT_UNIT_HALF(kRoughUnit) PT_UNIT_HALF(kDirectUnit) PT_UNIT_HALF(kEnvDirectUnit) PT_UNIT_HALF(kRouletteUnit)
 #undef PT_UNIT_HALF
 
 #ifdef PT_ENVIRONMENT_UNIT
@@ -1362,7 +1376,7 @@ template <bool BIG, bool STATS, bool ENV, int VIEW>
 __global__ __launch_bounds__(kBlock, (environment_waves<BIG, STATS, ENV, VIEW>())) void integrate_kernel_environment(const RenderArgs a) {
     constexpr bool SKY = true, NARROW = false;
     constexpr int ADAPT = VIEW != 0 ? 1 : 0;
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = true, GLASS = false, TEX = false, SMOOTH = false, ROUGH = false, DIRECT = false, ENVDIRECT = false, ROULETTE = false;
 #include "pt_integrator_body.inc"
 }
 namespace {
@@ -1398,7 +1412,7 @@ void (*room_kernel(bool narrow))(const RenderArgs) {
     else return nullptr;
 }
 #elif defined(PT_SURFACE_UNIT)
-// A surface unit (pt_kernels.hpp: SurfaceUnit; pt_glass_kernels.hip ... pt_direct_kernels.hip each compile this file with its number as
+// A surface unit (pt_kernels.hpp: SurfaceUnit; pt_glass_kernels.hip ... pt_roulette_kernels.hip each compile this file with its number as
 // PT_SURFACE_UNIT): this one section, as integrate_kernel_<name>, with the flag of every unit up to this one on.
 #define PT_UNIT_NAME_1 glass
 #define PT_UNIT_NAME_2 texture
@@ -1406,12 +1420,22 @@ void (*room_kernel(bool narrow))(const RenderArgs) {
 #define PT_UNIT_NAME_4 rough
 #define PT_UNIT_NAME_5 direct
 #define PT_UNIT_NAME_6 envdirect
+#define PT_UNIT_NAME_7 roulette
 #define PT_PASTE_(a, b) a##b
 #define PT_PASTE(a, b) PT_PASTE_(a, b)
 #define PT_UNIT_KERNEL PT_PASTE(integrate_kernel_, PT_PASTE(PT_UNIT_NAME_, PT_SURFACE_UNIT))
-static_assert(PT_SURFACE_UNIT >= kGlassUnit && PT_SURFACE_UNIT <= kEnvDirectUnit, "PT_SURFACE_UNIT: a SurfaceUnit");
+static_assert(PT_SURFACE_UNIT >= kGlassUnit && PT_SURFACE_UNIT <= kRouletteUnit, "PT_SURFACE_UNIT: a SurfaceUnit");
+// (the roulette unit holds the direct unit's kernels AND the environment-sampling unit's: there ENVDIRECT is a parameter of the kernel,
+// PT_UNIT_ENVD below, and not a function of the unit's number)
 constexpr bool kUnitTex = PT_SURFACE_UNIT >= kTextureUnit, kUnitSmooth = PT_SURFACE_UNIT >= kSmoothUnit, kUnitRough = PT_SURFACE_UNIT >= kRoughUnit,
-               kUnitDirect = PT_SURFACE_UNIT >= kDirectUnit, kUnitEnvDirect = PT_SURFACE_UNIT >= kEnvDirectUnit;
+               kUnitDirect = PT_SURFACE_UNIT >= kDirectUnit, kUnitEnvDirect = PT_SURFACE_UNIT == kEnvDirectUnit, kUnitRoulette = PT_SURFACE_UNIT == kRouletteUnit;
+#if PT_SURFACE_UNIT == 7
+#define PT_UNIT_TEMPLATE template <int MISS, bool BIG, bool STATS, int FORM, int VIEW, bool ENVD>
+#define PT_UNIT_ENVD ENVD
+#else
+#define PT_UNIT_TEMPLATE template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+#define PT_UNIT_ENVD kUnitEnvDirect
+#endif
 // ---------------------------------------------------------------------------------------------------------------
 // The dielectric kernels (pt_glass_kernels.hip: this file compiled with PT_SURFACE_UNIT 1, a translation unit of its own).  The body
 // with GLASS = true: a hit on a material the handle's table marks (RenderArgs::glass, pt_hip.h: pt_dielectric) reflects or refracts.
@@ -1500,47 +1524,69 @@ template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
 constexpr int envdirect_fewer_waves() {
     return 0;
 }
-template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
+// The roulette kernels (pt_hip.h: Russian roulette): the direct kernels and the environment-sampling kernels
+// (ENVD) with ROULETTE = true too -- from RenderArgs::rr_start on every scattering step ends with the roulette step (pt_roulette.hpp),
+// and the closed-room wide and 8 x 8 forms regenerate paths as the skybox kernels do.  The twin of such a kernel is the direct or the
+// environment-sampling kernel of the same arguments; waves per SIMD: that twin's minus roulette_fewer_waves
+// (tests/test_roulette_resources.py pins every kernel).
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW, bool ENVD>
+constexpr int roulette_fewer_waves() {
+    // At the direct twin's 4 waves and 128 VGPRs these spilled one vector register to scratch (the regeneration state, cur_pass and
+    // next_pass of two ray slots, on top of the twin's 123 to 128): the two-pixel small-scene kernel without a miss shader under the
+    // lens, the moving camera and the moving lens.  They are compiled for a wave fewer.
+    return (MISS == 0 && !BIG && !STATS && FORM == 0 && !ENVD && (VIEW == 2 || VIEW == 3 || VIEW == 4)) ? 1 : 0;
+}
+template <int MISS, bool BIG, bool STATS, int FORM, int VIEW, bool ENVD>
 constexpr int unit_waves() {
     return view_waves<MISS != 0, BIG, STATS, FORM < 2, FORM == 1, VIEW>() - glass_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() -
            (kUnitTex ? texture_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) - (kUnitSmooth ? smooth_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) -
            (kUnitRough ? rough_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) - (kUnitDirect ? direct_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) -
-           (kUnitEnvDirect ? envdirect_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0);
+           (ENVD ? envdirect_fewer_waves<MISS, BIG, STATS, FORM, VIEW>() : 0) - (kUnitRoulette ? roulette_fewer_waves<MISS, BIG, STATS, FORM, VIEW, ENVD>() : 0);
 }
-template <int MISS, bool BIG, bool STATS, int FORM, int VIEW>
-__global__ __launch_bounds__(kBlock, (unit_waves<MISS, BIG, STATS, FORM, VIEW>()))
+PT_UNIT_TEMPLATE
+__global__ __launch_bounds__(kBlock, (unit_waves<MISS, BIG, STATS, FORM, VIEW, PT_UNIT_ENVD>()))
 void PT_UNIT_KERNEL(const RenderArgs a) {
     constexpr bool SKY = MISS != 0, ENV = FORM < 2, NARROW = FORM == 1;
     constexpr int ADAPT = (FORM == 2 ? 2 : FORM == 3 ? 4 : 0) | (VIEW != 0 ? 1 : 0);
-    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true, TEX = kUnitTex, SMOOTH = kUnitSmooth, ROUGH = kUnitRough, DIRECT = kUnitDirect, ENVDIRECT = kUnitEnvDirect;
+    constexpr bool LENS = VIEW == 2 || VIEW == 4, MOTION = VIEW == 3 || VIEW == 4, PROJ = VIEW == 5, ENVMAP = MISS == 2, GLASS = true, TEX = kUnitTex, SMOOTH = kUnitSmooth, ROUGH = kUnitRough, DIRECT = kUnitDirect, ENVDIRECT = PT_UNIT_ENVD, ROULETTE = kUnitRoulette;
 #include "pt_integrator_body.inc"
 }
 namespace {
 using Kernel = void (*)(const RenderArgs);
 constexpr int kGlassViews = plan::kViews + 1, kGlassPerView = 3 * 2 * 2 * 4;
 // does the build have the twin of that kernel?  (the 8 x 8 form and the batch kernels: plan::variant_exists)
-template <int MISS, bool BIG, bool STATS, int FORM>
+template <int MISS, bool BIG, bool STATS, int FORM, bool ENVD>
 constexpr bool glass_kernel_exists() {
-    if constexpr (kUnitEnvDirect) return MISS == 2 && FORM == 0;   // (the unit needs an environment)
+    if constexpr (ENVD) return MISS == 2 && FORM == 0;   // (environment sampling needs an environment)
     else if constexpr (FORM == 0) return true;
     else if constexpr (MISS != 0 || STATS) return false;
     else return plan::variant_exists({false, BIG, false, FORM == 1, FORM == 1, FORM == 2 ? 2 : FORM == 3 ? 4 : 0, 1}, kBuild);
 }
-template <int I>
-Kernel glass_kernel_of() {   // I = (VIEW * 3 + MISS) * 16 + (big, stats) as bits 3..2 + FORM
+constexpr int kGlassTable = kGlassPerView * kGlassViews;
+template <int J>
+Kernel glass_kernel_of() {   // I = (VIEW * 3 + MISS) * 16 + (big, stats) as bits 3..2 + FORM; the roulette unit: J = I, and kGlassTable + I with ENVD
+    constexpr int I = J % kGlassTable;
     constexpr int kMiss = (I / 16) % 3, kForm = I & 3;
     constexpr bool kBig = (I & 8) != 0, kStats = (I & 4) != 0;
-    if constexpr (!glass_kernel_exists<kMiss, kBig, kStats, kForm>()) return nullptr;
+    [[maybe_unused]] constexpr bool kEnvd = kUnitRoulette ? J >= kGlassTable : kUnitEnvDirect;
+    if constexpr (!glass_kernel_exists<kMiss, kBig, kStats, kForm, kEnvd>()) return nullptr;
+#if PT_SURFACE_UNIT == 7
+    else return &PT_UNIT_KERNEL<kMiss, kBig, kStats, kForm, I / 48, kEnvd>;
+#else
     else return &PT_UNIT_KERNEL<kMiss, kBig, kStats, kForm, I / 48>;
+#endif
 }
 template <int... I>
 std::array<Kernel, sizeof...(I)> glass_kernel_table(std::integer_sequence<int, I...>) { return {glass_kernel_of<I>()...}; }
-const auto kGlassKernels = glass_kernel_table(std::make_integer_sequence<int, kGlassPerView * kGlassViews>());
+const auto kGlassKernels = glass_kernel_table(std::make_integer_sequence<int, kGlassTable * (kUnitRoulette ? 2 : 1)>());
 }  // namespace
 template <>
 hipError_t launch_surface_unit<PT_SURFACE_UNIT>(const RenderArgs &args, const plan::Variant &v, hipStream_t stream) {
-    if (surface_unit_of(args) != PT_SURFACE_UNIT || (kUnitDirect && (kUnitEnvDirect ? args.n_lights < 0 : args.n_lights <= 0))) return hipErrorInvalidValue;
-    if (kUnitEnvDirect && (args.env_map == nullptr || args.env_cells < 1 || args.env_cells > kEnvSampleMaxCells || args.env_cells > args.env_n ||
+    // (the roulette unit: env_alias picks the environment-sampling kernels, and the launch is then checked as that unit's)
+    const bool envd = kUnitRoulette ? args.env_alias != nullptr : kUnitEnvDirect;
+    if (surface_unit_of(args) != PT_SURFACE_UNIT || (kUnitDirect && (envd ? args.n_lights < 0 : args.n_lights <= 0))) return hipErrorInvalidValue;
+    if (kUnitRoulette && (args.rr_start < 1 || !roulette_params_ok(args.rr_start, args.rr_floor) || args.lights == nullptr)) return hipErrorInvalidValue;
+    if (envd && (args.env_map == nullptr || args.env_cells < 1 || args.env_cells > kEnvSampleMaxCells || args.env_cells > args.env_n ||
                            !(args.env_share > 0.0f && args.env_share <= 1.0f) || (args.n_lights == 0 && args.env_share != 1.0f) || args.lights == nullptr))
         return hipErrorInvalidValue;
     if ((kUnitRough && args.rough_alpha == nullptr) || (kUnitSmooth && args.smooth_normals == nullptr)) return hipErrorInvalidValue;
@@ -1549,12 +1595,14 @@ hipError_t launch_surface_unit<PT_SURFACE_UNIT>(const RenderArgs &args, const pl
     if (args.projection != 0 && v.view != 1) return hipErrorInvalidDeviceFunction;
     const int view = args.projection != 0 ? 5 : v.view;
     const int miss = args.env_map != nullptr ? 2 : v.sky ? 1 : 0, form = v.narrow ? 1 : v.pool == 2 ? 2 : v.pool == 4 ? 3 : 0;
-    const Kernel kernel = kGlassKernels[(view * 3 + miss) * 16 + (v.big ? 8 : 0) + (v.stats ? 4 : 0) + form];
+    const Kernel kernel = kGlassKernels[(kUnitRoulette && envd ? kGlassTable : 0) + (view * 3 + miss) * 16 + (v.big ? 8 : 0) + (v.stats ? 4 : 0) + form];
     if (!kernel) return hipErrorInvalidDeviceFunction;
     hipLaunchKernelGGL(kernel, dim3(args.n_tiles * args.n_chunks), dim3(kBlock), 0, stream, args);
     return hipGetLastError();
 }
 #undef PT_UNIT_KERNEL
+#undef PT_UNIT_TEMPLATE
+#undef PT_UNIT_ENVD
 #else
 // First-hit feature pass under a projection (pt_hip.h: pt_render_features_host): the ray pt_projection states for pixel (x, y) with
 // jitter 0, for launch_trace_rays.  (Here and not beside the pinhole's feature_rays_kernel in pt_denoise.hip: the ray needs this
@@ -1800,8 +1848,9 @@ hipError_t launch_surface_integrator(int unit, const RenderArgs &args, const pla
     return hipErrorNotSupported;   // the diagnostic builds are linked without the surface units: a handle with one of their tables is refused (PT_ERR_UNSUPPORTED)
 #else
     constexpr decltype(&launch_surface_unit<kGlassUnit>) kLaunch[] = {&launch_surface_unit<kGlassUnit>, &launch_surface_unit<kTextureUnit>, &launch_surface_unit<kSmoothUnit>,
-                                                                      &launch_surface_unit<kRoughUnit>, &launch_surface_unit<kDirectUnit>, &launch_surface_unit<kEnvDirectUnit>};
-    return unit >= kGlassUnit && unit <= kEnvDirectUnit ? kLaunch[unit - kGlassUnit](args, v, stream) : hipErrorInvalidValue;
+                                                                      &launch_surface_unit<kRoughUnit>, &launch_surface_unit<kDirectUnit>, &launch_surface_unit<kEnvDirectUnit>,
+                                                                      &launch_surface_unit<kRouletteUnit>};
+    return unit >= kGlassUnit && unit <= kRouletteUnit ? kLaunch[unit - kGlassUnit](args, v, stream) : hipErrorInvalidValue;
 #endif
 }
 

@@ -133,6 +133,12 @@ struct RenderArgs {
     const void *env_alias;
     int32_t env_cells;
     float env_share;
+    // The handle's Russian roulette (pt_hip.h: Russian roulette), appended likewise.  rr_start > 0 (only with lights; env_alias may be
+    // set too): the launch runs the roulette kernels (integrate_kernel_roulette, pt_roulette_kernels.hip: the direct kernels, or with
+    // env_alias the environment-sampling kernels, whose scattering steps end with the roulette step from depth + 1 >= rr_start on
+    // under the floor rr_floor in [2^-10, 1]; pt_roulette.hpp).
+    int32_t rr_start;
+    float rr_floor;
 #ifdef PT_BLOCK_PROFILE
     uint32_t *blockprof;                // diagnostic build only (tools/asm_profile.py): execution counters of the instrumented code object
 #endif
@@ -140,12 +146,12 @@ struct RenderArgs {
 
 // The constants the kernels of this library were compiled with: what plan::plan_tiles needs to know of the build.
 const plan::Build &integrator_build();
-// The surface units: translation units of their own (pt_glass_kernels.hip ... pt_envdirect_kernels.hip), each the unit below it with
-// one more table read where a ray has hit a surface.  A launch needs the unit of the highest table its arguments hold, and every
+// The surface units: translation units of their own (pt_glass_kernels.hip ... pt_roulette_kernels.hip), each the unit below it with
+// one more table read where a ray has hit a surface (the roulette unit: the direct and the environment-sampling unit with the step).  A launch needs the unit of the highest table its arguments hold, and every
 // table below that one is then never null (a handle without it passes an all-zero table).
-enum SurfaceUnit : int { kNoSurfaceUnit = 0, kGlassUnit, kTextureUnit, kSmoothUnit, kRoughUnit, kDirectUnit, kEnvDirectUnit };
+enum SurfaceUnit : int { kNoSurfaceUnit = 0, kGlassUnit, kTextureUnit, kSmoothUnit, kRoughUnit, kDirectUnit, kEnvDirectUnit, kRouletteUnit };
 inline int surface_unit_of(const RenderArgs &a) {
-    return a.env_alias ? kEnvDirectUnit : a.lights ? kDirectUnit : a.rough_alpha ? kRoughUnit : a.smooth_normals ? kSmoothUnit : a.tex_recs ? kTextureUnit : a.glass ? kGlassUnit : kNoSurfaceUnit;
+    return a.rr_start > 0 ? kRouletteUnit : a.env_alias ? kEnvDirectUnit : a.lights ? kDirectUnit : a.rough_alpha ? kRoughUnit : a.smooth_normals ? kSmoothUnit : a.tex_recs ? kTextureUnit : a.glass ? kGlassUnit : kNoSurfaceUnit;
 }
 // launches kernel `v` (plan::plan_tiles: Tiles::variant, whose tile geometry and chunks args holds) -- with args.projection != 0
 // the projection kernel of camera twin `v` (v.view == 1), which has the twin's tiles and chunks and no id of its own in the plan;

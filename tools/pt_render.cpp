@@ -65,14 +65,18 @@
 // Direct lighting (pt_scene_set_direct_lighting, not in the reference): -DIRECT 1 sends a shadow ray to a sampled point of a light at
 // every scattering diffuse hit and counts every path once (pt_hip.h: direct lighting); -DIRECT 0 is a run without the flag.  Any
 // other value, a model without a light and an emissive material that -TEXTURE lists end the program with status 2.  Every other flag
-// combines.  Not built: multiple importance sampling, sampling by power, direct terms for the GGX lobe, textured emitters, Russian
-// roulette.
+// combines.  Not built: multiple importance sampling, sampling by power, direct terms for the GGX lobe, textured emitters.
 // Environment sampling (pt_scene_set_environment_sampling, not in the reference): -DIRECT_ENV 1, with -ENV, sends the shadow ray of every
 // scattering diffuse hit to a direction drawn from the environment in proportion to its radiance or -- where the model has emitters --
 // to a point of a light, the environment with probability -DIRECT_ENV_SHARE p (0 < p < 1; default: by the two sources' power, within
 // 1/8 .. 7/8), and counts every path once (pt_hip.h: environment sampling); -DIRECT_ENV 0 is a run without the flag.  A missing -ENV, a
 // -SKYBOX, a share outside the range, a black environment and an emissive material that -TEXTURE lists end the program with status 2.
 // Every other flag combines, -DIRECT too.  Not built: multiple importance sampling with the diffuse lobe, a term for the GGX lobe.
+// Russian roulette (pt_scene_set_roulette, not in the reference): -RR start[:floor], with -DIRECT 1 or -DIRECT_ENV 1, ends a path from
+// scattering step `start` (a whole number >= 1) on with a probability that follows its throughput and divides the survivors by it, the
+// probability of surviving never below `floor` (2^-10 .. 1; default 1/16), so the estimate stays unbiased and -MRR can be raised until
+// the cap no longer matters (pt_hip.h: Russian roulette); -RR 0 is a run without the flag.  A malformed value, one out of range and
+// -RR without either of the two flags end the program with status 2.  Every other flag combines.
 // The denoiser (pt_denoise_host, not in the reference): -DENOISE <levels> (default 0: off; 5 is the usual choice) filters the final
 // image's linear mean with the feature-guided a-trous filter before the tone map, -DN_SIGMA_L / -DN_SIGMA_P set its luminance and
 // plane-distance widths (default 0: the library's).  The dispersion numbers and the file name are those of the undenoised frame; the
@@ -207,6 +211,9 @@ struct Options {
     std::string direct_env_text, direct_env_share_text;   // -DIRECT_ENV, -DIRECT_ENV_SHARE as given
     bool direct_env = false;
     float direct_env_share = 0.0f;         // 0 = the library's default
+    std::string rr_text;                   // -RR as given
+    int32_t rr_start = 0;                  // 0 = no roulette
+    float rr_floor = PT_ROULETTE_DEFAULT_FLOOR;
     std::vector<pt_rough> rough;           // what it makes (empty with -ROUGH mtl: the model's MTL decides)
     bool rough_mtl = false;
     std::string smooth_text, crease_text;  // -SMOOTH / -CREASE as given
@@ -326,6 +333,7 @@ void parse(int argc, char **argv, Options &o) {   // pairs `flag value` from arg
         if (f == "-DIRECT") o.direct_text = v;
         if (f == "-DIRECT_ENV") o.direct_env_text = v;
         if (f == "-DIRECT_ENV_SHARE") o.direct_env_share_text = v;
+        if (f == "-RR") o.rr_text = v;
         if (f == "-SMOOTH") o.smooth_text = v;
         if (f == "-CREASE") o.crease_text = v;
         if (f == "-TEXTURE") o.texture_text = v;
@@ -547,6 +555,18 @@ int configure(int argc, char **argv, Options &o) {
     }
     if (o.direct_env && !o.skybox.empty()) return refuse(2, "-DIRECT_ENV samples an environment (-ENV), not a -SKYBOX");
     if (o.direct_env && o.env.empty()) return refuse(2, "-DIRECT_ENV needs -ENV");
+    // -RR start[:floor]: start a whole number (0 = a run without the flag), floor in 2^-10 .. 1
+    if (!o.rr_text.empty()) {
+        const size_t colon = o.rr_text.find(':');
+        const std::string start = o.rr_text.substr(0, colon);
+        float sv = 0.0f;
+        const bool ok = !start.empty() && start.size() <= 7 && start.find_first_not_of("0123456789") == std::string::npos && parse_float(start, sv) &&
+                        (colon == std::string::npos || parse_float(o.rr_text.substr(colon + 1), o.rr_floor));
+        if (!ok) return refuse(2, "-RR takes start or start:floor (a whole number >= 0 and a number), not \"" + o.rr_text + "\"");
+        if (!(o.rr_floor >= 0.0009765625f && o.rr_floor <= 1.0f)) return refuse(2, "-RR: the floor must lie in 2^-10 .. 1, not " + o.rr_text.substr(colon + 1));
+        o.rr_start = static_cast<int32_t>(sv);
+        if (o.rr_start > 0 && !o.direct && !o.direct_env) return refuse(2, "-RR needs -DIRECT 1 or -DIRECT_ENV 1 (roulette needs their per-path accounting)");
+    }
     // -ROUGH: "mtl", or entries m:alpha separated by commas; alpha's range is the library's (pt_hip.h: rough specular)
     if (o.rough_text == "mtl") o.rough_mtl = true;
     for (size_t at = 0; !o.rough_text.empty() && !o.rough_mtl && at <= o.rough_text.size();) {
@@ -1365,6 +1385,8 @@ int main(int argc, char **argv) {
         const pt_env_sampling sampling = {o.direct_env_share};
         if (pt_scene_set_environment_sampling(r.scene, &sampling) != PT_OK) return refuse(2, std::string("-DIRECT_ENV: ") + pt_last_error());
     }
+    // -RR: after the two switches it needs
+    if (o.rr_start > 0 && pt_scene_set_roulette(r.scene, o.rr_start, o.rr_floor) != PT_OK) return refuse(2, std::string("-RR: ") + pt_last_error());
     if (o.camera && pt_scene_set_camera(r.scene, &o.view) != PT_OK) return die("pt_render");   // the frame's device copies inherit it
     // and its projection -- set before the lens and the motion, which the library refuses on a handle with one, as it refuses the
     // temporal stage when the first frame reaches it: asked here, before any device is looked at, with the library's own words
